@@ -8,6 +8,13 @@ exponential standard Hawkes, N=1024, M=1e6, Δtmax=1, mean look-back window K̄ 
 
     python bench.py --gpus N --steps K --warmup W [--workload windowed_k8|windowed_k64|
                                                    windowed_k512|recursive|logitnormal_k8]
+                                                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds every
+secondary leg after the headline (CPU baselines, default-dispatch / batch / changing-parameter /
+mle! / two-stream legs, the other workloads and configs; at N>1 the chains and sharded legs).
+--dump-outputs DIR writes the log-likelihood of the last timed step (one per rank) to
+DIR/loglik.npy (float64); the inputs are seeded, so two builds can be compared output for output.
 
 N>1: launched by torch.distributed.run, one rank per GPU; every rank evaluates its own
 independent stream (chains / restarts shard embarrassingly), weak scaling, and the
@@ -100,7 +107,7 @@ def run_workload(nhp, ctx, name, N, M, steps, warmup, sync):
     dev_ms = ctx.timer_stop()           # hipEvents on the stream the kernels run on; also drains it
     sync()
     wall = time.perf_counter() - t0
-    ll = ctx.fetch(0, 1)[0]
+    ll = ctx.fetch((steps - 1) % _lib.MAX_SLOTS, 1)[0]     # the last timed step's result
     return dict(name=name, wall=wall, dev_ms=dev_ms, ll=float(ll), pairs=int(ds.pairs), M=M, N=N, dataset_ms=1e3 * t_ds, first_ms=1e3 * t_first,
                 kind=w["kind"], data=(times, nodes, T), proc=proc, recursive=w["recursive"])
 
@@ -659,7 +666,14 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-default-dispatch", action="store_true", help="skip the recursive=true legs (the reference's default call)")
     ap.add_argument("--no-batch", action="store_true", help="skip the batch / changing-parameter legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every secondary leg (the options above select among them); "
+                         "without it a run measures the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's log-likelihood (one per rank) to DIR/loglik.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch                       # first: libnhp.so must bind to torch's HIP runtime copy
     import torch.distributed as dist
@@ -701,6 +715,18 @@ def main():
             lls = torch.cat(gathered)
     wall_s = float(wall.item())
     out = headline(args, r, world, wall_s, lls) if rank == 0 else None
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "loglik.npy"), lls.cpu().numpy().astype(np.float64))
+
+    if not args.full:                  # a plain run: the headline alone
+        if rank == 0:
+            print(finish_line(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # N > 1: the legs after the timed region (config 5's chains, one evaluation / one chain over all ranks) exchange through
     # RCCL communicators of the library's own.  They are secondary numbers and must never cost the headline line: an

@@ -16,10 +16,14 @@ PKG = os.path.join(ROOT, "networkhawkesprocesses.jl_amd")
 
 
 @pytest.fixture(scope="module")
-def lib():
+def lib(nhp):
     path = os.path.join(PKG, "libnhp.so")
     if not os.path.exists(path):
         subprocess.check_call(["bash", os.path.join(PKG, "csrc", "build.sh")])
+    # the package's loader maps torch's HIP runtime before libnhp.so; a bare dlopen first would map the system copy too, and
+    # in a suite run as one process the GPU tests after these would find no device through it
+    from nhp_amd import _lib
+    _lib.lib()
     return C.CDLL(path)
 
 

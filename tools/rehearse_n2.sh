@@ -8,7 +8,7 @@ mkdir -p $O
 cd $R
 run() {  # run <name> <deadline> <chain steps>
   NHP_BENCH_BACKEND=gloo NHP_BENCH_EXTRAS_DEADLINE_S=$2 timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-      --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 20 --warmup 3 --chain-steps $3 > $O/$1.out 2> $O/$1.err
+      --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 20 --warmup 3 --full --chain-steps $3 > $O/$1.out 2> $O/$1.err
   echo "exit status $?" >> $O/$1.out
   tail -c 1500 $O/$1.out
 }

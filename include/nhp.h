@@ -141,9 +141,33 @@ nhp_status nhp_cont_dataset_create(nhp_ctx *ctx, const double *events, const int
 nhp_status nhp_cont_dataset_create_columns(nhp_ctx *ctx, const double *events, const int64_t *nodes,
                                            int64_t n_events, int32_t n_nodes, double duration, double dt_max,
                                            int32_t col_begin, int32_t col_end, nhp_cont_dataset **out);
+/* The same dataset nhp_cont_dataset_create_columns makes -- every device array byte for byte, every scalar equal --
+ * with its pre-pass run on the device (window starts, node bucketing and window sort by a stable radix sort, pair
+ * offsets, child-slice rows, event records); only the work partition is decided on the host, by the same code.
+ * input_on_device = 0: events / nodes are host pointers (one raw upload, then the device build);
+ * input_on_device = 1: they are device pointers on ctx's device, read on ctx's stream (the caller orders its own producer
+ * before the call); they are not read after the call returns: the dataset owns copies.  Errors (status and message)
+ * are those of nhp_cont_dataset_create_columns. */
+nhp_status nhp_cont_dataset_create_device(nhp_ctx *ctx, const double *events, const int64_t *nodes, int64_t n_events,
+                                          int32_t n_nodes, double duration, double dt_max, int32_t col_begin,
+                                          int32_t col_end, int32_t input_on_device, nhp_cont_dataset **out);
 void nhp_cont_dataset_destroy(nhp_cont_dataset *ds);
 /* Σ_i K_i: parent-child pairs inside the look-back window (SURVEY 8d F_alg) */
 int64_t nhp_cont_dataset_pairs(const nhp_cont_dataset *ds);
+/* Introspection (tests, tools): copy one of the dataset's arrays to host memory.  *bytes = its size (0: the dataset has no
+ * such array); out = NULL asks for the size only; NHP_ESHAPE if cap_bytes is smaller. */
+enum {
+    NHP_DS_TIMES = 0, NHP_DS_NODES = 1, NHP_DS_EV = 2, NHP_DS_EV8 = 3, NHP_DS_POFF = 4, NHP_DS_SL_ROW = 5,
+    NHP_DS_SL_ITEM0 = 6, NHP_DS_CHILD = 7, NHP_DS_CHILD_W = 8, NHP_DS_WPOS = 9, NHP_DS_BOFF = 10, NHP_DS_ITEMS = 11,
+    NHP_DS_CNT = 12, NHP_DS_PAIR_OFF = 13, NHP_DS_N_ARRAYS = 14
+};
+nhp_status nhp_cont_dataset_export(nhp_ctx *ctx, const nhp_cont_dataset *ds, int32_t which, void *out, int64_t cap_bytes,
+                                   int64_t *bytes);
+/* the dataset's scalars as int64, in this order: M, N, pairs, group, n_items, max_item, max_window, n_zero_time,
+ * all_sole, sl_rows, n_slices, sl_nb, sl_max_rows and the bit patterns of t_last, ev8_t0, ev8_scale; writes
+ * min(cap, NHP_DS_N_SCALARS) values */
+#define NHP_DS_N_SCALARS 16
+nhp_status nhp_cont_dataset_scalars(const nhp_cont_dataset *ds, int64_t *out, int32_t cap);
 
 /* ---- continuous model: device-resident parameter blob --------------------------------- */
 nhp_status nhp_cont_model_create(nhp_ctx *ctx, const nhp_cont_model_desc *desc, nhp_cont_model **out);

@@ -138,10 +138,18 @@ class GaussianProcess:
         return np.asarray(self.mu(x), dtype=np.float64) + np.linalg.cholesky(sigma) @ rng.standard_normal(len(x))
 
 
+def host_array(x, dtype):
+    """A host numpy array of `x`: an array, a list or a torch tensor on any device (copied to the host)."""
+    if type(x).__module__.startswith("torch") and hasattr(x, "detach"):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x, dtype=dtype)
+
+
 def split_extract(data, parents, nnodes):
-    """Events attributed to the baseline (parent node 0), split by node -- src/baselines.jl:227-238."""
+    """Events attributed to the baseline (parent node 0), split by node -- src/baselines.jl:227-238.  events / nodes may
+    be torch tensors (copied to the host)."""
     events, nodes, duration = data
-    events, nodes = np.asarray(events, dtype=np.float64), np.asarray(nodes, dtype=np.int64)
+    events, nodes = host_array(events, np.float64), host_array(nodes, np.int64)
     parentnodes = np.asarray(parents[1], dtype=np.int64)
     out = []
     for node in range(1, nnodes + 1):

@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib
 from ._lib import DomainError
 from .components import (BernoulliNetworkModel, DenseNetworkModel, ExponentialImpulseResponse,
-                         HomogeneousProcess, LogGaussianCoxProcess, LogitNormalImpulseResponse)
+                         HomogeneousProcess, LogGaussianCoxProcess, LogitNormalImpulseResponse, host_array)
 
 
 class HawkesProcess:
@@ -105,50 +105,147 @@ class DeviceModel:
         _lib.check(_lib.lib().nhp_cont_model_set_params(self.ctx.h, self.h, _lib.dptr(x), len(x)), self.ctx.h)
 
 
+_CHILD = np.dtype([("t", np.float64), ("first", np.int32), ("idx", np.int32)])
+# nhp_cont_dataset_export: name -> (NHP_DS_* id, element type)
+DATASET_ARRAYS = {
+    "times": (0, np.dtype(np.float64)), "nodes": (1, np.dtype(np.int32)),
+    "ev": (2, np.dtype([("t", np.float64), ("node", np.int32), ("pad", np.int32)])), "ev8": (3, np.dtype(np.uint64)),
+    "poff": (4, np.dtype(np.uint32)), "sl_row": (5, np.dtype(np.uint32)), "sl_item0": (6, np.dtype(np.int32)),
+    "child": (7, _CHILD), "child_w": (8, _CHILD), "wpos": (9, np.dtype(np.int32)), "boff": (10, np.dtype(np.int32)),
+    "items": (11, np.dtype([("node", np.int32), ("kbeg", np.int32), ("kend", np.int32), ("first", np.int32)])),
+    "cnt": (12, np.dtype(np.float64)), "pair_off": (13, np.dtype(np.int64)),
+}
+# nhp_cont_dataset_scalars, in order (the last three are the bit patterns of doubles)
+DATASET_SCALARS = ("M", "N", "pairs", "group", "n_items", "max_item", "max_window", "n_zero_time", "all_sole", "sl_rows",
+                   "n_slices", "sl_nb", "sl_max_rows", "t_last", "ev8_t0", "ev8_scale")
+
+
+def _is_tensor(x):
+    return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
+
+
+def _on_device(x):
+    return _is_tensor(x) and x.device.type != "cpu"
+
+
+def _device_tensors(events, nodes, ctx):
+    """The (events, nodes) of a torch data triple, checked for the device route: float64 / int64, 1-D, contiguous, both on
+    ctx's device."""
+    if not (_is_tensor(events) and _is_tensor(nodes)):
+        raise ValueError("events and nodes must both be torch tensors on the context's device, or both host arrays")
+    for name, t, dt in (("events", events, "float64"), ("nodes", nodes, "int64")):
+        if str(t.dtype) != "torch." + dt:
+            raise TypeError(f"{name} must be a {dt} tensor, got {t.dtype}")
+        if t.device.type != "cuda" or t.device.index != ctx.device:
+            raise ValueError(f"{name} is on {t.device}, the context on cuda:{ctx.device}")
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a 1-D contiguous tensor")
+    if events.numel() != nodes.numel():
+        raise ValueError("events and nodes must have the same length")
+    return events, nodes
+
+
 class DeviceDataset:
     """nhp_cont_dataset handle: (events, nodes, duration) uploaded once, pre-pass done for Δtmax."""
 
-    def __init__(self, ctx, data, nnodes, Δtmax, columns=None):
+    def __init__(self, ctx, data, nnodes, Δtmax, columns=None, build="host"):
         """columns = (begin, end), 0-based half-open: a column shard (sharded.py) that evaluates only the children on
-        those nodes; None = the whole dataset."""
+        those nodes; None = the whole dataset.  build = "host" (the pre-pass on the host) or "device" (on the GPU,
+        nhp_cont_dataset_create_device: the same dataset, byte for byte).  events / nodes given as torch tensors on
+        ctx's device always take the device route and are copied on the device; no host copy is kept."""
+        if build not in ("host", "device"):
+            raise ValueError(f'build must be "host" or "device", not {build!r}')
         events, nodes, duration = data
-        self.events = _lib.f64(events)
-        self.nodes = np.ascontiguousarray(nodes, dtype=np.int64)
-        if len(self.events) != len(self.nodes):
-            raise ValueError("events and nodes must have the same length")
         self.duration, self.Δtmax, self.nnodes, self.ctx = float(duration), float(Δtmax), int(nnodes), ctx
         h = C.c_void_p()
         self.columns = (0, int(nnodes)) if columns is None else (int(columns[0]), int(columns[1]))
-        _lib.check(_lib.lib().nhp_cont_dataset_create_columns(ctx.h, _lib.dptr(self.events), _lib.iptr(self.nodes),
-                                                              len(self.events), nnodes, self.duration, self.Δtmax,
-                                                              self.columns[0], self.columns[1], C.byref(h)), ctx.h)
+        lib = _lib.lib()
+        if _on_device(events) or _on_device(nodes):
+            import torch
+            ev, nd = _device_tensors(events, nodes, ctx)
+            self.events = self.nodes = None
+            self.M, self.build = int(ev.numel()), "device"
+            torch.cuda.current_stream(ev.device).synchronize()      # the producer's work is done before the library reads
+            rc = lib.nhp_cont_dataset_create_device(ctx.h, ev.data_ptr(), nd.data_ptr(), self.M, nnodes, self.duration,
+                                                    self.Δtmax, self.columns[0], self.columns[1], 1, C.byref(h))
+        else:
+            self.events = _lib.f64(host_array(events, np.float64))
+            self.nodes = np.ascontiguousarray(host_array(nodes, np.int64))
+            if len(self.events) != len(self.nodes):
+                raise ValueError("events and nodes must have the same length")
+            self.M, self.build = len(self.events), build
+            if build == "device":
+                rc = lib.nhp_cont_dataset_create_device(ctx.h, self.events.ctypes.data, self.nodes.ctypes.data, self.M, nnodes,
+                                                        self.duration, self.Δtmax, self.columns[0], self.columns[1], 0,
+                                                        C.byref(h))
+            else:
+                rc = lib.nhp_cont_dataset_create_columns(ctx.h, _lib.dptr(self.events), _lib.iptr(self.nodes), self.M, nnodes,
+                                                         self.duration, self.Δtmax, self.columns[0], self.columns[1],
+                                                         C.byref(h))
+        _lib.check(rc, ctx.h)
         self.h = h
         self._fin = weakref.finalize(self, _lib.lib().nhp_cont_dataset_destroy, h)
 
     def __len__(self):
-        return len(self.events)
+        return self.M
 
     @property
     def pairs(self):
         return _lib.lib().nhp_cont_dataset_pairs(self.h)
 
+    def scalars(self):
+        """The dataset's scalars (DATASET_SCALARS) as a dict of ints; t_last, ev8_t0, ev8_scale as float64 bit patterns."""
+        buf = (C.c_int64 * len(DATASET_SCALARS))()
+        _lib.check(_lib.lib().nhp_cont_dataset_scalars(self.h, buf, len(buf)), self.ctx.h)
+        return dict(zip(DATASET_SCALARS, (int(v) for v in buf)))
+
+    def array(self, name):
+        """One of the dataset's arrays (DATASET_ARRAYS) as a host numpy copy; empty if the dataset has none."""
+        which, dt = DATASET_ARRAYS[name]
+        n = C.c_int64()
+        lib = _lib.lib()
+        _lib.check(lib.nhp_cont_dataset_export(self.ctx.h, self.h, which, None, 0, C.byref(n)), self.ctx.h)
+        out = np.empty(n.value, dtype=np.uint8)
+        if n.value:
+            _lib.check(lib.nhp_cont_dataset_export(self.ctx.h, self.h, which, out.ctypes.data, n.value, C.byref(n)), self.ctx.h)
+        return out.view(dt)
+
+    def layout(self):
+        """Every exported array and the scalars: {"arrays": {name: ndarray}, "scalars": {name: int}} (tests, tools)."""
+        return {"arrays": {k: self.array(k) for k in DATASET_ARRAYS}, "scalars": self.scalars()}
+
 
 _ds_cache = {}
 
 
-def device_dataset(process, data, ctx=None):
-    """Upload `data` once per (arrays, Δtmax); repeated calls (mle!, mcmc!) reuse the device copy."""
+def device_dataset(process, data, ctx=None, build="host"):
+    """Upload `data` once per (arrays, Δtmax); repeated calls (mle!, mcmc!) reuse the device copy.  build = "host" |
+    "device" picks where the pre-pass runs for host arrays (DeviceDataset); torch tensors on the context's device always
+    take the device route."""
     if isinstance(data, DeviceDataset):
         return data
     ctx = ctx or _lib.default_context()
     events, nodes, duration = data
-    key = (id(events), id(nodes), len(events), float(duration), float(process.impulses.Δtmax), process.ndims(), id(ctx))
+    N, Δtmax = process.ndims(), float(process.impulses.Δtmax)
+    if _on_device(events) or _on_device(nodes):
+        # (data_ptr, numel, version): an in-place refill of the tensors bumps their version and so builds again
+        key = ("tensor", events.data_ptr(), events.numel(), events._version, nodes.data_ptr(), nodes.numel(), nodes._version,
+               float(duration), Δtmax, N, id(ctx))
+        hit = _ds_cache.get(key)
+        if hit is not None and hit[1]() is events and hit[2]() is nodes:
+            return hit[0]
+        ds = DeviceDataset(ctx, data, N, Δtmax, build="device")
+        if len(_ds_cache) > 16:
+            _ds_cache.clear()
+        _ds_cache[key] = (ds, weakref.ref(events), weakref.ref(nodes))
+        return ds
+    key = (id(events), id(nodes), len(events), float(duration), Δtmax, N, id(ctx), build)
     hit = _ds_cache.get(key)
     # the arrays may have been refilled in place since the upload (a preallocated buffer reused for the next dataset):
     # a cheap content fingerprint decides, not the identity alone
     if hit is not None and hit[1]() is events and hit[2] == _fingerprint(events, nodes):
         return hit[0]
-    ds = DeviceDataset(ctx, data, process.ndims(), process.impulses.Δtmax)
+    ds = DeviceDataset(ctx, data, N, Δtmax, build=build)
     try:
         ref = weakref.ref(events)
     except TypeError:

@@ -49,7 +49,144 @@ extern "C" nhp_status nhp_cont_dataset_create(nhp_ctx *ctx, const double *events
     return nhp_cont_dataset_create_columns(ctx, events, nodes, M, N, duration, dt_max, 0, N, out);
 }
 
+uint64_t nhp_new_dataset_uid()
+{
+    static std::atomic<uint64_t> next_uid{1};
+    return next_uid.fetch_add(1);
+}
+
 bool nhp_is_column_shard(const nhp_cont_dataset *ds) { return ds->col_begin != 0 || ds->col_end != ds->N; }
+
+nhp_status nhp_cont_dataset_check_args(nhp_ctx *ctx, int64_t M, int32_t N, double duration, double dt_max, int32_t col_begin,
+                                       int32_t col_end)
+{
+    if (col_begin < 0 || col_end > N || col_begin >= col_end) {
+        nhp_set_error(ctx, "column range [%d, %d) must be a non-empty part of [0, %d)", col_begin, col_end, N);
+        return NHP_EINVAL;
+    }
+    if (M >= (int64_t)1 << 31) { nhp_set_error(ctx, "n_events must be < 2^31"); return NHP_EINVAL; }
+    if (!(duration >= 0.0)) { nhp_set_error(ctx, "duration must be non-negative"); return NHP_EDOMAIN; }
+    if (!(dt_max > 0.0)) { nhp_set_error(ctx, "dt_max must be positive"); return NHP_EDOMAIN; }
+    return NHP_OK;
+}
+
+void nhp_cont_partition(nhp_cont_dataset *ds, const nhp_lower_fn &lower, nhp_cont_plan &p)
+{
+    const int64_t M = ds->M, pairs = ds->pairs;
+    const int32_t N = ds->N;
+    const double dt_max = ds->dt_max;
+    ds->group = nhp_pick_group(M > 0 ? (double)pairs / (double)M : 0.0);
+    // partition buckets into items of at most `chunk` children; every node gets >= 1 item
+    // ~1024 items (4 per CU): one item per node when there are that many nodes (a node's column is
+    // then staged exactly once), otherwise nodes are cut into runs of M/1024 children
+    int64_t chunk = N >= 1024 ? (int64_t)(1.3 * (double)M / (double)N) + 1 : (M + 1023) / 1024;
+    chunk = std::max<int64_t>(32, std::min<int64_t>(4096, chunk));
+    const char *env = getenv("NHP_CHUNK");
+    if (env && atoi(env) > 0) chunk = std::min(atoi(env), 4096);
+    std::vector<nhp_item> &items = p.items;
+    items.clear();
+    // XCD-aware layout: workgroups are dealt round-robin over the 8 XCDs, so item b runs on XCD b % 8.
+    // Giving XCD x = s*(8/TP) + g the children of time part s on the nodes with c % (8/TP) == g makes
+    // every XCD touch only 1/TP of the event array (its 4 MiB L2 no longer streams all of it) at the
+    // price of staging each column TP times.  That price decides: at mean window 8 the staging eats the
+    // gain (tools/xcd.sh), at 64 two time parts win 6 %, at 512 four win 12 % (profiles/README.md).
+    // NHP_XCD = 0 | 2 | 4 | 8 overrides.  Speed heuristic only: any placement gives the same result.
+    const char *xenv = getenv("NHP_XCD");
+    const double kbar = M > 0 ? (double)pairs / (double)M : 0.0;
+    // Datasets whose pairs are kept as child slices (short and middle windows, below) are STREAMED by their log-likelihood and
+    // gradient kernels: no scattered window for an XCD's L2 to hold, so the second staging of every column only costs there
+    // (mean window 64: 103.8 us with two time parts, 78.8 us with none; the simulated set 54.5 -> 49.6).
+    const int64_t slices_maxk = getenv("NHP_SLICES_MAXK") ? atoi(getenv("NHP_SLICES_MAXK")) : 160;
+    const bool slices_on = !(getenv("NHP_SLICES") && atoi(getenv("NHP_SLICES")) == 0);
+    const bool sliced = slices_on && pairs > 0 && pairs <= slices_maxk * M && std::isfinite(dt_max) && dt_max > 0.0 && N <= 65534;
+    const int TP = xenv ? atoi(xenv) : (kbar >= 192.0 ? 4 : (kbar >= 24.0 && !sliced ? 2 : 0));
+    if ((TP == 2 || TP == 4 || TP == 8) && N >= 8 && M >= 16 * (int64_t)N) {
+        const int NG = 8 / TP;
+        for (int32_t c0 = 0; c0 < N; c0 += NG)
+            for (int s = 0; s < TP; ++s)
+                for (int g = 0; g < NG; ++g) {
+                    nhp_item it;
+                    const int32_t c = c0 + g < N ? c0 + g : N - 1;
+                    const bool real = c0 + g < N;
+                    const int32_t b = ds->h_boff[c];
+                    // children of c whose event index lies in [M*s/TP, M*(s+1)/TP): contiguous (time order)
+                    it.node = c;
+                    it.kbeg = real ? lower(c, s, TP) : b;
+                    it.kend = real ? lower(c, s + 1, TP) : b;
+                    it.first = real && s == 0;
+                    items.push_back(it);
+                }
+    } else
+    for (int32_t c = 0; c < N; ++c) {
+        int32_t b = ds->h_boff[c], e = ds->h_boff[c + 1];
+        int32_t n = e - b;
+        int32_t parts = std::max<int32_t>(1, (int32_t)((n + chunk - 1) / chunk));
+        for (int32_t q = 0; q < parts; ++q) {
+            nhp_item it;
+            it.node = c;
+            it.kbeg = b + (int32_t)((int64_t)n * q / parts);
+            it.kend = b + (int32_t)((int64_t)n * (q + 1) / parts);
+            it.first = q == 0;
+            items.push_back(it);
+        }
+    }
+    if (ds->col_begin != 0 || ds->col_end != N) {          // a column shard keeps the items of its own columns
+        std::vector<nhp_item> own;
+        for (const nhp_item &it : items)
+            if (it.node >= ds->col_begin && it.node < ds->col_end) own.push_back(it);
+        items.swap(own);
+    }
+    {   // bit 1 of `first`: the node's only item
+        std::vector<int32_t> per_node((size_t)N, 0);
+        for (const nhp_item &it : items) per_node[(size_t)it.node]++;
+        ds->all_sole = !items.empty();
+        for (nhp_item &it : items) {
+            if (per_node[(size_t)it.node] == 1) it.first |= 2;
+            else ds->all_sole = false;
+        }
+    }
+    ds->n_items = (int32_t)items.size();
+    ds->max_item = 0;
+    for (const nhp_item &it : items) ds->max_item = std::max(ds->max_item, it.kend - it.kbeg);
+    // Windowed kernels: children of an item are visited in rounds of (256/G)*U.  Measured orderings
+    // (tools/sortcmp.sh, K=8): 2 = whole item by window length (lanes of a wave run equal pair-loop
+    // trips; fastest, 43.4 us, FETCH_SIZE 99.9 MB raw), 1 = rounds in time order, window-sorted inside
+    // (all workgroups sweep the time axis together: 14 % less L2-miss traffic, 45.4 us), 0 = time
+    // order (48.8 us).  The sum does not depend on the order and the order is fixed: deterministic.
+    const int G = ds->group, U = G <= 8 ? NHP_U_SMALL : (G <= 32 ? NHP_U_MID : 1);
+    p.round = (NHP_WBLOCK / G) * U;
+    const char *flat = getenv("NHP_SORT");
+    p.sort_mode = flat ? atoi(flat) : 2;
+    p.sliced = sliced;
+    // pair offsets in child_w order (see nhp_cont_dataset::d_poff)
+    const int64_t plist_maxk = getenv("NHP_PLIST_MAXK") ? atoi(getenv("NHP_PLIST_MAXK")) : 40;      // (mean window 32: 95.5 -> 79.8 us; 64: 124 -> 148, so not there)
+    p.plist = pairs > 0 && pairs <= plist_maxk * M && pairs < ((int64_t)1 << 31) && std::isfinite(dt_max) && dt_max > 0.0 && N <= 65535;
+}
+
+bool nhp_cont_slices_keep(nhp_cont_dataset *ds, uint64_t rows, int32_t n_slices, int32_t max_rows)
+{
+    // padding must stay a small share (it is read like pairs) and the row index has to fit 32 bits with 64 records a row
+    if (rows >= ((uint64_t)1 << 25) || rows * 64 > (uint64_t)ds->pairs * 2 + 4096) { ds->sl_max_rows = 0; return false; }
+    ds->sl_rows = (int64_t)rows;
+    ds->n_slices = n_slices;
+    ds->sl_max_rows = max_rows;
+    int nb = 0;
+    while (((int64_t)1 << nb) <= ds->N) ++nb;                  // bit length of N: the padding records sit on node N
+    ds->sl_nb = nb;
+    return true;
+}
+
+bool nhp_ev8_params(int32_t N, int64_t M, double e0, double e1, double *t0, double *scale)
+{
+    // 8-byte records (nhp_internal.h): only where a node fits 16 bits and the span is a finite positive number
+    if (!(N <= 65535 && M > 0 && std::isfinite(e0) && std::isfinite(e1) && e1 > e0)) return false;
+    const double range = e1 - e0;
+    const int s2 = 47 - std::ilogb(range);                      // range * 2^s2 < 2^48
+    if (!(s2 > -900 && s2 < 900)) return false;
+    *t0 = e0;
+    *scale = std::ldexp(1.0, s2);
+    return true;
+}
 
 // The log-likelihood is a sum over child nodes c of  -∫λ0_c - Σ_p cnt[p]·W[p,c] + Σ_{i: c_i = c} log λ_i  and the
 // gradient is block-separable in the same columns, so one evaluation shards over GPUs by column range: every shard
@@ -60,13 +197,7 @@ extern "C" nhp_status nhp_cont_dataset_create_columns(nhp_ctx *ctx, const double
 {
     if (!ctx || !out || M < 0 || N < 1 || (M > 0 && (!events || !nodes))) return NHP_EINVAL;
     *out = nullptr;
-    if (col_begin < 0 || col_end > N || col_begin >= col_end) {
-        nhp_set_error(ctx, "column range [%d, %d) must be a non-empty part of [0, %d)", col_begin, col_end, N);
-        return NHP_EINVAL;
-    }
-    if (M >= (int64_t)1 << 31) { nhp_set_error(ctx, "n_events must be < 2^31"); return NHP_EINVAL; }
-    if (!(duration >= 0.0)) { nhp_set_error(ctx, "duration must be non-negative"); return NHP_EDOMAIN; }
-    if (!(dt_max > 0.0)) { nhp_set_error(ctx, "dt_max must be positive"); return NHP_EDOMAIN; }
+    NHP_TRY(nhp_cont_dataset_check_args(ctx, M, N, duration, dt_max, col_begin, col_end));
     for (int64_t i = 0; i < M; ++i) {
         if (nodes[i] < 1 || nodes[i] > N) {
             nhp_set_error(ctx, "node id %lld at event %lld outside 1..%d", (long long)nodes[i], (long long)(i + 1), N);
@@ -88,8 +219,7 @@ extern "C" nhp_status nhp_cont_dataset_create_columns(nhp_ctx *ctx, const double
     lap("validation");
 
     nhp_cont_dataset *ds = new nhp_cont_dataset();
-    static std::atomic<uint64_t> next_uid{1};
-    ds->uid = next_uid.fetch_add(1);
+    ds->uid = nhp_new_dataset_uid();
     ds->ctx = ctx; ds->M = M; ds->N = N; ds->duration = duration; ds->dt_max = dt_max;
     ds->col_begin = col_begin; ds->col_end = col_end;
     ds->t_last = M > 0 ? events[M - 1] : 0.0;
@@ -114,7 +244,6 @@ extern "C" nhp_status nhp_cont_dataset_create_columns(nhp_ctx *ctx, const double
     ds->h_pair_off.assign((size_t)N + 1, 0);
     for (int64_t i = 0; i < M; ++i) ds->h_pair_off[node32[i] + 1] += i - first[i];
     for (int32_t c = 0; c < N; ++c) ds->h_pair_off[c + 1] += ds->h_pair_off[c];
-    ds->group = nhp_pick_group(M > 0 ? (double)pairs / (double)M : 0.0);
     lap("pair offsets per node");
 
     // stable counting sort of children by node
@@ -129,95 +258,20 @@ extern "C" nhp_status nhp_cont_dataset_create_columns(nhp_ctx *ctx, const double
             r.t = events[i]; r.first = first[i]; r.idx = (int32_t)i;
         }
     }
-    // partition buckets into items of at most `chunk` children; every node gets >= 1 item
-    // ~1024 items (4 per CU): one item per node when there are that many nodes (a node's column is
-    // then staged exactly once), otherwise nodes are cut into runs of M/1024 children
-    int64_t chunk = N >= 1024 ? (int64_t)(1.3 * (double)M / (double)N) + 1 : (M + 1023) / 1024;
-    chunk = std::max<int64_t>(32, std::min<int64_t>(4096, chunk));
-    const char *env = getenv("NHP_CHUNK");
-    if (env && atoi(env) > 0) chunk = std::min(atoi(env), 4096);
-    std::vector<nhp_item> items;
-    // XCD-aware layout: workgroups are dealt round-robin over the 8 XCDs, so item b runs on XCD b % 8.
-    // Giving XCD x = s*(8/TP) + g the children of time part s on the nodes with c % (8/TP) == g makes
-    // every XCD touch only 1/TP of the event array (its 4 MiB L2 no longer streams all of it) at the
-    // price of staging each column TP times.  That price decides: at mean window 8 the staging eats the
-    // gain (tools/xcd.sh), at 64 two time parts win 6 %, at 512 four win 12 % (profiles/README.md).
-    // NHP_XCD = 0 | 2 | 4 | 8 overrides.  Speed heuristic only: any placement gives the same result.
-    const char *xenv = getenv("NHP_XCD");
-    const double kbar = M > 0 ? (double)pairs / (double)M : 0.0;
-    // Datasets whose pairs are kept as child slices (short and middle windows, below) are STREAMED by their log-likelihood and
-    // gradient kernels: no scattered window for an XCD's L2 to hold, so the second staging of every column only costs there
-    // (mean window 64: 103.8 us with two time parts, 78.8 us with none; the simulated set 54.5 -> 49.6).
-    const int64_t slices_maxk = getenv("NHP_SLICES_MAXK") ? atoi(getenv("NHP_SLICES_MAXK")) : 160;
-    const bool slices_on = !(getenv("NHP_SLICES") && atoi(getenv("NHP_SLICES")) == 0);
-    const bool sliced = slices_on && pairs > 0 && pairs <= slices_maxk * M && std::isfinite(dt_max) && dt_max > 0.0 && N <= 65534;
-    const int TP = xenv ? atoi(xenv) : (kbar >= 192.0 ? 4 : (kbar >= 24.0 && !sliced ? 2 : 0));
-    if ((TP == 2 || TP == 4 || TP == 8) && N >= 8 && M >= 16 * (int64_t)N) {
-        const int NG = 8 / TP;
-        for (int32_t c0 = 0; c0 < N; c0 += NG)
-            for (int s = 0; s < TP; ++s)
-                for (int g = 0; g < NG; ++g) {
-                    nhp_item it;
-                    const int32_t c = c0 + g < N ? c0 + g : N - 1;
-                    const bool real = c0 + g < N;
-                    const int32_t b = ds->h_boff[c], e = ds->h_boff[c + 1];
-                    // children of c whose event index lies in [M*s/TP, M*(s+1)/TP): contiguous (time order)
-                    auto lower = [&](int64_t bound) {
-                        int32_t lo = b, hi = e;
-                        while (lo < hi) { int32_t mid = (lo + hi) >> 1; if (child[mid].idx < bound) lo = mid + 1; else hi = mid; }
-                        return lo;
-                    };
-                    it.node = c;
-                    it.kbeg = real ? lower(M * s / TP) : b;
-                    it.kend = real ? lower(M * (s + 1) / TP) : b;
-                    it.first = real && s == 0;
-                    items.push_back(it);
-                }
-    } else
-    for (int32_t c = 0; c < N; ++c) {
-        int32_t b = ds->h_boff[c], e = ds->h_boff[c + 1];
-        int32_t n = e - b;
-        int32_t parts = std::max<int32_t>(1, (int32_t)((n + chunk - 1) / chunk));
-        for (int32_t q = 0; q < parts; ++q) {
-            nhp_item it;
-            it.node = c;
-            it.kbeg = b + (int32_t)((int64_t)n * q / parts);
-            it.kend = b + (int32_t)((int64_t)n * (q + 1) / parts);
-            it.first = q == 0;
-            items.push_back(it);
-        }
-    }
-    if (col_begin != 0 || col_end != N) {          // a column shard keeps the items of its own columns
-        std::vector<nhp_item> own;
-        for (const nhp_item &it : items)
-            if (it.node >= col_begin && it.node < col_end) own.push_back(it);
-        items.swap(own);
-    }
-    {   // bit 1 of `first`: the node's only item
-        std::vector<int32_t> per_node((size_t)N, 0);
-        for (const nhp_item &it : items) per_node[(size_t)it.node]++;
-        ds->all_sole = !items.empty();
-        for (nhp_item &it : items) {
-            if (per_node[(size_t)it.node] == 1) it.first |= 2;
-            else ds->all_sole = false;
-        }
-    }
-    ds->n_items = (int32_t)items.size();
-    for (const nhp_item &it : items) ds->max_item = std::max(ds->max_item, it.kend - it.kbeg);
+    nhp_cont_plan plan;
+    nhp_cont_partition(ds, [&](int32_t c, int32_t s, int32_t TP) {
+        const int64_t bound = M * s / TP;
+        int32_t lo = ds->h_boff[c], hi = ds->h_boff[c + 1];
+        while (lo < hi) { int32_t mid = (lo + hi) >> 1; if (child[mid].idx < bound) lo = mid + 1; else hi = mid; }
+        return lo;
+    }, plan);
+    const std::vector<nhp_item> &items = plan.items;
     lap("bucketing + items");
-    // Windowed kernels: children of an item are visited in rounds of (256/G)*U.  Measured orderings
-    // (tools/sortcmp.sh, K=8): 2 = whole item by window length (lanes of a wave run equal pair-loop
-    // trips; fastest, 43.4 us, FETCH_SIZE 99.9 MB raw), 1 = rounds in time order, window-sorted inside
-    // (all workgroups sweep the time axis together: 14 % less L2-miss traffic, 45.4 us), 0 = time
-    // order (48.8 us).  The sum does not depend on the order and the order is fixed: deterministic.
     std::vector<nhp_child> child_w(child);
     std::vector<int32_t> wpos((size_t)M);                 // bucket position of the child at each child_w position
     for (int64_t k = 0; k < M; ++k) wpos[(size_t)k] = (int32_t)k;
     {
-        const int G = ds->group, U = G <= 8 ? NHP_U_SMALL : (G <= 32 ? NHP_U_MID : 1);
-        const int round = (NHP_WBLOCK / G) * U;
-        const char *flat = getenv("NHP_SORT");
-        const int mode = flat ? atoi(flat) : 2;
+        const int round = plan.round, mode = plan.sort_mode;
         auto longer = [&](int32_t x, int32_t y) { return (child[x].idx - child[x].first) > (child[y].idx - child[y].first); };
         // items are disjoint ranges of wpos: sorted by a few host threads (37 ms of a 230 ms creation on one)
         auto sort_items = [&](size_t b, size_t e) {
@@ -241,8 +295,7 @@ extern "C" nhp_status nhp_cont_dataset_create_columns(nhp_ctx *ctx, const double
     }
     // pair offsets in child_w order (see nhp_cont_dataset::d_poff)
     std::vector<uint32_t> poff;
-    const int64_t plist_maxk = getenv("NHP_PLIST_MAXK") ? atoi(getenv("NHP_PLIST_MAXK")) : 40;      // (mean window 32: 95.5 -> 79.8 us; 64: 124 -> 148, so not there)
-    if (pairs > 0 && pairs <= plist_maxk * M && pairs < ((int64_t)1 << 31) && std::isfinite(dt_max) && dt_max > 0.0 && N <= 65535) {
+    if (plan.plist) {
         poff.resize((size_t)M + 1);
         uint32_t run = 0;
         for (int64_t k = 0; k < M; ++k) { poff[(size_t)k] = run; run += (uint32_t)(child_w[(size_t)k].idx - child_w[(size_t)k].first); }
@@ -253,9 +306,10 @@ extern "C" nhp_status nhp_cont_dataset_create_columns(nhp_ctx *ctx, const double
     std::vector<int32_t> sl_item0;
     // (short AND middle windows: the slices are streamed, 6 bytes a pair, where k_windowed gathers scattered windows --
     //  mean window 64: 115 -> ~70 us; at 512 the 3 GB list would cost what the exponentials do, so not there)
-    if (sliced) {
+    if (plan.sliced) {
         sl_item0.resize(items.size() + 1);
         uint64_t rows = 0;
+        int32_t max_rows = 0;
         for (size_t q = 0; q < items.size(); ++q) {
             sl_item0[q] = (int32_t)sl_row.size();
             for (int32_t k0 = items[q].kbeg; k0 < items[q].kend; k0 += 64) {
@@ -264,42 +318,30 @@ extern "C" nhp_status nhp_cont_dataset_create_columns(nhp_ctx *ctx, const double
                     longest = std::max(longest, child_w[(size_t)k].idx - child_w[(size_t)k].first);
                 sl_row.push_back((uint32_t)rows);
                 rows += (uint64_t)longest;
-                ds->sl_max_rows = std::max(ds->sl_max_rows, longest);
+                max_rows = std::max(max_rows, longest);
             }
         }
         sl_item0[items.size()] = (int32_t)sl_row.size();
         sl_row.push_back((uint32_t)rows);
-        // padding must stay a small share (it is read like pairs) and the row index has to fit 32 bits with 64 records a row
-        if (rows >= ((uint64_t)1 << 25) || rows * 64 > (uint64_t)pairs * 2 + 4096) { sl_row.clear(); sl_item0.clear(); ds->sl_max_rows = 0; }
-        else {
-            ds->sl_rows = (int64_t)rows;
-            ds->n_slices = (int32_t)sl_row.size() - 1;
-            int nb = 0;
-            while (((int64_t)1 << nb) <= N) ++nb;                  // bit length of N: the padding records sit on node N
-            ds->sl_nb = nb;
-            if (timing) fprintf(stderr, "[nhp dataset] child slices: %d slices, %lld rows = %.3f records per pair\n", ds->n_slices, (long long)rows,
-                                (double)rows * 64.0 / (double)pairs);
-        }
+        if (!nhp_cont_slices_keep(ds, rows, (int32_t)sl_row.size() - 1, max_rows)) { sl_row.clear(); sl_item0.clear(); }
+        else if (timing) fprintf(stderr, "[nhp dataset] child slices: %d slices, %lld rows = %.3f records per pair\n", ds->n_slices, (long long)rows,
+                                 (double)rows * 64.0 / (double)pairs);
     }
     std::vector<nhp_event> ev((size_t)M);
     lap("window sort + child_w + poff + slices");
     for (int64_t i = 0; i < M; ++i) { ev[i].t = events[i]; ev[i].node = node32[i]; ev[i].pad = 0; }
-    // 8-byte records (nhp_internal.h): only where a node fits 16 bits and the span is a finite positive number
+    // 8-byte records (nhp_internal.h)
     std::vector<uint64_t> ev8;
-    if (N <= 65535 && M > 0 && std::isfinite(events[0]) && std::isfinite(events[M - 1]) && events[M - 1] > events[0]) {
-        const double t0 = events[0], range = events[M - 1] - t0;
-        const int s2 = 47 - std::ilogb(range);                      // range * 2^s2 < 2^48
-        if (s2 > -900 && s2 < 900) {
-            const double scale = std::ldexp(1.0, s2);
-            ev8.resize((size_t)M);
-            for (int64_t i = 0; i < M; ++i) {
-                double q = std::nearbyint((events[i] - t0) * scale);
-                if (q < 0.0) q = 0.0;
-                if (q > 281474976710655.0) q = 281474976710655.0;
-                ev8[(size_t)i] = ((uint64_t)(uint32_t)node32[i] << 48) | (uint64_t)q;
-            }
-            ds->ev8_t0 = t0; ds->ev8_scale = scale;
+    double t0 = 0.0, scale = 0.0;
+    if (M > 0 && nhp_ev8_params(N, M, events[0], events[M - 1], &t0, &scale)) {
+        ev8.resize((size_t)M);
+        for (int64_t i = 0; i < M; ++i) {
+            double q = std::nearbyint((events[i] - t0) * scale);
+            if (q < 0.0) q = 0.0;
+            if (q > 281474976710655.0) q = 281474976710655.0;
+            ev8[(size_t)i] = ((uint64_t)(uint32_t)node32[i] << 48) | (uint64_t)q;
         }
+        ds->ev8_t0 = t0; ds->ev8_scale = scale;
     }
 
     lap("event records");
@@ -388,6 +430,52 @@ extern "C" void nhp_cont_dataset_destroy(nhp_cont_dataset *ds)
 }
 
 extern "C" int64_t nhp_cont_dataset_pairs(const nhp_cont_dataset *ds) { return ds ? ds->pairs : -1; }
+
+extern "C" nhp_status nhp_cont_dataset_export(nhp_ctx *ctx, const nhp_cont_dataset *ds, int32_t which, void *out, int64_t cap_bytes,
+                                              int64_t *bytes)
+{
+    if (!ctx || !ds || !bytes) return NHP_EINVAL;
+    const size_t M = (size_t)ds->M, N = (size_t)ds->N;
+    const void *src = nullptr;
+    size_t n = 0;
+    bool host = false;
+    switch (which) {
+    case NHP_DS_TIMES: src = ds->d_times; n = sizeof(double) * M; break;
+    case NHP_DS_NODES: src = ds->d_nodes; n = sizeof(int32_t) * M; break;
+    case NHP_DS_EV: src = ds->d_ev; n = sizeof(nhp_event) * M; break;
+    case NHP_DS_EV8: src = ds->d_ev8; n = ds->d_ev8 ? sizeof(uint64_t) * M : 0; break;
+    case NHP_DS_POFF: src = ds->d_poff; n = ds->d_poff ? sizeof(uint32_t) * (M + 1) : 0; break;
+    case NHP_DS_SL_ROW: src = ds->d_sl_row; n = ds->d_sl_row ? sizeof(uint32_t) * ((size_t)ds->n_slices + 1) : 0; break;
+    case NHP_DS_SL_ITEM0: src = ds->d_sl_item0; n = ds->d_sl_item0 ? sizeof(int32_t) * ((size_t)ds->n_items + 1) : 0; break;
+    case NHP_DS_CHILD: src = ds->d_child; n = sizeof(nhp_child) * M; break;
+    case NHP_DS_CHILD_W: src = ds->d_child_w; n = sizeof(nhp_child) * M; break;
+    case NHP_DS_WPOS: src = ds->d_wpos; n = sizeof(int32_t) * M; break;
+    case NHP_DS_BOFF: src = ds->d_boff; n = sizeof(int32_t) * (N + 1); break;
+    case NHP_DS_ITEMS: src = ds->d_items; n = sizeof(nhp_item) * (size_t)ds->n_items; break;
+    case NHP_DS_CNT: src = ds->d_cnt; n = sizeof(double) * N; break;
+    case NHP_DS_PAIR_OFF: src = ds->h_pair_off.data(); n = sizeof(int64_t) * ds->h_pair_off.size(); host = true; break;
+    default: nhp_set_error(ctx, "no dataset array %d", which); return NHP_EINVAL;
+    }
+    *bytes = (int64_t)n;
+    if (!out || n == 0) return NHP_OK;
+    if (cap_bytes < (int64_t)n) { nhp_set_error(ctx, "dataset array %d needs %lld bytes, %lld given", which, (long long)n, (long long)cap_bytes); return NHP_ESHAPE; }
+    if (host) { memcpy(out, src, n); return NHP_OK; }
+    NHP_HIP(ctx, hipSetDevice(ctx->device));
+    NHP_HIP(ctx, hipMemcpyAsync(out, src, n, hipMemcpyDeviceToHost, ctx->stream));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NHP_OK;
+}
+
+extern "C" nhp_status nhp_cont_dataset_scalars(const nhp_cont_dataset *ds, int64_t *out, int32_t cap)
+{
+    if (!ds || !out || cap < 0) return NHP_EINVAL;
+    auto bits = [](double x) { int64_t b; memcpy(&b, &x, sizeof b); return b; };
+    const int64_t v[NHP_DS_N_SCALARS] = {ds->M, ds->N, ds->pairs, ds->group, ds->n_items, ds->max_item, ds->max_window, ds->n_zero_time,
+                                         ds->all_sole, ds->sl_rows, ds->n_slices, ds->sl_nb, ds->sl_max_rows, bits(ds->t_last),
+                                         bits(ds->ev8_t0), bits(ds->ev8_scale)};
+    for (int32_t k = 0; k < cap && k < NHP_DS_N_SCALARS; ++k) out[k] = v[k];
+    return NHP_OK;
+}
 
 // ---- model ------------------------------------------------------------------------------
 

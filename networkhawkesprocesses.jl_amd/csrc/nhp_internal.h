@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <functional>
 #include <vector>
 
 #include "../../include/nhp.h"
@@ -315,6 +316,27 @@ void nhp_set_error(nhp_ctx *ctx, const char *fmt, ...);
 nhp_status nhp_ctx_reserve_partials(nhp_ctx *ctx, size_t n_doubles);
 nhp_status nhp_dataset_slab_stats(nhp_ctx *ctx, const nhp_cont_dataset *ds);      // cont_data.hip
 int nhp_pick_group(double mean_window);
+// Dataset creation: the decisions the host pre-pass (nhp_cont_dataset_create_columns) and the device pre-pass
+// (nhp_cont_dataset_create_device, cont_data_dev.hip) share, so the two builds cannot drift apart.
+struct nhp_cont_plan {
+    std::vector<nhp_item> items;
+    bool sliced = false;                // child slices (d_sl_row / d_sl_item0)
+    bool plist = false;                 // pair offsets (d_poff)
+    int sort_mode = 2;                  // NHP_SORT: 2 = each item by window length, 1 = inside rounds, 0 = bucket order
+    int round = 0;                      // children per round of the windowed kernels
+};
+uint64_t nhp_new_dataset_uid();       // process-unique (nhp_cont_dataset::uid)
+// lower(c, s, TP): the first bucket position of node c whose event index is >= M*s/TP (the time parts of the XCD layout)
+typedef std::function<int32_t(int32_t c, int32_t s, int32_t TP)> nhp_lower_fn;
+// needs ds->M, N, pairs, dt_max, col_begin/col_end and h_boff; sets ds->group, n_items, max_item, all_sole
+void nhp_cont_partition(nhp_cont_dataset *ds, const nhp_lower_fn &lower, nhp_cont_plan &p);
+// the argument checks before the per-event validation (same status and message on both routes)
+nhp_status nhp_cont_dataset_check_args(nhp_ctx *ctx, int64_t M, int32_t N, double duration, double dt_max, int32_t col_begin,
+                                       int32_t col_end);
+// child slices with `rows` rows in all: kept (sets sl_rows, n_slices, sl_nb, sl_max_rows) or dropped (false)
+bool nhp_cont_slices_keep(nhp_cont_dataset *ds, uint64_t rows, int32_t n_slices, int32_t max_rows);
+// the 8-byte event records' origin and scale from the first and the last time (false: no 8-byte records)
+bool nhp_ev8_params(int32_t N, int64_t M, double e0, double e1, double *t0, double *scale);
 // recursion_cost: what the caller's O(M·N) kernel costs relative to its windowed route, in units of the log-likelihood's
 // ratio (1 for the log-likelihood; the gradient's recursion is 3.5x the log-likelihood's, its windowed route 2.9x)
 nhp_status nhp_recursive_window(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const nhp_child **child_cut,

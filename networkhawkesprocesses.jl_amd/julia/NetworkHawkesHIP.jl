@@ -92,14 +92,23 @@ mutable struct Dataset          # (events, nodes, duration) uploaded once; pre-p
     h::Ptr{Cvoid}
 end
 # columns = 1-based node range this process evaluates (one loglikelihood / chain over several GPUs: `comm` keyword of the
-# entry points below); the default is the whole dataset
-function Dataset(ctx::Context, data, N::Integer, Δtmax::Real; columns::UnitRange{Int}=1:N)
+# entry points below); the default is the whole dataset.  build = :host (the pre-pass on the host) or :device (on the
+# GPU, nhp_cont_dataset_create_device: the same dataset, byte for byte)
+function Dataset(ctx::Context, data, N::Integer, Δtmax::Real; columns::UnitRange{Int}=1:N, build::Symbol=:host)
     events, nodes, duration = data
     ev, nd = Vector{Float64}(events), Vector{Int64}(nodes)
     r = Ref{Ptr{Cvoid}}(C_NULL)
-    GC.@preserve ev nd check(ccall((:nhp_cont_dataset_create_columns, libnhp), Int32,
-        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Int64, Int32, Float64, Float64, Int32, Int32, Ref{Ptr{Cvoid}}),
-        ctx.h, ev, nd, length(ev), N, duration, Δtmax, first(columns) - 1, last(columns), r), ctx.h)
+    if build === :device
+        GC.@preserve ev nd check(ccall((:nhp_cont_dataset_create_device, libnhp), Int32,
+            (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Int64, Int32, Float64, Float64, Int32, Int32, Int32, Ref{Ptr{Cvoid}}),
+            ctx.h, ev, nd, length(ev), N, duration, Δtmax, first(columns) - 1, last(columns), Int32(0), r), ctx.h)
+    elseif build === :host
+        GC.@preserve ev nd check(ccall((:nhp_cont_dataset_create_columns, libnhp), Int32,
+            (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Int64, Int32, Float64, Float64, Int32, Int32, Ref{Ptr{Cvoid}}),
+            ctx.h, ev, nd, length(ev), N, duration, Δtmax, first(columns) - 1, last(columns), r), ctx.h)
+    else
+        throw(ArgumentError("build must be :host or :device"))
+    end
     ds = Dataset(r[])
     finalizer(d -> ccall((:nhp_cont_dataset_destroy, libnhp), Cvoid, (Ptr{Cvoid},), d.h), ds)
 end

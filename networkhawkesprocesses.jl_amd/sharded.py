@@ -29,8 +29,8 @@ from . import _lib
 def column_costs(events, nodes, nnodes, Δtmax):
     """Per child node: parent-child pairs inside the look-back window plus a per-child constant -- what the
     windowed kernels' time is proportional to."""
-    events = np.asarray(events, dtype=np.float64)
-    nodes = np.asarray(nodes, dtype=np.int64)
+    from .components import host_array
+    events, nodes = host_array(events, np.float64), host_array(nodes, np.int64)
     if len(events) == 0:
         return np.ones(nnodes)
     # window of event i: parents j < i with t_j > t_i - Δtmax (strict, src/continuous.jl:291)
@@ -92,7 +92,8 @@ def _all_reduce_sum(x, ctx=None):
 class ShardedDataset:
     """This rank's column shard of (events, nodes, duration): built once, reused by every evaluation."""
 
-    def __init__(self, process, data, ctx=None, rank=None, world=None, ranges=None):
+    def __init__(self, process, data, ctx=None, rank=None, world=None, ranges=None, build="host"):
+        """build: where the shard's pre-pass runs (continuous.DeviceDataset); torch tensors take the device route."""
         from .continuous import DeviceDataset
         r, w = _world()
         self.rank = r if rank is None else int(rank)
@@ -103,7 +104,7 @@ class ShardedDataset:
         if len(self.ranges) != self.world:
             raise ValueError("one column range per rank")
         self.ctx = ctx or _lib.default_context()
-        self.local = DeviceDataset(self.ctx, data, N, Δtmax, columns=self.ranges[self.rank])
+        self.local = DeviceDataset(self.ctx, data, N, Δtmax, columns=self.ranges[self.rank], build=build)
 
 
 def sharded_loglikelihood(process, data, recursive=True, ctx=None, model=None):

@@ -586,17 +586,14 @@ nhp_status nhp_adj_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_mo
     const int32_t *d_k = ds->d_adj_k, *d_start = ds->d_adj_start;
     double *d_x = (double *)(base + o_x), *d_lam = (double *)(base + o_lam);
     double *d_uni = (double *)(base + o_uni), *d_bias = (double *)(base + o_bias);
-    static const int eval_threads = getenv("NHP_ADJ_EVAL_THREADS") ? atoi(getenv("NHP_ADJ_EVAL_THREADS")) : 512;
-#define NHP_AEVAL(imp, th, lqp)                                                                                        \
+#define NHP_AEVAL(imp, lqp)                                                                                            \
     do {                                                                                                               \
-        if (lds_eval > 64 * 1024) NHP_HIP(ctx, hipFuncSetAttribute((const void *)k_adj_eval<imp, th>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_eval)); \
-        hipLaunchKernelGGL((k_adj_eval<imp, th>), dim3(ncol), dim3(th), lds_eval, st, a, m->d_A, d_off, d_k, ds->d_adj_p, ds->d_adj_dt, lqp, d_x, \
+        if (lds_eval > 64 * 1024) NHP_HIP(ctx, hipFuncSetAttribute((const void *)k_adj_eval<imp, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_eval)); \
+        hipLaunchKernelGGL((k_adj_eval<imp, 512>), dim3(ncol), dim3(512), lds_eval, st, a, m->d_A, d_off, d_k, ds->d_adj_p, ds->d_adj_dt, lqp, d_x, \
                            max_children, d_lam, d_rho, rho, d_rho_scalar, d_u, seed, step, d_uni, d_bias);            \
     } while (0)
     if (expo) {
-        if (eval_threads == 256) NHP_AEVAL(NHP_IMPULSE_EXPONENTIAL, 256, (const double2 *)nullptr);
-        else if (eval_threads == 1024) NHP_AEVAL(NHP_IMPULSE_EXPONENTIAL, 1024, (const double2 *)nullptr);
-        else NHP_AEVAL(NHP_IMPULSE_EXPONENTIAL, 512, (const double2 *)nullptr);
+        NHP_AEVAL(NHP_IMPULSE_EXPONENTIAL, (const double2 *)nullptr);
     } else {
         if (!ds->d_adj_lq) {                                         // first logit-normal sweep on this dataset: the data half of the pdf
             nhp_cont_dataset *mds = const_cast<nhp_cont_dataset *>(ds);
@@ -607,9 +604,7 @@ nhp_status nhp_adj_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_mo
             }
             hipLaunchKernelGGL(k_adj_lq, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, (int64_t)ds->pairs, a.inv_dtmax, ds->d_adj_dt, mds->d_adj_lq);
         }
-        if (eval_threads == 256) NHP_AEVAL(NHP_IMPULSE_LOGITNORMAL, 256, (const double2 *)ds->d_adj_lq);
-        else if (eval_threads == 1024) NHP_AEVAL(NHP_IMPULSE_LOGITNORMAL, 1024, (const double2 *)ds->d_adj_lq);
-        else NHP_AEVAL(NHP_IMPULSE_LOGITNORMAL, 512, (const double2 *)ds->d_adj_lq);
+        NHP_AEVAL(NHP_IMPULSE_LOGITNORMAL, (const double2 *)ds->d_adj_lq);
     }
 #undef NHP_AEVAL
     NHP_HIP(ctx, hipGetLastError());

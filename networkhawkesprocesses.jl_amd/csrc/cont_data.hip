@@ -96,9 +96,8 @@ void nhp_cont_partition(nhp_cont_dataset *ds, const nhp_lower_fn &lower, nhp_con
     // Datasets whose pairs are kept as child slices (short and middle windows, below) are STREAMED by their log-likelihood and
     // gradient kernels: no scattered window for an XCD's L2 to hold, so the second staging of every column only costs there
     // (mean window 64: 103.8 us with two time parts, 78.8 us with none; the simulated set 54.5 -> 49.6).
-    const int64_t slices_maxk = getenv("NHP_SLICES_MAXK") ? atoi(getenv("NHP_SLICES_MAXK")) : 160;
-    const bool slices_on = !(getenv("NHP_SLICES") && atoi(getenv("NHP_SLICES")) == 0);
-    const bool sliced = slices_on && pairs > 0 && pairs <= slices_maxk * M && std::isfinite(dt_max) && dt_max > 0.0 && N <= 65534;
+    const int64_t slices_maxk = 160;           // most pairs per event a dataset is sliced at
+    const bool sliced = !nhp_slices_off(nullptr) && pairs > 0 && pairs <= slices_maxk * M && std::isfinite(dt_max) && dt_max > 0.0 && N <= 65534;
     const int TP = xenv ? atoi(xenv) : (kbar >= 192.0 ? 4 : (kbar >= 24.0 && !sliced ? 2 : 0));
     if ((TP == 2 || TP == 4 || TP == 8) && N >= 8 && M >= 16 * (int64_t)N) {
         const int NG = 8 / TP;
@@ -159,7 +158,7 @@ void nhp_cont_partition(nhp_cont_dataset *ds, const nhp_lower_fn &lower, nhp_con
     p.sort_mode = flat ? atoi(flat) : 2;
     p.sliced = sliced;
     // pair offsets in child_w order (see nhp_cont_dataset::d_poff)
-    const int64_t plist_maxk = getenv("NHP_PLIST_MAXK") ? atoi(getenv("NHP_PLIST_MAXK")) : 40;      // (mean window 32: 95.5 -> 79.8 us; 64: 124 -> 148, so not there)
+    const int64_t plist_maxk = 40;             // (mean window 32: 95.5 -> 79.8 us; 64: 124 -> 148, so not there)
     p.plist = pairs > 0 && pairs <= plist_maxk * M && pairs < ((int64_t)1 << 31) && std::isfinite(dt_max) && dt_max > 0.0 && N <= 65535;
 }
 

@@ -28,21 +28,6 @@ __device__ __forceinline__ double ggroup_sum(double v)
     return v;
 }
 
-__device__ __forceinline__ double grad_baseline_at(const nhp_cont_args &a, int c, double t)
-{
-#pragma clang fp contract(off)
-    if (a.baseline_kind == NHP_BASELINE_HOMOGENEOUS) return a.lambda0[c];
-    const double *x = a.grid;
-    const double *y = a.lambda0 + (size_t)c * a.grid_n;
-    int lo = 0, hi = a.grid_n - 1;
-    if (!(t < x[hi])) return y[hi];
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (t >= x[mid]) lo = mid; else hi = mid;
-    }
-    return (y[lo + 1] * (t - x[lo]) + y[lo] * (x[lo + 1] - t)) / (x[lo + 1] - x[lo]);
-}
-
 // params(baseline) is λ (N) or vcat(λ...) (N·G grid intensities of the LGCP): src/baselines.jl:41,173
 __device__ __forceinline__ size_t grad_nbase(const nhp_cont_args &a)
 {
@@ -188,105 +173,13 @@ __global__ __launch_bounds__(TH) void k_grad_windowed(nhp_cont_args a, const dou
     if (tid == 0 && gs != 0.0 && a.baseline_kind == NHP_BASELINE_HOMOGENEOUS) atomicAdd(&grad[c], gs);
 }
 
-// ---- recursive exponential: ll and gradient in one pass ---------------------------------------
-#define GR_RING 64
-__global__ __launch_bounds__(NHP_BLOCK) void k_grad_recursive(nhp_cont_args a, double *__restrict__ partials,
-                                                              double *__restrict__ grad)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    double *red = reinterpret_cast<double *>(smem);              // [4]
-    double *wpart = red + 4;                                     // [NHP_WAVES]
-    double *th = wpart + NHP_WAVES;                              // θ[p,c]
-    double *wth = th + a.N;                                      // (a·w)·θ
-    double *S = wth + a.N, *R = S + a.N;                         // state and derivative state at the last child
-    double *nS = R + a.N, *nR = nS + a.N;                        // segment accumulators referenced to t_k
-    double *GS = nR + a.N, *GR = GS + a.N;                       // Σ_k g_k S_p(t_k), Σ_k g_k R_p(t_k)
-
-    const int c = a.col_begin + blockIdx.x, N = a.N, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double integ = 0.0;
-    for (int p = tid; p < N; p += NHP_BLOCK) {
-        const size_t k = (size_t)p + (size_t)c * N;
-        const double w = a.W[k], weff = a.A ? a.A[k] * w : w, t = a.p1[k];
-        th[p] = t; wth[p] = weff * t;
-        S[p] = R[p] = nS[p] = nR[p] = GS[p] = GR[p] = 0.0;
-        integ += a.cnt[p] * w;
-    }
-    __syncthreads();
-    const int kb = a.boff[c], ke = a.boff[c + 1];
-    int prev_idx = 0;
-    double prev_t = 0.0, logsum = 0.0, gsum = 0.0;
-    for (int k = kb; k < ke; ++k) {
-        const nhp_child ch = a.child[k];
-        // four packed event records per thread in flight, exponentials evaluated unconditionally, atomics predicated
-        // (the scheme of k_recursive's fold)
-        for (int j0 = prev_idx + tid; j0 < ch.idx; j0 += 4 * NHP_BLOCK) {
-            nhp_event ev[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) ev[u] = a.ev[j0 + u * NHP_BLOCK < ch.idx ? j0 + u * NHP_BLOCK : j0];
-            double d[4], e[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { d[u] = ch.t - ev[u].t; e[u] = nhp_exp_neg(-(th[ev[u].node] * d[u])); }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (j0 + u * NHP_BLOCK < ch.idx && ev[u].t > 0.0) {
-                    atomicAdd(&nS[ev[u].node], e[u]);
-                    atomicAdd(&nR[ev[u].node], d[u] * e[u]);
-                }
-        }
-        __syncthreads();
-        const double gap = ch.t - prev_t;
-        double part = 0.0;
-        for (int p = tid; p < N; p += NHP_BLOCK) {
-            double s = S[p], r = R[p];
-            if (k != kb) {
-                const double dec = nhp_exp_neg(-(th[p] * gap));
-                r = dec * (r + gap * s);
-                s = dec * s;
-            }
-            s += nS[p]; r += nR[p];
-            nS[p] = 0.0; nR[p] = 0.0;
-            S[p] = s; R[p] = r;
-            part += wth[p] * s;
-        }
-        part = nhp_wave_sum(part);
-        if (lane == 0) wpart[wave] = part;
-        __syncthreads();
-        double lam = grad_baseline_at(a, c, ch.t);
-        for (int w = 0; w < NHP_WAVES; ++w) lam += wpart[w];
-        const double g = 1.0 / lam;
-        for (int p = tid; p < N; p += NHP_BLOCK) { GS[p] += g * S[p]; GR[p] += g * R[p]; }
-        if (tid == 0) {
-            logsum += nhp_log(lam);
-            if (a.baseline_kind == NHP_BASELINE_HOMOGENEOUS) gsum += g;
-            else grad_lgcp_scatter(a, c, ch.t, g, grad);
-        }
-        prev_idx = ch.idx;
-        prev_t = ch.t;
-    }
-    __syncthreads();
-    const size_t Nn = grad_nbase(a), NN = (size_t)N * (size_t)N;
-    for (int p = tid; p < N; p += NHP_BLOCK) {
-        const size_t k = (size_t)p + (size_t)c * N;
-        const double av = a.A ? a.A[k] : 1.0, w = a.W[k], t = th[p];
-        grad[Nn + NN + k] = -a.cnt[p] + av * t * GS[p];          // unmasked integral (D7)
-        grad[Nn + k] = av * w * (GS[p] - t * GR[p]);
-    }
-    const double blk = nhp_block_sum(logsum, red);
-    const double blk_int = nhp_block_sum(integ, red);
-    if (tid == 0) {
-        partials[2 * (size_t)blockIdx.x] = blk;
-        partials[2 * (size_t)blockIdx.x + 1] = blk_int;
-        if (a.baseline_kind == NHP_BASELINE_HOMOGENEOUS) grad[c] = -a.duration + gsum;
-    }
-}
-
 // ---- recursive exponential, gradient pass of the wave-partitioned recursion -------------------------------------------
 // k_recursive_waves (cont_recursive.hip) has evaluated the log-likelihood and left g_k = 1/λ_k of every child; with g known
 // the gradient needs no sum across parents any more: wave h of column c runs the same recursion on ITS parents -- state
 // S_p(t_k) = Σ_j e^{-θ(t_k - t_j)} and its θ-derivative state R_p(t_k) = Σ_j (t_k - t_j) e^{-θ(t_k - t_j)}, folded from the
 // per-part event lists (one exp, two LDS atomics per event) and decayed per child (one exp per parent) -- and accumulates
 // GS_p = Σ_k g_k S_p(t_k), GR_p = Σ_k g_k R_p(t_k) in registers.  No reduction, no ring, no barrier after the table is staged.
-// Reference: the objective of mle! (src/continuous.jl:144-198) differentiated by hand; same sums as k_grad_recursive.
+// Reference: the objective of mle! (src/continuous.jl:144-198) differentiated by hand.
 template <int PQ, int H>
 __global__ __launch_bounds__(64 * H) void k_grad_recursive_waves(nhp_cont_args a, nhp_rec_parts rp, const double *__restrict__ ginv,
                                                                  double *__restrict__ grad)
@@ -432,56 +325,34 @@ nhp_status nhp_grad_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_
         NHP_TRY(nhp_recursive_window(ctx, ds, m, &child_cut, &cut_group, 1.2));
     if ((flags & NHP_LL_RECURSIVE) && exp_imp && !child_cut) {
         // two passes of the wave-partitioned recursion: log-likelihood + 1/λ of every child, then the gradient sums
+        // (N > 4096: NHP_ENOTIMPL from nhp_rec_parts_for, before anything is launched)
         int PQ = 0, H = 0;
         nhp_rec_parts rp{};
         NHP_TRY(nhp_rec_parts_for(ctx, ds, &PQ, &H, &rp));
-        if (PQ) {
-            bool launched = false;
-            if (lgcp || nhp_is_column_shard(ds)) {
-                hipLaunchKernelGGL(k_grad_init, dim3(1024), dim3(256), 0, st, a, 0, d_grad);
-                NHP_HIP(ctx, hipGetLastError());
-            }
-            NHP_TRY(nhp_launch_recursive_waves(ctx, ds, m, ctx->d_results, d_lambda, &launched));
-            if (launched) {
-                const size_t wl = sizeof(double) * (64 + (size_t)H * 3 * 64 * PQ);
-                const int ncol = ds->col_end - ds->col_begin;
-#define NHP_GRW(Q, HH)                                                                                                           \
-                do {                                                                                                             \
-                    if (wl > 64 * 1024)                                                                                          \
-                        (void)hipFuncSetAttribute((const void *)k_grad_recursive_waves<Q, HH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl); \
-                    hipLaunchKernelGGL((k_grad_recursive_waves<Q, HH>), dim3((unsigned)ncol), dim3(64 * HH), wl, st, a, rp, d_lambda, d_grad); \
-                } while (0)
-                NHP_REC_SHAPES(NHP_GRW, launched = false);
-#undef NHP_GRW
-                if (launched) {
-                    NHP_HIP(ctx, hipGetLastError());
-                    *d_grad_out = d_grad;
-                    return NHP_OK;
-                }
-            }
-        }
-        const size_t lds = 8 * (4 + NHP_WAVES + 8 * N);
-        if (lds > 160 * 1024) { nhp_set_error(ctx, "recursive gradient: n_nodes = %d exceeds the LDS budget", ds->N); return NHP_ENOTIMPL; }
-        if (lds > 64 * 1024)
-            NHP_HIP(ctx, hipFuncSetAttribute((const void *)k_grad_recursive, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        NHP_TRY(nhp_ctx_reserve_partials(ctx, 2 * N));
         // the grid-intensity block is accumulated with atomics: start it from the integral's derivative; a column shard
         // needs the zeros of the columns it does not own
         if (lgcp || nhp_is_column_shard(ds)) {
             hipLaunchKernelGGL(k_grad_init, dim3(1024), dim3(256), 0, st, a, 0, d_grad);
             NHP_HIP(ctx, hipGetLastError());
         }
+        NHP_TRY(nhp_launch_recursive_waves(ctx, ds, m, ctx->d_results, d_lambda));
+        const size_t wl = sizeof(double) * (64 + (size_t)H * 3 * 64 * PQ);
         const int ncol = ds->col_end - ds->col_begin;
-        hipLaunchKernelGGL(k_grad_recursive, dim3((unsigned)ncol), dim3(NHP_BLOCK), lds, st, a, ctx->d_partials, d_grad);
+#define NHP_GRW(Q, HH)                                                                                                           \
+        do {                                                                                                                     \
+            if (wl > 64 * 1024)                                                                                                  \
+                (void)hipFuncSetAttribute((const void *)k_grad_recursive_waves<Q, HH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl); \
+            hipLaunchKernelGGL((k_grad_recursive_waves<Q, HH>), dim3((unsigned)ncol), dim3(64 * HH), wl, st, a, rp, d_lambda, d_grad); \
+        } while (0)
+        NHP_REC_SHAPES(NHP_GRW);
+#undef NHP_GRW
         NHP_HIP(ctx, hipGetLastError());
-        NHP_TRY(nhp_launch_finalize(ctx, a, ncol, ctx->d_results));
     } else {
         const int mask = child_cut ? 0 : 1;
         const int G = child_cut ? cut_group : ds->group;
         // exponential impulses on the dataset's own short / middle windows: ONE launch over the child and the parent slices
         // (cont_slices.hip: no LDS atomics, no λ round trip through HBM; k_grad_init only where items share a column)
-        if (!child_cut && exp_imp && ds->d_sl_row && !(getenv("NHP_SLICES") && atoi(getenv("NHP_SLICES")) == 0) &&
-            !(getenv("NHP_GRAD_SLICES") && atoi(getenv("NHP_GRAD_SLICES")) == 0)) {
+        if (!child_cut && exp_imp && ds->d_sl_row) {
             if (!nhp_grad_slices_direct(ds, m)) {
                 hipLaunchKernelGGL(k_grad_init, dim3(1024), dim3(256), 0, st, a, mask, d_grad);
                 NHP_HIP(ctx, hipGetLastError());
@@ -498,10 +369,9 @@ nhp_status nhp_grad_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_
         const size_t lds = 64 + 16 * N + 8 * N * (exp_imp ? 2 : 3) + (exp_imp ? 512 : 0);     // + the exponential's 2^(j/64) table
         if (lds > 160 * 1024) { nhp_set_error(ctx, "gradient: n_nodes = %d exceeds the 160 KiB LDS budget", ds->N); return NHP_ENOTIMPL; }
         dim3 grid((unsigned)ds->n_items);
-        // threads per item: 512 where an item has the pairs for them (NHP_GRAD_THREADS overrides)
+        // threads per item: 512 where an item has the pairs for them
         const double pairs_per_item = (double)(child_cut ? ds->cut_pairs : ds->pairs) / (double)std::max(1, ds->n_items);
-        static const int forced = getenv("NHP_GRAD_THREADS") ? atoi(getenv("NHP_GRAD_THREADS")) : 0;
-        const int TH = forced == 256 || forced == 512 ? forced : (pairs_per_item >= 4096.0 ? 512 : 256);
+        const int TH = pairs_per_item >= 4096.0 ? 512 : 256;
         if (exp_imp && TH == 512) launch_grad_group<NHP_IMPULSE_EXPONENTIAL, 512>(G, grid, lds, st, a, d_lambda, d_grad);
         else if (exp_imp) launch_grad_group<NHP_IMPULSE_EXPONENTIAL, 256>(G, grid, lds, st, a, d_lambda, d_grad);
         else if (TH == 512) launch_grad_group<NHP_IMPULSE_LOGITNORMAL, 512>(G, grid, lds, st, a, d_lambda, d_grad);

@@ -9,14 +9,14 @@
 // the network twin is NOT masked by A (D7).  The reference walks events serially and keeps an
 // N x N state; one event touches one row (update) and one column (read) of it.
 //
-// CDNA4 mapping: the state is partitioned by COLUMN.  Workgroup c owns S_{.,c} (N doubles in
-// LDS) plus column c of θ and of A∘W∘θ, and visits only the children of node c (node
-// buckets).  Between two consecutive children k-1 and k it folds the events of the segment
-// [idx_{k-1}, idx_k) -- contiguous in the time-ordered arrays, so the loads are coalesced --
-// into an accumulator with one exp and one LDS atomic each, then decays the state to t_k and
-// takes the dot product with the weights (one exp per parent node), lanes across parent
-// nodes.  Exp count per evaluation: M*N (segments) + M*N (decays) = the reference's 2*M*N,
-// but N workgroups wide and 256 lanes deep instead of serial.
+// CDNA4 mapping: the state is partitioned by COLUMN.  Workgroup c owns S_{.,c} plus column c
+// of θ and of A∘W∘θ, and visits only the children of node c (node buckets).  Between two
+// consecutive children k-1 and k it folds the events of the segment [idx_{k-1}, idx_k) into
+// an accumulator with one exp and one LDS atomic each, then decays the state to t_k and takes
+// the dot product with the weights (one exp per parent node), lanes across parent nodes.
+// Exp count per evaluation: M*N (segments) + M*N (decays) = the reference's 2*M*N, but N
+// workgroups wide instead of serial.  The parent nodes of a column are split between the
+// workgroup's waves (k_recursive_waves below).
 #include <algorithm>
 
 #include "nhp_internal.h"
@@ -40,162 +40,15 @@ __device__ __forceinline__ double rec_baseline(const nhp_cont_args &a, int c, do
     return (y[lo + 1] * (t - x[lo]) + y[lo] * (x[lo + 1] - t)) / (x[lo + 1] - x[lo]);
 }
 
-// Layout of one workgroup (column c): thread `tid` owns parent nodes p = tid + 256 q; their state
-// S_pc, θ_pc and (a·w·θ)_pc live in registers.  LDS holds θ[·,c] (gathered by node in the segment
-// pass) and TWO segment accumulators, so that folding segment k+1 and consuming segment k share
-// one barrier interval: one barrier per child instead of two, and two independent instruction
-// streams for the scheduler to interleave.
-// BLOCK threads, PQ parent nodes per thread (N <= BLOCK * PQ); the launcher picks 256 x 8 up to
-// N = 2048 and 512 x 8 up to 4096.
-template <int BLOCK, int PQ>
-__global__ __launch_bounds__(BLOCK) void k_recursive(nhp_cont_args a, double *__restrict__ partials)
-{
-    constexpr int WAVES = BLOCK / 64, REC_PQ = PQ, NP = BLOCK * PQ;   // NP >= N padded state slots: no bounds branches
-    extern __shared__ __align__(16) unsigned char smem[];
-    double *red = reinterpret_cast<double *>(smem);              // [8]
-    double *ring = red + 8;                                      // [2][NHP_RING * WAVES]
-    double *th = ring + 2 * NHP_RING * WAVES;                    // [NP] θ[p,c]
-    double *acc0 = th + NP;                                      // [NP] segment accumulators (double-buffered)
-    double *acc1 = acc0 + NP;
-
-    const int c = a.col_begin + blockIdx.x, N = a.N, tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-
-    double S[REC_PQ], thr[REC_PQ], wthr[REC_PQ];
-    double integ = 0.0;
-#pragma unroll
-    for (int q = 0; q < REC_PQ; ++q) {
-        const int p = tid + q * BLOCK;
-        S[q] = 0.0; thr[q] = 0.0; wthr[q] = 0.0;
-        th[p] = 0.0; acc0[p] = 0.0; acc1[p] = 0.0;               // slots p >= N stay (θ, aWθ, S) = 0
-        if (p < N) {
-            const size_t k = (size_t)p + (size_t)c * N;
-            const double w = a.W[k];
-            const double weff = a.A ? a.A[k] * w : w;
-            const double t = a.p1[k];
-            thr[q] = t; wthr[q] = weff * t;
-            th[p] = t;
-            integ += a.cnt[p] * w;                               // unmasked: src/continuous.jl:247,413
-        }
-    }
-    __syncthreads();
-
-    const int kb = a.boff[c], ke = a.boff[c + 1];
-    double logsum = 0.0;
-
-    // fold events into acc, referenced to time tk  (t_j > 0: the D9 seen-flag).  The FU exponentials of a thread are
-    // evaluated unconditionally (clamped records) and only the atomics are predicated: one basic block, so the
-    // independent polynomial chains interleave instead of running one masked block after the other.
-    constexpr int FU = 4;                                        // events per thread in flight together
-    auto fold_regs = [&](double *acc, const nhp_event *e, int j0, int je, double tk) {
-        double v[FU];
-#pragma unroll
-        for (int u = 0; u < FU; ++u) v[u] = nhp_exp_neg_ll(-(th[e[u].node] * (tk - e[u].t)));
-#pragma unroll
-        for (int u = 0; u < FU; ++u)
-            if (j0 + u * BLOCK < je && e[u].t > 0.0) atomicAdd(&acc[e[u].node], v[u]);
-    };
-    auto fold = [&](double *acc, int jb, int je, double tk) {
-        for (int j0 = jb + tid; j0 < je; j0 += FU * BLOCK) {
-            nhp_event e[FU];
-#pragma unroll
-            for (int u = 0; u < FU; ++u) e[u] = a.ev[j0 + u * BLOCK < je ? j0 + u * BLOCK : j0];
-            fold_regs(acc, e, j0, je, tk);
-        }
-    };
-
-    // child records (time, index) are kept in scalars and fetched two ahead, so their latency never
-    // sits on the loop (a struct copy here makes hipcc spill the records to scratch)
-    double ch_t = 0.0, nx_t = 0.0;
-    int ch_idx = 0, nx_idx = 0;
-    if (kb < ke) { ch_t = a.child[kb].t; ch_idx = a.child[kb].idx; nx_t = ch_t; nx_idx = ch_idx; }
-    if (kb + 1 < ke) { nx_t = a.child[kb + 1].t; nx_idx = a.child[kb + 1].idx; }
-    if (kb < ke) fold(acc0, 0, ch_idx, ch_t);
-    __syncthreads();
-    double prev_t = ch_t;                                        // first child: gap 0, exp(-0) = 1 on S = 0
-    double pending = 0.0;                                        // child k-1's lane partial: reduced under child k's math
-    for (int k = kb; k < ke; ++k) {
-        const int par = (k - kb) & 1;
-        double *accA = par ? acc0 : acc1;                        // filled now, consumed next iteration
-        double *accB = par ? acc1 : acc0;                        // filled last iteration, consumed now
-        const int kn = k + 2 < ke ? k + 2 : ke - 1;
-        const double nn_t = a.child[kn].t;
-        const int nn_idx = a.child[kn].idx;
-        // the first FU events per thread of the next segment are requested before the decay and folded after it, so
-        // their latency hides under the decay's exponentials; longer segments finish in the ordinary loop
-        const bool more = k + 1 < ke;
-        const int fb = ch_idx + tid, fe = more ? nx_idx : ch_idx;
-        nhp_event pe[FU];
-#pragma unroll
-        for (int u = 0; u < FU; ++u) pe[u] = a.ev[fb + u * BLOCK < fe ? fb + u * BLOCK : 0];
-        // decay the state to t_k, merge segment k, dot with the weights
-        const double gap = ch_t - prev_t;
-        double part = 0.0;
-#pragma unroll
-        for (int q = 0; q < REC_PQ; ++q) {
-            const int p = tid + q * BLOCK;
-            double s = S[q] * nhp_exp_neg_ll(-(thr[q] * gap));
-            s += accB[p];
-            accB[p] = 0.0;
-            S[q] = s;
-            part += wthr[q] * s;
-        }
-        // child k-1's reduction: independent of everything above, so its cross-lane latency is covered
-        if (k > kb) {
-            const double r = nhp_wave_sum(pending);
-            const int o = k - 1 - kb;
-            if (lane == 0) ring[(((o / NHP_RING) & 1) * NHP_RING + (o & (NHP_RING - 1))) * WAVES + wave] = r;
-        }
-        pending = part;
-        fold_regs(accA, pe, fb, fe, nx_t);
-        if (more) fold(accA, ch_idx + FU * BLOCK, nx_idx, nx_t);
-        __syncthreads();
-        // logs of a full half of the ring (children k-64 .. k-1), one lane each
-        const int done = k - kb;                                 // children whose partials are in the ring
-        if (done > 0 && (done & (NHP_RING - 1)) == 0) {
-            const int half = ((done - 1) / NHP_RING) & 1;
-            if (tid < NHP_RING) {
-                const double tk = a.child[k - NHP_RING + tid].t;
-                double lam = rec_baseline(a, c, tk);
-                for (int w = 0; w < WAVES; ++w) lam += ring[(half * NHP_RING + tid) * WAVES + w];
-                logsum += nhp_log(lam);
-            }
-        }
-        prev_t = ch_t;
-        ch_t = nx_t; ch_idx = nx_idx;
-        nx_t = nn_t; nx_idx = nn_idx;
-    }
-    if (kb < ke) {                                               // the last child's reduction and the ring's remainder
-        const int o = ke - 1 - kb;
-        const double r = nhp_wave_sum(pending);
-        if (lane == 0) ring[(((o / NHP_RING) & 1) * NHP_RING + (o & (NHP_RING - 1))) * WAVES + wave] = r;
-        __syncthreads();
-        const int slot = o & (NHP_RING - 1), half = (o / NHP_RING) & 1;
-        if (tid <= slot) {
-            const double tk = a.child[ke - 1 - slot + tid].t;
-            double lam = rec_baseline(a, c, tk);
-            for (int w = 0; w < WAVES; ++w) lam += ring[(half * NHP_RING + tid) * WAVES + w];
-            logsum += nhp_log(lam);
-        }
-    }
-    const double blk = nhp_block_sum_n<WAVES>(logsum, red);
-    const double blk_int = nhp_block_sum_n<WAVES>(integ, red);
-    if (tid == 0) {
-        partials[2 * (size_t)blockIdx.x] = blk;
-        partials[2 * (size_t)blockIdx.x + 1] = blk_int;
-    }
-}
-
 // ---- the recursion without a per-child barrier: one WAVE per (column, part of the parent nodes) ---------------------
-// k_recursive above folds a segment with the whole workgroup (rounds of FU·BLOCK events whatever the segment's length:
-// with ~N events between two children of a column and rounds of 1024, 1.58 rounds are evaluated for every one needed)
-// and then meets at a barrier before the decay: its waves wait 58 % of their time (profiles/README.md).  Here the parent
-// nodes are cut into H parts of NP = 64·PQ nodes and wave h of workgroup c owns S_{p,c} for the parents of part h ONLY:
-// it folds the events that fell on ITS parents (a per-part, time-ordered event list made once per dataset: data only)
-// in rounds of 64 and decays ITS states -- no other wave ever touches its accumulators, so the LDS atomics of a segment and
-// the reads of the decay are ordered by the wave's own instruction stream and the child loop has no barrier at all.  The
-// H partial intensities of a child meet in a ring (one barrier per NHP_RING children, as above).  Exponentials through
-// the 2^(j/64) table with -θ·64/ln 2 held per parent (nhp_exp_neg_tab_scaled).
+// The parent nodes are cut into H parts of NP = 64·PQ nodes and wave h of workgroup c owns S_{p,c} for the parents of part
+// h ONLY: it folds the events that fell on ITS parents (a per-part, time-ordered event list made once per dataset: data
+// only) in rounds of 64 and decays ITS states -- no other wave ever touches its accumulators, so the LDS atomics of a
+// segment and the reads of the decay are ordered by the wave's own instruction stream and the child loop has no barrier at
+// all.  (Round 1 folded a segment with the whole workgroup -- rounds of 1024 events whatever the segment's length -- and
+// met at a barrier before every decay: its waves waited 58 % of their time, profiles/README.md.)  The H partial
+// intensities of a child meet in a ring (one barrier per NHP_RING children).  Exponentials through the 2^(j/64) table
+// with -θ·64/ln 2 held per parent (nhp_exp_neg_tab_scaled).
 
 #define NHP_RECW_TS 66          // row stride of the reduction tile (doubles): 64 lanes + 2 of padding
 #define NHP_RECW_LDS(PQ, H) (sizeof(double) * (16 + 64 + 2 * NHP_RING * (size_t)(H) + (size_t)(H) * (2 * 64 * (PQ) + 8 * NHP_RECW_TS)))
@@ -552,16 +405,13 @@ static nhp_status rec_parts_build(nhp_ctx *ctx, const nhp_cont_dataset *ds, int 
     return NHP_OK;
 }
 
-// shape (parents per lane, parts) of the wave-partitioned recursion for this dataset, and its lists; *PQ = 0 when the
-// shape is not available (NHP_REC_WAVES=0, or N > 4096)
+// shape (parents per lane, parts) of the wave-partitioned recursion for this dataset, and its lists: one of the
+// NHP_REC_SHAPES, N <= 4096
 nhp_status nhp_rec_parts_for(nhp_ctx *ctx, const nhp_cont_dataset *ds, int *PQ_out, int *H_out, nhp_rec_parts *rp)
 {
-    *PQ_out = 0; *H_out = 0;
-    static const int waves = getenv("NHP_REC_WAVES") ? atoi(getenv("NHP_REC_WAVES")) : 1;
-    if (!waves || ds->N > 4096) return NHP_OK;
-    int PQ = ds->N <= 256 ? 1 : (ds->N <= 512 ? 2 : 4);
+    if (ds->N > 4096) { nhp_set_error(ctx, "recursive ll/gradient: n_nodes = %d > 4096 not supported", ds->N); return NHP_ENOTIMPL; }
+    const int PQ = ds->N <= 256 ? 1 : (ds->N <= 512 ? 2 : 4);
     int H = 1;
-    if (const char *env = getenv("NHP_REC_PARTS")) { int q = 0, hh = 0; if (sscanf(env, "%d,%d", &q, &hh) == 2 && 64 * q * hh >= ds->N) { PQ = q; H = hh; } }
     while (64 * PQ * H < ds->N) H *= 2;
     NHP_TRY(rec_parts_build(ctx, ds, 64 * PQ, H));
     *rp = nhp_rec_parts{ds->d_rec_ev, ds->d_rec_poff, ds->d_rec_rank};
@@ -570,19 +420,15 @@ nhp_status nhp_rec_parts_for(nhp_ctx *ctx, const nhp_cont_dataset *ds, int *PQ_o
 }
 
 // the O(M·N) recursion through k_recursive_waves: log-likelihood -> *d_out and, for the gradient pass, 1/λ of every child
-// -> d_ginv (bucket order; may be null).  *launched = false when no shape applies (the caller falls back).
-nhp_status nhp_launch_recursive_waves(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, double *d_out, double *d_ginv,
-                                      bool *launched)
+// -> d_ginv (bucket order; may be null)
+nhp_status nhp_launch_recursive_waves(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, double *d_out, double *d_ginv)
 {
-    *launched = false;
     int PQ = 0, H = 0;
     nhp_rec_parts rp{};
     NHP_TRY(nhp_rec_parts_for(ctx, ds, &PQ, &H, &rp));
-    if (!PQ) return NHP_OK;
     NHP_TRY(nhp_ctx_reserve_partials(ctx, 2 * (size_t)ds->N));
     nhp_cont_args a = nhp_make_args(ds, m);
     const size_t lds = NHP_RECW_LDS(PQ, H);
-    *launched = true;
 #define NHP_RECW(Q, HH)                                                                                                          \
         do {                                                                                                                     \
             if (lds > 64 * 1024)                                                                                                 \
@@ -590,9 +436,8 @@ nhp_status nhp_launch_recursive_waves(nhp_ctx *ctx, const nhp_cont_dataset *ds, 
             hipLaunchKernelGGL((k_recursive_waves<Q, HH>), dim3((unsigned)(ds->col_end - ds->col_begin)), dim3(64 * HH), lds, ctx->stream, \
                                a, rp, ctx->d_partials, d_ginv);                                                                  \
         } while (0)
-    NHP_REC_SHAPES(NHP_RECW, *launched = false);
+    NHP_REC_SHAPES(NHP_RECW);
 #undef NHP_RECW
-    if (!*launched) return NHP_OK;
     NHP_HIP(ctx, hipGetLastError());
     return nhp_launch_finalize(ctx, a, ds->col_end - ds->col_begin, d_out);
 }
@@ -602,30 +447,5 @@ static nhp_status nhp_launch_recursive_full(nhp_ctx *ctx, const nhp_cont_dataset
     if (m->impulse_kind != NHP_IMPULSE_EXPONENTIAL) return NHP_EINVAL;
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     if (ds->N > 4096) { nhp_set_error(ctx, "recursive ll: n_nodes = %d > 4096 not supported", ds->N); return NHP_ENOTIMPL; }
-    NHP_TRY(nhp_ctx_reserve_partials(ctx, 2 * (size_t)ds->N));
-    nhp_cont_args a = nhp_make_args(ds, m);
-    // one wave per (column, part of the parents), no barrier in the child loop (k_recursive_waves); NHP_REC_WAVES=0: the
-    // workgroup-wide fold + barrier per child (k_recursive).  NHP_REC_PARTS = "PQ,H" forces a shape (tools/kbench.py).
-    {
-        bool launched = false;
-        NHP_TRY(nhp_launch_recursive_waves(ctx, ds, m, d_out, nullptr, &launched));
-        if (launched) return NHP_OK;
-    }
-#define NHP_REC_LAUNCH(B, Q)                                                                                   \
-    do {                                                                                                       \
-        const size_t lds = sizeof(double) * (8 + 2 * NHP_RING * ((B) / 64) + 3 * (size_t)(B) * (Q));          \
-        if (lds > 64 * 1024)                                                                                   \
-            (void)hipFuncSetAttribute((const void *)k_recursive<B, Q>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_recursive<B, Q>), dim3((unsigned)(ds->col_end - ds->col_begin)), dim3(B), lds, ctx->stream, a, ctx->d_partials); \
-    } while (0)
-    // measured at N = 1024, M = 1e6 (first version: 256 x 8 3.16 ms, 512 x 4 3.35, 128 x 8 4.19, 64 x 16 7.35); with the
-    // segment loads issued ahead of the decay and the reduction deferred by one child: 256 x 4 2.97 ms
-    if (ds->N <= 256) NHP_REC_LAUNCH(256, 1);
-    else if (ds->N <= 512) NHP_REC_LAUNCH(256, 2);
-    else if (ds->N <= 1024) NHP_REC_LAUNCH(256, 4);
-    else if (ds->N <= 2048) NHP_REC_LAUNCH(256, 8);
-    else NHP_REC_LAUNCH(512, 8);
-#undef NHP_REC_LAUNCH
-    NHP_HIP(ctx, hipGetLastError());
-    return nhp_launch_finalize(ctx, a, ds->col_end - ds->col_begin, d_out);
+    return nhp_launch_recursive_waves(ctx, ds, m, d_out, nullptr);
 }

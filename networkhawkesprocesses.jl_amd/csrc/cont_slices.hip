@@ -1120,7 +1120,7 @@ static nhp_status launch_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const 
 {
     *launched = false;
     if (!ds->d_sl_row || ds->n_items <= 0 || m->impulse_kind != NHP_IMPULSE_EXPONENTIAL) return NHP_OK;
-    if (getenv("NHP_SLICES") && atoi(getenv("NHP_SLICES")) == 0) return NHP_OK;          // (A/B switch, read per call: the tests flip it)
+    if (nhp_slices_off(d_grad ? "NHP_GRAD_SLICES" : nullptr)) return NHP_OK;     // (NHP_GRAD_SLICES=0: the two-pass route of cont_grad.hip)
     const size_t lds = 320 + 16 * ((size_t)ds->N + 1) + 512 + (d_grad ? 8 * ((size_t)ds->max_item + 1) : 0);
     if (lds > 160 * 1024) return NHP_OK;
     NHP_HIP(ctx, hipSetDevice(ctx->device));
@@ -1183,7 +1183,7 @@ nhp_status nhp_launch_windowed_slices_ln(nhp_ctx *ctx, const nhp_cont_dataset *c
 {
     *launched = false;
     if (!cds->d_sl_row || cds->n_items <= 0 || m->impulse_kind != NHP_IMPULSE_LOGITNORMAL) return NHP_OK;
-    if ((getenv("NHP_SLICES") && atoi(getenv("NHP_SLICES")) == 0) || (getenv("NHP_SLICES_LN") && atoi(getenv("NHP_SLICES_LN")) == 0)) return NHP_OK;
+    if (nhp_slices_off("NHP_SLICES_LN")) return NHP_OK;
     const size_t lds = 320 + 24 * ((size_t)cds->N + 1);
     if (lds > 160 * 1024) return NHP_OK;
     NHP_HIP(ctx, hipSetDevice(ctx->device));
@@ -1228,7 +1228,6 @@ nhp_status nhp_launch_grad_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, cons
                                   bool *launched)
 {
     *launched = false;
-    if (getenv("NHP_GRAD_SLICES") && atoi(getenv("NHP_GRAD_SLICES")) == 0) return NHP_OK;   // (A/B switch: the two-pass route of cont_grad.hip)
     const bool direct = ds->all_sole && !nhp_is_column_shard(ds) && m->baseline_kind == NHP_BASELINE_HOMOGENEOUS;
     return launch_slices(ctx, ds, m, 1, d_out, d_grad, direct, launched);
 }
@@ -1287,7 +1286,7 @@ nhp_status nhp_launch_slices_batch(nhp_ctx *ctx, const nhp_cont_dataset *ds, con
 {
     *launched = false;
     if (!ds->d_sl_row || ds->n_items <= 0 || (S != 2 && S != 4)) return NHP_OK;
-    if ((getenv("NHP_SLICES") && atoi(getenv("NHP_SLICES")) == 0) || (getenv("NHP_BATCH_SLICES") && atoi(getenv("NHP_BATCH_SLICES")) == 0)) return NHP_OK;
+    if (nhp_slices_off("NHP_BATCH_SLICES")) return NHP_OK;
     for (int k = 0; k < S; ++k)
         if (!ms[k] || ms[k]->impulse_kind != NHP_IMPULSE_EXPONENTIAL || ms[k]->baseline_kind != NHP_BASELINE_HOMOGENEOUS) return NHP_OK;
     const size_t lds = 320 + 16 * ((size_t)ds->N + 1) * (size_t)S + 512;
@@ -1325,7 +1324,7 @@ nhp_status nhp_launch_sampler_slices(nhp_ctx *ctx, const nhp_cont_dataset *cds, 
     // (only windows below Julia's pairwise-sum threshold: the slice kernel sums sequentially)
     const bool expo = m->impulse_kind == NHP_IMPULSE_EXPONENTIAL;
     if (!cds->d_sl_row || cds->n_items <= 0 || (!expo && m->impulse_kind != NHP_IMPULSE_LOGITNORMAL) || cds->sl_max_rows + 1 > 1024) return NHP_OK;
-    if ((getenv("NHP_SLICES") && atoi(getenv("NHP_SLICES")) == 0) || (getenv("NHP_SAMPLER_SLICES") && atoi(getenv("NHP_SAMPLER_SLICES")) == 0)) return NHP_OK;
+    if (nhp_slices_off("NHP_SAMPLER_SLICES")) return NHP_OK;
     int B = 512, CACHE = 8;
     if (const char *cfg = getenv("NHP_SAMPLER_CFG")) sscanf(cfg, "%d,%d", &B, &CACHE);
     if (!((B == 256 || B == 512) && (CACHE == 8 || CACHE == 16))) { B = 512; CACHE = 8; }

@@ -348,6 +348,14 @@ nhp_status nhp_launch_windowed_as(nhp_ctx *ctx, const nhp_cont_dataset *ds, cons
                                   int group, int mask_integral, double *d_out);
 nhp_status nhp_ctx_reserve_scratch(nhp_ctx *ctx, size_t bytes);
 nhp_status nhp_ensure_pair_cache(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_args *a);   // cont_sampler.hip
+// The child-slice A/B switches, read on every call (the tests flip them inside one process): true when NHP_SLICES=0 (no
+// dataset is sliced, no route uses slices) or the route's own switch (NHP_SLICES_LN, NHP_GRAD_SLICES, NHP_BATCH_SLICES,
+// NHP_SAMPLER_SLICES; or null) is 0
+inline bool nhp_slices_off(const char *route_switch)
+{
+    const char *all = getenv("NHP_SLICES"), *route = route_switch ? getenv(route_switch) : nullptr;
+    return (all && atoi(all) == 0) || (route && atoi(route) == 0);
+}
 // cont_slices.hip: the exponential log-likelihood of the dataset's own short windows, one lane per child over the child
 // slices.  *launched = false (and NHP_OK) when the dataset has no slices or the model is not covered.
 nhp_status nhp_launch_windowed_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int mask_integral,
@@ -410,21 +418,18 @@ struct nhp_rec_parts {          // kernel-side view of the per-part lists (nhp_c
     const int32_t *rank;        // [H][M] by bucket position k: events of the part with time index < idx_k
 };
 nhp_status nhp_rec_parts_for(nhp_ctx *ctx, const nhp_cont_dataset *ds, int *PQ, int *H, nhp_rec_parts *rp);
-nhp_status nhp_launch_recursive_waves(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, double *d_out, double *d_ginv,
-                                      bool *launched);
-// the (parents per lane, parts) shapes both kernels are instantiated for: X(PQ, H) launches, `otherwise` runs when none fits
-#define NHP_REC_SHAPES(X, otherwise)              \
+nhp_status nhp_launch_recursive_waves(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, double *d_out, double *d_ginv);
+// the (parents per lane, parts) shapes nhp_rec_parts_for picks, which both kernels are instantiated for: X(PQ, H) launches
+// (N <= 64: 1 x 1, then 1 x 2, 1 x 4, 2 x 4, 4 x 4 up to N = 1024, 4 x 8, 4 x 16 up to N = 4096)
+#define NHP_REC_SHAPES(X)                         \
     do {                                          \
         if (PQ == 1 && H == 1) X(1, 1);           \
         else if (PQ == 1 && H == 2) X(1, 2);      \
         else if (PQ == 1 && H == 4) X(1, 4);      \
         else if (PQ == 2 && H == 4) X(2, 4);      \
-        else if (PQ == 2 && H == 8) X(2, 8);      \
         else if (PQ == 4 && H == 4) X(4, 4);      \
         else if (PQ == 4 && H == 8) X(4, 8);      \
-        else if (PQ == 4 && H == 16) X(4, 16);    \
-        else if (PQ == 8 && H == 2) X(8, 2);      \
-        else { otherwise; }                       \
+        else X(4, 16);                            \
     } while (0)
 // Ordering of one wave's own LDS traffic without draining it: the LDS unit executes a wave's instructions in issue order (an
 // atomic of lane A is seen by a later read of lane B of the same wave), so only the compiler must be kept from reordering.

@@ -262,8 +262,8 @@ def test_batch_lanes_follow_parameter_updates(nhp, orc):
 def test_batches_of_eight_share_one_pass(nhp, orc, kind, network, lgcp, N, M, T, monkeypatch):
     """nhp_cont_loglik_batch with 19 compatible models: 8 + 8 + 2 + 1 through k_windowed_batch (one lane per (child, model), the
     S columns in LDS, windows staged once per child) -- every value equals the oracle's windowed log-likelihood of its own
-    model, also with ragged windows (dense second case: windows of ~50 parents, several record chunks per child), and the
-    older 4-model kernel (NHP_BATCH_KERNEL=0) gives the same."""
+    model and the single evaluation's, also with ragged windows (dense second case: windows of ~50 parents, several record
+    chunks per child), through the slices batch (every workgroup shape) and k_windowed_batch alike."""
     import ctypes as C
     from nhp_amd import _lib
     ctx = nhp.default_context()

@@ -1,5 +1,4 @@
-"""Batched log-likelihood (nhp_cont_loglik_batch): NB parameter sets on one dataset.  NHP_BATCH_KERNEL=0 selects the older
-k_windowed_multi, NHP_BATCH_FUSE the largest group, NHP_BATCH_LANES=1 one stream; KBAR the mean window; KIND the impulse."""
+"""Batched log-likelihood (nhp_cont_loglik_batch): NB parameter sets on one dataset; KBAR the mean window; KIND the impulse."""
 import os, sys, time, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

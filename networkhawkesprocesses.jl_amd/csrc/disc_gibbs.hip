@@ -21,30 +21,8 @@
 // running sum with the bin's ascending thresholds u_(1) < u_(2) < ... (order statistics generated one
 // at a time from Philox, so n events cost one walk).  One lane owns a bin's running sum, in the
 // reference's category order with separate multiply and add: counts equal the oracle's, bit for bit.
-#ifndef RP_KC
-#define RP_KC 16        // categories a chunk (variant builds: 8 / 32, tools/dbg notes)
-#endif
-#ifndef RP_ABL
-#define RP_ABL 0        // (timing ablations, wrong results: 1 = no arithmetic in the walks, 2 = no global loads of the chunks, 3 = conflict-free G reads)
-#endif
+constexpr int RP_KC = 16;       // categories a chunk (8 and 32 were tried as variant builds)
 #define RP_KEY 0xD15C0DE5EEDC0FFEull
-#ifdef RP_STAMP
-// (debug build, tools/dbg/rpstamps.py) per workgroup: s_memtime ticks spent, over the chunks of walk 1 [0..3] and walk 2 [4..7], in the
-// barrier before a chunk is staged, the wait for its loads, staging + barrier, and its arithmetic
-__device__ unsigned long long g_rp_stamps[8 * 4096];
-extern "C" int nhp_debug_rp_stamps(unsigned long long *out, int n)
-{
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rp_stamps), sizeof(unsigned long long) * (size_t)n);
-}
-#define RP_T() __builtin_amdgcn_s_memtime()
-#define RP_ST_A() const unsigned long long ta = RP_T(); __syncthreads(); const unsigned long long tb0 = RP_T(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); const unsigned long long tb = RP_T()
-#define RP_ST_C() const unsigned long long tc = RP_T()
-#define RP_ST_D(w) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); { const unsigned long long td = RP_T(); st[4 * (w)] += tb0 - ta; st[4 * (w) + 1] += tb - tb0; st[4 * (w) + 2] += tc - tb; st[4 * (w) + 3] += td - tc; }
-#else
-#define RP_ST_A() __syncthreads()
-#define RP_ST_C() do { } while (0)
-#define RP_ST_D(w) do { } while (0)
-#endif
 
 __device__ __attribute__((noinline)) double rp_next_u(double u_prev, int remaining, uint64_t seed, uint64_t step, uint64_t bin, int j)
 {
@@ -55,22 +33,22 @@ __device__ __attribute__((noinline)) double rp_next_u(double u_prev, int remaini
     return u_prev + (1.0 - u_prev) * w;
 }
 
-// RP_SLOTS = occupied bins a thread carries through one pair of walks: the host picks the smallest of 1, 2, 4 whose
-// RP_TH·RP_SLOTS slots hold a tile's occupied bins (an empty slot costs the walk as much as a full one: at config 4 a
-// 64 x 128 tile holds ~400, and two slots per thread take 14.7 ms where four took 20.9).
+// RP_SLOTS = occupied bins a thread carries through one pair of walks: the host takes one where RP_TH slots hold a tile's
+// occupied bins, else two (an empty slot costs the walk as much as a full one: at config 4 a 64 x 128 tile holds ~400, and
+// two slots per thread take 14.7 ms where four took 20.9).
 // RP_TT x RP_CT = the tile (bins x child nodes), RP_TH threads.  What a launch moves is the staging traffic: per chunk of RP_KC
 // categories a tile fetches (RP_TT + RP_CT)·RP_KC doubles for RP_TT·RP_CT·rate occupied bins -- 78 GB per sweep at config 4 with
 // 64 x 128 tiles (5.6 TB/s out of L2 / the Infinity Cache: the bound of the 14 ms launch), half of that with 128 x 256.
-// COLM: the list runs column by column, every column padded to a multiple of RP_SLOTS, and a thread's slots are consecutive
+// The list runs column by column, every column padded to a multiple of RP_SLOTS, and a thread's slots are consecutive
 // entries -- bins of ONE node: E[category, node] is read once per category for all of them (and consecutive lanes read
 // consecutive nodes: no bank conflicts there), which leaves (1 + SLOTS) / SLOTS LDS reads per multiply-add instead of 2.
-// CHK: walk 1 keeps the running sum at the start of each eighth of the category axis (registers); walk 2 then enters a bin's
+// Walk 1 keeps the running sum at the start of each eighth of the category axis (registers); walk 2 then enters a bin's
 // chain at the eighth its first threshold falls into -- the same partial sum, bit for bit -- and leaves it when the bin's
 // events are placed: a bin with one event (97 % of them at 5 % occupancy) reads a sixteenth of the categories instead of all.
-// XCHG (with CHK): between the walks the bins still to be placed change lanes through LDS, ordered by the eighth their chain is
-// entered at -- a wave then holds bins of one or two eighths and skips the chunks of the others whole (scattered, some lane of
-// nearly every wave was inside its range in every chunk: the skipping of CHK was per lane only).
-template <int RP_SLOTS, int RP_TT, int RP_CT, int RP_TH, bool COLM, bool CHK, bool XCHG>
+// XCHG (two slots): between the walks the bins still to be placed change lanes through LDS, ordered by the eighth their chain
+// is entered at -- a wave then holds bins of one or two eighths and skips the chunks of the others whole (scattered, some lane
+// of nearly every wave was inside its range in every chunk: the skipping by eighths was per lane only).
+template <int RP_SLOTS, int RP_TT, int RP_CT, int RP_TH>
 __global__ __launch_bounds__(RP_TH, 4) void k_disc_resample_parents(const double *__restrict__ dataT, const double *__restrict__ conv,
                                                                const double *__restrict__ E2, const double *__restrict__ base,
                                                                const double *__restrict__ baseT, int64_t T, int N, int B,
@@ -78,6 +56,7 @@ __global__ __launch_bounds__(RP_TH, 4) void k_disc_resample_parents(const double
                                                                int *__restrict__ counts, int *__restrict__ base_counts, int xcd_ncy)
 {
 #pragma clang fp contract(off)
+    constexpr bool XCHG = RP_SLOTS == 2;
     extern __shared__ __align__(16) unsigned char rp_smem[];
     double (*Gt)[RP_TT] = reinterpret_cast<double (*)[RP_TT]>(rp_smem);                                   // [RP_KC][RP_TT]
     double (*Et)[RP_CT + 1] = reinterpret_cast<double (*)[RP_CT + 1]>(rp_smem + 8 * RP_KC * RP_TT);      // [RP_KC][RP_CT + 1]
@@ -97,20 +76,19 @@ __global__ __launch_bounds__(RP_TH, 4) void k_disc_resample_parents(const double
     }
     const int64_t t0 = (int64_t)tx * RP_TT;
     const int c0 = cy * RP_CT;
-    // Occupied bins, listed bin-row by bin-row (entry = tl·RP_CT + cl): consecutive lanes then share a
-    // bin row, so a wave's reads of a G row collapse to a few broadcast addresses and its reads of an E
-    // row hit distinct banks.  Flags are gathered with coalesced loads (t fastest), then compacted in order.
-    unsigned char *occ = reinterpret_cast<unsigned char *>(&Et[0][0]);       // [RP_TT][RP_CT] (COLM: [RP_CT][RP_TT]), before Et is used
+    // Occupied bins, listed column by column (entry = tl·RP_CT + cl).  Flags are gathered with coalesced loads (t fastest),
+    // then compacted in order.
+    unsigned char *occ = reinterpret_cast<unsigned char *>(&Et[0][0]);       // [RP_CT][RP_TT], before Et is used
     for (int i = tid; i < RP_TT * RP_CT; i += RP_TH) {
         const int tl_ = i % RP_TT, cl_ = i / RP_TT;
         const int64_t t = t0 + tl_;
         const int c = c0 + cl_;
-        occ[COLM ? i : tl_ * RP_CT + cl_] = (t < T && c < N && dataT[(size_t)t + (size_t)T * c] > 0.0) ? 1 : 0;
+        occ[i] = (t < T && c < N && dataT[(size_t)t + (size_t)T * c] > 0.0) ? 1 : 0;
     }
     __syncthreads();
-    if (COLM) {
+    {
         // whole columns per wave; a column's entries in bin order, then padding (0xFFFF) up to a multiple of RP_SLOTS
-        static_assert(!COLM || (RP_TT % 64 == 0 && (RP_TT * RP_CT / (RP_TH / 64)) % RP_TT == 0 && RP_TT * RP_CT < 65535), "tile shape (column-major list)");
+        static_assert(RP_TT % 64 == 0 && (RP_TT * RP_CT / (RP_TH / 64)) % RP_TT == 0 && RP_TT * RP_CT < 65535, "tile shape (column-major list)");
         const int lane = tid & 63, wave = tid >> 6;
         constexpr int CPW = RP_CT / (RP_TH / 64);                  // columns per wave
         int cnt = 0;
@@ -138,22 +116,6 @@ __global__ __launch_bounds__(RP_TH, 4) void k_disc_resample_parents(const double
             off += mp;
         }
         if (tid == RP_TH - 1) nb = off;
-    } else {
-        const int lane = tid & 63, wave = tid >> 6;
-        constexpr int PER_WAVE = RP_TT * RP_CT / (RP_TH / 64);
-        int cnt = 0;
-        for (int i = wave * PER_WAVE + lane; i < (wave + 1) * PER_WAVE; i += 64) cnt += __popcll(__ballot(occ[i] != 0));
-        if (lane == 0) wcnt[wave] = cnt;
-        __syncthreads();
-        int off = 0;
-        for (int w = 0; w < wave; ++w) off += wcnt[w];
-        for (int i = wave * PER_WAVE + lane; i < (wave + 1) * PER_WAVE; i += 64) {
-            const bool f = occ[i] != 0;
-            const unsigned long long m = __ballot(f);
-            if (f) list[off + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)i;
-            off += __popcll(m);
-        }
-        if (tid == RP_TH - 1) nb = off;
     }
     __syncthreads();
     const int nbins = nb;
@@ -176,7 +138,6 @@ __global__ __launch_bounds__(RP_TH, 4) void k_disc_resample_parents(const double
     unsigned gmask = 0, emask = 0;            // which of the fetched values are real (applied when staged,
     auto fetch = [&](int q0) {                // so that the loads stay in flight under the arithmetic)
         gmask = 0; emask = 0;
-        if (RP_ABL == 2) return;
 #pragma unroll
         for (int r = 0; r < GN; ++r) {
             const int qr = q0 + g_k0 + (RP_TH / RP_TT) * r;
@@ -199,14 +160,15 @@ __global__ __launch_bounds__(RP_TH, 4) void k_disc_resample_parents(const double
         for (int r = 0; r < EN; ++r) { const int e = tid + RP_TH * r; Et[e % RP_KC][e / RP_KC] = (emask >> r) & 1u ? re[r] : 0.0; }
     };
 
+    // more occupied bins than RP_TH·RP_SLOTS slots: a second round over the list (without the exchange)
     for (int b0 = 0; b0 < nbins; b0 += RP_TH * RP_SLOTS) {
         int tl[RP_SLOTS], cl[RP_SLOTS], n[RP_SLOTS], j[RP_SLOTS];
         double cum[RP_SLOTS], total[RP_SLOTS], thr[RP_SLOTS], u[RP_SLOTS];
 #pragma unroll
         for (int s = 0; s < RP_SLOTS; ++s) {
-            const int idx = COLM ? b0 + tid * RP_SLOTS + s : b0 + tid + RP_TH * s;
+            const int idx = b0 + tid * RP_SLOTS + s;
             const unsigned int e0 = idx < nbins ? list[idx] : 0xFFFFu;
-            const bool real = !COLM ? idx < nbins : e0 != 0xFFFFu;
+            const bool real = e0 != 0xFFFFu;
             const int e = real ? (int)e0 : 0;
             tl[s] = e / RP_CT; cl[s] = e % RP_CT;
             n[s] = real ? (int)dataT[(size_t)(t0 + tl[s]) + (size_t)T * (c0 + cl[s])] : 0;
@@ -214,17 +176,10 @@ __global__ __launch_bounds__(RP_TH, 4) void k_disc_resample_parents(const double
             cum[s] = n[s] > 0 ? (baseT ? baseT[(size_t)(t0 + tl[s]) + (size_t)T * (c0 + cl[s])] : base[c0 + cl[s]]) : 0.0;
             total[s] = 0.0; thr[s] = 0.0; u[s] = 0.0;
         }
-        if (RP_ABL == 3) {                                           // (timing only: G reads without bank conflicts)
-#pragma unroll
-            for (int s = 0; s < RP_SLOTS; ++s) tl[s] = (tid + 32 * s / RP_SLOTS * 0 + s * 37) % RP_TT;
-        }
-        const int clm = cl[0];                                       // (COLM: the slots' common column; a thread's first slot is never padding unless all are)
-#ifdef RP_STAMP
-        unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
+        const int clm = cl[0];                                       // the slots' common column (a thread's first slot is never padding unless all are)
         // ---- walk 1: row totals
-        constexpr int NSEG = CHK ? 8 : 1;
-        const int seg_len = CHK ? (((K + RP_KC - 1) / RP_KC + NSEG - 1) / NSEG) * RP_KC : K;     // categories per eighth (whole chunks)
+        constexpr int NSEG = 8;
+        const int seg_len = (((K + RP_KC - 1) / RP_KC + NSEG - 1) / NSEG) * RP_KC;     // categories per eighth (whole chunks)
         double chk[NSEG][RP_SLOTS];
         fetch(0);
 #pragma unroll
@@ -233,18 +188,16 @@ __global__ __launch_bounds__(RP_TH, 4) void k_disc_resample_parents(const double
             for (int s = 0; s < RP_SLOTS; ++s) chk[sg][s] = cum[s];
             const int qb = min(K, (sg + 1) * seg_len);
             for (int q0 = sg * seg_len; q0 < qb; q0 += RP_KC) {
-                RP_ST_A();
+                __syncthreads();
                 stage();
                 __syncthreads();
-                RP_ST_C();
                 if (q0 + RP_KC < K) fetch(q0 + RP_KC);
 #pragma unroll 4
-                for (int kk = 0; kk < (RP_ABL == 1 ? 0 : RP_KC); ++kk) {
+                for (int kk = 0; kk < RP_KC; ++kk) {
                     const double ec = Et[kk][clm];
 #pragma unroll
-                    for (int s = 0; s < RP_SLOTS; ++s) cum[s] = cum[s] + Gt[kk][tl[s]] * (COLM ? ec : Et[kk][cl[s]]);
+                    for (int s = 0; s < RP_SLOTS; ++s) cum[s] = cum[s] + Gt[kk][tl[s]] * ec;
                 }
-                RP_ST_D(0);
             }
         }
         // first thresholds; the baseline category
@@ -265,22 +218,19 @@ __global__ __launch_bounds__(RP_TH, 4) void k_disc_resample_parents(const double
             }
             if (j[s] >= n[s]) thr[s] = __builtin_inf();                      // nothing (left) to place: walk 2 never stops here
         }
-        // (CHK) where a bin's chain is entered: the last eighth whose starting sum has not passed the bin's next threshold
+        // where a bin's chain is entered: the last eighth whose starting sum has not passed the bin's next threshold
         // (sums of non-negative terms: the running sum never decreases, so nothing is placed before that point)
         int from[RP_SLOTS];
 #pragma unroll
         for (int s = 0; s < RP_SLOTS; ++s) {
             from[s] = 0;
-            if (CHK) {
-                int sg1 = 0;
-                double start = chk[0][s];
+            int sg1 = 0;
+            double start = chk[0][s];
 #pragma unroll
-                for (int sg = 1; sg < NSEG; ++sg) { const bool le = chk[sg][s] <= thr[s]; sg1 += le ? 1 : 0; start = le ? chk[sg][s] : start; }
-                if (thr[s] < __builtin_inf()) { cum[s] = start; from[s] = sg1 * seg_len; }
-            }
+            for (int sg = 1; sg < NSEG; ++sg) { const bool le = chk[sg][s] <= thr[s]; sg1 += le ? 1 : 0; start = le ? chk[sg][s] : start; }
+            if (thr[s] < __builtin_inf()) { cum[s] = start; from[s] = sg1 * seg_len; }
         }
-        if (CHK && XCHG && nbins <= RP_TH * RP_SLOTS) {                      // (one round of bins: the list's LDS is free as well)
-            static_assert(!XCHG || RP_SLOTS == 2, "the exchange hands a thread two consecutive places");
+        if (XCHG && nbins <= RP_TH * RP_SLOTS) {                             // (one round of bins: the list's LDS is free as well)
             constexpr int XCAP = RP_TH * RP_SLOTS, XSIDE = 256;
             static_assert(!XCHG || 256 + XCAP * 20 + XSIDE * 24 <= 8 * RP_KC * (RP_TT + RP_CT + 1) + 2 * RP_TT * RP_CT, "exchange buffers fit the kernel's LDS");
             int *xc = reinterpret_cast<int *>(rp_smem);                       // [0..7] bins per eighth, [8] bins with several events left, [9] gave up, [16..24] starts
@@ -336,66 +286,37 @@ __global__ __launch_bounds__(RP_TH, 4) void k_disc_resample_parents(const double
         // ---- walk 2: categories by inverse CDF
         fetch(0);
         for (int q0 = 0; q0 < K; q0 += RP_KC) {
-            RP_ST_A();
+            __syncthreads();
             stage();
             __syncthreads();
-            RP_ST_C();
             if (q0 + RP_KC < K) fetch(q0 + RP_KC);
 #pragma unroll
             for (int s = 0; s < RP_SLOTS; ++s) {
-              if (CHK && !(q0 >= from[s] && thr[s] < __builtin_inf())) continue;
-              if (RP_ABL != 1) {
-                  // The chunk's running sums in straight-line code, its LDS reads in flight together, every partial sum kept.  The
-                  // sums never decrease, so a threshold passed inside the chunk is placed at the first category whose sum exceeds it:
-                  // the number of partial sums at or below it -- compares, not a loop with an LDS round trip per category.  (That
-                  // loop ran in nearly every chunk: 8 waves x 128 bins place an event in one chunk of 256 each, so some wave of the
-                  // workgroup was always in it and the others waited at the barrier: 62 % of walk 2.)
-                  if (!CHK) {                                                  // (every lane in every chunk: the partial sums would spill)
-                      double e0 = cum[s];
+                if (!(q0 >= from[s] && thr[s] < __builtin_inf())) continue;
+                // The chunk's running sums in straight-line code, its LDS reads in flight together, every partial sum kept.  The
+                // sums never decrease, so a threshold passed inside the chunk is placed at the first category whose sum exceeds it:
+                // the number of partial sums at or below it -- compares, not a loop with an LDS round trip per category.  (That
+                // loop ran in nearly every chunk: 8 waves x 128 bins place an event in one chunk of 256 each, so some wave of the
+                // workgroup was always in it and the others waited at the barrier: 62 % of walk 2.)
+                double pre[RP_KC];
+                double e = cum[s];
 #pragma unroll
-                      for (int kk = 0; kk < RP_KC; ++kk) e0 = e0 + Gt[kk][tl[s]] * Et[kk][COLM ? clm : cl[s]];
-                      if (!(e0 > thr[s])) { cum[s] = e0; continue; }
-                      for (int kk = 0; kk < RP_KC; ++kk) {
-                          cum[s] = cum[s] + Gt[kk][tl[s]] * Et[kk][COLM ? clm : cl[s]];
-                          if (cum[s] > thr[s]) {
-                              const int c = c0 + cl[s];
-                              const uint64_t bin = (uint64_t)(t0 + tl[s]) + (uint64_t)T * (uint64_t)c;
-                              do {
-                                  atomicAdd(&counts[(size_t)c + (size_t)N * (1 + q0 + kk)], 1);
-                                  if (++j[s] < n[s]) { u[s] = rp_next_u(u[s], n[s] - j[s], seed, step, bin, j[s]); thr[s] = u[s] * total[s]; }
-                                  else thr[s] = __builtin_inf();
-                              } while (cum[s] > thr[s]);
-                          }
-                      }
-                      continue;
-                  }
-                  double pre[RP_KC];
-                  double e = cum[s];
+                for (int kk = 0; kk < RP_KC; ++kk) { e = e + Gt[kk][tl[s]] * Et[kk][cl[s]]; pre[kk] = e; }
+                if (e > thr[s]) {
+                    const int c = c0 + cl[s];
+                    const uint64_t bin = (uint64_t)(t0 + tl[s]) + (uint64_t)T * (uint64_t)c;
+                    do {
+                        int kx = 0;
 #pragma unroll
-                  for (int kk = 0; kk < RP_KC; ++kk) { e = e + Gt[kk][tl[s]] * Et[kk][cl[s]]; pre[kk] = e; }
-                  if (e > thr[s]) {
-                      const int c = c0 + cl[s];
-                      const uint64_t bin = (uint64_t)(t0 + tl[s]) + (uint64_t)T * (uint64_t)c;
-                      do {
-                          int kx = 0;
-#pragma unroll
-                          for (int kk = 0; kk < RP_KC; ++kk) kx += pre[kk] <= thr[s] ? 1 : 0;
-                          atomicAdd(&counts[(size_t)c + (size_t)N * (1 + q0 + kx)], 1);
-                          if (++j[s] < n[s]) { u[s] = rp_next_u(u[s], n[s] - j[s], seed, step, bin, j[s]); thr[s] = u[s] * total[s]; }
-                          else thr[s] = __builtin_inf();
-                      } while (e > thr[s]);
-                  }
-                  cum[s] = e;
-              }
+                        for (int kk = 0; kk < RP_KC; ++kk) kx += pre[kk] <= thr[s] ? 1 : 0;
+                        atomicAdd(&counts[(size_t)c + (size_t)N * (1 + q0 + kx)], 1);
+                        if (++j[s] < n[s]) { u[s] = rp_next_u(u[s], n[s] - j[s], seed, step, bin, j[s]); thr[s] = u[s] * total[s]; }
+                        else thr[s] = __builtin_inf();
+                    } while (e > thr[s]);
+                }
+                cum[s] = e;
             }
-            RP_ST_D(1);
         }
-#ifdef RP_STAMP
-        if (tid == 0) {
-            const unsigned int wg = blockIdx.x + gridDim.x * blockIdx.y;
-            if (wg < 4096) for (int k = 0; k < 8; ++k) g_rp_stamps[8 * wg + k] = st[k];
-        }
-#endif
 #pragma unroll
         for (int s = 0; s < RP_SLOTS; ++s)                                    // capped at the last category
             if (j[s] < n[s]) atomicAdd(&counts[(size_t)(c0 + cl[s]) + (size_t)N * K], n[s] - j[s]);
@@ -419,44 +340,22 @@ static nhp_status disc_parent_counts(nhp_ctx *ctx, const nhp_disc_dataset *ds, c
     // q / B for q < 2^24 as a multiply-high: exact with magic = floor(2^32 / B) + 1 while q·B < 2^32
     const unsigned b_magic = (unsigned)((((uint64_t)1 << 32) / (uint64_t)ds->B + 1) & 0xFFFFFFFFu);   // unused for B = 1
     if (ds->d_base_counts) NHP_HIP(ctx, hipMemsetAsync(ds->d_base_counts, 0, sizeof(int) * (size_t)ds->T * N, st));
-    // tile (bins x nodes, threads): the larger one halves the staging traffic per occupied bin where the problem fills it;
-    // NHP_RP_TILE = "TT,CT,THREADS" overrides (64,128,256 | 128,128,512 | 128,256,1024), NHP_RP_SLOTS the slots per thread
-    int TT = 64, CT = 128, TH = 256;
-    if (N >= 256 && ds->T >= 128 * 256) { TT = 128; CT = 128; TH = 512; }      // (10.6 ms; 128 x 256 x 1024 11.9, 64 x 128 x 256 12.4)
-    if (const char *ts = getenv("NHP_RP_TILE")) sscanf(ts, "%d,%d,%d", &TT, &CT, &TH);
-    if (!((TT == 64 && CT == 128 && TH == 256) || (TT == 128 && CT == 128 && TH == 512) || (TT == 128 && CT == 256 && TH == 1024))) { TT = 64; CT = 128; TH = 256; }
+    // tile (bins x nodes, threads): the larger one halves the staging traffic per occupied bin where the problem fills it
+    const bool large = N >= 256 && ds->T >= 128 * 256;                           // (10.6 ms; 128 x 256 x 1024 11.9, 64 x 128 x 256 12.4)
+    const int TT = large ? 128 : 64, CT = 128, TH = large ? 512 : 256;
     const int ntx = (int)((ds->T + TT - 1) / TT), ncy = (int)((N + CT - 1) / CT);
-    const int xcd_env = getenv("NHP_RP_XCD") ? atoi(getenv("NHP_RP_XCD")) : 1;
-    const int xcd_ncy = xcd_env && ncy > 1 ? ncy : 0;
+    const int xcd_ncy = ncy > 1 ? ncy : 0;                                        // several node tiles: a 1-D grid in XCD order
     dim3 grid(xcd_ncy ? (unsigned)(((ntx + 7) / 8) * 8 * ncy) : (unsigned)ntx, xcd_ncy ? 1u : (unsigned)ncy);
     // occupied bins of a tile: the mean plus three standard deviations (a tile that overflows its slots walks twice)
     const double mean = (double)ds->nocc * (double)(TT * CT) / ((double)ds->T * (double)std::max<size_t>(N, (size_t)CT));
-    // column-major list (slots of a thread share their node): every column of the tile is padded to a multiple of the slots
-    const int colm_env = getenv("NHP_RP_COLM") ? atoi(getenv("NHP_RP_COLM")) : 1;
-    const bool colm = colm_env != 0 && TT >= 64 && (TT * CT / (TH / 64)) % TT == 0;
-    const char *fs = getenv("NHP_RP_SLOTS");
-    auto need_for = [&](int sl) { return mean + 3.0 * sqrt(mean) + (colm ? 0.5 * (sl - 1) * CT : 0.0); };
-    // (four bins a thread measured 17-35 ms against 9-12 with two and a second round over the tile's list: only by request)
-    const int slots = fs ? atoi(fs) : (need_for(1) <= 1.0 * TH ? 1 : 2);
+    // (four bins a thread measured 17-35 ms against 9-12 with two and a second round over the tile's list)
+    const int slots = mean + 3.0 * sqrt(mean) <= 1.0 * TH ? 1 : 2;
     const size_t lds = 8 * (size_t)RP_KC * (size_t)(TT + CT + 1) + 2 * (size_t)TT * CT;      // (a list of 2048 entries instead: no more workgroups per CU -- 128 registers)
-#define RP_LAUNCH(S, tt, ct, th, cm, ck, xg)                                                                                      \
-    do {                                                                                                                          \
-        if (lds > 64 * 1024)                                                                                                      \
-            (void)hipFuncSetAttribute((const void *)k_disc_resample_parents<S, tt, ct, th, cm, ck, xg>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_disc_resample_parents<S, tt, ct, th, cm, ck, xg>), grid, dim3(th), lds, st, ds->d_dataT, ds->d_conv, E2, base, \
-                           lambda0 ? nullptr : ds->d_baseT, ds->T, ds->N, ds->B, b_magic, seed, step, d_counts, ds->d_base_counts, xcd_ncy); \
-    } while (0)
-#define RP_SL(tt, ct, th, cm, ck) do { if (slots == 1) RP_LAUNCH(1, tt, ct, th, cm, ck, false); else if (slots == 2) { if (ck && xchg) RP_LAUNCH(2, tt, ct, th, cm, ck, ck); else RP_LAUNCH(2, tt, ct, th, cm, ck, false); } else RP_LAUNCH(4, tt, ct, th, cm, ck, false); } while (0)
-#define RP_CK(tt, ct, th, cm) do { if (chk) RP_SL(tt, ct, th, cm, true); else RP_SL(tt, ct, th, cm, false); } while (0)
-#define RP_TILE(tt, ct, th) do { if (colm) RP_CK(tt, ct, th, true); else RP_CK(tt, ct, th, false); } while (0)
-    const int chk_env = getenv("NHP_RP_CHK") ? atoi(getenv("NHP_RP_CHK")) : 1;
-    const bool chk = chk_env != 0;
-    const bool xchg = !(getenv("NHP_RP_XCHG") && atoi(getenv("NHP_RP_XCHG")) == 0);
-    if (TT == 64) RP_TILE(64, 128, 256); else if (CT == 128) RP_TILE(128, 128, 512); else RP_TILE(128, 256, 1024);
-#undef RP_CK
-#undef RP_TILE
-#undef RP_SL
-#undef RP_LAUNCH
+    const auto kern = large ? (slots == 1 ? k_disc_resample_parents<1, 128, 128, 512> : k_disc_resample_parents<2, 128, 128, 512>)
+                            : (slots == 1 ? k_disc_resample_parents<1, 64, 128, 256> : k_disc_resample_parents<2, 64, 128, 256>);
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kern, grid, dim3(TH), lds, st, ds->d_dataT, ds->d_conv, E2, base, lambda0 ? nullptr : ds->d_baseT, ds->T, ds->N,
+                       ds->B, b_magic, seed, step, d_counts, ds->d_base_counts, xcd_ncy);
     if (ds->d_base_counts) const_cast<nhp_disc_dataset *>(ds)->base_counts_valid = true;
     NHP_HIP(ctx, hipGetLastError());
     *d_counts_out = d_counts;
@@ -614,12 +513,8 @@ __global__ __launch_bounds__(256) void k_dadj_tables(int N, int B, double dt, co
     SX[row] = sx;
 }
 
-#ifndef NHP_DA_GROUP
-#define NHP_DA_GROUP 16     // workgroups whose rows one of them adds; the next launch reads nspans / GROUP rows (4: 23.1, 8: 22.6, 16: 22.5, 32: 24.2 ms per sweep)
-#endif
-#ifndef DADJ_ABL
-#define DADJ_ABL 0      // (timing ablations: wrong results)
-#endif
+constexpr int NHP_DA_GROUP = 16;    // workgroups whose rows one of them adds; the next launch reads nspans / GROUP rows (4: 23.1, 8: 22.6, 16: 22.5, 32: 24.2 ms per sweep)
+constexpr int DADJ_TH = 512;        // threads of a k_dadj_step workgroup (1024 threads: 64 registers each -- the loop spills, 47 ms against 25)
 template <int BT>
 __device__ __forceinline__ double dadj_x(const double *__restrict__ G, int tt, const double *__restrict__ v, int B)
 {
@@ -665,7 +560,6 @@ struct nhp_dadj_args {
     double *partial, *gpartial;          // [workgroups][N], [3][N]: step p's sums in row p mod 3
     unsigned int *tick;                  // [groups] words 32 apart
     double *A;
-    unsigned long long *stamps;          // (DADJ_STAMP builds: 8 per workgroup)
 };
 
 // λ of the occupied bins under the current adjacency matrix -- the sweep's starting point -- without the T x N intensity GEMM
@@ -772,14 +666,10 @@ __global__ __launch_bounds__(TH, TH / 128) void k_dadj_lambda0(nhp_dadj_args a, 
     }
 }
 
-#ifdef DADJ_STAMP
-#define DADJ_ST(k) do { if (tid == 0 && a.stamps) a.stamps[8 * (size_t)blockIdx.x + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define DADJ_ST(k) do { } while (0)
-#endif
-template <int BT, bool PACK, bool VLDS, int TH>
-__global__ __launch_bounds__(TH, TH / 128) void k_dadj_step(int p, nhp_dadj_args a)
+template <int BT, bool PACK, bool VLDS>
+__global__ __launch_bounds__(DADJ_TH, DADJ_TH / 128) void k_dadj_step(int p, nhp_dadj_args a)
 {
+    constexpr int TH = DADJ_TH;
     extern __shared__ __align__(16) double dsm[];
     const int N = a.N, B = BT > 0 ? BT : a.B, tid = threadIdx.x;
     double *Gt = dsm;                                       // [B][SPAN]
@@ -788,7 +678,6 @@ __global__ __launch_bounds__(TH, TH / 128) void k_dadj_step(int p, nhp_dadj_args
     double *apl = acc + N, *dpl = apl + N;                  // [N] each
     double *Vl = dpl + N;                                   // [N·B] (VLDS)
     __shared__ int flag;
-    DADJ_ST(0);
     const int64_t t0 = a.span_t[blockIdx.x];
     const int span = a.span_t[blockIdx.x + 1] - (int)t0;    // <= SPAN
     const double *Vc = a.Vall + (size_t)p * N * B, *Vp = a.Vall + (size_t)(p > 0 ? p - 1 : 0) * N * B;
@@ -796,14 +685,14 @@ __global__ __launch_bounds__(TH, TH / 128) void k_dadj_step(int p, nhp_dadj_args
     // DADJ_PRE groups of four are requested while the tables are staged.
     const int i0 = a.occ_off[blockIdx.x], i1 = a.occ_off[blockIdx.x + 1];          // (multiples of 4: the spans are padded)
     const int per = ((i1 - i0 + 4 * TH - 1) / (4 * TH)) * 4;
-    const int mine = i0 + tid * per, mend = DADJ_ABL == 1 ? mine : min(mine + per, i1);
+    const int mine = i0 + tid * per, mend = min(mine + per, i1);
     constexpr int DADJ_PRE = 3;
     uint4 pre_w[DADJ_PRE];
     double2 pre_a[DADJ_PRE], pre_b[DADJ_PRE];
     // ---- row p - 1 is decided here, by every workgroup for itself (the group rows of step p - 1 are 128 KB out of L2: cheaper
     //      than a second ticket and a deciding workgroup at the end of that launch with everybody else gone); workgroup 0
     //      writes A.  Launch p = N does only this.
-    const unsigned int nwg = a.nspans, grp = blockIdx.x / NHP_DA_GROUP, ngrp = (nwg + NHP_DA_GROUP - 1) / NHP_DA_GROUP;
+    const unsigned int nwg = a.nspans, grp = blockIdx.x / NHP_DA_GROUP;
     const unsigned int gfirst = grp * NHP_DA_GROUP, gsize = min((unsigned int)NHP_DA_GROUP, nwg - gfirst);
     auto decide = [&]() __attribute__((always_inline)) {
         // (the group rows of step p - 1 were added into ONE row by their groups' last workgroups: 4 KB to read here, not 128)
@@ -839,7 +728,7 @@ __global__ __launch_bounds__(TH, TH / 128) void k_dadj_step(int p, nhp_dadj_args
             const int c = tid + TH * r;
             ra[r] = c < N ? a.AT[(size_t)p * N + c] : 0.0;
         }
-        if (VLDS && DADJ_ABL != 4) {
+        if (VLDS) {
             if ((N * B) % 2 == 0) {
                 const double2 *src = reinterpret_cast<const double2 *>(Vc);
                 double2 *dst = reinterpret_cast<double2 *>(Vl);
@@ -879,7 +768,6 @@ __global__ __launch_bounds__(TH, TH / 128) void k_dadj_step(int p, nhp_dadj_args
             Gp[e] = tt < span && t < a.T ? a.conv[(size_t)t + (size_t)a.T * ((size_t)(p - 1) + (size_t)N * b)] : 0.0;
         }
     __syncthreads();
-    DADJ_ST(1);
     const double *Vx = VLDS ? Vl : Vc;
     const int tb = (int)(t0 % NHP_DA_SPAN);
     // The entries are sorted by node, so a thread's entries mostly share their column: row c of V, a_p[c], dprev[c] are read
@@ -891,7 +779,7 @@ __global__ __launch_bounds__(TH, TH / 128) void k_dadj_step(int p, nhp_dadj_args
     auto entry = [&](int idx, int c, int tt, double sv, double lam) __attribute__((always_inline)) {
         if (c != c_cur) {
             if (c_cur >= 0 && run != 0.0) atomicAdd(&acc[c_cur], run);
-            c_cur = c; run = 0.0; apc = apl[c]; dpc = DADJ_ABL == 7 ? 0.0 : dpl[c];
+            c_cur = c; run = 0.0; apc = apl[c]; dpc = dpl[c];
             vrow = Vx + (size_t)c * B; vprow = Vp + (size_t)c * B;
             if (BT > 0) {
 #pragma unroll
@@ -909,9 +797,7 @@ __global__ __launch_bounds__(TH, TH / 128) void k_dadj_step(int p, nhp_dadj_args
         const double x = BT > 0 ? dadj_x<BT>(Gt, tt, v, B) : dadj_x<BT>(Gt, tt, vrow, B);
         if (x > 0.0) {
             const double l0 = lam - apc * x;
-            if (DADJ_ABL == 2) run += sv * l0;
-            else if (DADJ_ABL == 6) run += sv * (nhp_log(l0 + x) - nhp_log(l0));
-            else run += sv * dadj_logratio(l0, x);
+            run += sv * dadj_logratio(l0, x);
         }
     };
     auto packed4 = [&](int base, const uint4 q, const double2 la, const double2 lb) __attribute__((always_inline)) {
@@ -935,17 +821,14 @@ __global__ __launch_bounds__(TH, TH / 128) void k_dadj_step(int p, nhp_dadj_args
     }
     if (c_cur >= 0 && run != 0.0) atomicAdd(&acc[c_cur], run);
     __syncthreads();
-    DADJ_ST(2);
     // ---- tail: this workgroup's row; the last workgroup of each group adds its group's rows (fixed order; every row requested
     //      before the first is used: a serial `sum += load` is one L2 round trip per row)
     for (int c = tid; c < N; c += TH)
         __hip_atomic_store(&a.partial[(size_t)blockIdx.x * N + c], acc[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    DADJ_ST(3);
     if (tid == 0) flag = __hip_atomic_fetch_add(&a.tick[32 * grp], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsize - 1;
     __syncthreads();
-    DADJ_ST(4);
     if (!flag) return;
     double *gout = a.gpartial + (size_t)(p % 3) * N;
     for (int c = tid; c < N; c += TH) {
@@ -961,7 +844,14 @@ __global__ __launch_bounds__(TH, TH / 128) void k_dadj_step(int p, nhp_dadj_args
         atomicAdd(&gout[c], sum);                                   // (the row the next launch reads; zeroed two launches ago)
     }
     if (tid == 0) __hip_atomic_store(&a.tick[32 * grp], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    DADJ_ST(5);
+}
+
+// the step kernel for packed or unpacked entries, with V's rows in LDS or read from global memory
+template <int BT>
+static void (*dadj_step_kernel(bool pack, bool vlds))(int, nhp_dadj_args)
+{
+    return pack ? (vlds ? k_dadj_step<BT, true, true> : k_dadj_step<BT, true, false>)
+                : (vlds ? k_dadj_step<BT, false, true> : k_dadj_step<BT, false, false>);
 }
 
 // (A cooperative launch holding every workgroup for all N steps -- entries and λ in registers, the decision announced through
@@ -980,9 +870,6 @@ extern "C" nhp_status nhp_disc_resample_adjacency(nhp_ctx *ctx, const nhp_disc_d
     const size_t N = (size_t)ds->N, NN = N * N, B = (size_t)ds->B, TN = (size_t)ds->T * N;
     const size_t nocc = (size_t)(ds->nocc_pad > 0 ? ds->nocc_pad : 4);
     const int nwg = ds->da_nspans;                                     // the spans were cut when the dataset was made (NHP_DADJ_SPANS)
-    int th = 512;                                                      // (1024 threads: 64 registers each -- the loop spills, 47 ms against 25)
-    if (const char *cs = getenv("NHP_DADJ_THREADS")) th = atoi(cs);
-    if (th != 256 && th != 1024) th = 512;
     const int ngrp = (nwg + NHP_DA_GROUP - 1) / NHP_DA_GROUP;
     const size_t gsz = std::max<size_t>(2 * B * (size_t)NHP_DA_SPAN, std::max<size_t>(N, 1024));
     const size_t lds_base = 8 * (gsz + 3 * N), lds_v = 8 * N * B;
@@ -1049,41 +936,11 @@ extern "C" nhp_status nhp_disc_resample_adjacency(nhp_ctx *ctx, const nhp_disc_d
         }
         NHP_HIP(ctx, hipGetLastError());
     }
-#ifdef DADJ_STAMP
-    unsigned long long *d_st = nullptr;
-    const int st_step = getenv("NHP_DADJ_STAMP_STEP") ? atoi(getenv("NHP_DADJ_STAMP_STEP")) : 100;
-    if (getenv("NHP_DADJ_STAMPS") && hipMalloc((void **)&d_st, 64 * (size_t)nwg) == hipSuccess) (void)hipMemsetAsync(d_st, 0, 64 * (size_t)nwg, st);
-#define DADJ_STAMP_ARG a.stamps = (p == st_step ? d_st : nullptr)
-#else
-#define DADJ_STAMP_ARG (void)0
-#endif
-#define DADJ_GO(BT, PK, VL, TH_)                                                                                                    \
-    do {                                                                                                                           \
-        if (lds > 64 * 1024)                                                                                                       \
-            (void)hipFuncSetAttribute((const void *)k_dadj_step<BT, PK, VL, TH_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        for (int p = 0; p <= ds->N; ++p) {                         /* launch N: the last row's decision alone */                  \
-            DADJ_STAMP_ARG;                                                                                                        \
-            hipLaunchKernelGGL((k_dadj_step<BT, PK, VL, TH_>), dim3(p < ds->N ? (unsigned)nwg : 1u), dim3(TH_), lds, st, p, a);    \
-        }                                                                                                                          \
-    } while (0)
-#define DADJ_TH(BT, PK, VL) do { if (th == 256) DADJ_GO(BT, PK, VL, 256); else if (th == 512) DADJ_GO(BT, PK, VL, 512); else DADJ_GO(BT, PK, VL, 1024); } while (0)
-#define DADJ_V(BT, PK) do { if (vlds) DADJ_TH(BT, PK, true); else DADJ_TH(BT, PK, false); } while (0)
-    const bool pk = ds->d_occ_pack != nullptr;
-    if (ds->B == 8) { if (pk) DADJ_V(8, true); else DADJ_V(8, false); }
-    else if (ds->B == 4) { if (pk) DADJ_V(4, true); else DADJ_V(4, false); }
-    else { if (pk) DADJ_V(0, true); else DADJ_V(0, false); }
-#undef DADJ_V
-#undef DADJ_TH
-#undef DADJ_GO
-#ifdef DADJ_STAMP
-    if (d_st) {
-        std::vector<unsigned long long> h(8 * (size_t)nwg);
-        (void)hipMemcpyAsync(h.data(), d_st, 64 * (size_t)nwg, hipMemcpyDeviceToHost, st);
-        (void)hipStreamSynchronize(st);
-        if (FILE *f = fopen(getenv("NHP_DADJ_STAMPS"), "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-        (void)hipFree(d_st);
-    }
-#endif
+    const bool pk = ds->d_occ_pack != nullptr;                         // (B = 8 and 4 compiled in, any other B at run time)
+    const auto kern = ds->B == 8 ? dadj_step_kernel<8>(pk, vlds) : ds->B == 4 ? dadj_step_kernel<4>(pk, vlds) : dadj_step_kernel<0>(pk, vlds);
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    for (int p = 0; p <= ds->N; ++p)                                   // launch N: the last row's decision alone
+        hipLaunchKernelGGL(kern, dim3(p < ds->N ? (unsigned)nwg : 1u), dim3(DADJ_TH), lds, st, p, a);
     NHP_HIP(ctx, hipGetLastError());
     NHP_HIP(ctx, hipMemcpyAsync(A, dA, 8 * NN, hipMemcpyDeviceToHost, st));
     NHP_HIP(ctx, hipStreamSynchronize(st));

@@ -252,6 +252,39 @@ nhp_status nhp_cont_resample_adjacency(nhp_ctx *ctx, const nhp_cont_dataset *ds,
  * outside [grid_x[0], grid_x[end]] (the interpolator's DomainError, src/utils/interpolation.jl:27). */
 nhp_status nhp_cont_lgcp_loglik(nhp_ctx *ctx, const nhp_cont_dataset *ds, const int64_t *parentnodes,
                                 const double *grid_x, int32_t grid_n, const double *lam, double *ll);
+/* rand(process, duration)  src/continuous.jl:16-48,131-142,335-348 on the device, from the device-resident model (so a
+ * posterior-predictive draw from the state nhp_cont_mcmc_run leaves needs no download).  Generation-wise branching:
+ * Poisson immigrants per node (homogeneous: Poisson(λ0_c T) at uniform positions on [0, T); LGCP: Poisson(trapezoid ∫λ_c)
+ * positions by rejection from the piecewise-linear λ_c, src/baselines.jl:190-210), then Poisson(R_p) children per event,
+ * R_p = Σ_c W[p,c]·A[p,c], child node c with probability W[p,c]·A[p,c] / R_p, delay Exp(θ[p,c]) (not cut at dt_max,
+ * src/impulses.jl:53-66) or dt_max·logistic(μ[p,c] + Z/√τ[p,c]) (src/impulses.jl:180-202); events after `duration`
+ * are dropped with their descendants.
+ * Outputs: buffers of capacity max_events, host or device pointers by output_on_device (as input_on_device of
+ * nhp_cont_dataset_create_device); times ascending, nodes 1-based, parents (nullable) 0 for a baseline event, else the
+ * 1-based index of the parent in the returned order (a parent precedes its children).  Synchronous: the ctx stream is
+ * drained before the call returns.  Errors: NHP_EDOMAIN for a negative / non-finite duration, an LGCP duration other than
+ * the grid's end ("Sample duration does not match process duration.", src/baselines.jl:191), or parameters no process
+ * has (negative / non-finite weights or baseline, θ <= 0 or τ <= 0 on a link with weight, a row total W·A above 2^32);
+ * NHP_EINVAL for null pointers or max_events outside [0, 2^31); NHP_ENOMEM "branching process exploded (unstable
+ * weights?)" when the kept events pass max_events (nothing is written past the buffers; the ctx stays usable).
+ * The result depends on (model, duration, seed) only -- not on max_events or launch geometry.  Random numbers: the
+ * Philox4x32-10 block of nhp_rng.h, counter (c0, c1, c2, c3) = (e mod 2^32, (e >> 32) ^ (attempt << 8), step mod 2^32,
+ * step >> 32), key = seed ^ F for a family constant F, ten rounds; of the four output words, ua = (((w0:w1) >> 11) + 1)·2^-53
+ * and ub = (((w2:w3) >> 11) + 1)·2^-53 lie in (0, 1], u = ua - 2^-53 in [0, 1).  Poisson(m): m <= 0 -> 0; m < 10 inversion
+ * with u of attempt 0 (p = e^-m, F = p, k = 0; while u >= F and k < 100: k += 1, p = p·m/k, F += p); m >= 10 PTRS (Hörmann
+ * 1993) with U = u - 0.5 and V = ub of attempt 0, 1, 2, ...  Families, in draw order:
+ *   0x9E3779B97F4A7C15  immigrant count of node c:  Poisson(λ0_c T | ∫λ_c), step 0, e = c
+ *   0xBF58476D1CE4E5B9  immigrant k (immigrants numbered node by node): step 0, e = k; t = u·T (attempt 0); LGCP: attempt
+ *                       a = 0, 1, ... until ub·max λ_c <= λ_c(t)
+ *   0x94D049BB133111EB  child count of event i: Poisson(R_node), step = generation of i (immigrants 0), e = arena index i
+ *   0xD6E8FEB86659FD93  child slot s of generation g (slots numbered by parent arena index, then child): step g, e = s;
+ *                       attempt 0: node = first c with prefix_p[c] > u·R_p (sequential row prefix of W∘A; if none, the first
+ *                       prefix_p[c] >= u·R_p), exponential delay -log(ub)/θ; attempt 1: Z = sqrt(-2 log ua)·cos(2π w2/2^32)
+ * The arena holds the immigrants (index k), then each generation's surviving children in slot order.  Output order: a
+ * stable sort of the arena by time. */
+nhp_status nhp_cont_simulate(nhp_ctx *ctx, const nhp_cont_model *model, double duration, uint64_t seed, int64_t max_events,
+                             int32_t output_on_device, double *times, int64_t *nodes, int64_t *parents /* nullable */,
+                             int64_t *n_events);
 /* params(process) of the device-resident model: [λ0; θ | μ; τ; W]  src/continuous.jl:116-119 */
 nhp_status nhp_cont_model_get_params(nhp_ctx *ctx, const nhp_cont_model *model, double *x, int64_t len);
 /* process.adjacency_matrix of the device-resident model (after nhp_cont_network_step / nhp_cont_mcmc_run): [N*N] 0.0/1.0 */

@@ -104,6 +104,27 @@ class DeviceModel:
         x = _lib.f64(x)
         _lib.check(_lib.lib().nhp_cont_model_set_params(self.ctx.h, self.h, _lib.dptr(x), len(x)), self.ctx.h)
 
+    def simulate(self, duration, seed=0, max_events=5_000_000, return_parents=False):
+        """rand(process, duration) from the parameters this handle holds on the device (nhp_cont_simulate): (times, nodes,
+        duration), float64 / int64 torch tensors on the context's device, with `parents` (0 = baseline event, else the
+        1-based index of the parent) appended when return_parents.  More than max_events kept events raise RuntimeError."""
+        import torch
+        duration, max_events = float(duration), int(max_events)
+        if not 0 <= max_events < 2 ** 31:
+            raise ValueError(f"max_events = {max_events} outside [0, 2^31)")
+        dev = torch.device("cuda", self.ctx.device)
+        cap = max(max_events, 1)
+        t = torch.empty(cap, dtype=torch.float64, device=dev)
+        nd = torch.empty(cap, dtype=torch.int64, device=dev)
+        par = torch.empty(cap, dtype=torch.int64, device=dev) if return_parents else None
+        torch.cuda.current_stream(dev).synchronize()          # earlier users of the buffers' memory are done before the library writes
+        n = C.c_int64()
+        _lib.check(_lib.lib().nhp_cont_simulate(self.ctx.h, self.h, duration, int(seed) & (2 ** 64 - 1), max_events, 1, t.data_ptr(),
+                                                nd.data_ptr(), par.data_ptr() if return_parents else None, C.byref(n)), self.ctx.h)
+        k = n.value
+        out = (t[:k].clone(), nd[:k].clone(), duration)
+        return out + (par[:k].clone(),) if return_parents else out
+
 
 _CHILD = np.dtype([("t", np.float64), ("first", np.int32), ("idx", np.int32)])
 # nhp_cont_dataset_export: name -> (NHP_DS_* id, element type)

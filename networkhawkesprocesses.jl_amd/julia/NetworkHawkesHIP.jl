@@ -196,6 +196,21 @@ function resample_parents(p::NHP.ContinuousHawkesProcess, data; seed::UInt64=UIn
     stats ? (parents, parentnodes, (cnt0=cnt0, Mn=Mn, Mnm=Mnm, Xnm=Xnm, Vnm=Vnm)) : (parents, parentnodes)
 end
 
+# --- rand(process, duration) -> (events, nodes, duration)  src/continuous.jl:16-48,131-142,335-348 ---------------------
+# The GPU generator (Philox-keyed by `seed`: same law as the package's rand, not Julia's random stream).  device=false
+# defers to the package's own rand.  More than max_events kept events: ErrorException "branching process exploded".
+function rand(p::NHP.ContinuousHawkesProcess, duration::Float64; device::Bool=true, seed::Integer=0,
+              max_events::Integer=5_000_000, ctx=context())
+    device || return NHP.rand(p, duration)
+    times, nodes, n = Vector{Float64}(undef, max(max_events, 1)), Vector{Int64}(undef, max(max_events, 1)), Ref{Int64}(0)
+    with_model(ctx, p) do m
+        check(ccall((:nhp_cont_simulate, libnhp), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Float64, UInt64, Int64, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ref{Int64}),
+                    ctx.h, m, duration, seed % UInt64, max_events, Int32(0), times, nodes, C_NULL, n), ctx.h)
+    end
+    times[1:n[]], nodes[1:n[]], duration
+end
+
 # --- objective + analytic gradient of mle!  src/continuous.jl:144-198 -------------------------------------------------
 function loglikelihood_gradient(p::NHP.ContinuousStandardHawkesProcess, data; recursive=true, ctx=context(), comm=nothing,
                                 ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))

@@ -203,9 +203,23 @@ def rand_discrete(process, duration, seed=0):
     return data
 
 
-def rand(process, duration, seed=0):
-    """rand(process, duration): simulate data from a continuous or a discrete process."""
+def rand(process, duration, seed=0, *, device=False, ctx=None, max_events=5_000_000, return_parents=False):
+    """rand(process, duration): simulate data from a continuous or a discrete process.
+
+    device=False: the host simulators above (numpy PCG64).  device=True (continuous processes): the GPU generator
+    (nhp_cont_simulate) run on process.device_model(ctx); returns (times, nodes, duration) as float64 / int64 torch
+    tensors on the context's device -- with `parents` appended when return_parents=True (0 = baseline event, else the
+    1-based index of the parent event) -- which loglikelihood, device_dataset, mle_ and mcmc_ take on their device route.
+    The two routes draw from different generators (numpy PCG64 here, counter-based Philox on the device) with the same
+    law: host and device samples for one seed differ, and neither reproduces Julia's random stream.  More than
+    `max_events` kept events raise RuntimeError ("branching process exploded") on both routes."""
     from .discrete import DiscreteHawkesProcess
+    if return_parents and not device:
+        raise ValueError("return_parents=True needs device=True: the host simulators do not record parents")
     if isinstance(process, DiscreteHawkesProcess):
+        if device:
+            raise NotImplementedError("rand(process, duration; device=True) simulates continuous processes only")
         return rand_discrete(process, duration, seed)
-    return rand_continuous(process, duration, seed)
+    if device:
+        return process.device_model(ctx).simulate(duration, seed, max_events=max_events, return_parents=return_parents)
+    return rand_continuous(process, duration, seed, max_events=max_events)

@@ -285,6 +285,28 @@ nhp_status nhp_cont_lgcp_loglik(nhp_ctx *ctx, const nhp_cont_dataset *ds, const 
 nhp_status nhp_cont_simulate(nhp_ctx *ctx, const nhp_cont_model *model, double duration, uint64_t seed, int64_t max_events,
                              int32_t output_on_device, double *times, int64_t *nodes, int64_t *parents /* nullable */,
                              int64_t *n_events);
+/* The compensator Λ_c(t) = ∫ λ_c(s) ds from 0 (LGCP baseline: from grid_x[0]) to t, exactly, of the intensity as
+ * nhp_cont_intensity evaluates it (src/continuous.jl:84-96) -- the reference has no such function: its log-likelihood
+ * charges every event the full mass ΣW ("approximate (exact requires cdf)", src/continuous.jl:247).  Conventions of the
+ * intensity, literally: parents of time t are the events with t - dt_max < t_i < t (both strict); link weight W[p,c]
+ * (times A[p,c]); the exponential impulse θ e^{-θd} is cut at dt_max and not renormalised; the logit-normal pdf at
+ * x = d/dt_max is NOT divided by dt_max, so a link's total mass is W·dt_max; homogeneous baseline λ0_c; LGCP baseline = the
+ * piecewise-linear interpolant of (grid_x, λ_c), integrated exactly (a trapezoid per cell, a partial last cell).  With
+ *   H_{p,c}(d) = ∫_0^{min(d,dt_max)} pdf_{p,c} = 1 - e^{-θ min(d,dt_max)}                     (exponential)
+ *                                             = dt_max·Φ(√τ (logit(d/dt_max) - μ)) for d < dt_max, dt_max from there on   (logit-normal)
+ *   Λ_c(t) = base_c(t) + Σ_{i: t_i < t} W[n_i,c]·A[n_i,c]·H_{n_i,c}(t - t_i).
+ * Outputs (each nullable, not all three), events in the caller's (time) order:
+ *   at_events[k] = Λ_{n_k}(t_k), the compensator of the event's own node at the event;
+ *   residuals[k] = Λ_{n_k}(t_k) - Λ_{n_k}(t_prev), t_prev the previous event of the same node (the lower limit for the
+ *                  node's first event): i.i.d. Exp(1) under the true model (time rescaling);
+ *   total[c]     = Λ_c(duration): the expected number of events of node c.
+ * Host or device pointers by output_on_device (as in nhp_cont_simulate).  Synchronous; fp64 sums in a fixed order, so the
+ * results are identical from run to run.  Errors: NHP_EINVAL (null handles, no output requested), the dataset / model
+ * mismatches of the other entry points, NHP_EDOMAIN (an event or the duration outside the LGCP grid), NHP_ENOTIMPL on a
+ * column shard and when a node's columns of the parameter tables exceed the 160 KiB of LDS. */
+nhp_status nhp_cont_compensator(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *model,
+                                int32_t output_on_device, double *at_events /* [M] nullable */,
+                                double *residuals /* [M] nullable */, double *total /* [N] nullable */);
 /* params(process) of the device-resident model: [λ0; θ | μ; τ; W]  src/continuous.jl:116-119 */
 nhp_status nhp_cont_model_get_params(nhp_ctx *ctx, const nhp_cont_model *model, double *x, int64_t len);
 /* process.adjacency_matrix of the device-resident model (after nhp_cont_network_step / nhp_cont_mcmc_run): [N*N] 0.0/1.0 */

@@ -10,9 +10,9 @@ from .components import (BernoulliNetworkModel, DenseNetworkModel, DenseWeightMo
                          ExponentialImpulseResponse, GaussianProcess, HomogeneousProcess,
                          LogGaussianCoxProcess, LogitNormalImpulseResponse, OrnsteinUhlenbeckKernel,
                          PeriodicKernel, SquaredExponentialKernel, split_extract)
-from .continuous import (ContinuousHawkesProcess, ContinuousNetworkHawkesProcess,  # noqa: F401
-                         ContinuousStandardHawkesProcess, DeviceDataset, HawkesProcess, device_dataset,
-                         invalidate_device_datasets, total_intensity)
+from .continuous import (Compensator, ContinuousHawkesProcess, ContinuousNetworkHawkesProcess,  # noqa: F401
+                         ContinuousStandardHawkesProcess, DeviceDataset, HawkesProcess, TimeRescalingTest, compensator,
+                         device_dataset, invalidate_device_datasets, time_rescaling_test, total_intensity)
 from . import continuous as _cont
 from .discrete import (DiscreteDataset, DiscreteGaussianImpulseResponse, DiscreteHawkesProcess,  # noqa: F401
                        DiscreteHomogeneousProcess, DiscreteLogGaussianCoxProcess, DiscreteNetworkHawkesProcess,

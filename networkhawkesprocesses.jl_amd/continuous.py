@@ -407,3 +407,124 @@ def loglikelihood_gradient(process, data, recursive=True, ctx=None, model=None):
     _lib.check(_lib.lib().nhp_cont_loglik_grad(ctx.h, ds.h, model.h, _check_recursive(process, recursive),
                                                C.byref(ll), _lib.dptr(g), P), ctx.h)
     return ll.value, g
+
+
+class Compensator:
+    """Result of compensator(): at_events [M] and residuals [M] in the order of the events, total [N] (numpy arrays, or
+    float64 torch tensors on the context's device)."""
+
+    def __init__(self, at_events, residuals, total):
+        self.at_events, self.residuals, self.total = at_events, residuals, total
+
+    def __iter__(self):
+        return iter((self.at_events, self.residuals, self.total))
+
+    def __repr__(self):
+        return f"Compensator(events={len(self.at_events)}, nodes={len(self.total)})"
+
+
+def _continuous_only(process, what):
+    if not isinstance(process, ContinuousHawkesProcess):
+        raise TypeError(f"{what} takes a ContinuousStandardHawkesProcess or a ContinuousNetworkHawkesProcess, "
+                        f"not {type(process).__name__}")
+
+
+def compensator(process, data, ctx=None, model=None, device=False):
+    """The exact compensator Λ_c(t) = ∫₀ᵗ λ_c(s) ds of the intensity that intensity(process, data, t) evaluates
+    (src/continuous.jl:84-96; strict window, cut exponential, logit-normal pdf not divided by Δtmax), nhp_cont_compensator:
+
+        at_events[k] = Λ_{n_k}(t_k);  residuals[k] = Λ_{n_k}(t_k) - Λ_{n_k}(previous event of node n_k)  (Exp(1) under the
+        true model: time rescaling);  total[c] = Λ_c(duration), the expected number of events of node c.
+
+    device=False: numpy arrays.  device=True: float64 torch tensors on the context's device -- with `data` as device
+    tensors (rand(..., device=True)) no event crosses to the host.  `model`: a device-resident model to evaluate as is."""
+    from .sharded import ShardedDataset
+    _continuous_only(process, "compensator")
+    if isinstance(data, ShardedDataset):
+        raise NotImplementedError("compensator: not available on a column shard (sharded.ShardedDataset)")
+    ctx = ctx or _lib.default_context()
+    ds = device_dataset(process, data, ctx)
+    model = model or process.device_model(ctx)
+    M, N = len(ds), process.ndims()
+    fn = _lib.lib().nhp_cont_compensator
+    if device:
+        import torch
+        dev = torch.device("cuda", ctx.device)
+        at, res, tot = (torch.empty(n, dtype=torch.float64, device=dev) for n in (M, M, N))
+        torch.cuda.current_stream(dev).synchronize()          # earlier users of the buffers' memory are done before the library writes
+        _lib.check(fn(ctx.h, ds.h, model.h, 1, at.data_ptr(), res.data_ptr(), tot.data_ptr()), ctx.h)
+    else:
+        at, res, tot = np.empty(M), np.empty(M), np.empty(N)
+        _lib.check(fn(ctx.h, ds.h, model.h, 0, at.ctypes.data, res.ctypes.data, tot.ctypes.data), ctx.h)
+    return Compensator(at, res, tot)
+
+
+def kolmogorov_pvalue(d, n):
+    """P(D_n > d) of the one-sample Kolmogorov-Smirnov statistic: the asymptotic series at Stephens' effective
+    x = d (√n + 0.12 + 0.11/√n)."""
+    if not n or not np.isfinite(d):
+        return float("nan")
+    x = float(d) * (np.sqrt(n) + 0.12 + 0.11 / np.sqrt(n))
+    if x < 0.2:
+        return 1.0
+    k = np.arange(1, 101)
+    return float(min(1.0, max(0.0, 2.0 * np.sum((-1.0) ** (k - 1) * np.exp(-2.0 * k * k * x * x)))))
+
+
+class TimeRescalingTest:
+    """Kolmogorov-Smirnov test of the residuals against Exp(1): `statistic` / `pvalue` pooled over all events,
+    `node_statistic` / `node_pvalue` [N] per node (NaN for a node without events), `counts` [N]."""
+
+    def __init__(self, statistic, pvalue, node_statistic, node_pvalue, counts):
+        self.statistic, self.pvalue, self.counts = statistic, pvalue, counts
+        self.node_statistic, self.node_pvalue = node_statistic, node_pvalue
+
+    def __repr__(self):
+        return f"TimeRescalingTest(statistic={self.statistic:.4g}, pvalue={self.pvalue:.4g}, nodes={len(self.counts)})"
+
+
+def _ks_sorted(u):
+    """sup |F_n - U(0,1)| of an ascending sample (numpy array or torch tensor)."""
+    n = len(u)
+    if n == 0:
+        return float("nan")
+    if _is_tensor(u):
+        import torch
+        i = torch.arange(1, n + 1, dtype=torch.float64, device=u.device)
+        return float(torch.maximum((i / n - u).max(), (u - (i - 1) / n).max()))
+    i = np.arange(1, n + 1)
+    return float(max(np.max(i / n - u), np.max(u - (i - 1) / n)))
+
+
+def time_rescaling_test(process, data, ctx=None, model=None, device=None, residuals=None):
+    """Time-rescaling goodness of fit: under the true model the residuals of compensator(process, data) are i.i.d. Exp(1),
+    so u = 1 - exp(-residual) is uniform on (0, 1); returns the Kolmogorov-Smirnov statistic and p-value per node and
+    pooled (TimeRescalingTest).  device (default: where the events are) sorts with torch on the GPU instead of numpy on the
+    host; `residuals` reuses the result of an earlier compensator() call."""
+    _continuous_only(process, "time_rescaling_test")
+    events, nodes = data[0], data[1]
+    if device is None:
+        device = _on_device(events)
+    if residuals is None:
+        residuals = compensator(process, data, ctx=ctx, model=model, device=device).residuals
+    N = process.ndims()
+    if _is_tensor(residuals):
+        import torch
+        nd = nodes if _is_tensor(nodes) else torch.as_tensor(np.asarray(nodes, dtype=np.int64))
+        nd = nd.to(residuals.device)
+        u = -torch.expm1(-residuals)
+        pooled = _ks_sorted(torch.sort(u).values)
+        # per node: sort by (node, u) -- u lies in [0, 1], so node + u/2 orders both at once
+        order = torch.argsort(nd.to(torch.float64) + 0.5 * u)
+        us, counts = u[order], torch.bincount(nd - 1, minlength=N)
+        counts_h = counts.cpu().numpy()
+        off = np.concatenate([[0], np.cumsum(counts_h)])
+        stats = np.array([_ks_sorted(us[off[c]:off[c + 1]]) for c in range(N)])
+    else:
+        nd = np.asarray(nodes.cpu() if _is_tensor(nodes) else nodes, dtype=np.int64)
+        u = -np.expm1(-np.asarray(residuals, dtype=np.float64))
+        pooled = _ks_sorted(np.sort(u))
+        counts_h = np.bincount(nd - 1, minlength=N)
+        stats = np.array([_ks_sorted(np.sort(u[nd == c + 1])) for c in range(N)])
+    pvals = np.array([kolmogorov_pvalue(s, n) for s, n in zip(stats, counts_h)])
+    return TimeRescalingTest(pooled, kolmogorov_pvalue(pooled, int(counts_h.sum())), stats, pvals, counts_h)

@@ -211,6 +211,21 @@ function rand(p::NHP.ContinuousHawkesProcess, duration::Float64; device::Bool=tr
     times[1:n[]], nodes[1:n[]], duration
 end
 
+# --- compensator(process, data) -> (at_events, residuals, total): no reference counterpart ------------------------------
+# The exact integral Λ_c(t) of the intensity of src/continuous.jl:84-96 (the reference's own integral term is "approximate
+# (exact requires cdf)", src/continuous.jl:247): at_events[k] = Λ_{n_k}(t_k), residuals[k] = its increment since the previous
+# event of node n_k (Exp(1) under the true model: time rescaling), total[c] = Λ_c(duration), the expected count of node c.
+function compensator(p::NHP.ContinuousHawkesProcess, data; ctx=context(), ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    M, N = length(data[1]), NHP.ndims(p)
+    at_events, residuals, total = Vector{Float64}(undef, M), Vector{Float64}(undef, M), Vector{Float64}(undef, N)
+    with_model(ctx, p) do m
+        check(ccall((:nhp_cont_compensator, libnhp), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                    ctx.h, ds.h, m, Int32(0), at_events, residuals, total), ctx.h)
+    end
+    (at_events=at_events, residuals=residuals, total=total)
+end
+
 # --- objective + analytic gradient of mle!  src/continuous.jl:144-198 -------------------------------------------------
 function loglikelihood_gradient(p::NHP.ContinuousStandardHawkesProcess, data; recursive=true, ctx=context(), comm=nothing,
                                 ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))

@@ -506,6 +506,45 @@ nhp_status nhp_cont_mle_run(nhp_ctx *ctx, nhp_comm *comm /* nullable */, const n
                             double lower, double upper, double f_abstol, int32_t max_steps, double *x, int64_t len,
                             double *loss, int32_t *steps, int32_t *converged, int32_t *evals);
 
+/* Expectation-maximisation for the standard process with a homogeneous baseline (csrc/cont_em.hip).  The objective is the
+ * one nhp_cont_loglik evaluates, ll = -T Σ λ0 - Σ_p cnt_p Σ_c W[p,c] + Σ_i log λ_i; with term_ij = W[n_j,c_i]·ħ(t_i - t_j) over
+ * exactly the pairs λ_i sums under `flags` (the window, or every earlier event with NHP_LL_RECURSIVE and exponential
+ * impulses), the responsibilities are r_ij = term_ij / λ_i and r_i0 = λ0[c_i] / λ_i.
+ *
+ * nhp_cont_em_stats: one E-step at the model's current parameters.  *ll the log-likelihood; bg [N]: bg[c] = Σ_{i on c} r_i0;
+ * EM, S1, S2 [N*N] column-major [p + c*N] as the model (parent node p, child node c): EM = Σ r_ij;
+ *   exponential:  S1 = Σ r_ij·Δt_ij; S2 is not written (nullable);
+ *   logit-normal: S1 = Σ r_ij·z_ij, z = logit(Δt/dt_max); S2 = Σ r_ij·(z_ij - μ[p,c])², the second moment CENTRED at the
+ *                 model's current μ (the raw Σ r z² loses EM·μ² to cancellation; Σ r z² = S2 + 2μ·S1 - μ²·EM if wanted).
+ * Σ_p EM[p,c] + bg[c] = the number of events of node c.  Outputs are host or device pointers by output_on_device (as in
+ * nhp_cont_compensator; ll is always a host pointer).  Synchronous.  The sums are the gradient kernels' (the statistics are
+ * recovered from the fused log-likelihood + gradient launch without dividing by W, so weights on the lower bound keep theirs):
+ * fixed order on the one-launch routes, LDS atomics on the two-pass windowed route.
+ *
+ * nhp_cont_em_run: the whole iteration on the device.  x [len = N + N²·(2 | 3)] in params! order [λ0; θ | μ; τ; W]: the
+ * start on entry (clamped to [lower, upper]), the result on return; the device-resident `model` holds it too.  Iteration k
+ * runs the E-step at x_k, whose objective f_k (log-likelihood, plus logprior(x_k) with `priors`) goes to trace[k] (nullable,
+ * [max_steps + 1]), then the M-step, each coordinate clamped to the box:
+ *   λ0 = bg/T, W = EM/cnt_p, θ = EM/S1 | μ = S1/EM then τ = EM/Σ r (z - μ)² with the clamped μ;
+ *   with priors (Gamma(α0, β0) on λ0, Gamma(κ, ν) on W, Gamma(a, b) on θ | normal-gamma(μμ, κμ, a, b) on (μ, τ)) the modes
+ *   λ0 = (bg + α0 - 1)/(T + β0), W = (EM + κ - 1)/(cnt_p + ν), θ = (EM + a - 1)/(S1 + b), μ = (S1 + κμ·μμ)/(EM + κμ),
+ *   τ = (EM/2 + a - 1/2)/(Σ r (z - μ)²/2 + b + κμ(μ - μμ)²/2);
+ *   a coordinate whose term is flat (numerator and denominator both zero) keeps its value, a non-positive numerator goes
+ *   to `lower`, a zero denominator under a positive numerator to `upper`.
+ * No step decreases the objective.  Stops when |f_k - f_{k-1}| < f_abstol (*converged = 1, *steps = k, x = x_k) or with
+ * k = max_steps (*converged = 0); *loss = -f_k as nhp_cont_mle_run reports it.  The host reads one scalar per iteration.
+ * An empty dataset is handled (λ0 goes to `lower`, the rest stays).
+ *
+ * Errors of both: NHP_ENOTIMPL for an LGCP baseline, a model with an adjacency matrix, a column shard and the LDS limits of
+ * nhp_cont_loglik_grad; NHP_EDOMAIN when the intensity of some event is not positive and finite; NHP_ESHAPE for a wrong len. */
+nhp_status nhp_cont_em_stats(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *model, int32_t flags,
+                             int32_t output_on_device, double *ll, double *bg /* [N] */, double *EM /* [N*N] */,
+                             double *S1 /* [N*N] */, double *S2 /* [N*N] nullable */);
+nhp_status nhp_cont_em_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *model, int32_t flags,
+                           const nhp_gibbs_priors *priors /* nullable: unregularised */, double lower, double upper, double f_abstol,
+                           int32_t max_steps, double *x, int64_t len, double *loss, int32_t *steps, int32_t *converged,
+                           double *trace /* nullable, [max_steps + 1] */);
+
 /* mle!(process::DiscreteStandardHawkesProcess, data; f_abstol, guess) (src/discrete.jl:211-296) the same way: x = params(process)
  * = [λ0; vec(W .* θ)] (src/discrete.jl:178-182; homogeneous baseline), the objective -loglikelihood(process, data, convolved) with
  * params!'s split W = Σ_b, θ = x ./ W (:195-203) redone on the device per evaluation, its gradient from the two GEMMs of

@@ -21,8 +21,8 @@ from .discrete import (DiscreteDataset, DiscreteGaussianImpulseResponse, Discret
                        resample_parent_counts, update_, vb_)
 from . import discrete as _disc
 from .parents import node_counts, parent_counts, resample_parents, uniform_stream  # noqa: F401
-from .inference import (MarkovChainMonteCarlo, MaximumLikelihood, logprior,  # noqa: F401
-                        resample_adjacency_matrix_)
+from .inference import (ExpectedStatistics, MarkovChainMonteCarlo, MaximumLikelihood, em_, expected_statistics,  # noqa: F401
+                        logprior, resample_adjacency_matrix_)
 from . import inference as _inf
 from . import synthetic  # noqa: F401
 from .synthetic import rand  # noqa: F401   rand(process, duration): the reference's exported simulator name

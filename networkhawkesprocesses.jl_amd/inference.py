@@ -4,6 +4,7 @@ on the host is O(N²) bookkeeping and the conjugate random draws (SURVEY.md 2.1:
 
 Result containers keep the reference's field names (src/inference.jl:6-12,24-29,78-83).
 """
+import collections
 import time
 
 import numpy as np
@@ -177,6 +178,102 @@ def mle_(process, data, optimizer="L-BFGS-B", verbose=False, f_abstol=1e-6, regu
     process.params_(res.x)
     return MaximumLikelihood(res.x.copy(), -float(res.fun), state["steps"], time.time() - start,
                              "success" if (state["converged"] or res.success) else "failure")
+
+
+ExpectedStatistics = collections.namedtuple("ExpectedStatistics", "ll bg EM S1 S2")
+
+
+def _em_check(process, data, what):
+    """The argument errors of em_ / expected_statistics, raised before any device work."""
+    from .sharded import ShardedDataset
+    if not isinstance(process, ContinuousStandardHawkesProcess):
+        raise TypeError(f"{what} is defined for ContinuousStandardHawkesProcess")
+    if not isinstance(process.baseline, HomogeneousProcess):
+        raise NotImplementedError(f"{what}: the M-step of a LogGaussianCoxProcess baseline has no closed form")
+    if isinstance(data, ShardedDataset):
+        raise NotImplementedError(f"{what}: not available on a column shard (sharded.ShardedDataset)")
+
+
+def expected_statistics(process, data, recursive=True, device=False, ctx=None):
+    """The expected branching structure under the process's current parameters -- one E-step (nhp_cont_em_stats).
+
+    With r_ij = W[n_j,c_i]·ħ(t_i - t_j)/λ_i over the pairs the objective's λ_i sums (`recursive` as in loglikelihood) and
+    r_i0 = λ0[c_i]/λ_i:  ll, the log-likelihood;  bg[c] = Σ r_i0, the expected number of background events of node c;
+    EM[p, c] = Σ r_ij, the expected number of events of node c that are children of node p;  S1[p, c] = Σ r_ij·Δt_ij
+    (exponential) or Σ r_ij·z_ij, z = logit(Δt/Δtmax) (logit-normal);  S2[p, c] = Σ r_ij·(z_ij - μ[p, c])² (logit-normal, centred
+    at the current μ; None for exponential impulses).  device=False: numpy arrays; device=True: float64 torch tensors on the
+    context's device."""
+    import ctypes as C
+    from .continuous import _check_recursive
+    _em_check(process, data, "expected_statistics")
+    ctx = ctx or _lib.default_context()
+    ds = device_dataset(process, data, ctx)
+    model = process.device_model(ctx)
+    N = process.ndims()
+    ln = not isinstance(process.impulses, ExponentialImpulseResponse)
+    ll = C.c_double()
+    fn = _lib.lib().nhp_cont_em_stats
+    flags = _check_recursive(process, recursive)
+    if device:
+        import torch
+        dev = torch.device("cuda", ctx.device)
+        bg = torch.empty(N, dtype=torch.float64, device=dev)
+        mats = [torch.empty(N * N, dtype=torch.float64, device=dev) for _ in range(3 if ln else 2)]
+        torch.cuda.current_stream(dev).synchronize()          # earlier users of the buffers' memory are done before the library writes
+        _lib.check(fn(ctx.h, ds.h, model.h, flags, 1, C.byref(ll), bg.data_ptr(), mats[0].data_ptr(), mats[1].data_ptr(),
+                      mats[2].data_ptr() if ln else None), ctx.h)
+        mats = [m.view(N, N).t() for m in mats]               # column-major [p + c·N] -> [p, c]
+    else:
+        bg = np.empty(N)
+        mats = [np.empty(N * N) for _ in range(3 if ln else 2)]
+        _lib.check(fn(ctx.h, ds.h, model.h, flags, 0, C.byref(ll), bg.ctypes.data, mats[0].ctypes.data, mats[1].ctypes.data,
+                      mats[2].ctypes.data if ln else None), ctx.h)
+        mats = [m.reshape((N, N), order="F") for m in mats]
+    return ExpectedStatistics(ll.value, bg, mats[0], mats[1], mats[2] if ln else None)
+
+
+def em_(process, data, max_steps=1000, f_abstol=1e-6, regularize=False, guess=None, recursive=True, seed=None,
+        verbose=False, ctx=None, keep_trace=False):
+    """Expectation-maximisation fit of a standard process with a homogeneous baseline, the whole iteration on the GPU
+    (nhp_cont_em_run).
+
+    The objective is mle_'s: loglikelihood(process, data; recursive) [+ logprior(process) with regularize], on the same box
+    [1e-6, 10], from the same random start (or `guess`), stopped by the same |f - f_prev| < f_abstol rule; `process` is
+    overwritten with the estimate.  Because the objective charges every event the full mass Σ_c W[n_i, c], the M-step has
+    a closed form in every coordinate (with the reference's Gamma / normal-gamma priors too), so an iteration is one fused
+    log-likelihood + gradient launch plus an O(P) pass, needs no line search and never decreases the objective.  Returns
+    a MaximumLikelihood; keep_trace adds `.trace`, the objective at every iterate (steps + 1 values)."""
+    import ctypes as C
+    from .continuous import _check_recursive
+    _em_check(process, data, "em!")
+    P = len(process.params())
+    rng = np.random.default_rng(seed)
+    x0 = _rand_init_(process, rng) if guess is None else np.asarray(guess, dtype=np.float64)
+    if x0.shape != (P,):
+        raise ValueError("Parameter vector length does not match model parameter length.")
+    lower, upper = 1e-6, 1e1
+    priors = _priors(process) if regularize else None
+    ctx = ctx or _lib.default_context()
+    ds = device_dataset(process, data, ctx)
+    start = time.time()
+    x = np.clip(x0, lower, upper)                                   # (a new float64 vector: the caller's guess is not written to)
+    process.params_(x)                                              # column-major tables, as in mle_(optimizer="device")
+    model = process.device_model(ctx)
+    loss, steps, conv = C.c_double(), C.c_int32(), C.c_int32()
+    trace = np.full(int(max_steps) + 1, np.nan) if (keep_trace or verbose) else None
+    _lib.check(_lib.lib().nhp_cont_em_run(ctx.h, ds.h, model.h, _check_recursive(process, recursive),
+                                          C.byref(priors) if priors is not None else None, lower, upper, float(f_abstol),
+                                          int(max_steps), _lib.dptr(x), P, C.byref(loss), C.byref(steps), C.byref(conv),
+                                          _lib.dptr(trace)), ctx.h)
+    if verbose:
+        for k in range(steps.value + 1):
+            print(f" > step: {k}, loss: {-trace[k]}")
+        print(f" > steps: {steps.value}, loss: {loss.value}, elapsed: {time.time() - start}")
+    process.params_(x)
+    res = MaximumLikelihood(x, -float(loss.value), int(steps.value), time.time() - start, "success" if conv.value else "failure")
+    if keep_trace:
+        res.trace = trace[:steps.value + 1].copy()
+    return res
 
 
 def resample_adjacency_matrix_(process, data, u=None, seed=0, step=0, model=None, fetch=True, ctx=None):

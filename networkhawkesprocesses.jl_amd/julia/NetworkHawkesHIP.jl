@@ -371,6 +371,50 @@ function mle!(p::NHP.ContinuousStandardHawkesProcess, data; optimizer=Optim.BFGS
     res
 end
 
+# --- expected_statistics(process, data) and em!(process, data; ...) -> MaximumLikelihood: no reference counterpart --------
+# The expected branching structure (one E-step, nhp_cont_em_stats) and the expectation-maximisation fit with the whole
+# iteration on the device (nhp_cont_em_run): mle!'s objective, box [1e-6, 10], start and |f - f_prev| < f_abstol rule; the
+# M-step is closed-form in every coordinate (with the package's priors too: regularize=true), no step lowers the objective.
+# S2 (logit-normal only) is centred at the current μ: Σ r (z - μ)².
+function expected_statistics(p::NHP.ContinuousStandardHawkesProcess, data; recursive=true, ctx=context(),
+                             ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    N = NHP.ndims(p)
+    ln = !(p.impulses isa NHP.ExponentialImpulseResponse)
+    ll, bg = Ref{Float64}(0.0), Vector{Float64}(undef, N)
+    EM, S1, S2 = Matrix{Float64}(undef, N, N), Matrix{Float64}(undef, N, N), Matrix{Float64}(undef, N, N)
+    with_model(ctx, p) do m
+        check(ccall((:nhp_cont_em_stats, libnhp), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                    ctx.h, ds.h, m, llflags(p, recursive), Int32(0), ll, bg, EM, S1, ln ? pointer(S2) : Ptr{Float64}(C_NULL)), ctx.h)
+    end
+    (ll=ll[], bg=bg, EM=EM, S1=S1, S2=ln ? S2 : nothing)
+end
+
+function em!(p::NHP.ContinuousStandardHawkesProcess, data; max_steps=1000, f_abstol=1e-6, regularize=false, guess=nothing,
+             recursive=true, verbose=false, ctx=context(), keep_trace=false,
+             ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    p.baseline isa NHP.HomogeneousProcess || error("em!: the M-step of a LogGaussianCoxProcess baseline has no closed form")
+    guess = guess === nothing ? NHP._rand_init_(p) : guess
+    x = clamp.(Vector{Float64}(guess), 1e-6, 1e1)
+    P = length(x)
+    P == length(NHP.params(p)) || error("Parameter vector length does not match model parameter length.")
+    loss, steps, conv = Ref{Float64}(0.0), Ref{Int32}(0), Ref{Int32}(0)
+    trace = fill(NaN, max_steps + 1)
+    pri = Ref(priors(p))
+    t0 = time()
+    with_model(ctx, p) do m
+        GC.@preserve pri check(ccall((:nhp_cont_em_run, libnhp), Int32,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Priors}, Float64, Float64, Float64, Int32, Ptr{Float64}, Int64,
+             Ref{Float64}, Ref{Int32}, Ref{Int32}, Ptr{Float64}),
+            ctx.h, ds.h, m, llflags(p, recursive), regularize ? Base.unsafe_convert(Ptr{Priors}, pri) : Ptr{Priors}(C_NULL),
+            1e-6, 1e1, f_abstol, Int32(max_steps), x, P, loss, steps, conv, trace), ctx.h)
+    end
+    verbose && println(" > steps: $(steps[]), loss: $(loss[])")
+    NHP.params!(p, x)
+    res = NHP.MaximumLikelihood(x, -loss[], Int(steps[]), time() - t0, conv[] == 1 ? "success" : "failure")
+    keep_trace ? (res, trace[1:steps[]+1]) : res
+end
+
 # --- mcmc!(process, data; nsteps=1000, log_freq=100, verbose=false) -> MarkovChainMonteCarlo  src/inference.jl:49-70
 # A sweep -- parents, sufficient statistics, conjugate draws, (network) adjacency sweep and ρ -- stays on the device
 # (nhp_cont_gibbs_step / nhp_cont_network_step); `push!(res.samples, params(process))` downloads the parameters every

@@ -11,6 +11,8 @@ Host-side random draws (Gibbs conjugate updates, src/baselines.jl:72-77,
 src/weights.jl:59-64, src/impulses.jl:68-73,204-214, src/networks.jl:65-78) use numpy's
 Generator: statistically, not bitwise, the same as Julia's samplers.
 """
+import collections
+
 import numpy as np
 
 from ._lib import DomainError
@@ -423,3 +425,28 @@ class BernoulliNetworkModel(Network):
     def resample_links_(self, nlinks, size, rng):
         self.ρ = rng.beta(self.α + nlinks, self.β + size - nlinks)
         return self.ρ
+
+
+# ------------------------------------------------------------------------------ parameter vector
+ParamLayout = collections.namedtuple("ParamLayout", "baseline impulses weights adjacency")
+
+
+def param_layout(process, network=False):
+    """Where the blocks of a continuous process sit in a parameter vector, as slices.
+
+    Device order (default): params(process) of the standard process, [λ0; θ | μ; τ; W] -- the
+    order of params!, the gradient, the device-resident block and its running moments, which put
+    vec(A) behind it when the model has one; `weights.stop` is len(params) of the standard process.
+    network=True: params(process) of a ContinuousNetworkHawkesProcess,
+    [ρ; λ0; W; impulses; vec(A)] (src/continuous.jl:325-333)."""
+    N = process.ndims()
+    lengths = {"baseline": N if isinstance(process.baseline, HomogeneousProcess) else N * len(process.baseline.x),
+               "impulses": N * N * (1 if isinstance(process.impulses, ExponentialImpulseResponse) else 2),
+               "weights": N * N, "adjacency": N * N if hasattr(process, "network") else 0}
+    order = ("baseline", "weights", "impulses", "adjacency") if network else ParamLayout._fields
+    at = len(process.network.params()) if network else 0
+    where = {}
+    for name in order:
+        where[name] = slice(at, at + lengths[name])
+        at += lengths[name]
+    return ParamLayout(**where)

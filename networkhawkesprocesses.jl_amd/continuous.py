@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib
 from ._lib import DomainError
 from .components import (BernoulliNetworkModel, DenseNetworkModel, ExponentialImpulseResponse,
-                         HomogeneousProcess, LogGaussianCoxProcess, LogitNormalImpulseResponse, host_array)
+                         HomogeneousProcess, LogGaussianCoxProcess, LogitNormalImpulseResponse, host_array, param_layout)
 
 
 class HawkesProcess:
@@ -386,9 +386,7 @@ def intensity(process, data, times, ctx=None):
 
 def gradient_length(process):
     """len(params(process)) of the standard process, without building the vector (three column-major N x N copies)."""
-    N = process.ndims()
-    return (N if isinstance(process.baseline, HomogeneousProcess) else N * len(process.baseline.x)) \
-        + N * N * (2 if isinstance(process.impulses, ExponentialImpulseResponse) else 3)
+    return param_layout(process).weights.stop
 
 
 def loglikelihood_gradient(process, data, recursive=True, ctx=None, model=None):

@@ -503,9 +503,8 @@ static nhp_status copy_params(nhp_ctx *ctx, nhp_cont_model *m, const nhp_cont_mo
 {
     ++m->version;
     size_t NN = (size_t)m->N * m->N;
-    size_t nl = m->baseline_kind == NHP_BASELINE_LGCP ? (size_t)m->N * m->grid_n : (size_t)m->N;
     hipStream_t st = ctx->stream;
-    NHP_HIP(ctx, hipMemcpyAsync(m->d_lambda0, d->lambda0, sizeof(double) * nl, hipMemcpyHostToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(m->d_lambda0, d->lambda0, sizeof(double) * nhp_layout(m).nb, hipMemcpyHostToDevice, st));
     if (m->grid_n) {
         NHP_HIP(ctx, hipMemcpyAsync(m->d_grid, d->grid_x, sizeof(double) * m->grid_n, hipMemcpyHostToDevice, st));
         m->grid_end = d->grid_x[m->grid_n - 1];
@@ -533,15 +532,16 @@ extern "C" nhp_status nhp_cont_model_create(nhp_ctx *ctx, const nhp_cont_model_d
     m->grid_n = d->baseline_kind == NHP_BASELINE_LGCP ? d->grid_n : 0;
     m->impulse_kind = d->impulse_kind; m->has_A = d->A != nullptr; m->dt_max = d->dt_max;
     size_t NN = (size_t)m->N * m->N;
-    size_t nl = m->grid_n ? (size_t)m->N * m->grid_n : (size_t)m->N;
+    const nhp_layout L(m);
     nhp_status s = NHP_OK;
-    if ((s = upload<double>(ctx, &m->d_lambda0, nullptr, nl)) != NHP_OK ||
+    if ((s = upload<double>(ctx, &m->d_params, nullptr, L.P)) != NHP_OK ||
         (m->grid_n && (s = upload<double>(ctx, &m->d_grid, nullptr, (size_t)m->grid_n)) != NHP_OK) ||
-        (s = upload<double>(ctx, &m->d_p1, nullptr, NN)) != NHP_OK ||
-        (m->impulse_kind == NHP_IMPULSE_LOGITNORMAL && (s = upload<double>(ctx, &m->d_p2, nullptr, NN)) != NHP_OK) ||
-        (s = upload<double>(ctx, &m->d_W, nullptr, NN)) != NHP_OK ||
-        (m->has_A && (s = upload<double>(ctx, &m->d_A, nullptr, NN)) != NHP_OK) ||
-        (s = copy_params(ctx, m, d)) != NHP_OK) {
+        (m->has_A && (s = upload<double>(ctx, &m->d_A, nullptr, NN)) != NHP_OK)) {
+        nhp_cont_model_destroy(m);
+        return s;
+    }
+    *m = nhp_model_view(m, m->d_params);                              // the tables are the blocks of the vector
+    if ((s = copy_params(ctx, m, d)) != NHP_OK) {
         nhp_cont_model_destroy(m);
         return s;
     }
@@ -568,23 +568,35 @@ extern "C" nhp_status nhp_cont_model_update(nhp_ctx *ctx, nhp_cont_model *m, con
 extern "C" nhp_status nhp_cont_model_set_params(nhp_ctx *ctx, nhp_cont_model *m, const double *x, int64_t len)
 {
     if (!ctx || !m || !x) return NHP_EINVAL;
-    size_t N = (size_t)m->N, NN = N * N;
-    const size_t nb = m->baseline_kind == NHP_BASELINE_HOMOGENEOUS ? N : N * (size_t)m->grid_n;   // λ or vcat(λ...)
-    size_t nimp = m->impulse_kind == NHP_IMPULSE_EXPONENTIAL ? NN : 2 * NN;
-    if ((size_t)len != nb + nimp + NN) {
-        nhp_set_error(ctx, "Parameter vector length does not match model parameter length.");
-        return NHP_ESHAPE;
-    }
+    const nhp_layout L(m);
+    NHP_TRY(nhp_layout_check(ctx, L, len));
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     ++m->version;
-    hipStream_t st = ctx->stream;
-    NHP_HIP(ctx, hipMemcpyAsync(m->d_lambda0, x, sizeof(double) * nb, hipMemcpyHostToDevice, st));
-    NHP_HIP(ctx, hipMemcpyAsync(m->d_p1, x + nb, sizeof(double) * NN, hipMemcpyHostToDevice, st));
-    if (m->impulse_kind == NHP_IMPULSE_LOGITNORMAL)
-        NHP_HIP(ctx, hipMemcpyAsync(m->d_p2, x + nb + NN, sizeof(double) * NN, hipMemcpyHostToDevice, st));
-    NHP_HIP(ctx, hipMemcpyAsync(m->d_W, x + nb + nimp, sizeof(double) * NN, hipMemcpyHostToDevice, st));
-    NHP_HIP(ctx, hipStreamSynchronize(st));
+    NHP_HIP(ctx, hipMemcpyAsync(m->d_params, x, sizeof(double) * L.P, hipMemcpyHostToDevice, ctx->stream));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return NHP_OK;
+}
+
+// params(process) of the device-resident model, standard order [λ0; θ | μ; τ; W]
+extern "C" nhp_status nhp_cont_model_get_params(nhp_ctx *ctx, const nhp_cont_model *m, double *x, int64_t len)
+{
+    if (!ctx || !m || !x) return NHP_EINVAL;
+    if (m->baseline_kind != NHP_BASELINE_HOMOGENEOUS) return NHP_ENOTIMPL;
+    const nhp_layout L(m);
+    NHP_TRY(nhp_layout_check(ctx, L, len));
+    NHP_HIP(ctx, hipSetDevice(ctx->device));
+    return nhp_download(ctx, x, m->d_params, sizeof(double) * L.P);
+}
+
+extern "C" nhp_status nhp_cont_model_get_adjacency(nhp_ctx *ctx, const nhp_cont_model *m, double *A, int64_t len)
+{
+    if (!ctx || !m || !A) return NHP_EINVAL;
+    if (m->ctx != ctx) { nhp_set_error(ctx, "model belongs to another ctx"); return NHP_EINVAL; }
+    if (!m->has_A) { nhp_set_error(ctx, "get_adjacency: the model has no adjacency matrix"); return NHP_EINVAL; }
+    const size_t NN = (size_t)m->N * (size_t)m->N;
+    if ((size_t)len != NN) { nhp_set_error(ctx, "Parameter vector length does not match model parameter length."); return NHP_ESHAPE; }
+    NHP_HIP(ctx, hipSetDevice(ctx->device));
+    return nhp_download(ctx, A, m->d_A, 8 * NN);
 }
 
 extern "C" void nhp_cont_model_destroy(nhp_cont_model *m)
@@ -593,8 +605,7 @@ extern "C" void nhp_cont_model_destroy(nhp_cont_model *m)
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->stream);
     (void)hipFree(m->d_mom); (void)hipFree(m->d_rho);
-    (void)hipFree(m->d_lambda0); (void)hipFree(m->d_grid); (void)hipFree(m->d_p1);
-    (void)hipFree(m->d_p2); (void)hipFree(m->d_W); (void)hipFree(m->d_A);
+    (void)hipFree(m->d_params); (void)hipFree(m->d_grid); (void)hipFree(m->d_A);
     delete m;
 }
 

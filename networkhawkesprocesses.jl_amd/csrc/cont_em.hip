@@ -45,6 +45,9 @@ struct em_args {
 
 struct em_pair { double EM, S1, S2, D1; };
 
+// of the vectors x and g (the baseline is homogeneous: em_check)
+__device__ __forceinline__ nhp_layout em_layout(const em_args &a) { return nhp_layout(a.N, 0, NHP_BASELINE_HOMOGENEOUS, a.impulse); }
+
 __device__ __forceinline__ double em_clamp(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // the maximiser of num·log(v) - den·v on [lo, hi]: flat keeps `old`; no mass -> lo; no charge -> hi
@@ -58,19 +61,18 @@ __device__ __forceinline__ double em_ratio(double num, double den, double old, d
 
 __device__ __forceinline__ em_pair em_pair_stats(const em_args &a, const double *__restrict__ x, const double *__restrict__ g, size_t k)
 {
-    const size_t N = (size_t)a.N, NN = N * N;
-    const size_t nimp = a.impulse == NHP_IMPULSE_EXPONENTIAL ? NN : 2 * NN;
-    const double cp = a.cnt ? a.cnt[k % N] : 0.0;
+    const nhp_layout L = em_layout(a);
+    const double cp = a.cnt ? a.cnt[k % (size_t)a.N] : 0.0;
     em_pair s;
-    s.EM = x[N + nimp + k] * (g[N + nimp + k] + cp);
+    s.EM = x[L.W + k] * (g[L.W + k] + cp);
     if (a.impulse == NHP_IMPULSE_EXPONENTIAL) {
-        s.S1 = s.EM / x[N + k] - g[N + k];
+        s.S1 = s.EM / x[L.p1 + k] - g[L.p1 + k];
         s.S2 = 0.0; s.D1 = 0.0;
     } else {
-        const double mu = x[N + k], tau = x[N + NN + k];
-        s.D1 = g[N + k] / tau;
+        const double mu = x[L.p1 + k], tau = x[L.p2 + k];
+        s.D1 = g[L.p1 + k] / tau;
         s.S1 = s.EM * mu + s.D1;
-        s.S2 = s.EM / tau - 2.0 * g[N + NN + k];
+        s.S2 = s.EM / tau - 2.0 * g[L.p2 + k];
     }
     return s;
 }
@@ -116,7 +118,7 @@ __device__ __forceinline__ double em_prior_pair(const em_args &a, double w, doub
 __global__ __launch_bounds__(256) void k_em_start(em_args a, const double *__restrict__ xin, double *__restrict__ x, double *__restrict__ part)
 {
     const size_t N = (size_t)a.N, NN = N * N;
-    const size_t nimp = a.impulse == NHP_IMPULSE_EXPONENTIAL ? NN : 2 * NN;
+    const nhp_layout L = em_layout(a);
     double lp = 0.0;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < N + NN; i += (size_t)gridDim.x * 256) {
         if (i < N) {
@@ -126,10 +128,10 @@ __global__ __launch_bounds__(256) void k_em_start(em_args a, const double *__res
             continue;
         }
         const size_t k = i - N;
-        const double w = em_clamp(xin[N + nimp + k], a.lo, a.hi), p1 = em_clamp(xin[N + k], a.lo, a.hi);
+        const double w = em_clamp(xin[L.W + k], a.lo, a.hi), p1 = em_clamp(xin[L.p1 + k], a.lo, a.hi);
         double p2 = 0.0;
-        x[N + nimp + k] = w; x[N + k] = p1;
-        if (a.impulse != NHP_IMPULSE_EXPONENTIAL) { p2 = em_clamp(xin[N + NN + k], a.lo, a.hi); x[N + NN + k] = p2; }
+        x[L.W + k] = w; x[L.p1 + k] = p1;
+        if (a.impulse != NHP_IMPULSE_EXPONENTIAL) { p2 = em_clamp(xin[L.p2 + k], a.lo, a.hi); x[L.p2 + k] = p2; }
         if (a.use_prior) lp += em_prior_pair(a, w, p1, p2);
     }
     em_store_prior(lp, part);
@@ -153,7 +155,7 @@ __global__ __launch_bounds__(256) void k_em_mstep(em_args a, const double *__res
                                                   double *__restrict__ xn, double *__restrict__ partn)
 {
     const size_t N = (size_t)a.N, NN = N * N;
-    const size_t nimp = a.impulse == NHP_IMPULSE_EXPONENTIAL ? NN : 2 * NN;
+    const nhp_layout L = em_layout(a);
     const nhp_gibbs_priors &q = a.pr;
     double lp = 0.0;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < N + NN; i += (size_t)gridDim.x * 256) {
@@ -168,14 +170,14 @@ __global__ __launch_bounds__(256) void k_em_mstep(em_args a, const double *__res
         const size_t k = i - N;
         const em_pair s = em_pair_stats(a, x, g, k);
         const double cp = a.cnt ? a.cnt[k % N] : 0.0;
-        const double w = a.use_prior ? em_ratio(s.EM + q.kappa - 1.0, cp + q.nu, x[N + nimp + k], a.lo, a.hi)
-                                     : em_ratio(s.EM, cp, x[N + nimp + k], a.lo, a.hi);
+        const double w = a.use_prior ? em_ratio(s.EM + q.kappa - 1.0, cp + q.nu, x[L.W + k], a.lo, a.hi)
+                                     : em_ratio(s.EM, cp, x[L.W + k], a.lo, a.hi);
         double p1, p2 = 0.0;
         if (a.impulse == NHP_IMPULSE_EXPONENTIAL) {
-            p1 = a.use_prior ? em_ratio(s.EM + q.a - 1.0, s.S1 + q.b, x[N + k], a.lo, a.hi)
-                             : em_ratio(s.EM, s.S1, x[N + k], a.lo, a.hi);
+            p1 = a.use_prior ? em_ratio(s.EM + q.a - 1.0, s.S1 + q.b, x[L.p1 + k], a.lo, a.hi)
+                             : em_ratio(s.EM, s.S1, x[L.p1 + k], a.lo, a.hi);
         } else {
-            const double mu0 = x[N + k];
+            const double mu0 = x[L.p1 + k];
             const double mnum = a.use_prior ? s.S1 + q.kappa_mu * q.mu_mu : s.S1, mden = a.use_prior ? s.EM + q.kappa_mu : s.EM;
             p1 = mden > 0.0 ? em_clamp(mnum / mden, a.lo, a.hi) : mu0;
             const double d = p1 - mu0;
@@ -183,14 +185,14 @@ __global__ __launch_bounds__(256) void k_em_mstep(em_args a, const double *__res
             V = V > 0.0 ? V : 0.0;
             if (a.use_prior) {
                 const double dm = p1 - q.mu_mu;
-                p2 = em_ratio(0.5 * s.EM + q.a - 0.5, 0.5 * V + q.b + 0.5 * q.kappa_mu * (dm * dm), x[N + NN + k], a.lo, a.hi);
+                p2 = em_ratio(0.5 * s.EM + q.a - 0.5, 0.5 * V + q.b + 0.5 * q.kappa_mu * (dm * dm), x[L.p2 + k], a.lo, a.hi);
             } else {
-                p2 = em_ratio(s.EM, V, x[N + NN + k], a.lo, a.hi);
+                p2 = em_ratio(s.EM, V, x[L.p2 + k], a.lo, a.hi);
             }
-            xn[N + NN + k] = p2;
+            xn[L.p2 + k] = p2;
         }
-        xn[N + k] = p1;
-        xn[N + nimp + k] = w;
+        xn[L.p1 + k] = p1;
+        xn[L.W + k] = w;
         if (a.use_prior) lp += em_prior_pair(a, w, p1, p2);
     }
     em_store_prior(lp, partn);
@@ -239,44 +241,23 @@ em_args em_make_args(const nhp_cont_dataset *ds, const nhp_cont_model *m, const 
     return a;
 }
 
-// the device optimizers' block (ctx->d_mle), grown on demand
-nhp_status em_reserve(nhp_ctx *ctx, size_t need)
-{
-    if (ctx->mle_cap >= need) return NHP_OK;
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->d_mle);
-    ctx->d_mle = nullptr; ctx->mle_cap = 0;
-    if (hipMalloc(&ctx->d_mle, need) != hipSuccess) {
-        (void)hipGetLastError();
-        nhp_set_error(ctx, "out of device memory (EM state)");
-        return NHP_ENOMEM;
-    }
-    ctx->mle_cap = need;
-    return NHP_OK;
-}
-
-// E-step at the DEVICE vector d_x (a view of the model whose tables point into it, as nhp_cont_mle_run evaluates a trial):
+// E-step at the DEVICE vector d_x (through nhp_model_view, as nhp_cont_mle_run evaluates a trial):
 // log-likelihood -> ctx->d_results[0], gradient -> *d_grad
 nhp_status em_estep(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *m, int32_t flags, const double *d_x, int64_t P, double **d_grad)
 {
-    const size_t N = (size_t)m->N, NN = N * N;
-    const size_t nimp = m->impulse_kind == NHP_IMPULSE_EXPONENTIAL ? NN : 2 * NN;
     if (ds->M == 0) {
         NHP_TRY(nhp_ctx_reserve_scratch(ctx, 8 * (2 + (size_t)P)));
         double *g = (double *)ctx->d_scratch + 2;
         NHP_HIP(ctx, hipMemsetAsync(g, 0, 8 * (size_t)P, ctx->stream));
-        hipLaunchKernelGGL(k_em_empty, dim3(1), dim3(256), 0, ctx->stream, (int)N, ds->duration, d_x, g, ctx->d_results);
+        hipLaunchKernelGGL(k_em_empty, dim3(1), dim3(256), 0, ctx->stream, m->N, ds->duration, d_x, g, ctx->d_results);
         NHP_HIP(ctx, hipGetLastError());
         *d_grad = g;
         return NHP_OK;
     }
     ++m->version;
-    nhp_cont_model view = *m;
-    double *x = const_cast<double *>(d_x);                          // (read-only through the view)
-    view.d_lambda0 = x; view.d_p1 = x + N; view.d_W = x + N + nimp;
-    if (m->impulse_kind == NHP_IMPULSE_LOGITNORMAL) view.d_p2 = x + N + NN;
+    nhp_cont_model view = nhp_model_view(m, d_x);
     const nhp_status rc = nhp_grad_enqueue(ctx, ds, &view, flags, P, d_grad);
-    m->rec_version = view.rec_version; m->rec_ds = view.rec_ds; m->rec_cut = view.rec_cut;    // (the recursive route's cached bound)
+    nhp_model_view_keep_bound(m, view);
     return rc;
 }
 
@@ -300,25 +281,20 @@ extern "C" nhp_status nhp_cont_em_stats(nhp_ctx *ctx, const nhp_cont_dataset *ds
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_check_deferred(ctx));
     const size_t N = (size_t)m->N, NN = N * N;
-    const bool exp_imp = m->impulse_kind == NHP_IMPULSE_EXPONENTIAL;
-    const size_t nimp = exp_imp ? NN : 2 * NN;
-    const int64_t P = (int64_t)(N + nimp + NN);
-    if (exp_imp) S2 = nullptr;
-    // the model's tables as one vector in params! order, then the statistics (staged here for a host caller)
-    NHP_TRY(em_reserve(ctx, 8 * ((size_t)P + N + 3 * NN)));
-    double *d_x = (double *)ctx->d_mle, *o_bg = d_x + P, *o_EM = o_bg + N, *o_S1 = o_EM + NN, *o_S2 = S2 ? o_S1 + NN : nullptr;
+    const int64_t P = (int64_t)nhp_layout(m).P;
+    if (m->impulse_kind == NHP_IMPULSE_EXPONENTIAL) S2 = nullptr;
+    // the statistics at the model's own block (staged here for a host caller)
+    NHP_TRY(nhp_ctx_reserve_mle(ctx, 8 * (N + 3 * NN), "EM state"));
+    const double *d_x = m->d_params;
+    double *o_bg = (double *)ctx->d_mle, *o_EM = o_bg + N, *o_S1 = o_EM + NN, *o_S2 = S2 ? o_S1 + NN : nullptr;
     hipStream_t st = ctx->stream;
-    NHP_HIP(ctx, hipMemcpyAsync(d_x, m->d_lambda0, 8 * N, hipMemcpyDeviceToDevice, st));
-    NHP_HIP(ctx, hipMemcpyAsync(d_x + N, m->d_p1, 8 * NN, hipMemcpyDeviceToDevice, st));
-    if (!exp_imp) NHP_HIP(ctx, hipMemcpyAsync(d_x + N + NN, m->d_p2, 8 * NN, hipMemcpyDeviceToDevice, st));
-    NHP_HIP(ctx, hipMemcpyAsync(d_x + N + nimp, m->d_W, 8 * NN, hipMemcpyDeviceToDevice, st));
     double *d_grad = nullptr;
     nhp_cont_model mm = *m;                                           // (the E-step bumps the version of what it evaluates)
     NHP_TRY(em_estep(ctx, ds, &mm, flags, d_x, P, &d_grad));
     if (output_on_device) { o_bg = bg; o_EM = EM; o_S1 = S1; o_S2 = S2; }
     const em_args a = em_make_args(ds, m, nullptr, 0.0, 0.0);
     const unsigned nblk = (unsigned)std::min<size_t>(2048, (N + NN + 255) / 256);
-    hipLaunchKernelGGL(k_em_stats, dim3(nblk), dim3(256), 0, st, a, (const double *)d_x, (const double *)d_grad, o_bg, o_EM, o_S1, o_S2);
+    hipLaunchKernelGGL(k_em_stats, dim3(nblk), dim3(256), 0, st, a, d_x, (const double *)d_grad, o_bg, o_EM, o_S1, o_S2);
     NHP_HIP(ctx, hipGetLastError());
     if (!output_on_device) {
         NHP_TRY(nhp_download(ctx, bg, o_bg, 8 * N));
@@ -342,11 +318,8 @@ extern "C" nhp_status nhp_cont_em_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, 
     if (!ctx || !ds || !m || !x || !loss || !steps_out || !converged_out) return NHP_EINVAL;
     NHP_TRY(em_check(ctx, ds, m, "em!"));
     if (!(lower < upper) || max_steps < 0) return NHP_EDOMAIN;
-    const size_t N = (size_t)m->N, NN = N * N;
-    const bool exp_imp = m->impulse_kind == NHP_IMPULSE_EXPONENTIAL;
-    const size_t nimp = exp_imp ? NN : 2 * NN;
-    const size_t P = N + nimp + NN;
-    if ((size_t)len != P) { nhp_set_error(ctx, "Parameter vector length does not match model parameter length."); return NHP_ESHAPE; }
+    const size_t P = nhp_layout(m).P;
+    NHP_TRY(nhp_layout_check(ctx, nhp_layout(m), len));
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_check_deferred(ctx));
     hipStream_t st = ctx->stream;
@@ -356,7 +329,7 @@ extern "C" nhp_status nhp_cont_em_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, 
 
     // two vectors, each with the partial sums of its log prior behind it, and the objective's scalar
     const size_t stride = P + EM_BLK;
-    NHP_TRY(em_reserve(ctx, 8 * (2 * stride + 2)));
+    NHP_TRY(nhp_ctx_reserve_mle(ctx, 8 * (2 * stride + 2), "EM state"));
     double *d_x = (double *)ctx->d_mle, *d_xn = d_x + stride, *d_f = d_xn + stride;
     const em_args a = em_make_args(ds, m, priors, lower, upper);
     const dim3 grid(EM_BLK), block(256);
@@ -393,12 +366,9 @@ extern "C" nhp_status nhp_cont_em_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, 
         if (k == max_steps) break;
         std::swap(d_x, d_xn);
     }
-    // the model's own tables take the iterate
+    // the model's own block takes the iterate
     ++m->version;
-    NHP_HIP(ctx, hipMemcpyAsync(m->d_lambda0, d_x, 8 * N, hipMemcpyDeviceToDevice, st));
-    NHP_HIP(ctx, hipMemcpyAsync(m->d_p1, d_x + N, 8 * NN, hipMemcpyDeviceToDevice, st));
-    if (!exp_imp) NHP_HIP(ctx, hipMemcpyAsync(m->d_p2, d_x + N + NN, 8 * NN, hipMemcpyDeviceToDevice, st));
-    NHP_HIP(ctx, hipMemcpyAsync(m->d_W, d_x + N + nimp, 8 * NN, hipMemcpyDeviceToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(m->d_params, d_x, 8 * P, hipMemcpyDeviceToDevice, st));
     NHP_TRY(nhp_download(ctx, x, d_x, 8 * P));
     NHP_HIP(ctx, hipStreamSynchronize(st));
     *loss = -f; *steps_out = k; *converged_out = converged ? 1 : 0;

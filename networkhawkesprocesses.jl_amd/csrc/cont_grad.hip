@@ -28,12 +28,6 @@ __device__ __forceinline__ double ggroup_sum(double v)
     return v;
 }
 
-// params(baseline) is λ (N) or vcat(λ...) (N·G grid intensities of the LGCP): src/baselines.jl:41,173
-__device__ __forceinline__ size_t grad_nbase(const nhp_cont_args &a)
-{
-    return a.baseline_kind == NHP_BASELINE_HOMOGENEOUS ? (size_t)a.N : (size_t)a.N * (size_t)a.grid_n;
-}
-
 // ∂ log λ_i / ∂(grid intensities of node c) for an event at time t: g = 1/λ_i spread over the two grid
 // neighbours with the interpolation weights (src/utils/interpolation.jl:26-35)
 __device__ __forceinline__ void grad_lgcp_scatter(const nhp_cont_args &a, int c, double t, double g, double *grad)
@@ -56,10 +50,9 @@ __device__ __forceinline__ void grad_lgcp_scatter(const nhp_cont_args &a, int c,
 __global__ __launch_bounds__(256) void k_grad_init(nhp_cont_args a, int mask_integral, double *__restrict__ grad)
 {
     const size_t N = (size_t)a.N, NN = N * N;
-    const size_t nimp = a.impulse_kind == NHP_IMPULSE_EXPONENTIAL ? NN : 2 * NN;
-    const size_t nb = grad_nbase(a);
-    const size_t P = nb + nimp + NN;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += (size_t)gridDim.x * blockDim.x) {
+    const nhp_layout L(a);
+    const size_t nb = L.nb;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < L.P; i += (size_t)gridDim.x * blockDim.x) {
         double v = 0.0;
         // a column shard owns the terms of its child nodes only; everything else stays 0 so that shards add up
         const size_t col = i < nb ? (a.baseline_kind == NHP_BASELINE_HOMOGENEOUS ? i : i / (size_t)a.grid_n)
@@ -76,8 +69,8 @@ __global__ __launch_bounds__(256) void k_grad_init(nhp_cont_args a, int mask_int
                 const double left = g > 0 ? a.grid[g] - a.grid[g - 1] : 0.0, right = g + 1 < G ? a.grid[g + 1] - a.grid[g] : 0.0;
                 v = -0.5 * (left + right);
             }
-        } else if (i >= nb + nimp) {
-            const size_t k = i - nb - nimp;
+        } else if (i >= L.W) {
+            const size_t k = i - L.W;
             const double mk = (a.A && mask_integral) ? a.A[k] : 1.0;
             v = -a.cnt[k % N] * mk;
         }
@@ -155,18 +148,17 @@ __global__ __launch_bounds__(TH) void k_grad_windowed(nhp_cont_args a, const dou
         }
     }
     __syncthreads();
-    const size_t Nn = grad_nbase(a), NN = (size_t)N * (size_t)N;      // Nn: offset of the impulse block
-    const size_t nimp = IMP == NHP_IMPULSE_EXPONENTIAL ? NN : 2 * NN;
+    const nhp_layout L(a);
     for (int p = tid; p < N; p += TH) {
         const size_t k = (size_t)p + (size_t)c * N;
         const double av = a.A ? a.A[k] : 1.0;
         const double aw = av * a.W[k];
-        if (accH[p] != 0.0) atomicAdd(&grad[Nn + nimp + k], av * accH[p]);
+        if (accH[p] != 0.0) atomicAdd(&grad[L.W + k], av * accH[p]);
         if (IMP == NHP_IMPULSE_EXPONENTIAL) {
-            if (acc1[p] != 0.0) atomicAdd(&grad[Nn + k], aw * acc1[p]);
+            if (acc1[p] != 0.0) atomicAdd(&grad[L.p1 + k], aw * acc1[p]);
         } else {
-            if (acc1[p] != 0.0) atomicAdd(&grad[Nn + k], aw * acc1[p]);
-            if (acc2[p] != 0.0) atomicAdd(&grad[Nn + NN + k], aw * (0.5 / a.p2[k]) * acc2[p]);
+            if (acc1[p] != 0.0) atomicAdd(&grad[L.p1 + k], aw * acc1[p]);
+            if (acc2[p] != 0.0) atomicAdd(&grad[L.p2 + k], aw * (0.5 / a.p2[k]) * acc2[p]);
         }
     }
     const double gs = nhp_block_sum_n<TH / 64>(gsum, red);
@@ -264,15 +256,15 @@ __global__ __launch_bounds__(64 * H) void k_grad_recursive_waves(nhp_cont_args a
         ch_t = nx_t; ch_r = nx_r;
         nx_t = nn_t; nx_r = nn_r;
     }
-    const size_t Nn = grad_nbase(a), NN = (size_t)N * (size_t)N;
+    const nhp_layout L(a);                                       // (exponential impulses: W follows θ)
 #pragma unroll
     for (int q = 0; q < PQ; ++q) {
         const int p = h * NP + lane + 64 * q;
         if (p < N) {
             const size_t k = (size_t)p + (size_t)c * N;
             const double av = a.A ? a.A[k] : 1.0, w = a.W[k], t = a.p1[k];
-            grad[Nn + NN + k] = -a.cnt[p] + av * t * GS[q];      // unmasked integral (D7)
-            grad[Nn + k] = av * w * (GS[q] - t * GR[q]);
+            grad[L.W + k] = -a.cnt[p] + av * t * GS[q];          // unmasked integral (D7)
+            grad[L.p1 + k] = av * w * (GS[q] - t * GR[q]);
         }
     }
     if (tid == 0 && a.baseline_kind == NHP_BASELINE_HOMOGENEOUS) grad[c] = -a.duration + gsum;
@@ -305,11 +297,10 @@ nhp_status nhp_grad_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_
                             double **d_grad_out)
 {
     NHP_TRY(nhp_check_pair(ctx, ds, m));
-    const size_t N = (size_t)ds->N, NN = N * N;
+    const size_t N = (size_t)ds->N, P = nhp_layout(m).P;
     const bool exp_imp = m->impulse_kind == NHP_IMPULSE_EXPONENTIAL;
     const bool lgcp = m->baseline_kind != NHP_BASELINE_HOMOGENEOUS;
-    const size_t P = (lgcp ? N * (size_t)m->grid_n : N) + (exp_imp ? 2 : 3) * NN;
-    if ((size_t)grad_len != P) { nhp_set_error(ctx, "Parameter vector length does not match model parameter length."); return NHP_ESHAPE; }
+    NHP_TRY(nhp_layout_check(ctx, nhp_layout(m), grad_len));
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t M = (size_t)(ds->M > 0 ? ds->M : 1);
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, 8 * (2 + P + M)));

@@ -657,19 +657,11 @@ extern "C" nhp_status nhp_cont_gibbs_step(nhp_ctx *ctx, const nhp_cont_dataset *
 // params(process) of every step (src/inference.jl:61) -- 4N²+N doubles, 33.5 MB per step at N = 1024, i.e. more PCIe
 // time than the whole sweep takes -- while what a chain is read for are posterior means and variances (chains.py
 // gathers exactly these).  Order: params(process) of the standard process, then vec(A) when the model has one.
-__global__ __launch_bounds__(256) void k_moments(int64_t N, int64_t nimp, const double *__restrict__ lambda0,
-                                                 const double *__restrict__ p1, const double *__restrict__ p2,
-                                                 const double *__restrict__ W, const double *__restrict__ A,
+__global__ __launch_bounds__(256) void k_moments(const double *__restrict__ params, int64_t P, const double *__restrict__ A,
                                                  int64_t len, double *__restrict__ mom, double *__restrict__ rho)
 {
-    const int64_t NN = N * N;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < len; i += (int64_t)gridDim.x * 256) {
-        double x;
-        if (i < N) x = lambda0[i];
-        else if (i < N + NN) x = p1[i - N];
-        else if (i < N + nimp) x = p2[i - N - NN];
-        else if (i < N + nimp + NN) x = W[i - N - nimp];
-        else x = A[i - N - nimp - NN];
+        const double x = i < P ? params[i] : A[i - P];
         mom[i] += x;
         mom[len + i] += x * x;
     }
@@ -682,8 +674,7 @@ extern "C" nhp_status nhp_cont_model_moments_reset(nhp_ctx *ctx, nhp_cont_model 
     if (m->ctx != ctx) { nhp_set_error(ctx, "model belongs to another ctx"); return NHP_EINVAL; }
     if (m->baseline_kind != NHP_BASELINE_HOMOGENEOUS) { nhp_set_error(ctx, "moments: homogeneous baseline only"); return NHP_ENOTIMPL; }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
-    const int64_t N = m->N, NN = N * N;
-    const int64_t len = N + (m->impulse_kind == NHP_IMPULSE_EXPONENTIAL ? NN : 2 * NN) + NN + (m->has_A ? NN : 0);
+    const int64_t len = (int64_t)nhp_layout(m).P + (m->has_A ? (int64_t)m->N * m->N : 0);
     if (!m->d_mom || m->mom_len != len) {
         if (m->d_mom) { NHP_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(m->d_mom); m->d_mom = nullptr; }
         if (hipMalloc((void **)&m->d_mom, sizeof(double) * 2 * (size_t)len) != hipSuccess) {
@@ -704,10 +695,9 @@ extern "C" nhp_status nhp_cont_model_moments_accumulate(nhp_ctx *ctx, nhp_cont_m
     if (m->ctx != ctx) { nhp_set_error(ctx, "model belongs to another ctx"); return NHP_EINVAL; }
     if (!m->d_mom) NHP_TRY(nhp_cont_model_moments_reset(ctx, m));
     NHP_HIP(ctx, hipSetDevice(ctx->device));
-    const int64_t N = m->N, NN = N * N, nimp = m->impulse_kind == NHP_IMPULSE_EXPONENTIAL ? NN : 2 * NN;
     const unsigned blocks = (unsigned)std::min<int64_t>((m->mom_len + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_moments, dim3(blocks), dim3(256), 0, ctx->stream, N, nimp, m->d_lambda0, m->d_p1, m->d_p2, m->d_W,
-                       m->has_A ? m->d_A : nullptr, m->mom_len, m->d_mom, m->d_rho);
+    hipLaunchKernelGGL(k_moments, dim3(blocks), dim3(256), 0, ctx->stream, (const double *)m->d_params, (int64_t)nhp_layout(m).P,
+                       (const double *)(m->has_A ? m->d_A : nullptr), m->mom_len, m->d_mom, m->d_rho);
     NHP_HIP(ctx, hipGetLastError());
     ++m->mom_count;
     return NHP_OK;
@@ -724,35 +714,6 @@ extern "C" nhp_status nhp_cont_model_moments_fetch(nhp_ctx *ctx, const nhp_cont_
     NHP_TRY(nhp_download(ctx, sumsq, m->d_mom + len, sizeof(double) * (size_t)len));
     *count = m->mom_count;
     return NHP_OK;
-}
-
-// params(process) of the device-resident model, standard order [λ0; θ | μ; τ; W]
-extern "C" nhp_status nhp_cont_model_get_params(nhp_ctx *ctx, const nhp_cont_model *m, double *x, int64_t len)
-{
-    if (!ctx || !m || !x) return NHP_EINVAL;
-    if (m->baseline_kind != NHP_BASELINE_HOMOGENEOUS) return NHP_ENOTIMPL;
-    const size_t N = (size_t)m->N, NN = N * N;
-    const size_t nimp = m->impulse_kind == NHP_IMPULSE_EXPONENTIAL ? NN : 2 * NN;
-    if ((size_t)len != N + nimp + NN) { nhp_set_error(ctx, "Parameter vector length does not match model parameter length."); return NHP_ESHAPE; }
-    NHP_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    (void)st;
-    NHP_TRY(nhp_download(ctx, x, m->d_lambda0, 8 * N));
-    NHP_TRY(nhp_download(ctx, x + N, m->d_p1, 8 * NN));
-    if (m->impulse_kind == NHP_IMPULSE_LOGITNORMAL) NHP_TRY(nhp_download(ctx, x + N + NN, m->d_p2, 8 * NN));
-    NHP_TRY(nhp_download(ctx, x + N + nimp, m->d_W, 8 * NN));
-    return NHP_OK;
-}
-
-extern "C" nhp_status nhp_cont_model_get_adjacency(nhp_ctx *ctx, const nhp_cont_model *m, double *A, int64_t len)
-{
-    if (!ctx || !m || !A) return NHP_EINVAL;
-    if (m->ctx != ctx) { nhp_set_error(ctx, "model belongs to another ctx"); return NHP_EINVAL; }
-    if (!m->has_A) { nhp_set_error(ctx, "get_adjacency: the model has no adjacency matrix"); return NHP_EINVAL; }
-    const size_t NN = (size_t)m->N * (size_t)m->N;
-    if ((size_t)len != NN) { nhp_set_error(ctx, "Parameter vector length does not match model parameter length."); return NHP_ESHAPE; }
-    NHP_HIP(ctx, hipSetDevice(ctx->device));
-    return nhp_download(ctx, A, m->d_A, 8 * NN);
 }
 
 

@@ -408,8 +408,7 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
         const double punit = __builtin_ldexp(a.dt_max, -ps.dbits);
         const uint32_t pmask = ps.dmask;
         const int psh = ps.psh;
-        const size_t nbase = a.baseline_kind == NHP_BASELINE_HOMOGENEOUS ? (size_t)N : (size_t)N * (size_t)a.grid_n;
-        const size_t NN = (size_t)N * (size_t)N;
+        const nhp_layout L(a);                                      // (exponential impulses: W follows θ)
         // a lane's node and its parameters, requested a slice ahead
         struct lanep { int p; double th, wv, av, cn; };
         auto lane_params = [&](const int jj) {
@@ -471,11 +470,11 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
                 const double gT = (cur.av * cur.wv) * acc1;         // ∂/∂θ[p,c]: a·w Σ g·(1 - θΔ) e^{-θΔ}
                 if (ps.direct) {
                     const double mk = (a.A && mask_integral) ? cur.av : 1.0;
-                    ps.grad[nbase + NN + k] = gW - cur.cn * mk;
-                    ps.grad[nbase + k] = gT;
+                    ps.grad[L.W + k] = gW - cur.cn * mk;
+                    ps.grad[L.p1 + k] = gT;
                 } else {
-                    if (gW != 0.0) atomicAdd(&ps.grad[nbase + NN + k], gW);
-                    if (gT != 0.0) atomicAdd(&ps.grad[nbase + k], gT);
+                    if (gW != 0.0) atomicAdd(&ps.grad[L.W + k], gW);
+                    if (gT != 0.0) atomicAdd(&ps.grad[L.p1 + k], gT);
                 }
             }
             jp = jn; prow0 = row0n; Kp = Kn; cur = nxt;

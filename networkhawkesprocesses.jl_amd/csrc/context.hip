@@ -166,6 +166,21 @@ nhp_status nhp_ctx_reserve_partials(nhp_ctx *ctx, size_t n)
     return NHP_OK;
 }
 
+nhp_status nhp_ctx_reserve_mle(nhp_ctx *ctx, size_t bytes, const char *what)
+{
+    if (bytes <= ctx->mle_cap) return NHP_OK;
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(ctx->d_mle);
+    ctx->d_mle = nullptr; ctx->mle_cap = 0;
+    if (hipMalloc(&ctx->d_mle, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        nhp_set_error(ctx, "out of device memory (%s)", what);
+        return NHP_ENOMEM;
+    }
+    ctx->mle_cap = bytes;
+    return NHP_OK;
+}
+
 nhp_status nhp_check_deferred(nhp_ctx *ctx)
 {
     if (!ctx->err_pending) return NHP_OK;

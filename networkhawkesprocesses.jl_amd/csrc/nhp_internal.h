@@ -188,10 +188,13 @@ struct nhp_cont_model {
     nhp_ctx *ctx = nullptr;
     int32_t N = 0, baseline_kind = 0, grid_n = 0, impulse_kind = 0, has_A = 0;
     double dt_max = 0.0, grid_end = 0.0;
-    double *d_lambda0 = nullptr, *d_grid = nullptr;
+    // params(process) = [λ0; θ | μ; τ; W] as ONE device block of nhp_layout(m).P doubles (owned); the tables point into it
+    double *d_params = nullptr;
+    double *d_lambda0 = nullptr;
     double *d_p1 = nullptr;             // theta (exp) or mu (logit-normal)
-    double *d_p2 = nullptr;             // tau (logit-normal)
-    double *d_W = nullptr, *d_A = nullptr;
+    double *d_p2 = nullptr;             // tau (logit-normal; null for exponential impulses)
+    double *d_W = nullptr;
+    double *d_grid = nullptr, *d_A = nullptr;
     // parameters change through create/update/set_params and the device-side draws: `version` counts the changes, so
     // quantities derived from the parameters (the recursive path's truncation window) are recomputed only when stale
     uint64_t version = 1;
@@ -254,6 +257,24 @@ struct nhp_cont_args {
     int32_t dbg;        // phase-ablation bits; only read in -DNHP_ABLATE builds (tools/ablate.sh)
 };
 
+// Where the tables sit in the parameter vector, params! order [λ0; θ | μ; τ; W] (src/continuous.jl:121-129): the one definition
+// for the host entry points and the kernels.  The baseline block is λ (N) or vcat(λ...) (N·grid_n grid intensities of the
+// LGCP: src/baselines.jl:41,173); p1 = θ | μ follows it, then τ (logit-normal only: p2 == W otherwise), then W.
+struct nhp_layout {
+    size_t nb = 0, p1 = 0, p2 = 0, W = 0, P = 0;    // length of the baseline block; offsets of the tables; length of the vector
+    nhp_layout() = default;
+    __host__ __device__ nhp_layout(int32_t N, int32_t grid_n, int32_t baseline_kind, int32_t impulse_kind)
+    {
+        const size_t NN = (size_t)N * (size_t)N;
+        nb = baseline_kind == NHP_BASELINE_HOMOGENEOUS ? (size_t)N : (size_t)N * (size_t)grid_n;
+        p1 = nb; p2 = p1 + NN;
+        W = impulse_kind == NHP_IMPULSE_EXPONENTIAL ? p2 : p2 + NN;
+        P = W + NN;
+    }
+    explicit nhp_layout(const nhp_cont_model *m) : nhp_layout(m->N, m->grid_n, m->baseline_kind, m->impulse_kind) {}
+    __host__ __device__ explicit nhp_layout(const nhp_cont_args &a) : nhp_layout(a.N, a.grid_n, a.baseline_kind, a.impulse_kind) {}
+};
+
 struct nhp_disc_dataset {
     nhp_ctx *ctx = nullptr;
     int32_t N = 0, B = 0, L = 0;
@@ -313,7 +334,34 @@ void nhp_set_error(nhp_ctx *ctx, const char *fmt, ...);
         if (s_ != NHP_OK) return s_;       \
     } while (0)
 
+// a caller's vector against the model's: the one length check of every entry point that takes params(process)
+inline nhp_status nhp_layout_check(nhp_ctx *ctx, const nhp_layout &L, int64_t len)
+{
+    if ((size_t)len == L.P) return NHP_OK;
+    nhp_set_error(ctx, "Parameter vector length does not match model parameter length.");
+    return NHP_ESHAPE;
+}
+// The model with its tables pointing into the DEVICE vector d_x (params! order) instead of its own block: what mle! and em!
+// evaluate a trial through, so no parameter is copied per evaluation (read-only through the view).
+inline nhp_cont_model nhp_model_view(const nhp_cont_model *m, const double *d_x)
+{
+    const nhp_layout L(m);
+    nhp_cont_model v = *m;
+    double *x = const_cast<double *>(d_x);
+    v.d_lambda0 = x; v.d_p1 = x + L.p1; v.d_W = x + L.W;
+    if (m->impulse_kind == NHP_IMPULSE_LOGITNORMAL) v.d_p2 = x + L.p2;
+    return v;
+}
+// ... and the recursive route's cached bound, which an evaluation through a view may have renewed, back to the model
+inline void nhp_model_view_keep_bound(nhp_cont_model *m, const nhp_cont_model &view)
+{
+    m->rec_version = view.rec_version; m->rec_ds = view.rec_ds; m->rec_cut = view.rec_cut;
+}
+
 nhp_status nhp_ctx_reserve_partials(nhp_ctx *ctx, size_t n_doubles);
+// the device optimizers' block (ctx->d_mle: mle!, em!, expected_statistics), grown on demand and kept between runs; `what`
+// names the state in the out-of-memory message
+nhp_status nhp_ctx_reserve_mle(nhp_ctx *ctx, size_t bytes, const char *what);
 nhp_status nhp_dataset_slab_stats(nhp_ctx *ctx, const nhp_cont_dataset *ds);      // cont_data.hip
 int nhp_pick_group(double mean_window);
 // Dataset creation: the decisions the host pre-pass (nhp_cont_dataset_create_columns) and the device pre-pass

@@ -255,16 +255,7 @@ nhp_status nhp_lbfgs_box(nhp_ctx *ctx, int64_t P, double lower, double upper, do
     // x, x_new, g, g_new, q, d + HIST pairs (s_i, y_i): (6 + 2·HIST)·P doubles (370 MB at N = 1024)
     const size_t nvec = 6 + NB;
     const size_t need = 8 * (nvec * (size_t)P + (size_t)RBLK * NACC + NACC + 1);
-    if (ctx->mle_cap < need) {                                  // (kept by the context between runs)
-        (void)hipFree(ctx->d_mle);
-        ctx->d_mle = nullptr; ctx->mle_cap = 0;
-        if (hipMalloc(&ctx->d_mle, need) != hipSuccess) {
-            (void)hipGetLastError();
-            nhp_set_error(ctx, "out of device memory (mle! state)");
-            return NHP_ENOMEM;
-        }
-        ctx->mle_cap = need;
-    }
+    NHP_TRY(nhp_ctx_reserve_mle(ctx, need, "mle! state"));
     if (!ctx->h_mle_scal && hipHostMalloc((void **)&ctx->h_mle_scal, 8 * (NACC + 1)) != hipSuccess) {
         ctx->h_mle_scal = nullptr;
         nhp_set_error(ctx, "out of pinned memory");

@@ -12,7 +12,7 @@ from scipy import optimize
 from scipy.special import gammaln
 
 from . import _lib
-from .components import (ExponentialImpulseResponse, HomogeneousProcess, LogitNormalImpulseResponse)
+from .components import (ExponentialImpulseResponse, HomogeneousProcess, LogitNormalImpulseResponse, param_layout)
 from .continuous import (ContinuousNetworkHawkesProcess, ContinuousStandardHawkesProcess,
                          device_dataset, loglikelihood, loglikelihood_gradient)
 from .parents import resample_parents
@@ -335,22 +335,18 @@ def _priors(process):
 def _pull_params(process, model, ctx):
     """Copy the device-resident parameters back into the component structs (in-place semantics of
     the reference: "all inference methods overwrite model parameters", docs/src/index.md:109-111)."""
-    import ctypes as C
-    N = process.ndims()
-    nimp = N * N * (1 if isinstance(process.impulses, ExponentialImpulseResponse) else 2)
-    x = np.empty(N + nimp + N * N)
+    L = param_layout(process)
+    x = np.empty(L.weights.stop)
     _lib.check(_lib.lib().nhp_cont_model_get_params(ctx.h, model.h, _lib.dptr(x), len(x)), ctx.h)
-    process.baseline.λ = x[:N].copy()
-    process.impulses.params_(x[N:N + nimp])
-    process.weights.params_(x[N + nimp:])
+    process.baseline.λ = x[L.baseline].copy()
+    process.impulses.params_(x[L.impulses])
+    process.weights.params_(x[L.weights])
 
 
 def _fetch_moments(process, model, ctx, network, rho_sum, rho_sq):
     """Mean and mean square of params(process) from the device-side running sums, in params(process) order."""
     import ctypes as C
-    N = process.ndims()
-    nimp = N * N * (1 if isinstance(process.impulses, ExponentialImpulseResponse) else 2)
-    L = N + nimp + N * N + (N * N if network else 0)
+    L = moments_length(process)
     s, q = np.empty(L), np.empty(L)
     cnt = C.c_int64()
     _lib.check(_lib.lib().nhp_cont_model_moments_fetch(ctx.h, model.h, _lib.dptr(s), _lib.dptr(q), L, C.byref(cnt)), ctx.h)
@@ -360,23 +356,19 @@ def _fetch_moments(process, model, ctx, network, rho_sum, rho_sq):
 
 def moments_length(process):
     """Length of the device-side running sums of nhp_cont_model_moments_*: [λ0; impulses; W; vec(A) if any]."""
-    N = process.ndims()
-    nimp = N * N * (1 if isinstance(process.impulses, ExponentialImpulseResponse) else 2)
-    return N + nimp + N * N + (N * N if isinstance(process, ContinuousNetworkHawkesProcess) else 0)
+    return param_layout(process).adjacency.stop
 
 
 def _moments_in_params_order(process, s, q, count, network, rho_sum, rho_sq):
     """Σx, Σx² in the device order -> mean and mean square in params(process) order."""
-    N = process.ndims()
-    nimp = N * N * (1 if isinstance(process.impulses, ExponentialImpulseResponse) else 2)
     n = max(1, count)
     mean, m2 = s / n, q / n
     if network:        # device order [λ0; impulses; W; vec(A)] -> params(process) = [ρ; λ0; W; impulses; vec(A)] (src/continuous.jl:325-333)
         k = len(process.network.params())
-        a, b, c = N, N + nimp, N + nimp + N * N
+        L = param_layout(process)
 
         def order(v, rho):
-            return np.concatenate([np.full(k, rho), v[:a], v[b:c], v[a:b], v[c:]])
+            return np.concatenate([np.full(k, rho), v[L.baseline], v[L.weights], v[L.impulses], v[L.adjacency]])
         mean, m2 = order(mean, rho_sum / n), order(m2, rho_sq / n)
     return mean, m2
 
@@ -400,16 +392,12 @@ def _merge_shards(process, shard, network):
     from .sharded import _all_reduce_sum
     N = process.ndims()
     full = _all_reduce_sum(process.params() * _owned_mask(process, shard, network), shard.ctx)
-    k = len(process.network.params()) if network else 0
-    nimp = N * N * (1 if isinstance(process.impulses, ExponentialImpulseResponse) else 2)
-    process.baseline.λ = full[k:k + N].copy()
+    L = param_layout(process, network)
+    process.baseline.λ = full[L.baseline].copy()
+    process.impulses.params_(full[L.impulses])
+    process.weights.params_(full[L.weights])
     if network:
-        process.weights.params_(full[k + N:k + N + N * N])
-        process.impulses.params_(full[k + N + N * N:k + N + N * N + nimp])
-        process.adjacency_matrix = full[k + N + N * N + nimp:].reshape((N, N), order="F").copy()
-    else:
-        process.impulses.params_(full[N:N + nimp])
-        process.weights.params_(full[N + nimp:])
+        process.adjacency_matrix = full[L.adjacency].reshape((N, N), order="F").copy()
 
 
 def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_samples=True, device_draws=True,

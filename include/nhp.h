@@ -307,6 +307,56 @@ nhp_status nhp_cont_simulate(nhp_ctx *ctx, const nhp_cont_model *model, double d
 nhp_status nhp_cont_compensator(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *model,
                                 int32_t output_on_device, double *at_events /* [M] nullable */,
                                 double *residuals /* [M] nullable */, double *total /* [N] nullable */);
+/* forecast(process, data, horizon): `nsamples` = S independent continuations of the observed events on (T0, T0 + h], T0 = the
+ * dataset's duration, h = horizon, conditional on those events -- the reference has no such function.  The law is the
+ * GENERATIVE model's, the one nhp_cont_simulate samples (src/continuous.jl:16-48), not the likelihood's convention: exponential
+ * delays are not cut at dt_max, and a link's expected child count is W[p,c]·A[p,c] for both impulse kinds (the logit-normal
+ * mass carries no dt_max factor, unlike nhp_cont_compensator).  With the delay CDF F_pc(d) = -expm1(-θ d) (exponential) or
+ * Φ(√τ (logit(d/dt_max) - μ)) for 0 < d < dt_max, 0 below and 1 from there on (logit-normal), one continuation is the union of
+ * three independent parts, exactly:
+ *   carry-over: the not-yet-realised direct children of the observed events; event j (node p, time t_j) has
+ *     Poisson(W[p,c]A[p,c]·(F_pc(T0+h-t_j) - F_pc(T0-t_j))) of them on node c, their delays from F_pc given the interval;
+ *   new immigrants: Poisson(λ0_c h) per node, uniform on (T0, T0+h];
+ *   descendants of both, by the generation loop of nhp_cont_simulate with the end time Tend = fl(T0 + h).
+ * Exponential impulses (memoryless): the events of node p enter through G[p,c] = Σ_{j on p} e^{-θ[p,c](T0 - t_j)} (one fp64 running
+ * sum per (p,c) over p's events in time order, terms below e^-708 are exactly 0: at most M·N exponentials, once per call), the
+ * carry mass of a link is m[p,c] = W·A·G·(-expm1(-θh)), CP[p,c] = the running sum of m[0..p, c] over p, carry[c] = CP[N-1, c].
+ * Logit-normal impulses (thinning): the events with T0 - t_j < dt_max (j >= w0, Wn of them) are the parents of generation 0 in
+ * every replica, draw Poisson(R_p) children as every event does, and the children with T0 < t <= Tend stay;
+ * carry[c] = Σ_{j >= w0} W·A·(F(Tend - t_j) - F(T0 - t_j)) in time order.
+ * Outputs, host or device pointers by output_on_device (as in nhp_cont_simulate):
+ *   carry[N] (nullable): the expected number of carry-over events per node, deterministic (fixed-order fp64 sums);
+ *   counts[S*N], replica-major: the events of node c in (T0, Tend] in replica r;
+ *   times / nodes [capacity max_events] and offsets[S+1] (all three or none): replica r owns [offsets[r], offsets[r+1]), its
+ *     times absolute and ascending, its nodes 1-based; counts[r, :] is the bincount of its nodes.  Order: a stable sort of the
+ *     kept events by time, then stably by replica;
+ *   phase_ms[2] (nullable, host): wall milliseconds of the boundary state (tables, G, carry masses) and of the ensemble.
+ * max_events caps the kept events of all replicas together.  The result depends on (model, dataset, horizon, nsamples, seed)
+ * only -- not on max_events, the chunk size or launch geometry; replica r's draws are NOT promised to be the same for different
+ * nsamples.  Synchronous.  Errors: NHP_EDOMAIN for a negative / non-finite horizon or the parameter checks of
+ * nhp_cont_simulate; NHP_EINVAL for null handles, nsamples < 1, max_events outside [0, 2^31), paths given in part; the dataset /
+ * model mismatches of the other entry points; NHP_ENOTIMPL for an LGCP baseline (the grid ends where the data end), a column
+ * shard, nsamples·N >= 2^30 or nsamples·Wn + max_events >= 2^31 (32-bit arena indices; no kernel stages a table in LDS, so N
+ * itself has no limit); NHP_ENOMEM "branching process exploded (unstable weights?)" when the kept events pass max_events
+ * (nothing is written past the buffers; the ctx stays usable).
+ * Random numbers: the Philox block, uniforms ua, ub, u and the Poisson sampler of nhp_cont_simulate above, with these families
+ * (key = seed ^ F), in draw order; e = r·N + c numbers the (replica, node) pairs:
+ *   0xA0761D6478BD642F  immigrant count of (r, c): Poisson(λ0_c·h), step 0, element e
+ *   0xE7037ED1A0B428DB  exponential carry-over count of (r, c): Poisson(carry[c]), step 0, element e (logit-normal: none)
+ *   0x8EBC6AF09C88C6E3  root k -- roots numbered by e, the immigrants of a pair before its carry-over children: step 0, element k,
+ *                       attempt 0; immigrant: t = T0 + ua·h; carry-over child of node c: parent node = first p with
+ *                       CP[p,c] > u·carry[c] (if none, the first CP[p,c] >= u·carry[c]), delay d = min(-log1p(-ub·q)/θ[p,c], h) with
+ *                       q = -expm1(-θ[p,c]·h), t = T0 + d; a t that rounds to T0 becomes the next double after T0
+ *   0x589965CC75374CC3  child count of arena entry i: Poisson(R_node), step = generation of i, element i
+ *   0x1D8E4E27C47D124F  child slot s of generation g: step g, element s; node and delay as family 0xD6E8... of nhp_cont_simulate
+ * The arena holds [generation 0: entry r·Wn + (j - w0) = window event j in replica r (logit-normal; none for exponential) |
+ * generation 1: the roots, entry S·Wn + k, then the surviving children of generation 0 | generation g + 1: the surviving
+ * children of generation g], survivors (T0 < t <= Tend) in slot order, slots numbered by parent arena index, then child.
+ * Generation 0 is not part of the result. */
+nhp_status nhp_cont_forecast(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *model, double horizon,
+                             int32_t nsamples, uint64_t seed, int64_t max_events, int32_t output_on_device,
+                             double *carry /* [N] nullable */, int64_t *counts /* [S*N] */, double *times /* nullable */,
+                             int64_t *nodes, int64_t *offsets /* [S+1] */, double *phase_ms /* [2] nullable */);
 /* params(process) of the device-resident model: [λ0; θ | μ; τ; W]  src/continuous.jl:116-119 */
 nhp_status nhp_cont_model_get_params(nhp_ctx *ctx, const nhp_cont_model *model, double *x, int64_t len);
 /* process.adjacency_matrix of the device-resident model (after nhp_cont_network_step / nhp_cont_mcmc_run): [N*N] 0.0/1.0 */

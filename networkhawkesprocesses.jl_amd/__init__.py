@@ -11,8 +11,8 @@ from .components import (BernoulliNetworkModel, DenseNetworkModel, DenseWeightMo
                          LogGaussianCoxProcess, LogitNormalImpulseResponse, OrnsteinUhlenbeckKernel,
                          PeriodicKernel, SquaredExponentialKernel, split_extract)
 from .continuous import (Compensator, ContinuousHawkesProcess, ContinuousNetworkHawkesProcess,  # noqa: F401
-                         ContinuousStandardHawkesProcess, DeviceDataset, HawkesProcess, TimeRescalingTest, compensator,
-                         device_dataset, invalidate_device_datasets, time_rescaling_test, total_intensity)
+                         ContinuousStandardHawkesProcess, DeviceDataset, Forecast, HawkesProcess, TimeRescalingTest, compensator,
+                         device_dataset, forecast, invalidate_device_datasets, time_rescaling_test, total_intensity)
 from . import continuous as _cont
 from .discrete import (DiscreteDataset, DiscreteGaussianImpulseResponse, DiscreteHawkesProcess,  # noqa: F401
                        DiscreteHomogeneousProcess, DiscreteLogGaussianCoxProcess, DiscreteNetworkHawkesProcess,

@@ -97,6 +97,7 @@ def _declare(lib):
     f("nhp_cont_dataset_create_device", i32, _vp, _vp, _vp, i64, i32, dbl, dbl, i32, i32, i32, C.POINTER(_vp))
     f("nhp_cont_simulate", i32, _vp, _vp, dbl, u64, i64, i32, _vp, _vp, _vp, C.POINTER(i64))
     f("nhp_cont_compensator", i32, _vp, _vp, _vp, i32, _vp, _vp, _vp)
+    f("nhp_cont_forecast", i32, _vp, _vp, _vp, dbl, i32, u64, i64, i32, _vp, _vp, _vp, _vp, _vp, _dp)
     f("nhp_cont_dataset_export", i32, _vp, _vp, i32, _vp, i64, C.POINTER(i64))
     f("nhp_cont_dataset_scalars", i32, _vp, C.POINTER(i64), i32)
     f("nhp_cont_dataset_destroy", None, _vp)

@@ -457,6 +457,87 @@ def compensator(process, data, ctx=None, model=None, device=False):
     return Compensator(at, res, tot)
 
 
+class Forecast:
+    """Result of forecast(): counts [S, N] int64 (events of node c in (T, T + horizon] in replica r), carry [N] (the
+    expected number of carry-over events per node), paths = None or (times, nodes, offsets): replica r owns
+    [offsets[r], offsets[r + 1]) of the absolute, ascending times and the 1-based nodes.  numpy arrays, or torch tensors
+    on the context's device."""
+
+    def __init__(self, counts, carry, paths, duration, horizon, phase_ms=None):
+        self.counts, self.carry, self.paths, self.duration, self.horizon, self.phase_ms = counts, carry, paths, duration, horizon, phase_ms
+
+    def __iter__(self):
+        return iter((self.counts, self.carry, self.paths))
+
+    def __repr__(self):
+        return f"Forecast(nsamples={self.counts.shape[0]}, nodes={self.counts.shape[1]}, paths={self.paths is not None})"
+
+    def path(self, r):
+        """(times, nodes) of replica r."""
+        times, nodes, offsets = self.paths
+        lo, hi = int(offsets[r]), int(offsets[r + 1])
+        return times[lo:hi], nodes[lo:hi]
+
+
+def forecast(process, data, horizon, nsamples=1000, seed=0, *, return_paths=False, device=False, max_events=5_000_000, ctx=None,
+             model=None):
+    """`nsamples` independent continuations of `data` = (events, nodes, T) on (T, T + horizon], conditional on the observed
+    events (nhp_cont_forecast): the carry-over children of the observed events, new immigrants, and the descendants of both.
+    The law is the generative model's, the one rand(process, duration) samples -- exponential delays are not cut at Δtmax
+    and a link has W[p,c]·A[p,c] expected children for both impulse kinds -- not the likelihood's convention (compensator).
+    Homogeneous baselines only: a LogGaussianCoxProcess grid ends where the data end.
+
+    Returns Forecast(counts, carry, paths); paths only with return_paths.  device=False: numpy arrays; device=True: torch
+    tensors on the context's device.  `data`: a host triple, a device-tensor triple or a DeviceDataset.  The sample depends on
+    (process, data, horizon, nsamples, seed) only; replica r's draws are not the same for different nsamples.  `max_events`
+    caps the events of all replicas together; past it RuntimeError ("branching process exploded").  A path appended to the
+    history, with duration T + horizon, is data for loglikelihood and compensator."""
+    from .sharded import ShardedDataset
+    _continuous_only(process, "forecast")
+    if isinstance(process.baseline, LogGaussianCoxProcess):
+        raise NotImplementedError("forecast: not available with a LogGaussianCoxProcess baseline (the grid ends where the data end)")
+    if isinstance(data, ShardedDataset):
+        raise NotImplementedError("forecast: not available on a column shard (sharded.ShardedDataset)")
+    horizon, S, max_events = float(horizon), int(nsamples), int(max_events)
+    if S != nsamples or S < 1:
+        raise ValueError(f"nsamples = {nsamples} must be a positive integer")
+    if not 0.0 <= horizon < float("inf"):
+        raise DomainError(f"horizon must be non-negative and finite, got {horizon}")
+    if not 0 <= max_events < 2 ** 31:
+        raise ValueError(f"max_events = {max_events} outside [0, 2^31)")
+    ctx = ctx or _lib.default_context()
+    ds = device_dataset(process, data, ctx)
+    model = model or process.device_model(ctx)
+    N, cap = process.ndims(), max(max_events, 1)
+    fn = _lib.lib().nhp_cont_forecast
+    phase = np.zeros(2)
+    seed = int(seed) & (2 ** 64 - 1)
+    if device:
+        import torch
+        dev = torch.device("cuda", ctx.device)
+        counts = torch.empty((S, N), dtype=torch.int64, device=dev)
+        carry = torch.empty(N, dtype=torch.float64, device=dev)
+        t = nd = off = None
+        if return_paths:
+            t = torch.empty(cap, dtype=torch.float64, device=dev)
+            nd = torch.empty(cap, dtype=torch.int64, device=dev)
+            off = torch.empty(S + 1, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()          # earlier users of the buffers' memory are done before the library writes
+        ptr = [x.data_ptr() if x is not None else None for x in (carry, counts, t, nd, off)]
+    else:
+        counts, carry = np.empty((S, N), dtype=np.int64), np.empty(N)
+        t = nd = off = None
+        if return_paths:
+            t, nd, off = np.empty(cap), np.empty(cap, dtype=np.int64), np.empty(S + 1, dtype=np.int64)
+        ptr = [x.ctypes.data if x is not None else None for x in (carry, counts, t, nd, off)]
+    _lib.check(fn(ctx.h, ds.h, model.h, horizon, S, seed, max_events, 1 if device else 0, *ptr, _lib.dptr(phase)), ctx.h)
+    paths = None
+    if return_paths:
+        n = int(off[-1])
+        paths = (t[:n].clone(), nd[:n].clone(), off) if device else (t[:n].copy(), nd[:n].copy(), off)
+    return Forecast(counts, carry, paths, ds.duration, horizon, phase_ms=(float(phase[0]), float(phase[1])))
+
+
 def kolmogorov_pvalue(d, n):
     """P(D_n > d) of the one-sample Kolmogorov-Smirnov statistic: the asymptotic series at Stephens' effective
     x = d (√n + 0.12 + 0.11/√n)."""

@@ -226,6 +226,30 @@ function compensator(p::NHP.ContinuousHawkesProcess, data; ctx=context(), ds=Dat
     (at_events=at_events, residuals=residuals, total=total)
 end
 
+# --- forecast(process, data, horizon) -> (counts, carry, paths): no reference counterpart -------------------------------
+# nsamples independent continuations of data = (events, nodes, T) on (T, T + horizon], conditional on the observed events,
+# under the generative model of rand (exponential delays not cut at Δtmax, W·A expected children per link; not the
+# likelihood's convention): counts is nsamples x N, carry[c] the expected number of carry-over events of node c, paths
+# (with paths=true) = (times, nodes, offsets), replica r owning offsets[r]+1 : offsets[r+1] of the absolute, ascending times
+# and the 1-based nodes.  Homogeneous baselines only.  More than max_events events in all: "branching process exploded".
+function forecast(p::NHP.ContinuousHawkesProcess, data, horizon::Real; nsamples::Integer=1000, seed::Integer=0, paths::Bool=false,
+                  max_events::Integer=5_000_000, ctx=context(), ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    N, S = NHP.ndims(p), Int(nsamples)
+    counts, carry = Matrix{Int64}(undef, N, max(S, 0)), Vector{Float64}(undef, N)      # column r = replica r (replica-major in memory)
+    cap = max(max_events, 1)
+    times, nodes = paths ? (Vector{Float64}(undef, cap), Vector{Int64}(undef, cap)) : (Float64[], Int64[])
+    offsets = paths ? Vector{Int64}(undef, S + 1) : Int64[]
+    with_model(ctx, p) do m
+        check(ccall((:nhp_cont_forecast, libnhp), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int32, UInt64, Int64, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{Float64},
+                     Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
+                    ctx.h, ds.h, m, Float64(horizon), Int32(S), seed % UInt64, max_events, Int32(0), carry, counts,
+                    paths ? times : C_NULL, paths ? nodes : C_NULL, paths ? offsets : C_NULL, C_NULL), ctx.h)
+    end
+    n = paths ? offsets[end] : 0
+    (counts=permutedims(counts), carry=carry, paths=paths ? (times[1:n], nodes[1:n], offsets) : nothing)
+end
+
 # --- objective + analytic gradient of mle!  src/continuous.jl:144-198 -------------------------------------------------
 function loglikelihood_gradient(p::NHP.ContinuousStandardHawkesProcess, data; recursive=true, ctx=context(), comm=nothing,
                                 ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))

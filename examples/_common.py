@@ -11,3 +11,14 @@ nhp = entry.load_package()
 def show(title, truth, estimate):
     print(title)
     print(np.column_stack([truth, estimate])[:12])
+
+
+def discrete_data(process, duration, seed, device_rand=False):
+    """The data of a discrete example: the host simulator, or with --device-rand the GPU generator (disc_rand)."""
+    if device_rand:
+        return nhp.disc_rand(process, duration, seed=seed)
+    return nhp.synthetic.rand(process, duration, seed=seed)
+
+
+def device_rand_switch():
+    return "--device-rand" in sys.argv[1:]

@@ -1,6 +1,6 @@
 """Discrete-time standard process with Gaussian-basis impulse responses: mle!, mcmc! and vb!.
 Mirrors examples/discrete-gaussian-standard-hawkes.jl and -vb.jl."""
-from _common import nhp, np, show
+from _common import device_rand_switch, discrete_data, nhp, np, show
 
 
 def make(nnodes=2, nbasis=3, nlags=4, dt=1.0, seed=0):
@@ -11,11 +11,11 @@ def make(nnodes=2, nbasis=3, nlags=4, dt=1.0, seed=0):
     return nhp.DiscreteStandardHawkesProcess(baseline, impulses, weights, dt)
 
 
-def main(duration=1000, nsteps=100, seed=0):
+def main(duration=1000, nsteps=100, seed=0, device_rand=False):
     process = make(seed=seed)
     print(f"Process is stable? {nhp.isstable(process)}")
     θ = process.params()
-    data = nhp.synthetic.rand(process, duration, seed=seed)
+    data = discrete_data(process, duration, seed, device_rand)
     print(f"Generated {data.sum()} events")
     res = nhp.mle_(process, data, seed=seed)
     show("true vs mle", θ, res.maximizer)
@@ -29,4 +29,4 @@ def main(duration=1000, nsteps=100, seed=0):
 
 
 if __name__ == "__main__":
-    main()
+    main(device_rand=device_rand_switch())      # --device-rand: simulate on the GPU (disc_rand)

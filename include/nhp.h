@@ -476,6 +476,47 @@ nhp_status nhp_disc_lgcp_loglik(nhp_ctx *ctx, const nhp_disc_dataset *ds, const 
 nhp_status nhp_disc_vb_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
                            double alpha0, double beta0, double kappa, double nu, double gamma, int32_t n_steps,
                            double *alpha_v, double *beta_v, double *kappa_v, double *nu_v, double *gamma_v);
+/* rand(process::DiscreteHawkesProcess, steps)  src/discrete.jl:20-38 on the device: the N x T count matrix of a discrete
+ * Hawkes process over bins t = 1..T.  The law: cell (c, t) receives Poisson(base[t,c]) immigrants, base[t,c] = lambda0[c]·dt
+ * (homogeneous baseline) or the caller's per-bin means base [T*N], t fastest, already times dt (intensity(baseline, 1:T) of a
+ * DiscreteLogGaussianCoxProcess) -- exactly one of lambda0 and base is given; every event at (p, t) has Poisson(h[p,c,l])
+ * children in cell (c, t+l), independently for every c and every lag l = 1..L, h[p,c,l] = W[p,c]·A[p,c]·dt·Σ_b θ[p,c,b]·φ[l,b];
+ * children past bin T are dropped with their descendants.  W, theta, A (nullable) are host arrays laid out as
+ * nhp_disc_intensity takes them (column-major [p, c(, b)]), phi [L*B] lag fastest as nhp_disc_basis makes it (lags 1..L).
+ * It is drawn in stages (Poisson superposition), with the tables
+ *   cdf[l,b] = φ[1,b] + ... + φ[l,b] (sequential), m_b = cdf[L,b]·dt,
+ *   S[p,c] = Σ_b θ[p,c,b]·m_b (sequential from 0, b ascending), G[p,c] = (W[p,c]·A[p,c])·S[p,c],
+ *   prefix_p[c] = G[p,1] + ... + G[p,c] (sequential), R_p = prefix_p[N],
+ * all in fp64 without contraction: an event has Poisson(R_p) children (an immigrant cell of multiplicity k draws
+ * Poisson(k·R_p) once), a child takes its node from prefix_p, its basis from the running sums of θ[p,c,b]·m_b, its lag from
+ * cdf[·,b].
+ * Outputs, host or device pointers by output_on_device (as in nhp_cont_simulate): counts [N*T], node fastest (the layout
+ * nhp_disc_dataset_create reads); background [N*T] (nullable), the immigrants alone -- parents[:, :, 1] of the reference's
+ * augmented model, transposed; n_events (host) = Σ counts; n_generations (host, nullable) = the generations that hold an
+ * event, the immigrants' included.  Synchronous.  The result depends on (parameters, T, seed) only
+ * -- not on max_events, the chunk size or launch geometry (integer atomic sums).
+ * Errors: NHP_EINVAL for null pointers, both or neither of lambda0 / base, non-positive n_nodes, n_bins, n_lags or n_basis,
+ * max_events outside [0, 2^31); NHP_ENOTIMPL for n_bins >= 2^31 (32-bit bins in the arena) or n_nodes·n_bins >= 2^56 (int64
+ * byte offsets into the matrix); NHP_EDOMAIN for a negative or non-finite dt, W, W·A, θ, φ or baseline mean, a cell mean above
+ * 2^20 or a row total R_p above 2^32; NHP_ENOMEM "branching process exploded (unstable weights?)" when the events pass
+ * max_events (nothing is written past the arena; the ctx stays usable), or when the device cannot hold the scratch (28 bytes per
+ * event of max_events, 16 per slot of a chunk, the parameters, and the two matrices when the outputs are host pointers).
+ * Random numbers: the Philox block, the uniforms ua, ub in (0, 1], u = ua - 2^-53, v = ub - 2^-53 in [0, 1) and the Poisson
+ * sampler of nhp_cont_simulate above, with these families (key = seed ^ F), in draw order; nodes, bins and basis 0-based:
+ *   0xA3B195354A39B70D  immigrants of cell (c, t): Poisson(base[t,c]), step 0, element e = c + N·t
+ *   0x1B03738712FAD5C9  child count of arena entry i: Poisson(k_i·R_node), step = generation of i (immigrants 0), element i
+ *   0xC2B2AE3D27D4EB4F  child slot s of generation g (slots numbered by parent arena index, then child): step g, element s;
+ *                       attempt 0: node = first c with prefix_p[c] > u·R_p (if none, the first prefix_p[c] >= u·R_p); basis =
+ *                       first b with S_b > v·S[p,c], S_b the running sum θ[p,c,0]·m_0 + ... + θ[p,c,b]·m_b (if none, the first
+ *                       S_b >= v·S[p,c]); attempt 1: lag l = first l with cdf[l,b] > u·cdf[L,b] (if none, the first >=);
+ *                       the child's bin is t_parent + l and it is kept when that is at most T
+ * The arena holds the occupied cells in the order of e (entry = node, bin, multiplicity k), then each generation's surviving
+ * children in slot order (k = 1). */
+nhp_status nhp_disc_simulate(nhp_ctx *ctx, const double *lambda0 /* [N] or NULL */, const double *base /* [T*N] or NULL */,
+                             const double *W, const double *theta, const double *A /* nullable */, const double *phi,
+                             int32_t n_lags, int32_t n_basis, double dt, int32_t n_nodes, int64_t n_bins, uint64_t seed,
+                             int64_t max_events, int32_t output_on_device, int64_t *counts /* [N*T] */,
+                             int64_t *background /* [N*T] nullable */, int64_t *n_events, int32_t *n_generations /* nullable */);
 
 /* ---- several GPUs: RCCL over xGMI   ------------------------------------------------------------
  * One process (or host thread) per GPU, one nhp_ctx each.  The reference has no distributed code (README.md:42 lists

@@ -335,6 +335,63 @@ def _convolved(process, data, convolved, ctx):
     return ds
 
 
+def disc_rand(process, steps, seed=0, *, ctx=None, max_events=50_000_000, return_background=False, device=False):
+    """rand(process::DiscreteHawkesProcess, steps) on the GPU (nhp_disc_simulate) -- the device route for discrete
+    processes; `rand(process, steps)` is the host simulator and keeps refusing device=True for them.
+
+    Returns the N x steps int64 count matrix of src/discrete.jl:20-38 as a numpy array, or with device=True as a torch
+    tensor on the context's device; with return_background=True the pair (counts, background), background the immigrants
+    alone (parents[:, :, 1] of the reference's augmented model, as N x steps).  Works for DiscreteStandardHawkesProcess and
+    DiscreteNetworkHawkesProcess with either baseline; for a DiscreteLogGaussianCoxProcess the per-bin means are
+    baseline.intensity(1:steps), and bins outside its grid raise "Sample duration does not match process duration." (where
+    the host simulator's intensity(baseline, 1:steps) fails).  The draws come from counter-based Philox streams
+    (include/nhp.h has the scheme): the same law as the host simulator, not the same sample; the result depends on the
+    parameters, steps and seed only.  More than `max_events` events raise RuntimeError ("branching process exploded")."""
+    out = _disc_simulate(process, steps, seed, ctx, max_events, return_background, device)
+    return out[:2] if return_background else out[0]
+
+
+def _disc_simulate(process, steps, seed, ctx, max_events, return_background, device):
+    """disc_rand's call of nhp_disc_simulate -> (counts, background | None, events, generations)."""
+    if not isinstance(process, DiscreteHawkesProcess):
+        raise TypeError("disc_rand simulates discrete processes; rand(process, duration, device=True) is the device route "
+                        "for continuous ones")
+    if int(steps) != steps or steps < 1:
+        raise ValueError(f"steps = {steps} must be a positive integer")
+    steps, max_events = int(steps), int(max_events)
+    if not 0 <= max_events < 2 ** 31:
+        raise ValueError(f"max_events = {max_events} outside [0, 2^31)")
+    N = process.ndims()
+    l0, W, th, A = process._lowered()
+    base = None
+    if l0 is None:
+        b = process.baseline
+        if steps > b.x[-1] or 1 < b.x[0]:
+            raise ValueError("Sample duration does not match process duration.")
+        base = np.asfortranarray(b.intensity(np.arange(1, steps + 1, dtype=np.float64))).ravel(order="K")      # T x N, t fastest
+    phi = np.asfortranarray(process.impulses.basis())
+    L, B = phi.shape
+    ph = phi.ravel(order="K")
+    ctx = ctx or _lib.default_context()
+    n, gens = C.c_int64(), C.c_int32()
+    if device:
+        import torch
+        dev = torch.device("cuda", ctx.device)
+        out = torch.empty((steps, N), dtype=torch.int64, device=dev)               # node fastest: the transpose is N x T
+        bg = torch.empty((steps, N), dtype=torch.int64, device=dev) if return_background else None
+        torch.cuda.current_stream(dev).synchronize()      # earlier users of the buffers' memory are done before the library writes
+        po, pb = out.data_ptr(), (bg.data_ptr() if return_background else None)
+    else:
+        out = np.empty((steps, N), dtype=np.int64)
+        bg = np.empty((steps, N), dtype=np.int64) if return_background else None
+        po, pb = out.ctypes.data, (bg.ctypes.data if return_background else None)
+    _lib.check(_lib.lib().nhp_disc_simulate(ctx.h, _lib.dptr(l0), _lib.dptr(base), _lib.dptr(W), _lib.dptr(th), _lib.dptr(A),
+                                            _lib.dptr(ph), L, B, process.dt, N, steps, int(seed) & (2 ** 64 - 1), max_events,
+                                            1 if device else 0, po, pb, C.byref(n), C.byref(gens)), ctx.h)
+    tr = (lambda x: None if x is None else x.t()) if device else (lambda x: None if x is None else x.T)
+    return tr(out), tr(bg), n.value, gens.value
+
+
 def disc_intensity(process, data=None, convolved=None, ctx=None):
     """intensity(process, convolved) / intensity(process, data) -> T x N -- src/discrete.jl:115-131"""
     ctx = ctx or _lib.default_context()

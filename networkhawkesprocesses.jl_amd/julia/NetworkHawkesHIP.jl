@@ -211,6 +211,33 @@ function rand(p::NHP.ContinuousHawkesProcess, duration::Float64; device::Bool=tr
     times[1:n[]], nodes[1:n[]], duration
 end
 
+# --- rand(process, steps) -> N x steps counts  src/discrete.jl:20-38 ---------------------------------------------------
+# The discrete branching sampler on the GPU (nhp_disc_simulate; same law, Philox-keyed by `seed`).  background=true also
+# returns the immigrants alone (parents[:, :, 1] of the augmented model, as N x steps).  A DiscreteLogGaussianCoxProcess
+# baseline enters as its per-bin means intensity(baseline, 1:steps).
+function rand(p::NHP.DiscreteHawkesProcess, steps::Int64; device::Bool=true, seed::Integer=0, max_events::Integer=50_000_000,
+              background::Bool=false, ctx=context())
+    device || return NHP.rand(p, steps)
+    steps >= 1 || error("steps must be positive")
+    N = NHP.ndims(p)
+    lgcp = p.baseline isa NHP.DiscreteLogGaussianCoxProcess
+    lgcp && (1 >= p.baseline.x[1] && steps <= p.baseline.x[end] || error("Sample duration does not match process duration."))
+    l0 = lgcp ? nothing : Vector{Float64}(p.baseline.λ)
+    base = lgcp ? Matrix{Float64}(NHP.intensity(p.baseline, Float64.(1:steps))) : nothing          # T x N, t fastest
+    W, θ = Matrix{Float64}(p.weights.W), Array{Float64,3}(p.impulses.θ)
+    A = p isa NHP.DiscreteNetworkHawkesProcess ? Matrix{Float64}(p.adjacency_matrix) : nothing
+    phi = basis_matrix(p.impulses)
+    L, B = size(phi)
+    counts, n = Matrix{Int64}(undef, N, steps), Ref{Int64}(0)
+    bg = background ? Matrix{Int64}(undef, N, steps) : nothing
+    GC.@preserve l0 base A bg check(ccall((:nhp_disc_simulate, libnhp), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Float64, Int32,
+         Int64, UInt64, Int64, Int32, Ptr{Int64}, Ptr{Int64}, Ref{Int64}, Ptr{Int32}),
+        ctx.h, aptr(l0), aptr(base), W, θ, aptr(A), phi, L, B, p.dt, N, steps, seed % UInt64, max_events, Int32(0), counts,
+        bg === nothing ? Ptr{Int64}(C_NULL) : pointer(bg), n, Ptr{Int32}(C_NULL)), ctx.h)
+    background ? (counts, bg) : counts
+end
+
 # --- compensator(process, data) -> (at_events, residuals, total): no reference counterpart ------------------------------
 # The exact integral Λ_c(t) of the intensity of src/continuous.jl:84-96 (the reference's own integral term is "approximate
 # (exact requires cdf)", src/continuous.jl:247): at_events[k] = Λ_{n_k}(t_k), residuals[k] = its increment since the previous

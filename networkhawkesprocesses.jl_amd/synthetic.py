@@ -212,7 +212,10 @@ def rand(process, duration, seed=0, *, device=False, ctx=None, max_events=5_000_
     1-based index of the parent event) -- which loglikelihood, device_dataset, mle_ and mcmc_ take on their device route.
     The two routes draw from different generators (numpy PCG64 here, counter-based Philox on the device) with the same
     law: host and device samples for one seed differ, and neither reproduces Julia's random stream.  More than
-    `max_events` kept events raise RuntimeError ("branching process exploded") on both routes."""
+    `max_events` kept events raise RuntimeError ("branching process exploded") on both routes.
+
+    Discrete processes take the host simulator here and device=True keeps raising NotImplementedError: their device route
+    is `disc_rand(process, steps, seed)` (nhp_disc_simulate), which returns the N x T count matrix."""
     from .discrete import DiscreteHawkesProcess
     if return_parents and not device:
         raise ValueError("return_parents=True needs device=True: the host simulators do not record parents")

@@ -307,6 +307,37 @@ nhp_status nhp_cont_simulate(nhp_ctx *ctx, const nhp_cont_model *model, double d
 nhp_status nhp_cont_compensator(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *model,
                                 int32_t output_on_device, double *at_events /* [M] nullable */,
                                 double *residuals /* [M] nullable */, double *total /* [N] nullable */);
+/* map_parents(process, data): the posterior-mode parent of every event and its posterior probability -- the reference has no
+ * such function.  The categories of event i are those of nhp_cont_resample_parents in its order: the events i-1, i-2, ...,
+ * down to the first of the look-back window with weight A·W·ħ(t_i - t_j), then the baseline λ0_c(t_i); weights are the
+ * sampler's bits.  parents[i] = 0 (baseline) or the 1-based event index, parentnodes[i] = 0 or the 1-based node, prob[i] =
+ * w_max / Σw.  The FIRST maximum in category order wins: of equal parent weights the most recent, a parent before the
+ * baseline.  The first event gets (0, 0) and prob 1.  Sums in a fixed order: two calls give the same bits.  Outputs are host
+ * or device pointers by output_on_device (as in nhp_cont_compensator).  Synchronous.  Errors: NHP_EINVAL (null handles, no
+ * output requested), the dataset / model mismatches of the other entry points, NHP_EDOMAIN when some event's weights do
+ * not sum to a positive finite value, NHP_ENOTIMPL on a column shard and beyond the 160 KiB LDS column budget. */
+nhp_status nhp_cont_map_parents(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *model,
+                                int32_t output_on_device, int64_t *parents /* [M] nullable */,
+                                int64_t *parentnodes /* [M] nullable */, double *prob /* [M] nullable; not all three NULL */);
+/* cascades(process, data, parents): the forest a parent vector forms on the dataset's events.  parents[k] (k = 0 .. M-1) is 0
+ * for an immigrant, else the 1-based index of an event that precedes k: 1 <= parents[k] <= k (the convention of
+ * nhp_cont_resample_parents / nhp_cont_simulate / nhp_cont_map_parents); anything else is NHP_EDOMAIN, checked on the device
+ * before anything is written.  `parents` is a host or a device pointer by parents_on_device, the array outputs by
+ * output_on_device; n_cascades and n_rounds are host pointers.
+ *   per event:    root[k] 1-based index of the immigrant ancestor (k + 1 for an immigrant), generation[k] 0 for an immigrant
+ *                 else the parent's + 1, descendants[k] the events of k's subtree, k excluded
+ *   per cascade:  one per immigrant in ascending root order, *n_cascades of them (capacity M; all four arrays or none):
+ *                 casc_root, casc_size (root included), casc_depth (largest generation), casc_end (time of the last event)
+ *   per node:     immigrants[c] roots on node c, offspring[c] = Σ descendants over the events on c, reach[p + c*N] events on
+ *                 node c whose root is on node p, roots included (Σ reach = M)
+ * O(M log depth) by pointer doubling, *n_rounds rounds (<= 31); integer atomics only: identical from run to run.  M < 2^31.
+ * Synchronous.  NHP_EINVAL (null handles, some but not all cascade arrays), NHP_ENOTIMPL on a column shard. */
+nhp_status nhp_cont_cascades(nhp_ctx *ctx, const nhp_cont_dataset *ds, const int64_t *parents /* [M] */,
+                             int32_t parents_on_device, int32_t output_on_device,
+                             int64_t *root, int64_t *generation, int64_t *descendants /* [M] each, nullable */,
+                             int64_t *casc_root, int64_t *casc_size, int64_t *casc_depth, double *casc_end,
+                             int64_t *n_cascades /* host, nullable */, int64_t *immigrants, int64_t *offspring /* [N] nullable */,
+                             int64_t *reach /* [N*N] column-major, nullable */, int32_t *n_rounds /* host, nullable */);
 /* forecast(process, data, horizon): `nsamples` = S independent continuations of the observed events on (T0, T0 + h], T0 = the
  * dataset's duration, h = horizon, conditional on those events -- the reference has no such function.  The law is the
  * GENERATIVE model's, the one nhp_cont_simulate samples (src/continuous.jl:16-48), not the likelihood's convention: exponential

@@ -20,7 +20,8 @@ from .discrete import (DiscreteDataset, DiscreteGaussianImpulseResponse, Discret
                        disc_rand, disc_resample_adjacency_matrix_,
                        resample_parent_counts, update_, vb_)
 from . import discrete as _disc
-from .parents import node_counts, parent_counts, resample_parents, uniform_stream  # noqa: F401
+from .parents import (Cascades, cascades, map_parents, node_counts, parent_counts, resample_parents,  # noqa: F401
+                      uniform_stream)
 from .inference import (ExpectedStatistics, MarkovChainMonteCarlo, MaximumLikelihood, em_, expected_statistics,  # noqa: F401
                         logprior, resample_adjacency_matrix_)
 from . import inference as _inf

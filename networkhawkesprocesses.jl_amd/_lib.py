@@ -137,6 +137,8 @@ def _declare(lib):
         ("nhp_cont_loglik_grad", (_vp, _vp, _vp, i32, _dp, _dp, i64)),
         ("nhp_cont_intensity", (_vp, _vp, _vp, _dp, i64, _dp)),
         ("nhp_cont_resample_parents", (_vp, _vp, _vp, _dp, u64, u64, _ip, _ip, C.POINTER(Stats))),
+        ("nhp_cont_map_parents", (_vp, _vp, _vp, i32, _vp, _vp, _vp)),
+        ("nhp_cont_cascades", (_vp, _vp, _vp, i32, i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(i64), _vp, _vp, _vp, C.POINTER(i32))),
         ("nhp_disc_dataset_create", (_vp, _ip, i32, i64, C.POINTER(_vp))),
         ("nhp_disc_basis", (i32, i32, dbl, _dp)),
         ("nhp_disc_convolve", (_vp, _vp, _dp, i32, i32, _dp)),

@@ -253,6 +253,51 @@ function compensator(p::NHP.ContinuousHawkesProcess, data; ctx=context(), ds=Dat
     (at_events=at_events, residuals=residuals, total=total)
 end
 
+# --- map_parents(process, data) -> (parents, parentnodes, prob): no reference counterpart --------------------------------
+# The posterior-mode parent of every event over the categories resample_parents draws from (the events of the look-back
+# window, most recent first, then the baseline) and its posterior probability w_max / Σw.  parents[i] = 0 (baseline) or the
+# 1-based event index; the first maximum wins (of equal parent weights the most recent, a parent before the baseline).
+function map_parents(p::NHP.ContinuousHawkesProcess, data; ctx=context(), ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    M = length(data[1])
+    parents, parentnodes, prob = Vector{Int64}(undef, M), Vector{Int64}(undef, M), Vector{Float64}(undef, M)
+    with_model(ctx, p) do m
+        check(ccall((:nhp_cont_map_parents, libnhp), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
+                    ctx.h, ds.h, m, Int32(0), parents, parentnodes, prob), ctx.h)
+    end
+    (parents=parents, parentnodes=parentnodes, prob=prob)
+end
+
+# --- cascades(process, data; parents=:map) -> NamedTuple: no reference counterpart ---------------------------------------
+# The forest a parent assignment forms: parents = :map (map_parents), :sample (one draw of resample_parents with `seed`) or
+# a Vector{Int64} of length M (0 = immigrant, else the 1-based index of an earlier event; anything else: DomainError).
+# Per event root, generation, descendants; per cascade (ascending root) cascade_root, cascade_size, cascade_depth,
+# cascade_end; per node immigrants, offspring and reach[p, c] = events on node c whose root is on node p.
+function cascades(p::NHP.ContinuousHawkesProcess, data; parents=:map, seed::Integer=0, ctx=context(),
+                  ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    M, N = length(data[1]), NHP.ndims(p)
+    if parents isa Symbol
+        parents in (:map, :sample) || throw(ArgumentError("parents must be :map, :sample or a Vector{Int64} of length $M"))
+        par = parents == :map ? map_parents(p, data; ctx=ctx, ds=ds).parents : resample_parents(p, data; seed=seed % UInt64, ctx=ctx, ds=ds)[1]
+    else
+        eltype(parents) <: Integer || throw(ArgumentError("parents must hold integers"))
+        length(parents) == M || throw(ArgumentError("parents must hold one entry per event: expected length $M, got $(length(parents))"))
+        par = Vector{Int64}(parents)
+    end
+    root, generation, descendants = Vector{Int64}(undef, M), Vector{Int64}(undef, M), Vector{Int64}(undef, M)
+    croot, csize, cdepth, cend = Vector{Int64}(undef, M), Vector{Int64}(undef, M), Vector{Int64}(undef, M), Vector{Float64}(undef, M)
+    immigrants, offspring, reach = Vector{Int64}(undef, N), Vector{Int64}(undef, N), Matrix{Int64}(undef, N, N)
+    n, rounds = Ref{Int64}(0), Ref{Int32}(0)
+    check(ccall((:nhp_cont_cascades, libnhp), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Int32, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64},
+                 Ptr{Float64}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ref{Int32}),
+                ctx.h, ds.h, par, Int32(0), Int32(0), root, generation, descendants, croot, csize, cdepth, cend, n, immigrants, offspring,
+                reach, rounds), ctx.h)
+    k = n[]
+    (parents=par, root=root, generation=generation, descendants=descendants, cascade_root=croot[1:k], cascade_size=csize[1:k],
+     cascade_depth=cdepth[1:k], cascade_end=cend[1:k], immigrants=immigrants, offspring=offspring, reach=reach, rounds=Int(rounds[]))
+end
+
 # --- forecast(process, data, horizon) -> (counts, carry, paths): no reference counterpart -------------------------------
 # nsamples independent continuations of data = (events, nodes, T) on (T, T + horizon], conditional on the observed events,
 # under the generative model of rand (exponential delays not cut at Δtmax, W·A expected children per link; not the

@@ -548,6 +548,58 @@ nhp_status nhp_disc_simulate(nhp_ctx *ctx, const double *lambda0 /* [N] or NULL 
                              int32_t n_lags, int32_t n_basis, double dt, int32_t n_nodes, int64_t n_bins, uint64_t seed,
                              int64_t max_events, int32_t output_on_device, int64_t *counts /* [N*T] */,
                              int64_t *background /* [N*T] nullable */, int64_t *n_events, int32_t *n_generations /* nullable */);
+/* disc_forecast(process, data, horizon): `nsamples` = S independent continuations of an observed count matrix s[p, 1..T0] over
+ * the H = horizon_bins bins T0+1 .. T0+H, conditional on the counts -- the reference has no such function.  The law is the one
+ * nhp_disc_simulate draws; with h[p,c,l] as there, one continuation is the union of three independent parts, exactly:
+ *   carry-over: the children the observed events still have beyond T0; cell (c, T0+k) receives Poisson(carry[k,c]) of them,
+ *     carry[k,c] = Σ_p Σ_{l=k..L, T0+k-l >= 1} s[p, T0+k-l]·h[p,c,l] (0 for k > L);
+ *   new immigrants: Poisson(base[k,c]) per cell, base[k,c] = lambda0[c]·dt or the caller's per-bin means base [H*N], k fastest,
+ *     already times dt (intensity(baseline, T0+1 .. T0+H) of a DiscreteLogGaussianCoxProcess) -- exactly one of the two is given;
+ *   descendants of both, by the generation loop of nhp_disc_simulate; a child of an entry in forecast bin k at lag l lands in
+ *     bin k+l of the same replica and is kept when k+l <= H.
+ * `history` [n_history_bins*N] int64, node fastest (the layout nhp_disc_dataset_create reads), is the last n_history_bins bins
+ * of the data, a host pointer or with history_on_device a device pointer; n_history_bins is at least min(L, T0), more is allowed
+ * and changes nothing: only the last Tu = min(L, n_history_bins) bins are copied or read.  W, theta, A (nullable), phi are host
+ * arrays as nhp_disc_simulate takes them.
+ * Boundary state, all in fp64 without contraction, every sum sequential from 0.0 in the stated order (K = min(L, H); k, b, p, c
+ * 0-based from here on, forecast bin k is T0+1+k; lags l = 1..L):
+ *   cdf, m_b, S, G, prefix_p, R_p: the tables of nhp_disc_simulate;
+ *   x[k,p,b] = Σ_l (double)s[p, T0+1+k-l]·φ[l,b] over l = k+1 .. min(L, Tu+k), l ascending, for k < K;
+ *   carry[k,c] = dt·Σ_p Σ_b ((W[p,c]·A[p,c])·θ[p,c,b])·x[k,p,b], p ascending, b ascending inside (W[p,c] alone without A), for
+ *     k < K; exactly 0.0 for k >= K;
+ *   cm[k,c] = base[k,c] + carry[k,c]: the mean of the one Poisson draw that stands for carry-over and immigrants of a cell;
+ *   expected[k,c] = μ_k[c], the exact predictive mean: μ_k = cm_k + Σ_{l=1..min(L,k)} H_lᵀ μ_{k-l}, H_l[p,c] = h[p,c,l], bin after
+ *     bin as z[p,b] = Σ_l φ[l,b]·μ[k-l,p] (l ascending) and μ[k,c] = cm[k,c] + dt·Σ_p Σ_b ((W·A)·θ)[p,c,b]·z[p,b] in a fixed order
+ *     (64 interleaved partial sums over p, joined by a butterfly): the same bits on every call, not a sequential sum.
+ * Outputs, host or device pointers by output_on_device: totals [S*N], replica-major: the events of node c in replica r over the
+ * horizon; cell_sum [H*N], node fastest: Σ_r of the counts of cell (k, c); paths [S*H*N] (nullable), node fastest, then bin, then
+ * replica: the count matrix of every replica (one replica's slice has the layout nhp_disc_dataset_create reads; without it no
+ * S·H·N buffer exists); carry [H*N] and expected [H*N] (both nullable), node fastest; n_events (host) = the events of all
+ * replicas; n_generations (host, nullable) = the generations that hold an entry, the cells' included.  Synchronous.  The result
+ * depends on (parameters, the last min(L, T0) bins of the data, H, S, seed) only -- not on max_events, the chunk size or launch
+ * geometry (integer atomic sums); replica r's draws are NOT promised to be the same for different nsamples.
+ * Errors: NHP_EINVAL for null pointers, both or neither of lambda0 / base, non-positive n_nodes, n_lags, n_basis,
+ * n_history_bins, horizon_bins or nsamples, max_events outside [0, 2^31); NHP_ENOTIMPL for nsamples·horizon_bins >= 2^31 (32-bit
+ * bins in the arena) or nsamples·horizon_bins·n_nodes >= 2^56; NHP_EDOMAIN for a negative history count, a negative or
+ * non-finite dt, W, W·A, θ, φ or baseline mean, a cell mean cm above 2^20 or a row total R_p above 2^32 (checked flags: no draw
+ * is made); NHP_ENOMEM "branching process exploded (unstable weights?)" when the events of all replicas together pass max_events
+ * (nothing is written past the arena; the ctx stays usable), or when the device cannot hold the scratch.
+ * Random numbers: the Philox block, the uniforms and the Poisson sampler of nhp_disc_simulate, with three families of its own
+ * (key = seed ^ F), in draw order:
+ *   0xDA942042E4DD58B5  carry-over + immigrants of cell (c, k) of replica r: Poisson(cm[k,c]), step 0, element e = c + N·(k + H·r)
+ *   0xD1B54A32D192ED03  child count of arena entry i: Poisson(k_i·R_node), step = generation of i (cells 0), element i
+ *   0x8CB92BA72F3D8DD7  child slot s of generation g (slots numbered by parent arena index, then child): step g, element s;
+ *                       node, basis and lag from attempts 0 and 1 as family 0xC2B2... of nhp_disc_simulate; the child's bin is
+ *                       k_parent + l in its parent's replica and it is kept when k_parent + l <= H - 1 (0-based)
+ * The arena holds the occupied cells in the order of e (entry = node, bin k + H·r, multiplicity), then each generation's
+ * surviving children in slot order (multiplicity 1); all replicas share it. */
+nhp_status nhp_disc_forecast(nhp_ctx *ctx, const double *lambda0 /* [N] or NULL */, const double *base /* [H*N] or NULL */,
+                             const double *W, const double *theta, const double *A /* nullable */, const double *phi,
+                             int32_t n_lags, int32_t n_basis, double dt, int32_t n_nodes, const int64_t *history,
+                             int64_t n_history_bins, int32_t history_on_device, int64_t horizon_bins, int64_t nsamples,
+                             uint64_t seed, int64_t max_events, int32_t output_on_device, int64_t *totals /* [S*N] */,
+                             int64_t *cell_sum /* [H*N] */, int64_t *paths /* [S*H*N] nullable */, double *carry /* [H*N] nullable */,
+                             double *expected /* [H*N] nullable */, int64_t *n_events, int32_t *n_generations /* nullable */);
 
 /* ---- several GPUs: RCCL over xGMI   ------------------------------------------------------------
  * One process (or host thread) per GPU, one nhp_ctx each.  The reference has no distributed code (README.md:42 lists

@@ -392,6 +392,124 @@ def _disc_simulate(process, steps, seed, ctx, max_events, return_background, dev
     return tr(out), tr(bg), n.value, gens.value
 
 
+class DiscreteForecast:
+    """Result of disc_forecast(): totals [S, N] int64 (events of node c over the horizon in replica r), mean [N, H] (the
+    ensemble mean per cell, cell_sum / S), expected [N, H] (the exact predictive mean, no sampling), carry [N, H] (the expected
+    carry-over children of the observed events per cell, 0 beyond nlags bins), paths = None or [S, N, H] int64 (the count matrix
+    of every replica), cell_sum [N, H] int64, events (of all replicas) and generations.  numpy arrays, or torch tensors on the
+    context's device."""
+
+    def __init__(self, totals, cell_sum, expected, carry, paths, events, generations):
+        self.totals, self.cell_sum, self.expected, self.carry, self.paths = totals, cell_sum, expected, carry, paths
+        if hasattr(cell_sum, "new_full"):             # a tensor divisor: an IEEE division, as numpy's (a scalar one multiplies by 1/S)
+            self.mean = cell_sum.double() / cell_sum.new_full((), totals.shape[0]).double()
+        else:
+            self.mean = cell_sum / float(totals.shape[0])
+        self.events, self.generations = events, generations
+
+    def __repr__(self):
+        return (f"DiscreteForecast(nsamples={self.totals.shape[0]}, nodes={self.totals.shape[1]}, horizon={self.mean.shape[1]}, "
+                f"paths={self.paths is not None})")
+
+
+def _history_tail(data, N, L):
+    """The last min(L, T0) bins of an N x T0 count matrix as [bins, N] int64, node fastest -> (tail, T0, on_device)."""
+    if isinstance(data, DiscreteDataset):
+        raise TypeError("disc_forecast: a DiscreteDataset keeps no host copy of its counts; pass the N x T count matrix "
+                        "(a numpy array or a device tensor)")
+    if type(data).__module__.split(".")[0] == "torch":
+        import torch
+        if data.dim() != 2 or data.shape[0] != N or data.shape[1] < 1:
+            raise ValueError(f"data must be an N x T matrix with N = {N} rows and at least one bin, got {tuple(data.shape)}")
+        if data.dtype.is_floating_point or data.dtype in (torch.bool, torch.complex64, torch.complex128):
+            raise TypeError("data must be an integer count matrix")
+        T0 = int(data.shape[1])
+        tu = min(L, T0)
+        if data.is_cuda:
+            return data[:, T0 - tu:].t().to(torch.int64).contiguous(), T0, True
+        data = data.numpy()
+    data = np.asarray(data)
+    if data.ndim != 2 or data.shape[0] != N or data.shape[1] < 1:
+        raise ValueError(f"data must be an N x T matrix with N = {N} rows and at least one bin, got {data.shape}")
+    if data.dtype.kind not in "iu":
+        raise TypeError("data must be an integer count matrix")
+    T0 = data.shape[1]
+    if data.dtype.kind == "i" and np.any(data < 0):                 # the whole host matrix; of a device matrix the tail, on the device
+        raise DomainError("disc_forecast: counts must be non-negative")
+    tail = np.ascontiguousarray(data[:, T0 - min(L, T0):].T.astype(np.int64))
+    return tail, T0, False
+
+
+def disc_forecast(process, data, horizon, nsamples=1000, seed=0, *, return_paths=False, device=False, max_events=50_000_000,
+                  ctx=None):
+    """`nsamples` independent continuations of the N x T0 count matrix `data` over the next `horizon` bins, conditional on
+    the observed counts (nhp_disc_forecast) -- the forecast for discrete processes; `forecast(process, data, horizon)` is
+    the one for continuous processes and keeps refusing discrete ones.  A continuation is the union of the children the
+    observed events still have beyond T0 (the carry-over: a process restarted at T0 would lose them), new immigrants, and
+    the descendants of both, under the law disc_rand samples.
+
+    Returns DiscreteForecast(totals [S, N], mean [N, H], expected [N, H], carry [N, H], paths None | [S, N, H], events,
+    generations); `expected` is the exact predictive mean (a linear recursion, no sampling), `mean` the ensemble's.
+    device=False: numpy arrays; device=True: torch tensors on the context's device.  `data`: a numpy integer matrix or a
+    torch tensor (for instance disc_rand(..., device=True)); only its last nlags bins are uploaded or read (negative counts
+    raise DomainError: anywhere in a host matrix, before any device work; in the last nlags bins of a device tensor).  For a
+    DiscreteLogGaussianCoxProcess the grid must reach T0 + horizon ("Sample duration does not match process duration."
+    otherwise).  The sample depends on (process, the last nlags bins of data, horizon, nsamples, seed) only; replica r's
+    draws are not the same for different nsamples.  More than `max_events` events in all replicas together raise
+    RuntimeError ("branching process exploded").  A replica's path appended to the data is data for loglikelihood."""
+    if not isinstance(process, DiscreteHawkesProcess):
+        raise TypeError("disc_forecast forecasts discrete processes; forecast(process, data, horizon) is the route for "
+                        "continuous ones")
+    for name, v in (("horizon", horizon), ("nsamples", nsamples)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or v < 1:
+            raise ValueError(f"{name} = {v} must be a positive integer")
+    H, S, max_events = int(horizon), int(nsamples), int(max_events)
+    if not 0 <= max_events < 2 ** 31:
+        raise ValueError(f"max_events = {max_events} outside [0, 2^31)")
+    N = process.ndims()
+    L = process.nlags()
+    tail, T0, on_device = _history_tail(data, N, L)
+    l0, W, th, A = process._lowered()
+    base = None
+    if l0 is None:
+        b = process.baseline
+        if T0 + H > b.x[-1] or T0 + 1 < b.x[0]:
+            raise ValueError("Sample duration does not match process duration.")
+        base = np.asfortranarray(b.intensity(np.arange(T0 + 1, T0 + H + 1, dtype=np.float64))).ravel(order="K")  # H x N, k fastest
+    phi = np.asfortranarray(process.impulses.basis())
+    L, B = phi.shape
+    ph = phi.ravel(order="K")
+    ctx = ctx or _lib.default_context()
+    n, gens = C.c_int64(), C.c_int32()
+    if on_device and tail.device.index != ctx.device:
+        raise ValueError(f"data lives on {tail.device}, the context on device {ctx.device}")
+    if device or on_device:
+        import torch
+        dev = torch.device("cuda", ctx.device)
+    if device:
+        tot = torch.empty((S, N), dtype=torch.int64, device=dev)
+        cell = torch.empty((H, N), dtype=torch.int64, device=dev)
+        mu, carry = (torch.empty((H, N), dtype=torch.float64, device=dev) for _ in range(2))
+        paths = torch.empty((S, H, N), dtype=torch.int64, device=dev) if return_paths else None
+        ptr = [x.data_ptr() if x is not None else None for x in (tot, cell, paths, carry, mu)]
+    else:
+        tot, cell = np.empty((S, N), dtype=np.int64), np.empty((H, N), dtype=np.int64)
+        mu, carry = np.empty((H, N)), np.empty((H, N))
+        paths = np.empty((S, H, N), dtype=np.int64) if return_paths else None
+        ptr = [x.ctypes.data if x is not None else None for x in (tot, cell, paths, carry, mu)]
+    if device or on_device:
+        torch.cuda.current_stream(dev).synchronize()      # the tail is written and the buffers' earlier users are done
+    hp = tail.data_ptr() if on_device else tail.ctypes.data
+    _lib.check(_lib.lib().nhp_disc_forecast(ctx.h, _lib.dptr(l0), _lib.dptr(base), _lib.dptr(W), _lib.dptr(th), _lib.dptr(A),
+                                            _lib.dptr(ph), L, B, process.dt, N, hp, tail.shape[0], 1 if on_device else 0, H, S,
+                                            int(seed) & (2 ** 64 - 1), max_events, 1 if device else 0, *ptr, C.byref(n),
+                                            C.byref(gens)), ctx.h)
+    if device:
+        return DiscreteForecast(tot, cell.t(), mu.t(), carry.t(), None if paths is None else paths.transpose(1, 2), n.value,
+                                gens.value)
+    return DiscreteForecast(tot, cell.T, mu.T, carry.T, None if paths is None else paths.transpose(0, 2, 1), n.value, gens.value)
+
+
 def disc_intensity(process, data=None, convolved=None, ctx=None):
     """intensity(process, convolved) / intensity(process, data) -> T x N -- src/discrete.jl:115-131"""
     ctx = ctx or _lib.default_context()

@@ -322,6 +322,41 @@ function forecast(p::NHP.ContinuousHawkesProcess, data, horizon::Real; nsamples:
     (counts=permutedims(counts), carry=carry, paths=paths ? (times[1:n], nodes[1:n], offsets) : nothing)
 end
 
+# --- forecast(process::DiscreteHawkesProcess, data, horizon): no reference counterpart -----------------------------------
+# nsamples independent continuations of the N x T0 count matrix over the next `horizon` bins, conditional on the observed
+# counts, under the law of rand (nhp_disc_forecast): totals is nsamples x N, mean / expected / carry are N x horizon (the
+# ensemble mean per cell, the exact predictive mean, the expected carry-over children of the observed events), paths (with
+# paths=true) is N x horizon x nsamples.  Only the last nlags bins of data are read.  A DiscreteLogGaussianCoxProcess grid
+# must reach T0 + horizon.  More than max_events events in all replicas: "branching process exploded".
+function forecast(p::NHP.DiscreteHawkesProcess, data::Matrix{Int64}, horizon::Integer; nsamples::Integer=1000, seed::Integer=0,
+                  paths::Bool=false, max_events::Integer=50_000_000, ctx=context())
+    N, T0 = size(data)
+    N == NHP.ndims(p) && T0 >= 1 || error("data must be an N x T matrix with N = $(NHP.ndims(p)) rows and at least one bin")
+    H, S = Int64(horizon), Int64(nsamples)
+    H >= 1 && S >= 1 || error("horizon and nsamples must be positive")
+    all(>=(0), data) || throw(DomainError(minimum(data), "counts must be non-negative"))
+    lgcp = p.baseline isa NHP.DiscreteLogGaussianCoxProcess
+    lgcp && (T0 + 1 >= p.baseline.x[1] && T0 + H <= p.baseline.x[end] || error("Sample duration does not match process duration."))
+    l0 = lgcp ? nothing : Vector{Float64}(p.baseline.λ)
+    base = lgcp ? Matrix{Float64}(NHP.intensity(p.baseline, Float64.(T0+1:T0+H))) : nothing        # H x N, k fastest
+    W, θ = Matrix{Float64}(p.weights.W), Array{Float64,3}(p.impulses.θ)
+    A = p isa NHP.DiscreteNetworkHawkesProcess ? Matrix{Float64}(p.adjacency_matrix) : nothing
+    phi = basis_matrix(p.impulses)
+    L, B = size(phi)
+    tail = Matrix{Int64}(data[:, max(1, T0 - L + 1):T0])                 # N x Tu, node fastest
+    totals, cell = Matrix{Int64}(undef, N, S), Matrix{Int64}(undef, N, H)  # column r = replica r, column k = bin k
+    carry, expected = Matrix{Float64}(undef, N, H), Matrix{Float64}(undef, N, H)
+    pth = paths ? Array{Int64,3}(undef, N, H, S) : nothing
+    n, gens = Ref{Int64}(0), Ref{Int32}(0)
+    GC.@preserve l0 base A pth check(ccall((:nhp_disc_forecast, libnhp), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Float64, Int32,
+         Ptr{Int64}, Int64, Int32, Int64, Int64, UInt64, Int64, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64},
+         Ref{Int64}, Ref{Int32}),
+        ctx.h, aptr(l0), aptr(base), W, θ, aptr(A), phi, L, B, p.dt, N, tail, size(tail, 2), Int32(0), H, S, seed % UInt64, max_events,
+        Int32(0), totals, cell, pth === nothing ? Ptr{Int64}(C_NULL) : pointer(pth), carry, expected, n, gens), ctx.h)
+    (totals=permutedims(totals), mean=cell ./ S, expected=expected, carry=carry, paths=pth, events=n[], generations=Int(gens[]))
+end
+
 # --- objective + analytic gradient of mle!  src/continuous.jl:144-198 -------------------------------------------------
 function loglikelihood_gradient(p::NHP.ContinuousStandardHawkesProcess, data; recursive=true, ctx=context(), comm=nothing,
                                 ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))

@@ -434,6 +434,8 @@ nhp_status nhp_probe_lbfgs(nhp_ctx *ctx, int64_t n, const double *h, const doubl
                            int32_t max_steps, double *x, double *loss, int32_t *steps, int32_t *converged, int32_t *evaluations);
 
 /* ---- discrete data: N x T counts  src/discrete.jl:18,80 -------------------------------- */
+/* data [N*T], node fastest.  A negative count anywhere in the matrix is refused with NHP_EDOMAIN ("counts must be
+ * non-negative"), found in the host pass over the matrix before any kernel runs; nothing stays allocated. */
 nhp_status nhp_disc_dataset_create(nhp_ctx *ctx, const int64_t *data, int32_t n_nodes, int64_t n_bins,
                                    nhp_disc_dataset **out);
 void nhp_disc_dataset_destroy(nhp_disc_dataset *ds);

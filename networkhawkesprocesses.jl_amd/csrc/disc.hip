@@ -816,6 +816,8 @@ extern "C" nhp_status nhp_disc_dataset_create(nhp_ctx *ctx, const int64_t *data,
         ds->nocc = nocc;
         ds->nocc_pad = (int64_t)ot.size();
         ds->da_nspans = (int32_t)nsp;
+        // any negative entry, not a negative node total: [-1, 0, 5, ...] would pass the kernels as a finite, wrong likelihood
+        if (vmin < 0) { (void)hipFree(d_raw); nhp_set_error(ctx, "counts must be non-negative"); nhp_disc_dataset_destroy(ds); return NHP_EDOMAIN; }
         if (ot.size() >= ((size_t)1 << 31)) { (void)hipFree(d_raw); nhp_set_error(ctx, "too many occupied bins"); nhp_disc_dataset_destroy(ds); return NHP_ENOTIMPL; }
         const size_t no = ot.size() ? ot.size() : 4;
         if (hipMalloc(&ds->d_occ_t, 4 * no) != hipSuccess || hipMalloc(&ds->d_occ_c, 4 * no) != hipSuccess ||
@@ -853,10 +855,7 @@ extern "C" nhp_status nhp_disc_dataset_create(nhp_ctx *ctx, const int64_t *data,
     NHP_HIP(ctx, hipStreamSynchronize(st));
     (void)hipFree(d_raw);
     ds->lgamma_sum = 0.0;
-    for (int n = 0; n < N; ++n) {
-        ds->lgamma_sum += h[(size_t)N + n];
-        if (h[n] < 0.0) { nhp_set_error(ctx, "counts must be non-negative"); nhp_disc_dataset_destroy(ds); return NHP_EDOMAIN; }
-    }
+    for (int n = 0; n < N; ++n) ds->lgamma_sum += h[(size_t)N + n];
     *out = ds;
     return NHP_OK;
 }

@@ -249,6 +249,8 @@ class DiscreteDataset:
         data = np.asarray(data)
         if data.ndim != 2:
             raise ValueError("data must be an N x T matrix")
+        if data.size and data.min() < 0:              # any entry (a node's total may still be positive); nhp_disc_dataset_create
+            raise DomainError("counts must be non-negative")        # refuses the same, this one before any device work
         self.N, self.T = data.shape
         self.ctx = ctx
         self.node_counts = data.sum(axis=1).astype(np.float64)    # node_counts(data): src/parents.jl:118-121

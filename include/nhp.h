@@ -602,6 +602,57 @@ nhp_status nhp_disc_forecast(nhp_ctx *ctx, const double *lambda0 /* [N] or NULL 
                              uint64_t seed, int64_t max_events, int32_t output_on_device, int64_t *totals /* [S*N] */,
                              int64_t *cell_sum /* [H*N] */, int64_t *paths /* [S*H*N] nullable */, double *carry /* [H*N] nullable */,
                              double *expected /* [H*N] nullable */, int64_t *n_events, int32_t *n_generations /* nullable */);
+/* disc_residuals(process, data): goodness of fit of a discrete process on its count matrix -- the reference has no such
+ * function.  The law is the one of nhp_disc_loglik (src/discrete.jl:91-102): cell (t, c) is Poisson(μ[t,c]), μ = the matrix
+ * nhp_disc_intensity returns for the same arguments (dt is inside it; lambda0 = NULL: the dataset's LGCP baseline, as there).
+ * nhp_disc_convolve must have run on `ds`.  With s the observed count, p(k) the Poisson(μ) pmf and F(k) = p(0) + ... + p(k),
+ * F(-1) = 0, every cell gives
+ *   pit     = F(s-1) + v·p(s), v in [0, 1) uniform: the randomized probability integral transform, uniform under the model;
+ *   pearson = (s - μ)/√μ;
+ *   D       = s·log(s/μ) + μ - s (μ at s = 0): half its deviance term,
+ * and every node c the sums over its T cells
+ *   expected[c] = Σμ, observed[c] = Σs (int64), chi2[c] = Σ (s-μ)²/μ, deviance[c] = 2·ΣD,
+ *   histogram[c, j] = the cells with min(floor(pit·nbins), nbins - 1) = j (int64).
+ * A cell with μ = 0 exactly: s = 0 gives pit = v, pearson = 0 and adds nothing to chi2 and deviance; s > 0 has probability 0
+ * under the model: pit = 1, pearson = +inf, chi2[c] becomes +inf, the deviance leaves the cell out, and `impossible` (host)
+ * counts it.  cumulative[t, c] = μ[1,c] + ... + μ[t,c], the compensator of node c at the end of bin t.
+ * Arithmetic of a cell with μ > 0, in fp64 without contraction, exactly as written (√ and / correctly rounded; exp and log
+ * are the device's, good to a few ulp, so a restatement agrees to rounding, not bit for bit):
+ *   d = s - μ; pearson = d/√μ; the chi2 term is (d·d)/μ;
+ *   s = 0: D = μ, p(s) = exp(-μ); otherwise
+ *     D: if |d| < 0.1·(s+μ): x = d/(s+μ), w = x·x, q = (((((((((w/21 + 1/19)·w + 1/17)·w + 1/15)·w + 1/13)·w + 1/11)·w + 1/9)·w
+ *          + 1/7)·w + 1/5)·w + 1/3)·w, D = d·x + ((2·s)·x)·q (the series of s·log(s/μ) + μ - s in x); else D = s·log(s/μ) + μ - s;
+ *     δ(s), the Stirling error lgamma(s+1) - (s+½)·log s + s - ½·log 2π: for s < 16 its correctly rounded value (a table); from
+ *          16 on, with z = s·s, (1/12 - (1/360 - (1/1260 - (1/1680 - (1/1188)/z)/z)/z)/z)/s;
+ *     p(s) = exp(-δ(s) - D)/√(6.283185307179586·s) (the saddle-point form: no s·log μ - μ - lgamma(s+1), which loses 7 digits
+ *          at μ = 2^20);
+ *   s <= μ, the lower tail downward: t = p(s), a = 0, k = s; while k > 0: t = (t·k)/μ, a = a + t, k = k - 1, stop unless
+ *          t > 2^-60·a; pit = a + v·p(s);
+ *   s > μ, the upper tail upward: t = p(s), a = 0, k = s; repeat: k = k + 1, t = (t·μ)/k, a = a + t, until not
+ *          t > (2^-60·a)·(1 - μ/(k+1)) (what is left is below t·r/(1-r), r = μ/(k+1)); pit = (1 - a) - (1 - v)·p(s);
+ *   pit is then clamped to [0, 1].  A tail takes 77 steps at most for μ <= 64 and 8 487 at μ = 2^20 eight sigma out.
+ * The node sums are formed in one fixed order (a workgroup's partial per 1024 bins, the partials joined in bin order by a second
+ * kernel), the scan likewise, the integer sums by integer atomics: the same call gives the same bits, whatever the launch.
+ * Random numbers: the Philox block and the uniform ua of nhp_disc_simulate with a family of its own (key = seed ^ F):
+ *   0x2545F4914F6CDD1D  v of cell (c, t), c and t 0-based: step 0, element e = c + N·t, attempt 0, v = ua - 2^-53
+ * The seed changes pit and the histogram, nothing else.
+ * Outputs, host or device pointers by output_on_device (as in nhp_disc_forecast): the planes pit, pearson, cumulative [T*N], t
+ * fastest (index t + T·c: the layout of nhp_disc_intensity; row-major it is the N x T matrix), each nullable, and an absent
+ * plane is neither computed as a plane nor written; expected, chi2, deviance [N]; observed [N] int64; histogram [N*nbins] int64, bin
+ * fastest; impossible: a host int64 whatever output_on_device says; pass_ms (host, nullable): the milliseconds k_disc_residuals
+ * took on the device, between the two events of the ctx timer (a running nhp_ctx_timer_start is overwritten).  Synchronous.
+ * Errors: NHP_EINVAL for null pointers (the planes excepted), nbins outside [1, 4096], no convolution on `ds`, lambda0 = NULL
+ * without an LGCP baseline; NHP_EDOMAIN for a cell mean that is negative or not finite; NHP_ENOTIMPL for a cell mean or a count
+ * above 2^20 (the cap nhp_disc_simulate puts on a cell mean; it bounds the tail loops) and for N·ceil(T/1024) >= 2^31;
+ * NHP_ENOMEM when the device cannot hold the scratch (μ, and the requested planes when the outputs are host pointers).  The
+ * domain and size checks run in a kernel of their own before the pass, so after them nothing has been written to the outputs
+ * except *impossible = 0; after any error the ctx stays usable. */
+nhp_status nhp_disc_residuals(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *lambda0 /* [N] or NULL */, const double *W,
+                              const double *theta, const double *A /* nullable */, double dt, uint64_t seed, int32_t nbins,
+                              int32_t output_on_device, double *pit /* [T*N] nullable */, double *pearson /* [T*N] nullable */,
+                              double *cumulative /* [T*N] nullable */, double *expected /* [N] */, int64_t *observed /* [N] */,
+                              double *chi2 /* [N] */, double *deviance /* [N] */, int64_t *histogram /* [N*nbins] */,
+                              int64_t *impossible /* host */, double *pass_ms /* host, nullable */);
 
 /* ---- several GPUs: RCCL over xGMI   ------------------------------------------------------------
  * One process (or host thread) per GPU, one nhp_ctx each.  The reference has no distributed code (README.md:42 lists

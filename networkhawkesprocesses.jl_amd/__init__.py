@@ -14,10 +14,11 @@ from .continuous import (Compensator, ContinuousHawkesProcess, ContinuousNetwork
                          ContinuousStandardHawkesProcess, DeviceDataset, Forecast, HawkesProcess, TimeRescalingTest, compensator,
                          device_dataset, forecast, invalidate_device_datasets, time_rescaling_test, total_intensity)
 from . import continuous as _cont
-from .discrete import (DiscreteDataset, DiscreteForecast, DiscreteGaussianImpulseResponse, DiscreteHawkesProcess,  # noqa: F401
-                       DiscreteHomogeneousProcess, DiscreteLogGaussianCoxProcess, DiscreteNetworkHawkesProcess,
-                       DiscreteStandardHawkesProcess, VariationalInference, convolve, disc_parent_counts,
-                       disc_forecast, disc_rand, disc_resample_adjacency_matrix_,
+from .discrete import (DiscreteDataset, DiscreteFitTest, DiscreteForecast, DiscreteGaussianImpulseResponse,  # noqa: F401
+                       DiscreteHawkesProcess, DiscreteHomogeneousProcess, DiscreteLogGaussianCoxProcess,
+                       DiscreteNetworkHawkesProcess, DiscreteResiduals, DiscreteStandardHawkesProcess, VariationalInference,
+                       convolve, disc_parent_counts, disc_forecast, disc_goodness_of_fit, disc_rand, disc_residuals,
+                       disc_resample_adjacency_matrix_,
                        resample_parent_counts, update_, vb_)
 from . import discrete as _disc
 from .parents import (Cascades, cascades, map_parents, node_counts, parent_counts, resample_parents,  # noqa: F401

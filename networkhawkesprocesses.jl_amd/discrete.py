@@ -512,6 +512,126 @@ def disc_forecast(process, data, horizon, nsamples=1000, seed=0, *, return_paths
     return DiscreteForecast(tot, cell.T, mu.T, carry.T, None if paths is None else paths.transpose(0, 2, 1), n.value, gens.value)
 
 
+class DiscreteResiduals:
+    """Result of disc_residuals(): per cell pit, pearson, cumulative [N, T] (None when not requested); per node expected
+    (Σ_t μ), observed (Σ_t s, int64), chi2 (Σ_t (s-μ)²/μ), deviance [N] and histogram [N, nbins] int64 (cells per bin of pit);
+    impossible: the cells with μ = 0 and a positive count; bins = T.  numpy arrays, or torch tensors on the context's device."""
+
+    def __init__(self, pit, pearson, cumulative, expected, observed, chi2, deviance, histogram, impossible, bins):
+        self.pit, self.pearson, self.cumulative = pit, pearson, cumulative
+        self.expected, self.observed, self.chi2, self.deviance, self.histogram = expected, observed, chi2, deviance, histogram
+        self.impossible, self.bins = impossible, bins
+        self.pass_ms = None                           # the residual kernel's device time, ms (tools/residuals_discrete.py)
+
+    def __repr__(self):
+        planes = [k for k in ("pit", "pearson", "cumulative") if getattr(self, k) is not None]
+        return (f"DiscreteResiduals(nodes={self.histogram.shape[0]}, bins={self.bins}, nbins={self.histogram.shape[1]}, "
+                f"planes={planes}, impossible={self.impossible})")
+
+
+def disc_residuals(process, data=None, convolved=None, seed=0, nbins=20, *, pit=True, pearson=False, cumulative=False,
+                   device=False, ctx=None):
+    """Residuals of a discrete process on its N x T count matrix (nhp_disc_residuals): cell (t, c) is Poisson(μ[t,c]) with
+    μ = intensity(process, data), and one pass on the GPU makes of every cell its randomized probability integral transform
+    pit = F(s-1) + v·p(s), v uniform -- exactly uniform on [0, 1) under the model, whatever the means --, its Pearson residual
+    (s-μ)/√μ, and of every node Σμ against Σs, χ² = Σ(s-μ)²/μ, the deviance and the histogram of its pit values over `nbins`
+    equal bins; `cumulative` is the compensator Σ_{t' <= t} μ[t',c].  The T x N intensity never leaves the device.
+
+    Returns DiscreteResiduals; the planes pit, pearson, cumulative are [N, T] or None when not requested (an absent plane is
+    not computed).  device=False: numpy arrays; device=True: torch tensors on the context's device.  `data`: the count matrix,
+    or pass `convolved` (a DiscreteDataset after convolve()).  A cell with μ = 0 and a positive count is impossible under the
+    model: pit = 1, pearson = inf (so chi2 of its node is inf), counted in `impossible`.  The uniforms come from a
+    counter-based Philox stream of their own (include/nhp.h): the result depends on (process, data, seed, nbins) only, and
+    the seed changes pit and the histogram alone.  Raises TypeError for a continuous process (compensator /
+    time_rescaling_test are its route), ValueError for nbins outside [1, 4096], DomainError for a negative or non-finite
+    mean, NotImplementedError for a mean or a count above 2^20."""
+    if not isinstance(process, DiscreteHawkesProcess):
+        raise TypeError("disc_residuals takes discrete processes; compensator(process, data) and time_rescaling_test are the "
+                        "route for continuous ones")
+    if isinstance(nbins, bool) or not isinstance(nbins, (int, np.integer)) or not 1 <= nbins <= 4096:
+        raise ValueError(f"nbins = {nbins} must be an integer in [1, 4096]")
+    nbins = int(nbins)
+    ctx = ctx or _lib.default_context()
+    ds = _convolved(process, data, convolved, ctx)
+    l0, W, th, A = process._lowered()
+    N, T = ds.N, ds.T
+    want = (pit, pearson, cumulative)
+    if device:
+        import torch
+        dev = torch.device("cuda", ctx.device)
+        planes = [torch.empty((N, T), dtype=torch.float64, device=dev) if w else None for w in want]
+        ex, chi, dv = (torch.empty(N, dtype=torch.float64, device=dev) for _ in range(3))
+        ob = torch.empty(N, dtype=torch.int64, device=dev)
+        hist = torch.empty((N, nbins), dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()      # earlier users of the buffers' memory are done before the library writes
+        ptr = [x.data_ptr() if x is not None else None for x in (*planes, ex, ob, chi, dv, hist)]
+    else:
+        planes = [np.empty((N, T)) if w else None for w in want]
+        ex, chi, dv = np.empty(N), np.empty(N), np.empty(N)
+        ob, hist = np.empty(N, dtype=np.int64), np.empty((N, nbins), dtype=np.int64)
+        ptr = [x.ctypes.data if x is not None else None for x in (*planes, ex, ob, chi, dv, hist)]
+    imp, ms = C.c_int64(), C.c_double()
+    _lib.check(_lib.lib().nhp_disc_residuals(ctx.h, ds.h, _lib.dptr(l0), _lib.dptr(W), _lib.dptr(th), _lib.dptr(A), process.dt,
+                                             int(seed) & (2 ** 64 - 1), nbins, 1 if device else 0, *ptr, C.byref(imp),
+                                             C.byref(ms)), ctx.h)
+    res = DiscreteResiduals(*planes, ex, ob, chi, dv, hist, imp.value, T)
+    res.pass_ms = ms.value
+    return res
+
+
+class DiscreteFitTest:
+    """Result of disc_goodness_of_fit(): `statistic` / `pvalue`: the Kolmogorov-Smirnov test of all pit values against
+    U(0, 1); `node_statistic` / `node_pvalue` [N]: the same per node; `histogram_chi2` / `histogram_pvalue`: the χ² test of
+    the pooled pit histogram against equal bins (nbins - 1 degrees of freedom); `dispersion` [N] = chi2 / T, near 1 under the
+    model (above it: overdispersed counts); `expected`, `observed` [N]: Σμ against Σs per node; `impossible`: cells the model
+    gives probability 0."""
+
+    def __init__(self, statistic, pvalue, node_statistic, node_pvalue, histogram_chi2, histogram_pvalue, dispersion, expected,
+                 observed, impossible):
+        self.statistic, self.pvalue, self.node_statistic, self.node_pvalue = statistic, pvalue, node_statistic, node_pvalue
+        self.histogram_chi2, self.histogram_pvalue = histogram_chi2, histogram_pvalue
+        self.dispersion, self.expected, self.observed, self.impossible = dispersion, expected, observed, impossible
+
+    def __repr__(self):
+        return (f"DiscreteFitTest(statistic={self.statistic:.4g}, pvalue={self.pvalue:.4g}, "
+                f"histogram_pvalue={self.histogram_pvalue:.4g}, nodes={len(self.dispersion)}, impossible={self.impossible})")
+
+
+def disc_goodness_of_fit(process, data=None, convolved=None, residuals=None, seed=0, nbins=20, *, device=False, ctx=None):
+    """Does the process describe the count matrix?  The pit values of disc_residuals() are uniform on [0, 1) under the model:
+    returns their Kolmogorov-Smirnov statistic and p-value, pooled and per node, the χ² uniformity test of the pooled pit
+    histogram, the per-node dispersion chi2 / T and Σμ against Σs (DiscreteFitTest).  `residuals` reuses an earlier
+    disc_residuals() result (it must hold the pit plane); with device=True (or residuals that live on the device) the values
+    are sorted with torch on the GPU, otherwise with numpy on the host."""
+    from scipy.special import gammaincc
+    from .continuous import _is_tensor, _ks_sorted, kolmogorov_pvalue
+    if residuals is None:
+        residuals = disc_residuals(process, data, convolved, seed, nbins, pit=True, device=device, ctx=ctx)
+    elif not isinstance(process, DiscreteHawkesProcess):
+        raise TypeError("disc_goodness_of_fit takes discrete processes; time_rescaling_test is the route for continuous ones")
+    r = residuals
+    if r.pit is None:
+        raise ValueError("disc_goodness_of_fit: the residuals hold no pit plane (disc_residuals(..., pit=True))")
+    N, T = r.pit.shape
+    if _is_tensor(r.pit):
+        import torch
+        rows = torch.sort(r.pit, dim=1).values
+        pooled = _ks_sorted(torch.sort(r.pit.reshape(-1)).values)
+        host = lambda x: x.cpu().numpy()
+    else:
+        rows = np.sort(r.pit, axis=1)
+        pooled = _ks_sorted(np.sort(r.pit, axis=None))
+        host = np.asarray
+    stats = np.array([_ks_sorted(rows[c]) for c in range(N)])
+    pvals = np.array([kolmogorov_pvalue(s, T) for s in stats])
+    h = host(r.histogram).sum(axis=0).astype(np.float64)
+    k = len(h)
+    x2 = float(np.sum((h - h.sum() / k) ** 2 / (h.sum() / k)))
+    hp = float(gammaincc(0.5 * (k - 1), 0.5 * x2)) if k > 1 else float("nan")
+    return DiscreteFitTest(pooled, kolmogorov_pvalue(pooled, N * T), stats, pvals, x2, hp, host(r.chi2) / T, host(r.expected),
+                           host(r.observed), r.impossible)
+
+
 def disc_intensity(process, data=None, convolved=None, ctx=None):
     """intensity(process, convolved) / intensity(process, data) -> T x N -- src/discrete.jl:115-131"""
     ctx = ctx or _lib.default_context()

@@ -688,6 +688,29 @@ function loglikelihood(p::NHP.DiscreteHawkesProcess, data::Matrix{Int64}, c::Con
     ll[]
 end
 
+# --- residuals(process, data[, convolved]): no reference counterpart -------------------------------------------------------
+# Goodness of fit of a discrete process on its counts (nhp_disc_residuals): cell (t, c) is Poisson(λ[t,c]) with λ =
+# intensity(p, c); pit (T x N, with pit=true) is the randomized probability integral transform F(s-1) + v·p(s) of every cell,
+# uniform on [0, 1) under the model; pearson = (s-λ)/√λ; cumulative = cumsum(λ, dims=1); per node expected = Σλ, observed = Σs,
+# chi2 = Σ(s-λ)²/λ, deviance, and histogram (nbins x N) of the pit values; impossible = the cells with λ = 0 and s > 0.
+# Homogeneous baselines (the LGCP baseline goes through the dataset, as for the other discrete calls of the Python binding).
+function residuals(p::NHP.DiscreteHawkesProcess, data::Matrix{Int64}, c::Convolved=convolve(p, data); seed::Integer=0, nbins::Integer=20,
+                   pit::Bool=true, pearson::Bool=false, cumulative::Bool=false, ctx=context())
+    1 <= nbins <= 4096 || throw(ArgumentError("nbins = $nbins outside [1, 4096]"))
+    l0, W, θ, A = lowered(p)
+    plane(on) = on ? Matrix{Float64}(undef, c.T, c.N) : nothing
+    u, r, cum = plane(pit), plane(pearson), plane(cumulative)
+    expected, chi2, deviance = Vector{Float64}(undef, c.N), Vector{Float64}(undef, c.N), Vector{Float64}(undef, c.N)
+    observed, histogram, impossible = Vector{Int64}(undef, c.N), Matrix{Int64}(undef, nbins, c.N), Ref{Int64}(0)
+    GC.@preserve A u r cum check(ccall((:nhp_disc_residuals, libnhp), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, UInt64, Int32, Int32, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ref{Int64}, Ptr{Float64}),
+        ctx.h, c.h, l0, W, θ, aptr(A), p.dt, seed % UInt64, Int32(nbins), Int32(0), aptr(u), aptr(r), aptr(cum), expected, observed,
+        chi2, deviance, histogram, impossible, Ptr{Float64}(C_NULL)), ctx.h)
+    (pit=u, pearson=r, cumulative=cum, expected=expected, observed=observed, chi2=chi2, deviance=deviance, histogram=histogram,
+     impossible=impossible[])
+end
+
 # --- update!(process, data, convolved): one mean-field step  src/discrete.jl:369-375 ----------------------------------
 # (src/parents.jl:136-177 + src/baselines.jl:444-452, src/weights.jl:70-91, src/impulses.jl:355-371, fused: the
 # T x N x (1+NB) responsibilities are never formed).  Overwrites the variational parameters of the components in place

@@ -181,7 +181,14 @@ void nhp_cont_model_destroy(nhp_cont_model *model);
 nhp_status nhp_cont_loglik(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *model,
                            int32_t flags, double *ll);
 /* Asynchronous form for batches (finite-difference sweeps, chains): enqueue evaluations
- * into result slots [0, NHP_MAX_SLOTS), then fetch them with one synchronisation. */
+ * into result slots [0, NHP_MAX_SLOTS), then fetch them with one synchronisation.
+ * Ordering: evaluations enqueued in succession may run concurrently -- odd and even slots go to the context's two
+ * internal streams, so alternate the slots to overlap them; two evaluations into the same slot stay in order.  Each
+ * evaluation is ordered after every earlier call on the context that is not an enqueue (parameter uploads, dataset
+ * builds, samplers, nhp_ctx_timer_start) and before every later one (nhp_cont_model_set_params, the destroy functions,
+ * ...), so a model or dataset may be changed or destroyed right after the enqueue.  A slot's value is defined after
+ * nhp_ctx_fetch, nhp_ctx_synchronize or nhp_ctx_timer_stop.  The recursive formulation (NHP_LL_RECURSIVE,
+ * exponential impulses) is not overlapped: it is a call like any other. */
 #define NHP_MAX_SLOTS 4096
 nhp_status nhp_cont_loglik_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds,
                                    const nhp_cont_model *model, int32_t flags, int32_t slot);

@@ -104,7 +104,7 @@ extern "C" void nhp_comm_destroy(nhp_comm *comm)
     if (!comm) return;
     if (comm->ctx) {
         (void)hipSetDevice(comm->ctx->device);
-        (void)hipStreamSynchronize(comm->ctx->stream);
+        (void)hipStreamSynchronize(comm->ctx->main());
     }
     if (comm->nccl && rccl().ok) (void)rccl().CommDestroy((ncclComm_t)comm->nccl);
     delete comm;
@@ -124,7 +124,7 @@ nhp_status nhp_comm_allreduce_dev(nhp_ctx *ctx, nhp_comm *comm, double *d_buf, s
 {
     NHP_TRY(check_comm(ctx, comm));
     if (n == 0) return NHP_OK;
-    NHP_RCCL(ctx, rccl().AllReduce(d_buf, d_buf, n, ncclDouble, ncclSum, (ncclComm_t)comm->nccl, ctx->stream));
+    NHP_RCCL(ctx, rccl().AllReduce(d_buf, d_buf, n, ncclDouble, ncclSum, (ncclComm_t)comm->nccl, ctx->main()));
     return NHP_OK;
 }
 
@@ -132,7 +132,7 @@ nhp_status nhp_comm_allgather_dev(nhp_ctx *ctx, nhp_comm *comm, const double *d_
 {
     NHP_TRY(check_comm(ctx, comm));
     if (n == 0) return NHP_OK;
-    NHP_RCCL(ctx, rccl().AllGather(d_mine, d_all, n, ncclDouble, (ncclComm_t)comm->nccl, ctx->stream));
+    NHP_RCCL(ctx, rccl().AllGather(d_mine, d_all, n, ncclDouble, (ncclComm_t)comm->nccl, ctx->main()));
     return NHP_OK;
 }
 
@@ -145,7 +145,7 @@ extern "C" nhp_status nhp_allreduce_sum(nhp_ctx *ctx, nhp_comm *comm, double *x,
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, 8 * (size_t)n));
     double *d = (double *)ctx->d_scratch;
-    NHP_HIP(ctx, hipMemcpyAsync(d, x, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(d, x, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->main()));
     NHP_TRY(nhp_comm_allreduce_dev(ctx, comm, d, (size_t)n));
     return nhp_download(ctx, x, d, 8 * (size_t)n);
 }
@@ -159,7 +159,7 @@ extern "C" nhp_status nhp_allgather(nhp_ctx *ctx, nhp_comm *comm, const double *
     const size_t w = (size_t)comm->world;
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, 8 * (size_t)n * (w + 1)));
     double *d_mine = (double *)ctx->d_scratch, *d_all = d_mine + n;
-    NHP_HIP(ctx, hipMemcpyAsync(d_mine, mine, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(d_mine, mine, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->main()));
     NHP_TRY(nhp_comm_allgather_dev(ctx, comm, d_mine, (size_t)n, d_all));
     return nhp_download(ctx, all, d_all, 8 * (size_t)n * w);
 }
@@ -188,10 +188,10 @@ nhp_status nhp_grad_enqueue_reduced(nhp_ctx *ctx, nhp_comm *comm, const nhp_cont
     *d_grad_out = d_grad;
     if (!comm) return NHP_OK;
     NHP_TRY(check_comm(ctx, comm));
-    hipLaunchKernelGGL(k_pack_ll, dim3(1), dim3(1), 0, ctx->stream, ctx->d_results, d_grad - 1);
+    hipLaunchKernelGGL(k_pack_ll, dim3(1), dim3(1), 0, ctx->main(), ctx->d_results, d_grad - 1);
     NHP_HIP(ctx, hipGetLastError());
     NHP_TRY(nhp_comm_allreduce_dev(ctx, comm, d_grad - 1, (size_t)grad_len + 1));
-    NHP_HIP(ctx, hipMemcpyAsync(ctx->d_results, d_grad - 1, 8, hipMemcpyDeviceToDevice, ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(ctx->d_results, d_grad - 1, 8, hipMemcpyDeviceToDevice, ctx->main()));
     return NHP_OK;
 }
 
@@ -223,9 +223,9 @@ extern "C" nhp_status nhp_gather_moments(nhp_ctx *ctx, nhp_comm *comm, const nhp
     double *d_all = (double *)ctx->d_scratch, *d_mine4 = d_all + 2 * L * w, *d_all4 = d_mine4 + 4;
     NHP_TRY(nhp_comm_allgather_dev(ctx, comm, m->d_mom, 2 * L, d_all));
     double mine4[4] = {(double)m->mom_count, 0.0, 0.0, 0.0};
-    NHP_HIP(ctx, hipMemcpyAsync(d_mine4, mine4, 8, hipMemcpyHostToDevice, ctx->stream));
-    if (m->d_rho) NHP_HIP(ctx, hipMemcpyAsync(d_mine4 + 1, m->d_rho, 24, hipMemcpyDeviceToDevice, ctx->stream));
-    else NHP_HIP(ctx, hipMemsetAsync(d_mine4 + 1, 0, 24, ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(d_mine4, mine4, 8, hipMemcpyHostToDevice, ctx->main()));
+    if (m->d_rho) NHP_HIP(ctx, hipMemcpyAsync(d_mine4 + 1, m->d_rho, 24, hipMemcpyDeviceToDevice, ctx->main()));
+    else NHP_HIP(ctx, hipMemsetAsync(d_mine4 + 1, 0, 24, ctx->main()));
     NHP_TRY(nhp_comm_allgather_dev(ctx, comm, d_mine4, 4, d_all4));
     for (size_t r = 0; r < w; ++r) {
         NHP_TRY(nhp_download(ctx, sum_all + r * L, d_all + r * 2 * L, 8 * L));

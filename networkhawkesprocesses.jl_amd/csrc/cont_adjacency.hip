@@ -548,7 +548,7 @@ nhp_status nhp_adj_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_mo
         nhp_set_error(ctx, "resample_adjacency: a node with %d events (N = %d) exceeds the 160 KiB LDS column state", max_children, ds->N);
         return NHP_ENOTIMPL;
     }
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     nhp_cont_args a = nhp_make_args(ds, m);
     // a column shard sweeps its own columns: the columns of A are independent given the data (src/continuous.jl:444-470)
     const unsigned ncol = (unsigned)(ds->col_end - ds->col_begin);
@@ -623,7 +623,7 @@ extern "C" nhp_status nhp_cont_resample_adjacency(nhp_ctx *ctx, const nhp_cont_d
     double *d_links = nullptr;
     NHP_TRY(nhp_adj_enqueue(ctx, ds, m, rho_matrix, rho, nullptr, u, seed, step, &d_links));
     const size_t N = (size_t)ds->N, NN = N * N;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     std::vector<double> links(N);
     NHP_HIP(ctx, hipMemcpyAsync(links.data(), d_links, 8 * N, hipMemcpyDeviceToHost, st));
     NHP_HIP(ctx, hipStreamSynchronize(st));
@@ -663,7 +663,7 @@ static nhp_status ensure_rho(nhp_ctx *ctx, nhp_cont_model *m)
 {
     if (m->d_rho) return NHP_OK;
     NHP_HIP(ctx, hipMalloc((void **)&m->d_rho, 4 * sizeof(double)));
-    NHP_HIP(ctx, hipMemsetAsync(m->d_rho, 0, 4 * sizeof(double), ctx->stream));
+    NHP_HIP(ctx, hipMemsetAsync(m->d_rho, 0, 4 * sizeof(double), ctx->main()));
     return NHP_OK;
 }
 
@@ -674,8 +674,8 @@ extern "C" nhp_status nhp_cont_model_set_rho(nhp_ctx *ctx, nhp_cont_model *m, do
     if (!(rho >= 0.0 && rho <= 1.0)) { nhp_set_error(ctx, "link probability must lie in [0, 1]"); return NHP_EDOMAIN; }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(ensure_rho(ctx, m));
-    NHP_HIP(ctx, hipMemcpyAsync(m->d_rho, &rho, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));          // `rho` is a stack value
+    NHP_HIP(ctx, hipMemcpyAsync(m->d_rho, &rho, sizeof(double), hipMemcpyHostToDevice, ctx->main()));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));          // `rho` is a stack value
     return NHP_OK;
 }
 
@@ -698,12 +698,12 @@ extern "C" nhp_status nhp_cont_network_step(nhp_ctx *ctx, nhp_comm *comm, const 
     if (!comm && ds && nhp_is_column_shard(ds)) { nhp_set_error(ctx, "network_step: a column shard needs the communicator of its ranks"); return NHP_EINVAL; }
     double *d_links = nullptr;
     NHP_TRY(nhp_adj_enqueue(ctx, ds, m, nullptr, 0.5, m->d_rho, nullptr, seed, step, &d_links));
-    hipLaunchKernelGGL(k_links_total, dim3(1), dim3(256), 0, ctx->stream, d_links, ds->N, m->d_rho);
+    hipLaunchKernelGGL(k_links_total, dim3(1), dim3(256), 0, ctx->main(), d_links, ds->N, m->d_rho);
     NHP_HIP(ctx, hipGetLastError());
     if (comm) NHP_TRY(nhp_comm_allreduce_dev(ctx, comm, m->d_rho + 3, 1));      // the shards' link counts (a one-rank clique runs the same call)
     const double nn = (double)ds->N * (double)ds->N;
     if (!fixed) {
-        hipLaunchKernelGGL(k_rho_draw, dim3(1), dim3(64), 0, ctx->stream, m->d_rho, alpha, beta, nn, seed, step);
+        hipLaunchKernelGGL(k_rho_draw, dim3(1), dim3(64), 0, ctx->main(), m->d_rho, alpha, beta, nn, seed, step);
         NHP_HIP(ctx, hipGetLastError());
     }
     return NHP_OK;
@@ -716,7 +716,7 @@ extern "C" nhp_status nhp_cont_network_sweep(nhp_ctx *ctx, const nhp_cont_datase
     if (!m->d_rho) { nhp_set_error(ctx, "network_sweep: set the link probability first (nhp_cont_model_set_rho)"); return NHP_EINVAL; }
     double *d_links = nullptr;
     NHP_TRY(nhp_adj_enqueue(ctx, ds, m, nullptr, 0.5, m->d_rho, nullptr, seed, step, &d_links));
-    hipLaunchKernelGGL(k_links_total, dim3(1), dim3(256), 0, ctx->stream, d_links, ds->N, m->d_rho);
+    hipLaunchKernelGGL(k_links_total, dim3(1), dim3(256), 0, ctx->main(), d_links, ds->N, m->d_rho);
     NHP_HIP(ctx, hipGetLastError());
     return nhp_download(ctx, n_links, m->d_rho + 3, sizeof(double));
 }
@@ -730,10 +730,10 @@ extern "C" nhp_status nhp_cont_network_rho(nhp_ctx *ctx, nhp_cont_model *m, doub
     if (alpha == 0.0 && beta == 0.0) return NHP_OK;
     if (!(alpha > 0.0 && beta > 0.0) || !(n_links >= 0.0 && n_links <= n_entries)) { nhp_set_error(ctx, "network_rho: bad Beta parameters"); return NHP_EDOMAIN; }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
-    NHP_HIP(ctx, hipMemcpyAsync(m->d_rho + 3, &n_links, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_rho_draw, dim3(1), dim3(64), 0, ctx->stream, m->d_rho, alpha, beta, n_entries, seed, step);
+    NHP_HIP(ctx, hipMemcpyAsync(m->d_rho + 3, &n_links, sizeof(double), hipMemcpyHostToDevice, ctx->main()));
+    hipLaunchKernelGGL(k_rho_draw, dim3(1), dim3(64), 0, ctx->main(), m->d_rho, alpha, beta, n_entries, seed, step);
     NHP_HIP(ctx, hipGetLastError());
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));                       // n_links is a stack value
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));                       // n_links is a stack value
     return NHP_OK;
 }
 

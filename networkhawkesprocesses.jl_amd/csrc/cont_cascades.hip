@@ -108,7 +108,7 @@ extern "C" nhp_status nhp_cont_map_parents(nhp_ctx *ctx, const nhp_cont_dataset 
     if (M == 0 || ds->n_items == 0) return NHP_OK;
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_check_deferred(ctx));
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     int64_t *o_par = parents, *o_pno = parentnodes;
     double *o_prob = prob;
     if (!output_on_device) {
@@ -306,7 +306,7 @@ extern "C" nhp_status nhp_cont_cascades(nhp_ctx *ctx, const nhp_cont_dataset *ds
     NHP_WHOLE_DATASET(ctx, ds, "cascades");
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_check_deferred(ctx));
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     const size_t M = (size_t)ds->M, N = (size_t)ds->N, NN = N * N, Mp = M ? M : 1;
     const bool casc = n_casc_out == 4, host_out = !output_on_device;
     const size_t nb = (Mp + CASC_BLOCK - 1) / CASC_BLOCK;

@@ -264,7 +264,7 @@ extern "C" nhp_status nhp_cont_compensator(nhp_ctx *ctx, const nhp_cont_dataset 
     }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_check_deferred(ctx));
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     const bool events = (at_events || residuals) && M > 0;
     const bool finite = ds->dt_max < INFINITY && M > 0;
     const size_t rows = finite ? M / COMP_CHUNK + 1 : 0, groups = (rows + COMP_GROUP - 1) / COMP_GROUP;

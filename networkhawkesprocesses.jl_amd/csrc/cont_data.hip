@@ -23,7 +23,7 @@ static nhp_status upload(nhp_ctx *ctx, T **dst, const T *src, size_t n)
     *dst = nullptr;
     if (n == 0) n = 1;
     NHP_HIP(ctx, hipMalloc((void **)dst, sizeof(T) * n));
-    if (src) NHP_HIP(ctx, hipMemcpyAsync(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice, ctx->stream));
+    if (src) NHP_HIP(ctx, hipMemcpyAsync(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice, ctx->main()));
     return NHP_OK;
 }
 
@@ -366,7 +366,7 @@ extern "C" nhp_status nhp_cont_dataset_create_columns(nhp_ctx *ctx, const double
         nhp_cont_dataset_destroy(ds);
         return NHP_ENOMEM;
     }
-    hipError_t e = hipStreamSynchronize(ctx->stream);   // host vectors go out of scope below
+    hipError_t e = hipStreamSynchronize(ctx->main());   // host vectors go out of scope below
     if (e != hipSuccess) { nhp_set_error(ctx, "upload failed: %s", hipGetErrorString(e)); nhp_cont_dataset_destroy(ds); return NHP_EHIP; }
     lap("uploads");
     *out = ds;
@@ -384,8 +384,8 @@ nhp_status nhp_dataset_slab_stats(nhp_ctx *ctx, const nhp_cont_dataset *cds)
     const int64_t M = ds->M;
     if (M <= 1) return NHP_OK;
     std::vector<double> events((size_t)M);
-    NHP_HIP(ctx, hipMemcpyAsync(events.data(), ds->d_times, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(events.data(), ds->d_times, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, ctx->main()));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     if (!(events[M - 1] > events[0])) return NHP_OK;
     const double span = events[M - 1] - events[0];
     std::vector<double> lens;
@@ -417,7 +417,7 @@ extern "C" void nhp_cont_dataset_destroy(nhp_cont_dataset *ds)
 {
     if (!ds) return;
     (void)hipSetDevice(ds->ctx->device);
-    (void)hipStreamSynchronize(ds->ctx->stream);
+    (void)hipStreamSynchronize(ds->ctx->main());
     (void)hipFree(ds->d_times); (void)hipFree(ds->d_nodes); (void)hipFree(ds->d_child); (void)hipFree(ds->d_child_w); (void)hipFree(ds->d_wpos); (void)hipFree(ds->d_ev); (void)hipFree(ds->d_ev8); (void)hipFree(ds->d_poff); (void)hipFree(ds->d_plist); (void)hipFree(ds->d_plq); (void)hipFree(ds->d_pnode);
     (void)hipFree(ds->d_sl_row); (void)hipFree(ds->d_sl_item0); (void)hipFree(ds->d_sl_lo); (void)hipFree(ds->d_sl_hi);
     (void)hipFree(ds->d_sl_L); (void)hipFree(ds->d_sl_Q); (void)hipFree(ds->d_sl_D);
@@ -460,8 +460,8 @@ extern "C" nhp_status nhp_cont_dataset_export(nhp_ctx *ctx, const nhp_cont_datas
     if (cap_bytes < (int64_t)n) { nhp_set_error(ctx, "dataset array %d needs %lld bytes, %lld given", which, (long long)n, (long long)cap_bytes); return NHP_ESHAPE; }
     if (host) { memcpy(out, src, n); return NHP_OK; }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
-    NHP_HIP(ctx, hipMemcpyAsync(out, src, n, hipMemcpyDeviceToHost, ctx->stream));
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(out, src, n, hipMemcpyDeviceToHost, ctx->main()));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     return NHP_OK;
 }
 
@@ -503,7 +503,7 @@ static nhp_status copy_params(nhp_ctx *ctx, nhp_cont_model *m, const nhp_cont_mo
 {
     ++m->version;
     size_t NN = (size_t)m->N * m->N;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     NHP_HIP(ctx, hipMemcpyAsync(m->d_lambda0, d->lambda0, sizeof(double) * nhp_layout(m).nb, hipMemcpyHostToDevice, st));
     if (m->grid_n) {
         NHP_HIP(ctx, hipMemcpyAsync(m->d_grid, d->grid_x, sizeof(double) * m->grid_n, hipMemcpyHostToDevice, st));
@@ -572,8 +572,8 @@ extern "C" nhp_status nhp_cont_model_set_params(nhp_ctx *ctx, nhp_cont_model *m,
     NHP_TRY(nhp_layout_check(ctx, L, len));
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     ++m->version;
-    NHP_HIP(ctx, hipMemcpyAsync(m->d_params, x, sizeof(double) * L.P, hipMemcpyHostToDevice, ctx->stream));
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(m->d_params, x, sizeof(double) * L.P, hipMemcpyHostToDevice, ctx->main()));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     return NHP_OK;
 }
 
@@ -603,7 +603,7 @@ extern "C" void nhp_cont_model_destroy(nhp_cont_model *m)
 {
     if (!m) return;
     (void)hipSetDevice(m->ctx->device);
-    (void)hipStreamSynchronize(m->ctx->stream);
+    (void)hipStreamSynchronize(m->ctx->main());
     (void)hipFree(m->d_mom); (void)hipFree(m->d_rho);
     (void)hipFree(m->d_params); (void)hipFree(m->d_grid); (void)hipFree(m->d_A);
     delete m;

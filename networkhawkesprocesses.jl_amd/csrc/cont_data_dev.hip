@@ -199,7 +199,7 @@ static nhp_status dd_create(nhp_ctx *ctx, const double *events, const int64_t *n
         fprintf(stderr, "[nhp dataset, device] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
         t_last = now;
     };
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     const unsigned gM = dd_grid(M, DD_BLOCK);
     const unsigned ntM = dd_grid(M, DD_TILE);
     const bool want_bounds = N >= 8 && M >= 16 * (int64_t)N;    // the XCD layout's time parts are possible

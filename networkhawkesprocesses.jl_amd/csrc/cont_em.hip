@@ -248,8 +248,8 @@ nhp_status em_estep(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *m,
     if (ds->M == 0) {
         NHP_TRY(nhp_ctx_reserve_scratch(ctx, 8 * (2 + (size_t)P)));
         double *g = (double *)ctx->d_scratch + 2;
-        NHP_HIP(ctx, hipMemsetAsync(g, 0, 8 * (size_t)P, ctx->stream));
-        hipLaunchKernelGGL(k_em_empty, dim3(1), dim3(256), 0, ctx->stream, m->N, ds->duration, d_x, g, ctx->d_results);
+        NHP_HIP(ctx, hipMemsetAsync(g, 0, 8 * (size_t)P, ctx->main()));
+        hipLaunchKernelGGL(k_em_empty, dim3(1), dim3(256), 0, ctx->main(), m->N, ds->duration, d_x, g, ctx->d_results);
         NHP_HIP(ctx, hipGetLastError());
         *d_grad = g;
         return NHP_OK;
@@ -287,7 +287,7 @@ extern "C" nhp_status nhp_cont_em_stats(nhp_ctx *ctx, const nhp_cont_dataset *ds
     NHP_TRY(nhp_ctx_reserve_mle(ctx, 8 * (N + 3 * NN), "EM state"));
     const double *d_x = m->d_params;
     double *o_bg = (double *)ctx->d_mle, *o_EM = o_bg + N, *o_S1 = o_EM + NN, *o_S2 = S2 ? o_S1 + NN : nullptr;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     double *d_grad = nullptr;
     nhp_cont_model mm = *m;                                           // (the E-step bumps the version of what it evaluates)
     NHP_TRY(em_estep(ctx, ds, &mm, flags, d_x, P, &d_grad));
@@ -322,7 +322,7 @@ extern "C" nhp_status nhp_cont_em_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, 
     NHP_TRY(nhp_layout_check(ctx, nhp_layout(m), len));
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_check_deferred(ctx));
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     em_host hs;
     if (hipHostMalloc((void **)&hs.h, 8) != hipSuccess) { hs.h = nullptr; nhp_set_error(ctx, "out of pinned memory"); return NHP_ENOMEM; }
     NHP_HIP(ctx, hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));

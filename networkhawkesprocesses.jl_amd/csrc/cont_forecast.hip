@@ -368,7 +368,7 @@ extern "C" nhp_status nhp_cont_forecast(nhp_ctx *ctx, const nhp_cont_dataset *ds
     }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_check_deferred(ctx));
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     if (phase_ms) phase_ms[0] = phase_ms[1] = 0.0;
 
     // ---- results that leave through a staging copy when the caller's pointers are host memory

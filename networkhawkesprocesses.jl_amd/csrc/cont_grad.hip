@@ -307,7 +307,7 @@ nhp_status nhp_grad_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_
     double *d_grad = (double *)ctx->d_scratch + 2, *d_lambda = d_grad + P;
     *d_grad_out = d_grad;
     nhp_cont_args a = nhp_make_args(ds, m);
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     // the recursive formulation through its truncated window when the bound allows (cont_recursive.hip): the windowed
     // gradient on the other window starts, with the recursion's unmasked integral
     const nhp_child *child_cut = nullptr;

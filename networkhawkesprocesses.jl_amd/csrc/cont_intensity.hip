@@ -109,7 +109,7 @@ extern "C" nhp_status nhp_cont_intensity(nhp_ctx *ctx, const nhp_cont_dataset *d
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, 8 * (3 * NN + (size_t)Q + (size_t)Q * N)));
     double *r1 = (double *)ctx->d_scratch, *r2 = r1 + NN, *r3 = r2 + NN, *dq = r3 + NN, *dout = dq + Q;
     nhp_cont_args a = nhp_make_args(ds, m);
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     NHP_HIP(ctx, hipMemcpyAsync(dq, times, 8 * (size_t)Q, hipMemcpyHostToDevice, st));
     dim3 tg((unsigned)((N + 31) / 32), (unsigned)((N + 31) / 32));
     hipLaunchKernelGGL(k_transpose_params, tg, dim3(256), 0, st, a, r1, r2, r3);

@@ -76,7 +76,7 @@ extern "C" nhp_status nhp_cont_lgcp_loglik(nhp_ctx *ctx, const nhp_cont_dataset 
     const size_t o_x = carve(8 * G), o_lam = carve(8 * N * G), o_ll = carve(8 * N), o_pn = carve(parentnodes ? 8 * (M ? M : 1) : 8);
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, off));
     char *base = (char *)ctx->d_scratch;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     if (parentnodes && M) {
         for (size_t i = 0; i < M; ++i)
             if (parentnodes[i] < 0 || parentnodes[i] > (int64_t)N) { nhp_set_error(ctx, "lgcp_loglik: parentnodes[%zu] outside 0..N", i); return NHP_EDOMAIN; }

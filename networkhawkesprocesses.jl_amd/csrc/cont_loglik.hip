@@ -839,13 +839,13 @@ static nhp_status enqueue_batch(nhp_ctx *ctx, const nhp_cont_dataset *ds, const 
     dim3 grid((unsigned)ds->n_items);
     if (expo && a.ev8) {
         if (lds > 64 * 1024) NHP_HIP(ctx, hipFuncSetAttribute((const void *)k_windowed_batch<NHP_IMPULSE_EXPONENTIAL, S, THREADS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((k_windowed_batch<NHP_IMPULSE_EXPONENTIAL, S, THREADS, true>), grid, dim3(THREADS), lds, ctx->stream, a, mm, ctx->d_partials, ctx->d_counter);
+        hipLaunchKernelGGL((k_windowed_batch<NHP_IMPULSE_EXPONENTIAL, S, THREADS, true>), grid, dim3(THREADS), lds, ctx->lane(), a, mm, ctx->d_partials, ctx->d_counter);
     } else if (expo) {
         if (lds > 64 * 1024) NHP_HIP(ctx, hipFuncSetAttribute((const void *)k_windowed_batch<NHP_IMPULSE_EXPONENTIAL, S, THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((k_windowed_batch<NHP_IMPULSE_EXPONENTIAL, S, THREADS>), grid, dim3(THREADS), lds, ctx->stream, a, mm, ctx->d_partials, ctx->d_counter);
+        hipLaunchKernelGGL((k_windowed_batch<NHP_IMPULSE_EXPONENTIAL, S, THREADS>), grid, dim3(THREADS), lds, ctx->lane(), a, mm, ctx->d_partials, ctx->d_counter);
     } else {
         if (lds > 64 * 1024) NHP_HIP(ctx, hipFuncSetAttribute((const void *)k_windowed_batch<NHP_IMPULSE_LOGITNORMAL, S, THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((k_windowed_batch<NHP_IMPULSE_LOGITNORMAL, S, THREADS>), grid, dim3(THREADS), lds, ctx->stream, a, mm, ctx->d_partials, ctx->d_counter);
+        hipLaunchKernelGGL((k_windowed_batch<NHP_IMPULSE_LOGITNORMAL, S, THREADS>), grid, dim3(THREADS), lds, ctx->lane(), a, mm, ctx->d_partials, ctx->d_counter);
     }
     NHP_HIP(ctx, hipGetLastError());
     return NHP_OK;
@@ -941,7 +941,7 @@ static nhp_status run_windowed(nhp_ctx *ctx, const nhp_cont_dataset *ds, const n
                 mds->d_plist = nullptr;
                 (void)hipGetLastError();
             } else {
-                hipLaunchKernelGGL(k_pairs_build, dim3((unsigned)((ds->M + 255) / 256)), dim3(256), 0, ctx->stream, a, mds->d_plist);
+                hipLaunchKernelGGL(k_pairs_build, dim3((unsigned)((ds->M + 255) / 256)), dim3(256), 0, ctx->main(), a, mds->d_plist);
                 NHP_HIP(ctx, hipGetLastError());
                 a.plist = mds->d_plist;
             }
@@ -959,12 +959,12 @@ static nhp_status run_windowed(nhp_ctx *ctx, const nhp_cont_dataset *ds, const n
         if (expo_p) {                                                                                         \
             if (lds2 > 64 * 1024)                                                                             \
                 (void)hipFuncSetAttribute((const void *)k_windowed_pairs<NHP_IMPULSE_EXPONENTIAL, g, u, b>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); \
-            hipLaunchKernelGGL((k_windowed_pairs<NHP_IMPULSE_EXPONENTIAL, g, u, b>), grid, dim3(b), lds2, ctx->stream, a, mask_integral, ds->max_item, \
+            hipLaunchKernelGGL((k_windowed_pairs<NHP_IMPULSE_EXPONENTIAL, g, u, b>), grid, dim3(b), lds2, ctx->lane(), a, mask_integral, ds->max_item, \
                                ctx->d_partials, d_lambda, ctx->d_counter, d_out);                                       \
         } else {                                                                                              \
             if (lds2 > 64 * 1024)                                                                             \
                 (void)hipFuncSetAttribute((const void *)k_windowed_pairs<NHP_IMPULSE_LOGITNORMAL, g, u, b>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); \
-            hipLaunchKernelGGL((k_windowed_pairs<NHP_IMPULSE_LOGITNORMAL, g, u, b>), grid, dim3(b), lds2, ctx->stream, a, mask_integral, ds->max_item, \
+            hipLaunchKernelGGL((k_windowed_pairs<NHP_IMPULSE_LOGITNORMAL, g, u, b>), grid, dim3(b), lds2, ctx->lane(), a, mask_integral, ds->max_item, \
                                ctx->d_partials, d_lambda, ctx->d_counter, d_out);                                       \
         }                                                                                                     \
     }
@@ -979,63 +979,81 @@ static nhp_status run_windowed(nhp_ctx *ctx, const nhp_cont_dataset *ds, const n
         }
     }
     if (m->impulse_kind == NHP_IMPULSE_EXPONENTIAL)
-        launch_group<NHP_IMPULSE_EXPONENTIAL>(G, grid, lds, ctx->stream, a, mask_integral, ctx->d_partials, d_lambda, ctx->d_counter, d_out);
+        launch_group<NHP_IMPULSE_EXPONENTIAL>(G, grid, lds, ctx->lane(), a, mask_integral, ctx->d_partials, d_lambda, ctx->d_counter, d_out);
     else
-        launch_group<NHP_IMPULSE_LOGITNORMAL>(G, grid, lds, ctx->stream, a, mask_integral, ctx->d_partials, d_lambda, ctx->d_counter, d_out);
+        launch_group<NHP_IMPULSE_LOGITNORMAL>(G, grid, lds, ctx->lane(), a, mask_integral, ctx->d_partials, d_lambda, ctx->d_counter, d_out);
     NHP_HIP(ctx, hipGetLastError());
     return NHP_OK;
 }
 
 nhp_status nhp_launch_finalize(nhp_ctx *ctx, const nhp_cont_args &a, int n_partials, double *d_out)
 {
-    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(NHP_BLOCK), 0, ctx->stream, a, ctx->d_partials, n_partials, d_out);
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(NHP_BLOCK), 0, ctx->main(), a, ctx->d_partials, n_partials, d_out);
     NHP_HIP(ctx, hipGetLastError());
     return NHP_OK;
 }
 
+// The launchers the other translation units call (mle, mcmc, em, grad, the recursive route): on the main stream, after a
+// join -- run_windowed's launch lines take the lane's raw stream, which only nhp_cont_loglik_enqueue / _batch may skip to.
 nhp_status nhp_launch_windowed(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, double *d_out)
 {
+    ctx->join_lanes();
     return run_windowed(ctx, ds, m, d_out, nullptr);
 }
 
 nhp_status nhp_launch_windowed_as(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const nhp_child *child_w,
                                   int group, int mask_integral, double *d_out)
 {
+    ctx->join_lanes();
     return run_windowed(ctx, ds, m, d_out, nullptr, child_w, group, mask_integral);
 }
 
 nhp_status nhp_launch_event_intensity_as(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const nhp_child *child_w,
                                          int group, int mask_integral, double *d_lambda)
 {
+    ctx->join_lanes();
     return run_windowed(ctx, ds, m, nullptr, d_lambda, child_w, group, mask_integral);
 }
 
 nhp_status nhp_launch_event_intensity(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, double *d_lambda)
 {
+    ctx->join_lanes();
     return run_windowed(ctx, ds, m, nullptr, d_lambda);
 }
 
 // ---- C ABI ------------------------------------------------------------------------------
 
+// One evaluation on the context's current lane (the caller has flipped or not).  The windowed routes are one launch with
+// the fused reduction and take lane(); the recursive route has several launches and a read-back and stays on main().
+static bool recursive_route(const nhp_cont_model *m, int32_t flags)
+{
+    return m && (flags & NHP_LL_RECURSIVE) && m->impulse_kind == NHP_IMPULSE_EXPONENTIAL;
+}
+
 static nhp_status enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int32_t flags, int32_t slot)
 {
     NHP_TRY(nhp_check_pair(ctx, ds, m));
     if (slot < 0 || slot >= NHP_MAX_SLOTS) return NHP_EINVAL;
-    if ((flags & NHP_LL_RECURSIVE) && m->impulse_kind == NHP_IMPULSE_EXPONENTIAL)
-        return nhp_launch_recursive_flags(ctx, ds, m, flags, ctx->d_results + slot);
-    return nhp_launch_windowed(ctx, ds, m, ctx->d_results + slot);
+    if (recursive_route(m, flags)) return nhp_launch_recursive_flags(ctx, ds, m, flags, ctx->d_results + slot);
+    return run_windowed(ctx, ds, m, ctx->d_results + slot, nullptr);
 }
 
+// Odd slots go to the second lane, even ones stay on the main stream: two evaluations into one slot share a lane and stay
+// ordered, successive slots alternate and overlap (include/nhp.h: the ordering contract).
 extern "C" nhp_status nhp_cont_loglik_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds,
                                               const nhp_cont_model *m, int32_t flags, int32_t slot)
 {
+    if (!ctx) return NHP_EINVAL;
+    nhp_lane_guard lane{ctx};
+    if ((slot & 1) && ctx->stream2 && !recursive_route(m, flags)) lane.flip();
     return enqueue(ctx, ds, m, flags, slot);
 }
 
 extern "C" nhp_status nhp_cont_loglik(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m,
                                       int32_t flags, double *ll)
 {
-    if (!ll) return NHP_EINVAL;
+    if (!ll || !ctx) return NHP_EINVAL;
+    ctx->join_lanes();                                      // a call like any other: after both lanes, on the main stream
     NHP_TRY(enqueue(ctx, ds, m, flags, 0));
     return nhp_ctx_fetch(ctx, 0, 1, ll);
 }
@@ -1057,15 +1075,10 @@ extern "C" nhp_status nhp_cont_loglik_batch(nhp_ctx *ctx, const nhp_cont_dataset
     const double kbar = ds && ds->M > 0 ? (double)ds->pairs / (double)ds->M : 0.0;
     // Windowed launches alternate between the context's two lanes (stream + partial sums + tickets each): they are
     // independent -- different result slots, read-only data and models -- so the second lane forks from the main stream
-    // (everything enqueued before this call, e.g. parameter uploads, is visible to it) and joins it before the results
-    // are fetched.  The lane is switched by swapping the context's fields around a launch, so the launch code is shared.
-    struct lane_guard {
-        nhp_ctx *c; bool on = false;
-        void flip() { std::swap(c->stream, c->stream2); std::swap(c->d_partials, c->d_partials2); std::swap(c->partials_cap, c->partials2_cap);
-                      std::swap(c->d_counter, c->d_counter2); on = !on; }
-        ~lane_guard() { if (on) flip(); }
-    } lane{ctx};
-    bool forked = false;
+    // at its first launch (everything enqueued before this call, e.g. parameter uploads, is visible to it) and the main
+    // stream joins it before the results are fetched: lane() and main() see to both (nhp_internal.h).
+    if (ctx) ctx->join_lanes();                             // joins a streak of enqueues: the tickets of lane 2 are back at 0
+    nhp_lane_guard lane{ctx};
     int launches = 0;
     for (int32_t done = 0; done < nb; done += NHP_MAX_SLOTS) {
         const int32_t n = nb - done < NHP_MAX_SLOTS ? nb - done : NHP_MAX_SLOTS;
@@ -1089,14 +1102,7 @@ extern "C" nhp_status nhp_cont_loglik_batch(nhp_ctx *ctx, const nhp_cont_dataset
                 else if (all_compatible(2) && batch_lds<2>(ds, expo0, NHP_BATCH_THREADS(2)) <= cap) take = 2;
             }
             const bool second = windowed && ctx && ctx->stream2 && (launches & 1);
-            if (second) {
-                if (!forked) {
-                    NHP_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-                    NHP_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-                    forked = true;
-                }
-                lane.flip();
-            }
+            if (second) lane.flip();
             for (int q = 1; q < take; ++q) NHP_TRY(nhp_check_pair(ctx, ds, ms[q]));
             // exponential models on a dataset with child slices: four (or two) at a time through ONE pass over the slices
             // (cont_slices.hip: every pair record fetched and decoded once for all of them)
@@ -1119,12 +1125,7 @@ extern "C" nhp_status nhp_cont_loglik_batch(nhp_ctx *ctx, const nhp_cont_dataset
             if (windowed) ++launches;
             k += take;
         }
-        if (forked) {                                       // the main stream continues after the second lane's launches
-            NHP_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-            NHP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-            forked = false;
-        }
-        NHP_TRY(nhp_ctx_fetch(ctx, 0, n, ll + done));
+        NHP_TRY(nhp_ctx_fetch(ctx, 0, n, ll + done));           // (joins the second lane's launches)
     }
     return NHP_OK;
 }
@@ -1137,7 +1138,7 @@ extern "C" nhp_status nhp_cont_event_intensity(nhp_ctx *ctx, const nhp_cont_data
     NHP_WHOLE_DATASET(ctx, ds, "event_intensity");
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, sizeof(double) * (size_t)(ds->M > 0 ? ds->M : 1)));
     NHP_TRY(nhp_launch_event_intensity(ctx, ds, m, (double *)ctx->d_scratch));
-    NHP_HIP(ctx, hipMemcpyAsync(lambda, ctx->d_scratch, sizeof(double) * (size_t)ds->M, hipMemcpyDeviceToHost, ctx->stream));
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(lambda, ctx->d_scratch, sizeof(double) * (size_t)ds->M, hipMemcpyDeviceToHost, ctx->main()));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     return NHP_OK;
 }

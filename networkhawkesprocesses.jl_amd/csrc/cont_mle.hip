@@ -25,7 +25,7 @@ extern "C" nhp_status nhp_cont_mle_run(nhp_ctx *ctx, nhp_comm *comm, const nhp_c
     // evaluated straight from the optimizer's vector through nhp_model_view, so no parameter is copied per evaluation; the
     // run's last call (commit) copies the iterate into the model's own block and evaluates there.
     auto eval = [&](const double *d_x, double *d_g, bool commit) -> nhp_status {
-        hipStream_t st = ctx->stream;
+        hipStream_t st = ctx->main();
         ++m->version;
         if (commit) NHP_HIP(ctx, hipMemcpyAsync(m->d_params, d_x, 8 * (size_t)P, hipMemcpyDeviceToDevice, st));
         nhp_cont_model view = commit ? *m : nhp_model_view(m, d_x);
@@ -75,16 +75,16 @@ extern "C" nhp_status nhp_probe_lbfgs(nhp_ctx *ctx, int64_t n, const double *h, 
     const int nblk = 64;
     if (hipMalloc((void **)&d_h, 8 * (2 * (size_t)n + nblk)) != hipSuccess) return NHP_ENOMEM;
     double *d_c = d_h + n, *d_part = d_c + n;
-    NHP_HIP(ctx, hipMemcpyAsync(d_h, h, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    NHP_HIP(ctx, hipMemcpyAsync(d_c, c, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(d_h, h, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->main()));
+    NHP_HIP(ctx, hipMemcpyAsync(d_c, c, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->main()));
     auto eval = [&](const double *d_x, double *d_g, bool) -> nhp_status {
-        hipLaunchKernelGGL(k_probe_quad, dim3(nblk), dim3(256), 0, ctx->stream, d_x, (const double *)d_h, (const double *)d_c, n, d_g, d_part);
-        hipLaunchKernelGGL(k_probe_quad_final, dim3(1), dim3(64), 0, ctx->stream, (const double *)d_part, nblk, ctx->d_results);
+        hipLaunchKernelGGL(k_probe_quad, dim3(nblk), dim3(256), 0, ctx->main(), d_x, (const double *)d_h, (const double *)d_c, n, d_g, d_part);
+        hipLaunchKernelGGL(k_probe_quad_final, dim3(1), dim3(64), 0, ctx->main(), (const double *)d_part, nblk, ctx->d_results);
         NHP_HIP(ctx, hipGetLastError());
         return NHP_OK;
     };
     const nhp_status rc = nhp_lbfgs_box(ctx, n, lower, upper, f_abstol, max_steps, eval, x, loss, steps_out, converged_out, evals_out);
-    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipStreamSynchronize(ctx->main());
     (void)hipFree(d_h);
     return rc;
 }

@@ -264,11 +264,11 @@ static nhp_status rec_cut_for(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nh
     const int blocks = 64;
     NHP_TRY(nhp_ctx_reserve_partials(ctx, 3 * (size_t)blocks));
     nhp_cont_args a = nhp_make_args(ds, m);
-    hipLaunchKernelGGL(k_rec_stats, dim3(blocks), dim3(256), 0, ctx->stream, a, ctx->d_partials);
+    hipLaunchKernelGGL(k_rec_stats, dim3(blocks), dim3(256), 0, ctx->main(), a, ctx->d_partials);
     NHP_HIP(ctx, hipGetLastError());
     double h[3 * 64];
-    NHP_HIP(ctx, hipMemcpyAsync(h, ctx->d_partials, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(h, ctx->d_partials, sizeof(h), hipMemcpyDeviceToHost, ctx->main()));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     double tmin = h[0], wmax = h[1], lmin = h[2];
     for (int b = 1; b < blocks; ++b) {
         if (h[3 * b] < tmin || h[3 * b] != h[3 * b]) tmin = h[3 * b];
@@ -328,14 +328,14 @@ nhp_status nhp_recursive_window(nhp_ctx *ctx, const nhp_cont_dataset *ds, const 
     }
     if (ds->cut_cached != cut) {
         unsigned long long *d_pairs = reinterpret_cast<unsigned long long *>(ctx->d_counter + 32 * (NHP_REC_PAIR_SLOT));
-        NHP_HIP(ctx, hipMemsetAsync(d_pairs, 0, sizeof(unsigned long long), ctx->stream));
-        hipLaunchKernelGGL(k_rec_windows, dim3((unsigned)((ds->M + 255) / 256)), dim3(256), 0, ctx->stream, ds->d_child, ds->d_times,
+        NHP_HIP(ctx, hipMemsetAsync(d_pairs, 0, sizeof(unsigned long long), ctx->main()));
+        hipLaunchKernelGGL(k_rec_windows, dim3((unsigned)((ds->M + 255) / 256)), dim3(256), 0, ctx->main(), ds->d_child, ds->d_times,
                            ds->M, cut, (int)ds->n_zero_time, mds->d_child_cut, d_pairs);
         NHP_HIP(ctx, hipGetLastError());
         unsigned long long hp = 0;
-        NHP_HIP(ctx, hipMemcpyAsync(&hp, d_pairs, sizeof(hp), hipMemcpyDeviceToHost, ctx->stream));
-        NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        NHP_HIP(ctx, hipMemsetAsync(d_pairs, 0, sizeof(unsigned long long), ctx->stream));    // counters rest at 0
+        NHP_HIP(ctx, hipMemcpyAsync(&hp, d_pairs, sizeof(hp), hipMemcpyDeviceToHost, ctx->main()));
+        NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
+        NHP_HIP(ctx, hipMemsetAsync(d_pairs, 0, sizeof(unsigned long long), ctx->main()));    // counters rest at 0
         ds->cut_cached = cut;
         ds->cut_pairs = (int64_t)hp;
     }
@@ -370,9 +370,9 @@ static nhp_status rec_parts_build(nhp_ctx *ctx, const nhp_cont_dataset *ds, int 
     const size_t M = (size_t)ds->M;
     std::vector<double> t(M ? M : 1);
     std::vector<int32_t> node(M ? M : 1);
-    NHP_HIP(ctx, hipMemcpyAsync(t.data(), ds->d_times, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->stream));
-    NHP_HIP(ctx, hipMemcpyAsync(node.data(), ds->d_nodes, sizeof(int32_t) * M, hipMemcpyDeviceToHost, ctx->stream));
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(t.data(), ds->d_times, sizeof(double) * M, hipMemcpyDeviceToHost, ctx->main()));
+    NHP_HIP(ctx, hipMemcpyAsync(node.data(), ds->d_nodes, sizeof(int32_t) * M, hipMemcpyDeviceToHost, ctx->main()));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     std::vector<int32_t> poff((size_t)H + 1, 0), seen((size_t)H, 0), rank((size_t)H * (M ? M : 1));
     for (size_t i = 0; i < M; ++i)
         if (t[i] > 0.0) poff[(size_t)(node[i] / np) + 1]++;
@@ -397,10 +397,10 @@ static nhp_status rec_parts_build(nhp_ctx *ctx, const nhp_cont_dataset *ds, int 
         nhp_set_error(ctx, "out of device memory (recursion: per-part event lists)");
         return NHP_ENOMEM;
     }
-    NHP_HIP(ctx, hipMemcpyAsync(mds->d_rec_ev, ev.data(), sizeof(nhp_event) * ev.size(), hipMemcpyHostToDevice, ctx->stream));
-    NHP_HIP(ctx, hipMemcpyAsync(mds->d_rec_poff, poff.data(), sizeof(int32_t) * poff.size(), hipMemcpyHostToDevice, ctx->stream));
-    NHP_HIP(ctx, hipMemcpyAsync(mds->d_rec_rank, rank.data(), sizeof(int32_t) * rank.size(), hipMemcpyHostToDevice, ctx->stream));
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the host vectors go out of scope
+    NHP_HIP(ctx, hipMemcpyAsync(mds->d_rec_ev, ev.data(), sizeof(nhp_event) * ev.size(), hipMemcpyHostToDevice, ctx->main()));
+    NHP_HIP(ctx, hipMemcpyAsync(mds->d_rec_poff, poff.data(), sizeof(int32_t) * poff.size(), hipMemcpyHostToDevice, ctx->main()));
+    NHP_HIP(ctx, hipMemcpyAsync(mds->d_rec_rank, rank.data(), sizeof(int32_t) * rank.size(), hipMemcpyHostToDevice, ctx->main()));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));          // the host vectors go out of scope
     mds->rec_np = np; mds->rec_h = H;
     return NHP_OK;
 }
@@ -433,7 +433,7 @@ nhp_status nhp_launch_recursive_waves(nhp_ctx *ctx, const nhp_cont_dataset *ds, 
         do {                                                                                                                     \
             if (lds > 64 * 1024)                                                                                                 \
                 (void)hipFuncSetAttribute((const void *)k_recursive_waves<Q, HH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_recursive_waves<Q, HH>), dim3((unsigned)(ds->col_end - ds->col_begin)), dim3(64 * HH), lds, ctx->stream, \
+            hipLaunchKernelGGL((k_recursive_waves<Q, HH>), dim3((unsigned)(ds->col_end - ds->col_begin)), dim3(64 * HH), lds, ctx->main(), \
                                a, rp, ctx->d_partials, d_ginv);                                                                  \
         } while (0)
     NHP_REC_SHAPES(NHP_RECW);

@@ -148,7 +148,7 @@ nhp_status nhp_ensure_pair_cache(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_c
             a->plq = nullptr; a->pnode = nullptr;
             return NHP_EINVAL;
         }
-        hipLaunchKernelGGL(k_plq_build, dim3((unsigned)((ds->M + 255) / 256)), dim3(256), 0, ctx->stream, *a, mds->d_plq, mds->d_pnode);
+        hipLaunchKernelGGL(k_plq_build, dim3((unsigned)((ds->M + 255) / 256)), dim3(256), 0, ctx->main(), *a, mds->d_plq, mds->d_pnode);
         NHP_HIP(ctx, hipGetLastError());
     }
     a->plq = ds->d_plq; a->pnode = ds->d_pnode;
@@ -464,7 +464,7 @@ static nhp_status run_sampler(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nh
     double *d_u = u ? (double *)(base + o_u) : nullptr;
     (void)o_err;
     int *d_err = ctx->d_err;                 // the context's own word: the deferred check outlives the scratch layout
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     NHP_HIP(ctx, hipMemsetAsync(d_err, 0, sizeof(int), st));
     if (u && M) NHP_HIP(ctx, hipMemcpyAsync(d_u, u, 8 * M, hipMemcpyHostToDevice, st));
     if (nhp_is_column_shard(ds)) {
@@ -541,7 +541,7 @@ extern "C" nhp_status nhp_cont_resample_parents(nhp_ctx *ctx, const nhp_cont_dat
     samp_out o;
     NHP_TRY(run_sampler(ctx, ds, m, u, seed, step, parents || parentnodes, stats != nullptr, &o));
     const size_t M = (size_t)ds->M, N = (size_t)ds->N, NN = N * N;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     (void)st;
     if (stats) {                                   // through the pinned staging buffer (nhp_download synchronises)
         if (stats->cnt0) NHP_TRY(nhp_download(ctx, stats->cnt0, o.cnt0, 8 * N));
@@ -607,7 +607,7 @@ extern "C" nhp_status nhp_cont_gibbs_step(nhp_ctx *ctx, const nhp_cont_dataset *
     gibbs_priors g{pr->alpha0, pr->beta0, pr->kappa, pr->nu, pr->a, pr->b, pr->mu_mu, pr->kappa_mu};
     const size_t NN = (size_t)ds->N * ds->N;
     ++m->version;
-    hipLaunchKernelGGL(k_gibbs_draw, dim3((unsigned)((NN + 255) / 256)), dim3(256), 0, ctx->stream, ds->N, ds->col_begin, ds->col_end,
+    hipLaunchKernelGGL(k_gibbs_draw, dim3((unsigned)((NN + 255) / 256)), dim3(256), 0, ctx->main(), ds->N, ds->col_begin, ds->col_end,
                        m->impulse_kind, ds->duration, g, seed, step, o.cnt0, ds->d_cnt, o.Mnm, o.X, o.V, m->d_lambda0, m->d_p1, m->d_p2, m->d_W);
     NHP_HIP(ctx, hipGetLastError());
     return earlier;
@@ -636,15 +636,15 @@ extern "C" nhp_status nhp_cont_model_moments_reset(nhp_ctx *ctx, nhp_cont_model 
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t len = (int64_t)nhp_layout(m).P + (m->has_A ? (int64_t)m->N * m->N : 0);
     if (!m->d_mom || m->mom_len != len) {
-        if (m->d_mom) { NHP_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(m->d_mom); m->d_mom = nullptr; }
+        if (m->d_mom) { NHP_HIP(ctx, hipStreamSynchronize(ctx->main())); (void)hipFree(m->d_mom); m->d_mom = nullptr; }
         if (hipMalloc((void **)&m->d_mom, sizeof(double) * 2 * (size_t)len) != hipSuccess) {
             nhp_set_error(ctx, "out of device memory (sample moments)");
             return NHP_ENOMEM;
         }
         m->mom_len = len;
     }
-    NHP_HIP(ctx, hipMemsetAsync(m->d_mom, 0, sizeof(double) * 2 * (size_t)len, ctx->stream));
-    if (m->d_rho) NHP_HIP(ctx, hipMemsetAsync(m->d_rho + 1, 0, 2 * sizeof(double), ctx->stream));
+    NHP_HIP(ctx, hipMemsetAsync(m->d_mom, 0, sizeof(double) * 2 * (size_t)len, ctx->main()));
+    if (m->d_rho) NHP_HIP(ctx, hipMemsetAsync(m->d_rho + 1, 0, 2 * sizeof(double), ctx->main()));
     m->mom_count = 0;
     return NHP_OK;
 }
@@ -656,7 +656,7 @@ extern "C" nhp_status nhp_cont_model_moments_accumulate(nhp_ctx *ctx, nhp_cont_m
     if (!m->d_mom) NHP_TRY(nhp_cont_model_moments_reset(ctx, m));
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     const unsigned blocks = (unsigned)std::min<int64_t>((m->mom_len + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_moments, dim3(blocks), dim3(256), 0, ctx->stream, (const double *)m->d_params, (int64_t)nhp_layout(m).P,
+    hipLaunchKernelGGL(k_moments, dim3(blocks), dim3(256), 0, ctx->main(), (const double *)m->d_params, (int64_t)nhp_layout(m).P,
                        (const double *)(m->has_A ? m->d_A : nullptr), m->mom_len, m->d_mom, m->d_rho);
     NHP_HIP(ctx, hipGetLastError());
     ++m->mom_count;
@@ -702,10 +702,10 @@ extern "C" nhp_status nhp_probe_draws(nhp_ctx *ctx, int32_t kind, uint64_t seed,
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, 3 * sizeof(double) * (size_t)n));
     double *da = (double *)ctx->d_scratch, *db = da + n, *dout = db + n;
     if (kind != 1) {
-        NHP_HIP(ctx, hipMemcpyAsync(da, a, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-        NHP_HIP(ctx, hipMemcpyAsync(db, b, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        NHP_HIP(ctx, hipMemcpyAsync(da, a, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->main()));
+        NHP_HIP(ctx, hipMemcpyAsync(db, b, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->main()));
     }
-    hipLaunchKernelGGL(k_probe_draws, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, kind, seed, step, n, da, db, dout);
+    hipLaunchKernelGGL(k_probe_draws, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->main(), kind, seed, step, n, da, db, dout);
     NHP_HIP(ctx, hipGetLastError());
     return nhp_download(ctx, out, dout, sizeof(double) * (size_t)n);
 }

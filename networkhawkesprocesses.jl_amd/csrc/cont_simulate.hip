@@ -222,7 +222,7 @@ extern "C" nhp_status nhp_cont_simulate(nhp_ctx *ctx, const nhp_cont_model *m, d
     *n_events = 0;
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_check_deferred(ctx));
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     const int32_t N = m->N;
     const int64_t cap = max_events;
     const int64_t CH = std::min(std::max(cap, SIM_CHUNK_MIN), SIM_CHUNK_MAX);

@@ -1031,11 +1031,11 @@ static nhp_status ensure_slices(nhp_ctx *ctx, const nhp_cont_dataset *cds, const
         nhp_set_error(ctx, "out of device memory (child slices)");
         return NHP_ENOMEM;
     }
-    NHP_HIP(ctx, hipMemsetAsync(ds->d_sl_lo + (size_t)ds->sl_rows * 64, 0, 4 * 16 * 64, ctx->stream));
-    NHP_HIP(ctx, hipMemsetAsync(ds->d_sl_hi + (size_t)ds->sl_rows * 64, 0, 2 * 16 * 64, ctx->stream));
+    NHP_HIP(ctx, hipMemsetAsync(ds->d_sl_lo + (size_t)ds->sl_rows * 64, 0, 4 * 16 * 64, ctx->main()));
+    NHP_HIP(ctx, hipMemsetAsync(ds->d_sl_hi + (size_t)ds->sl_rows * 64, 0, 2 * 16 * 64, ctx->main()));
     const nhp_slices sl = slices_view(ds);
     if (ds->n_items > 0)
-        hipLaunchKernelGGL(k_slices_build, dim3((unsigned)ds->n_items), dim3(256), 0, ctx->stream, a, sl, ds->d_sl_lo, ds->d_sl_hi);
+        hipLaunchKernelGGL(k_slices_build, dim3((unsigned)ds->n_items), dim3(256), 0, ctx->main(), a, sl, ds->d_sl_lo, ds->d_sl_hi);
     NHP_HIP(ctx, hipGetLastError());
     return NHP_OK;
 }
@@ -1086,12 +1086,12 @@ static nhp_status ensure_parent_slices(nhp_ctx *ctx, const nhp_cont_dataset *cds
         (void)hipFuncSetAttribute((const void *)k_ps_rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute((const void *)k_ps_fill, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
-    hipLaunchKernelGGL(k_ps_count, dim3((unsigned)ni), dim3(256), lds, ctx->stream, a, d_cnt);
-    hipLaunchKernelGGL(k_ps_rank, dim3((unsigned)ni), dim3(256), lds, ctx->stream, N, spi, d_cnt, ds->d_ps_perm, d_rankof, d_rows);
+    hipLaunchKernelGGL(k_ps_count, dim3((unsigned)ni), dim3(256), lds, ctx->main(), a, d_cnt);
+    hipLaunchKernelGGL(k_ps_rank, dim3((unsigned)ni), dim3(256), lds, ctx->main(), N, spi, d_cnt, ds->d_ps_perm, d_rankof, d_rows);
     if (hipGetLastError() != hipSuccess) return fail(NHP_EHIP, "launch failed");
     std::vector<uint32_t> rows((size_t)ni * spi), off((size_t)ni * spi + 1);
-    if (hipMemcpyAsync(rows.data(), d_rows, 4 * rows.size(), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(NHP_EHIP, "copy failed");
+    if (hipMemcpyAsync(rows.data(), d_rows, 4 * rows.size(), hipMemcpyDeviceToHost, ctx->main()) != hipSuccess ||
+        hipStreamSynchronize(ctx->main()) != hipSuccess) return fail(NHP_EHIP, "copy failed");
     uint64_t run = 0;
     for (size_t q = 0; q < rows.size(); ++q) { off[q] = (uint32_t)run; run += rows[q]; }
     off[rows.size()] = (uint32_t)run;
@@ -1100,14 +1100,14 @@ static nhp_status ensure_parent_slices(nhp_ctx *ctx, const nhp_cont_dataset *cds
     const size_t n = ((size_t)run + 16) * 64;
     if (hipMalloc((void **)&ds->d_ps_lo, 4 * n) != hipSuccess || hipMalloc((void **)&ds->d_ps_hi, 2 * n) != hipSuccess)
         return fail(NHP_ENOMEM, "out of device memory");
-    if (hipMemcpyAsync(ds->d_ps_row, off.data(), 4 * off.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipMemsetAsync(ds->d_ps_lo + (size_t)run * 64, 0, 4 * 16 * 64, ctx->stream) != hipSuccess ||
-        hipMemsetAsync(ds->d_ps_hi + (size_t)run * 64, 0, 2 * 16 * 64, ctx->stream) != hipSuccess)
+    if (hipMemcpyAsync(ds->d_ps_row, off.data(), 4 * off.size(), hipMemcpyHostToDevice, ctx->main()) != hipSuccess ||
+        hipMemsetAsync(ds->d_ps_lo + (size_t)run * 64, 0, 4 * 16 * 64, ctx->main()) != hipSuccess ||
+        hipMemsetAsync(ds->d_ps_hi + (size_t)run * 64, 0, 2 * 16 * 64, ctx->main()) != hipSuccess)
         return fail(NHP_EHIP, "copy failed");
     const nhp_pslices ps = pslices_view(ds);
-    hipLaunchKernelGGL(k_ps_fill, dim3((unsigned)ni), dim3(256), lds, ctx->stream, a, ps, d_cnt, d_rankof, ds->d_ps_lo, ds->d_ps_hi);
-    hipLaunchKernelGGL(k_ps_sort, dim3((unsigned)ni), dim3(256), 0, ctx->stream, N, ps, d_cnt, ds->d_ps_lo, ds->d_ps_hi);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(NHP_EHIP, "fill failed");   // (`off` and the scratch go out of scope)
+    hipLaunchKernelGGL(k_ps_fill, dim3((unsigned)ni), dim3(256), lds, ctx->main(), a, ps, d_cnt, d_rankof, ds->d_ps_lo, ds->d_ps_hi);
+    hipLaunchKernelGGL(k_ps_sort, dim3((unsigned)ni), dim3(256), 0, ctx->main(), N, ps, d_cnt, ds->d_ps_lo, ds->d_ps_hi);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->main()) != hipSuccess) return fail(NHP_EHIP, "fill failed");   // (`off` and the scratch go out of scope)
     (void)hipFree(d_cnt); (void)hipFree(d_rows); (void)hipFree(d_rankof);
     return NHP_OK;
 }
@@ -1148,7 +1148,7 @@ static nhp_status launch_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const 
     do {                                                                                                              \
         if (lds > 64 * 1024)                                                                                          \
             (void)hipFuncSetAttribute((const void *)k_windowed_slices<b, cc, f, g>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_windowed_slices<b, cc, f, g>), grid, dim3(b), lds, ctx->stream, a, sl, ps, mask_integral, ctx->d_partials, \
+        hipLaunchKernelGGL((k_windowed_slices<b, cc, f, g>), grid, dim3(b), lds, ctx->lane(), a, sl, ps, mask_integral, ctx->d_partials, \
                            ctx->d_counter, d_out);                                                                    \
     } while (0)
 #define NHP_SCASE(b, cc)                                                                                              \
@@ -1206,7 +1206,7 @@ nhp_status nhp_launch_windowed_slices_ln(nhp_ctx *ctx, const nhp_cont_dataset *c
     do {                                                                                                              \
         if (lds > 64 * 1024)                                                                                          \
             (void)hipFuncSetAttribute((const void *)k_windowed_slices_ln<b, cc, f>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_windowed_slices_ln<b, cc, f>), grid, dim3(b), lds, ctx->stream, a, sl, (const double *)ds->d_sl_L,  \
+        hipLaunchKernelGGL((k_windowed_slices_ln<b, cc, f>), grid, dim3(b), lds, ctx->lane(), a, sl, (const double *)ds->d_sl_L,  \
                            (const double *)ds->d_sl_Q, mask_integral, ctx->d_partials, ctx->d_counter, d_out, d_lambda); \
     } while (0)
 #define NHP_LNC(b, cc) do { if (flat) NHP_LNL(b, cc, true); else NHP_LNL(b, cc, false); } while (0)
@@ -1227,6 +1227,7 @@ nhp_status nhp_launch_grad_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, cons
                                   bool *launched)
 {
     *launched = false;
+    ctx->join_lanes();                                  // (launch_slices takes the lane's raw stream: the gradient joins first)
     const bool direct = ds->all_sole && !nhp_is_column_shard(ds) && m->baseline_kind == NHP_BASELINE_HOMOGENEOUS;
     return launch_slices(ctx, ds, m, 1, d_out, d_grad, direct, launched);
 }
@@ -1270,7 +1271,7 @@ static nhp_status launch_sets(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nh
     do {                                                                                                               \
         if (lds > 64 * 1024)                                                                                           \
             (void)hipFuncSetAttribute((const void *)k_slices_batch<b, cc, S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_slices_batch<b, cc, S>), grid, dim3(b), lds, ctx->stream, a, sl, st, ctx->d_partials, ctx->d_counter); \
+        hipLaunchKernelGGL((k_slices_batch<b, cc, S>), grid, dim3(b), lds, ctx->lane(), a, sl, st, ctx->d_partials, ctx->d_counter); \
     } while (0)
     if (B == 256 && C == 2) NHP_BL(256, 2); else if (B == 256) NHP_BL(256, 4);
     else if (B == 1024 && C == 2) NHP_BL(1024, 2); else if (B == 1024) NHP_BL(1024, 4);
@@ -1309,9 +1310,9 @@ static nhp_status ensure_lq_planes(nhp_ctx *ctx, nhp_cont_dataset *ds, const nhp
         *ok = false;
         return NHP_OK;
     }
-    NHP_HIP(ctx, hipMemsetAsync(ds->d_sl_L + (size_t)ds->sl_rows * 64, 0, 8 * 16 * 64, ctx->stream));
-    NHP_HIP(ctx, hipMemsetAsync(ds->d_sl_Q + (size_t)ds->sl_rows * 64, 0, 8 * 16 * 64, ctx->stream));
-    hipLaunchKernelGGL(k_slices_build_lq, dim3((unsigned)ds->n_items), dim3(256), 0, ctx->stream, a, sl, ds->d_sl_L, ds->d_sl_Q);
+    NHP_HIP(ctx, hipMemsetAsync(ds->d_sl_L + (size_t)ds->sl_rows * 64, 0, 8 * 16 * 64, ctx->main()));
+    NHP_HIP(ctx, hipMemsetAsync(ds->d_sl_Q + (size_t)ds->sl_rows * 64, 0, 8 * 16 * 64, ctx->main()));
+    hipLaunchKernelGGL(k_slices_build_lq, dim3((unsigned)ds->n_items), dim3(256), 0, ctx->main(), a, sl, ds->d_sl_L, ds->d_sl_Q);
     NHP_HIP(ctx, hipGetLastError());
     return NHP_OK;
 }
@@ -1337,8 +1338,8 @@ nhp_status nhp_launch_sampler_slices(nhp_ctx *ctx, const nhp_cont_dataset *cds, 
     if (expo && !ds->d_sl_D) {
         const size_t n = ((size_t)ds->sl_rows + 16) * 64;
         if (hipMalloc((void **)&ds->d_sl_D, 8 * n) != hipSuccess) { (void)hipGetLastError(); ds->d_sl_D = nullptr; return NHP_OK; }
-        NHP_HIP(ctx, hipMemsetAsync(ds->d_sl_D + (size_t)ds->sl_rows * 64, 0, 8 * 16 * 64, ctx->stream));
-        hipLaunchKernelGGL(k_slices_build_d, dim3((unsigned)ds->n_items), dim3(256), 0, ctx->stream, a, sl, ds->d_sl_D);
+        NHP_HIP(ctx, hipMemsetAsync(ds->d_sl_D + (size_t)ds->sl_rows * 64, 0, 8 * 16 * 64, ctx->main()));
+        hipLaunchKernelGGL(k_slices_build_d, dim3((unsigned)ds->n_items), dim3(256), 0, ctx->main(), a, sl, ds->d_sl_D);
         NHP_HIP(ctx, hipGetLastError());
     }
     if (!expo) {
@@ -1352,12 +1353,12 @@ nhp_status nhp_launch_sampler_slices(nhp_ctx *ctx, const nhp_cont_dataset *cds, 
         if (expo) {                                                                                                    \
             if (lds > 64 * 1024)                                                                                       \
                 (void)hipFuncSetAttribute((const void *)k_sampler_slices<b, cc, NHP_IMPULSE_EXPONENTIAL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_sampler_slices<b, cc, NHP_IMPULSE_EXPONENTIAL>), grid, dim3(b), lds, ctx->stream, a, sl, (const double *)ds->d_sl_D, \
+            hipLaunchKernelGGL((k_sampler_slices<b, cc, NHP_IMPULSE_EXPONENTIAL>), grid, dim3(b), lds, ctx->main(), a, sl, (const double *)ds->d_sl_D, \
                                (const double *)nullptr, d_u, seed, step, parents, pnodes, pn_b, dt_b, d_err);      \
         } else {                                                                                                       \
             if (lds > 64 * 1024)                                                                                       \
                 (void)hipFuncSetAttribute((const void *)k_sampler_slices<b, cc, NHP_IMPULSE_LOGITNORMAL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_sampler_slices<b, cc, NHP_IMPULSE_LOGITNORMAL>), grid, dim3(b), lds, ctx->stream, a, sl, (const double *)ds->d_sl_L, \
+            hipLaunchKernelGGL((k_sampler_slices<b, cc, NHP_IMPULSE_LOGITNORMAL>), grid, dim3(b), lds, ctx->main(), a, sl, (const double *)ds->d_sl_L, \
                                (const double *)ds->d_sl_Q, d_u, seed, step, parents, pnodes, pn_b, dt_b, d_err);      \
         }                                                                                                              \
     } while (0)

@@ -69,13 +69,13 @@ extern "C" nhp_status nhp_ctx_create(int32_t device, nhp_ctx **out)
     hipDeviceProp_t prop;
     NHP_HIP(ctx, hipGetDeviceProperties(&prop, device));
     ctx->cu_count = prop.multiProcessorCount;
-    NHP_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+    NHP_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream_main, hipStreamNonBlocking));
     NHP_HIP(ctx, hipEventCreate(&ctx->ev0));
     NHP_HIP(ctx, hipEventCreate(&ctx->ev1));
     NHP_HIP(ctx, hipMalloc(&ctx->d_results, sizeof(double) * NHP_MAX_SLOTS));
     NHP_HIP(ctx, hipHostMalloc(&ctx->h_results, sizeof(double) * NHP_MAX_SLOTS));
     NHP_HIP(ctx, hipMalloc(&ctx->d_counter, 128 * 80));
-    NHP_HIP(ctx, hipMemsetAsync(ctx->d_counter, 0, 128 * 80, ctx->stream));
+    NHP_HIP(ctx, hipMemsetAsync(ctx->d_counter, 0, 128 * 80, ctx->main()));
     NHP_HIP(ctx, hipMalloc((void **)&ctx->d_err, sizeof(int)));
     NHP_HIP(ctx, hipHostMalloc((void **)&ctx->h_err, sizeof(int)));
     *ctx->h_err = 0;
@@ -84,9 +84,9 @@ extern "C" nhp_status nhp_ctx_create(int32_t device, nhp_ctx **out)
     NHP_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
     NHP_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
     NHP_HIP(ctx, hipMalloc(&ctx->d_counter2, 128 * 80));
-    NHP_HIP(ctx, hipMemsetAsync(ctx->d_counter2, 0, 128 * 80, ctx->stream));
-    NHP_HIP(ctx, hipMemsetAsync(ctx->d_results, 0, sizeof(double) * NHP_MAX_SLOTS, ctx->stream));
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NHP_HIP(ctx, hipMemsetAsync(ctx->d_counter2, 0, 128 * 80, ctx->main()));
+    NHP_HIP(ctx, hipMemsetAsync(ctx->d_results, 0, sizeof(double) * NHP_MAX_SLOTS, ctx->main()));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     *out = ctx;
     return NHP_OK;
 }
@@ -95,7 +95,7 @@ extern "C" void nhp_ctx_destroy(nhp_ctx *ctx)
 {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->stream_main) (void)hipStreamSynchronize(ctx->main());     // (joins the second lane first)
     if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
     if (ctx->d_partials2) (void)hipFree(ctx->d_partials2);
     if (ctx->d_counter2) (void)hipFree(ctx->d_counter2);
@@ -115,28 +115,28 @@ extern "C" void nhp_ctx_destroy(nhp_ctx *ctx)
     if (ctx->d_counter) (void)hipFree(ctx->d_counter);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    if (ctx->stream_main) (void)hipStreamDestroy(ctx->stream_main);
     delete ctx;
 }
 
 extern "C" nhp_status nhp_ctx_synchronize(nhp_ctx *ctx)
 {
     if (!ctx) return NHP_EINVAL;
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     return nhp_check_deferred(ctx);
 }
 
 extern "C" nhp_status nhp_ctx_timer_start(nhp_ctx *ctx)
 {
     if (!ctx) return NHP_EINVAL;
-    NHP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    NHP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->main()));
     return NHP_OK;
 }
 
 extern "C" nhp_status nhp_ctx_timer_stop(nhp_ctx *ctx, double *elapsed_ms)
 {
     if (!ctx || !elapsed_ms) return NHP_EINVAL;
-    NHP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    NHP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->main()));
     NHP_HIP(ctx, hipEventSynchronize(ctx->ev1));
     float ms = 0.f;
     NHP_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
@@ -148,8 +148,8 @@ extern "C" nhp_status nhp_ctx_fetch(nhp_ctx *ctx, int32_t first_slot, int32_t n,
 {
     if (!ctx || !out || first_slot < 0 || n < 0 || first_slot + n > NHP_MAX_SLOTS) return NHP_EINVAL;
     NHP_HIP(ctx, hipMemcpyAsync(ctx->h_results + first_slot, ctx->d_results + first_slot,
-                                sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                                sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->main()));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     memcpy(out, ctx->h_results + first_slot, sizeof(double) * (size_t)n);
     return NHP_OK;
 }
@@ -157,7 +157,7 @@ extern "C" nhp_status nhp_ctx_fetch(nhp_ctx *ctx, int32_t first_slot, int32_t n,
 nhp_status nhp_ctx_reserve_partials(nhp_ctx *ctx, size_t n)
 {
     if (n <= ctx->partials_cap) return NHP_OK;
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     if (ctx->d_partials) (void)hipFree(ctx->d_partials);
     ctx->d_partials = nullptr;
     ctx->partials_cap = 0;
@@ -169,7 +169,7 @@ nhp_status nhp_ctx_reserve_partials(nhp_ctx *ctx, size_t n)
 nhp_status nhp_ctx_reserve_mle(nhp_ctx *ctx, size_t bytes, const char *what)
 {
     if (bytes <= ctx->mle_cap) return NHP_OK;
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     (void)hipFree(ctx->d_mle);
     ctx->d_mle = nullptr; ctx->mle_cap = 0;
     if (hipMalloc(&ctx->d_mle, bytes) != hipSuccess) {
@@ -197,22 +197,22 @@ nhp_status nhp_check_deferred(nhp_ctx *ctx)
 nhp_status nhp_download(nhp_ctx *ctx, void *dst, const void *d_src, size_t bytes)
 {
     NHP_TRY(nhp_check_deferred(ctx));
-    if (bytes == 0) { NHP_HIP(ctx, hipStreamSynchronize(ctx->stream)); return NHP_OK; }
+    if (bytes == 0) { NHP_HIP(ctx, hipStreamSynchronize(ctx->main())); return NHP_OK; }
     if (bytes > ctx->stage_cap) {
-        NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
         if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
         ctx->h_stage = nullptr; ctx->stage_cap = 0;
         const size_t cap = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
         if (hipHostMalloc(&ctx->h_stage, cap) != hipSuccess) {       // no pinned memory: fall back to the direct copy
             ctx->h_stage = nullptr;
-            NHP_HIP(ctx, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-            NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            NHP_HIP(ctx, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->main()));
+            NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
             return NHP_OK;
         }
         ctx->stage_cap = cap;
     }
-    NHP_HIP(ctx, hipMemcpyAsync(ctx->h_stage, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(ctx->h_stage, d_src, bytes, hipMemcpyDeviceToHost, ctx->main()));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     memcpy(dst, ctx->h_stage, bytes);
     return NHP_OK;
 }
@@ -220,7 +220,7 @@ nhp_status nhp_download(nhp_ctx *ctx, void *dst, const void *d_src, size_t bytes
 nhp_status nhp_ctx_reserve_scratch(nhp_ctx *ctx, size_t bytes)
 {
     if (bytes <= ctx->scratch_cap) return NHP_OK;
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     ctx->d_scratch = nullptr;
     ctx->scratch_cap = 0;

@@ -767,7 +767,7 @@ extern "C" nhp_status nhp_disc_dataset_create(nhp_ctx *ctx, const int64_t *data,
     ds->ctx = ctx; ds->N = N; ds->T = T;
     const size_t NT = (size_t)N * (size_t)T;
     int64_t *d_raw = nullptr;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     hipError_t e;
     if ((e = hipMalloc(&d_raw, 8 * NT)) != hipSuccess || (e = hipMalloc(&ds->d_dataT, 8 * NT)) != hipSuccess ||
         (e = hipMalloc(&ds->d_colsum, 8 * 2 * (size_t)N)) != hipSuccess) {
@@ -864,7 +864,7 @@ extern "C" void nhp_disc_dataset_destroy(nhp_disc_dataset *ds)
 {
     if (!ds) return;
     (void)hipSetDevice(ds->ctx->device);
-    (void)hipStreamSynchronize(ds->ctx->stream);
+    (void)hipStreamSynchronize(ds->ctx->main());
     (void)hipFree(ds->d_dataT); (void)hipFree(ds->d_data8); (void)hipFree(ds->d_conv); (void)hipFree(ds->d_colsum);
     (void)hipFree(ds->d_occ_t); (void)hipFree(ds->d_occ_c); (void)hipFree(ds->d_occ_s); (void)hipFree(ds->d_occ_off); (void)hipFree(ds->d_occ_pack); (void)hipFree(ds->d_span_t);
     (void)hipFree(ds->d_convsum); (void)hipFree(ds->d_baseT); (void)hipFree(ds->d_base_counts);
@@ -877,7 +877,7 @@ extern "C" nhp_status nhp_disc_convolve(nhp_ctx *ctx, nhp_disc_dataset *ds, cons
     if (!ctx || !ds || !phi || L < 1 || B < 1) return NHP_EINVAL;
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t TNB = (size_t)ds->T * ds->N * B;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     if (ds->B != B || !ds->d_conv) {
         NHP_HIP(ctx, hipStreamSynchronize(st));
         if (ds->d_conv) (void)hipFree(ds->d_conv);
@@ -966,7 +966,7 @@ nhp_status nhp_disc_stage_bump(nhp_ctx *ctx, const nhp_disc_dataset *ds, const d
     double *dth = p; p += NN * B;
     double *dA = p; p += NN;
     *extra_ptr = p;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     if (lambda0) NHP_HIP(ctx, hipMemcpyAsync(dl0, lambda0, 8 * N, hipMemcpyHostToDevice, st));
     else NHP_HIP(ctx, hipMemsetAsync(dl0, 0, 8 * N, st));          // per-bin baseline comes from ds->d_baseT
     NHP_HIP(ctx, hipMemcpyAsync(dW, W, 8 * NN, hipMemcpyHostToDevice, st));
@@ -987,7 +987,7 @@ nhp_status nhp_disc_launch_intensity(nhp_ctx *ctx, const nhp_disc_dataset *ds, c
     g.A = ds->d_conv; g.lda = (size_t)ds->T; g.B = E; g.ldb = (size_t)ds->N * ds->B;
     g.M = (int)ds->T; g.N = ds->N; g.K = ds->N * ds->B; g.k_chunk = g.K;
     g.base = base; g.baseT = per_bin_baseline ? ds->d_baseT : nullptr; g.out = dlam;
-    launch_gemm<true, EPI_INTENSITY>(g, 1, ctx->stream, gemm1_tile_m(g.M, g.N, ctx->cu_count));
+    launch_gemm<true, EPI_INTENSITY>(g, 1, ctx->main(), gemm1_tile_m(g.M, g.N, ctx->cu_count));
     NHP_HIP(ctx, hipGetLastError());
     return NHP_OK;
 }
@@ -1005,10 +1005,10 @@ extern "C" nhp_status nhp_disc_intensity(nhp_ctx *ctx, const nhp_disc_dataset *d
     g.A = ds->d_conv; g.lda = (size_t)ds->T; g.B = E; g.ldb = (size_t)ds->N * ds->B;
     g.M = (int)ds->T; g.N = ds->N; g.K = ds->N * ds->B; g.k_chunk = g.K;
     g.base = base; g.baseT = lambda0 ? nullptr : ds->d_baseT; g.out = dlam;
-    launch_gemm<true, EPI_INTENSITY>(g, 1, ctx->stream, gemm1_tile_m(g.M, g.N, ctx->cu_count));
+    launch_gemm<true, EPI_INTENSITY>(g, 1, ctx->main(), gemm1_tile_m(g.M, g.N, ctx->cu_count));
     NHP_HIP(ctx, hipGetLastError());
-    NHP_HIP(ctx, hipMemcpyAsync(lam, dlam, 8 * TN, hipMemcpyDeviceToHost, ctx->stream));
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(lam, dlam, 8 * TN, hipMemcpyDeviceToHost, ctx->main()));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     return NHP_OK;
 }
 
@@ -1027,9 +1027,9 @@ extern "C" nhp_status nhp_disc_loglik(nhp_ctx *ctx, const nhp_disc_dataset *ds, 
     const int blocks = ((g.M + bm - 1) / bm) * ((g.N + BN - 1) / BN);
     NHP_TRY(nhp_ctx_reserve_partials(ctx, 2 * (size_t)blocks));
     g.partials = ctx->d_partials;
-    launch_gemm<true, EPI_LOGLIK>(g, 1, ctx->stream, bm);
+    launch_gemm<true, EPI_LOGLIK>(g, 1, ctx->main(), bm);
     NHP_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_sum_pairs, dim3(1), dim3(256), 0, ctx->stream, ctx->d_partials, blocks, ds->lgamma_sum, ctx->d_results);
+    hipLaunchKernelGGL(k_sum_pairs, dim3(1), dim3(256), 0, ctx->main(), ctx->d_partials, blocks, ds->lgamma_sum, ctx->d_results);
     NHP_HIP(ctx, hipGetLastError());
     return nhp_ctx_fetch(ctx, 0, 1, ll);
 }
@@ -1162,7 +1162,7 @@ static nhp_status disc_grad_enqueue(nhp_ctx *ctx, const nhp_disc_dataset *ds, co
     double *dcolp = x; x += (size_t)q.row_blocks * N;
     double *dslab = x; x += (size_t)q.splits * K * N;
     double *dgrad = x;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     // GEMM-1 once, with both epilogues: the Poisson log-likelihood partials AND R = data / Z with its column sums
     gemm_args g{};
     g.A = ds->d_conv; g.lda = T; g.B = E; g.ldb = K; g.M = (int)T; g.N = (int)N; g.K = (int)K; g.k_chunk = (int)K;
@@ -1206,7 +1206,7 @@ extern "C" nhp_status nhp_disc_loglik_grad(nhp_ctx *ctx, const nhp_disc_dataset 
     double *E, *base, *x, *dgrad;
     NHP_TRY(nhp_disc_stage_bump(ctx, ds, lambda0, W, theta, nullptr, dt, &E, &base, q.extra(), &x));
     NHP_TRY(disc_grad_enqueue(ctx, ds, q, lambda0 != nullptr, E, base, x, dt, &dgrad));
-    NHP_HIP(ctx, hipMemcpyAsync(grad, dgrad, 8 * (q.nbase + q.NN * q.B), hipMemcpyDeviceToHost, ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(grad, dgrad, 8 * (q.nbase + q.NN * q.B), hipMemcpyDeviceToHost, ctx->main()));
     return nhp_ctx_fetch(ctx, 0, 1, ll);
 }
 
@@ -1248,7 +1248,7 @@ extern "C" nhp_status nhp_disc_mle_run(nhp_ctx *ctx, const nhp_disc_dataset *ds,
     // scratch: E | base | the evaluation's buffers (nhp_disc_stage_bump's layout without its host-side copies)
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, 8 * (q.K * q.N + q.N + q.extra())));
     auto eval = [&](const double *d_x, double *d_g, bool /*commit*/) -> nhp_status {
-        hipStream_t st = ctx->stream;
+        hipStream_t st = ctx->main();
         double *E = (double *)ctx->d_scratch, *base = E + q.K * q.N, *xs = base + q.N, *dgrad = nullptr;
         hipLaunchKernelGGL(k_disc_bump_from_x, dim3((unsigned)((q.NN + 255) / 256)), dim3(256), 0, st, (int)q.N, (int)q.B, dt, d_x, E, base);
         NHP_TRY(disc_grad_enqueue(ctx, ds, q, true, E, base, xs, dt, &dgrad));
@@ -1298,7 +1298,7 @@ extern "C" nhp_status nhp_disc_vb_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, 
     double *dR = p; p += T * N;
     double *dcolp = p; p += (size_t)row_blocks * N;
     double *dslab = p;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     NHP_HIP(ctx, hipMemcpyAsync(dav, alpha_v, 8 * N, hipMemcpyHostToDevice, st));
     NHP_HIP(ctx, hipMemcpyAsync(dbv, beta_v, 8 * N, hipMemcpyHostToDevice, st));
     NHP_HIP(ctx, hipMemcpyAsync(dkv, kappa_v, 8 * NN, hipMemcpyHostToDevice, st));
@@ -1354,7 +1354,7 @@ extern "C" nhp_status nhp_disc_set_lgcp_baseline(nhp_ctx *ctx, nhp_disc_dataset 
     ds->h_grid_x.assign(grid_x, grid_x + grid_n);
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, 8 * (G + G * N)));
     double *dx = (double *)ctx->d_scratch, *dl = dx + G;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     NHP_HIP(ctx, hipMemcpyAsync(dx, grid_x, 8 * G, hipMemcpyHostToDevice, st));
     NHP_HIP(ctx, hipMemcpyAsync(dl, lam, 8 * G * N, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_disc_base_interp, dim3((unsigned)((T + 255) / 256), (unsigned)N), dim3(256), 0, st, dx, grid_n, dl, dt, ds->T, ds->d_baseT);
@@ -1376,7 +1376,7 @@ extern "C" nhp_status nhp_disc_lgcp_loglik(nhp_ctx *ctx, const nhp_disc_dataset 
     if (ds->h_grid_x[0] + (double)(ds->T - 1) * dt > ds->h_grid_x[G - 1]) { nhp_set_error(ctx, "lgcp_loglik: bins fall outside the grid support"); return NHP_EDOMAIN; }
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, 8 * (G + G * N + N)));
     double *dx = (double *)ctx->d_scratch, *dc = dx + G, *dll = dc + G * N;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     NHP_HIP(ctx, hipMemcpyAsync(dx, ds->h_grid_x.data(), 8 * G, hipMemcpyHostToDevice, st));
     NHP_HIP(ctx, hipMemcpyAsync(dc, cand, 8 * G * N, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_disc_lgcp_ll, dim3((unsigned)N), dim3(256), 0, st, ds->d_base_counts, ds->T, (int)G, dx, dc, dt, dll);

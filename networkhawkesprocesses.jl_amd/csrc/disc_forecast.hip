@@ -194,7 +194,7 @@ extern "C" nhp_status nhp_disc_forecast(nhp_ctx *ctx, const double *lambda0, con
     if (n_generations) *n_generations = 0;
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_check_deferred(ctx));
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     const int32_t N = n_nodes, B = n_basis, L = n_lags;
     const int64_t H = horizon_bins, S = nsamples, HN = H * N, SN = S * N, NT = S * HN, NN = (int64_t)N * N;
     const int32_t K = (int32_t)std::min<int64_t>(L, H);                  // forecast bins the observed events still reach

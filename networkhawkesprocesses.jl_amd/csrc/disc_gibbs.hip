@@ -334,7 +334,7 @@ static nhp_status disc_parent_counts(nhp_ctx *ctx, const nhp_disc_dataset *ds, c
     double *E2, *base, *extra;
     NHP_TRY(nhp_disc_stage_bump(ctx, ds, lambda0, W, theta, A, dt, &E2, &base, (NC + 1) / 2 + 1 + extra_doubles, &extra, 1));
     int *d_counts = reinterpret_cast<int *>(extra);
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     NHP_HIP(ctx, hipMemsetAsync(d_counts, 0, sizeof(int) * NC, st));
     if (ds->T >= ((int64_t)1 << 31) || K >= ((size_t)1 << 24)) { nhp_set_error(ctx, "resample_parents: T or N*B too large"); return NHP_ENOTIMPL; }
     // q / B for q < 2^24 as a multiply-high: exact with magic = floor(2^32 / B) + 1 while q·B < 2^32
@@ -375,7 +375,7 @@ extern "C" nhp_status nhp_disc_resample_parents(nhp_ctx *ctx, const nhp_disc_dat
     const size_t N = (size_t)ds->N, NC = N * (1 + N * (size_t)ds->B);
     int *d_counts;
     NHP_TRY(disc_parent_counts(ctx, ds, lambda0, W, theta, A, dt, seed, step, 0, &d_counts, nullptr, nullptr, nullptr, nullptr));
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     std::vector<int> h((size_t)NC);
     NHP_HIP(ctx, hipMemcpyAsync(h.data(), d_counts, sizeof(int) * NC, hipMemcpyDeviceToHost, st));
     NHP_HIP(ctx, hipStreamSynchronize(st));
@@ -422,7 +422,7 @@ extern "C" nhp_status nhp_disc_gibbs_step(nhp_ctx *ctx, const nhp_disc_dataset *
     int *d_counts;
     double *dW, *dth, *dl0;
     NHP_TRY(disc_parent_counts(ctx, ds, lambda0, W, theta, A, dt, seed, step, 0, &d_counts, nullptr, &dW, &dth, &dl0));
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     // Σ_t data[p, t] = node_counts(data): the first half of the dataset's column statistics
     hipLaunchKernelGGL(k_disc_gibbs_draw, dim3((unsigned)((NN + 255) / 256)), dim3(256), 0, st, (int)N, (int)B, (double)ds->T * dt,
                        alpha0, beta0, kappa, nu, gamma0, seed, step, d_counts, ds->d_colsum, dl0, dW, dth);
@@ -899,7 +899,7 @@ extern "C" nhp_status nhp_disc_resample_adjacency(nhp_ctx *ctx, const nhp_disc_d
     unsigned int *tick = reinterpret_cast<unsigned int *>(x);            // 32 words per group ticket
     // stage_bump left W, θ, A on the device just before the extra block: recover the pointers
     double *dW = base + 2 * N, *dth = dW + NN, *dA = dth + NN * B;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     if (u) NHP_HIP(ctx, hipMemcpyAsync(d_u, u, 8 * NN, hipMemcpyHostToDevice, st));
     if (rho_matrix) NHP_HIP(ctx, hipMemcpyAsync(d_rho, rho_matrix, 8 * NN, hipMemcpyHostToDevice, st));
     // λ under the current A at the occupied bins: from the entry lists themselves (k_dadj_lambda0) where a thread's share fits

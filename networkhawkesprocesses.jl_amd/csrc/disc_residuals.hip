@@ -256,7 +256,7 @@ extern "C" nhp_status nhp_disc_residuals(nhp_ctx *ctx, const nhp_disc_dataset *d
     *impossible = 0;
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_check_deferred(ctx));
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     const int32_t N = ds->N;
     const int64_t T = ds->T, TN = T * N, nch64 = (T + RES_CHUNK - 1) / RES_CHUNK, NB = (int64_t)N * nbins;
     if (nch64 * N >= ((int64_t)1 << 31)) {

@@ -88,7 +88,7 @@ extern "C" nhp_status nhp_disc_simulate(nhp_ctx *ctx, const double *lambda0, con
     if (n_generations) *n_generations = 0;
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_check_deferred(ctx));
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     const int32_t N = n_nodes, B = n_basis, L = n_lags;
     const int64_t T = n_bins, NT = (int64_t)N * T, NN = (int64_t)N * N;
     const int64_t cap = max_events;

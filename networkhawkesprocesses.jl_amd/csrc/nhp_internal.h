@@ -6,6 +6,7 @@
 #include <string>
 #include <functional>
 #include <vector>
+#include <utility>
 
 #include "../../include/nhp.h"
 
@@ -21,7 +22,9 @@
 
 struct nhp_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
+    // The main stream.  Reached only through main() (or lane() at the launch lines of the pipelined log-likelihood
+    // routes): see the lanes below.
+    hipStream_t stream_main = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double *d_results = nullptr;        // [NHP_MAX_SLOTS] log-likelihood results
     double *h_results = nullptr;        // pinned mirror
@@ -30,9 +33,15 @@ struct nhp_ctx {
     void *d_scratch = nullptr;          // general scratch (gradients, sampler output)
     size_t scratch_cap = 0;             // bytes
     unsigned int *d_counter = nullptr;  // arrival ticket of the fused last-block reduction (kept at 0 between launches)
-    // Second lane for independent evaluations inside one call (nhp_cont_loglik_batch): its own stream, partial sums and
-    // tickets.  A launch has fixed costs -- dispatch / completion, column staging, the reduction tail -- during which
-    // the chip idles; with two lanes they run under the other lane's pair loops (profiles/README.md: two streams).
+    // Second lane for independent evaluations (nhp_cont_loglik_enqueue: odd result slots; nhp_cont_loglik_batch: every
+    // other launch): its own stream, partial sums and tickets.  A launch has fixed costs -- dispatch / completion,
+    // column staging, the reduction tail -- during which the chip idles; with two lanes they run under the other
+    // lane's pair loops (profiles/README.md: two streams).  Ordering is kept by the two accessors below, not by the
+    // callers: everything but the launch lines of the pipelined routes goes through main(), which first makes the main
+    // stream wait for whatever lane 2 still has in flight (the JOIN) and notes that the main stream has new work; the
+    // launch lines go through lane(), which before a launch on lane 2 makes it wait for that new work (the FORK) and
+    // otherwise adds nothing -- a streak of enqueues costs one launch each and no event.  nhp_lane_guard switches the
+    // lane around a launch by swapping the partial sums and tickets, so the launch code is shared.
     // Deferred sampler error (nhp_cont_gibbs_step): the sweep's "weights do not sum to a positive finite value" flag is
     // copied to a pinned word behind the sweep and looked at when the NEXT sweep has been enqueued (or at any call that
     // synchronises), so a chain keeps one step in flight instead of draining the GPU every step.
@@ -46,6 +55,36 @@ struct nhp_ctx {
     double *d_partials2 = nullptr;
     size_t partials2_cap = 0;
     unsigned int *d_counter2 = nullptr;
+    bool on_lane2 = false;              // the fields above are swapped (nhp_lane_guard): lane() is stream2
+    bool lane2_busy = false;            // lane 2 has launches the main stream has not waited for
+    bool main_touched = true;           // the main stream got work through main() since lane 2 last waited for it
+    // A failed event call inside the accessors would lose a fork or a join without a word: its status is kept here and
+    // reported by the next NHP_HIP check on this context (and so by fetch / synchronize / timer_stop at the latest).
+    hipError_t lane_err = hipSuccess;
+    void lane_call(hipError_t e) { if (e != hipSuccess && lane_err == hipSuccess) lane_err = e; }
+    // the JOIN: the main stream waits for what lane 2 has in flight, and is noted as having new work
+    void join_lanes()
+    {
+        if (lane2_busy) {
+            lane2_busy = false;
+            lane_call(hipEventRecord(ev_join, stream2));
+            lane_call(hipStreamWaitEvent(stream_main, ev_join, 0));
+        }
+        main_touched = true;
+    }
+    // the main stream, for everything that is not an independent evaluation: ordered after both lanes
+    hipStream_t main() { join_lanes(); return stream_main; }
+    // the current lane's stream, for the launch of an independent evaluation: ordered after what main() has been given
+    hipStream_t lane()
+    {
+        if (!on_lane2) return stream_main;
+        if (main_touched) {
+            main_touched = false;
+            lane_call(hipEventRecord(ev_fork, stream_main));
+            lane_call(hipStreamWaitEvent(stream2, ev_fork, 0));
+        }
+        return stream2;
+    }
     int cu_count = 256;
     // the device optimizer's state (nhp_lbfgs.h): kept between mle! runs -- allocating and freeing ~400 MB per run cost
     // several ms of a 30 ms run
@@ -53,6 +92,21 @@ struct nhp_ctx {
     size_t mle_cap = 0;
     double *h_mle_scal = nullptr;       // pinned scalars of its readbacks
     std::string err;
+};
+
+// Switches the context to its second lane and back (flip / flip, or the destructor): the launch code reads d_partials,
+// d_counter and lane() and so serves either lane.  Flipping back notes that lane 2 may have work in flight.
+struct nhp_lane_guard {
+    nhp_ctx *c;
+    bool on = false;
+    void flip()
+    {
+        std::swap(c->d_partials, c->d_partials2); std::swap(c->partials_cap, c->partials2_cap);
+        std::swap(c->d_counter, c->d_counter2);
+        c->on_lane2 = on = !on;
+        if (!on) c->lane2_busy = true;
+    }
+    ~nhp_lane_guard() { if (on) flip(); }
 };
 
 // One contiguous run of bucketed children of a single node, processed by one workgroup.
@@ -320,9 +374,18 @@ nhp_status nhp_disc_launch_intensity(nhp_ctx *ctx, const nhp_disc_dataset *ds, c
 
 // ---- error plumbing -------------------------------------------------------------------
 void nhp_set_error(nhp_ctx *ctx, const char *fmt, ...);
+// the status a fork or join inside main() / lane() left behind, once (hipSuccess: none; ctx may be null)
+inline hipError_t nhp_take_lane_error(nhp_ctx *ctx)
+{
+    if (!ctx || ctx->lane_err == hipSuccess) return hipSuccess;
+    const hipError_t e = ctx->lane_err;
+    ctx->lane_err = hipSuccess;
+    return e;
+}
 #define NHP_HIP(ctx, call)                                                                   \
     do {                                                                                     \
         hipError_t e_ = (call);                                                              \
+        if (e_ == hipSuccess) e_ = nhp_take_lane_error(ctx);                                 \
         if (e_ != hipSuccess) {                                                              \
             nhp_set_error(ctx, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
             return NHP_EHIP;                                                                 \
@@ -442,7 +505,7 @@ bool nhp_is_column_shard(const nhp_cont_dataset *ds);
         }                                                                                                     \
     } while (0)
 
-// launchers implemented in the kernel translation units (all asynchronous on ctx->stream)
+// launchers implemented in the kernel translation units (all asynchronous on the main stream, after a join)
 nhp_status nhp_launch_windowed(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, double *d_out);
 nhp_status nhp_launch_recursive(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, double *d_out);
 nhp_status nhp_launch_finalize(nhp_ctx *ctx, const nhp_cont_args &a, int n_partials, double *d_out);

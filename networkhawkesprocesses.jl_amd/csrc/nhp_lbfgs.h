@@ -11,7 +11,7 @@
 // Per step: two passes over the history, one evaluation, two synchronisations.  Stopping rule: the reference's mle! callback,
 // |f_k - f_{k-1}| < f_abstol (src/continuous.jl:168-181, src/discrete.jl:247-258), or a zero projected gradient.
 //
-// The objective is given as `eval(d_x, d_g, commit)`: enqueue on ctx->stream the evaluation at the DEVICE vector d_x, leaving
+// The objective is given as `eval(d_x, d_g, commit)`: enqueue on ctx->main() the evaluation at the DEVICE vector d_x, leaving
 // the log-likelihood in ctx->d_results[0] and g = -∇ll in d_g (f = -ll is minimised); asynchronous.  `commit` marks the
 // run's last call -- the iterate the caller's model has to hold afterwards (a trial may be evaluated straight from d_x).
 #pragma once
@@ -207,7 +207,7 @@ struct mle_state {
 // synchronisation
 nhp_status multidot3(mle_state &s, const double *u, const double *v, const double *w, int na, double *out /* [NACC + 1] */)
 {
-    hipStream_t st = s.ctx->stream;
+    hipStream_t st = s.ctx->main();
     hipLaunchKernelGGL(k_mle_multidot3, dim3(RBLK), dim3(256), 0, st, u, v, w, (const double *)s.d_base, na, s.P, s.d_part);
     hipLaunchKernelGGL(k_mle_multidot_final, dim3(NACC), dim3(256), 0, st, (const double *)s.d_part, RBLK, NACC, (const double *)nullptr, s.d_scal);
     NHP_HIP(s.ctx, hipGetLastError());
@@ -220,7 +220,7 @@ nhp_status multidot3(mle_state &s, const double *u, const double *v, const doubl
 // u·v and the log-likelihood of the evaluation enqueued before -> host: the one readback of a line-search trial
 nhp_status dot_with_ll(mle_state &s, const double *u, const double *v, double *uv, double *ll)
 {
-    hipStream_t st = s.ctx->stream;
+    hipStream_t st = s.ctx->main();
     hipLaunchKernelGGL(k_mle_dot, dim3(RBLK), dim3(256), 0, st, u, v, s.P, s.d_part);
     hipLaunchKernelGGL(k_mle_multidot_final, dim3(1), dim3(256), 0, st, (const double *)s.d_part, RBLK, 1, (const double *)s.ctx->d_results, s.d_scal);
     NHP_HIP(s.ctx, hipGetLastError());
@@ -237,7 +237,7 @@ nhp_status nhp_lbfgs_box(nhp_ctx *ctx, int64_t P, double lower, double upper, do
                          double *loss, int32_t *steps_out, int32_t *converged_out, int32_t *evals_out)
 {
     NHP_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
+    hipStream_t st = ctx->main();
     // NHP_TIMING=1: where a run spends its wall time outside the steps (stderr)
     static const bool timing = getenv("NHP_TIMING") && atoi(getenv("NHP_TIMING")) != 0;
     static const bool trace = getenv("NHP_MLE_TRACE") && atoi(getenv("NHP_MLE_TRACE")) != 0;     // one line per accepted step (stderr)

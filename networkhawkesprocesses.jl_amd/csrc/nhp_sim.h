@@ -135,8 +135,8 @@ struct sim_pinned {
 template <typename S>
 static nhp_status sim_read(nhp_ctx *ctx, S *h, const S *d)
 {
-    NHP_HIP(ctx, hipMemcpyAsync(h, d, sizeof(S), hipMemcpyDeviceToHost, ctx->stream));
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(h, d, sizeof(S), hipMemcpyDeviceToHost, ctx->main()));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     return NHP_OK;
 }
 

@@ -33,12 +33,12 @@ extern "C" nhp_status nhp_probe_math(nhp_ctx *ctx, int32_t op, const double *x, 
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, 3 * 8 * (size_t)n));
     double *dx = (double *)ctx->d_scratch, *dy = dx + n, *dout = dy + n;
-    NHP_HIP(ctx, hipMemcpyAsync(dx, x, 8 * n, hipMemcpyHostToDevice, ctx->stream));
-    if (y) NHP_HIP(ctx, hipMemcpyAsync(dy, y, 8 * n, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, op, dx, y ? dy : nullptr, n, dout);
+    NHP_HIP(ctx, hipMemcpyAsync(dx, x, 8 * n, hipMemcpyHostToDevice, ctx->main()));
+    if (y) NHP_HIP(ctx, hipMemcpyAsync(dy, y, 8 * n, hipMemcpyHostToDevice, ctx->main()));
+    hipLaunchKernelGGL(k_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->main(), op, dx, y ? dy : nullptr, n, dout);
     NHP_HIP(ctx, hipGetLastError());
-    NHP_HIP(ctx, hipMemcpyAsync(out, dout, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
-    NHP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NHP_HIP(ctx, hipMemcpyAsync(out, dout, 8 * n, hipMemcpyDeviceToHost, ctx->main()));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     return NHP_OK;
 }
 
@@ -75,10 +75,10 @@ extern "C" nhp_status nhp_probe_rate(nhp_ctx *ctx, int32_t mode, int32_t iters, 
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, 8 * (size_t)blocks * 256));
     double *sink = (double *)ctx->d_scratch;
-    hipLaunchKernelGGL(k_probe_rate, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, mode, iters, sink);   // warm-up
-    NHP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    hipLaunchKernelGGL(k_probe_rate, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, mode, iters, sink);
-    NHP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    hipLaunchKernelGGL(k_probe_rate, dim3((unsigned)blocks), dim3(256), 0, ctx->main(), mode, iters, sink);   // warm-up
+    NHP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->main()));
+    hipLaunchKernelGGL(k_probe_rate, dim3((unsigned)blocks), dim3(256), 0, ctx->main(), mode, iters, sink);
+    NHP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->main()));
     NHP_HIP(ctx, hipEventSynchronize(ctx->ev1));
     float ms = 0.f;
     NHP_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
@@ -118,13 +118,13 @@ extern "C" nhp_status nhp_probe_gather(nhp_ctx *ctx, int32_t n_windows, int32_t 
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, 16 * (size_t)array_recs + 64));
     double2 *arr = (double2 *)ctx->d_scratch;
     double *sink = (double *)(arr + array_recs);
-    NHP_HIP(ctx, hipMemsetAsync(arr, 0, 16 * (size_t)array_recs, ctx->stream));
+    NHP_HIP(ctx, hipMemsetAsync(arr, 0, 16 * (size_t)array_recs, ctx->main()));
     const int reps = 20;
-    hipLaunchKernelGGL(k_probe_gather, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, arr, (unsigned)array_recs, recs, n_windows, sink);
-    NHP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    hipLaunchKernelGGL(k_probe_gather, dim3((unsigned)blocks), dim3(256), 0, ctx->main(), arr, (unsigned)array_recs, recs, n_windows, sink);
+    NHP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->main()));
     for (int r = 0; r < reps; ++r)
-        hipLaunchKernelGGL(k_probe_gather, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, arr, (unsigned)array_recs, recs, n_windows, sink);
-    NHP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        hipLaunchKernelGGL(k_probe_gather, dim3((unsigned)blocks), dim3(256), 0, ctx->main(), arr, (unsigned)array_recs, recs, n_windows, sink);
+    NHP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->main()));
     NHP_HIP(ctx, hipEventSynchronize(ctx->ev1));
     float ms = 0.f;
     NHP_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
@@ -182,14 +182,14 @@ extern "C" nhp_status nhp_probe_stream(nhp_ctx *ctx, int32_t mode, int64_t bytes
     uint32_t *a32 = (uint32_t *)ctx->d_scratch;
     uint16_t *a16 = (uint16_t *)(a32 + n32);
     double *sink = (double *)((char *)ctx->d_scratch + ((4 * n32 + 2 * n16 + 7) & ~(size_t)7));
-    NHP_HIP(ctx, hipMemsetAsync(a32, 0, 4 * n32 + 2 * n16, ctx->stream));
+    NHP_HIP(ctx, hipMemsetAsync(a32, 0, 4 * n32 + 2 * n16, ctx->main()));
     const int reps = 20;
     for (int r = 0; r <= reps; ++r) {
-        if (r == 1) NHP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        if (mode == 0) hipLaunchKernelGGL(k_probe_stream<0>, dim3((unsigned)blocks), dim3((unsigned)threads), 0, ctx->stream, a32, a16, rows_per_wave, sink);
-        else hipLaunchKernelGGL(k_probe_stream<1>, dim3((unsigned)blocks), dim3((unsigned)threads), 0, ctx->stream, a32, a16, rows_per_wave, sink);
+        if (r == 1) NHP_HIP(ctx, hipEventRecord(ctx->ev0, ctx->main()));
+        if (mode == 0) hipLaunchKernelGGL(k_probe_stream<0>, dim3((unsigned)blocks), dim3((unsigned)threads), 0, ctx->main(), a32, a16, rows_per_wave, sink);
+        else hipLaunchKernelGGL(k_probe_stream<1>, dim3((unsigned)blocks), dim3((unsigned)threads), 0, ctx->main(), a32, a16, rows_per_wave, sink);
     }
-    NHP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    NHP_HIP(ctx, hipEventRecord(ctx->ev1, ctx->main()));
     NHP_HIP(ctx, hipEventSynchronize(ctx->ev1));
     float ms = 0.f;
     NHP_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));

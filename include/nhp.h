@@ -516,6 +516,29 @@ nhp_status nhp_disc_lgcp_loglik(nhp_ctx *ctx, const nhp_disc_dataset *ds, const 
 nhp_status nhp_disc_vb_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
                            double alpha0, double beta0, double kappa, double nu, double gamma, int32_t n_steps,
                            double *alpha_v, double *beta_v, double *kappa_v, double *nu_v, double *gamma_v);
+/* svi!(process, data) -- a stub in the reference (src/inference.jl:190): n_steps steps of stochastic variational inference
+ * for DiscreteStandardHawkesProcess + DenseWeightModel + DiscreteHomogeneousProcess, the variational parameters resident on
+ * the device in between (one upload, one download, no synchronisation inside the loop).
+ * Blocks: Tb = min(batch_bins, T); the bins are cut into nb = ceil(T / Tb) consecutive blocks, block j = [j·Tb, min(T, (j+1)·Tb)).
+ * batch_bins >= T gives one block; otherwise it must be a multiple of 16 and >= 16 (NHP_EINVAL; nothing is rounded).
+ * Step k of the call is global step i = step0 + k + 1 on block j_i = blocks[k] (each in [0, nb)) or, with blocks = NULL, the
+ * draw nhp_disc_svi_blocks documents.  With (α', κ', γ') the update! of nhp_disc_vb_step with every sum over t restricted to
+ * the block (the factors from the current parameters; Ŝ is the convolution of the whole data):
+ *   α̂ = α0 + nb (α' - α0),  γ̂ = γ + nb (γ' - γ),  κ̂ = κ + Σ_b (γ̂ - γ),  β̂ = 1/β0 + T·dt,  ν̂[p,c] = ν + Σ_{t<T} data[p,t],
+ * and every parameter x <- (1 - ρ_i) x + ρ_i x̂ with ρ_i = (i + delay)^(-forgetting), delay >= 0, forgetting in (0.5, 1].
+ * Resident mode (phi = NULL): the dataset holds Ŝ (nhp_disc_convolve).  Streamed mode (phi [n_lags*n_basis], lag fastest,
+ * as nhp_disc_basis makes it): every step convolves its block into a Tb x N x B image, bit for bit the resident rows; the
+ * dataset needs no Ŝ and keeps none, and scratch is O(Tb·N·B).  Argument errors are NHP_EINVAL / NHP_ENOTIMPL with a message,
+ * before any launch. */
+nhp_status nhp_disc_svi_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
+                            double alpha0, double beta0, double kappa, double nu, double gamma,
+                            int64_t batch_bins, double delay, double forgetting, uint64_t seed, int64_t step0, int32_t n_steps,
+                            const int32_t *blocks /* nullable [n_steps] */, const double *phi /* nullable */, int32_t n_lags,
+                            int32_t n_basis, double *alpha_v, double *beta_v, double *kappa_v, double *nu_v, double *gamma_v);
+/* The blocks nhp_disc_svi_run draws for global steps step0 + 1 .. step0 + n (host side, no device): out[k] =
+ * min(nb - 1, floor(nb · u_i)), u_i the Philox4x32-10 uniform in [0, 1) with key seed ^ 0x5C1B10C5D2A7E391, counter words
+ * (event = 0, step = i), i = step0 + k + 1 -- a function of (seed, i) alone. */
+nhp_status nhp_disc_svi_blocks(uint64_t seed, int64_t step0, int64_t n, int32_t nb, int32_t *out);
 /* rand(process::DiscreteHawkesProcess, steps)  src/discrete.jl:20-38 on the device: the N x T count matrix of a discrete
  * Hawkes process over bins t = 1..T.  The law: cell (c, t) receives Poisson(base[t,c]) immigrants, base[t,c] = lambda0[c]·dt
  * (homogeneous baseline) or the caller's per-bin means base [T*N], t fastest, already times dt (intensity(baseline, 1:T) of a

@@ -1334,6 +1334,253 @@ extern "C" nhp_status nhp_disc_vb_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, 
     return NHP_OK;
 }
 
+// ---- stochastic variational inference (svi!: a stub in the reference, src/inference.jl:190) ----
+// One step = the mean-field update! with every sum over t restricted to one block of bins, the block statistics scaled by
+// the number of blocks nb, and the result blended into the current parameters with weight ρ.  The two GEMMs are the VB
+// step's, on the block's rows of Ŝ (pointer offset t0, lda = T) or of a block-sized image convolved on the fly.
+
+// Ŝ rows [t0, t0 + rows) of every (node, basis) into out[(t - t0) + n·ldo + b·ldo·N]: k_disc_convolve_dense with a window.
+// Counts are read from t0 - L on, zeros before bin 0; a bin's sum runs l = 1..L in increasing order with separate multiply
+// and add, so a row is bit for bit the row nhp_disc_convolve writes (either of its kernels: a skipped term is +0.0·ϕ).
+__global__ __launch_bounds__(256) void k_disc_convolve_window(const double *__restrict__ dataT, int N, int64_t T,
+                                                              const double *__restrict__ phi, int L, int B, int64_t t0, int rows,
+                                                              size_t ldo, double *__restrict__ out)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double csm[];
+    double *tile = csm;                                  // [256 + L]: data[n, tb-L .. tb+255], tb = t0 + 256·blockIdx.x
+    double *phiT = csm + 256 + L;                        // [L][Bp], Bp = B rounded up to CONV_CB
+    const int n = blockIdx.y, tid = threadIdx.x;
+    const int Bp = (B + CONV_CB - 1) / CONV_CB * CONV_CB;
+    const int r0 = blockIdx.x * 256;
+    const double *d = dataT + (size_t)n * T;
+    for (int i = tid; i < 256 + L; i += 256) {
+        const int64_t tt = t0 + r0 - L + i;
+        tile[i] = (tt >= 0 && tt < T) ? d[tt] : 0.0;
+    }
+    for (int i = tid; i < L * Bp; i += 256) {
+        const int l = i / Bp, b = i % Bp;
+        phiT[i] = b < B ? phi[l + (size_t)b * L] : 0.0;
+    }
+    __syncthreads();
+    const int r = r0 + tid;
+    for (int b0 = 0; b0 < B; b0 += CONV_CB) {
+        double s[CONV_CB];
+#pragma unroll
+        for (int q = 0; q < CONV_CB; ++q) s[q] = 0.0;
+        for (int l = 1; l <= L; ++l) {
+            const double x = tile[tid + L - l];          // data[n, t - l]
+            const double *ph = phiT + (size_t)(l - 1) * Bp + b0;
+#pragma unroll
+            for (int q = 0; q < CONV_CB; ++q) s[q] = s[q] + x * ph[q];
+        }
+        if (r < rows) {
+#pragma unroll
+            for (int q = 0; q < CONV_CB; ++q)
+                if (b0 + q < B) out[(size_t)r + (size_t)n * ldo + (size_t)(b0 + q) * ldo * N] = s[q] > 0.0 ? s[q] : 0.0;
+        }
+    }
+}
+
+// the block's counts as a compact rows x N matrix (the GEMM epilogue indexes its count operand with the output's shape)
+__global__ __launch_bounds__(256) void k_svi_block_data(const double *__restrict__ dataT, int64_t T, int64_t t0, int rows, int N,
+                                                        double *__restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)rows * N) return;
+    const size_t r = i % rows, c = i / rows;
+    out[i] = dataT[(size_t)t0 + r + c * (size_t)T];
+}
+
+// After GEMM-2 on the block: Γ = E ⊙ Σ_z slab_z, γ' = γ + Γ;  γ̂ = γ + nb (γ' - γ),  κ̂ = κ + Σ_b (γ̂ - γ),
+// ν̂[p,c] = ν + Σ_t data[p,t] (whole data);  x <- (1 - ρ) x + ρ x̂.  Fixed summation order, no atomics.
+__global__ __launch_bounds__(256) void k_svi_finish(int N, int B, int n_slabs, const double *__restrict__ slabs,
+                                                    const double *__restrict__ E, const double *__restrict__ colsum,
+                                                    double kappa, double nu, double gamma, double nb, double rho,
+                                                    double *__restrict__ kappa_v, double *__restrict__ nu_v,
+                                                    double *__restrict__ gamma_v)
+{
+    const size_t NN = (size_t)N * N, K = (size_t)N * B;
+    const size_t pc = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (pc >= NN) return;
+    const size_t p = pc % N, c = pc / N;
+    const double keep = 1.0 - rho;
+    double ksum = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const size_t o = p + (size_t)b * N + c * K;
+        double s = 0.0;
+        for (int z = 0; z < n_slabs; ++z) s += slabs[(size_t)z * K * N + o];
+        const double gp = gamma + E[o] * s;
+        const double gh = gamma + nb * (gp - gamma);
+        ksum += gh - gamma;
+        gamma_v[pc + (size_t)b * NN] = keep * gamma_v[pc + (size_t)b * NN] + rho * gh;
+    }
+    kappa_v[pc] = keep * kappa_v[pc] + rho * (kappa + ksum);
+    nu_v[pc] = keep * nu_v[pc] + rho * (nu + colsum[p]);
+}
+
+// α' = α0 + e0[c]·Σ_{t in block} R[t,c];  α̂ = α0 + nb (α' - α0),  β̂ = 1/β0 + T·dt (whole T);  the same blend
+__global__ __launch_bounds__(256) void k_svi_baseline(int N, int row_blocks, const double *__restrict__ colpart,
+                                                      const double *__restrict__ e0, double alpha0, double beta0, double Tdt,
+                                                      double nb, double rho, double *__restrict__ alpha_v, double *__restrict__ beta_v)
+{
+    __shared__ double part[4][64];                       // 64 columns x 4 row-slices, combined in a fixed order
+    const int cl = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cl;
+    double s = 0.0;
+    if (c < N)
+        for (int r = sl; r < row_blocks; r += 4) s += colpart[(size_t)r * N + c];
+    part[sl][cl] = s;
+    __syncthreads();
+    if (sl == 0 && c < N) {
+        const double ap = alpha0 + e0[c] * (((part[0][cl] + part[1][cl]) + part[2][cl]) + part[3][cl]);
+        const double keep = 1.0 - rho;
+        alpha_v[c] = keep * alpha_v[c] + rho * (alpha0 + nb * (ap - alpha0));
+        beta_v[c] = keep * beta_v[c] + rho * (1.0 / beta0 + Tdt);
+    }
+}
+
+// Block of step i (global, 1-based): floor(nb·u), u the Philox4x32-10 uniform with key seed ^ SVI_KEY and counter
+// (event 0, step i) -- a function of (seed, i) alone, so a run cut into chunks draws the same sequence.
+#define SVI_KEY 0x5C1B10C5D2A7E391ull
+static inline int32_t svi_block_of(uint64_t seed, uint64_t i, int32_t nb)
+{
+    const int32_t j = (int32_t)(nhp_philox_uniform(seed ^ SVI_KEY, i, 0) * (double)nb);
+    return j < nb ? j : nb - 1;
+}
+
+extern "C" nhp_status nhp_disc_svi_blocks(uint64_t seed, int64_t step0, int64_t n, int32_t nb, int32_t *out)
+{
+    if (!out || n < 0 || step0 < 0 || nb < 1) return NHP_EINVAL;
+    for (int64_t k = 0; k < n; ++k) out[k] = svi_block_of(seed, (uint64_t)(step0 + k + 1), nb);
+    return NHP_OK;
+}
+
+// GEMM-2's split of a `len`-long reduction (the VB step's rule).  svi_split_cap is the most slabs the rule can give: it is
+// monotone in len, so the cap of a whole block bounds every block, whole or short, and sizes the slab scratch.
+static int svi_split_cap(int64_t len, int tiles2, int cu_count)
+{
+    return std::max(1, std::min((2 * cu_count + tiles2 - 1) / tiles2, (int)((len + 4 * BK - 1) / (4 * BK))));
+}
+static void svi_split(int64_t len, int tiles2, int cu_count, int *splits, int *k_chunk)
+{
+    const int s = svi_split_cap(len, tiles2, cu_count);
+    int kc = (int)((len + s - 1) / s);
+    kc = ((kc + BK - 1) / BK) * BK;
+    *k_chunk = kc;
+    *splits = (int)((len + kc - 1) / kc);              // <= s: rounding the chunk up only removes slabs
+}
+
+extern "C" nhp_status nhp_disc_svi_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
+                                       double alpha0, double beta0, double kappa, double nu, double gamma,
+                                       int64_t batch_bins, double delay, double forgetting, uint64_t seed, int64_t step0,
+                                       int32_t n_steps, const int32_t *blocks, const double *phi, int32_t n_lags, int32_t n_basis,
+                                       double *alpha_v, double *beta_v, double *kappa_v, double *nu_v, double *gamma_v)
+{
+    if (!ctx || !ds || !alpha_v || !beta_v || !kappa_v || !nu_v || !gamma_v) return NHP_EINVAL;
+    if (n_steps < 1 || step0 < 0) { nhp_set_error(ctx, "svi: n_steps must be >= 1 and step0 >= 0"); return NHP_EINVAL; }
+    if (!(dt > 0.0)) { nhp_set_error(ctx, "svi: dt must be positive"); return NHP_EINVAL; }
+    if (!(delay >= 0.0)) { nhp_set_error(ctx, "svi: delay must be >= 0"); return NHP_EINVAL; }
+    if (!(forgetting > 0.5 && forgetting <= 1.0)) { nhp_set_error(ctx, "svi: forgetting must lie in (0.5, 1]"); return NHP_EINVAL; }
+    const int64_t Tn = ds->T;
+    // a convention of the interface (block starts on whole 16-element reduction chunks), not a need of the GEMM, which loads
+    // single doubles at any lda; nothing is rounded silently
+    if (batch_bins < Tn && (batch_bins < 16 || batch_bins % 16 != 0)) {
+        nhp_set_error(ctx, "svi: batch_bins = %lld must be a multiple of 16 (>= 16), or >= the %lld bins of the data", (long long)batch_bins, (long long)Tn);
+        return NHP_EINVAL;
+    }
+    const int64_t Tb = std::min(batch_bins, Tn);
+    const int32_t nb = (int32_t)((Tn + Tb - 1) / Tb);
+    if (blocks)
+        for (int32_t k = 0; k < n_steps; ++k)
+            if (blocks[k] < 0 || blocks[k] >= nb) { nhp_set_error(ctx, "svi: blocks[%d] = %d is outside [0, %d)", k, blocks[k], nb); return NHP_EINVAL; }
+    if (ds->d_baseT) { nhp_set_error(ctx, "svi: defined for DiscreteHomogeneousProcess baselines only"); return NHP_ENOTIMPL; }
+    const bool streamed = phi != nullptr;
+    if (streamed && (n_lags < 1 || n_basis < 1)) { nhp_set_error(ctx, "svi: the streamed mode needs n_lags >= 1 and n_basis >= 1"); return NHP_EINVAL; }
+    if (!streamed && !ds->d_conv) { nhp_set_error(ctx, "svi: convolve(process, data) must run first, or pass the basis for the streamed mode"); return NHP_EINVAL; }
+    const size_t N = (size_t)ds->N, NN = N * N, B = (size_t)(streamed ? n_basis : ds->B), K = N * B, T = (size_t)Tn, L = streamed ? (size_t)n_lags : 0;
+    const size_t lds_conv = 8 * (256 + L + L * ((B + CONV_CB - 1) / CONV_CB * CONV_CB));
+    if (streamed && lds_conv > 64 * 1024) { nhp_set_error(ctx, "svi: nlags * nbasis = %d * %d exceeds the LDS budget", n_lags, n_basis); return NHP_ENOTIMPL; }
+    NHP_HIP(ctx, hipSetDevice(ctx->device));
+    const int tiles2 = (int)(((K + BM - 1) / BM) * ((N + BN - 1) / BN));
+    const int max_splits = svi_split_cap(Tb, tiles2, ctx->cu_count);
+    const size_t max_row_blocks = (size_t)((Tb + BM - 1) / BM);
+    const size_t need = 8 * (K * N + N + N + N + NN + NN + NN * B + 2 * (size_t)Tb * N + max_row_blocks * N + (size_t)max_splits * K * N +
+                             (streamed ? (size_t)Tb * K + L * B : 0));
+    NHP_TRY(nhp_ctx_reserve_scratch(ctx, need));
+    double *p = (double *)ctx->d_scratch;
+    double *dE = p; p += K * N;
+    double *de0 = p; p += N;
+    double *dav = p; p += N;
+    double *dbv = p; p += N;
+    double *dkv = p; p += NN;
+    double *dnv = p; p += NN;
+    double *dgv = p; p += NN * B;
+    double *dD = p; p += (size_t)Tb * N;
+    double *dR = p; p += (size_t)Tb * N;
+    double *dcolp = p; p += max_row_blocks * N;
+    double *dslab = p; p += (size_t)max_splits * K * N;
+    double *dimg = p; p += streamed ? (size_t)Tb * K : 0;
+    double *dphi = p;
+    hipStream_t st = ctx->main();
+    NHP_HIP(ctx, hipMemcpyAsync(dav, alpha_v, 8 * N, hipMemcpyHostToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(dbv, beta_v, 8 * N, hipMemcpyHostToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(dkv, kappa_v, 8 * NN, hipMemcpyHostToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(dnv, nu_v, 8 * NN, hipMemcpyHostToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(dgv, gamma_v, 8 * NN * B, hipMemcpyHostToDevice, st));
+    if (streamed) NHP_HIP(ctx, hipMemcpyAsync(dphi, phi, 8 * L * B, hipMemcpyHostToDevice, st));
+    for (int32_t k = 0; k < n_steps; ++k) {           // variational parameters stay on the device between steps
+        const uint64_t i = (uint64_t)step0 + (uint64_t)k + 1;
+        const int64_t j = blocks ? blocks[k] : svi_block_of(seed, i, nb);
+        const int64_t t0 = j * Tb, len = std::min<int64_t>(Tn, t0 + Tb) - t0;
+        const double rho = pow((double)i + delay, -forgetting);
+        const int bm = gemm1_tile_m(len, (int)N, ctx->cu_count);
+        const int row_blocks = (int)((len + bm - 1) / bm);
+        int splits, k_chunk;
+        svi_split(len, tiles2, ctx->cu_count, &splits, &k_chunk);
+        hipLaunchKernelGGL(k_vb_factors, dim3((unsigned)((NN + 255) / 256)), dim3(256), 0, st, (int)N, (int)B, dav, dbv, dkv, dnv, dgv, dE, de0);
+        const double *G, *D = ds->d_dataT;
+        size_t ldg;
+        if (!streamed) {
+            G = ds->d_conv + t0; ldg = T;
+        } else {
+            hipLaunchKernelGGL(k_disc_convolve_window, dim3((unsigned)((len + 255) / 256), (unsigned)N), dim3(256), lds_conv, st, ds->d_dataT, (int)N,
+                               Tn, dphi, (int)L, (int)B, t0, (int)len, (size_t)len, dimg);
+            G = dimg; ldg = (size_t)len;
+        }
+        if (len < Tn) {
+            hipLaunchKernelGGL(k_svi_block_data, dim3((unsigned)(((size_t)len * N + 255) / 256)), dim3(256), 0, st, ds->d_dataT, Tn, t0, (int)len,
+                               (int)N, dD);
+            D = dD;
+        }
+        NHP_HIP(ctx, hipGetLastError());
+        // GEMM-1 on the block's rows: Z = e0 ⊕ G·E, R = data / Z, column sums of R
+        gemm_args g1{};
+        g1.A = G; g1.lda = ldg; g1.B = dE; g1.ldb = K; g1.M = (int)len; g1.N = (int)N; g1.K = (int)K; g1.k_chunk = (int)K;
+        g1.base = de0; g1.dataT = D; g1.out = dR; g1.partials = dcolp;
+        launch_gemm<true, EPI_VB_Z>(g1, 1, st, bm);
+        NHP_HIP(ctx, hipGetLastError());
+        // GEMM-2: slabs_z = Gᵀ·R over chunk z of the block
+        gemm_args g2{};
+        g2.A = G; g2.lda = ldg; g2.B = dR; g2.ldb = (size_t)len; g2.M = (int)K; g2.N = (int)N; g2.K = (int)len; g2.k_chunk = k_chunk;
+        g2.out = dslab;
+        launch_gemm<false, EPI_SLAB>(g2, splits, st);
+        NHP_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_svi_baseline, dim3((unsigned)((N + 63) / 64)), dim3(256), 0, st, (int)N, row_blocks, dcolp, de0,
+                           alpha0, beta0, (double)T * dt, (double)nb, rho, dav, dbv);
+        hipLaunchKernelGGL(k_svi_finish, dim3((unsigned)((NN + 255) / 256)), dim3(256), 0, st, (int)N, (int)B, splits, dslab, dE,
+                           ds->d_colsum, kappa, nu, gamma, (double)nb, rho, dkv, dnv, dgv);
+        NHP_HIP(ctx, hipGetLastError());
+    }
+    NHP_HIP(ctx, hipMemcpyAsync(alpha_v, dav, 8 * N, hipMemcpyDeviceToHost, st));
+    NHP_HIP(ctx, hipMemcpyAsync(beta_v, dbv, 8 * N, hipMemcpyDeviceToHost, st));
+    NHP_HIP(ctx, hipMemcpyAsync(kappa_v, dkv, 8 * NN, hipMemcpyDeviceToHost, st));
+    NHP_HIP(ctx, hipMemcpyAsync(nu_v, dnv, 8 * NN, hipMemcpyDeviceToHost, st));
+    NHP_HIP(ctx, hipMemcpyAsync(gamma_v, dgv, 8 * NN * B, hipMemcpyDeviceToHost, st));
+    NHP_HIP(ctx, hipStreamSynchronize(st));
+    return NHP_OK;
+}
+
 // DiscreteLogGaussianCoxProcess(x, λ, Σ, m, dt) as the baseline of this dataset's process (src/baselines.jl:461-509):
 // builds the per-bin baseline intensity on the device; later calls that pass lambda0 = NULL use it.
 extern "C" nhp_status nhp_disc_set_lgcp_baseline(nhp_ctx *ctx, nhp_disc_dataset *ds, const double *grid_x, int32_t grid_n,

@@ -906,6 +906,94 @@ class VariationalInference:
         return f"\n* Status: {self.status}\n    step: {self.step}\n    elapsed: {self.elapsed}"
 
 
+def svi_blocks(seed, step0, n, nblocks):
+    """The blocks svi_ draws for global steps step0 + 1 .. step0 + n (nhp_disc_svi_blocks): a function of (seed, step)
+    alone, computed on the host."""
+    out = np.empty(int(n), dtype=np.int32)
+    rc = _lib.lib().nhp_disc_svi_blocks(int(seed), int(step0), int(n), int(nblocks), out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != _lib.OK:
+        raise ValueError("svi_blocks: seed, step0 >= 0, n >= 0 and nblocks >= 1 are required")
+    return out
+
+
+def svi_(process, data, nsteps=1000, batch_bins=4096, delay=1.0, forgetting=0.6, seed=0, blocks=None, streamed=False,
+         trace_every=0, step0=0, ctx=None):
+    """svi!(process, data; ...) -- a stub in the reference (src/inference.jl:190): stochastic variational inference for the
+    models update_ accepts.  The T bins are cut into nb = ceil(T / batch_bins) consecutive blocks; step i (global, 1-based:
+    step0 + 1, ...) takes one block -- blocks[k] for the k-th step of this call, or a draw that depends on (seed, i) alone
+    (svi_blocks) -- computes the mean-field update! on that block alone, scales the block statistics by nb and blends the
+    result into the variational parameters with weight ρ_i = (i + delay)^(-forgetting).  batch_bins >= T gives one block;
+    otherwise it must be a multiple of 16.  streamed=True convolves each block on the fly instead of keeping the T x N x B
+    convolution on the device (the same numbers).  trace_every = k runs chunks of k steps and appends
+    variational_params(process) after each; 0 keeps only the final parameters.  svi_(..., step0=res.step) resumes a run
+    exactly.  Returns a VariationalInference whose `step` counts steps (step0 included)."""
+    from .components import SparseWeightModel
+    if (not isinstance(process, DiscreteStandardHawkesProcess) or not isinstance(process.weights, DenseWeightModel)
+            or isinstance(process.weights, SparseWeightModel)):
+        raise NotImplementedError("SVI exists only for DiscreteStandardHawkesProcess + DenseWeightModel "
+                                  "(the reference's network / sparse variants are broken: SURVEY D6)")
+    if not isinstance(process.baseline, DiscreteHomogeneousProcess):
+        raise NotImplementedError("svi! is defined for DiscreteHomogeneousProcess baselines only (src/baselines.jl:444-456)")
+    T = data.T if isinstance(data, DiscreteDataset) else np.asarray(data).shape[1]
+    nsteps, batch_bins, step0, trace_every = int(nsteps), int(batch_bins), int(step0), int(trace_every)
+    if nsteps < 0 or step0 < 0 or trace_every < 0:
+        raise ValueError("svi!: nsteps, step0 and trace_every must be non-negative")
+    if batch_bins < T and (batch_bins < 16 or batch_bins % 16 != 0):
+        raise ValueError(f"svi!: batch_bins = {batch_bins} must be a multiple of 16 (>= 16), or >= the {T} bins of the data")
+    if not delay >= 0.0:
+        raise ValueError("svi!: delay must be >= 0")
+    if not 0.5 < forgetting <= 1.0:
+        raise ValueError("svi!: forgetting must lie in (0.5, 1]")
+    Tb = min(batch_bins, T)
+    nb = -(-T // Tb)
+    if blocks is not None:
+        blocks = np.ascontiguousarray(blocks, dtype=np.int32)
+        if blocks.ndim != 1 or len(blocks) < nsteps:
+            raise ValueError(f"svi!: blocks holds {blocks.size} entries for {nsteps} steps")
+        if blocks.size and (blocks.min() < 0 or blocks.max() >= nb):
+            raise ValueError(f"svi!: block indices must lie in [0, {nb})")
+    ctx = ctx or _lib.default_context()
+    start = time.time()
+    b, w, imp = process.baseline, process.weights, process.impulses
+    N, B = process.ndims(), imp.nbasis()
+    if streamed:
+        ds = data if isinstance(data, DiscreteDataset) else DiscreteDataset(ctx, data)
+        phi = imp.basis()
+        L = phi.shape[0]
+        ph = np.asfortranarray(phi).ravel(order="K")
+    else:
+        ds = data if isinstance(data, DiscreteDataset) and data.B == B else convolve(process, data, ctx)
+        ph, L = None, 0
+    av, bv = _lib.f64(b.αv).copy(), _lib.f64(b.βv).copy()
+    kv, nv, gv = _lib.colmajor(w.κv).copy(), _lib.colmajor(w.νv).copy(), _lib.colmajor(imp.γv).copy()
+
+    def store():                                  # column-major views of the library's buffers, as update_ keeps them: no
+        b.αv, b.βv = av, bv                       # transposing copy here or at the next call (a later chunk updates them in place)
+        w.κv, w.νv = kv.reshape((N, N), order="F"), nv.reshape((N, N), order="F")
+        imp.γv = gv.reshape((N, N, B), order="F")
+
+    res = VariationalInference()
+    res.step = step0
+    done = 0
+    while done < nsteps:
+        n = min(trace_every, nsteps - done) if trace_every else nsteps
+        blk = None if blocks is None else blocks[done:done + n].ctypes.data_as(C.POINTER(C.c_int32))
+        _lib.check(_lib.lib().nhp_disc_svi_run(ctx.h, ds.h, process.dt, b.α0, b.β0, w.κ, w.ν, imp.γ, batch_bins, float(delay),
+                                               float(forgetting), int(seed), step0 + done, n, blk, _lib.dptr(ph), L, B,
+                                               _lib.dptr(av), _lib.dptr(bv), _lib.dptr(kv), _lib.dptr(nv), _lib.dptr(gv)),
+                   ctx.h)
+        done += n
+        res.step = step0 + done
+        store()
+        if trace_every:
+            res.trace.append(process.variational_params())
+    if not trace_every:
+        res.trace.append(process.variational_params())
+    res.elapsed = time.time() - start
+    res.status = "complete"
+    return res
+
+
 def vb_(process, data, max_steps=1000, Δx_thresh=1e-6, Δq_thresh=1e-2, verbose=False, keep_trace=True, ctx=None):
     """vb!(process, data; max_steps, Δx_thresh, Δq_thresh, verbose) -- src/inference.jl:153-181.
     Like the reference (whose convergence test is commented out, :163-176) it runs max_steps updates.

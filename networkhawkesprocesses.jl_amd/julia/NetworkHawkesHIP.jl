@@ -743,6 +743,60 @@ function vb!(p::NHP.DiscreteStandardHawkesProcess, data::Matrix{Int64}; max_step
     return res
 end
 
+# --- svi!(process, data; nsteps=1_000, batch_bins=4096, delay=1.0, forgetting=0.6, seed=0, blocks=nothing, streamed=false,
+#          trace_every=0, step0=0) -> VariationalInference       a stub in the reference (src/inference.jl:190)
+# Stochastic variational inference (nhp_disc_svi_run; the contract is in include/nhp.h): the T bins are cut into
+# nb = cld(T, batch_bins) consecutive blocks, step i = step0 + k takes one block -- blocks[k] (0-based, as the library counts
+# them), or a draw that depends on (seed, i) alone -- and blends the block's update!, scaled by nb, into the variational
+# parameters with weight (i + delay)^(-forgetting).  streamed=true convolves each block on the fly and never holds the
+# T x N x B convolution.  trace_every = k appends variational_params(process) every k steps; 0 keeps the final ones.
+function svi!(p::NHP.DiscreteStandardHawkesProcess, data::Matrix{Int64}; nsteps::Integer=1_000, batch_bins::Integer=4096, delay=1.0,
+              forgetting=0.6, seed::Integer=0, blocks=nothing, streamed::Bool=false, trace_every::Integer=0, step0::Integer=0,
+              ctx=context())
+    p.weights isa NHP.DenseWeightModel || error("svi! exists only for DenseWeightModel")
+    p.baseline isa NHP.DiscreteHomogeneousProcess || error("svi! is defined for DiscreteHomogeneousProcess baselines only")
+    N, T = size(data)
+    (batch_bins >= T || (batch_bins >= 16 && batch_bins % 16 == 0)) || throw(ArgumentError("batch_bins must be a multiple of 16, or >= the number of bins"))
+    delay >= 0 || throw(ArgumentError("delay must be >= 0"))
+    0.5 < forgetting <= 1 || throw(ArgumentError("forgetting must lie in (0.5, 1]"))
+    nb = cld(T, min(batch_bins, T))
+    blk = blocks === nothing ? nothing : Vector{Int32}(blocks)
+    blk === nothing || (length(blk) >= nsteps && all(0 .<= blk .< nb)) || throw(ArgumentError("blocks: nsteps indices in [0, $nb) are required"))
+    phi = basis_matrix(p.impulses)
+    L, B = size(phi)
+    if streamed
+        r = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:nhp_disc_dataset_create, libnhp), Int32, (Ptr{Cvoid}, Ptr{Int64}, Int32, Int64, Ref{Ptr{Cvoid}}), ctx.h, data, N, T, r), ctx.h)
+        c = Convolved(r[], N, T, 0, data, nothing)
+        finalizer(x -> ccall((:nhp_disc_dataset_destroy, libnhp), Cvoid, (Ptr{Cvoid},), x.h), c)
+    else
+        c = convolve(p, data; ctx=ctx)
+    end
+    b, w, imp = p.baseline, p.weights, p.impulses
+    αv, βv = Vector{Float64}(b.αv), Vector{Float64}(b.βv)
+    κv, νv, γv = Matrix{Float64}(w.κv), Matrix{Float64}(w.νv), Array{Float64,3}(imp.γv)
+    res = NHP.VariationalInference(p)
+    res.step = step0
+    start_time = time()
+    done = 0
+    while done < nsteps
+        n = trace_every > 0 ? min(trace_every, nsteps - done) : nsteps
+        bp = blk === nothing ? Ptr{Int32}(C_NULL) : pointer(blk, done + 1)
+        GC.@preserve blk phi c check(ccall((:nhp_disc_svi_run, libnhp), Int32,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, Float64, Int64, Float64, Float64, UInt64, Int64, Int32,
+             Ptr{Int32}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+            ctx.h, c.h, p.dt, b.α0, b.β0, w.κ, w.ν, imp.γ, batch_bins, delay, forgetting, seed % UInt64, step0 + done, n,
+            bp, streamed ? pointer(phi) : Ptr{Float64}(C_NULL), L, B, αv, βv, κv, νv, γv), ctx.h)
+        done += n
+        res.step = step0 + done
+        b.αv, b.βv, w.κv, w.νv, imp.γv = copy(αv), copy(βv), copy(κv), copy(νv), copy(γv)
+        trace_every > 0 && push!(res.trace, NHP.variational_params(p))
+    end
+    trace_every > 0 || push!(res.trace, NHP.variational_params(p))
+    res.elapsed = time() - start_time
+    return res
+end
+
 # --- mle!(process::DiscreteStandardHawkesProcess, data; optimizer=BFGS, verbose=false, f_abstol=1e-6, regularize=false,
 #          guess=nothing, max_increase_steps=3) -> MaximumLikelihood   src/discrete.jl:211-296 ---------------------------
 # Parameter vector [λ0; vec(W .* θ)] (params / params!, src/discrete.jl:174-201).  regularize=true calls the reference's

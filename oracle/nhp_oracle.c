@@ -561,8 +561,10 @@ int orc_cont_resample_adjacency(const orc_cont_model *m, const double *times, co
  * No reference code: the reference hands Optim no gradient (src/continuous.jl:190), so one
  * gradient costs it 2P objective calls.  Formulas from SURVEY.md 7; validated in tests/ by
  * central finite differences of the ll functions above.  Output order is params! order
- * (src/continuous.jl:121-129): [λ0 (N); θ (N²) | μ (N²); τ (N²); W (N²)].  Homogeneous
- * baseline only.  recursive != 0 differentiates the recursive formulation (all earlier
+ * (src/continuous.jl:121-129): [λ0 (N) | grid intensities (G·N, g fastest); θ (N²) | μ (N²); τ (N²); W (N²)].  Both
+ * baselines: the grid block is the trapezoid rule's derivative (duration ignored) plus 1/λ
+ * spread over the event's two grid neighbours.  Held to the extended-precision restatement
+ * tests/cont_grad_ref.py by tests/test_cont_grad_host.py.  recursive != 0 differentiates the recursive formulation (all earlier
  * parents with time > 0, unmasked integral). */
 int orc_cont_loglik_grad(const orc_cont_model *m, const double *times, const int64_t *nodes,
                          int64_t M, double duration, int recursive, double *ll_out, double *grad)

@@ -802,6 +802,32 @@ nhp_status nhp_cont_em_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_mo
                            int32_t max_steps, double *x, int64_t len, double *loss, int32_t *steps, int32_t *converged,
                            double *trace /* nullable, [max_steps + 1] */);
 
+/* Observed information and Hessian-vector products of the continuous log-likelihood (csrc/cont_information.hip).  The
+ * objective nhp_cont_loglik evaluates separates by child node c, so its Hessian is block diagonal: one block per column
+ * over the D = 1 + kinds·N parameters [λ0[c]; θ[:,c] | μ[:,c]; τ[:,c]; W[:,c]] (kinds = 2 exponential, 3 logit-normal), row and
+ * column 0 λ0[c], then 1 + q·N + p for impulse kind q of parent p, then 1 + (kinds-1)·N + p for W[p,c].  Homogeneous baseline;
+ * standard and network models (a = A[p,c] multiplies the pair sums).  flags: NHP_LL_RECURSIVE (exponential impulses) sums
+ * every earlier event with t_j > 0 through the truncated windows of nhp_cont_loglik (less than 2^-60·λ_i dropped per event).
+ *
+ * nhp_cont_information: blocks[k] = MINUS the Hessian block of column columns[k] (all N columns in order when columns is
+ * NULL), D·D doubles each, column-major, exactly symmetric; a host pointer, or a device pointer with on_device.  *ll
+ * (nullable, host) the log-likelihood.  tile_nodes: parent nodes per tile of a block kept in LDS; 0 picks the whole block
+ * where it fits the 160 KiB and the largest tile that does otherwise.  Sums are LDS and global fp64 atomics: entries are
+ * not bit-reproducible from run to run.
+ * nhp_cont_hessian_vec: out = H·v (the Hessian itself), v and out [len = P] in params! order [λ0; θ | μ; τ; W]; host
+ * pointers, or device pointers with on_device.  Stores no block.
+ *
+ * Both are synchronous and write nothing when they refuse: NHP_ENOTIMPL for an LGCP baseline, a column shard,
+ * NHP_LL_FULL_RECURSION, a recursive objective without a usable truncated window, and a tile or column that does not fit
+ * the LDS; NHP_EINVAL for a column index outside [0, N) or repeated, n_columns <= 0 with columns given, tile_nodes outside
+ * [0, N], and len != P; NHP_ENOMEM when the blocks do not fit in device memory.  nhp_last_error gives the reason. */
+nhp_status nhp_cont_information(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *model, int32_t flags,
+                                const int32_t *columns /* [n_columns], 0-based; NULL: all */, int32_t n_columns,
+                                int32_t tile_nodes /* 0: auto */, int32_t on_device,
+                                double *ll /* nullable */, double *blocks /* [n_columns · D · D], each block column-major */);
+nhp_status nhp_cont_hessian_vec(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *model, int32_t flags,
+                                int32_t on_device, const double *v /* [P] */, double *out /* [P] */, int64_t len);
+
 /* mle!(process::DiscreteStandardHawkesProcess, data; f_abstol, guess) (src/discrete.jl:211-296) the same way: x = params(process)
  * = [λ0; vec(W .* θ)] (src/discrete.jl:178-182; homogeneous baseline), the objective -loglikelihood(process, data, convolved) with
  * params!'s split W = Σ_b, θ = x ./ W (:195-203) redone on the device per evaluation, its gradient from the two GEMMs of

@@ -23,8 +23,9 @@ from .discrete import (DiscreteDataset, DiscreteFitTest, DiscreteForecast, Discr
 from . import discrete as _disc
 from .parents import (Cascades, cascades, map_parents, node_counts, parent_counts, resample_parents,  # noqa: F401
                       uniform_stream)
-from .inference import (ExpectedStatistics, MarkovChainMonteCarlo, MaximumLikelihood, em_, expected_statistics,  # noqa: F401
-                        logprior, resample_adjacency_matrix_)
+from .inference import (ExpectedStatistics, Information, MarkovChainMonteCarlo, MaximumLikelihood, StandardErrors,  # noqa: F401
+                        em_, expected_statistics, hessian_vector_product, logprior, observed_information,
+                        resample_adjacency_matrix_, standard_errors)
 from . import inference as _inf
 from . import synthetic  # noqa: F401
 from .synthetic import rand  # noqa: F401   rand(process, duration): the reference's exported simulator name

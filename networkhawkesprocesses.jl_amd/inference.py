@@ -276,6 +276,205 @@ def em_(process, data, max_steps=1000, f_abstol=1e-6, regularize=False, guess=No
     return res
 
 
+# ---- observed information, Hessian-vector products, standard errors ------------------------------------------------------
+Information = collections.namedtuple("Information", "ll columns blocks names")
+StandardErrors = collections.namedtuple("StandardErrors", "se lower_ci upper_ci free pd")
+
+
+def _information_check(process, data, what):
+    """_em_check's argument errors (a network process is admitted: its A multiplies the pair sums), before any device work."""
+    from .sharded import ShardedDataset
+    if not isinstance(process, (ContinuousStandardHawkesProcess, ContinuousNetworkHawkesProcess)):
+        raise TypeError(f"{what} is defined for continuous Hawkes processes")
+    if not isinstance(process.baseline, HomogeneousProcess):
+        raise NotImplementedError(f"{what}: not available for a LogGaussianCoxProcess baseline")
+    if isinstance(data, ShardedDataset):
+        raise NotImplementedError(f"{what}: not available on a column shard (sharded.ShardedDataset)")
+
+
+def _kinds(process):
+    return ("θ", "W") if isinstance(process.impulses, ExponentialImpulseResponse) else ("μ", "τ", "W")
+
+
+def _params_order(process):
+    """[λ0; θ | μ; τ; W]: params! order, for a network process too (whose params() leads with ρ and ends with vec(A))."""
+    return np.concatenate([process.baseline.params(), process.impulses.params(), process.weights.params()])
+
+
+def block_index(N, kinds, c):
+    """Positions in the params!-order vector of the rows of column c's block: λ0[c], then p fastest inside each kind."""
+    k = np.arange(kinds)[:, None] * N * N + np.arange(N)[None, :] + c * N
+    return np.concatenate([[c], N + k.ravel()])
+
+
+def _check_columns(columns, N):
+    if columns is None:
+        return np.arange(N, dtype=np.int32)
+    cols = np.asarray(columns)
+    if cols.ndim != 1 or len(cols) == 0 or not np.issubdtype(cols.dtype, np.integer):
+        raise ValueError("columns must be a non-empty list of 0-based node indices")
+    if cols.min() < 0 or cols.max() >= N or len(np.unique(cols)) != len(cols):
+        raise ValueError(f"columns must be distinct indices in [0, {N})")
+    return np.ascontiguousarray(cols, dtype=np.int32)
+
+
+def _prior_information(process, cols):
+    """Minus the Hessian of logprior, column by column: (diag [n, D], the (μ, τ) entries [n, N] or None)."""
+    b, w, imp = process.baseline, process.weights, process.impulses
+    N = process.ndims()
+    full = lambda v: np.broadcast_to(np.asarray(v, dtype=np.float64), (N, N))
+    parts = [((np.broadcast_to(b.α0, (N,)) - 1.0) / np.asarray(b.λ) ** 2)[cols][:, None]]
+    off = None
+    if isinstance(imp, ExponentialImpulseResponse):
+        parts.append(((full(imp.α) - 1.0) / imp.θ ** 2)[:, cols].T)
+    else:
+        parts.append((full(imp.κμ) * imp.τ)[:, cols].T)
+        parts.append(((full(imp.α0) - 1.0 + 0.5) / imp.τ ** 2)[:, cols].T)
+        off = (full(imp.κμ) * (imp.μ - full(imp.μμ)))[:, cols].T
+    parts.append(((full(w.κ) - 1.0) / w.W ** 2)[:, cols].T)
+    return np.concatenate(parts, axis=1), off
+
+
+def observed_information(process, data, columns=None, recursive=True, regularize=False, device=False, tile_nodes=0, ctx=None):
+    """The observed information of the objective mle_ / em_ maximise, at the process's current parameters
+    (nhp_cont_information).
+
+    The objective separates by child node, so the information is block diagonal: `blocks[k]` is MINUS the Hessian over the
+    D = 1 + kinds·N parameters [λ0[c]; θ[:,c] | μ[:,c]; τ[:,c]; W[:,c]] of column c = columns[k] (all columns in order by
+    default), positive definite at a well-determined optimum; `names[r]` = (kind, parent) of row r (parent None for λ0).
+    regularize adds minus the Hessian of logprior (and logprior to ll).  recursive as in loglikelihood; where the recursive objective has no
+    truncated window the call raises NotImplementedError.  tile_nodes: parent nodes per LDS tile of a block (0: automatic).
+    device=False: numpy [n_columns, D, D]; device=True: a float64 torch tensor on the context's device.  Returns
+    Information(ll, columns, blocks, names)."""
+    import ctypes as C
+    from .continuous import _check_recursive
+    _information_check(process, data, "observed_information")
+    N = process.ndims()
+    cols = _check_columns(columns, N)
+    if not (isinstance(tile_nodes, (int, np.integer)) and 0 <= tile_nodes <= N):
+        raise ValueError(f"tile_nodes must be an integer in [0, {N}] (0: automatic)")
+    kinds = _kinds(process)
+    D = 1 + len(kinds) * N
+    prior = _prior_information(process, cols) if regularize else None
+    ctx = ctx or _lib.default_context()
+    ds = device_dataset(process, data, ctx)
+    model = process.device_model(ctx)
+    flags = _check_recursive(process, recursive)
+    ll = C.c_double()
+    fn = _lib.lib().nhp_cont_information
+    if device:
+        import torch
+        dev = torch.device("cuda", ctx.device)
+        out = torch.empty((len(cols), D, D), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()          # earlier users of the buffer's memory are done before the library writes
+        _lib.check(fn(ctx.h, ds.h, model.h, flags, cols.ctypes.data_as(C.POINTER(C.c_int32)), len(cols), int(tile_nodes), 1, C.byref(ll), out.data_ptr()), ctx.h)
+        blocks = out.transpose(1, 2)                           # column-major blocks (symmetric: the same numbers)
+    else:
+        out = np.empty((len(cols), D, D))
+        _lib.check(fn(ctx.h, ds.h, model.h, flags, cols.ctypes.data_as(C.POINTER(C.c_int32)), len(cols), int(tile_nodes), 0, C.byref(ll), out.ctypes.data), ctx.h)
+        blocks = out.transpose(0, 2, 1)
+    value = ll.value
+    if prior is not None:
+        diag, off = prior
+        r = np.arange(D)
+        if device:
+            blocks = blocks.contiguous()
+            blocks[:, r, r] += torch.as_tensor(diag, device=dev)
+        else:
+            blocks = np.ascontiguousarray(blocks)
+            blocks[:, r, r] += diag
+        if off is not None:
+            mu, tau = 1 + np.arange(N), 1 + N + np.arange(N)
+            o = torch.as_tensor(off, device=dev) if device else off
+            blocks[:, mu, tau] += o
+            blocks[:, tau, mu] += o
+        value += logprior(process)
+    names = [("λ0", None)] + [(k, p) for k in kinds[:-1] for p in range(N)] + [("W", p) for p in range(N)]
+    return Information(value, cols.copy(), blocks, names)
+
+
+def hessian_vector_product(process, data, v, recursive=True, device=False, ctx=None):
+    """H·v for the Hessian H of loglikelihood(process, data; recursive) at the process's current parameters, v and the
+    result in params! order [λ0; θ | μ; τ; W] (nhp_cont_hessian_vec: two window walks per event, no block is stored).  H is
+    the Hessian itself, not minus it.  device=False: numpy in and out; device=True: float64 torch tensors on the
+    context's device."""
+    from .continuous import _check_recursive
+    _information_check(process, data, "hessian_vector_product")
+    N = process.ndims()
+    P = N + len(_kinds(process)) * N * N
+    if device:
+        import torch
+        if not (isinstance(v, torch.Tensor) and v.dtype == torch.float64 and v.is_cuda and tuple(v.shape) == (P,)):
+            raise ValueError(f"device=True takes a float64 tensor of length {P} on the context's device")
+    else:
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.shape != (P,):
+            raise ValueError("Parameter vector length does not match model parameter length.")
+    ctx = ctx or _lib.default_context()
+    ds = device_dataset(process, data, ctx)
+    model = process.device_model(ctx)
+    flags = _check_recursive(process, recursive)
+    fn = _lib.lib().nhp_cont_hessian_vec
+    if device:
+        dev = torch.device("cuda", ctx.device)
+        v = v.contiguous()
+        out = torch.empty(P, dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        _lib.check(fn(ctx.h, ds.h, model.h, flags, 1, v.data_ptr(), out.data_ptr(), P), ctx.h)
+        return out
+    out = np.empty(P)
+    _lib.check(fn(ctx.h, ds.h, model.h, flags, 0, v.ctypes.data, out.ctypes.data, P), ctx.h)
+    return out
+
+
+def _standard_errors_from_blocks(blocks, cols, x, N, kinds, lower, upper, level):
+    """standard_errors' host part: free sets, Cholesky of the free sub-blocks, Wald intervals."""
+    from scipy.linalg import solve_triangular
+    from scipy.stats import norm
+    P = len(x)
+    se = np.full(P, np.nan)
+    free = np.zeros(P, dtype=bool)
+    pd = np.zeros(len(cols), dtype=bool)
+    for k, c in enumerate(cols):
+        idx = block_index(N, kinds, int(c))
+        B = np.asarray(blocks[k], dtype=np.float64)
+        inside = (x[idx] > lower) & (x[idx] < upper)
+        f = inside & np.any(B != 0.0, axis=1)
+        sub = B[np.ix_(f, f)]
+        ok = bool(np.all(np.isfinite(sub)))
+        if ok and f.any():
+            try:
+                L = np.linalg.cholesky(sub)
+                Li = solve_triangular(L, np.eye(len(L)), lower=True)
+                var = (Li * Li).sum(axis=0)
+                ok = bool(np.all(np.isfinite(var)) and np.all(var > 0.0))
+            except np.linalg.LinAlgError:
+                ok = False
+        pd[k] = ok
+        if ok:
+            free[idx[f]] = True
+            if f.any():
+                se[idx[f]] = np.sqrt(var)
+    z = norm.ppf(0.5 + 0.5 * level)
+    return StandardErrors(se, x - z * se, x + z * se, free, pd)
+
+
+def standard_errors(process, data, columns=None, recursive=True, regularize=False, lower=1e-6, upper=10.0, level=0.95, ctx=None):
+    """Standard errors and Wald intervals of the fitted process's parameters from the inverse observed information.
+
+    se, lower_ci, upper_ci [P] in params! order, NaN where undefined; free [P]: the parameters the inverse was taken over --
+    those strictly inside the box (lower, upper) whose row of the column's block is not identically zero (a link with
+    A = 0 or W = 0's impulse parameters, a parent no window joins to the column); pd [n_columns]: the free sub-block of
+    column columns[k] is positive definite (Cholesky on the host).  A column that is not gets NaNs, no exception."""
+    if not 0.0 < level < 1.0:
+        raise ValueError("level must lie in (0, 1)")
+    if not lower < upper:
+        raise ValueError("lower must be below upper")
+    info = observed_information(process, data, columns=columns, recursive=recursive, regularize=regularize, ctx=ctx)
+    return _standard_errors_from_blocks(info.blocks, info.columns, _params_order(process), process.ndims(), len(_kinds(process)),
+                                        lower, upper, level)
+
+
 def resample_adjacency_matrix_(process, data, u=None, seed=0, step=0, model=None, fetch=True, ctx=None):
     """resample_adjacency_matrix!(process, data) -- src/continuous.jl:444-470: one Gibbs sweep of the
     adjacency matrix, columns in parallel, entries of a column in sequence (resample_column! :472-487).

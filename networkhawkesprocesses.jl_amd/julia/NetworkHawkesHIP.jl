@@ -546,6 +546,39 @@ function em!(p::NHP.ContinuousStandardHawkesProcess, data; max_steps=1000, f_abs
     keep_trace ? (res, trace[1:steps[]+1]) : res
 end
 
+# --- observed_information(process, data) and hessian_vector_product(process, data, v): no reference counterpart ---------------
+# The objective separates by child node, so minus its Hessian is block diagonal: blocks[:, :, k] is the D x D block of column
+# columns[k] (1-based here) over [λ0[c]; θ[:,c] | μ[:,c]; τ[:,c]; W[:,c]], D = 1 + kinds·N (nhp_cont_information; homogeneous
+# baseline).  hessian_vector_product returns H·v (the Hessian itself) in params! order (nhp_cont_hessian_vec).  recursive=true
+# sums every earlier event through the truncated windows of loglikelihood and errors where there is none.
+function observed_information(p::NHP.ContinuousHawkesProcess, data; columns=nothing, recursive=true, tile_nodes=0, ctx=context(),
+                              ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    N = NHP.ndims(p)
+    kinds = p.impulses isa NHP.ExponentialImpulseResponse ? 2 : 3
+    D = 1 + kinds * N
+    cols = columns === nothing ? collect(1:N) : collect(Int, columns)
+    c0 = Vector{Int32}(cols .- 1)
+    ll, blocks = Ref{Float64}(0.0), Array{Float64}(undef, D, D, length(cols))
+    with_model(ctx, p) do m
+        check(ccall((:nhp_cont_information, libnhp), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Int32}, Int32, Int32, Int32, Ref{Float64}, Ptr{Float64}),
+                    ctx.h, ds.h, m, llflags(p, recursive), c0, Int32(length(c0)), Int32(tile_nodes), Int32(0), ll, blocks), ctx.h)
+    end
+    (ll=ll[], columns=cols, blocks=blocks)
+end
+
+function hessian_vector_product(p::NHP.ContinuousHawkesProcess, data, v::AbstractVector; recursive=true, ctx=context(),
+                                ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    x = Vector{Float64}(v)
+    out = similar(x)
+    with_model(ctx, p) do m
+        check(ccall((:nhp_cont_hessian_vec, libnhp), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Int64),
+                    ctx.h, ds.h, m, llflags(p, recursive), Int32(0), x, out, length(x)), ctx.h)
+    end
+    out
+end
+
 # --- mcmc!(process, data; nsteps=1000, log_freq=100, verbose=false) -> MarkovChainMonteCarlo  src/inference.jl:49-70
 # A sweep -- parents, sufficient statistics, conjugate draws, (network) adjacency sweep and ρ -- stays on the device
 # (nhp_cont_gibbs_step / nhp_cont_network_step); `push!(res.samples, params(process))` downloads the parameters every

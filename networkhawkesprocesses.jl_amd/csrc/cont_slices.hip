@@ -36,14 +36,24 @@ struct nhp_slices {               // kernel-side view of nhp_cont_dataset::d_sl_
 
 #ifdef NHP_STAMP      // diagnostic build only (tools/dbg/slstamps.py): s_memrealtime (100 MHz, one clock for all XCDs) at the phase boundaries of wave 0 of every workgroup
 __device__ unsigned long long g_sl_stamps[8 * 4096];
+__device__ unsigned long long g_sl_wave_end[16 * 4096];      // and of EVERY wave at the end of its slices (0: the workgroup has no such wave)
 #define NHP_SL_STAMP(i) do { if (threadIdx.x == 0 && blockIdx.x < 4096) g_sl_stamps[8 * blockIdx.x + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define NHP_SL_STAMP_WAVE() do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 4096) g_sl_wave_end[16 * blockIdx.x + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 extern "C" int nhp_debug_stamps_slices(unsigned long long *out, int n)
 {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sl_stamps), sizeof(unsigned long long) * (size_t)n);
 }
+extern "C" int nhp_debug_stamps_slices_waves(unsigned long long *out, int n)
+{
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sl_wave_end), sizeof(unsigned long long) * (size_t)n);
+}
 #else
 #define NHP_SL_STAMP(i) do { } while (0)
+#define NHP_SL_STAMP_WAVE() do { } while (0)
 #endif
+
+// the dealing of slices to waves as the kernels below compute it, for a host test
+extern "C" int32_t nhp_debug_slice_of(int32_t round, int32_t wave, int32_t nw) { return nhp_slice_of(round, wave, nw); }
 
 __device__ __forceinline__ double sl_baseline(const nhp_cont_args &a, int c, double t)
 {
@@ -367,8 +377,9 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
     };
     double prod = 1.0, gsum = 0.0;
     int pexp = 0;
+    int rnd = 0;                                                    // the wave's slices in snake order (nhp_slice_of)
     while (j < ns) {
-        const int jn = j + NW;
+        const int jn = nhp_slice_of(++rnd, w, NW);
         uint32_t row0n = 0;
         int Kn = 0;
         if (jn < ns) { row0n = sl.row[s0 + jn]; Kn = (int)(sl.row[s0 + jn + 1] - row0n); }
@@ -400,6 +411,7 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
         prod = __builtin_amdgcn_frexp_mant(prod);
         j = jn; row0 = row0n; K = Kn;
     }
+    NHP_SL_STAMP_WAVE();
     NHP_SL_STAMP(2);
     if (GRAD) {
         // ---- phase B: the item's pairs by parent node ----
@@ -623,8 +635,9 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
     int pexp[S];
 #pragma unroll
     for (int m = 0; m < S; ++m) { lam0[m] = st.lambda0[m][c]; prod[m] = 1.0; pexp[m] = 0; }
+    int rnd = 0;                                                    // the wave's slices in snake order (nhp_slice_of)
     while (j < ns) {
-        const int jn = j + NW;
+        const int jn = nhp_slice_of(++rnd, w, NW);
         uint32_t row0n = 0;
         int Kn = 0;
         if (jn < ns) { row0n = sl.row[s0 + jn]; Kn = (int)(sl.row[s0 + jn + 1] - row0n); }
@@ -946,8 +959,9 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices_ln(nhp_cont_args a, n
     };
     double prod = 1.0;
     int pexp = 0;
+    int rnd = 0;                                                    // the wave's slices in snake order (nhp_slice_of)
     while (j < ns) {
-        const int jn = j + NW;
+        const int jn = nhp_slice_of(++rnd, w, NW);
         uint32_t row0n = 0;
         int Kn = 0;
         if (jn < ns) { row0n = sl.row[s0 + jn]; Kn = (int)(sl.row[s0 + jn + 1] - row0n); }

@@ -467,6 +467,15 @@ inline bool nhp_slices_off(const char *route_switch)
     const char *all = getenv("NHP_SLICES"), *route = route_switch ? getenv(route_switch) : nullptr;
     return (all && atoi(all) == 0) || (route && atoi(route) == 0);
 }
+// How an item's child slices are dealt to the nw waves of its workgroup: in snake order.  Round r hands out slices
+// r·nw .. r·nw + nw - 1, forwards when r is even and backwards when it is odd.  Children are sorted longest window first, so
+// slice j has about as many rows as the item's 64·j-th longest window: dealt forwards every round, wave 0 would take the
+// longest slice of each.  Round 0 is j = wave (a kernel's head requests that slice's rows before anything else).  A wave's
+// slices increase with the round, so once one is past the item's last every later one is too.
+__host__ __device__ inline int32_t nhp_slice_of(int32_t round, int32_t wave, int32_t nw)
+{
+    return round * nw + ((round & 1) ? nw - 1 - wave : wave);
+}
 // cont_slices.hip: the exponential log-likelihood of the dataset's own short windows, one lane per child over the child
 // slices.  *launched = false (and NHP_OK) when the dataset has no slices or the model is not covered.
 nhp_status nhp_launch_windowed_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int mask_integral,

@@ -1,6 +1,8 @@
 """Phase timeline of k_windowed_slices from a -DNHP_STAMP build (NHP_LIB=... python tools/dbg/slstamps.py): wave 0 of every
 workgroup stamps s_memrealtime (100 MHz, the same clock on every XCD) at its start, after the column is staged, after its
-slices, after the block sums, after the ticket.  Times in us from the launch's first workgroup start."""
+slices, after the block sums, after the ticket; EVERY wave stamps the end of its own slices, and the spread between a
+workgroup's first and last wave to finish is what the dealing of slices to waves (nhp_slice_of) is there to shrink: the early
+waves wait at the block-sum barrier for the last one.  Times in us from the launch's first workgroup start."""
 import os, sys, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
@@ -30,3 +32,30 @@ for k, name in enumerate(("column staging", "slices (pair rows)", "log + block s
 print("workgroup lifetime mean %.2f us, max %.2f; last ticket at %.2f us after the first start" % ((t[:, 4] - t[:, 0]).mean(), (t[:, 4] - t[:, 0]).max(), t[:, 4].max()))
 order = np.argsort(t[:, 0])
 print("start time by dispatch order (every 128th workgroup):", " ".join(f"{t[order[i], 0]:.2f}" for i in range(0, n, 128)))
+
+# every wave's end of slices: the waves that have a slice at all (w < slices of the item), workgroup by workgroup
+ds = nhp.device_dataset(proc, (times, nodes, T), ctx)
+sc = ds.scalars()
+per_item = (sc["max_item"] + 63) // 64
+B = 512 if per_item >= 12 else 256 if per_item >= 6 else 128 if per_item >= 3 else 64      # launch_slices' choice
+if os.environ.get("NHP_SLICES_CFG"):
+    B = int(os.environ["NHP_SLICES_CFG"].split(",")[0])
+NW = B // 64
+ns = np.diff(ds.array("sl_item0"))[:n]
+wbuf = np.zeros(16 * n, dtype=np.uint64)
+fw = _lib.lib().nhp_debug_stamps_slices_waves
+fw.restype = C.c_int
+assert fw(wbuf.ctypes.data_as(C.POINTER(C.c_uint64)), 16 * n) == 0
+we = (wbuf.reshape(n, 16).astype(np.int64) - st[:, 0].min()) / 100.0
+busy = np.arange(16)[None, :] < np.minimum(ns, NW)[:, None]
+has = busy.any(axis=1)
+first = np.where(busy, we, np.inf).min(axis=1)[has]
+last = np.where(busy, we, -np.inf).max(axis=1)[has]
+spread = last - first
+print(f"{NW} waves per workgroup, {ns.mean():.2f} slices per item")
+print(f"spread between a workgroup's first and last wave to end its slices: mean {spread.mean():6.2f}  p10 {np.percentile(spread, 10):6.2f}  "
+      f"p50 {np.percentile(spread, 50):6.2f}  p90 {np.percentile(spread, 90):6.2f}  max {spread.max():6.2f} us")
+since = we[has] - t[has, 1][:, None]                  # from the column's barrier to the wave's last slice
+mean_w = [float(since[busy[has][:, w], w].mean()) if busy[has][:, w].any() else float("nan") for w in range(NW)]
+print("slices phase by wave (mean us after the column is staged):", " ".join(f"{v:.2f}" for v in mean_w))
+print(f"last wave {(last - t[has, 1]).mean():6.2f} us, mean wave {np.nanmean(np.where(busy[has], since, np.nan), axis=1).mean():6.2f} us after the column is staged")

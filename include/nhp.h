@@ -836,6 +836,35 @@ nhp_status nhp_cont_hessian_vec(nhp_ctx *ctx, const nhp_cont_dataset *ds, const 
 nhp_status nhp_disc_mle_run(nhp_ctx *ctx, const nhp_disc_dataset *data, double dt, double lower, double upper, double f_abstol,
                             int32_t max_steps, double *x, int64_t len, double *loss, int32_t *steps, int32_t *converged, int32_t *evals);
 
+/* Observed and Fisher information of the discrete log-likelihood nhp_disc_loglik evaluates, in mle!'s parameters
+ * x = [λ0 (N); vec(η)], η = W∘θ (csrc/disc_information.hip; DiscreteStandardHawkesProcess with a homogeneous baseline, what
+ * nhp_disc_mle_run fits).  λ[t,c] = dt·x_tᵀ z_c with x_t = [1; Ŝ[t,·,·]] and z_c = [λ0[c]; η[·,c,·]] is linear, so minus the
+ * Hessian is block diagonal by child node c, one D x D block each, D = 1 + N·B:
+ *     kind 0, observed:  J_c = dt²·Σ_t (s[t,c]/λ[t,c]²)·x_t x_tᵀ        kind 1, Fisher:  I_c = dt²·Σ_t (1/λ[t,c])·x_t x_tᵀ
+ * Row and column 0 are λ0[c]; row 1 + b·N + p is η[p,c,b] (vec(η) restricted to column c).  Both kinds are positive
+ * semi-definite.  nhp_disc_convolve must have run on the dataset.
+ *
+ * nhp_disc_information: blocks[k] = the block of column columns[k] (all N columns in order when columns is NULL), D·D
+ * doubles each, column-major, exactly symmetric; a host pointer or a device pointer (the library asks the runtime which).
+ * *ll (nullable, host): the log-likelihood of the same parameters, the value nhp_disc_loglik returns.  tile_rows: rows of
+ * a tile of a block, a multiple of 16 up to 96; slab_bins: bins of a slab of the time axis (rounded up to whole 16-bin
+ * chunks), whose partial blocks are summed in slab order; 0 picks either automatically.  No atomics: the same call gives
+ * the same bits.  The observed kind loads only the 16-bin chunks of a column that hold an event.
+ * nhp_disc_hessian_vec: out = J·v, the INFORMATION (minus the Hessian, positive semi-definite sign) of the given kind
+ * times v; v and out are full-length vectors [N + N·N·B] in mle!'s order, host or device pointers.  Stores no block.
+ *
+ * Both are synchronous and write nothing when they refuse: NHP_ENOTIMPL for an LGCP baseline (lambda0 == NULL with a grid
+ * attached); NHP_EDOMAIN for a column index outside [0, N) or repeated, and dt <= 0; NHP_EINVAL for null pointers, a kind
+ * other than 0 / 1, n_columns <= 0 with columns given, tile_rows not a multiple of 16 in [0, 96], slab_bins < 0;
+ * NHP_ENOMEM, with the byte count, when the blocks or the split-T workspace do not fit in device memory. */
+nhp_status nhp_disc_information(nhp_ctx *ctx, const nhp_disc_dataset *data, const double *lambda0, const double *W,
+                                const double *theta, double dt, int32_t kind /* 0 observed, 1 Fisher */,
+                                const int32_t *columns /* [n_columns], 0-based; NULL: all */, int32_t n_columns,
+                                int32_t tile_rows /* 0: auto */, int32_t slab_bins /* 0: auto */,
+                                double *ll /* nullable */, double *blocks /* [n_columns · D · D], each block column-major */);
+nhp_status nhp_disc_hessian_vec(nhp_ctx *ctx, const nhp_disc_dataset *data, const double *lambda0, const double *W,
+                                const double *theta, double dt, int32_t kind, const double *v /* [P] */, double *out /* [P] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,8 @@ from .discrete import (DiscreteDataset, DiscreteFitTest, DiscreteForecast, Discr
                        DiscreteNetworkHawkesProcess, DiscreteResiduals, DiscreteStandardHawkesProcess, VariationalInference,
                        convolve, disc_parent_counts, disc_forecast, disc_goodness_of_fit, disc_rand, disc_residuals,
                        disc_resample_adjacency_matrix_,
+                       DiscreteInformation, DiscreteStandardErrors, disc_hessian_vector_product, disc_observed_information,
+                       disc_standard_errors,
                        resample_parent_counts, svi_, svi_blocks, update_, vb_)
 from . import discrete as _disc
 from .parents import (Cascades, cascades, map_parents, node_counts, parent_counts, resample_parents,  # noqa: F401

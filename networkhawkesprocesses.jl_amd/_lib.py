@@ -88,6 +88,8 @@ def _declare(lib):
       C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp)
     f("nhp_cont_information", i32, _vp, _vp, _vp, i32, C.POINTER(i32), i32, i32, i32, C.POINTER(C.c_double), _vp)
     f("nhp_cont_hessian_vec", i32, _vp, _vp, _vp, i32, i32, _vp, _vp, i64)
+    f("nhp_disc_information", i32, _vp, _vp, _dp, _dp, _dp, dbl, i32, C.POINTER(i32), i32, i32, i32, C.POINTER(C.c_double), _vp)
+    f("nhp_disc_hessian_vec", i32, _vp, _vp, _dp, _dp, _dp, dbl, i32, _vp, _vp)
     f("nhp_ctx_create", i32, i32, C.POINTER(_vp))
     f("nhp_ctx_destroy", None, _vp)
     f("nhp_last_error", C.c_char_p, _vp)

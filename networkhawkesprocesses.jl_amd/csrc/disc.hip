@@ -1210,6 +1210,44 @@ extern "C" nhp_status nhp_disc_loglik_grad(nhp_ctx *ctx, const nhp_disc_dataset 
     return nhp_ctx_fetch(ctx, 0, 1, ll);
 }
 
+// ---- thin launchers for disc_information.hip (declared in nhp_internal.h): the two GEMM launches it re-drives ----
+// the Poisson log-likelihood of a staged bump table -> ctx->d_results[0]: nhp_disc_loglik's own launch pair, so its bits
+nhp_status nhp_disc_launch_loglik(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *E, const double *base)
+{
+    gemm_args g{};
+    g.A = ds->d_conv; g.lda = (size_t)ds->T; g.B = E; g.ldb = (size_t)ds->N * ds->B;
+    g.M = (int)ds->T; g.N = ds->N; g.K = ds->N * ds->B; g.k_chunk = g.K;
+    g.base = base; g.baseT = nullptr; g.dataT = ds->d_dataT;
+    const int bm = gemm1_tile_m(g.M, g.N, ctx->cu_count);
+    const int blocks = ((g.M + bm - 1) / bm) * ((g.N + BN - 1) / BN);
+    NHP_TRY(nhp_ctx_reserve_partials(ctx, 2 * (size_t)blocks));
+    g.partials = ctx->d_partials;
+    launch_gemm<true, EPI_LOGLIK>(g, 1, ctx->main(), bm);
+    NHP_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_sum_pairs, dim3(1), dim3(256), 0, ctx->main(), ctx->d_partials, blocks, ds->lgamma_sum, ctx->d_results);
+    NHP_HIP(ctx, hipGetLastError());
+    return NHP_OK;
+}
+
+// the T-slabs of the gradient's Gᵀ·R: how many, and their length
+void nhp_disc_gtr_plan(nhp_ctx *ctx, const nhp_disc_dataset *ds, int *splits, int *k_chunk)
+{
+    const disc_grad_plan q = disc_grad_sizes(ctx, ds, true);
+    *splits = q.splits; *k_chunk = q.k_chunk;
+}
+
+// slabs[z][k + c·K] = Σ_{t in slab z} Ŝ[t,k]·R[t,c]   (R is T x N, t fastest; the caller sums the slabs in order)
+nhp_status nhp_disc_launch_gtr(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *dR, int splits, int k_chunk, double *dslab)
+{
+    gemm_args g2{};
+    g2.A = ds->d_conv; g2.lda = (size_t)ds->T; g2.B = dR; g2.ldb = (size_t)ds->T;
+    g2.M = ds->N * ds->B; g2.N = ds->N; g2.K = (int)ds->T; g2.k_chunk = k_chunk;
+    g2.out = dslab;
+    launch_gemm<false, EPI_SLAB>(g2, splits, ctx->main());
+    NHP_HIP(ctx, hipGetLastError());
+    return NHP_OK;
+}
+
 // ---- mle!(process::DiscreteStandardHawkesProcess, data) with the optimizer's state on the device (src/discrete.jl:211-296) ----
 // x = params(process) = [λ0; vec(W .* θ)] (src/discrete.jl:178-182).  params!(process, x) (:195-203) splits the second block
 // into W = Σ_b x[p,c,b] and θ = x ./ W, and the objective's bump is (W·θ)·dt (:381-385): the same three roundings here, from

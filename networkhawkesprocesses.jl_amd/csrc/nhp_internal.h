@@ -371,6 +371,11 @@ nhp_status nhp_disc_stage_bump(nhp_ctx *ctx, const nhp_disc_dataset *ds, const d
                                double **extra_ptr, int cat_order = 0);
 nhp_status nhp_disc_launch_intensity(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *E, const double *base,
                                      bool per_bin_baseline, double *dlam);
+// disc.hip launches re-driven by disc_information.hip: the log-likelihood of a staged bump table (-> ctx->d_results[0], the
+// bits of nhp_disc_loglik), and the gradient's split-T Gᵀ·R (R [T x N], t fastest) into `splits` slabs of N·B x N
+nhp_status nhp_disc_launch_loglik(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *E, const double *base);
+void nhp_disc_gtr_plan(nhp_ctx *ctx, const nhp_disc_dataset *ds, int *splits, int *k_chunk);
+nhp_status nhp_disc_launch_gtr(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *dR, int splits, int k_chunk, double *dslab);
 
 // ---- error plumbing -------------------------------------------------------------------
 void nhp_set_error(nhp_ctx *ctx, const char *fmt, ...);

@@ -4,6 +4,7 @@ src/baselines.jl:358-456 and src/impulses.jl:272-375) on top of libnhp.so.
 `data` is the reference's N x T Int64 count matrix (src/discrete.jl:18,80); `convolved` is the
 T x N x B array of basis-filtered counts, kept on the device inside a DiscreteDataset handle.
 """
+import collections
 import ctypes as C
 import time
 import weakref
@@ -761,6 +762,176 @@ def disc_mle_(process, data, optimizer="L-BFGS-B", verbose=False, f_abstol=1e-6,
     disc_params_(process, res.x)
     return MaximumLikelihood(res.x.copy(), -float(res.fun), state["steps"], time.time() - start,
                              "success" if (state["converged"] or res.success) else "failure")
+
+
+DiscreteInformation = collections.namedtuple("DiscreteInformation", "ll columns blocks names kind")
+DiscreteStandardErrors = collections.namedtuple("DiscreteStandardErrors", "se lower_ci upper_ci free pd se_W se_theta")
+_INFORMATION_KINDS = {"observed": 0, "fisher": 1}
+
+
+def _disc_information_check(process, what):
+    if not isinstance(process, DiscreteStandardHawkesProcess):
+        raise TypeError(f"{what} is defined for DiscreteStandardHawkesProcess, the process mle! fits (src/discrete.jl:211)")
+    if isinstance(process.baseline, DiscreteLogGaussianCoxProcess):
+        raise NotImplementedError(f"{what} takes the homogeneous baseline (the LGCP baseline is not covered)")
+
+
+def _disc_kind(kind):
+    if kind not in _INFORMATION_KINDS:
+        raise ValueError("kind must be 'observed' or 'fisher'")
+    return _INFORMATION_KINDS[kind]
+
+
+def disc_block_index(N, B, c):
+    """Positions in [λ0; vec(η)] of the rows of column c's block: λ0[c], then η[p,c,b] at row 1 + b·N + p."""
+    return np.concatenate([[c], N + (np.arange(B)[:, None] * N * N + np.arange(N)[None, :] + c * N).ravel()])
+
+
+def disc_observed_information(process, data=None, convolved=None, columns=None, kind="observed", device=False, tile_rows=0,
+                              slab_bins=0, ctx=None):
+    """The information of the discrete log-likelihood in mle_'s parameters [λ0; vec(η)], η = W∘θ, at the process's current
+    parameters (nhp_disc_information).
+
+    The intensity is linear in these parameters, so the information is block diagonal by child node: `blocks[k]` is the
+    D x D block, D = 1 + N·B, of column c = columns[k] (all columns in order by default) over [λ0[c]; η[:,c,:]] -- row 0 is
+    λ0[c], row 1 + b·N + p is η[p,c,b]; `names[r]` = ("λ0", None, None) or ("η", p, b).  kind="observed": minus the
+    Hessian, dt²·Σ_t (s/λ²)·x xᵀ; kind="fisher": its expectation under the model, dt²·Σ_t (1/λ)·x xᵀ.  Both are positive
+    semi-definite, exactly symmetric and bit-reproducible.  tile_rows (a multiple of 16 up to 96) and slab_bins force the
+    tiling of a block and of the time axis (0: automatic).  device=False: numpy [n_columns, D, D]; device=True: a float64
+    torch tensor view of the buffer the kernels wrote.  Returns DiscreteInformation(ll, columns, blocks, names, kind)."""
+    from .inference import _check_columns
+    _disc_information_check(process, "disc_observed_information")
+    code = _disc_kind(kind)
+    ctx = ctx or _lib.default_context()
+    ds = _convolved(process, data, convolved, ctx)
+    N, B = ds.N, ds.B
+    cols = _check_columns(columns, N)
+    for name, v in (("tile_rows", tile_rows), ("slab_bins", slab_bins)):
+        if not (isinstance(v, (int, np.integer)) and v >= 0):
+            raise ValueError(f"{name} must be a non-negative integer (0: automatic)")
+    D = 1 + N * B
+    l0, W, th, _ = process._lowered()
+    ll = C.c_double()
+    fn = _lib.lib().nhp_disc_information
+    args = (ctx.h, ds.h, _lib.dptr(l0), _lib.dptr(W), _lib.dptr(th), process.dt, code, cols.ctypes.data_as(C.POINTER(C.c_int32)),
+            len(cols), int(tile_rows), int(slab_bins), C.byref(ll))
+    if device:
+        import torch
+        dev = torch.device("cuda", ctx.device)
+        out = torch.empty((len(cols), D, D), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()          # earlier users of the buffer's memory are done before the library writes
+        _lib.check(fn(*args, out.data_ptr()), ctx.h)
+        blocks = out.transpose(1, 2)                           # column-major blocks (symmetric: the same numbers)
+    else:
+        out = np.empty((len(cols), D, D))
+        _lib.check(fn(*args, out.ctypes.data), ctx.h)
+        blocks = out.transpose(0, 2, 1)
+    names = [("λ0", None, None)] + [("η", p, b) for b in range(B) for p in range(N)]
+    return DiscreteInformation(ll.value, cols.copy(), blocks, names, kind)
+
+
+def disc_hessian_vector_product(process, data=None, convolved=None, v=None, kind="observed", device=False, ctx=None):
+    """J·v for the information J of the given kind (disc_observed_information: MINUS the Hessian of the log-likelihood for
+    kind="observed", positive semi-definite sign), v and the result full-length vectors in mle_'s order [λ0; vec(η)]
+    (nhp_disc_hessian_vec: two intensity launches and the gradient's Gᵀ·R, no block is stored).  device=False: numpy in and
+    out; device=True: float64 torch tensors on the context's device."""
+    _disc_information_check(process, "disc_hessian_vector_product")
+    code = _disc_kind(kind)
+    if v is None:
+        raise ValueError("v is required")
+    ctx = ctx or _lib.default_context()
+    ds = _convolved(process, data, convolved, ctx)
+    P = ds.N + ds.N * ds.N * ds.B
+    if device:
+        import torch
+        if not (isinstance(v, torch.Tensor) and v.dtype == torch.float64 and v.is_cuda and tuple(v.shape) == (P,)):
+            raise ValueError(f"device=True takes a float64 tensor of length {P} on the context's device")
+    else:
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.shape != (P,):
+            raise ValueError("Parameter vector length does not match model parameter length.")
+    l0, W, th, _ = process._lowered()
+    fn = _lib.lib().nhp_disc_hessian_vec
+    args = (ctx.h, ds.h, _lib.dptr(l0), _lib.dptr(W), _lib.dptr(th), process.dt, code)
+    if device:
+        dev = torch.device("cuda", ctx.device)
+        v = v.contiguous()
+        out = torch.empty(P, dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        _lib.check(fn(*args, v.data_ptr(), out.data_ptr()), ctx.h)
+        return out
+    out = np.empty(P)
+    _lib.check(fn(*args, v.ctypes.data, out.ctypes.data), ctx.h)
+    return out
+
+
+def _disc_standard_errors_from_blocks(blocks, cols, x, N, B, lower, upper, level):
+    """disc_standard_errors' host part: free sets, Cholesky inverses of the free sub-blocks, Wald intervals, and the
+    standard errors of W = Σ_b η (exact) and θ = η/W (delta method) from each link's B x B covariance."""
+    from scipy.linalg import solve_triangular
+    from scipy.stats import norm
+    P = len(x)
+    se = np.full(P, np.nan)
+    free = np.zeros(P, dtype=bool)
+    pd = np.zeros(len(cols), dtype=bool)
+    se_W = np.full((N, N), np.nan)
+    se_theta = np.full((N, N, B), np.nan)
+    for k, c in enumerate(cols):
+        idx = disc_block_index(N, B, int(c))
+        J = np.asarray(blocks[k], dtype=np.float64)
+        inside = (x[idx] > lower) & (x[idx] < upper)
+        f = inside & np.any(J != 0.0, axis=1)
+        sub = J[np.ix_(f, f)]
+        ok = bool(f.any() and np.all(np.isfinite(sub)))
+        if ok:
+            try:
+                L = np.linalg.cholesky(sub)
+                Li = solve_triangular(L, np.eye(len(L)), lower=True)
+                cov = Li.T @ Li
+                var = np.diag(cov)
+                ok = bool(np.all(np.isfinite(var)) and np.all(var > 0.0))
+            except np.linalg.LinAlgError:
+                ok = False
+        pd[k] = ok
+        if not ok:
+            continue
+        free[idx[f]] = True
+        se[idx[f]] = np.sqrt(var)
+        pos = np.full(len(idx), -1)
+        pos[f] = np.arange(int(f.sum()))
+        for p in range(N):
+            rows = 1 + np.arange(B) * N + p                        # η[p,c,·] in the block
+            fr = f[rows]
+            if not fr.any():
+                continue
+            S = cov[np.ix_(pos[rows[fr]], pos[rows[fr]])]          # a bound or unidentified η[p,c,b] is held fixed
+            se_W[p, c] = np.sqrt(S.sum())
+            eta = x[idx[rows]]
+            w = eta.sum()
+            G = (np.eye(B) - (eta / w)[:, None]) / w               # ∂θ_b/∂η_b' = (δ_bb' - θ_b)/W
+            Gf = G[:, fr]
+            se_theta[p, c] = np.sqrt(np.maximum(np.einsum("ij,jk,ik->i", Gf, S, Gf), 0.0))
+    z = norm.ppf(0.5 + 0.5 * level)
+    return DiscreteStandardErrors(se, x - z * se, x + z * se, free, pd, se_W, se_theta)
+
+
+def disc_standard_errors(process, data=None, convolved=None, columns=None, kind="observed", lower=1e-6, upper=10.0, level=0.95,
+                         ctx=None):
+    """Standard errors and Wald intervals of a fitted DiscreteStandardHawkesProcess from the inverse information
+    (disc_observed_information; the blocks are Cholesky-inverted on the host).
+
+    se, lower_ci, upper_ci [P] in mle_'s order [λ0; vec(η)], NaN for the parameters that are not free and the columns not
+    asked for; free [P]: the parameters the inverse was taken over -- those strictly inside the box (lower, upper) whose
+    row of the column's block is not identically zero; pd [n_columns]: the free sub-block of column columns[k] is positive
+    definite (a column that is not gets NaNs, no exception).  se_W [N, N]: sqrt(1ᵀ Cov(η[p,c,·]) 1), exact because
+    W = Σ_b η; se_theta [N, N, B]: the delta method for θ = η/W.  There is no `regularize`."""
+    if not 0.0 < level < 1.0:
+        raise ValueError("level must lie in (0, 1)")
+    if not lower < upper:
+        raise ValueError("lower must be below upper")
+    info = disc_observed_information(process, data, convolved, columns=columns, kind=kind, ctx=ctx)
+    N, B = process.ndims(), process.impulses.nbasis()
+    return _disc_standard_errors_from_blocks(info.blocks, info.columns, process.params(), N, B, lower, upper, level)
 
 
 def resample_parent_counts(process, data=None, convolved=None, seed=0, step=0, ctx=None):

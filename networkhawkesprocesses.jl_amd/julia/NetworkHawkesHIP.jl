@@ -868,6 +868,39 @@ function mle!(p::NHP.DiscreteStandardHawkesProcess, data::Matrix{Int64}; optimiz
     run_mle(fg!, guess; optimizer=optimizer, verbose=verbose, f_abstol=f_abstol, max_increase_steps=max_increase_steps)
 end
 
+# --- observed_information(process, data) and hessian_vector_product(process, data, v) for the discrete process: no reference
+# counterpart.  In mle!'s parameters [λ0; vec(W .* θ)] the intensity is linear, so the information is block diagonal by child
+# node: blocks[:, :, k] is the D x D block, D = 1 + N·B, of column columns[k] (1-based here) over [λ0[c]; η[:,c,:]], row 1 the
+# baseline, row 1 + (b-1)·N + p the entry η[p,c,b] (nhp_disc_information; homogeneous baseline).  kind = :observed is minus the
+# Hessian, :fisher its expectation.  hessian_vector_product returns J·v, the INFORMATION times v (positive semi-definite sign).
+function observed_information(p::NHP.DiscreteStandardHawkesProcess, data::Matrix{Int64}; columns=nothing, kind=:observed,
+                              tile_rows=0, slab_bins=0, ctx=context(), convolved=convolve(p, data; ctx=ctx))
+    N = NHP.ndims(p)
+    D = 1 + N * size(p.impulses.θ, 3)
+    cols = columns === nothing ? collect(1:N) : collect(Int, columns)
+    c0 = Vector{Int32}(cols .- 1)
+    l0, W, θ, _ = lowered(p)
+    ll, blocks = Ref{Float64}(0.0), Array{Float64}(undef, D, D, length(cols))
+    check(ccall((:nhp_disc_information, libnhp), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Int32, Ptr{Int32}, Int32, Int32, Int32,
+                 Ref{Float64}, Ptr{Float64}),
+                ctx.h, convolved.h, l0, W, θ, p.dt, Int32(kind === :fisher ? 1 : 0), c0, Int32(length(c0)), Int32(tile_rows),
+                Int32(slab_bins), ll, blocks), ctx.h)
+    (ll=ll[], columns=cols, blocks=blocks, kind=kind)
+end
+
+function hessian_vector_product(p::NHP.DiscreteStandardHawkesProcess, data::Matrix{Int64}, v::AbstractVector; kind=:observed,
+                                ctx=context(), convolved=convolve(p, data; ctx=ctx))
+    x = Vector{Float64}(v)
+    length(x) == length(NHP.params(p)) || error("Parameter vector length does not match model parameter length.")
+    out = similar(x)
+    l0, W, θ, _ = lowered(p)
+    check(ccall((:nhp_disc_hessian_vec, libnhp), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Int32, Ptr{Float64}, Ptr{Float64}),
+                ctx.h, convolved.h, l0, W, θ, p.dt, Int32(kind === :fisher ? 1 : 0), x, out), ctx.h)
+    out
+end
+
 # --- resample!(process, data, convolved): one discrete Gibbs sweep  src/discrete.jl:362-368,416-422 -------------------
 # Parent counts (src/parents.jl:82-134, reduced straight to counts[N, 1+NB]) and the conjugate draws on the device; the
 # network process then sweeps its adjacency matrix (src/discrete.jl:424-480) and redraws ρ (src/networks.jl:70-78).

@@ -716,13 +716,15 @@ nhp_status nhp_cont_loglik_grad_allreduce(nhp_ctx *ctx, nhp_comm *comm, const nh
                                           int32_t flags, double *ll, double *grad, int64_t grad_len);
 /* BASELINE config 5: the per-chain posterior summaries (the running sums of nhp_cont_model_moments_*, still on each
  * rank's device) all-gathered over RCCL: sum_all / sumsq_all [world * len] (rank r at r*len), counts [world],
- * rho_all [world * 3] (ρ, Σρ, Σρ² of nhp_cont_model_get_rho; zeros for a model without a device-side ρ). */
+ * rho_all [world * 3] (ρ, Σρ, Σρ² of nhp_cont_model_get_rho; zeros for a model without a device-side ρ).
+ * NHP_ENOTIMPL for a model with a block network: its K² + K sums are not part of the exchange. */
 nhp_status nhp_gather_moments(nhp_ctx *ctx, nhp_comm *comm, const nhp_cont_model *model, double *sum_all, double *sumsq_all,
                               int64_t len, int64_t *counts, double *rho_all);
 
 /* ---- network model on the device + chain driver  (src/networks.jl:54-78, src/inference.jl:49-70) ---------------
  * BernoulliNetworkModel.ρ kept next to the model on the device so that a network mcmc! step never drains the stream:
- * _set_rho uploads it, _get_rho returns {ρ, Σρ, Σρ²} (the sums follow nhp_cont_model_moments_accumulate / _reset). */
+ * _set_rho uploads it, _get_rho returns {ρ, Σρ, Σρ²} (the sums follow nhp_cont_model_moments_accumulate / _reset).
+ * _set_rho also detaches a block network (nhp_cont_model_set_sbm) the model had: its network is the scalar ρ from then on. */
 nhp_status nhp_cont_model_set_rho(nhp_ctx *ctx, nhp_cont_model *model, double rho);
 nhp_status nhp_cont_model_get_rho(nhp_ctx *ctx, const nhp_cont_model *model, double *out /* [3] */);
 /* resample_adjacency_matrix!(process, data) with the device-resident ρ (src/continuous.jl:444-487), then
@@ -748,6 +750,46 @@ nhp_status nhp_cont_network_rho(nhp_ctx *ctx, nhp_cont_model *model, double alph
 nhp_status nhp_cont_mcmc_run(nhp_ctx *ctx, nhp_comm *comm /* nullable */, const nhp_cont_dataset *ds, nhp_cont_model *model,
                              const nhp_gibbs_priors *priors, double net_alpha, double net_beta, uint64_t seed,
                              uint64_t step0, int64_t n_steps, int64_t burn);
+
+/* ---- StochasticBlockNetworkModel (csrc/sbm.hip; the reference's src/networks.jl ends in its empty stub) --------------
+ * K blocks, N nodes: z_n ~ Categorical(π), π ~ Dirichlet(γ·1_K), ρ[k,l] ~ Beta(α, β), A[p,c] ~ Bernoulli(ρ[z_p, z_c]) for all
+ * N² entries.  Labels are 0-based int32; ρ is K x K column-major (ρ[k,l] at k + K·l); A is N x N column-major.
+ * resample!(network, A) = block counts, ρ | counts, π | sizes, then one collapsed-Gibbs sweep over the labels.
+ * Errors: NHP_EINVAL for K outside 1..64, NHP_EDOMAIN for a label outside 0..K-1, a ρ entry outside (0, 1), π not positive or
+ * not summing to 1 within 1e-12, a non-positive prior parameter; NHP_ENOTIMPL where the label sweep's tables do not fit the
+ * LDS (8·N·K + 16·K·(K|1) + N/2 + N + 16 bytes <= 160 KiB and N <= 8192).
+ *
+ * Stand-alone entries on a host A (synchronous). */
+/* L[k,l] = Σ A[p,c]·[z_p = k][z_c = l] (diagonal included) -> links [K*K]; block sizes -> sizes [K].  Exact integers. */
+nhp_status nhp_sbm_block_counts(nhp_ctx *ctx, const double *A, int32_t n_nodes, int32_t n_blocks, const int32_t *z, int64_t *links,
+                                int64_t *sizes);
+/* ρ[k,l] ~ Beta(alpha + L, beta + n_k·n_l - L) as X/(X+Y) from two Philox-keyed Gammas (a pair with an empty block draws
+ * from the prior), π ~ Dirichlet(gamma + n) as normalised Gammas, keyed (seed, step): csrc/nhp_rng.h. */
+nhp_status nhp_sbm_draw(nhp_ctx *ctx, int32_t n_blocks, const int64_t *links, const int64_t *sizes, double alpha, double beta,
+                        double gamma, uint64_t seed, uint64_t step, double *rho_out /* [K*K] */, double *pi_out /* [K] */);
+/* n_sweeps label sweeps over n = 0..N-1 in order.  Step i = n + N·sweep draws z_n from
+ *   p_k ∝ π_k · Π_l ρ[k,l]^out_l (1-ρ[k,l])^(cnt_l - out_l) · ρ[l,k]^in_l (1-ρ[l,k])^(cnt_l - in_l) · (A[n,n] ? ρ[k,k] : 1-ρ[k,k])
+ * (out_l, in_l, cnt_l over the other nodes at their current labels) as the first k with u_i <= p_0 + ... + p_k.
+ * u [n_sweeps*N] (nullable: the sweep's own Philox stream keyed (seed, step)); u_used (nullable) returns the uniforms,
+ * probs (nullable) [n_sweeps*N*K] the conditional of step i at i·K.  Bit-reproducible for a fixed uniform stream. */
+nhp_status nhp_sbm_resample_blocks(nhp_ctx *ctx, const double *A, int32_t n_nodes, int32_t n_blocks, int32_t *z_inout, const double *rho,
+                                   const double *pi, const double *u, uint64_t seed, uint64_t step, int32_t n_sweeps, double *u_used,
+                                   double *probs);
+/* The model's state kept next to the continuous model on the device, as ρ of the Bernoulli model is.  _set_sbm uploads
+ * (z, ρ, π) and the priors; _get_sbm returns them (every output nullable) with the running sums of the kept steps
+ * (nhp_cont_model_moments_accumulate / _reset carry them; nhp_cont_model_set_rho detaches the block network again): sums = [Σρ (K²); Σρ² (K²); Σπ (K); Σπ² (K)] and block_counts
+ * [N*K], the kept steps node n spent in block k at n + N·k. */
+nhp_status nhp_cont_model_set_sbm(nhp_ctx *ctx, nhp_cont_model *model, int32_t n_blocks, const int32_t *z, const double *rho,
+                                  const double *pi, double alpha, double beta, double gamma);
+nhp_status nhp_cont_model_get_sbm(nhp_ctx *ctx, const nhp_cont_model *model, int32_t *z, double *rho, double *pi, double *sums,
+                                  int64_t *block_counts);
+/* The label sweep runs at the chain steps that are multiples of `every` (default 1: every step); ρ and π are drawn at every step. */
+nhp_status nhp_cont_model_set_sbm_labels_every(nhp_ctx *ctx, nhp_cont_model *model, int32_t every);
+/* One network step of mcmc! under the block model: the link-probability matrix ρ[z_p, z_c] from the current state, the
+ * adjacency sweep (the Philox key of nhp_cont_network_step), then resample!(network, A).  Asynchronous; nothing crosses
+ * PCIe.  NHP_ENOTIMPL on a column shard (the labels need every column).  nhp_cont_mcmc_run takes this step for a model
+ * with a block network attached and ignores net_alpha / net_beta. */
+nhp_status nhp_cont_sbm_step(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *model, uint64_t seed, uint64_t step);
 
 /* mle!(process, data; f_abstol, guess) (src/continuous.jl:144-198) with the optimizer's state on the device: minimises
  * -loglikelihood(process, data) over params(process) = [λ0 | grid intensities; θ | μ, τ; W] on the reference's box

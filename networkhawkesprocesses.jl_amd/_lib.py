@@ -78,6 +78,13 @@ def _declare(lib):
     f("nhp_cont_network_step", i32, _vp, _vp, _vp, _vp, dbl, dbl, u64, u64)
     f("nhp_cont_network_sweep", i32, _vp, _vp, _vp, u64, u64, _dp)
     f("nhp_cont_network_rho", i32, _vp, _vp, dbl, dbl, dbl, dbl, u64, u64)
+    f("nhp_sbm_block_counts", i32, _vp, _dp, i32, i32, _vp, _vp, _vp)
+    f("nhp_sbm_draw", i32, _vp, i32, _vp, _vp, dbl, dbl, dbl, u64, u64, _dp, _dp)
+    f("nhp_sbm_resample_blocks", i32, _vp, _dp, i32, i32, _vp, _dp, _dp, _dp, u64, u64, i32, _dp, _dp)
+    f("nhp_cont_model_set_sbm", i32, _vp, _vp, i32, _vp, _dp, _dp, dbl, dbl, dbl)
+    f("nhp_cont_model_get_sbm", i32, _vp, _vp, _vp, _dp, _dp, _dp, _vp)
+    f("nhp_cont_model_set_sbm_labels_every", i32, _vp, _vp, i32)
+    f("nhp_cont_sbm_step", i32, _vp, _vp, _vp, u64, u64)
     f("nhp_cont_mcmc_run", i32, _vp, _vp, _vp, _vp, C.POINTER(GibbsPriors), dbl, dbl, u64, u64, i64, i64)
     f("nhp_disc_mle_run", i32, _vp, _vp, dbl, dbl, dbl, dbl, i32, _dp, i64, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
       C.POINTER(C.c_int32))

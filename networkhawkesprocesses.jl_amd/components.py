@@ -15,6 +15,7 @@ import collections
 
 import numpy as np
 
+from . import _lib
 from ._lib import DomainError
 
 
@@ -425,6 +426,81 @@ class BernoulliNetworkModel(Network):
     def resample_links_(self, nlinks, size, rng):
         self.ρ = rng.beta(self.α + nlinks, self.β + size - nlinks)
         return self.ρ
+
+
+class StochasticBlockNetworkModel(Network):
+    """StochasticBlockNetworkModel(nnodes, nblocks, ρ, π, z; α, β, γ) -- the reference names the model and leaves it an
+    empty stub (src/networks.jl, last lines).  Nodes belong to latent blocks and a link p → c exists with the
+    probability of its pair of blocks:
+
+        z_n ~ Categorical(π),  π ~ Dirichlet(γ·1_K),  ρ[k,l] ~ Beta(α, β),  A[p,c] ~ Bernoulli(ρ[z_p, z_c])
+
+    for all N² entries (the diagonal is counted, as BernoulliNetworkModel counts it).  Labels are 0-based.  With one
+    block this is BernoulliNetworkModel.  params() is [vec(ρ) column-major; π]; the labels are latent state, not
+    parameters.  Block labels are identified only up to a permutation, so a chain can switch them: summaries of ρ, π
+    and the labels over a chain are meaningful only as long as it did not."""
+
+    def __init__(self, nnodes, nblocks, ρ=None, π=None, z=None, α=1.0, β=1.0, γ=1.0):
+        self.nnodes, self.nblocks = int(nnodes), int(nblocks)
+        K = self.nblocks
+        if K < 1 or K > 64:
+            raise ValueError("nblocks must lie in 1..64")
+        self.α, self.β, self.γ = float(α), float(β), float(γ)
+        if not (self.α > 0 and self.β > 0 and self.γ > 0):
+            raise _lib.DomainError("the priors need α, β, γ > 0")
+        self.ρ = np.full((K, K), 0.5) if ρ is None else np.array(ρ, dtype=np.float64).reshape((K, K))
+        self.π = np.full(K, 1.0 / K) if π is None else np.array(π, dtype=np.float64).reshape(K)
+        self.z = (np.arange(self.nnodes) % K).astype(np.int32) if z is None else np.array(z, dtype=np.int32).reshape(self.nnodes)
+        if np.any(self.z < 0) or np.any(self.z >= K):
+            raise _lib.DomainError(f"labels must lie in 0..{K - 1}")
+        if not np.all((self.ρ > 0) & (self.ρ < 1)):
+            raise _lib.DomainError("ρ must lie in the open interval (0, 1)")
+        if not (np.all(self.π > 0) and abs(self.π.sum() - 1.0) <= 1e-12):
+            raise _lib.DomainError("π must be positive and sum to 1")
+
+    def params(self):
+        return np.concatenate([self.ρ.ravel(order="F"), self.π])
+
+    def link_probability(self):
+        return self.ρ[np.ix_(self.z, self.z)]
+
+    def rand(self, rng):
+        """Labels from π, then A from ρ[z_p, z_c]."""
+        self.z = rng.choice(self.nblocks, size=self.nnodes, p=self.π).astype(np.int32)
+        return (rng.uniform(size=(self.nnodes, self.nnodes)) < self.link_probability()).astype(np.float64)
+
+    def block_counts(self, A, ctx=None):
+        """(L, n): L[k,l] = Σ A[p,c]·[z_p = k][z_c = l] and the block sizes, from the GPU (exact integers)."""
+        ctx = ctx or _lib.default_context()
+        K, N = self.nblocks, self.nnodes
+        Af = _lib.colmajor(A)
+        z = np.ascontiguousarray(self.z, dtype=np.int32)
+        L, n = np.empty(K * K, dtype=np.int64), np.empty(K, dtype=np.int64)
+        _lib.check(_lib.lib().nhp_sbm_block_counts(ctx.h, _lib.dptr(Af), N, K, z.ctypes.data, L.ctypes.data, n.ctypes.data), ctx.h)
+        return L.reshape((K, K), order="F"), n
+
+    def resample_(self, A, rng, seed=None, step=0, ctx=None, labels=True):
+        """resample!(network, A): block counts, ρ[k,l] ~ Beta(α + L, β + n_k n_l - L), π ~ Dirichlet(γ + n), then one
+        collapsed-Gibbs sweep over the labels (node after node, each given the current labels of all others) -- all
+        on the GPU (csrc/sbm.hip), keyed (seed, step).  Without a seed one is drawn from `rng`."""
+        ctx = ctx or _lib.default_context()
+        if seed is None:
+            seed = int(rng.integers(0, 2 ** 63))
+        K, N = self.nblocks, self.nnodes
+        lib = _lib.lib()
+        Af = _lib.colmajor(A)
+        L, n = self.block_counts(A, ctx)
+        Lf = np.ascontiguousarray(L.ravel(order="F"))
+        rho, pi = np.empty(K * K), np.empty(K)
+        _lib.check(lib.nhp_sbm_draw(ctx.h, K, Lf.ctypes.data, n.ctypes.data, self.α, self.β, self.γ, seed, step, _lib.dptr(rho),
+                                    _lib.dptr(pi)), ctx.h)
+        self.ρ, self.π = rho.reshape((K, K), order="F"), pi
+        if labels:
+            z = np.ascontiguousarray(self.z, dtype=np.int32).copy()
+            _lib.check(lib.nhp_sbm_resample_blocks(ctx.h, _lib.dptr(Af), N, K, z.ctypes.data, _lib.dptr(rho), _lib.dptr(pi), None, seed,
+                                                   step, 1, None, None), ctx.h)
+            self.z = z
+        return self.params()
 
 
 # ------------------------------------------------------------------------------ parameter vector

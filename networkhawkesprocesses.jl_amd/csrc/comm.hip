@@ -215,6 +215,10 @@ extern "C" nhp_status nhp_gather_moments(nhp_ctx *ctx, nhp_comm *comm, const nhp
     if (!m || !sum_all || !sumsq_all || !counts) return NHP_EINVAL;
     if (m->ctx != ctx) { nhp_set_error(ctx, "model belongs to another ctx"); return NHP_EINVAL; }
     if (!m->d_mom) { nhp_set_error(ctx, "moments: nothing accumulated"); return NHP_EINVAL; }
+    if (m->sbm) {
+        nhp_set_error(ctx, "gather_moments: the sums of a block network's rho and pi are not gathered (nhp_cont_model_get_sbm per chain)");
+        return NHP_ENOTIMPL;
+    }
     if (len != m->mom_len) { nhp_set_error(ctx, "Parameter vector length does not match model parameter length."); return NHP_ESHAPE; }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t w = (size_t)comm->world, L = (size_t)len;

@@ -529,13 +529,14 @@ __global__ __launch_bounds__(64) void k_adj_sweep(nhp_cont_args a, double *__res
 }
 
 // One sweep of A, enqueued on the ctx stream; the per-column link counts are left at *d_links_out [N] in the scratch.
-// Link probabilities: rho_matrix (host, N*N) | d_rho_scalar (device scalar) | rho.
+// Link probabilities: rho_matrix (host, N*N) | d_rho_matrix (device, N*N) | d_rho_scalar (device scalar) | rho.
 nhp_status nhp_adj_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *m, const double *rho_matrix, double rho,
-                           const double *d_rho_scalar, const double *u, uint64_t seed, uint64_t step, double **d_links_out)
+                           const double *d_rho_scalar, const double *u, uint64_t seed, uint64_t step, double **d_links_out,
+                           const double *d_rho_matrix)
 {
     NHP_TRY(nhp_check_pair(ctx, ds, m));
     if (!m->has_A) { nhp_set_error(ctx, "resample_adjacency: the model has no adjacency matrix"); return NHP_EINVAL; }
-    if (!rho_matrix && !d_rho_scalar && !(rho >= 0.0 && rho <= 1.0)) { nhp_set_error(ctx, "link probability must lie in [0, 1]"); return NHP_EDOMAIN; }
+    if (!rho_matrix && !d_rho_matrix && !d_rho_scalar && !(rho >= 0.0 && rho <= 1.0)) { nhp_set_error(ctx, "link probability must lie in [0, 1]"); return NHP_EDOMAIN; }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t N = (size_t)ds->N, NN = N * N, P = (size_t)(ds->pairs > 0 ? ds->pairs : 1);
     int max_children = 1;
@@ -579,7 +580,7 @@ nhp_status nhp_adj_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_mo
     if (u) NHP_HIP(ctx, hipMemcpyAsync(base + o_u, u, 8 * NN, hipMemcpyHostToDevice, st));
     if (rho_matrix) NHP_HIP(ctx, hipMemcpyAsync(base + o_rho, rho_matrix, 8 * NN, hipMemcpyHostToDevice, st));
     const double *d_u = u ? (const double *)(base + o_u) : nullptr;
-    const double *d_rho = rho_matrix ? (const double *)(base + o_rho) : nullptr;
+    const double *d_rho = rho_matrix ? (const double *)(base + o_rho) : d_rho_matrix;
     double *d_links = (double *)(base + o_links);
     if (ncol != (unsigned)N) NHP_HIP(ctx, hipMemsetAsync(d_links, 0, 8 * N, st));        // links of the columns this shard does not own
     const int64_t *d_off = ds->d_adj_off;
@@ -673,6 +674,7 @@ extern "C" nhp_status nhp_cont_model_set_rho(nhp_ctx *ctx, nhp_cont_model *m, do
     if (m->ctx != ctx) { nhp_set_error(ctx, "model belongs to another ctx"); return NHP_EINVAL; }
     if (!(rho >= 0.0 && rho <= 1.0)) { nhp_set_error(ctx, "link probability must lie in [0, 1]"); return NHP_EDOMAIN; }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
+    NHP_TRY(nhp_sbm_detach(ctx, m));                          // a scalar link probability replaces a block network the model had
     NHP_TRY(ensure_rho(ctx, m));
     NHP_HIP(ctx, hipMemcpyAsync(m->d_rho, &rho, sizeof(double), hipMemcpyHostToDevice, ctx->main()));
     NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));          // `rho` is a stack value
@@ -744,11 +746,12 @@ extern "C" nhp_status nhp_cont_mcmc_run(nhp_ctx *ctx, nhp_comm *comm, const nhp_
 {
     if (!ctx || !m || !pr || n_steps < 0) return NHP_EINVAL;
     NHP_TRY(nhp_check_pair(ctx, ds, m));
-    if (m->has_A && !m->d_rho) { nhp_set_error(ctx, "mcmc_run: set the network's link probability first (nhp_cont_model_set_rho)"); return NHP_EINVAL; }
+    if (m->has_A && !m->sbm && !m->d_rho) { nhp_set_error(ctx, "mcmc_run: set the network's link probability first (nhp_cont_model_set_rho)"); return NHP_EINVAL; }
     for (int64_t k = 0; k < n_steps; ++k) {
         const uint64_t step = step0 + (uint64_t)k;
         NHP_TRY(nhp_cont_gibbs_step(ctx, ds, m, pr, seed, step));           // (reports a sampler error one sweep late)
-        if (m->has_A) NHP_TRY(nhp_cont_network_step(ctx, comm, ds, m, net_alpha, net_beta, seed, step));
+        if (m->has_A && m->sbm) NHP_TRY(nhp_cont_sbm_step(ctx, ds, m, seed, step));      // (net_alpha, net_beta: the model has its own priors)
+        else if (m->has_A) NHP_TRY(nhp_cont_network_step(ctx, comm, ds, m, net_alpha, net_beta, seed, step));
         if (burn >= 0 && (int64_t)step >= burn) NHP_TRY(nhp_cont_model_moments_accumulate(ctx, m));
     }
     return nhp_ctx_synchronize(ctx);

@@ -262,7 +262,15 @@ struct nhp_cont_model {
     // BernoulliNetworkModel.ρ on the device (nhp_cont_model_set_rho / nhp_cont_network_step): {ρ, Σρ, Σρ², ΣA of the
     // latest sweep}; the sums follow the moments above
     double *d_rho = nullptr;
+    // StochasticBlockNetworkModel on the device (sbm.hip: nhp_cont_model_set_sbm / nhp_cont_sbm_step): labels, ρ[K x K], π,
+    // the link-probability matrix the adjacency sweep reads and the running sums of the kept steps; null: no block network
+    struct nhp_sbm_state *sbm = nullptr;
 };
+// sbm.hip: release the block network's state; its share of nhp_cont_model_moments_reset / _accumulate (asynchronous)
+void nhp_sbm_free(nhp_cont_model *m);
+nhp_status nhp_sbm_detach(nhp_ctx *ctx, nhp_cont_model *m);      // set_rho: the model's network is no block model (any more)
+nhp_status nhp_sbm_moments_reset(nhp_ctx *ctx, nhp_cont_model *m);
+nhp_status nhp_sbm_moments_accumulate(nhp_ctx *ctx, nhp_cont_model *m);
 
 // RCCL communicator of one rank (comm.hip); librccl.so.1 is dlopen'ed on first use
 struct nhp_comm {
@@ -280,9 +288,11 @@ nhp_status nhp_grad_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_
 // comm.hip: the same, with the shards' [ll; grad] summed over the ranks on the device when `comm` is given (nullable)
 nhp_status nhp_grad_enqueue_reduced(nhp_ctx *ctx, nhp_comm *comm, const nhp_cont_dataset *ds, const nhp_cont_model *m, int32_t flags,
                                     int64_t grad_len, double **d_grad);
-// cont_adjacency.hip: enqueue one sweep of A; per-column link counts land at *d_links [N] (scratch)
+// cont_adjacency.hip: enqueue one sweep of A; per-column link counts land at *d_links [N] (scratch).  d_rho_matrix
+// (nullable): the N x N link probabilities already on the device (outside the context's scratch), used when rho_matrix is null
 nhp_status nhp_adj_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *m, const double *rho_matrix, double rho,
-                           const double *d_rho_scalar, const double *u, uint64_t seed, uint64_t step, double **d_links);
+                           const double *d_rho_scalar, const double *u, uint64_t seed, uint64_t step, double **d_links,
+                           const double *d_rho_matrix = nullptr);
 
 
 // Kernel-side view of model + data (passed by value).

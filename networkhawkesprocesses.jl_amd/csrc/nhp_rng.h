@@ -41,6 +41,17 @@ __device__ __forceinline__ double rng_cos_turn(uint32_t c)
 // `fam` at chain step `step` consumes Philox counters (e, attempt) under key (seed ^ fam-constant,
 // step), so a chain is reproducible on the device and independent of launch geometry.  Julia's
 // samplers cannot be matched bit for bit ([3P] Distributions / Random); parity is distributional.
+//
+// The block network model (sbm.hip) adds three families, all under (seed ^ constant, step):
+//   NHP_KEY_SBM_RHO    ρ[k,l] = X/(X+Y): elements 2i and 2i+1 of dev_gamma, i = k + K·l
+//   NHP_KEY_SBM_PI     π = g/Σg: element k of dev_gamma
+//   NHP_KEY_SBM_LABEL  the label sweep's own uniforms: nhp_philox_uniform(seed ^ constant, step, n + N·sweep) for node n
+// The parent sampler draws nhp_philox_uniform(seed, step, event) and the adjacency sweeps
+// nhp_philox_uniform(seed ^ 0xBE5466CF34E90C6C | 0xAD7AC3117D15C0DE, step, entry): the label stream shares their
+// counters but not their key, so no two of the streams coincide.
+#define NHP_KEY_SBM_RHO 0xC0AC29B7C97C50DDull
+#define NHP_KEY_SBM_PI 0x2FFD72DBD01ADFB7ull
+#define NHP_KEY_SBM_LABEL 0xD1310BA698DFB5ACull
 __device__ __forceinline__ void philox_2u(uint64_t key, uint64_t step, uint64_t e, uint32_t attempt, double *ua, double *ub)
 {
     uint32_t c0 = (uint32_t)e, c1 = (uint32_t)(e >> 32) ^ (attempt << 8), c2 = (uint32_t)step, c3 = (uint32_t)(step >> 32);

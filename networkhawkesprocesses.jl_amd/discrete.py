@@ -979,6 +979,15 @@ def disc_resample_adjacency_matrix_(process, data=None, convolved=None, u=None, 
     return nl.value
 
 
+def _resample_network(process, links, N, rng, seed, step, ctx):
+    """resample!(network, A) after the adjacency sweep: the block model needs the swept matrix, the others its link count."""
+    from .components import StochasticBlockNetworkModel
+    if isinstance(process.network, StochasticBlockNetworkModel):
+        process.network.resample_(process.adjacency_matrix, rng, seed=seed, step=step, ctx=ctx)
+    else:
+        process.network.resample_links_(links, N * N, rng)
+
+
 def disc_resample_(process, data, convolved, rng, seed=0, step=0, ctx=None, device_draws=True):
     """resample!(process::DiscreteStandardHawkesProcess, data, convolved) -- src/discrete.jl:362-368, and the
     network twin :416-424 (adds the adjacency sweep and the network's ρ).
@@ -1002,7 +1011,7 @@ def disc_resample_(process, data, convolved, rng, seed=0, step=0, ctx=None, devi
         b.λ, w.W, imp.θ = l0, W.reshape((N, N), order="F"), th.reshape((N, N, B), order="F")
         if isinstance(process, DiscreteNetworkHawkesProcess):
             links = disc_resample_adjacency_matrix_(process, convolved=ds, seed=seed, step=step, ctx=ctx)
-            process.network.resample_links_(links, N * N, rng)
+            _resample_network(process, links, N, rng, seed, step, ctx)
         return process.params()
     counts = resample_parent_counts(process, convolved=ds, seed=seed, step=step, ctx=ctx)
     if isinstance(b, DiscreteLogGaussianCoxProcess):
@@ -1016,7 +1025,7 @@ def disc_resample_(process, data, convolved, rng, seed=0, step=0, ctx=None, devi
     imp.θ = g / g.sum(axis=2, keepdims=True)                                                         # Dirichlet: src/impulses.jl:337-353
     if isinstance(process, DiscreteNetworkHawkesProcess):
         links = disc_resample_adjacency_matrix_(process, convolved=ds, seed=seed, step=step, ctx=ctx)
-        process.network.resample_links_(links, N * N, rng)
+        _resample_network(process, links, N, rng, seed, step, ctx)
     return process.params()
 
 

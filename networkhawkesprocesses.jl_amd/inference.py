@@ -502,7 +502,7 @@ def resample_adjacency_matrix_(process, data, u=None, seed=0, step=0, model=None
     return nl.value
 
 
-def resample_(process, data, rng, step=0, seed=0, ctx=None):
+def resample_(process, data, rng, step=0, seed=0, ctx=None, labels_every=1):
     """resample!(process, data) -- src/continuous.jl:202-208,350-358: one Gibbs sweep.
 
     Parents and every sufficient statistic come from one GPU call; the conjugate draws are host
@@ -520,7 +520,11 @@ def resample_(process, data, rng, step=0, seed=0, ctx=None):
         process.impulses.resample_(st["Mnm"], st["Xnm"], st["Vnm"], rng)
     if isinstance(process, ContinuousNetworkHawkesProcess):
         resample_adjacency_matrix_(process, data, seed=seed, step=step, ctx=ctx)
-        process.network.resample_(process.adjacency_matrix, rng)
+        from .components import StochasticBlockNetworkModel
+        if isinstance(process.network, StochasticBlockNetworkModel):      # on the GPU, keyed like the device-resident step
+            process.network.resample_(process.adjacency_matrix, rng, seed=seed, step=step, ctx=ctx, labels=step % labels_every == 0)
+        else:
+            process.network.resample_(process.adjacency_matrix, rng)
     return process.params()
 
 
@@ -600,7 +604,7 @@ def _merge_shards(process, shard, network):
 
 
 def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_samples=True, device_draws=True,
-          ctx=None, moments=False, burn=0):
+          ctx=None, moments=False, burn=0, labels_every=1):
     """mcmc!(process, data; nsteps, log_freq, verbose) -- src/inference.jl:49-70.
 
     With `device_draws` (default) a whole sweep -- parents, statistics, conjugate draws -- stays on
@@ -614,6 +618,16 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
     summaries chains.py gathers -- with no per-step transfer; combine with keep_samples=False for long chains at large N
     (a sample is 4N²+N doubles, 33.5 MB at N = 1024).
 
+    A StochasticBlockNetworkModel is resampled on the GPU on every route (csrc/sbm.hip): with the device-side draws its
+    labels, ρ and π stay next to the model and a network step never leaves the device; with device_draws=False (or an
+    LGCP baseline) A comes back every step and the network's resample_ runs through the stand-alone entries.  The label
+    sweep is a chain of N dependent steps and is the longest part of such a step: `labels_every=k`
+    resamples the labels at the steps that are multiples of k only (ρ and π every step).  With `moments=True` the
+    K² + K network entries of res.mean / res.m2 are those of [vec(ρ); π] and `res.block_counts` [N x K] counts the
+    kept steps each node spent in each block.  Block labels are identified only up to a permutation: a chain can
+    switch them, and then these averages mix the blocks.  A ShardedDataset raises NotImplementedError (the labels'
+    conditional needs every column of A).
+
     ONE chain over several GPUs: pass a `sharded.ShardedDataset` (device draws, keep_samples=False).  A sweep is
     separable by child-node column -- the parents of the children on c, column c's statistics and conjugate draws and
     the sweep of A[:, c] touch column c only, and every random stream is keyed by global event / entry indices -- so
@@ -621,8 +635,13 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
     is the scalar link count the network's ρ update needs, and at the end the ranks' columns (and moments) are merged."""
     import ctypes as C
     from .sharded import ShardedDataset, _all_reduce_sum
-    from .components import BernoulliNetworkModel, DenseNetworkModel
+    from .components import BernoulliNetworkModel, DenseNetworkModel, StochasticBlockNetworkModel
     shard = data if isinstance(data, ShardedDataset) else None
+    sbm = isinstance(getattr(process, "network", None), StochasticBlockNetworkModel)
+    if sbm and shard is not None:
+        raise NotImplementedError("a StochasticBlockNetworkModel chain is not sharded: the block labels need every column of A")
+    if int(labels_every) < 1:
+        raise ValueError("labels_every must be a positive integer")
     if not isinstance(process.baseline, HomogeneousProcess):
         device_draws = False      # nhp_cont_gibbs_step draws the homogeneous λ0; the LGCP curve is a host slice loop
     if moments and not device_draws:
@@ -642,8 +661,13 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
     # drawn there (src/networks.jl:70-78), so a network step needs no synchronisation; DenseNetworkModel keeps ρ = 1
     net = process.network if network else None
     net_a, net_b = (net.α, net.β) if isinstance(net, BernoulliNetworkModel) else (0.0, 0.0)
-    device_net = device_draws and isinstance(net, (BernoulliNetworkModel, DenseNetworkModel))
-    if device_net:
+    device_net = device_draws and isinstance(net, (BernoulliNetworkModel, DenseNetworkModel, StochasticBlockNetworkModel))
+    if device_net and sbm:
+        z = np.ascontiguousarray(net.z, dtype=np.int32)
+        _lib.check(lib.nhp_cont_model_set_sbm(ctx.h, model.h, net.nblocks, z.ctypes.data, _lib.dptr(_lib.colmajor(net.ρ)),
+                                              _lib.dptr(_lib.f64(net.π)), net.α, net.β, net.γ), ctx.h)
+        _lib.check(lib.nhp_cont_model_set_sbm_labels_every(ctx.h, model.h, int(labels_every)), ctx.h)
+    elif device_net:
         _lib.check(lib.nhp_cont_model_set_rho(ctx.h, model.h, net.ρ if isinstance(net, BernoulliNetworkModel) else 1.0), ctx.h)
     comm = _lib.comm_for(ctx) if shard is not None else None
     host_exchange = shard is not None and shard.world > 1 and comm is None        # gloo rehearsal: link counts through the host
@@ -651,6 +675,16 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
         _lib.check(lib.nhp_cont_model_moments_reset(ctx.h, model.h), ctx.h)
 
     def pull_rho():
+        if device_net and sbm:             # (z, ρ, π) into the component; the running sums of [vec(ρ); π] and their squares
+            K, N = net.nblocks, net.nnodes
+            z, rho, pi = np.empty(N, dtype=np.int32), np.empty(K * K), np.empty(K)
+            sums, bc = np.empty(2 * K * K + 2 * K), np.empty(N * K, dtype=np.int64)
+            _lib.check(lib.nhp_cont_model_get_sbm(ctx.h, model.h, z.ctypes.data, _lib.dptr(rho), _lib.dptr(pi), _lib.dptr(sums),
+                                                  bc.ctypes.data), ctx.h)
+            net.z, net.ρ, net.π = z, rho.reshape((K, K), order="F"), pi
+            res.block_counts = bc.reshape((N, K), order="F")
+            KK = K * K
+            return [None, np.concatenate([sums[:KK], sums[2 * KK:2 * KK + K]]), np.concatenate([sums[KK:2 * KK], sums[2 * KK + K:]])]
         if device_net and isinstance(net, BernoulliNetworkModel):
             r3 = np.empty(3)
             _lib.check(lib.nhp_cont_model_get_rho(ctx.h, model.h, _lib.dptr(r3)), ctx.h)
@@ -684,7 +718,9 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
         if device_draws:
             _lib.check(lib.nhp_cont_gibbs_step(ctx.h, ds.h, model.h, C.byref(pri), seed, res.steps), ctx.h)
             last = keep_samples or res.steps == nsteps - 1
-            if network and device_net and not host_exchange:
+            if network and device_net and sbm:
+                _lib.check(lib.nhp_cont_sbm_step(ctx.h, ds.h, model.h, seed, res.steps), ctx.h)
+            elif network and device_net and not host_exchange:
                 _lib.check(lib.nhp_cont_network_step(ctx.h, comm.h if comm is not None else None, ds.h, model.h, net_a, net_b,
                                                      seed, res.steps), ctx.h)
             elif network and device_net:                     # ranks without an RCCL clique: the one exchange of a step, by hand
@@ -704,7 +740,7 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
                     pull_rho()
             x = process.params() if keep_samples else None
         else:
-            x = resample_(process, ds, rng, step=res.steps, seed=seed, ctx=ctx)
+            x = resample_(process, ds, rng, step=res.steps, seed=seed, ctx=ctx, labels_every=int(labels_every))
         if keep_samples:
             res.samples.append(x)
         res.steps += 1

@@ -654,6 +654,67 @@ function mcmc!(p::NHP.ContinuousHawkesProcess, data; nsteps=1000, log_freq=100, 
     return moments ? (res, mom) : res
 end
 
+# --- StochasticBlockNetworkModel: the reference names it and leaves an empty stub (src/networks.jl, last lines) -------------
+# z_n ~ Categorical(π), π ~ Dirichlet(γ), ρ[k,l] ~ Beta(α, β), A[p,c] ~ Bernoulli(ρ[z_p, z_c]); labels are 1-based here and
+# 0-based in the library.  resample!(net, A) runs on the GPU through the stand-alone entries (csrc/sbm.hip); set_sbm! /
+# get_sbm! / sbm_step! keep the state next to a device model `m` (with_model), where nhp_cont_mcmc_run takes the block-model
+# network step by itself.  Block labels are identified only up to a permutation: a chain can switch them.
+mutable struct StochasticBlockNetworkModel
+    nnodes::Int; nblocks::Int
+    ρ::Matrix{Float64}; π::Vector{Float64}; z::Vector{Int}
+    α::Float64; β::Float64; γ::Float64
+end
+StochasticBlockNetworkModel(nnodes, nblocks; ρ=fill(0.5, nblocks, nblocks), π=fill(1 / nblocks, nblocks),
+                            z=[mod(n - 1, nblocks) + 1 for n in 1:nnodes], α=1.0, β=1.0, γ=1.0) =
+    StochasticBlockNetworkModel(nnodes, nblocks, ρ, π, z, α, β, γ)
+NHP.params(net::StochasticBlockNetworkModel) = [vec(net.ρ); net.π]
+link_probability(net::StochasticBlockNetworkModel) = net.ρ[net.z, net.z]
+
+function block_counts(net::StochasticBlockNetworkModel, A::Matrix{Float64}; ctx=context())
+    K = net.nblocks
+    z0, L, n = Int32.(net.z .- 1), Matrix{Int64}(undef, K, K), Vector{Int64}(undef, K)
+    check(ccall((:nhp_sbm_block_counts, libnhp), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}),
+                ctx.h, A, net.nnodes, K, z0, L, n), ctx.h)
+    L, n
+end
+
+function resample!(net::StochasticBlockNetworkModel, A::Matrix{Float64}; seed::UInt64=UInt64(0), step::Integer=0, ctx=context())
+    K = net.nblocks
+    L, n = block_counts(net, A; ctx=ctx)
+    check(ccall((:nhp_sbm_draw, libnhp), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Int64}, Float64, Float64, Float64, UInt64, UInt64, Ptr{Float64}, Ptr{Float64}),
+                ctx.h, K, L, n, net.α, net.β, net.γ, seed, UInt64(step), net.ρ, net.π), ctx.h)
+    z0 = Int32.(net.z .- 1)
+    check(ccall((:nhp_sbm_resample_blocks, libnhp), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt64, UInt64, Int32,
+                 Ptr{Float64}, Ptr{Float64}),
+                ctx.h, A, net.nnodes, K, z0, net.ρ, net.π, C_NULL, seed, UInt64(step), Int32(1), C_NULL, C_NULL), ctx.h)
+    net.z = Int.(z0) .+ 1
+    NHP.params(net)
+end
+
+function set_sbm!(ctx::Context, m::Ptr{Cvoid}, net::StochasticBlockNetworkModel; labels_every::Integer=1)
+    check(ccall((:nhp_cont_model_set_sbm, libnhp), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Float64),
+                ctx.h, m, net.nblocks, Int32.(net.z .- 1), net.ρ, net.π, net.α, net.β, net.γ), ctx.h)
+    check(ccall((:nhp_cont_model_set_sbm_labels_every, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), ctx.h, m, labels_every), ctx.h)
+end
+
+# -> (sums = [Σρ; Σρ²; Σπ; Σπ²], block_counts N x K) over the kept steps; the state itself goes into `net`
+function get_sbm!(ctx::Context, m::Ptr{Cvoid}, net::StochasticBlockNetworkModel)
+    K, N = net.nblocks, net.nnodes
+    z0, sums, bc = Vector{Int32}(undef, N), Vector{Float64}(undef, 2K * K + 2K), Matrix{Int64}(undef, N, K)
+    check(ccall((:nhp_cont_model_get_sbm, libnhp), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                ctx.h, m, z0, net.ρ, net.π, sums, bc), ctx.h)
+    net.z = Int.(z0) .+ 1
+    sums, bc
+end
+
+# one network step of mcmc! under the block model (asynchronous): link probabilities, adjacency sweep, resample!(network, A)
+sbm_step!(ctx::Context, ds, m::Ptr{Cvoid}; seed::UInt64=UInt64(0), step::Integer=0) =
+    check(ccall((:nhp_cont_sbm_step, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt64, UInt64), ctx.h, ds.h, m, seed, UInt64(step)), ctx.h)
+
 # BASELINE config 5: after every rank ran its own chain with keep_samples=false, the per-chain posterior sums (still on
 # the devices) all-gathered over RCCL: returns (sum, sumsq) as len x world matrices, the sample counts, and ρ's sums.
 function gather_moments(ctx::Context, comm::Comm, m::Ptr{Cvoid}, len::Integer)

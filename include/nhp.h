@@ -535,6 +535,37 @@ nhp_status nhp_disc_svi_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
                             int64_t batch_bins, double delay, double forgetting, uint64_t seed, int64_t step0, int32_t n_steps,
                             const int32_t *blocks /* nullable [n_steps] */, const double *phi /* nullable */, int32_t n_lags,
                             int32_t n_basis, double *alpha_v, double *beta_v, double *kappa_v, double *nu_v, double *gamma_v);
+/* update! / vb! for DiscreteNetworkHawkesProcess + SparseWeightModel + DiscreteHomogeneousProcess (broken wiring in the
+ * reference; every formula is in src/weights.jl:141-173, src/discrete.jl:482-492, src/networks.jl:80-93).
+ * Mean-field family q(A[p,c] = 1) = rho_v[p,c], q(W | A = a) = Gamma(kappa_v<a>, nu_v<a>); arrays column-major [p, c(, b)].
+ * One step, factors from the OLD parameters:  ElogW = (1 - ρv)(ψ(κv0) - log νv0) + ρv (ψ(κv1) - log νv1) in the factor
+ * E of nhp_disc_vb_run; its two GEMMs and its baseline update unchanged; with Γ = E ⊙ (Gᵀ·R):
+ *   γv = γ + Γ,  κv_a = κ_a + Σ_b Γ,  νv_a[p,c] = ν_a + Σ_t data[p,t]                     (a = 0 spike, a = 1 slab)
+ *   logit ρv = ψ(αv_net) - ψ(βv_net) + [κ1 log ν1 - lgamma κ1 + lgamma κv1 - κv1 log νv1]
+ *                                    - [κ0 log ν0 - lgamma κ0 + lgamma κv0 - κv0 log νv0]   (new κv/νv, old network)
+ *   ρv = 1/(1 + exp(-logit)), exactly 0 or 1 when saturated;  αv_net = α + Σρv,  βv_net = β + Σ(1 - ρv)   (all N² links)
+ * net_kind 0 = DenseNetworkModel: rho_v is set to 1 on entry and stays 1, net_alpha_v / net_beta_v may be NULL and are not
+ * touched; 1 = BernoulliNetworkModel with prior Beta(net_alpha, net_beta).  Any other kind is NHP_ENOTIMPL.  Every rho_v
+ * must lie in [0, 1], every κ, ν, γ, α, β (priors and variational) must be > 0: NHP_EINVAL with a message, before any launch.
+ * One upload, one download, no synchronisation inside the n_steps; the sums over links have one fixed order, so a run is
+ * reproducible bit for bit. */
+nhp_status nhp_disc_netvb_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
+                              double alpha0, double beta0, double kappa0, double nu0, double kappa1, double nu1, double gamma,
+                              int32_t net_kind, double net_alpha, double net_beta, int32_t n_steps,
+                              double *alpha_v, double *beta_v, double *kappa_v0, double *nu_v0, double *kappa_v1, double *nu_v1,
+                              double *gamma_v, double *rho_v, double *net_alpha_v /* nullable if dense */,
+                              double *net_beta_v /* nullable if dense */);
+/* svi! for the same model: the block step of nhp_disc_svi_run (its blocks, seeds, modes and argument rules) gives α̂, γ̂ and
+ * Σ_b (γ̂ - γ);  κ̂v_a = κ_a + Σ_b (γ̂ - γ),  ν̂v_a = ν_a + Σ_{t<T} data[p,t],  ρ̂v from the logit above at (κ̂v, ν̂v) and the
+ * current network parameters,  α̂v_net = α + Σρ̂v,  β̂v_net = β + Σ(1 - ρ̂v);  then every parameter, ρv included,
+ * x <- (1 - ρ_i) x + ρ_i x̂.  One block, delay 0, forgetting 1, one step is one step of nhp_disc_netvb_run. */
+nhp_status nhp_disc_netsvi_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
+                               double alpha0, double beta0, double kappa0, double nu0, double kappa1, double nu1, double gamma,
+                               int32_t net_kind, double net_alpha, double net_beta,
+                               int64_t batch_bins, double delay, double forgetting, uint64_t seed, int64_t step0, int32_t n_steps,
+                               const int32_t *blocks /* nullable [n_steps] */, const double *phi /* nullable */, int32_t n_lags,
+                               int32_t n_basis, double *alpha_v, double *beta_v, double *kappa_v0, double *nu_v0, double *kappa_v1,
+                               double *nu_v1, double *gamma_v, double *rho_v, double *net_alpha_v, double *net_beta_v);
 /* The blocks nhp_disc_svi_run draws for global steps step0 + 1 .. step0 + n (host side, no device): out[k] =
  * min(nb - 1, floor(nb · u_i)), u_i the Philox4x32-10 uniform in [0, 1) with key seed ^ 0x5C1B10C5D2A7E391, counter words
  * (event = 0, step = i), i = step0 + k + 1 -- a function of (seed, i) alone. */

@@ -22,7 +22,7 @@ from .discrete import (DiscreteDataset, DiscreteFitTest, DiscreteForecast, Discr
                        disc_resample_adjacency_matrix_,
                        DiscreteInformation, DiscreteStandardErrors, disc_hessian_vector_product, disc_observed_information,
                        disc_standard_errors,
-                       resample_parent_counts, svi_, svi_blocks, update_, vb_)
+                       resample_parent_counts, svi_, svi_blocks, update_, variational_mean_, vb_)
 from . import discrete as _disc
 from .parents import (Cascades, cascades, map_parents, node_counts, parent_counts, resample_parents,  # noqa: F401
                       uniform_stream)

@@ -362,15 +362,18 @@ class DenseWeightModel(Weights):
 class SparseWeightModel(DenseWeightModel):
     """SparseWeightModel(W) -- src/weights.jl:104-127: the weights of a network process, with separate Gamma priors
     for absent (κ0, ν0) and present (κ1, ν1) links.  Its Gibbs update (src/weights.jl:133-139) is the dense one under
-    the present-link prior -- W ~ Gamma(κ1 + Mnm, 1/(ν1 + Mn[p])) -- so every kernel sees it as a DenseWeightModel with
-    (κ, ν) = (κ1, ν1).  The variational methods of the reference are broken (undefined `p`, `ν1`, `ρ`, field-name
-    mismatches: src/weights.jl:141-173) and raise here."""
+    the present-link prior -- W ~ Gamma(κ1 + Mnm, 1/(ν1 + Mn[p])) -- so every Gibbs kernel sees it as a DenseWeightModel
+    with (κ, ν) = (κ1, ν1).  The variational methods of the reference throw on their wiring (undefined `p`, `ν1`, `ρ`,
+    field-name mismatches: src/weights.jl:141-173); their intended semantics run on the GPU for a network
+    process (update_): q(W | A = a) = Gamma(κv_a, νv_a) and q(A = 1) = ρv, an N x N matrix that starts as
+    None, meaning "start from network.link_probability()"."""
 
     def __init__(self, W, κ0=1.0, ν0=1.0, κ1=1.0, ν1=1.0):
         super().__init__(W, κ1, ν1)
         self.κ0, self.ν0, self.κ1, self.ν1 = float(κ0), float(ν0), float(κ1), float(ν1)
         self.κv0, self.νv0 = np.ones_like(self.W), np.ones_like(self.W)
         self.κv1, self.νv1 = np.ones_like(self.W), np.ones_like(self.W)
+        self.ρv = None
 
     def variational_params(self):
         """src/weights.jl:131"""
@@ -405,10 +408,12 @@ class DenseNetworkModel(Network):
 
 
 class BernoulliNetworkModel(Network):
-    """BernoulliNetworkModel(ρ, N) with Beta(α, β) prior -- src/networks.jl:34-78."""
+    """BernoulliNetworkModel(ρ, N) with Beta(α, β) prior -- src/networks.jl:34-78; (αv, βv) are the parameters of the
+    variational Beta of ρ (src/networks.jl:54: both start at 1)."""
 
-    def __init__(self, ρ, nnodes, α=1.0, β=1.0):
+    def __init__(self, ρ, nnodes, α=1.0, β=1.0, αv=1.0, βv=1.0):
         self.ρ, self.α, self.β, self.nnodes = float(ρ), float(α), float(β), int(nnodes)
+        self.αv, self.βv = float(αv), float(βv)
 
     def params(self):
         return np.array([self.ρ])

@@ -18,6 +18,7 @@
 
 #include "nhp_internal.h"
 #include "nhp_math.h"
+#include "nhp_netvb.h"
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 
@@ -1617,6 +1618,387 @@ extern "C" nhp_status nhp_disc_svi_run(nhp_ctx *ctx, const nhp_disc_dataset *ds,
     NHP_HIP(ctx, hipMemcpyAsync(gamma_v, dgv, 8 * NN * B, hipMemcpyDeviceToHost, st));
     NHP_HIP(ctx, hipStreamSynchronize(st));
     return NHP_OK;
+}
+
+// ---- VB and SVI for the network process: spike-and-slab weights around the two GEMMs above ----
+// q(A[p,c] = 1) = ρv[p,c], q(W | A = a) = Gamma(κv_a, νv_a); the reference writes every formula (src/weights.jl:141-173,
+// src/discrete.jl:482-492, src/networks.jl:80-93) and throws on the wiring.  The GEMMs, their epilogues and the baseline
+// kernels are the dense step's; the three kernels below are the per-link layer around them.
+
+// E[(p,b), c] = exp(ψ(γv[p,c,b]) - ψ(Σ_b γv) + ElogW),  ElogW = (1 - ρv)(ψ(κv0) - log νv0) + ρv (ψ(κv1) - log νv1): two
+// products and one sum, never contracted, so ρv = 1 leaves the slab's term exactly (the dense step's factor bit for bit)
+__global__ __launch_bounds__(256) void k_netvb_factors(int N, int B, const double *__restrict__ alpha_v,
+                                                       const double *__restrict__ beta_v,
+                                                       const double *__restrict__ kappa_v0, const double *__restrict__ nu_v0,
+                                                       const double *__restrict__ kappa_v1, const double *__restrict__ nu_v1,
+                                                       const double *__restrict__ gamma_v, const double *__restrict__ rho_v,
+                                                       double *__restrict__ E, double *__restrict__ e0)
+{
+#pragma clang fp contract(off)
+    const size_t NN = (size_t)N * N, K = (size_t)N * B;
+    const size_t pc = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (pc < NN) {
+        const size_t p = pc % N, c = pc / N;
+        double gs = 0.0;
+        for (int b = 0; b < B; ++b) gs += gamma_v[pc + (size_t)b * NN];
+        const double r = rho_v[pc];
+        const double elw0 = nhp_digamma(kappa_v0[pc]) - nhp_log(nu_v0[pc]);
+        const double elw1 = nhp_digamma(kappa_v1[pc]) - nhp_log(nu_v1[pc]);
+        const double elw = (1.0 - r) * elw0 + r * elw1;
+        const double dgs = nhp_digamma(gs);
+        for (int b = 0; b < B; ++b) {
+            const double elt = nhp_digamma(gamma_v[pc + (size_t)b * NN]) - dgs;
+            E[p + (size_t)b * N + c * K] = nhp_exp(elt + elw);
+        }
+    }
+    if (pc < (size_t)N) e0[pc] = nhp_exp(nhp_digamma(alpha_v[pc]) - nhp_log(beta_v[pc]));
+}
+
+// lgamma(x + d) - lgamma(x) for x > 0, x + d > 0.  Both arguments grow with the counts while d = κ1 - κ0 stays, so past
+// 16 the difference is taken inside Stirling's formula, where the two leading terms combine without cancellation:
+//   (x - 1/2) log1p(d/x) + d log(x + d) - d + [s(x + d) - s(x)],   s(z) = 1/(12 z) - 1/(360 z³) + ... (error < 1e-16 at 16).
+// Below 16 the two library values are at most 28 in size and their difference loses nothing that matters.
+__device__ __forceinline__ double netvb_stirling_tail(double z)
+{
+    const double f = 1.0 / (z * z);
+    return (1.0 / 12.0 + f * (-1.0 / 360.0 + f * (1.0 / 1260.0 + f * (-1.0 / 1680.0 + f * (1.0 / 1188.0))))) / z;
+}
+__device__ __forceinline__ double netvb_lgamma_diff(double x, double d)
+{
+    const double y = x + d;
+    if (x < 16.0 || y < 16.0) return lgamma(y) - lgamma(x);
+    return ((x - 0.5) * log1p(d / x) + d * nhp_log(y) - d) + (netvb_stirling_tail(y) - netvb_stirling_tail(x));
+}
+
+// logit ρv = net + prior + [lgamma κv1 - lgamma κv0] - [κv1 log νv1 - κv0 log νv0] with κv1 = κv0 + dk, νv1 = νv0 + dn
+// (dk = κ1 - κ0, dn = ν1 - ν0): the second bracket is κv0 log1p(dn/νv0) + dk log νv1, again without cancellation
+__device__ __forceinline__ double netvb_logit(double net, double prior, double dk, double dn, double kv0, double nv0, double nv1)
+{
+#pragma clang fp contract(off)
+    return ((net + prior) + netvb_lgamma_diff(kv0, dk)) - (kv0 * log1p(dn / nv0) + dk * nhp_log(nv1));
+}
+
+// 1/(1 + exp(-x)) in the form that keeps the small side's relative accuracy; exactly 0 below -708 and 1 above 37, no NaN
+__device__ __forceinline__ double netvb_sigmoid(double x)
+{
+    if (x >= 0.0) return 1.0 / (1.0 + nhp_exp(-x));
+    const double e = nhp_exp(x);
+    return e / (1.0 + e);
+}
+
+// After GEMM-2: Γ = E ⊙ Σ_z slab_z and the hats γ̂ = γ + nb Γ, κ̂_a = κ_a + Σ_b (γ̂ - γ), ν̂_a[p,c] = ν_a + Σ_t data[p,t]
+// (VB: nb = 1 and γ̂ = γ + Γ as k_vb_finish writes it); ρ̂ from the logit at the hats and the OLD network parameters
+// netp = (αv, βv); then x <- x̂ (VB) or x <- (1 - r) x + r x̂ (SVI), ρv included.  Every workgroup leaves the pair
+// (Σ ρ̂, Σ (1 - ρ̂)) of its 256 links in partials[2·blockIdx.x ..]: the order inside nhp_block_sum2_n is fixed.
+template <bool SVI>
+__global__ __launch_bounds__(256) void k_netvb_finish(int N, int B, int n_slabs, const double *__restrict__ slabs,
+                                                      const double *__restrict__ E, const double *__restrict__ colsum,
+                                                      double kappa0, double nu0, double kappa1, double nu1, double gamma,
+                                                      double nb, double r, int net_kind, double prior,
+                                                      const double *__restrict__ netp,
+                                                      double *__restrict__ kappa_v0, double *__restrict__ nu_v0,
+                                                      double *__restrict__ kappa_v1, double *__restrict__ nu_v1,
+                                                      double *__restrict__ gamma_v, double *__restrict__ rho_v,
+                                                      double *__restrict__ partials)
+{
+    __shared__ double red[2 * NHP_WAVES];
+    const size_t NN = (size_t)N * N, K = (size_t)N * B;
+    const size_t pc = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const double keep = 1.0 - r;
+    double rh = 0.0, rc = 0.0;                         // ρ̂ and 1 - ρ̂ of this link; a thread past the end adds nothing
+    if (pc < NN) {
+        const size_t p = pc % N, c = pc / N;
+        double ksum = 0.0;
+        for (int b = 0; b < B; ++b) {
+            const size_t o = p + (size_t)b * N + c * K;
+            double s = 0.0;
+            for (int z = 0; z < n_slabs; ++z) s += slabs[(size_t)z * K * N + o];
+            if (SVI) {                                 // the statements of k_svi_finish ...
+                const double gp = gamma + E[o] * s;
+                const double gh = gamma + nb * (gp - gamma);
+                ksum += gh - gamma;
+                gamma_v[pc + (size_t)b * NN] = keep * gamma_v[pc + (size_t)b * NN] + r * gh;
+            } else {                                   // ... and of k_vb_finish, so the dense limit keeps their bits
+                const double G = E[o] * s;
+                gamma_v[pc + (size_t)b * NN] = gamma + G;
+                ksum += G;
+            }
+        }
+        const double k0h = kappa0 + ksum, k1h = kappa1 + ksum, n0h = nu0 + colsum[p], n1h = nu1 + colsum[p];
+        if (net_kind == 0) {
+            rh = 1.0;
+        } else {
+            const double net = nhp_digamma(netp[0]) - nhp_digamma(netp[1]);
+            rh = netvb_sigmoid(netvb_logit(net, prior, kappa1 - kappa0, nu1 - nu0, k0h, n0h, n1h));
+        }
+        rc = 1.0 - rh;
+        if (SVI) {
+            kappa_v0[pc] = keep * kappa_v0[pc] + r * k0h;
+            nu_v0[pc] = keep * nu_v0[pc] + r * n0h;
+            kappa_v1[pc] = keep * kappa_v1[pc] + r * k1h;
+            nu_v1[pc] = keep * nu_v1[pc] + r * n1h;
+            rho_v[pc] = net_kind ? keep * rho_v[pc] + r * rh : 1.0;
+        } else {
+            kappa_v0[pc] = k0h; nu_v0[pc] = n0h; kappa_v1[pc] = k1h; nu_v1[pc] = n1h;
+            rho_v[pc] = rh;
+        }
+    }
+    nhp_block_sum2_n<NHP_WAVES>(rh, rc, red);
+    if (threadIdx.x == 0) { partials[2 * (size_t)blockIdx.x] = rh; partials[2 * (size_t)blockIdx.x + 1] = rc; }
+}
+
+// One workgroup: thread i adds the pairs i, i + 256, ... in increasing order, nhp_block_sum2_n joins the 256 threads in
+// its fixed order; αv = α + Σρ̂, βv = β + Σ(1 - ρ̂) over all N² links, the diagonal included (src/networks.jl:86-90)
+template <bool SVI>
+__global__ __launch_bounds__(256) void k_netvb_network(int n_pairs, const double *__restrict__ partials, double alpha, double beta,
+                                                       double r, double *__restrict__ netp)
+{
+    __shared__ double red[2 * NHP_WAVES];
+    double a = 0.0, b = 0.0;
+    for (int i = threadIdx.x; i < n_pairs; i += 256) { a += partials[2 * (size_t)i]; b += partials[2 * (size_t)i + 1]; }
+    nhp_block_sum2_n<NHP_WAVES>(a, b, red);
+    if (threadIdx.x == 0) {
+        const double ah = alpha + a, bh = beta + b;
+        if (SVI) {
+            const double keep = 1.0 - r;
+            netp[0] = keep * netp[0] + r * ah;
+            netp[1] = keep * netp[1] + r * bh;
+        } else {
+            netp[0] = ah; netp[1] = bh;
+        }
+    }
+}
+
+// the device block of a network run's parameters, in the order netvb_param_doubles counts them
+struct netvb_bufs {
+    double *E, *e0, *av, *bv, *kv0, *nv0, *kv1, *nv1, *gv, *rho, *netp, *part, *end;
+};
+static netvb_bufs netvb_carve(double *p, size_t N, size_t B)
+{
+    const size_t NN = N * N, K = N * B;
+    netvb_bufs u;
+    u.E = p; p += K * N;
+    u.e0 = p; p += N;
+    u.av = p; p += N;
+    u.bv = p; p += N;
+    u.kv0 = p; p += NN;
+    u.nv0 = p; p += NN;
+    u.kv1 = p; p += NN;
+    u.nv1 = p; p += NN;
+    u.gv = p; p += NN * B;
+    u.rho = p; p += NN;
+    u.netp = p; p += 2;
+    u.part = p; p += 2 * netvb_link_blocks(N);
+    u.end = p;
+    return u;
+}
+
+struct netvb_host {
+    double *alpha_v, *beta_v, *kappa_v0, *nu_v0, *kappa_v1, *nu_v1, *gamma_v, *rho_v, *net_alpha_v, *net_beta_v;
+};
+
+// one upload / one download of the parameters; a dense network's ρv is 1 whatever the caller's array holds
+static nhp_status netvb_upload(nhp_ctx *ctx, hipStream_t st, const netvb_bufs &u, const netvb_host &h, size_t N, size_t B, int net_kind,
+                               double *net_stage)
+{
+    const size_t NN = N * N;
+    NHP_HIP(ctx, hipMemcpyAsync(u.av, h.alpha_v, 8 * N, hipMemcpyHostToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(u.bv, h.beta_v, 8 * N, hipMemcpyHostToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(u.kv0, h.kappa_v0, 8 * NN, hipMemcpyHostToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(u.nv0, h.nu_v0, 8 * NN, hipMemcpyHostToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(u.kv1, h.kappa_v1, 8 * NN, hipMemcpyHostToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(u.nv1, h.nu_v1, 8 * NN, hipMemcpyHostToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(u.gv, h.gamma_v, 8 * NN * B, hipMemcpyHostToDevice, st));
+    if (net_kind == 0)
+        for (size_t i = 0; i < NN; ++i) h.rho_v[i] = 1.0;
+    NHP_HIP(ctx, hipMemcpyAsync(u.rho, h.rho_v, 8 * NN, hipMemcpyHostToDevice, st));
+    net_stage[0] = net_kind ? *h.net_alpha_v : 1.0;
+    net_stage[1] = net_kind ? *h.net_beta_v : 1.0;
+    NHP_HIP(ctx, hipMemcpyAsync(u.netp, net_stage, 16, hipMemcpyHostToDevice, st));
+    return NHP_OK;
+}
+static nhp_status netvb_download(nhp_ctx *ctx, hipStream_t st, const netvb_bufs &u, const netvb_host &h, size_t N, size_t B, int net_kind,
+                                 double *net_stage)
+{
+    const size_t NN = N * N;
+    NHP_HIP(ctx, hipMemcpyAsync(h.alpha_v, u.av, 8 * N, hipMemcpyDeviceToHost, st));
+    NHP_HIP(ctx, hipMemcpyAsync(h.beta_v, u.bv, 8 * N, hipMemcpyDeviceToHost, st));
+    NHP_HIP(ctx, hipMemcpyAsync(h.kappa_v0, u.kv0, 8 * NN, hipMemcpyDeviceToHost, st));
+    NHP_HIP(ctx, hipMemcpyAsync(h.nu_v0, u.nv0, 8 * NN, hipMemcpyDeviceToHost, st));
+    NHP_HIP(ctx, hipMemcpyAsync(h.kappa_v1, u.kv1, 8 * NN, hipMemcpyDeviceToHost, st));
+    NHP_HIP(ctx, hipMemcpyAsync(h.nu_v1, u.nv1, 8 * NN, hipMemcpyDeviceToHost, st));
+    NHP_HIP(ctx, hipMemcpyAsync(h.gamma_v, u.gv, 8 * NN * B, hipMemcpyDeviceToHost, st));
+    NHP_HIP(ctx, hipMemcpyAsync(h.rho_v, u.rho, 8 * NN, hipMemcpyDeviceToHost, st));
+    NHP_HIP(ctx, hipMemcpyAsync(net_stage, u.netp, 16, hipMemcpyDeviceToHost, st));
+    NHP_HIP(ctx, hipStreamSynchronize(st));
+    if (net_kind) { *h.net_alpha_v = net_stage[0]; *h.net_beta_v = net_stage[1]; }
+    return NHP_OK;
+}
+
+static nhp_status netvb_check(nhp_ctx *ctx, const char *what, const nhp_disc_dataset *ds, const netvb_priors &q, double dt, int64_t B,
+                              int32_t n_steps, const netvb_host &h)
+{
+    char msg[256];
+    const int rc = netvb_check_args(what, q, dt, ds->N, B, n_steps, h.alpha_v, h.beta_v, h.kappa_v0, h.nu_v0, h.kappa_v1, h.nu_v1,
+                                    h.gamma_v, h.rho_v, h.net_alpha_v, h.net_beta_v, msg, sizeof msg);
+    if (rc == NETVB_OK) return NHP_OK;
+    nhp_set_error(ctx, "%s", msg);
+    return rc == NETVB_ENOTIMPL ? NHP_ENOTIMPL : NHP_EINVAL;
+}
+
+extern "C" nhp_status nhp_disc_netvb_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
+                                         double alpha0, double beta0, double kappa0, double nu0, double kappa1, double nu1, double gamma,
+                                         int32_t net_kind, double net_alpha, double net_beta, int32_t n_steps,
+                                         double *alpha_v, double *beta_v, double *kappa_v0, double *nu_v0, double *kappa_v1,
+                                         double *nu_v1, double *gamma_v, double *rho_v, double *net_alpha_v, double *net_beta_v)
+{
+    if (!ctx || !ds) return NHP_EINVAL;
+    const netvb_priors q{alpha0, beta0, kappa0, nu0, kappa1, nu1, gamma, net_kind, net_alpha, net_beta};
+    const netvb_host h{alpha_v, beta_v, kappa_v0, nu_v0, kappa_v1, nu_v1, gamma_v, rho_v, net_alpha_v, net_beta_v};
+    if (!ds->d_conv) { nhp_set_error(ctx, "netvb: convolve(process, data) must run before update!"); return NHP_EINVAL; }
+    if (ds->d_baseT) { nhp_set_error(ctx, "netvb: defined for DiscreteHomogeneousProcess baselines only"); return NHP_ENOTIMPL; }
+    NHP_TRY(netvb_check(ctx, "netvb", ds, q, dt, ds->B, n_steps, h));
+    NHP_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t N = (size_t)ds->N, B = (size_t)ds->B, K = N * B, T = (size_t)ds->T;
+    const int bm = gemm1_tile_m((int64_t)T, (int)N, ctx->cu_count);
+    const int row_blocks = (int)((T + bm - 1) / bm);
+    const int tiles2 = (int)(((K + BM - 1) / BM) * ((N + BN - 1) / BN));
+    int splits, k_chunk;
+    svi_split((int64_t)T, tiles2, ctx->cu_count, &splits, &k_chunk);          // the rule of nhp_disc_vb_run
+    const size_t need = 8 * (netvb_param_doubles(N, B) + T * N + (size_t)row_blocks * N + (size_t)splits * K * N);
+    NHP_TRY(nhp_ctx_reserve_scratch(ctx, need));
+    const netvb_bufs u = netvb_carve((double *)ctx->d_scratch, N, B);
+    double *dR = u.end, *dcolp = dR + T * N, *dslab = dcolp + (size_t)row_blocks * N;
+    const unsigned link_blocks = (unsigned)netvb_link_blocks(N);
+    const double prior = netvb_prior_logit(q);
+    double net_stage[2];
+    hipStream_t st = ctx->main();
+    NHP_TRY(netvb_upload(ctx, st, u, h, N, B, net_kind, net_stage));
+    for (int step = 0; step < n_steps; ++step) {      // every parameter stays on the device between steps
+        hipLaunchKernelGGL(k_netvb_factors, dim3(link_blocks), dim3(256), 0, st, (int)N, (int)B, u.av, u.bv, u.kv0, u.nv0, u.kv1, u.nv1,
+                           u.gv, u.rho, u.E, u.e0);
+        NHP_HIP(ctx, hipGetLastError());
+        gemm_args g1{};
+        g1.A = ds->d_conv; g1.lda = T; g1.B = u.E; g1.ldb = K; g1.M = (int)T; g1.N = (int)N; g1.K = (int)K; g1.k_chunk = (int)K;
+        g1.base = u.e0; g1.dataT = ds->d_dataT; g1.out = dR; g1.partials = dcolp;
+        launch_gemm<true, EPI_VB_Z>(g1, 1, st, bm);
+        NHP_HIP(ctx, hipGetLastError());
+        gemm_args g2{};
+        g2.A = ds->d_conv; g2.lda = T; g2.B = dR; g2.ldb = T; g2.M = (int)K; g2.N = (int)N; g2.K = (int)T; g2.k_chunk = k_chunk;
+        g2.out = dslab;
+        launch_gemm<false, EPI_SLAB>(g2, splits, st);
+        NHP_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_vb_baseline, dim3((unsigned)((N + 63) / 64)), dim3(256), 0, st, (int)N, row_blocks, dcolp, u.e0,
+                           alpha0, beta0, (double)T * dt, u.av, u.bv);
+        hipLaunchKernelGGL(k_netvb_finish<false>, dim3(link_blocks), dim3(256), 0, st, (int)N, (int)B, splits, dslab, u.E, ds->d_colsum,
+                           kappa0, nu0, kappa1, nu1, gamma, 1.0, 1.0, (int)net_kind, prior, u.netp, u.kv0, u.nv0, u.kv1, u.nv1, u.gv,
+                           u.rho, u.part);
+        if (net_kind)
+            hipLaunchKernelGGL(k_netvb_network<false>, dim3(1), dim3(256), 0, st, (int)link_blocks, u.part, net_alpha, net_beta, 1.0, u.netp);
+        NHP_HIP(ctx, hipGetLastError());
+    }
+    return netvb_download(ctx, st, u, h, N, B, net_kind, net_stage);
+}
+
+extern "C" nhp_status nhp_disc_netsvi_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
+                                          double alpha0, double beta0, double kappa0, double nu0, double kappa1, double nu1, double gamma,
+                                          int32_t net_kind, double net_alpha, double net_beta,
+                                          int64_t batch_bins, double delay, double forgetting, uint64_t seed, int64_t step0,
+                                          int32_t n_steps, const int32_t *blocks, const double *phi, int32_t n_lags, int32_t n_basis,
+                                          double *alpha_v, double *beta_v, double *kappa_v0, double *nu_v0, double *kappa_v1,
+                                          double *nu_v1, double *gamma_v, double *rho_v, double *net_alpha_v, double *net_beta_v)
+{
+    if (!ctx || !ds) return NHP_EINVAL;
+    const netvb_priors q{alpha0, beta0, kappa0, nu0, kappa1, nu1, gamma, net_kind, net_alpha, net_beta};
+    const netvb_host h{alpha_v, beta_v, kappa_v0, nu_v0, kappa_v1, nu_v1, gamma_v, rho_v, net_alpha_v, net_beta_v};
+    if (n_steps < 1 || step0 < 0) { nhp_set_error(ctx, "netsvi: n_steps must be >= 1 and step0 >= 0"); return NHP_EINVAL; }
+    if (!(delay >= 0.0)) { nhp_set_error(ctx, "netsvi: delay must be >= 0"); return NHP_EINVAL; }
+    if (!(forgetting > 0.5 && forgetting <= 1.0)) { nhp_set_error(ctx, "netsvi: forgetting must lie in (0.5, 1]"); return NHP_EINVAL; }
+    const int64_t Tn = ds->T;
+    if (batch_bins < Tn && (batch_bins < 16 || batch_bins % 16 != 0)) {
+        nhp_set_error(ctx, "netsvi: batch_bins = %lld must be a multiple of 16 (>= 16), or >= the %lld bins of the data", (long long)batch_bins, (long long)Tn);
+        return NHP_EINVAL;
+    }
+    const int64_t Tb = std::min(batch_bins, Tn);
+    const int32_t nb = (int32_t)((Tn + Tb - 1) / Tb);
+    if (blocks)
+        for (int32_t k = 0; k < n_steps; ++k)
+            if (blocks[k] < 0 || blocks[k] >= nb) { nhp_set_error(ctx, "netsvi: blocks[%d] = %d is outside [0, %d)", k, blocks[k], nb); return NHP_EINVAL; }
+    if (ds->d_baseT) { nhp_set_error(ctx, "netsvi: defined for DiscreteHomogeneousProcess baselines only"); return NHP_ENOTIMPL; }
+    const bool streamed = phi != nullptr;
+    if (streamed && (n_lags < 1 || n_basis < 1)) { nhp_set_error(ctx, "netsvi: the streamed mode needs n_lags >= 1 and n_basis >= 1"); return NHP_EINVAL; }
+    if (!streamed && !ds->d_conv) { nhp_set_error(ctx, "netsvi: convolve(process, data) must run first, or pass the basis for the streamed mode"); return NHP_EINVAL; }
+    NHP_TRY(netvb_check(ctx, "netsvi", ds, q, dt, streamed ? n_basis : ds->B, n_steps, h));
+    const size_t N = (size_t)ds->N, B = (size_t)(streamed ? n_basis : ds->B), K = N * B, T = (size_t)Tn, L = streamed ? (size_t)n_lags : 0;
+    const size_t lds_conv = 8 * (256 + L + L * ((B + CONV_CB - 1) / CONV_CB * CONV_CB));
+    if (streamed && lds_conv > 64 * 1024) { nhp_set_error(ctx, "netsvi: nlags * nbasis = %d * %d exceeds the LDS budget", n_lags, n_basis); return NHP_ENOTIMPL; }
+    NHP_HIP(ctx, hipSetDevice(ctx->device));
+    const int tiles2 = (int)(((K + BM - 1) / BM) * ((N + BN - 1) / BN));
+    const int max_splits = svi_split_cap(Tb, tiles2, ctx->cu_count);
+    const size_t max_row_blocks = (size_t)((Tb + BM - 1) / BM);
+    const size_t need = 8 * (netvb_param_doubles(N, B) + 2 * (size_t)Tb * N + max_row_blocks * N + (size_t)max_splits * K * N +
+                             (streamed ? (size_t)Tb * K + L * B : 0));
+    NHP_TRY(nhp_ctx_reserve_scratch(ctx, need));
+    const netvb_bufs u = netvb_carve((double *)ctx->d_scratch, N, B);
+    double *p = u.end;
+    double *dD = p; p += (size_t)Tb * N;
+    double *dR = p; p += (size_t)Tb * N;
+    double *dcolp = p; p += max_row_blocks * N;
+    double *dslab = p; p += (size_t)max_splits * K * N;
+    double *dimg = p; p += streamed ? (size_t)Tb * K : 0;
+    double *dphi = p;
+    const unsigned link_blocks = (unsigned)netvb_link_blocks(N);
+    const double prior = netvb_prior_logit(q);
+    double net_stage[2];
+    hipStream_t st = ctx->main();
+    NHP_TRY(netvb_upload(ctx, st, u, h, N, B, net_kind, net_stage));
+    if (streamed) NHP_HIP(ctx, hipMemcpyAsync(dphi, phi, 8 * L * B, hipMemcpyHostToDevice, st));
+    for (int32_t k = 0; k < n_steps; ++k) {           // every parameter stays on the device between steps
+        const uint64_t i = (uint64_t)step0 + (uint64_t)k + 1;
+        const int64_t j = blocks ? blocks[k] : svi_block_of(seed, i, nb);
+        const int64_t t0 = j * Tb, len = std::min<int64_t>(Tn, t0 + Tb) - t0;
+        const double rho = pow((double)i + delay, -forgetting);
+        const int bm = gemm1_tile_m(len, (int)N, ctx->cu_count);
+        const int row_blocks = (int)((len + bm - 1) / bm);
+        int splits, k_chunk;
+        svi_split(len, tiles2, ctx->cu_count, &splits, &k_chunk);
+        hipLaunchKernelGGL(k_netvb_factors, dim3(link_blocks), dim3(256), 0, st, (int)N, (int)B, u.av, u.bv, u.kv0, u.nv0, u.kv1, u.nv1,
+                           u.gv, u.rho, u.E, u.e0);
+        const double *G, *D = ds->d_dataT;
+        size_t ldg;
+        if (!streamed) {
+            G = ds->d_conv + t0; ldg = T;
+        } else {
+            hipLaunchKernelGGL(k_disc_convolve_window, dim3((unsigned)((len + 255) / 256), (unsigned)N), dim3(256), lds_conv, st, ds->d_dataT, (int)N,
+                               Tn, dphi, (int)L, (int)B, t0, (int)len, (size_t)len, dimg);
+            G = dimg; ldg = (size_t)len;
+        }
+        if (len < Tn) {
+            hipLaunchKernelGGL(k_svi_block_data, dim3((unsigned)(((size_t)len * N + 255) / 256)), dim3(256), 0, st, ds->d_dataT, Tn, t0, (int)len,
+                               (int)N, dD);
+            D = dD;
+        }
+        NHP_HIP(ctx, hipGetLastError());
+        gemm_args g1{};
+        g1.A = G; g1.lda = ldg; g1.B = u.E; g1.ldb = K; g1.M = (int)len; g1.N = (int)N; g1.K = (int)K; g1.k_chunk = (int)K;
+        g1.base = u.e0; g1.dataT = D; g1.out = dR; g1.partials = dcolp;
+        launch_gemm<true, EPI_VB_Z>(g1, 1, st, bm);
+        NHP_HIP(ctx, hipGetLastError());
+        gemm_args g2{};
+        g2.A = G; g2.lda = ldg; g2.B = dR; g2.ldb = (size_t)len; g2.M = (int)K; g2.N = (int)N; g2.K = (int)len; g2.k_chunk = k_chunk;
+        g2.out = dslab;
+        launch_gemm<false, EPI_SLAB>(g2, splits, st);
+        NHP_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_svi_baseline, dim3((unsigned)((N + 63) / 64)), dim3(256), 0, st, (int)N, row_blocks, dcolp, u.e0,
+                           alpha0, beta0, (double)T * dt, (double)nb, rho, u.av, u.bv);
+        hipLaunchKernelGGL(k_netvb_finish<true>, dim3(link_blocks), dim3(256), 0, st, (int)N, (int)B, splits, dslab, u.E, ds->d_colsum,
+                           kappa0, nu0, kappa1, nu1, gamma, (double)nb, rho, (int)net_kind, prior, u.netp, u.kv0, u.nv0, u.kv1, u.nv1,
+                           u.gv, u.rho, u.part);
+        if (net_kind)
+            hipLaunchKernelGGL(k_netvb_network<true>, dim3(1), dim3(256), 0, st, (int)link_blocks, u.part, net_alpha, net_beta, rho, u.netp);
+        NHP_HIP(ctx, hipGetLastError());
+    }
+    return netvb_download(ctx, st, u, h, N, B, net_kind, net_stage);
 }
 
 // DiscreteLogGaussianCoxProcess(x, λ, Σ, m, dt) as the baseline of this dataset's process (src/baselines.jl:461-509):

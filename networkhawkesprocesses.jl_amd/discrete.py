@@ -314,6 +314,17 @@ class DiscreteNetworkHawkesProcess(DiscreteHawkesProcess):
         return np.concatenate([self.network.params(), self.baseline.params(), self.weights.params(),
                                self.impulses.params(), self.adjacency_matrix.ravel(order="F")])
 
+    def link_probabilities(self):
+        """q(A = 1): the weights' ρv, or link_probability(network) while no update has run."""
+        ρv = getattr(self.weights, "ρv", None)
+        return self.network.link_probability() if ρv is None else ρv
+
+    def variational_params(self):
+        """[baseline; κv0; νv0; κv1; νv1; γv; vec(ρv); αv; βv] -- the last two for a Bernoulli network only"""
+        net = [np.array([self.network.αv, self.network.βv])] if hasattr(self.network, "αv") else []
+        return np.concatenate([self.baseline.variational_params(), self.weights.variational_params(),
+                               self.impulses.variational_params(), self.link_probabilities().ravel(order="F")] + net)
+
 
 def convolve(process, data, ctx=None, fetch=False):
     """convolve(process, data) -- src/discrete.jl:146-151.  Returns a DiscreteDataset whose device
@@ -1050,19 +1061,86 @@ def disc_mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, 
     return res
 
 
+def _vb_kind(process, what):
+    """'standard' or 'network' for the models the variational drivers are built for; NotImplementedError naming the
+    part that is not."""
+    from .components import BernoulliNetworkModel, DenseNetworkModel, SparseWeightModel
+    if isinstance(process, DiscreteNetworkHawkesProcess):
+        if not isinstance(process.weights, SparseWeightModel):
+            raise NotImplementedError(f"{what}: a DiscreteNetworkHawkesProcess needs a SparseWeightModel (weights: "
+                                      f"{type(process.weights).__name__} has no spike-and-slab parameters)")
+        if not isinstance(process.network, (DenseNetworkModel, BernoulliNetworkModel)):
+            raise NotImplementedError(f"{what}: network VB is built for DenseNetworkModel and BernoulliNetworkModel (network: "
+                                      f"{type(process.network).__name__} has no variational update)")
+        kind = "network"
+    elif (isinstance(process, DiscreteStandardHawkesProcess) and isinstance(process.weights, DenseWeightModel)
+          and not isinstance(process.weights, SparseWeightModel)):
+        kind = "standard"
+    else:
+        raise NotImplementedError(f"{what} exists for DiscreteStandardHawkesProcess + DenseWeightModel and for "
+                                  "DiscreteNetworkHawkesProcess + SparseWeightModel (sparse weights on a standard process "
+                                  "have no network to draw links from: SURVEY D6)")
+    if not isinstance(process.baseline, DiscreteHomogeneousProcess):
+        raise NotImplementedError(f"{what} is defined for DiscreteHomogeneousProcess baselines only (baseline: "
+                                  "src/baselines.jl:444-456)")
+    return kind
+
+
+class _NetVB:
+    """The buffers nhp_disc_netvb_run / nhp_disc_netsvi_run update in place, and the way back into the process."""
+
+    def __init__(self, process):
+        from .components import BernoulliNetworkModel
+        b, w, imp, net = process.baseline, process.weights, process.impulses, process.network
+        self.process, self.N, self.B = process, process.ndims(), imp.nbasis()
+        self.kind = 1 if isinstance(net, BernoulliNetworkModel) else 0
+        self.av, self.bv = _lib.f64(b.αv).copy(), _lib.f64(b.βv).copy()
+        self.k0, self.n0 = _lib.colmajor(w.κv0).copy(), _lib.colmajor(w.νv0).copy()
+        self.k1, self.n1 = _lib.colmajor(w.κv1).copy(), _lib.colmajor(w.νv1).copy()
+        self.gv = _lib.colmajor(imp.γv).copy()
+        self.rho = _lib.colmajor(np.asarray(process.link_probabilities(), dtype=np.float64)).copy()
+        if self.rho.size != self.N * self.N:
+            raise ValueError("ρv must be an N x N matrix")
+        if self.kind and not np.all((self.rho >= 0.0) & (self.rho <= 1.0)):
+            raise DomainError("ρv: link probabilities must lie in [0, 1]")
+        self.na = C.c_double(net.αv if self.kind else 1.0)
+        self.nb = C.c_double(net.βv if self.kind else 1.0)
+        self.prior = (net.α, net.β) if self.kind else (1.0, 1.0)
+
+    def priors(self):
+        b, w, imp = self.process.baseline, self.process.weights, self.process.impulses
+        return (b.α0, b.β0, w.κ0, w.ν0, w.κ1, w.ν1, imp.γ, self.kind, self.prior[0], self.prior[1])
+
+    def pointers(self):
+        return tuple(_lib.dptr(x) for x in (self.av, self.bv, self.k0, self.n0, self.k1, self.n1, self.gv, self.rho)) + (
+            C.cast(C.byref(self.na), C.POINTER(C.c_double)), C.cast(C.byref(self.nb), C.POINTER(C.c_double)))
+
+    def store(self):
+        p, N, B = self.process, self.N, self.B
+        b, w, imp = p.baseline, p.weights, p.impulses
+        b.αv, b.βv = self.av, self.bv
+        w.κv0, w.νv0 = self.k0.reshape((N, N), order="F"), self.n0.reshape((N, N), order="F")
+        w.κv1, w.νv1 = self.k1.reshape((N, N), order="F"), self.n1.reshape((N, N), order="F")
+        w.ρv = self.rho.reshape((N, N), order="F")
+        imp.γv = self.gv.reshape((N, N, B), order="F")
+        if self.kind:
+            p.network.αv, p.network.βv = self.na.value, self.nb.value
+
+
 def update_(process, data, convolved, ctx=None, n_steps=1):
     """update!(process, data, convolved) -- src/discrete.jl:369-375: one mean-field step (or n_steps
     of them with the parameters resident on the device in between); the variational parameters of
-    baseline, weights and impulses are overwritten in place."""
-    from .components import SparseWeightModel
-    if (not isinstance(process, DiscreteStandardHawkesProcess) or not isinstance(process.weights, DenseWeightModel)
-            or isinstance(process.weights, SparseWeightModel)):
-        raise NotImplementedError("VB exists only for DiscreteStandardHawkesProcess + DenseWeightModel "
-                                  "(the reference's network / sparse variants are broken: SURVEY D6)")
-    if not isinstance(process.baseline, DiscreteHomogeneousProcess):
-        raise NotImplementedError("update! is defined for DiscreteHomogeneousProcess baselines only (src/baselines.jl:444-456)")
+    baseline, weights and impulses are overwritten in place.  For a DiscreteNetworkHawkesProcess with a
+    SparseWeightModel (src/discrete.jl:494-501, intended semantics: DESIGN §3.19) also weights.ρv and the Bernoulli
+    network's (αv, βv); process.adjacency_matrix is not touched."""
+    kind = _vb_kind(process, "update!")
     ctx = ctx or _lib.default_context()
     ds = _convolved(process, data, convolved, ctx)
+    if kind == "network":
+        st = _NetVB(process)
+        _lib.check(_lib.lib().nhp_disc_netvb_run(ctx.h, ds.h, process.dt, *st.priors(), n_steps, *st.pointers()), ctx.h)
+        st.store()
+        return process.variational_params()
     b, w, imp = process.baseline, process.weights, process.impulses
     N, B = process.ndims(), imp.nbasis()
     av, bv = _lib.f64(b.αv).copy(), _lib.f64(b.βv).copy()
@@ -1074,6 +1152,25 @@ def update_(process, data, convolved, ctx=None, n_steps=1):
     w.κv, w.νv = kv.reshape((N, N), order="F"), nv.reshape((N, N), order="F")
     imp.γv = gv.reshape((N, N, B), order="F")
     return process.variational_params()
+
+
+def variational_mean_(process):
+    """Set the process's parameters to the means of its variational factors: λ0 = αv/βv, θ = γv/Σ_b γv, W = κv/νv; for a
+    network process W = κv1/νv1 (the slab), A = (ρv > 0.5) and, for a Bernoulli network, ρ = αv/(αv + βv).  After it
+    disc_loglikelihood, disc_forecast and disc_residuals run on a VB fit."""
+    b, w, imp = process.baseline, process.weights, process.impulses
+    b.λ = np.asarray(b.αv, dtype=np.float64) / np.asarray(b.βv, dtype=np.float64)
+    g = np.asarray(imp.γv, dtype=np.float64)
+    imp.θ = g / g.sum(axis=2, keepdims=True)
+    if isinstance(process, DiscreteNetworkHawkesProcess):
+        _vb_kind(process, "variational_mean!")
+        w.W = np.asarray(w.κv1, dtype=np.float64) / np.asarray(w.νv1, dtype=np.float64)
+        process.adjacency_matrix = (np.asarray(process.link_probabilities()) > 0.5).astype(np.float64)
+        if hasattr(process.network, "αv"):
+            process.network.ρ = process.network.αv / (process.network.αv + process.network.βv)
+    else:
+        w.W = np.asarray(w.κv, dtype=np.float64) / np.asarray(w.νv, dtype=np.float64)
+    return process
 
 
 class VariationalInference:
@@ -1107,13 +1204,7 @@ def svi_(process, data, nsteps=1000, batch_bins=4096, delay=1.0, forgetting=0.6,
     convolution on the device (the same numbers).  trace_every = k runs chunks of k steps and appends
     variational_params(process) after each; 0 keeps only the final parameters.  svi_(..., step0=res.step) resumes a run
     exactly.  Returns a VariationalInference whose `step` counts steps (step0 included)."""
-    from .components import SparseWeightModel
-    if (not isinstance(process, DiscreteStandardHawkesProcess) or not isinstance(process.weights, DenseWeightModel)
-            or isinstance(process.weights, SparseWeightModel)):
-        raise NotImplementedError("SVI exists only for DiscreteStandardHawkesProcess + DenseWeightModel "
-                                  "(the reference's network / sparse variants are broken: SURVEY D6)")
-    if not isinstance(process.baseline, DiscreteHomogeneousProcess):
-        raise NotImplementedError("svi! is defined for DiscreteHomogeneousProcess baselines only (src/baselines.jl:444-456)")
+    kind = _vb_kind(process, "svi!")
     T = data.T if isinstance(data, DiscreteDataset) else np.asarray(data).shape[1]
     nsteps, batch_bins, step0, trace_every = int(nsteps), int(batch_bins), int(step0), int(trace_every)
     if nsteps < 0 or step0 < 0 or trace_every < 0:
@@ -1144,13 +1235,17 @@ def svi_(process, data, nsteps=1000, batch_bins=4096, delay=1.0, forgetting=0.6,
     else:
         ds = data if isinstance(data, DiscreteDataset) and data.B == B else convolve(process, data, ctx)
         ph, L = None, 0
-    av, bv = _lib.f64(b.αv).copy(), _lib.f64(b.βv).copy()
-    kv, nv, gv = _lib.colmajor(w.κv).copy(), _lib.colmajor(w.νv).copy(), _lib.colmajor(imp.γv).copy()
+    if kind == "network":                         # the same loop on nhp_disc_netsvi_run: four weight tables, ρv, the network
+        net = _NetVB(process)
+        store = net.store
+    else:
+        av, bv = _lib.f64(b.αv).copy(), _lib.f64(b.βv).copy()
+        kv, nv, gv = _lib.colmajor(w.κv).copy(), _lib.colmajor(w.νv).copy(), _lib.colmajor(imp.γv).copy()
 
-    def store():                                  # column-major views of the library's buffers, as update_ keeps them: no
-        b.αv, b.βv = av, bv                       # transposing copy here or at the next call (a later chunk updates them in place)
-        w.κv, w.νv = kv.reshape((N, N), order="F"), nv.reshape((N, N), order="F")
-        imp.γv = gv.reshape((N, N, B), order="F")
+        def store():                              # column-major views of the library's buffers, as update_ keeps them: no
+            b.αv, b.βv = av, bv                   # transposing copy here or at the next call (a later chunk updates them in place)
+            w.κv, w.νv = kv.reshape((N, N), order="F"), nv.reshape((N, N), order="F")
+            imp.γv = gv.reshape((N, N, B), order="F")
 
     res = VariationalInference()
     res.step = step0
@@ -1158,10 +1253,15 @@ def svi_(process, data, nsteps=1000, batch_bins=4096, delay=1.0, forgetting=0.6,
     while done < nsteps:
         n = min(trace_every, nsteps - done) if trace_every else nsteps
         blk = None if blocks is None else blocks[done:done + n].ctypes.data_as(C.POINTER(C.c_int32))
-        _lib.check(_lib.lib().nhp_disc_svi_run(ctx.h, ds.h, process.dt, b.α0, b.β0, w.κ, w.ν, imp.γ, batch_bins, float(delay),
-                                               float(forgetting), int(seed), step0 + done, n, blk, _lib.dptr(ph), L, B,
-                                               _lib.dptr(av), _lib.dptr(bv), _lib.dptr(kv), _lib.dptr(nv), _lib.dptr(gv)),
-                   ctx.h)
+        if kind == "network":
+            _lib.check(_lib.lib().nhp_disc_netsvi_run(ctx.h, ds.h, process.dt, *net.priors(), batch_bins, float(delay),
+                                                      float(forgetting), int(seed), step0 + done, n, blk, _lib.dptr(ph), L, B,
+                                                      *net.pointers()), ctx.h)
+        else:
+            _lib.check(_lib.lib().nhp_disc_svi_run(ctx.h, ds.h, process.dt, b.α0, b.β0, w.κ, w.ν, imp.γ, batch_bins, float(delay),
+                                                   float(forgetting), int(seed), step0 + done, n, blk, _lib.dptr(ph), L, B,
+                                                   _lib.dptr(av), _lib.dptr(bv), _lib.dptr(kv), _lib.dptr(nv), _lib.dptr(gv)),
+                       ctx.h)
         done += n
         res.step = step0 + done
         store()
@@ -1179,6 +1279,7 @@ def vb_(process, data, max_steps=1000, Δx_thresh=1e-6, Δq_thresh=1e-2, verbose
     Like the reference (whose convergence test is commented out, :163-176) it runs max_steps updates.
     keep_trace=False runs them back to back on the device and records only the final parameters
     (the reference's per-step trace is 2N + N²B + 2N² doubles a step)."""
+    _vb_kind(process, "vb!")
     ctx = ctx or _lib.default_context()
     start = time.time()
     convolved = convolve(process, data, ctx)

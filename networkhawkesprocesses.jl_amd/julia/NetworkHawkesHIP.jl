@@ -891,6 +891,90 @@ function svi!(p::NHP.DiscreteStandardHawkesProcess, data::Matrix{Int64}; nsteps:
     return res
 end
 
+# --- update! / vb! / svi! for DiscreteNetworkHawkesProcess + SparseWeightModel (nhp_disc_netvb_run, nhp_disc_netsvi_run) ---
+# The reference's methods throw on their wiring (src/discrete.jl:494-501, src/weights.jl:141-173); the formulas are its own
+# (include/nhp.h).  Its SparseWeightModel has no field for q(A = 1), so ρv travels as an N x N matrix the caller keeps: it
+# is updated in place, `nothing` starts from link_probability(network).  DenseNetworkModel gives ρv ≡ 1; the Bernoulli
+# network's αv, βv are updated in place; other networks and baselines are refused by the library.
+net_kind(n::NHP.DenseNetworkModel) = Int32(0)
+net_kind(n::NHP.BernoulliNetworkModel) = Int32(1)
+net_kind(n) = error("network VB is built for DenseNetworkModel and BernoulliNetworkModel")
+net_prior(n::NHP.BernoulliNetworkModel) = (Float64(n.α), Float64(n.β), Ref(Float64(n.αv)), Ref(Float64(n.βv)))
+net_prior(n) = (1.0, 1.0, Ref(1.0), Ref(1.0))
+function net_store!(p::NHP.DiscreteNetworkHawkesProcess, αv, βv, κ0, ν0, κ1, ν1, γv, na, nb)
+    b, w, imp = p.baseline, p.weights, p.impulses
+    b.αv, b.βv, w.κv0, w.νv0, w.κv1, w.νv1, imp.γv = copy(αv), copy(βv), copy(κ0), copy(ν0), copy(κ1), copy(ν1), copy(γv)
+    p.network isa NHP.BernoulliNetworkModel && ((p.network.αv, p.network.βv) = (na[], nb[]))
+end
+net_params(p, ρv, na, nb) = p.network isa NHP.BernoulliNetworkModel ?
+    [NHP.variational_params(p.baseline); NHP.variational_params(p.weights); NHP.variational_params(p.impulses); vec(ρv); na[]; nb[]] :
+    [NHP.variational_params(p.baseline); NHP.variational_params(p.weights); NHP.variational_params(p.impulses); vec(ρv)]
+
+function update!(p::NHP.DiscreteNetworkHawkesProcess, data, c::Convolved; ρv::Union{Nothing,Matrix{Float64}}=nothing,
+                 n_steps::Integer=1, ctx=context())
+    p.weights isa NHP.SparseWeightModel || error("network update! needs a SparseWeightModel")
+    b, w, imp = p.baseline, p.weights, p.impulses
+    ρ = ρv === nothing ? Matrix{Float64}(NHP.link_probability(p.network)) : ρv
+    αv, βv, γv = Vector{Float64}(b.αv), Vector{Float64}(b.βv), Array{Float64,3}(imp.γv)
+    κ0, ν0, κ1, ν1 = Matrix{Float64}(w.κv0), Matrix{Float64}(w.νv0), Matrix{Float64}(w.κv1), Matrix{Float64}(w.νv1)
+    α, β, na, nb = net_prior(p.network)
+    check(ccall((:nhp_disc_netvb_run, libnhp), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, Float64, Float64, Float64, Int32, Float64, Float64, Int32,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ref{Float64}, Ref{Float64}),
+        ctx.h, c.h, p.dt, b.α0, b.β0, w.κ0, w.ν0, w.κ1, w.ν1, imp.γ, net_kind(p.network), α, β, n_steps,
+        αv, βv, κ0, ν0, κ1, ν1, γv, ρ, na, nb), ctx.h)
+    net_store!(p, αv, βv, κ0, ν0, κ1, ν1, γv, na, nb)
+    (net_params(p, ρ, na, nb), ρ)
+end
+
+function vb!(p::NHP.DiscreteNetworkHawkesProcess, data::Matrix{Int64}; max_steps::Int64=1_000, Δx_thresh=1e-6, Δq_thresh=1e-2,
+             verbose=false, ρv::Union{Nothing,Matrix{Float64}}=nothing, ctx=context())
+    convolved = convolve(p, data; ctx=ctx)
+    res = NHP.VariationalInference(p)
+    ρ = ρv === nothing ? Matrix{Float64}(NHP.link_probability(p.network)) : ρv
+    start_time = time()
+    while res.step < max_steps
+        push!(res.trace, update!(p, data, convolved; ρv=ρ, ctx=ctx)[1])
+        res.step += 1
+    end
+    res.elapsed = time() - start_time
+    return res, ρ
+end
+
+# resident mode; the keywords are svi!'s for the standard process
+function svi!(p::NHP.DiscreteNetworkHawkesProcess, data::Matrix{Int64}; nsteps::Integer=1_000, batch_bins::Integer=4096, delay=1.0,
+              forgetting=0.6, seed::Integer=0, blocks=nothing, step0::Integer=0, ρv::Union{Nothing,Matrix{Float64}}=nothing,
+              ctx=context())
+    p.weights isa NHP.SparseWeightModel || error("network svi! needs a SparseWeightModel")
+    N, T = size(data)
+    nb_ = cld(T, min(batch_bins, T))
+    blk = blocks === nothing ? nothing : Vector{Int32}(blocks)
+    blk === nothing || (length(blk) >= nsteps && all(0 .<= blk .< nb_)) || throw(ArgumentError("blocks: nsteps indices in [0, $nb_) are required"))
+    c = convolve(p, data; ctx=ctx)
+    b, w, imp = p.baseline, p.weights, p.impulses
+    ρ = ρv === nothing ? Matrix{Float64}(NHP.link_probability(p.network)) : ρv
+    αv, βv, γv = Vector{Float64}(b.αv), Vector{Float64}(b.βv), Array{Float64,3}(imp.γv)
+    κ0, ν0, κ1, ν1 = Matrix{Float64}(w.κv0), Matrix{Float64}(w.νv0), Matrix{Float64}(w.κv1), Matrix{Float64}(w.νv1)
+    α, β, na, nb = net_prior(p.network)
+    res = NHP.VariationalInference(p)
+    bp = blk === nothing ? Ptr{Int32}(C_NULL) : pointer(blk)
+    start_time = time()
+    GC.@preserve blk c check(ccall((:nhp_disc_netsvi_run, libnhp), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, Float64, Float64, Float64, Int32, Float64, Float64,
+         Int64, Float64, Float64, UInt64, Int64, Int32, Ptr{Int32}, Ptr{Float64}, Int32, Int32,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ref{Float64}, Ref{Float64}),
+        ctx.h, c.h, p.dt, b.α0, b.β0, w.κ0, w.ν0, w.κ1, w.ν1, imp.γ, net_kind(p.network), α, β,
+        batch_bins, delay, forgetting, seed % UInt64, step0, nsteps, bp, Ptr{Float64}(C_NULL), 0, 0,
+        αv, βv, κ0, ν0, κ1, ν1, γv, ρ, na, nb), ctx.h)
+    net_store!(p, αv, βv, κ0, ν0, κ1, ν1, γv, na, nb)
+    res.step = step0 + nsteps
+    push!(res.trace, net_params(p, ρ, na, nb))
+    res.elapsed = time() - start_time
+    return res, ρ
+end
+
 # --- mle!(process::DiscreteStandardHawkesProcess, data; optimizer=BFGS, verbose=false, f_abstol=1e-6, regularize=false,
 #          guess=nothing, max_increase_steps=3) -> MaximumLikelihood   src/discrete.jl:211-296 ---------------------------
 # Parameter vector [λ0; vec(W .* θ)] (params / params!, src/discrete.jl:174-201).  regularize=true calls the reference's

@@ -748,7 +748,7 @@ nhp_status nhp_cont_loglik_grad_allreduce(nhp_ctx *ctx, nhp_comm *comm, const nh
 /* BASELINE config 5: the per-chain posterior summaries (the running sums of nhp_cont_model_moments_*, still on each
  * rank's device) all-gathered over RCCL: sum_all / sumsq_all [world * len] (rank r at r*len), counts [world],
  * rho_all [world * 3] (ρ, Σρ, Σρ² of nhp_cont_model_get_rho; zeros for a model without a device-side ρ).
- * NHP_ENOTIMPL for a model with a block network: its K² + K sums are not part of the exchange. */
+ * NHP_ENOTIMPL for a model with a block network or a latent distance network: their sums are not part of the exchange. */
 nhp_status nhp_gather_moments(nhp_ctx *ctx, nhp_comm *comm, const nhp_cont_model *model, double *sum_all, double *sumsq_all,
                               int64_t len, int64_t *counts, double *rho_all);
 
@@ -821,6 +821,55 @@ nhp_status nhp_cont_model_set_sbm_labels_every(nhp_ctx *ctx, nhp_cont_model *mod
  * PCIe.  NHP_ENOTIMPL on a column shard (the labels need every column).  nhp_cont_mcmc_run takes this step for a model
  * with a block network attached and ignores net_alpha / net_beta. */
 nhp_status nhp_cont_sbm_step(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *model, uint64_t seed, uint64_t step);
+
+/* ---- LatentDistanceNetworkModel (csrc/latent.hip; the other empty stub at the end of the reference's src/networks.jl) ----
+ * N nodes in D latent dimensions: z_n ~ N(0, σ² I), b ~ N(μb, σb²), η[p,c] = b - ‖z_p - z_c‖², A[p,c] ~ Bernoulli(1/(1 + exp(-η[p,c])))
+ * for all N² entries (the diagonal has η = b).  Positions are N x D column-major (z_n[d] at n + N·d); A is N x N column-major.
+ * log p(A | z, b) = Σ A·η - softplus(η), softplus(η) = max(η, 0) + log1p(exp(-|η|)).
+ * resample!(network, A) = a sweep over the positions n = 0..N-1, each by elliptical slice sampling given the others, on
+ *   L_n(z) = Σ_{j≠n} s_nj·η_j - 2·softplus(η_j), η_j = b - ‖z - z_j‖², s_nj = A[n,j] + A[j,n]
+ * with the prior ellipse ν ~ N(0, σ² I), then elliptical slice sampling of b - μb (prior N(0, σb²)) on the full log-likelihood.
+ * A slice step follows the reference's elliptical_slice (src/baselines.jl:287-326): threshold L(current) + log u0, θ1 = 2π·u1,
+ * bracket [θ1 - 2π, θ1], a rejected θ < 0 becomes the lower end and any other the upper end, θ_k uniform in the bracket by
+ * u_k, candidate x·cos θ + ν·sin θ, the first with L >= threshold is accepted, 100 attempts; where the reference throws after
+ * them the value is kept and the event counted (`exhausted`).
+ * Errors: NHP_EINVAL for N < 1 or D < 1; NHP_ENOTIMPL for D > 8, N > 8192 or 8·N·D + 24·ceil(N/32) + 1576 bytes > 160 KiB (the
+ * position sweep keeps every position in LDS); NHP_EDOMAIN for a non-finite position or offset, sigma or
+ * sigma_b <= 0.
+ *
+ * Stand-alone entries on a host A (synchronous). */
+/* out [1 + N]: log p(A | z, b), then the N conditional terms L_n at the current state. */
+nhp_status nhp_latent_loglik(nhp_ctx *ctx, const double *A, int32_t n_nodes, int32_t n_dims, const double *z, double b, double *out);
+/* n_sweeps position sweeps, each followed by the offset update when do_offset is set; n_sweeps = 0 with do_offset: the
+ * offset update alone, once.  A sweep has N + 1 slice steps (the offset's is the last; with n_sweeps = 0 it is the only one).
+ * draws (nullable: the kernel's own Philox stream keyed (seed, step), csrc/nhp_rng.h) holds the stream of every step: a
+ * node's step [D standard normals; u0; u1..u100], the offset's step [1 normal; u0; u1..u100], N·(D + 101) + 102 doubles per
+ * sweep (102 with n_sweeps = 0); the slots of an offset step that does not run are read by nothing.  Outputs, all nullable:
+ * draws_used returns the stream; attempts [sweeps·(N + 1)] the index 1..100 of the accepted candidate (101: all 100 failed,
+ * 0: the step did not run); ll_trace [sweeps·(N + 1)·101] per step the threshold, then L at the candidates 1..attempts
+ * (entries after the accepted one are unspecified: a batch may have evaluated more); exhausted the number of steps that
+ * used up their attempts.  Bit-reproducible for a fixed draw stream. */
+nhp_status nhp_latent_resample(nhp_ctx *ctx, const double *A, int32_t n_nodes, int32_t n_dims, double *z_inout, double *b_inout,
+                               double sigma, double mu_b, double sigma_b, const double *draws, uint64_t seed, uint64_t step,
+                               int32_t n_sweeps, int32_t do_offset, double *draws_used, int32_t *attempts, double *ll_trace,
+                               int64_t *exhausted);
+/* The model's state kept next to the continuous model on the device.  _set_latent uploads (z, b) and the priors (the first
+ * call allocates; it detaches a block network, as _set_sbm detaches a latent distance network and _set_rho both).
+ * _get_latent returns them (every output nullable) with the running sums of the kept steps (nhp_cont_model_moments_accumulate
+ * / _reset carry them): sums = [Σb; Σb²], p_sum [N*N] = Σ 1/(1 + exp(-η[p,c])) -- positions are identified only up to
+ * rotation, reflection and sign, so the link probabilities are summed and not the positions -- and the count of exhausted
+ * slice steps since _set_latent. */
+nhp_status nhp_cont_model_set_latent(nhp_ctx *ctx, nhp_cont_model *model, int32_t n_dims, const double *z, double b, double sigma,
+                                     double mu_b, double sigma_b);
+nhp_status nhp_cont_model_get_latent(nhp_ctx *ctx, const nhp_cont_model *model, double *z, double *b, double *sums, double *p_sum,
+                                     int64_t *exhausted);
+/* The position sweep runs at the chain steps that are multiples of `every` (default 1); the offset update at every step. */
+nhp_status nhp_cont_model_set_latent_positions_every(nhp_ctx *ctx, nhp_cont_model *model, int32_t every);
+/* One network step of mcmc! under the latent distance model: the link-probability matrix from the current (z, b), the
+ * adjacency sweep (the Philox key of nhp_cont_network_step), then resample!(network, A) with its own stream keyed (seed, step).
+ * Asynchronous; nothing crosses PCIe.  NHP_ENOTIMPL on a column shard (the positions need every column).  nhp_cont_mcmc_run
+ * takes this step for a model with a latent distance network attached and ignores net_alpha / net_beta. */
+nhp_status nhp_cont_latent_step(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *model, uint64_t seed, uint64_t step);
 
 /* mle!(process, data; f_abstol, guess) (src/continuous.jl:144-198) with the optimizer's state on the device: minimises
  * -loglikelihood(process, data) over params(process) = [λ0 | grid intensities; θ | μ, τ; W] on the reference's box

@@ -7,7 +7,7 @@ Julia's `f!` becomes `f_`.
 """
 from ._lib import Context, DomainError, NhpError, default_context  # noqa: F401
 from .components import (BernoulliNetworkModel, DenseNetworkModel, DenseWeightModel, SparseWeightModel,  # noqa: F401
-                         StochasticBlockNetworkModel,
+                         StochasticBlockNetworkModel, LatentDistanceNetworkModel,
                          ExponentialImpulseResponse, GaussianProcess, HomogeneousProcess,
                          LogGaussianCoxProcess, LogitNormalImpulseResponse, OrnsteinUhlenbeckKernel,
                          PeriodicKernel, SquaredExponentialKernel, split_extract)

@@ -85,6 +85,12 @@ def _declare(lib):
     f("nhp_cont_model_get_sbm", i32, _vp, _vp, _vp, _dp, _dp, _dp, _vp)
     f("nhp_cont_model_set_sbm_labels_every", i32, _vp, _vp, i32)
     f("nhp_cont_sbm_step", i32, _vp, _vp, _vp, u64, u64)
+    f("nhp_latent_loglik", i32, _vp, _dp, i32, i32, _dp, dbl, _dp)
+    f("nhp_latent_resample", i32, _vp, _dp, i32, i32, _dp, _dp, dbl, dbl, dbl, _dp, u64, u64, i32, i32, _dp, _vp, _dp, _vp)
+    f("nhp_cont_model_set_latent", i32, _vp, _vp, i32, _dp, dbl, dbl, dbl, dbl)
+    f("nhp_cont_model_get_latent", i32, _vp, _vp, _dp, _dp, _dp, _dp, _vp)
+    f("nhp_cont_model_set_latent_positions_every", i32, _vp, _vp, i32)
+    f("nhp_cont_latent_step", i32, _vp, _vp, _vp, u64, u64)
     f("nhp_cont_mcmc_run", i32, _vp, _vp, _vp, _vp, C.POINTER(GibbsPriors), dbl, dbl, u64, u64, i64, i64)
     f("nhp_disc_mle_run", i32, _vp, _vp, dbl, dbl, dbl, dbl, i32, _dp, i64, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
       C.POINTER(C.c_int32))

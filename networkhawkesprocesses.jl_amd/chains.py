@@ -94,16 +94,16 @@ def run_chains(make_process, data, n_chains, nsteps, base_seed=0, burn=0, ctx=No
             ds = device_dataset(process, data, ctx)         # uploaded once per GPU, shared by its chains
         # posterior summaries accumulate on the device when the whole sweep runs there (homogeneous baseline): no
         # per-step transfer of params(process) (33.5 MB at N = 1024); otherwise from the kept samples
-        from .components import HomogeneousProcess, StochasticBlockNetworkModel
+        from .components import HomogeneousProcess, LatentDistanceNetworkModel, StochasticBlockNetworkModel
         on_device = isinstance(process.baseline, HomogeneousProcess) and mcmc_kwargs.get("device_draws", True)
         if on_device:
             kw = {a: v for a, v in mcmc_kwargs.items() if a not in ("keep_samples", "moments", "burn")}
             res = mcmc_(process, ds, nsteps=nsteps, seed=chain_seed(base_seed, k), ctx=ctx, keep_samples=False,
                         moments=True, burn=burn, **kw)
             local[k] = {"n": np.array([float(res.n)]), "mean": res.mean, "m2": res.m2}
-            # (a block network's K² + K sums are not part of nhp_gather_moments: its chains' summaries, complete in
-            #  res.mean / res.m2, take the host exchange below)
-            if not isinstance(getattr(process, "network", None), StochasticBlockNetworkModel):
+            # (a block network's K² + K sums and a latent distance network's sums are not part of nhp_gather_moments: their
+            #  chains' summaries, complete in res.mean / res.m2, take the host exchange below)
+            if not isinstance(getattr(process, "network", None), (StochasticBlockNetworkModel, LatentDistanceNetworkModel)):
                 device_models[k] = (process, process._dev)
         else:
             res = mcmc_(process, ds, nsteps=nsteps, seed=chain_seed(base_seed, k), ctx=ctx, **mcmc_kwargs)
@@ -121,13 +121,16 @@ def gather_device_summaries(device_models, n_chains, ctx, comm):
     from . import _lib
     from .inference import _moments_in_params_order, moments_length
     from .continuous import ContinuousNetworkHawkesProcess
-    from .components import StochasticBlockNetworkModel
+    from .components import LatentDistanceNetworkModel, StochasticBlockNetworkModel
     world, rank = comm.world, comm.rank
     out = {}
     for slot, k in enumerate(sorted(device_models)):
         process, model = device_models[k]
         if isinstance(getattr(process, "network", None), StochasticBlockNetworkModel):
             raise NotImplementedError("gather_device_summaries: a block network's sums of ρ and π are not gathered on the device")
+        if isinstance(getattr(process, "network", None), LatentDistanceNetworkModel):
+            raise NotImplementedError("gather_device_summaries: a latent distance network's sums of b and of the link probabilities "
+                                      "are not gathered on the device")
         L = moments_length(process)
         s, q = np.empty((world, L)), np.empty((world, L))
         counts, rho = np.empty(world, dtype=np.int64), np.empty((world, 3))

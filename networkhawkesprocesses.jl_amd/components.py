@@ -508,6 +508,74 @@ class StochasticBlockNetworkModel(Network):
         return self.params()
 
 
+class LatentDistanceNetworkModel(Network):
+    """LatentDistanceNetworkModel(nnodes, ndims, z, b; σ, μb, σb) -- the reference names the model and leaves it an empty
+    stub (src/networks.jl, last lines).  Nodes have positions in a latent space and a link is the likelier the closer
+    its two nodes are:
+
+        z_n ~ N(0, σ² I_D),  b ~ N(μb, σb²),  A[p,c] ~ Bernoulli(1 / (1 + exp(-(b - ‖z_p - z_c‖²))))
+
+    for all N² entries (the diagonal is counted, with the logit b).  params() is [b]; the positions `z` (N x D) are
+    latent state, not parameters.  Positions are identified only up to rotation, reflection and sign, so over a chain
+    the link-probability matrix is the summary to average, not the positions."""
+
+    MAX_DIMS = 8
+
+    def __init__(self, nnodes, ndims=2, z=None, b=0.0, σ=1.0, μb=0.0, σb=1.0):
+        self.nnodes, self.ndims = int(nnodes), int(ndims)
+        if self.nnodes < 1:
+            raise ValueError("nnodes must be positive")
+        if self.ndims < 1 or self.ndims > self.MAX_DIMS:
+            raise ValueError(f"ndims must lie in 1..{self.MAX_DIMS}")
+        self.σ, self.μb, self.σb, self.b = float(σ), float(μb), float(σb), float(b)
+        if not (self.σ > 0 and self.σb > 0 and np.isfinite([self.σ, self.σb, self.μb]).all()):
+            raise _lib.DomainError("the priors need σ, σb > 0 and a finite μb")
+        self.z = (np.zeros((self.nnodes, self.ndims)) if z is None
+                  else np.array(z, dtype=np.float64).reshape((self.nnodes, self.ndims)))
+        if not (np.all(np.isfinite(self.z)) and np.isfinite(self.b)):
+            raise _lib.DomainError("positions and offset must be finite")
+
+    def params(self):
+        return np.array([self.b])
+
+    def link_probability(self):
+        diff = self.z[:, None, :] - self.z[None, :, :]
+        with np.errstate(over="ignore"):
+            return 1.0 / (1.0 + np.exp(np.sum(diff * diff, axis=2) - self.b))
+
+    def rand(self, rng):
+        """Positions from their prior, then A from the link probabilities (b stays)."""
+        self.z = self.σ * rng.standard_normal((self.nnodes, self.ndims))
+        return (rng.uniform(size=(self.nnodes, self.nnodes)) < self.link_probability()).astype(np.float64)
+
+    def loglikelihood(self, A, ctx=None, conditionals=False):
+        """log p(A | z, b) = Σ A·η - softplus(η) over all N² entries, from the GPU; with `conditionals` also the N terms
+        L_n = Σ_{j≠n} (A[n,j] + A[j,n])·η_nj - 2·softplus(η_nj) the position sweep slices on."""
+        ctx = ctx or _lib.default_context()
+        out = np.empty(self.nnodes + 1)
+        z = _lib.colmajor(self.z)
+        _lib.check(_lib.lib().nhp_latent_loglik(ctx.h, _lib.dptr(_lib.colmajor(A)), self.nnodes, self.ndims, _lib.dptr(z), self.b,
+                                                _lib.dptr(out)), ctx.h)
+        return (float(out[0]), out[1:]) if conditionals else float(out[0])
+
+    def resample_(self, A, rng, seed=None, step=0, ctx=None, positions=True):
+        """resample!(network, A): one elliptical-slice sweep over the positions (node after node, each given the current
+        positions of all others; skipped with positions=False), then an elliptical-slice update of b -- all on the GPU
+        (csrc/latent.hip), keyed (seed, step).  Without a seed one is drawn from `rng`.  `self.exhausted` counts the
+        slice steps of this call that used up their 100 attempts and kept their value."""
+        import ctypes as C
+        ctx = ctx or _lib.default_context()
+        if seed is None:
+            seed = int(rng.integers(0, 2 ** 63))
+        z = _lib.colmajor(self.z).copy()
+        b, ex = C.c_double(self.b), C.c_int64(0)
+        _lib.check(_lib.lib().nhp_latent_resample(ctx.h, _lib.dptr(_lib.colmajor(A)), self.nnodes, self.ndims, _lib.dptr(z), C.byref(b),
+                                                  self.σ, self.μb, self.σb, None, seed, step, 1 if positions else 0, 1, None, None,
+                                                  None, C.byref(ex)), ctx.h)
+        self.z, self.b, self.exhausted = z.reshape((self.nnodes, self.ndims), order="F"), b.value, int(ex.value)
+        return self.params()
+
+
 # ------------------------------------------------------------------------------ parameter vector
 ParamLayout = collections.namedtuple("ParamLayout", "baseline impulses weights adjacency")
 

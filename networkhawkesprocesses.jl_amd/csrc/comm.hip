@@ -219,6 +219,11 @@ extern "C" nhp_status nhp_gather_moments(nhp_ctx *ctx, nhp_comm *comm, const nhp
         nhp_set_error(ctx, "gather_moments: the sums of a block network's rho and pi are not gathered (nhp_cont_model_get_sbm per chain)");
         return NHP_ENOTIMPL;
     }
+    if (m->latent) {
+        nhp_set_error(ctx, "gather_moments: the sums of a latent distance network's offset and link probabilities are not gathered "
+                           "(nhp_cont_model_get_latent per chain)");
+        return NHP_ENOTIMPL;
+    }
     if (len != m->mom_len) { nhp_set_error(ctx, "Parameter vector length does not match model parameter length."); return NHP_ESHAPE; }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t w = (size_t)comm->world, L = (size_t)len;

@@ -675,6 +675,7 @@ extern "C" nhp_status nhp_cont_model_set_rho(nhp_ctx *ctx, nhp_cont_model *m, do
     if (!(rho >= 0.0 && rho <= 1.0)) { nhp_set_error(ctx, "link probability must lie in [0, 1]"); return NHP_EDOMAIN; }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_sbm_detach(ctx, m));                          // a scalar link probability replaces a block network the model had
+    NHP_TRY(nhp_latent_detach(ctx, m));                       // ... or a latent distance network
     NHP_TRY(ensure_rho(ctx, m));
     NHP_HIP(ctx, hipMemcpyAsync(m->d_rho, &rho, sizeof(double), hipMemcpyHostToDevice, ctx->main()));
     NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));          // `rho` is a stack value
@@ -746,11 +747,12 @@ extern "C" nhp_status nhp_cont_mcmc_run(nhp_ctx *ctx, nhp_comm *comm, const nhp_
 {
     if (!ctx || !m || !pr || n_steps < 0) return NHP_EINVAL;
     NHP_TRY(nhp_check_pair(ctx, ds, m));
-    if (m->has_A && !m->sbm && !m->d_rho) { nhp_set_error(ctx, "mcmc_run: set the network's link probability first (nhp_cont_model_set_rho)"); return NHP_EINVAL; }
+    if (m->has_A && !m->sbm && !m->latent && !m->d_rho) { nhp_set_error(ctx, "mcmc_run: set the network's link probability first (nhp_cont_model_set_rho)"); return NHP_EINVAL; }
     for (int64_t k = 0; k < n_steps; ++k) {
         const uint64_t step = step0 + (uint64_t)k;
         NHP_TRY(nhp_cont_gibbs_step(ctx, ds, m, pr, seed, step));           // (reports a sampler error one sweep late)
         if (m->has_A && m->sbm) NHP_TRY(nhp_cont_sbm_step(ctx, ds, m, seed, step));      // (net_alpha, net_beta: the model has its own priors)
+        else if (m->has_A && m->latent) NHP_TRY(nhp_cont_latent_step(ctx, ds, m, seed, step));
         else if (m->has_A) NHP_TRY(nhp_cont_network_step(ctx, comm, ds, m, net_alpha, net_beta, seed, step));
         if (burn >= 0 && (int64_t)step >= burn) NHP_TRY(nhp_cont_model_moments_accumulate(ctx, m));
     }

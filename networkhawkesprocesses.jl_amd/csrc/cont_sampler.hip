@@ -646,6 +646,7 @@ extern "C" nhp_status nhp_cont_model_moments_reset(nhp_ctx *ctx, nhp_cont_model 
     NHP_HIP(ctx, hipMemsetAsync(m->d_mom, 0, sizeof(double) * 2 * (size_t)len, ctx->main()));
     if (m->d_rho) NHP_HIP(ctx, hipMemsetAsync(m->d_rho + 1, 0, 2 * sizeof(double), ctx->main()));
     if (m->sbm) NHP_TRY(nhp_sbm_moments_reset(ctx, m));
+    if (m->latent) NHP_TRY(nhp_latent_moments_reset(ctx, m));
     m->mom_count = 0;
     return NHP_OK;
 }
@@ -661,6 +662,7 @@ extern "C" nhp_status nhp_cont_model_moments_accumulate(nhp_ctx *ctx, nhp_cont_m
                        (const double *)(m->has_A ? m->d_A : nullptr), m->mom_len, m->d_mom, m->d_rho);
     NHP_HIP(ctx, hipGetLastError());
     if (m->sbm) NHP_TRY(nhp_sbm_moments_accumulate(ctx, m));
+    if (m->latent) NHP_TRY(nhp_latent_moments_accumulate(ctx, m));
     ++m->mom_count;
     return NHP_OK;
 }

@@ -265,12 +265,23 @@ struct nhp_cont_model {
     // StochasticBlockNetworkModel on the device (sbm.hip: nhp_cont_model_set_sbm / nhp_cont_sbm_step): labels, ρ[K x K], π,
     // the link-probability matrix the adjacency sweep reads and the running sums of the kept steps; null: no block network
     struct nhp_sbm_state *sbm = nullptr;
+    // LatentDistanceNetworkModel on the device (latent.hip: nhp_cont_model_set_latent / nhp_cont_latent_step): positions, the
+    // offset b, the link-probability matrix and the running sums of the kept steps; null: no latent distance network.  At
+    // most one of sbm and latent is set.
+    struct nhp_latent_state *latent = nullptr;
 };
 // sbm.hip: release the block network's state; its share of nhp_cont_model_moments_reset / _accumulate (asynchronous)
 void nhp_sbm_free(nhp_cont_model *m);
 nhp_status nhp_sbm_detach(nhp_ctx *ctx, nhp_cont_model *m);      // set_rho: the model's network is no block model (any more)
 nhp_status nhp_sbm_moments_reset(nhp_ctx *ctx, nhp_cont_model *m);
 nhp_status nhp_sbm_moments_accumulate(nhp_ctx *ctx, nhp_cont_model *m);
+// sbm.hip: A [N x N doubles on the device] -> colb[n*W + w] bit j = A[32w + j, n], rowb[n*W + w] bit j = A[n, 32w + j] (asynchronous)
+nhp_status nhp_sbm_enqueue_pack(nhp_ctx *ctx, const double *d_A, int N, uint32_t *colb, uint32_t *rowb);
+// latent.hip: the same four for the latent distance network's state
+void nhp_latent_free(nhp_cont_model *m);
+nhp_status nhp_latent_detach(nhp_ctx *ctx, nhp_cont_model *m);
+nhp_status nhp_latent_moments_reset(nhp_ctx *ctx, nhp_cont_model *m);
+nhp_status nhp_latent_moments_accumulate(nhp_ctx *ctx, nhp_cont_model *m);
 
 // RCCL communicator of one rank (comm.hip); librccl.so.1 is dlopen'ed on first use
 struct nhp_comm {

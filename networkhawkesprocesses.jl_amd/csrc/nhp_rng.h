@@ -49,6 +49,13 @@ __device__ __forceinline__ double rng_cos_turn(uint32_t c)
 // The parent sampler draws nhp_philox_uniform(seed, step, event) and the adjacency sweeps
 // nhp_philox_uniform(seed ^ 0xBE5466CF34E90C6C | 0xAD7AC3117D15C0DE, step, entry): the label stream shares their
 // counters but not their key, so no two of the streams coincide.
+//
+// The latent distance network model (latent.hip) adds two, under (seed ^ constant, step).  Slice step g = sweep·(N+1) + n
+// of a resample (n = N: the offset's step) draws
+//   NHP_KEY_LAT_NORMAL   its standard normals: dev_normal element 8g + d, d < D (the offset: element 8g), attempt 0
+//   NHP_KEY_LAT_UNIFORM  u0 and the angles' u1..u100: nhp_philox_uniform(seed ^ constant, step, 101g + k), k = 0..100
+#define NHP_KEY_LAT_NORMAL 0x8979FB1BD1310BA6ull
+#define NHP_KEY_LAT_UNIFORM 0x3F84D5B5B5470917ull
 #define NHP_KEY_SBM_RHO 0xC0AC29B7C97C50DDull
 #define NHP_KEY_SBM_PI 0x2FFD72DBD01ADFB7ull
 #define NHP_KEY_SBM_LABEL 0xD1310BA698DFB5ACull

@@ -375,15 +375,21 @@ static sbm_work sbm_carve(char *base, int N, int K)
     return w;
 }
 
+// A -> its bit rows and columns (asynchronous); the latent distance model (latent.hip) reads the same words
+nhp_status nhp_sbm_enqueue_pack(nhp_ctx *ctx, const double *d_A, int N, uint32_t *colb, uint32_t *rowb)
+{
+    const int W = (N + 31) / 32;
+    hipLaunchKernelGGL(k_sbm_pack, dim3((unsigned)(((size_t)N * W + 255) / 256), 2), dim3(256), 0, ctx->main(), d_A, N, W, colb, rowb);
+    NHP_HIP(ctx, hipGetLastError());
+    return NHP_OK;
+}
+
 // bits of A, the per-node tables and the block counts for the labels d_z (all on the device, asynchronous)
 static nhp_status sbm_enqueue_tables(nhp_ctx *ctx, const double *d_A, int N, int K, const int32_t *d_z, const sbm_work &w, bool pack)
 {
     hipStream_t st = ctx->main();
     const int W = (N + 31) / 32;
-    if (pack) {
-        hipLaunchKernelGGL(k_sbm_pack, dim3((unsigned)(((size_t)N * W + 255) / 256), 2), dim3(256), 0, st, d_A, N, W, w.colb, w.rowb);
-        NHP_HIP(ctx, hipGetLastError());
-    }
+    if (pack) NHP_TRY(nhp_sbm_enqueue_pack(ctx, d_A, N, w.colb, w.rowb));
     NHP_HIP(ctx, hipMemsetAsync(w.L, 0, 8 * ((size_t)K * K + K), st));
     hipLaunchKernelGGL(k_sbm_tables, dim3((unsigned)N), dim3(64), 0, st, w.colb, w.rowb, d_z, N, W, K, w.out, w.in, w.L, w.sizes);
     NHP_HIP(ctx, hipGetLastError());
@@ -567,6 +573,7 @@ extern "C" nhp_status nhp_cont_model_set_sbm(nhp_ctx *ctx, nhp_cont_model *m, in
     NHP_TRY(sbm_check_priors(ctx, "set_sbm", alpha, beta, gamma));
     NHP_TRY(sbm_check_sweep(ctx, N, K));
     NHP_HIP(ctx, hipSetDevice(ctx->device));
+    NHP_TRY(nhp_latent_detach(ctx, m));                       // one structured network at a time
     NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
     if (m->sbm && m->sbm->K != K) nhp_sbm_free(m);
     const size_t KK = (size_t)K * K, W = ((size_t)N + 31) / 32;

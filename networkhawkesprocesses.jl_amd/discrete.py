@@ -991,9 +991,10 @@ def disc_resample_adjacency_matrix_(process, data=None, convolved=None, u=None, 
 
 
 def _resample_network(process, links, N, rng, seed, step, ctx):
-    """resample!(network, A) after the adjacency sweep: the block model needs the swept matrix, the others its link count."""
-    from .components import StochasticBlockNetworkModel
-    if isinstance(process.network, StochasticBlockNetworkModel):
+    """resample!(network, A) after the adjacency sweep: the block and the latent distance model need the swept matrix, the
+    others its link count."""
+    from .components import LatentDistanceNetworkModel, StochasticBlockNetworkModel
+    if isinstance(process.network, (StochasticBlockNetworkModel, LatentDistanceNetworkModel)):
         process.network.resample_(process.adjacency_matrix, rng, seed=seed, step=step, ctx=ctx)
     else:
         process.network.resample_links_(links, N * N, rng)

@@ -502,7 +502,7 @@ def resample_adjacency_matrix_(process, data, u=None, seed=0, step=0, model=None
     return nl.value
 
 
-def resample_(process, data, rng, step=0, seed=0, ctx=None, labels_every=1):
+def resample_(process, data, rng, step=0, seed=0, ctx=None, labels_every=1, positions_every=1):
     """resample!(process, data) -- src/continuous.jl:202-208,350-358: one Gibbs sweep.
 
     Parents and every sufficient statistic come from one GPU call; the conjugate draws are host
@@ -520,9 +520,11 @@ def resample_(process, data, rng, step=0, seed=0, ctx=None, labels_every=1):
         process.impulses.resample_(st["Mnm"], st["Xnm"], st["Vnm"], rng)
     if isinstance(process, ContinuousNetworkHawkesProcess):
         resample_adjacency_matrix_(process, data, seed=seed, step=step, ctx=ctx)
-        from .components import StochasticBlockNetworkModel
+        from .components import LatentDistanceNetworkModel, StochasticBlockNetworkModel
         if isinstance(process.network, StochasticBlockNetworkModel):      # on the GPU, keyed like the device-resident step
             process.network.resample_(process.adjacency_matrix, rng, seed=seed, step=step, ctx=ctx, labels=step % labels_every == 0)
+        elif isinstance(process.network, LatentDistanceNetworkModel):
+            process.network.resample_(process.adjacency_matrix, rng, seed=seed, step=step, ctx=ctx, positions=step % positions_every == 0)
         else:
             process.network.resample_(process.adjacency_matrix, rng)
     return process.params()
@@ -604,7 +606,7 @@ def _merge_shards(process, shard, network):
 
 
 def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_samples=True, device_draws=True,
-          ctx=None, moments=False, burn=0, labels_every=1):
+          ctx=None, moments=False, burn=0, labels_every=1, positions_every=1):
     """mcmc!(process, data; nsteps, log_freq, verbose) -- src/inference.jl:49-70.
 
     With `device_draws` (default) a whole sweep -- parents, statistics, conjugate draws -- stays on
@@ -628,6 +630,14 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
     switch them, and then these averages mix the blocks.  A ShardedDataset raises NotImplementedError (the labels'
     conditional needs every column of A).
 
+    A LatentDistanceNetworkModel takes the same routes (csrc/latent.hip): its positions and offset b stay next to the
+    device model, or its resample_ runs through the stand-alone entry with the chain's (seed, step).  The position sweep
+    is N dependent slice steps and the longest part of such a step: `positions_every=k` sweeps the
+    positions at the steps that are multiples of k only (b every step).  With `moments=True` the network entry of
+    res.mean / res.m2 is that of b, `res.link_probability_mean` [N x N] is the mean link-probability matrix over the kept
+    steps (the summary that does not depend on how the latent space is rotated or reflected) and `res.exhausted` counts
+    the slice steps that used up their 100 attempts.  A ShardedDataset raises NotImplementedError.
+
     ONE chain over several GPUs: pass a `sharded.ShardedDataset` (device draws, keep_samples=False).  A sweep is
     separable by child-node column -- the parents of the children on c, column c's statistics and conjugate draws and
     the sweep of A[:, c] touch column c only, and every random stream is keyed by global event / entry indices -- so
@@ -635,13 +645,18 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
     is the scalar link count the network's ρ update needs, and at the end the ranks' columns (and moments) are merged."""
     import ctypes as C
     from .sharded import ShardedDataset, _all_reduce_sum
-    from .components import BernoulliNetworkModel, DenseNetworkModel, StochasticBlockNetworkModel
+    from .components import BernoulliNetworkModel, DenseNetworkModel, LatentDistanceNetworkModel, StochasticBlockNetworkModel
     shard = data if isinstance(data, ShardedDataset) else None
     sbm = isinstance(getattr(process, "network", None), StochasticBlockNetworkModel)
+    latent = isinstance(getattr(process, "network", None), LatentDistanceNetworkModel)
     if sbm and shard is not None:
         raise NotImplementedError("a StochasticBlockNetworkModel chain is not sharded: the block labels need every column of A")
+    if latent and shard is not None:
+        raise NotImplementedError("a LatentDistanceNetworkModel chain is not sharded: the positions need every column of A")
     if int(labels_every) < 1:
         raise ValueError("labels_every must be a positive integer")
+    if int(positions_every) < 1:
+        raise ValueError("positions_every must be a positive integer")
     if not isinstance(process.baseline, HomogeneousProcess):
         device_draws = False      # nhp_cont_gibbs_step draws the homogeneous λ0; the LGCP curve is a host slice loop
     if moments and not device_draws:
@@ -661,8 +676,13 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
     # drawn there (src/networks.jl:70-78), so a network step needs no synchronisation; DenseNetworkModel keeps ρ = 1
     net = process.network if network else None
     net_a, net_b = (net.α, net.β) if isinstance(net, BernoulliNetworkModel) else (0.0, 0.0)
-    device_net = device_draws and isinstance(net, (BernoulliNetworkModel, DenseNetworkModel, StochasticBlockNetworkModel))
-    if device_net and sbm:
+    device_net = device_draws and isinstance(net, (BernoulliNetworkModel, DenseNetworkModel, StochasticBlockNetworkModel,
+                                                   LatentDistanceNetworkModel))
+    if device_net and latent:
+        _lib.check(lib.nhp_cont_model_set_latent(ctx.h, model.h, net.ndims, _lib.dptr(_lib.colmajor(net.z)), net.b, net.σ, net.μb, net.σb),
+                   ctx.h)
+        _lib.check(lib.nhp_cont_model_set_latent_positions_every(ctx.h, model.h, int(positions_every)), ctx.h)
+    elif device_net and sbm:
         z = np.ascontiguousarray(net.z, dtype=np.int32)
         _lib.check(lib.nhp_cont_model_set_sbm(ctx.h, model.h, net.nblocks, z.ctypes.data, _lib.dptr(_lib.colmajor(net.ρ)),
                                               _lib.dptr(_lib.f64(net.π)), net.α, net.β, net.γ), ctx.h)
@@ -674,7 +694,17 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
     if moments:
         _lib.check(lib.nhp_cont_model_moments_reset(ctx.h, model.h), ctx.h)
 
+    p_sum = [None]                         # a latent distance network's summed link probabilities, as last pulled
+
     def pull_rho():
+        if device_net and latent:          # (z, b) into the component; Σb, Σb² and the summed link probabilities
+            N, D = net.nnodes, net.ndims
+            z, b, sums, ps, ex = np.empty(N * D), C.c_double(), np.empty(2), np.empty(N * N), C.c_int64()
+            _lib.check(lib.nhp_cont_model_get_latent(ctx.h, model.h, _lib.dptr(z), C.byref(b), _lib.dptr(sums), _lib.dptr(ps), C.byref(ex)),
+                       ctx.h)
+            net.z, net.b = z.reshape((N, D), order="F"), b.value
+            res.exhausted, p_sum[0] = int(ex.value), ps.reshape((N, N), order="F")
+            return [None, sums[:1], sums[1:]]
         if device_net and sbm:             # (z, ρ, π) into the component; the running sums of [vec(ρ); π] and their squares
             K, N = net.nblocks, net.nnodes
             z, rho, pi = np.empty(N, dtype=np.int32), np.empty(K * K), np.empty(K)
@@ -720,6 +750,8 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
             last = keep_samples or res.steps == nsteps - 1
             if network and device_net and sbm:
                 _lib.check(lib.nhp_cont_sbm_step(ctx.h, ds.h, model.h, seed, res.steps), ctx.h)
+            elif network and device_net and latent:
+                _lib.check(lib.nhp_cont_latent_step(ctx.h, ds.h, model.h, seed, res.steps), ctx.h)
             elif network and device_net and not host_exchange:
                 _lib.check(lib.nhp_cont_network_step(ctx.h, comm.h if comm is not None else None, ds.h, model.h, net_a, net_b,
                                                      seed, res.steps), ctx.h)
@@ -740,7 +772,10 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
                     pull_rho()
             x = process.params() if keep_samples else None
         else:
-            x = resample_(process, ds, rng, step=res.steps, seed=seed, ctx=ctx, labels_every=int(labels_every))
+            x = resample_(process, ds, rng, step=res.steps, seed=seed, ctx=ctx, labels_every=int(labels_every),
+                          positions_every=int(positions_every))
+            if latent:
+                res.exhausted = getattr(res, "exhausted", 0) + net.exhausted
         if keep_samples:
             res.samples.append(x)
         res.steps += 1
@@ -756,6 +791,8 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
     if moments:
         r3 = pull_rho() if network else np.zeros(3)
         res.mean, res.m2, res.n = _fetch_moments(process, model, ctx, network, r3[1], r3[2])
+        if latent:
+            res.link_probability_mean = p_sum[0] / max(1, res.n)
         if shard is not None and shard.world > 1:
             mask = _owned_mask(process, shard, network)
             res.mean, res.m2 = _all_reduce_sum(res.mean * mask, ctx), _all_reduce_sum(res.m2 * mask, ctx)

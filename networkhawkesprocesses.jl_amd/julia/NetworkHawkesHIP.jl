@@ -715,6 +715,64 @@ end
 sbm_step!(ctx::Context, ds, m::Ptr{Cvoid}; seed::UInt64=UInt64(0), step::Integer=0) =
     check(ccall((:nhp_cont_sbm_step, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt64, UInt64), ctx.h, ds.h, m, seed, UInt64(step)), ctx.h)
 
+# --- LatentDistanceNetworkModel: the other empty stub at the end of src/networks.jl -------------------------------------------
+# z_n ~ N(0, σ² I_D), b ~ N(μb, σb²), A[p,c] ~ Bernoulli(1 / (1 + exp(-(b - ‖z_p - z_c‖²)))); z is N x D.  resample!(net, A) runs on
+# the GPU through the stand-alone entry (csrc/latent.hip): one elliptical-slice sweep over the positions, then the offset;
+# set_latent! / get_latent! / latent_step! keep the state next to a device model `m` (with_model), where nhp_cont_mcmc_run
+# takes the latent network step by itself.  Positions are identified only up to rotation, reflection and sign.
+mutable struct LatentDistanceNetworkModel
+    nnodes::Int; ndims::Int
+    z::Matrix{Float64}; b::Float64
+    σ::Float64; μb::Float64; σb::Float64
+end
+LatentDistanceNetworkModel(nnodes, ndims=2; z=zeros(nnodes, ndims), b=0.0, σ=1.0, μb=0.0, σb=1.0) =
+    LatentDistanceNetworkModel(nnodes, ndims, z, b, σ, μb, σb)
+NHP.params(net::LatentDistanceNetworkModel) = [net.b]
+link_probability(net::LatentDistanceNetworkModel) =
+    [1 / (1 + exp(sum(abs2, net.z[p, :] .- net.z[c, :]) - net.b)) for p in 1:net.nnodes, c in 1:net.nnodes]
+
+# -> (log p(A | z, b), the N conditional terms L_n the position sweep slices on)
+function latent_loglikelihood(net::LatentDistanceNetworkModel, A::Matrix{Float64}; ctx=context())
+    out = Vector{Float64}(undef, net.nnodes + 1)
+    check(ccall((:nhp_latent_loglik, libnhp), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Float64, Ptr{Float64}),
+                ctx.h, A, net.nnodes, net.ndims, net.z, net.b, out), ctx.h)
+    out[1], out[2:end]
+end
+
+# -> the number of slice steps that used up their 100 attempts and kept their value
+function resample!(net::LatentDistanceNetworkModel, A::Matrix{Float64}; seed::UInt64=UInt64(0), step::Integer=0, positions::Bool=true,
+                   ctx=context())
+    b, exhausted = Ref{Float64}(net.b), Ref{Int64}(0)
+    check(ccall((:nhp_latent_resample, libnhp), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ref{Float64}, Float64, Float64, Float64, Ptr{Float64}, UInt64, UInt64,
+                 Int32, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ref{Int64}),
+                ctx.h, A, net.nnodes, net.ndims, net.z, b, net.σ, net.μb, net.σb, C_NULL, seed, UInt64(step), Int32(positions ? 1 : 0),
+                Int32(1), C_NULL, C_NULL, C_NULL, exhausted), ctx.h)
+    net.b = b[]
+    exhausted[]
+end
+
+function set_latent!(ctx::Context, m::Ptr{Cvoid}, net::LatentDistanceNetworkModel; positions_every::Integer=1)
+    check(ccall((:nhp_cont_model_set_latent, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Float64, Float64, Float64, Float64),
+                ctx.h, m, net.ndims, net.z, net.b, net.σ, net.μb, net.σb), ctx.h)
+    check(ccall((:nhp_cont_model_set_latent_positions_every, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32), ctx.h, m, positions_every), ctx.h)
+end
+
+# -> (sums = [Σb; Σb²], Σ link probability N x N, exhausted slice steps) over the kept steps; the state itself goes into `net`
+function get_latent!(ctx::Context, m::Ptr{Cvoid}, net::LatentDistanceNetworkModel)
+    N = net.nnodes
+    b, sums, ps, exhausted = Ref{Float64}(0.0), Vector{Float64}(undef, 2), Matrix{Float64}(undef, N, N), Ref{Int64}(0)
+    check(ccall((:nhp_cont_model_get_latent, libnhp), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}),
+                ctx.h, m, net.z, b, sums, ps, exhausted), ctx.h)
+    net.b = b[]
+    sums, ps, exhausted[]
+end
+
+# one network step of mcmc! under the latent distance model (asynchronous): link probabilities, adjacency sweep, resample!(network, A)
+latent_step!(ctx::Context, ds, m::Ptr{Cvoid}; seed::UInt64=UInt64(0), step::Integer=0) =
+    check(ccall((:nhp_cont_latent_step, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt64, UInt64), ctx.h, ds.h, m, seed, UInt64(step)), ctx.h)
+
 # BASELINE config 5: after every rank ran its own chain with keep_samples=false, the per-chain posterior sums (still on
 # the devices) all-gathered over RCCL: returns (sum, sumsq) as len x world matrices, the sample counts, and ρ's sums.
 function gather_moments(ctx::Context, comm::Comm, m::Ptr{Cvoid}, len::Integer)

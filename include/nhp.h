@@ -186,9 +186,15 @@ nhp_status nhp_cont_loglik(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_c
  * internal streams, so alternate the slots to overlap them; two evaluations into the same slot stay in order.  Each
  * evaluation is ordered after every earlier call on the context that is not an enqueue (parameter uploads, dataset
  * builds, samplers, nhp_ctx_timer_start) and before every later one (nhp_cont_model_set_params, the destroy functions,
- * ...), so a model or dataset may be changed or destroyed right after the enqueue.  A slot's value is defined after
- * nhp_ctx_fetch, nhp_ctx_synchronize or nhp_ctx_timer_stop.  The recursive formulation (NHP_LL_RECURSIVE,
- * exponential impulses) is not overlapped: it is a call like any other. */
+ * ...), so a model or dataset may be changed or destroyed right after the enqueue.  A slot's value EXISTS only after the
+ * next joining call on the context -- any call that is not an enqueue; the caller reads it after nhp_ctx_fetch,
+ * nhp_ctx_synchronize or nhp_ctx_timer_stop.  An evaluation over a dataset's child slices leaves the partial sums of its
+ * workgroups in a buffer the CONTEXT keeps for the slot and marks the slot pending; the joining call adds up every pending
+ * slot in one small launch, in the order the evaluation itself would have used (the same bits), before it does anything
+ * else.  The buffer is the context's, so the sum is still made when the slot's dataset or model has been destroyed in
+ * between; a later evaluation into the slot replaces the earlier one, pending or not.  NHP_DEFER_FINALIZE=0 in the
+ * environment when the context is created: every evaluation adds its own sums up (one launch each, nothing pending).
+ * The recursive formulation (NHP_LL_RECURSIVE, exponential impulses) is not overlapped: it is a call like any other. */
 #define NHP_MAX_SLOTS 4096
 nhp_status nhp_cont_loglik_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds,
                                    const nhp_cont_model *model, int32_t flags, int32_t slot);

@@ -909,8 +909,9 @@ static void launch_group(int G, dim3 grid, size_t lds, hipStream_t st, const nhp
 
 static nhp_status run_windowed(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m,
                                double *d_out, double *d_lambda, const nhp_child *child_w = nullptr, int group = 0,
-                               int mask_integral = 1)
+                               int mask_integral = 1, int32_t defer_slot = -1, bool *deferred = nullptr)
 {
+    if (deferred) *deferred = false;
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t per = m->impulse_kind == NHP_IMPULSE_EXPONENTIAL ? 16 : 24;
     const size_t lds = 192 + per * (size_t)ds->N + 512;            // + the 64-entry exp table
@@ -926,12 +927,12 @@ static nhp_status run_windowed(nhp_ctx *ctx, const nhp_cont_dataset *ds, const n
     // ... one lane per child over the child slices (cont_slices.hip) when there is no λ output: 6-byte records
     if (!child_w && !d_lambda && d_out && expo_p && !plist_off) {
         bool launched = false;
-        NHP_TRY(nhp_launch_windowed_slices(ctx, ds, m, mask_integral, d_out, &launched));
+        NHP_TRY(nhp_launch_windowed_slices(ctx, ds, m, mask_integral, d_out, &launched, defer_slot, deferred));
         if (launched) return NHP_OK;
     }
     if (!child_w && (d_out || d_lambda) && m->impulse_kind == NHP_IMPULSE_LOGITNORMAL && !plist_off) {     // ... and the logit-normal twin (λ out as well)
         bool launched = false;
-        NHP_TRY(nhp_launch_windowed_slices_ln(ctx, ds, m, mask_integral, d_out, d_lambda, &launched));
+        NHP_TRY(nhp_launch_windowed_slices_ln(ctx, ds, m, mask_integral, d_out, d_lambda, &launched, defer_slot, deferred));
         if (launched) return NHP_OK;
     }
     if (!child_w && ds->d_poff && !plist_off && G <= 16 && (expo_p || nhp_ensure_pair_cache(ctx, ds, &a) == NHP_OK)) {
@@ -1030,12 +1031,18 @@ static bool recursive_route(const nhp_cont_model *m, int32_t flags)
     return m && (flags & NHP_LL_RECURSIVE) && m->impulse_kind == NHP_IMPULSE_EXPONENTIAL;
 }
 
-static nhp_status enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int32_t flags, int32_t slot)
+// `defer` (nhp_cont_loglik_enqueue only): the slices route may leave the last sum to the next join; whatever
+// writes the slot's value itself takes a pending mark off the slot, or the join would put the older sum over it.
+static nhp_status enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int32_t flags, int32_t slot,
+                          bool defer = false)
 {
     NHP_TRY(nhp_check_pair(ctx, ds, m));
     if (slot < 0 || slot >= NHP_MAX_SLOTS) return NHP_EINVAL;
-    if (recursive_route(m, flags)) return nhp_launch_recursive_flags(ctx, ds, m, flags, ctx->d_results + slot);
-    return run_windowed(ctx, ds, m, ctx->d_results + slot, nullptr);
+    if (recursive_route(m, flags)) return nhp_launch_recursive_flags(ctx, ds, m, flags, ctx->d_results + slot);   // (joins first)
+    bool deferred = false;
+    NHP_TRY(run_windowed(ctx, ds, m, ctx->d_results + slot, nullptr, nullptr, 0, 1, defer ? slot : -1, &deferred));
+    if (!deferred) ctx->pend.clear(slot);
+    return NHP_OK;
 }
 
 // Odd slots go to the second lane, even ones stay on the main stream: two evaluations into one slot share a lane and stay
@@ -1046,7 +1053,7 @@ extern "C" nhp_status nhp_cont_loglik_enqueue(nhp_ctx *ctx, const nhp_cont_datas
     if (!ctx) return NHP_EINVAL;
     nhp_lane_guard lane{ctx};
     if ((slot & 1) && ctx->stream2 && !recursive_route(m, flags)) lane.flip();
-    return enqueue(ctx, ds, m, flags, slot);
+    return enqueue(ctx, ds, m, flags, slot, ctx->defer_finalize);
 }
 
 extern "C" nhp_status nhp_cont_loglik(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m,

@@ -257,7 +257,9 @@ __global__ __launch_bounds__(256) void k_ps_sort(int N, nhp_pslices ps, const ui
 // summed, across slice boundaries too (the first rows of a wave's next slice are requested under the last rows of this one,
 // and the very first set before the column is staged: its addresses need the slice table only).
 // GRAD: the analytic gradient in the same launch (the objective of mle!, src/continuous.jl:144-198, differentiated by hand;
-// formulas at the top of cont_grad.hip).  Phase A is the log-likelihood itself and leaves g_k = 1/λ_k of the item's children
+// formulas at the top of cont_grad.hip).  `out` null: the block sums only, without the baseline's integral (the caller adds it up
+// and owns that term).  `defer` (with `out` given, the enqueue route): the whole evaluation's block sums, baseline integral
+// included, into `partials` -- here a result slot's own buffer -- and no second stage: k_finalize_slots adds them at the join.  Phase A is the log-likelihood itself and leaves g_k = 1/λ_k of the item's children
 // in LDS; phase B walks the item's PARENT slices -- lane = parent node p, its θ[p,c], W[p,c] in registers, row r = the node's
 // r-th pair as {child slot, delay} -- and every lane sums Σ g·e^{-θΔ} and Σ g·(1-θΔ)·e^{-θΔ} over its own pairs: no atomics,
 // no cross-lane step, the list streamed once.  An item that is its node's only one stores the column's gradient (the
@@ -265,7 +267,7 @@ __global__ __launch_bounds__(256) void k_ps_sort(int N, nhp_pslices ps, const ui
 template <int BLOCK, int C, bool FLAT, bool GRAD>
 __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_slices sl, nhp_pslices ps, int mask_integral,
                                                             double *__restrict__ partials, unsigned int *__restrict__ counter,
-                                                            double *__restrict__ out)
+                                                            double *__restrict__ out, int defer)
 {
     constexpr int NW = BLOCK / 64;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -505,11 +507,12 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
         __syncthreads();
     }
     NHP_SL_STAMP(3);
-    if (!out) {
+    if (!out || defer) {
         if (tid == 0) {
             partials[2 * (size_t)blockIdx.x] = blk;
             partials[2 * (size_t)blockIdx.x + 1] = blk_int;
         }
+        NHP_SL_STAMP(4);
         return;
     }
     // fused second stage (as k_windowed): write-through partials, one sharded ticket; the workgroup that draws the last
@@ -887,7 +890,7 @@ __global__ __launch_bounds__(BLOCK) void k_sampler_slices(nhp_cont_args a, nhp_s
 template <int BLOCK, int C, bool FLAT>
 __global__ __launch_bounds__(BLOCK) void k_windowed_slices_ln(nhp_cont_args a, nhp_slices sl, const double *__restrict__ L, const double *__restrict__ Q,
                                                                int mask_integral, double *__restrict__ partials, unsigned int *__restrict__ counter,
-                                                               double *__restrict__ out, double *__restrict__ lambda_out)
+                                                               double *__restrict__ out, double *__restrict__ lambda_out, int defer)
 {
     constexpr int NW = BLOCK / 64;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -992,7 +995,7 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices_ln(nhp_cont_args a, n
     if (prod == 0.0) acc = -__builtin_inf();
     double blk = acc, blk_int = integ;
     nhp_block_sum2_n<NW>(blk, blk_int, red);
-    if (!out) {
+    if (!out || defer) {                                            // (defer: as in k_windowed_slices)
         if (tid == 0) { partials[2 * (size_t)blockIdx.x] = blk; partials[2 * (size_t)blockIdx.x + 1] = blk_int; }
         return;
     }
@@ -1129,9 +1132,10 @@ static nhp_status ensure_parent_slices(nhp_ctx *ctx, const nhp_cont_dataset *cds
 // grad != nullptr: log-likelihood AND gradient (k_windowed_slices<.., GRAD>); the gradient must have been initialised by
 // k_grad_init unless `direct`
 static nhp_status launch_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int mask_integral, double *d_out,
-                                double *d_grad, bool direct, bool *launched)
+                                double *d_grad, bool direct, bool *launched, int32_t defer_slot = -1, bool *deferred = nullptr)
 {
     *launched = false;
+    if (deferred) *deferred = false;
     if (!ds->d_sl_row || ds->n_items <= 0 || m->impulse_kind != NHP_IMPULSE_EXPONENTIAL) return NHP_OK;
     if (nhp_slices_off(d_grad ? "NHP_GRAD_SLICES" : nullptr)) return NHP_OK;     // (NHP_GRAD_SLICES=0: the two-pass route of cont_grad.hip)
     const size_t lds = 320 + 16 * ((size_t)ds->N + 1) + 512 + (d_grad ? 8 * ((size_t)ds->max_item + 1) : 0);
@@ -1158,12 +1162,21 @@ static nhp_status launch_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const 
     dim3 grid((unsigned)ds->n_items);
     bool ok = false;
     const bool flat = m->baseline_kind == NHP_BASELINE_HOMOGENEOUS;
+    // the enqueue route: the block sums into the slot's own buffer, added up at the next join (k_finalize_slots repeats the
+    // order of a workgroup of up to 512; one of 1024 keeps its fused sum)
+    const bool known = (B == 64 || B == 128 || B == 256 || B == 512) && (C == 2 || C == 4 || C == 8);
+    const int defer = defer_slot >= 0 && !d_grad && d_out && known ? 1 : 0;
+    double *partials = ctx->d_partials;
+    if (defer) {
+        NHP_TRY(nhp_ctx_reserve_slot_partials(ctx, defer_slot, 2 * (size_t)ds->n_items));
+        partials = ctx->d_slot_partials[defer_slot];
+    }
 #define NHP_SLAUNCH(b, cc, f, g)                                                                                      \
     do {                                                                                                              \
         if (lds > 64 * 1024)                                                                                          \
             (void)hipFuncSetAttribute((const void *)k_windowed_slices<b, cc, f, g>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_windowed_slices<b, cc, f, g>), grid, dim3(b), lds, ctx->lane(), a, sl, ps, mask_integral, ctx->d_partials, \
-                           ctx->d_counter, d_out);                                                                    \
+        hipLaunchKernelGGL((k_windowed_slices<b, cc, f, g>), grid, dim3(b), lds, ctx->lane(), a, sl, ps, mask_integral, partials, \
+                           ctx->d_counter, d_out, defer);                                                             \
     } while (0)
 #define NHP_SCASE(b, cc)                                                                                              \
     if (!ok && B == b && C == cc) {                                                                                   \
@@ -1178,23 +1191,28 @@ static nhp_status launch_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const 
 #undef NHP_SROW
 #undef NHP_SCASE
     NHP_HIP(ctx, hipGetLastError());
+    if (defer) {
+        ctx->pend.mark(defer_slot, ds->n_items, B);
+        if (deferred) *deferred = true;
+    }
     *launched = true;
     return NHP_OK;
 }
 
 nhp_status nhp_launch_windowed_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int mask_integral,
-                                      double *d_out, bool *launched)
+                                      double *d_out, bool *launched, int32_t defer_slot, bool *deferred)
 {
-    return launch_slices(ctx, ds, m, mask_integral, d_out, nullptr, false, launched);
+    return launch_slices(ctx, ds, m, mask_integral, d_out, nullptr, false, launched, defer_slot, deferred);
 }
 
 static nhp_status ensure_lq_planes(nhp_ctx *ctx, nhp_cont_dataset *ds, const nhp_cont_args &a, const nhp_slices &sl, bool *ok);
 
 // logit-normal impulses: the same call for k_windowed_slices_ln (NHP_SLICES_LN=0: the pair-cache kernel)
 nhp_status nhp_launch_windowed_slices_ln(nhp_ctx *ctx, const nhp_cont_dataset *cds, const nhp_cont_model *m, int mask_integral,
-                                         double *d_out, double *d_lambda, bool *launched)
+                                         double *d_out, double *d_lambda, bool *launched, int32_t defer_slot, bool *deferred)
 {
     *launched = false;
+    if (deferred) *deferred = false;
     if (!cds->d_sl_row || cds->n_items <= 0 || m->impulse_kind != NHP_IMPULSE_LOGITNORMAL) return NHP_OK;
     if (nhp_slices_off("NHP_SLICES_LN")) return NHP_OK;
     const size_t lds = 320 + 24 * ((size_t)cds->N + 1);
@@ -1216,12 +1234,18 @@ nhp_status nhp_launch_windowed_slices_ln(nhp_ctx *ctx, const nhp_cont_dataset *c
     if (!((B == 64 || B == 256 || B == 512) && (C == 2 || C == 4))) { B = 256; C = 2; }
     const bool flat = m->baseline_kind == NHP_BASELINE_HOMOGENEOUS;
     dim3 grid((unsigned)ds->n_items);
+    const int defer = defer_slot >= 0 && d_out && !d_lambda ? 1 : 0;     // (as launch_slices; every workgroup size here is <= 512)
+    double *partials = ctx->d_partials;
+    if (defer) {
+        NHP_TRY(nhp_ctx_reserve_slot_partials(ctx, defer_slot, 2 * (size_t)ds->n_items));
+        partials = ctx->d_slot_partials[defer_slot];
+    }
 #define NHP_LNL(b, cc, f)                                                                                             \
     do {                                                                                                              \
         if (lds > 64 * 1024)                                                                                          \
             (void)hipFuncSetAttribute((const void *)k_windowed_slices_ln<b, cc, f>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL((k_windowed_slices_ln<b, cc, f>), grid, dim3(b), lds, ctx->lane(), a, sl, (const double *)ds->d_sl_L,  \
-                           (const double *)ds->d_sl_Q, mask_integral, ctx->d_partials, ctx->d_counter, d_out, d_lambda); \
+                           (const double *)ds->d_sl_Q, mask_integral, partials, ctx->d_counter, d_out, d_lambda, defer); \
     } while (0)
 #define NHP_LNC(b, cc) do { if (flat) NHP_LNL(b, cc, true); else NHP_LNL(b, cc, false); } while (0)
     if (B == 64) { if (C == 2) NHP_LNC(64, 2); else NHP_LNC(64, 4); }
@@ -1230,6 +1254,10 @@ nhp_status nhp_launch_windowed_slices_ln(nhp_ctx *ctx, const nhp_cont_dataset *c
 #undef NHP_LNC
 #undef NHP_LNL
     NHP_HIP(ctx, hipGetLastError());
+    if (defer) {
+        ctx->pend.mark(defer_slot, ds->n_items, B);
+        if (deferred) *deferred = true;
+    }
     *launched = true;
     return NHP_OK;
 }

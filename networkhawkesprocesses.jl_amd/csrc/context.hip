@@ -44,6 +44,89 @@ extern "C" int32_t nhp_abi_layout(int32_t *out, int32_t cap)
     return NHP_ABI_LAYOUT_LEN;
 }
 
+// ---- deferred sums of enqueued evaluations --------------------------------------------------------------------
+// One workgroup per pending slot adds the partial sums its evaluation's workgroups left, in the order the last workgroup
+// of the fused reduction uses (k_windowed_slices): thread t of a workgroup of `block` takes partials t, t + block, ..., the
+// waves' sums are added wave by wave, *out = (0 - Σ integral) + Σ log λ.  The launch has 512 threads whatever `block` was (at
+// most 512): the threads past `block` hold +0.0, which changes no bit of a sum that starts at +0.0.
+#define NHP_FIN_CHUNK 240        // slots per launch: their descriptors travel by value in the launch's arguments (under 4 KB)
+struct nhp_fin_item { const double *partials; int32_t n; uint16_t slot, block; };
+struct nhp_fin_args { nhp_fin_item it[NHP_FIN_CHUNK]; };
+
+__global__ __launch_bounds__(512) void k_finalize_slots(nhp_fin_args q, double *__restrict__ results)
+{
+    __shared__ double red[16];
+    const nhp_fin_item it = q.it[blockIdx.x];
+    const int tid = threadIdx.x, B = it.block;
+    double sl_ = 0.0, si = 0.0;
+    if (tid < B)
+        for (int i = tid; i < it.n; i += B) {
+            sl_ += it.partials[2 * (size_t)i];
+            si += it.partials[2 * (size_t)i + 1];
+        }
+    nhp_block_sum2_n<8>(sl_, si, red);
+    if (tid == 0) results[it.slot] = (0.0 - si) + sl_;
+}
+
+void nhp_ctx::finalize_pending()
+{
+    static thread_local int32_t slots[NHP_MAX_SLOTS], counts[NHP_MAX_SLOTS], blocks[NHP_MAX_SLOTS];
+    const int32_t n = pend.drain(slots, counts, blocks);
+    if (n <= 0) return;
+    lane_call(hipSetDevice(device));
+    for (int32_t k0 = 0; k0 < n; k0 += NHP_FIN_CHUNK) {
+        const int32_t cnt = n - k0 < NHP_FIN_CHUNK ? n - k0 : NHP_FIN_CHUNK;
+        nhp_fin_args q{};
+        for (int32_t k = 0; k < cnt; ++k) {
+            const int32_t s = slots[k0 + k];
+            q.it[k].partials = d_slot_partials[s];
+            q.it[k].n = counts[k0 + k];
+            q.it[k].slot = (uint16_t)s;
+            q.it[k].block = (uint16_t)blocks[k0 + k];
+        }
+        hipLaunchKernelGGL(k_finalize_slots, dim3((unsigned)cnt), dim3(512), 0, stream_main, q, d_results);
+        lane_call(hipGetLastError());
+        ++finalize_launches;
+    }
+}
+
+nhp_status nhp_ctx_reserve_slot_partials(nhp_ctx *ctx, int32_t slot, size_t n)
+{
+    if (n <= ctx->slot_cap[slot]) return NHP_OK;
+    if (ctx->d_slot_partials[slot]) {                       // (a slot's first buffer: nothing to wait for, the streak goes on)
+        NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));    // the join adds up what the old buffer holds first
+        (void)hipFree(ctx->d_slot_partials[slot]);
+    }
+    ctx->d_slot_partials[slot] = nullptr;
+    ctx->slot_cap[slot] = 0;
+    NHP_HIP(ctx, hipMalloc(&ctx->d_slot_partials[slot], sizeof(double) * n));
+    ctx->slot_cap[slot] = (uint32_t)n;
+    return NHP_OK;
+}
+
+// diagnostics for the tests: finalize launches of this context so far; and the pending-slot bookkeeping on its own, no device
+extern "C" int64_t nhp_debug_finalize_launches(const nhp_ctx *ctx) { return ctx ? ctx->finalize_launches : -1; }
+extern "C" void *nhp_debug_pending_new(void) { return new nhp_pending(); }
+extern "C" void nhp_debug_pending_free(void *p) { delete static_cast<nhp_pending *>(p); }
+extern "C" int32_t nhp_debug_pending_mark(void *p, int32_t slot, int32_t n, int32_t block)
+{
+    if (!p || slot < 0 || slot >= NHP_MAX_SLOTS || n <= 0) return -1;
+    static_cast<nhp_pending *>(p)->mark(slot, n, block);
+    return 0;
+}
+extern "C" int32_t nhp_debug_pending_clear(void *p, int32_t slot)
+{
+    if (!p || slot < 0 || slot >= NHP_MAX_SLOTS) return -1;
+    static_cast<nhp_pending *>(p)->clear(slot);
+    return 0;
+}
+// -> the marked slots with their counts and workgroup sizes ([NHP_MAX_SLOTS] each); returns how many, none marked afterwards
+extern "C" int32_t nhp_debug_pending_drain(void *p, int32_t *slots, int32_t *counts, int32_t *blocks)
+{
+    if (!p || !slots || !counts || !blocks) return -1;
+    return static_cast<nhp_pending *>(p)->drain(slots, counts, blocks);
+}
+
 extern "C" const char *nhp_last_error(const nhp_ctx *ctx)
 {
     return ctx ? ctx->err.c_str() : g_last_error.c_str();
@@ -65,6 +148,7 @@ extern "C" nhp_status nhp_ctx_create(int32_t device, nhp_ctx **out)
     }
     nhp_ctx *ctx = new nhp_ctx();
     ctx->device = device;
+    if (const char *df = getenv("NHP_DEFER_FINALIZE")) ctx->defer_finalize = atoi(df) != 0;
     NHP_HIP(ctx, hipSetDevice(device));
     hipDeviceProp_t prop;
     NHP_HIP(ctx, hipGetDeviceProperties(&prop, device));
@@ -97,6 +181,8 @@ extern "C" void nhp_ctx_destroy(nhp_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->stream_main) (void)hipStreamSynchronize(ctx->main());     // (joins the second lane first)
     if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
+    for (int s = 0; s < NHP_MAX_SLOTS; ++s)
+        if (ctx->d_slot_partials[s]) (void)hipFree(ctx->d_slot_partials[s]);
     if (ctx->d_partials2) (void)hipFree(ctx->d_partials2);
     if (ctx->d_counter2) (void)hipFree(ctx->d_counter2);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);

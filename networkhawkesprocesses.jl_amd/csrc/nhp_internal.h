@@ -20,6 +20,38 @@
 #define NHP_U_MID 4     // G = 16, 32 (tools/uvar.sh: 4 beats 2 by 5-8 % at K=64, 512)
 #endif
 
+// Which result slots hold a DEFERRED sum: an evaluation enqueued through nhp_cont_loglik_enqueue on the slices
+// route leaves its workgroups' partial sums in the slot's own buffer and the slot is marked here; the next join adds them
+// up, every marked slot in one launch.  Plain bookkeeping, no device call: mark (the later launch into a slot replaces the
+// earlier), clear (a launch that writes the slot's value itself) and drain (the join: every slot still marked, in the order
+// of its first mark, and none marked afterwards).
+struct nhp_pending {
+    int32_t n[NHP_MAX_SLOTS] = {};          // partial pairs the slot's deferred launch wrote; 0: not marked
+    uint16_t block[NHP_MAX_SLOTS] = {};     // that launch's workgroup size: the order of the sum follows it
+    uint8_t listed[NHP_MAX_SLOTS] = {};     // the slot is in `order` (marked now or cleared since)
+    std::vector<int32_t> order;
+    void mark(int32_t slot, int32_t n_partials, int32_t block_size)
+    {
+        n[slot] = n_partials;
+        block[slot] = (uint16_t)block_size;
+        if (!listed[slot]) { listed[slot] = 1; order.push_back(slot); }
+    }
+    void clear(int32_t slot) { n[slot] = 0; }
+    bool any() const { return !order.empty(); }
+    // -> slots[k], counts[k], blocks[k] of the marked slots; returns how many
+    int32_t drain(int32_t *slots, int32_t *counts, int32_t *blocks)
+    {
+        int32_t k = 0;
+        for (const int32_t s : order) {
+            listed[s] = 0;
+            if (n[s] > 0) { slots[k] = s; counts[k] = n[s]; blocks[k] = block[s]; ++k; }
+            n[s] = 0;
+        }
+        order.clear();
+        return k;
+    }
+};
+
 struct nhp_ctx {
     int device = 0;
     // The main stream.  Reached only through main() (or lane() at the launch lines of the pipelined log-likelihood
@@ -62,7 +94,18 @@ struct nhp_ctx {
     // reported by the next NHP_HIP check on this context (and so by fetch / synchronize / timer_stop at the latest).
     hipError_t lane_err = hipSuccess;
     void lane_call(hipError_t e) { if (e != hipSuccess && lane_err == hipSuccess) lane_err = e; }
-    // the JOIN: the main stream waits for what lane 2 has in flight, and is noted as having new work
+    // Deferred sums of the enqueue route: a partial-sum buffer per result slot (grown on demand, 2 doubles per
+    // workgroup), the slots whose sum is still owed, and the switch NHP_DEFER_FINALIZE (read when the context is made; 0:
+    // the enqueue route keeps the fused ticket).  The buffers belong to the context, so a pending slot outlives its dataset
+    // and model.
+    double *d_slot_partials[NHP_MAX_SLOTS] = {};
+    uint32_t slot_cap[NHP_MAX_SLOTS] = {};      // in doubles
+    nhp_pending pend;
+    bool defer_finalize = true;
+    int64_t finalize_launches = 0;              // k_finalize_slots launches so far (nhp_debug_finalize_launches)
+    void finalize_pending();                    // context.hip: one launch (per 240 slots) on the main stream
+    // the JOIN: the main stream waits for what lane 2 has in flight, then adds up the deferred slots of both lanes before
+    // anything else is given to it, and is noted as having new work
     void join_lanes()
     {
         if (lane2_busy) {
@@ -70,6 +113,7 @@ struct nhp_ctx {
             lane_call(hipEventRecord(ev_join, stream2));
             lane_call(hipStreamWaitEvent(stream_main, ev_join, 0));
         }
+        if (pend.any()) finalize_pending();
         main_touched = true;
     }
     // the main stream, for everything that is not an independent evaluation: ordered after both lanes
@@ -448,6 +492,8 @@ inline void nhp_model_view_keep_bound(nhp_cont_model *m, const nhp_cont_model &v
 }
 
 nhp_status nhp_ctx_reserve_partials(nhp_ctx *ctx, size_t n_doubles);
+// the deferred sums' buffer of one result slot (ctx->d_slot_partials[slot]), grown on demand like d_partials
+nhp_status nhp_ctx_reserve_slot_partials(nhp_ctx *ctx, int32_t slot, size_t n_doubles);
 // the device optimizers' block (ctx->d_mle: mle!, em!, expected_statistics), grown on demand and kept between runs; `what`
 // names the state in the out-of-memory message
 nhp_status nhp_ctx_reserve_mle(nhp_ctx *ctx, size_t bytes, const char *what);
@@ -504,10 +550,14 @@ __host__ __device__ inline int32_t nhp_slice_of(int32_t round, int32_t wave, int
 }
 // cont_slices.hip: the exponential log-likelihood of the dataset's own short windows, one lane per child over the child
 // slices.  *launched = false (and NHP_OK) when the dataset has no slices or the model is not covered.
+// defer_slot >= 0 (nhp_cont_loglik_enqueue only, d_out = ctx->d_results + defer_slot): the workgroups leave their partial sums
+// in that slot's buffer and the slot is marked pending instead of the fused last-workgroup sum; *deferred says whether the
+// launch took that exit (it keeps the fused sum where the deferred one could not repeat its order: workgroups of 1024).
 nhp_status nhp_launch_windowed_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int mask_integral,
-                                      double *d_out, bool *launched);
+                                      double *d_out, bool *launched, int32_t defer_slot = -1, bool *deferred = nullptr);
 nhp_status nhp_launch_windowed_slices_ln(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int mask_integral,
-                                      double *d_out, double *d_lambda, bool *launched);
+                                      double *d_out, double *d_lambda, bool *launched, int32_t defer_slot = -1,
+                                      bool *deferred = nullptr);
 // the same with the analytic gradient (params! order, P doubles at d_grad) from one fused launch over the child and the
 // parent slices; *launched = false when the pair is not covered
 nhp_status nhp_launch_grad_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, double *d_out, double *d_grad,

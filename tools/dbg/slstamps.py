@@ -1,6 +1,6 @@
 """Phase timeline of k_windowed_slices from a -DNHP_STAMP build (NHP_LIB=... python tools/dbg/slstamps.py): wave 0 of every
 workgroup stamps s_memrealtime (100 MHz, the same clock on every XCD) at its start, after the column is staged, after its
-slices, after the block sums, after the ticket; EVERY wave stamps the end of its own slices, and the spread between a
+slices, after the block sums, after the ticket (ENQUEUE=1: after the stores of the deferred exit); EVERY wave stamps the end of its own slices, and the spread between a
 workgroup's first and last wave to finish is what the dealing of slices to waves (nhp_slice_of) is there to shrink: the early
 waves wait at the block-sum barrier for the last one.  Times in us from the launch's first workgroup start."""
 import os, sys, ctypes as C
@@ -13,8 +13,14 @@ ctx = nhp.Context(0)
 N, M = 1024, 1_000_000
 times, nodes, T = nhp.synthetic.s_metric_data(N, M, kbar=float(os.environ.get("KBAR", 8.0)))
 proc = nhp.synthetic.s_metric_process(N, M, T, "exponential", 1.0)
-for _ in range(5):
-    nhp.loglikelihood(proc, (times, nodes, T), recursive=False, ctx=ctx)
+if os.environ.get("ENQUEUE"):                        # the enqueue route: its last stamp is the deferred exit (NHP_DEFER_FINALIZE=0: the ticket)
+    ds0, model = nhp.device_dataset(proc, (times, nodes, T), ctx), proc.device_model(ctx)
+    for _ in range(5):
+        _lib.check(_lib.lib().nhp_cont_loglik_enqueue(ctx.h, ds0.h, model.h, 0, 0), ctx.h)
+        ctx.synchronize()
+else:
+    for _ in range(5):
+        nhp.loglikelihood(proc, (times, nodes, T), recursive=False, ctx=ctx)
 n = 1024
 buf = np.zeros(8 * n, dtype=np.uint64)
 fn = _lib.lib().nhp_debug_stamps_slices

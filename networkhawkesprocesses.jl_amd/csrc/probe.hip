@@ -21,6 +21,9 @@ __global__ void k_probe(int op, const double *__restrict__ x, const double *__re
     case 2: r = __builtin_sqrt(a); break;
     case 3: r = a / b; break;
     case 4: r = nhp_exp_neg(a); break;
+    case 9: r = -expm1(-a); break;                                     // the compensator's three library calls, as it writes them
+    case 10: r = log(a / (1.0 - a)); break;
+    case 11: r = 0.5 * erfc(-0.7071067811865476 * a); break;
     case 5: { double scale = 1.0 / a; r = nhp_pdf_exponential(1.0 / scale, b); } break;     // (θ, Δt)
     default: r = nhp_pdf_logitnormal(0.25, __builtin_sqrt(a), 1.0 / 2.0, b); break;         // (τ, Δt), μ=.25, Δtmax=2
     }

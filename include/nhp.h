@@ -574,6 +574,44 @@ nhp_status nhp_disc_netsvi_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double 
                                const int32_t *blocks /* nullable [n_steps] */, const double *phi /* nullable */, int32_t n_lags,
                                int32_t n_basis, double *alpha_v, double *beta_v, double *kappa_v0, double *nu_v0, double *kappa_v1,
                                double *nu_v1, double *gamma_v, double *rho_v, double *net_alpha_v, double *net_beta_v);
+/* update! / vb! for the same process with a StochasticBlockNetworkModel of n_blocks = K <= 64 blocks:
+ *   z_n ~ Categorical(π),  π ~ Dirichlet(net_gamma·1_K),  ρ[k,l] ~ Beta(net_alpha, net_beta),  A[p,c] ~ Bernoulli(ρ[z_p, z_c]).
+ * The family of nhp_disc_netvb_run plus q(z_n) = Categorical(m[n,:]), q(π) = Dirichlet(gamma_v_net), q(ρ[k,l]) =
+ * Beta(net_alpha_v[k,l], net_beta_v[k,l]);  m [N*K] is column-major [n, k], the tables [K*K] column-major [k, l].
+ * With E1 = ψ(αv) - ψ(αv + βv), E0 = ψ(βv) - ψ(αv + βv), D = E1 - E0, Eπ = ψ(γv) - ψ(Σγv) and the pair weight
+ * ω[p,c,k,l] = m[p,k] m[c,l] for p != c, ω[p,p,k,l] = m[p,k] δ_kl (a node has one label), one step is the step of
+ * nhp_disc_netvb_run with
+ *   1. the network term of the logit per link, net[p,c] = Σ_kl ω D, from the OLD m and tables;
+ *   2. αv[k,l] = α + Σ_pc ω ρv,  βv[k,l] = β + Σ_pc ω (1 - ρv),  γv[k] = γ + Σ_n m[n,k]  from the NEW ρv and the current m;
+ *   3. when the step's global number step0 + 1, step0 + 2, ... (step0 = the steps earlier calls took: the caller counts
+ *      them, as for nhp_disc_svi_run) is a multiple of labels_every, one sweep of coordinate ascent over
+ *      the nodes 0 .. N-1, each reading the current m of all others and the tables of 2:  m[n,:] = softmax(s),
+ *      s_k = Eπ[k] + ρv[n,n] E1[k,k] + (1 - ρv[n,n]) E0[k,k] + Σ_{c≠n} Σ_l m[c,l] (ρv[n,c] E1[k,l] + (1 - ρv[n,c]) E0[k,l])
+ *                                                            + Σ_{p≠n} Σ_l m[p,l] (ρv[p,n] E1[l,k] + (1 - ρv[p,n]) E0[l,k]).
+ * Every row of m must be non-negative and sum to 1 within 1e-12, every table and prior must be > 0: NHP_EINVAL before any
+ * launch.  The sweep keeps m in LDS: 8 (N K + 2 N + 20 Kp) bytes, Kp the next power of two of K, must fit 160 KiB, else
+ * NHP_ENOTIMPL with the byte count, before any launch.  One upload, one download, no synchronisation inside the n_steps,
+ * every sum in one fixed order: n calls of one step, each with the step0 the calls before it reached, are one call of
+ * n steps, bit for bit, for every labels_every. */
+nhp_status nhp_disc_sbmvb_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
+                              double alpha0, double beta0, double kappa0, double nu0, double kappa1, double nu1, double gamma,
+                              int32_t n_blocks, double net_alpha, double net_beta, double net_gamma, int32_t labels_every,
+                              int64_t step0, int32_t n_steps, double *alpha_v, double *beta_v, double *kappa_v0, double *nu_v0, double *kappa_v1,
+                              double *nu_v1, double *gamma_v, double *rho_v, double *m, double *net_alpha_v, double *net_beta_v,
+                              double *gamma_v_net);
+/* svi! for the block network: the block step of nhp_disc_netsvi_run gives ρ̂v; the hats of the tables are 2. above at ρ̂v and
+ * the current m, the hat of m is one sweep (at global steps i that are multiples of labels_every) over a copy of m with ρ̂v
+ * and those hats; then every parameter, m included, x <- (1 - ρ_i) x + ρ_i x̂ (a convex combination keeps m on the
+ * simplex); at a step without a sweep m has no hat and stays bit for bit.  Blocks, seeds, step0 and the two modes as nhp_disc_svi_run.  One block, delay 0, forgetting 1, one step is
+ * one step of nhp_disc_sbmvb_run. */
+nhp_status nhp_disc_sbmsvi_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
+                               double alpha0, double beta0, double kappa0, double nu0, double kappa1, double nu1, double gamma,
+                               int32_t n_blocks, double net_alpha, double net_beta, double net_gamma, int32_t labels_every,
+                               int64_t batch_bins, double delay, double forgetting, uint64_t seed, int64_t step0, int32_t n_steps,
+                               const int32_t *blocks /* nullable [n_steps] */, const double *phi /* nullable */, int32_t n_lags,
+                               int32_t n_basis, double *alpha_v, double *beta_v, double *kappa_v0, double *nu_v0, double *kappa_v1,
+                               double *nu_v1, double *gamma_v, double *rho_v, double *m, double *net_alpha_v, double *net_beta_v,
+                               double *gamma_v_net);
 /* The blocks nhp_disc_svi_run draws for global steps step0 + 1 .. step0 + n (host side, no device): out[k] =
  * min(nb - 1, floor(nb · u_i)), u_i the Philox4x32-10 uniform in [0, 1) with key seed ^ 0x5C1B10C5D2A7E391, counter words
  * (event = 0, step = i), i = step0 + k + 1 -- a function of (seed, i) alone. */

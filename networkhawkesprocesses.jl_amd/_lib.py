@@ -155,6 +155,10 @@ def _declare(lib):
       _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp)
     f("nhp_disc_netsvi_run", i32, _vp, _vp, dbl, dbl, dbl, dbl, dbl, dbl, dbl, dbl, i32, dbl, dbl, i64, dbl, dbl, u64, i64, i32, i32p,
       _dp, i32, i32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp)
+    f("nhp_disc_sbmvb_run", i32, _vp, _vp, dbl, dbl, dbl, dbl, dbl, dbl, dbl, dbl, i32, dbl, dbl, dbl, i32, i64, i32,
+      _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp)
+    f("nhp_disc_sbmsvi_run", i32, _vp, _vp, dbl, dbl, dbl, dbl, dbl, dbl, dbl, dbl, i32, dbl, dbl, dbl, i32, i64, dbl, dbl, u64, i64, i32,
+      i32p, _dp, i32, i32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp)
     f("nhp_cont_resample_adjacency", i32, _vp, _vp, _vp, _dp, dbl, _dp, u64, u64, _dp, _dp)
     f("nhp_probe_math", i32, _vp, i32, _dp, _dp, i64, _dp)
     f("nhp_probe_draws", i32, _vp, i32, u64, u64, i64, _dp, _dp, _dp)

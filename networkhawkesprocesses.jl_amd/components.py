@@ -443,7 +443,8 @@ class StochasticBlockNetworkModel(Network):
     for all N² entries (the diagonal is counted, as BernoulliNetworkModel counts it).  Labels are 0-based.  With one
     block this is BernoulliNetworkModel.  params() is [vec(ρ) column-major; π]; the labels are latent state, not
     parameters.  Block labels are identified only up to a permutation, so a chain can switch them: summaries of ρ, π
-    and the labels over a chain are meaningful only as long as it did not."""
+    and the labels over a chain are meaningful only as long as it did not.  The variational state (mv, αv, βv, γv) of
+    update_ / vb_ / svi_ on a discrete network process is None until variational_init_ creates it."""
 
     def __init__(self, nnodes, nblocks, ρ=None, π=None, z=None, α=1.0, β=1.0, γ=1.0):
         self.nnodes, self.nblocks = int(nnodes), int(nblocks)
@@ -462,6 +463,43 @@ class StochasticBlockNetworkModel(Network):
             raise _lib.DomainError("ρ must lie in the open interval (0, 1)")
         if not (np.all(self.π > 0) and abs(self.π.sum() - 1.0) <= 1e-12):
             raise _lib.DomainError("π must be positive and sum to 1")
+        # the variational state: None until variational_init_ creates it
+        self.mv = self.αv = self.βv = self.γv = None
+        self.labels_every, self.vb_step = 1, 0
+
+    def variational_init_(self, seed=None, sharpness=0.5, labels_every=1):
+        """Create the variational state of update_ / vb_ / svi_: q(z_n) = Categorical(mv[n,:]), q(ρ[k,l]) = Beta(αv, βv),
+        q(π) = Dirichlet(γv), with mv = sharpness·onehot(z) + (1 - sharpness)/K around the current labels, αv = α, βv = β,
+        γv = γ.  With a seed every row of mv is mixed with a Dirichlet(1) draw (weight 0.1), which breaks ties between
+        nodes that share a label.  Mean-field over labels has the uniform state as a fixed point: from mv ≡ 1/K every node
+        sees the same blocks, every label scores the same and nothing ever moves.  sharpness = 0 is that state and is
+        refused; nothing creates this state implicitly, which is why a freshly constructed model has no variational
+        update.  The sweep over the labels runs at the steps whose global number is a multiple of labels_every, as in
+        mcmc_: vb_step counts the steps update_ / vb_ have taken since this call (0 here), whether they came one per call
+        or many, and svi_ counts with its own step0."""
+        K, N = self.nblocks, self.nnodes
+        if not 0.0 < sharpness <= 1.0:
+            raise ValueError("variational_init!: sharpness must lie in (0, 1]; 0 is the symmetric fixed point of the label "
+                             "update, from which no step moves")
+        if int(labels_every) < 1:
+            raise ValueError("labels_every must be a positive integer")
+        m = np.full((N, K), (1.0 - sharpness) / K)
+        m[np.arange(N), self.z] += sharpness
+        if seed is not None:
+            m = 0.9 * m + 0.1 * np.random.default_rng(seed).dirichlet(np.ones(K), N)
+        self.mv = m / m.sum(axis=1, keepdims=True)
+        self.αv, self.βv = np.full((K, K), self.α), np.full((K, K), self.β)
+        self.γv = np.full(K, self.γ)
+        self.labels_every, self.vb_step = int(labels_every), 0
+        return self
+
+    def has_variational_state(self):
+        return self.mv is not None
+
+    def variational_params(self):
+        """[vec(αv); vec(βv); γv; vec(mv)], column-major"""
+        return np.concatenate([np.asarray(self.αv).ravel(order="F"), np.asarray(self.βv).ravel(order="F"), np.asarray(self.γv),
+                               np.asarray(self.mv).ravel(order="F")])
 
     def params(self):
         return np.concatenate([self.ρ.ravel(order="F"), self.π])

@@ -19,6 +19,7 @@
 #include "nhp_internal.h"
 #include "nhp_math.h"
 #include "nhp_netvb.h"
+#include "nhp_sbmvb.h"
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 
@@ -1690,7 +1691,24 @@ __device__ __forceinline__ double netvb_sigmoid(double x)
 // (VB: nb = 1 and γ̂ = γ + Γ as k_vb_finish writes it); ρ̂ from the logit at the hats and the OLD network parameters
 // netp = (αv, βv); then x <- x̂ (VB) or x <- (1 - r) x + r x̂ (SVI), ρv included.  Every workgroup leaves the pair
 // (Σ ρ̂, Σ (1 - ρ̂)) of its 256 links in partials[2·blockIdx.x ..]: the order inside nhp_block_sum2_n is fixed.
-template <bool SVI>
+// What the finish kernel reads for a block network: net[p,c] = Σ_l (m·D)[p,l] m[c,l] off the diagonal and
+// Σ_k m[p,k] D[k,k] on it (a node has one label), D = ψ(αv) - ψ(βv) per pair of blocks; an SVI step also keeps ρ̂.
+struct sbmvb_link {
+    int K;
+    const double *m, *mD, *D;
+    double *rho_hat;
+};
+__device__ __forceinline__ double sbmvb_net(const sbmvb_link &s, size_t N, size_t p, size_t c)
+{
+    double net = 0.0;
+    if (p == c)
+        for (int k = 0; k < s.K; ++k) net += s.m[p + (size_t)k * N] * s.D[(size_t)k * s.K + k];
+    else
+        for (int l = 0; l < s.K; ++l) net += s.mD[p + (size_t)l * N] * s.m[c + (size_t)l * N];
+    return net;
+}
+
+template <bool SVI, bool SBM = false>
 __global__ __launch_bounds__(256) void k_netvb_finish(int N, int B, int n_slabs, const double *__restrict__ slabs,
                                                       const double *__restrict__ E, const double *__restrict__ colsum,
                                                       double kappa0, double nu0, double kappa1, double nu1, double gamma,
@@ -1699,7 +1717,7 @@ __global__ __launch_bounds__(256) void k_netvb_finish(int N, int B, int n_slabs,
                                                       double *__restrict__ kappa_v0, double *__restrict__ nu_v0,
                                                       double *__restrict__ kappa_v1, double *__restrict__ nu_v1,
                                                       double *__restrict__ gamma_v, double *__restrict__ rho_v,
-                                                      double *__restrict__ partials)
+                                                      double *__restrict__ partials, sbmvb_link blk)
 {
     __shared__ double red[2 * NHP_WAVES];
     const size_t NN = (size_t)N * N, K = (size_t)N * B;
@@ -1728,8 +1746,9 @@ __global__ __launch_bounds__(256) void k_netvb_finish(int N, int B, int n_slabs,
         if (net_kind == 0) {
             rh = 1.0;
         } else {
-            const double net = nhp_digamma(netp[0]) - nhp_digamma(netp[1]);
+            const double net = SBM ? sbmvb_net(blk, (size_t)N, p, c) : nhp_digamma(netp[0]) - nhp_digamma(netp[1]);
             rh = netvb_sigmoid(netvb_logit(net, prior, kappa1 - kappa0, nu1 - nu0, k0h, n0h, n1h));
+            if (SBM && SVI) blk.rho_hat[pc] = rh;
         }
         rc = 1.0 - rh;
         if (SVI) {
@@ -1767,6 +1786,316 @@ __global__ __launch_bounds__(256) void k_netvb_network(int n_pairs, const double
             netp[0] = ah; netp[1] = bh;
         }
     }
+}
+
+// ---- the block network's variational layer: q(z_n) = Categorical(m[n,:]), q(π) = Dirichlet(γv),
+// q(ρ[k,l]) = Beta(αv[k,l], βv[k,l]) around the per-link step above.  m is [n, k] and the K x K tables [k, l], column-major.
+
+// The expectations of one set of tables: D = ψ(αv) - ψ(βv) (= E1 - E0, the ψ(αv + βv) cancels and is never formed),
+// E1 = ψ(αv) - ψ(αv + βv), E0 = ψ(βv) - ψ(αv + βv), their transposes (the sweep reads a row and a column of each, both
+// with consecutive threads on consecutive addresses) and Eπ = ψ(γv) - ψ(Σγv), γv added in increasing k.
+__global__ __launch_bounds__(256) void k_sbmvb_expect(int K, const double *__restrict__ alpha_v, const double *__restrict__ beta_v,
+                                                      const double *__restrict__ gamma_v, double *__restrict__ D,
+                                                      double *__restrict__ tabs, double *__restrict__ Epi)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    double *E1 = tabs, *E0 = tabs + K * K, *E1T = tabs + 2 * K * K, *E0T = tabs + 3 * K * K;   // the layout k_sbmvb_sweep reads
+    if (i < K * K) {
+        const int k = i % K, l = i / K;
+        const double da = nhp_digamma(alpha_v[i]), db = nhp_digamma(beta_v[i]), ds = nhp_digamma(alpha_v[i] + beta_v[i]);
+        D[i] = da - db;
+        E1[i] = da - ds; E0[i] = db - ds;
+        E1T[l + k * K] = da - ds; E0T[l + k * K] = db - ds;
+    }
+    if (i < K) {
+        double gs = 0.0;
+        for (int k = 0; k < K; ++k) gs += gamma_v[k];
+        Epi[i] = nhp_digamma(gamma_v[i]) - nhp_digamma(gs);
+    }
+}
+
+// (m·D)[n, l] = Σ_k m[n,k] D[k,l], k increasing: after it a link's network term costs K multiply-adds
+__global__ __launch_bounds__(256) void k_sbmvb_md(int N, int K, const double *__restrict__ m, const double *__restrict__ D,
+                                                  double *__restrict__ mD)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)N * K) return;
+    const size_t n = i % N, l = i / N;
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) s += m[n + (size_t)k * N] * D[k + l * K];
+    mD[i] = s;
+}
+
+// U1[p, l] = Σ_{c≠p} ρv[p,c] m[c,l] and U0[p, l] = Σ_{c≠p} (1 - ρv[p,c]) m[c,l], c increasing.  One thread per (p, l) with
+// p fastest: a wave reads 64 consecutive p of column c of ρv (ρv is [p, c] column-major) and one m[c, l], so the product
+// that walks ρv along its rows is coalesced as it stands and ρvᵀ is never needed.  The diagonal is left out here and
+// enters the tables with its own weight.
+__global__ __launch_bounds__(256) void k_sbmvb_u(int N, int K, const double *__restrict__ rho, const double *__restrict__ m,
+                                                 double *__restrict__ U1, double *__restrict__ U0)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)N * K) return;
+    const size_t p = i % N, l = i / N;
+    double u1 = 0.0, u0 = 0.0;
+    for (size_t c = 0; c < (size_t)N; ++c) {
+        if (c == p) continue;
+        const double r = rho[p + c * N], mm = m[c + l * N];
+        u1 += r * mm;
+        u0 += (1.0 - r) * mm;
+    }
+    U1[i] = u1; U0[i] = u0;
+}
+
+// One workgroup per pair (k, l): αv[k,l] = α + Σ_p m[p,k] (U1[p,l] + δ_kl ρv[p,p]), βv likewise from U0 and 1 - ρv[p,p]
+// (ω[p,p,k,l] = m[p,k] δ_kl: a node has one label), and for l = 0 also γv[k] = γ + Σ_p m[p,k].  Thread i adds the nodes
+// i, i + 256, ... in increasing order and nhp_block_sum2_n joins the threads in its fixed order; every term is >= 0.
+__global__ __launch_bounds__(256) void k_sbmvb_tables(int N, int K, const double *__restrict__ rho, const double *__restrict__ m,
+                                                      const double *__restrict__ U1, const double *__restrict__ U0,
+                                                      double alpha, double beta, double gamma, double *__restrict__ alpha_v,
+                                                      double *__restrict__ beta_v, double *__restrict__ gamma_v)
+{
+    __shared__ double red[2 * NHP_WAVES];
+    const size_t k = blockIdx.x % K, l = blockIdx.x / K;
+    double a = 0.0, b = 0.0, g = 0.0;
+    for (size_t p = threadIdx.x; p < (size_t)N; p += 256) {
+        const double mk = m[p + k * N];
+        double u1 = U1[p + l * N], u0 = U0[p + l * N];
+        if (k == l) { const double r = rho[p + p * N]; u1 += r; u0 += 1.0 - r; }
+        a += mk * u1;
+        b += mk * u0;
+        g += mk;
+    }
+    nhp_block_sum2_n<NHP_WAVES>(a, b, red);
+    if (threadIdx.x == 0) { alpha_v[blockIdx.x] = alpha + a; beta_v[blockIdx.x] = beta + b; }
+    if (l == 0) {
+        g = nhp_block_sum_n<NHP_WAVES>(g, red);
+        if (threadIdx.x == 0) gamma_v[k] = gamma + g;
+    }
+}
+
+// The label sweep: sequential coordinate ascent over the nodes 0 .. N-1 in ONE workgroup, each node reading the current m
+// of all others.  m lives in LDS as [n][k]; row n and column n of ρv are in LDS too and those of node n + 1 are requested
+// into registers before node n's sums start (they do not change during a sweep), so their latency hides behind the sums.
+// For node n the 256 threads are dealt as (l, g), l < Kp (the next power of two of K), g < 256/Kp: thread (l, g) adds, over
+// the nodes c = g, g + 256/Kp, ... ≠ n in increasing order, the four sums
+//   A1[l] = Σ ρv[n,c] m[c,l],  A0[l] = Σ (1 - ρv[n,c]) m[c,l],  B1[l] = Σ ρv[c,n] m[c,l],  B0[l] = Σ (1 - ρv[c,n]) m[c,l]
+// fresh from the LDS copy of m (no second table, nothing accumulates from node to node); a butterfly over the lanes of
+// equal l, one LDS pass over the four waves in increasing order, and the first K lanes of wave 0 hold
+//   s_k = Eπ[k] + ρv[n,n] E1[k,k] + (1 - ρv[n,n]) E0[k,k] + Σ_l (A1[l] E1[k,l] + A0[l] E0[k,l] + B1[l] E1[l,k] + B0[l] E0[l,k]),
+// m[n,:] = softmax(s) shifted by its maximum: an entry may underflow to exactly 0, the largest is exp(0) = 1, so the
+// normaliser is >= 1 and nothing is NaN.  Every order is fixed: the sweep is reproducible bit for bit.
+// `tabs` is ONE block of 4·K² doubles, E1, E0, E1ᵀ, E0ᵀ in that order (sbmvb_bufs::tabs, the only pointer to them that
+// is handed out).  TAB: the block is copied to LDS once per sweep, when it fits next to the rest; a score then waits on
+// LDS and not, K times in a row, on global loads.
+template <int NPT, bool TAB>
+__global__ __launch_bounds__(256) void k_sbmvb_sweep(int N, int K, int Kp, const double *__restrict__ rho,
+                                                     const double *__restrict__ tabs, const double *__restrict__ Epi,
+                                                     double *__restrict__ m)
+{
+    extern __shared__ double sbmvb_lds[];
+    double *ml = sbmvb_lds;                            // m[n*K + k]
+    double *row = ml + (size_t)N * K;                  // ρv[n, c] of the current node
+    double *col = row + N;                             // ρv[p, n]
+    double *wsum = col + N;                            // [(wave*4 + q)*Kp + l]
+    double *fin = wsum + SBMVB_WAVES * 4 * Kp;         // [q*Kp + l]
+    double *tab = fin + 4 * Kp;                        // TAB: the four tables, K² each
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int l = t & (Kp - 1), g = t / Kp, G = 256 / Kp;
+    const int KK = K * K;
+    if (TAB)
+        for (int i = t; i < 4 * KK; i += 256) tab[i] = tabs[i];
+    const double *tb = TAB ? tab : tabs;
+    const double *e1 = tb, *e0 = tb + KK, *e1t = tb + 2 * KK, *e0t = tb + 3 * KK;
+    for (int i = t; i < N * K; i += 256) ml[(i % N) * K + i / N] = m[i];
+    for (int c = t; c < N; c += 256) { row[c] = rho[(size_t)c * N]; col[c] = rho[c]; }
+    const double epi = t < K ? Epi[t] : 0.0;           // lane k of wave 0 keeps Eπ[k] for the whole sweep
+    __syncthreads();
+    for (int n = 0; n < N; ++n) {
+        double nr[NPT], nc[NPT];
+        if (n + 1 < N) {
+#pragma unroll
+            for (int i = 0; i < NPT; ++i) {
+                const int c = t + i * 256;
+                if (c < N) { nr[i] = rho[(size_t)(n + 1) + (size_t)c * N]; nc[i] = rho[(size_t)c + (size_t)(n + 1) * N]; }
+            }
+        }
+        double a1 = 0.0, a0 = 0.0, b1 = 0.0, b0 = 0.0;
+#pragma unroll 4
+        for (int c = g; c < N; c += G) {               // node n itself enters with weight 0: no branch in the loop
+            const double mm = (l < K && c != n) ? ml[c * K + l] : 0.0;
+            const double r = row[c], q = col[c];
+            a1 += r * mm;
+            a0 += (1.0 - r) * mm;
+            b1 += q * mm;
+            b0 += (1.0 - q) * mm;
+        }
+        const double rnn = row[n];
+        for (int off = Kp; off < 64; off <<= 1) {
+            a1 += __shfl_xor(a1, off);
+            a0 += __shfl_xor(a0, off);
+            b1 += __shfl_xor(b1, off);
+            b0 += __shfl_xor(b0, off);
+        }
+        if (lane < Kp) {
+            wsum[(w * 4 + 0) * Kp + lane] = a1;
+            wsum[(w * 4 + 1) * Kp + lane] = a0;
+            wsum[(w * 4 + 2) * Kp + lane] = b1;
+            wsum[(w * 4 + 3) * Kp + lane] = b0;
+        }
+        __syncthreads();                               // every read of row / col for node n is done
+        if (n + 1 < N) {
+#pragma unroll
+            for (int i = 0; i < NPT; ++i) {
+                const int c = t + i * 256;
+                if (c < N) { row[c] = nr[i]; col[c] = nc[i]; }
+            }
+        }
+        if (t < 4 * Kp) {                              // t = q*Kp + l
+            double s = 0.0;
+            for (int v = 0; v < SBMVB_WAVES; ++v) s += wsum[v * 4 * Kp + t];
+            fin[t] = s;
+        }
+        __syncthreads();
+        if (w == 0) {
+            double s = -INFINITY;
+            if (lane < K) {
+                const int k = lane;
+                s = epi + (rnn * e1[k + k * K] + (1.0 - rnn) * e0[k + k * K]);
+                for (int j = 0; j < K; ++j)
+                    s += (fin[j] * e1[k + j * K] + fin[Kp + j] * e0[k + j * K]) +
+                         (fin[2 * Kp + j] * e1t[k + j * K] + fin[3 * Kp + j] * e0t[k + j * K]);
+            }
+            double mx = s;                             // butterflies over the first Kp lanes only: log2(Kp) stages
+            for (int off = Kp >> 1; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
+            const double e = lane < K ? nhp_exp(s - mx) : 0.0;
+            double z = e;
+            for (int off = Kp >> 1; off > 0; off >>= 1) z += __shfl_xor(z, off);
+            if (lane < K) {
+                const double v = e / z;
+                ml[n * K + lane] = v;
+                m[(size_t)n + (size_t)lane * N] = v;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// x <- (1 - r) x + r x̂ over the block model's state (m, αv, βv, γv, contiguous): a convex combination keeps m on the simplex
+__global__ __launch_bounds__(256) void k_sbmvb_blend(size_t n, double r, const double *__restrict__ hat, double *__restrict__ x)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const double keep = 1.0 - r;
+    if (i < n) x[i] = keep * x[i] + r * hat[i];
+}
+
+// the block model's part of a run: the priors, the schedule of the sweep and the caller's in/out arrays
+struct sbmvb_args {
+    int32_t K;
+    double alpha, beta, gamma;
+    int32_t labels_every;
+    int64_t step0;                                     // VB: steps already taken (SVI has its own step0)
+    double *m, *alpha_v, *beta_v, *gamma_v;
+};
+
+// its device block, after the network run's own (netvb_bufs::end), in the order sbmvb_param_doubles counts it
+struct sbmvb_bufs {
+    double *m, *av, *bv, *gv, *mh, *avh, *bvh, *gvh, *D, *tabs, *Epi, *mD, *U1, *U0, *rho_hat, *end;
+};
+static sbmvb_bufs sbmvb_carve(double *p, size_t N, size_t K, bool svi)
+{
+    const size_t NK = N * K, KK = K * K;
+    sbmvb_bufs s;
+    s.m = p; p += NK;
+    s.av = p; p += KK;
+    s.bv = p; p += KK;
+    s.gv = p; p += K;
+    s.mh = p; p += NK;
+    s.avh = p; p += KK;
+    s.bvh = p; p += KK;
+    s.gvh = p; p += K;
+    s.D = p; p += KK;
+    s.tabs = p; p += 4 * KK;                           // E1, E0, E1ᵀ, E0ᵀ
+    s.Epi = p; p += K;
+    s.mD = p; p += NK;
+    s.U1 = p; p += NK;
+    s.U0 = p; p += NK;
+    s.rho_hat = p; p += svi ? N * N : 0;
+    s.end = p;
+    return s;
+}
+
+static nhp_status sbmvb_check(nhp_ctx *ctx, const char *what, int64_t N, const sbmvb_args &a)
+{
+    char msg[256];
+    const int rc = sbmvb_check_args(what, N, a.K, a.alpha, a.beta, a.gamma, a.labels_every, a.m, a.alpha_v, a.beta_v, a.gamma_v, msg, sizeof msg);
+    if (rc == NETVB_OK) return NHP_OK;
+    nhp_set_error(ctx, "%s", msg);
+    return rc == NETVB_ENOTIMPL ? NHP_ENOTIMPL : NHP_EINVAL;
+}
+
+static nhp_status sbmvb_copy(nhp_ctx *ctx, hipStream_t st, const sbmvb_bufs &s, const sbmvb_args &a, size_t N, bool up)
+{
+    const size_t K = (size_t)a.K;
+    double *dev[4] = {s.m, s.av, s.bv, s.gv}, *host[4] = {a.m, a.alpha_v, a.beta_v, a.gamma_v};
+    const size_t bytes[4] = {8 * N * K, 8 * K * K, 8 * K * K, 8 * K};
+    for (int i = 0; i < 4; ++i)
+        NHP_HIP(ctx, up ? hipMemcpyAsync(dev[i], host[i], bytes[i], hipMemcpyHostToDevice, st)
+                        : hipMemcpyAsync(host[i], dev[i], bytes[i], hipMemcpyDeviceToHost, st));
+    return NHP_OK;
+}
+
+// before the finish kernel: D from the OLD tables and m·D from the OLD m
+static void sbmvb_before_finish(hipStream_t st, const sbmvb_bufs &s, size_t N, size_t K)
+{
+    hipLaunchKernelGGL(k_sbmvb_expect, dim3((unsigned)((K * K + 255) / 256)), dim3(256), 0, st, (int)K, s.av, s.bv, s.gv, s.D, s.tabs,
+                       s.Epi);
+    hipLaunchKernelGGL(k_sbmvb_md, dim3((unsigned)((N * K + 255) / 256)), dim3(256), 0, st, (int)N, (int)K, s.m, s.D, s.mD);
+}
+
+static nhp_status sbmvb_launch_sweep(nhp_ctx *ctx, hipStream_t st, const sbmvb_bufs &s, size_t N, size_t K, const double *rho, double *m)
+{
+    const size_t need = sbmvb_sweep_lds_bytes(N, K), with_tables = need + sbmvb_sweep_table_bytes(K);
+    const bool tab = with_tables <= (size_t)SBMVB_LDS_LIMIT;      // the tables ride along when they fit; the limit is `need`
+    const size_t lds = tab ? with_tables : need;
+    const int Kp = (int)sbmvb_pow2(K);
+#define NHP_SBMVB_SWEEP_(npt, tb)                                                                                                    \
+    do {                                                                                                                             \
+        if (lds > 64 * 1024)                                                                                                         \
+            NHP_HIP(ctx, hipFuncSetAttribute((const void *)k_sbmvb_sweep<npt, tb>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+        hipLaunchKernelGGL((k_sbmvb_sweep<npt, tb>), dim3(1), dim3(SBMVB_THREADS), lds, st, (int)N, (int)K, Kp, rho, s.tabs, s.Epi, m); \
+    } while (0)
+#define NHP_SBMVB_SWEEP(npt) do { if (tab) NHP_SBMVB_SWEEP_(npt, true); else NHP_SBMVB_SWEEP_(npt, false); } while (0)
+    if (N <= 256) NHP_SBMVB_SWEEP(1);
+    else if (N <= 1024) NHP_SBMVB_SWEEP(4);
+    else if (N <= 4096) NHP_SBMVB_SWEEP(16);
+    else NHP_SBMVB_SWEEP(32);                          // the LDS limit keeps N below 8192
+#undef NHP_SBMVB_SWEEP
+#undef NHP_SBMVB_SWEEP_
+    return NHP_OK;
+}
+
+// after the finish kernel: the tables from the NEW ρv (SVI: ρ̂v) and the current m, then the sweep when this step has one.
+// VB writes the state itself; SVI writes the hats, sweeps a copy of m and blends.
+static nhp_status sbmvb_after_finish(nhp_ctx *ctx, hipStream_t st, const sbmvb_bufs &s, const sbmvb_args &a, size_t N, const double *rho,
+                                     bool svi, bool sweep, double r)
+{
+    const size_t K = (size_t)a.K, NK = N * K;
+    double *av = svi ? s.avh : s.av, *bv = svi ? s.bvh : s.bv, *gv = svi ? s.gvh : s.gv, *m = svi ? s.mh : s.m;
+    hipLaunchKernelGGL(k_sbmvb_u, dim3((unsigned)((NK + 255) / 256)), dim3(256), 0, st, (int)N, (int)K, rho, s.m, s.U1, s.U0);
+    hipLaunchKernelGGL(k_sbmvb_tables, dim3((unsigned)(K * K)), dim3(256), 0, st, (int)N, (int)K, rho, s.m, s.U1, s.U0, a.alpha, a.beta,
+                       a.gamma, av, bv, gv);
+    if (sweep) {
+        if (svi) NHP_HIP(ctx, hipMemcpyAsync(s.mh, s.m, 8 * NK, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(k_sbmvb_expect, dim3((unsigned)((K * K + 255) / 256)), dim3(256), 0, st, (int)K, av, bv, gv, s.D, s.tabs,
+                           s.Epi);
+        NHP_TRY(sbmvb_launch_sweep(ctx, st, s, N, K, rho, m));
+    }
+    if (svi) {                                         // a step without a sweep has no m̂: m stays bit for bit, the tables blend
+        const size_t skip = sweep ? 0 : NK, n = sbmvb_state_doubles(N, K) - skip;
+        hipLaunchKernelGGL(k_sbmvb_blend, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, r, s.mh + skip, s.m + skip);
+    }
+    NHP_HIP(ctx, hipGetLastError());
+    return NHP_OK;
 }
 
 // the device block of a network run's parameters, in the order netvb_param_doubles counts them
@@ -1846,18 +2175,23 @@ static nhp_status netvb_check(nhp_ctx *ctx, const char *what, const nhp_disc_dat
     return rc == NETVB_ENOTIMPL ? NHP_ENOTIMPL : NHP_EINVAL;
 }
 
-extern "C" nhp_status nhp_disc_netvb_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
-                                         double alpha0, double beta0, double kappa0, double nu0, double kappa1, double nu1, double gamma,
-                                         int32_t net_kind, double net_alpha, double net_beta, int32_t n_steps,
-                                         double *alpha_v, double *beta_v, double *kappa_v0, double *nu_v0, double *kappa_v1,
-                                         double *nu_v1, double *gamma_v, double *rho_v, double *net_alpha_v, double *net_beta_v)
+// The VB run of a dense or Bernoulli network (sb = nullptr) or of a block network (sb: net_kind is 1 for the checks and the
+// kernels, the scalar network parameters are placeholders nobody reads).
+static nhp_status netvb_run_impl(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
+                                 double alpha0, double beta0, double kappa0, double nu0, double kappa1, double nu1, double gamma,
+                                 int32_t net_kind, double net_alpha, double net_beta, int32_t n_steps,
+                                 double *alpha_v, double *beta_v, double *kappa_v0, double *nu_v0, double *kappa_v1,
+                                 double *nu_v1, double *gamma_v, double *rho_v, double *net_alpha_v, double *net_beta_v,
+                                 const sbmvb_args *sb)
 {
     if (!ctx || !ds) return NHP_EINVAL;
+    const char *what = sb ? "sbmvb" : "netvb";
     const netvb_priors q{alpha0, beta0, kappa0, nu0, kappa1, nu1, gamma, net_kind, net_alpha, net_beta};
     const netvb_host h{alpha_v, beta_v, kappa_v0, nu_v0, kappa_v1, nu_v1, gamma_v, rho_v, net_alpha_v, net_beta_v};
-    if (!ds->d_conv) { nhp_set_error(ctx, "netvb: convolve(process, data) must run before update!"); return NHP_EINVAL; }
-    if (ds->d_baseT) { nhp_set_error(ctx, "netvb: defined for DiscreteHomogeneousProcess baselines only"); return NHP_ENOTIMPL; }
-    NHP_TRY(netvb_check(ctx, "netvb", ds, q, dt, ds->B, n_steps, h));
+    if (!ds->d_conv) { nhp_set_error(ctx, "%s: convolve(process, data) must run before update!", what); return NHP_EINVAL; }
+    if (ds->d_baseT) { nhp_set_error(ctx, "%s: defined for DiscreteHomogeneousProcess baselines only", what); return NHP_ENOTIMPL; }
+    NHP_TRY(netvb_check(ctx, what, ds, q, dt, ds->B, n_steps, h));
+    if (sb) NHP_TRY(sbmvb_check(ctx, what, ds->N, *sb));
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t N = (size_t)ds->N, B = (size_t)ds->B, K = N * B, T = (size_t)ds->T;
     const int bm = gemm1_tile_m((int64_t)T, (int)N, ctx->cu_count);
@@ -1865,7 +2199,9 @@ extern "C" nhp_status nhp_disc_netvb_run(nhp_ctx *ctx, const nhp_disc_dataset *d
     const int tiles2 = (int)(((K + BM - 1) / BM) * ((N + BN - 1) / BN));
     int splits, k_chunk;
     svi_split((int64_t)T, tiles2, ctx->cu_count, &splits, &k_chunk);          // the rule of nhp_disc_vb_run
-    const size_t need = 8 * (netvb_param_doubles(N, B) + T * N + (size_t)row_blocks * N + (size_t)splits * K * N);
+    const size_t KB = sb ? (size_t)sb->K : 0;
+    const size_t need = 8 * (netvb_param_doubles(N, B) + T * N + (size_t)row_blocks * N + (size_t)splits * K * N +
+                             (sb ? sbmvb_param_doubles(N, KB, false) : 0));
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, need));
     const netvb_bufs u = netvb_carve((double *)ctx->d_scratch, N, B);
     double *dR = u.end, *dcolp = dR + T * N, *dslab = dcolp + (size_t)row_blocks * N;
@@ -1874,6 +2210,11 @@ extern "C" nhp_status nhp_disc_netvb_run(nhp_ctx *ctx, const nhp_disc_dataset *d
     double net_stage[2];
     hipStream_t st = ctx->main();
     NHP_TRY(netvb_upload(ctx, st, u, h, N, B, net_kind, net_stage));
+    sbmvb_bufs s{};
+    if (sb) {
+        s = sbmvb_carve(dslab + (size_t)splits * K * N, N, KB, false);
+        NHP_TRY(sbmvb_copy(ctx, st, s, *sb, N, true));
+    }
     for (int step = 0; step < n_steps; ++step) {      // every parameter stays on the device between steps
         hipLaunchKernelGGL(k_netvb_factors, dim3(link_blocks), dim3(256), 0, st, (int)N, (int)B, u.av, u.bv, u.kv0, u.nv0, u.kv1, u.nv1,
                            u.gv, u.rho, u.E, u.e0);
@@ -1890,54 +2231,93 @@ extern "C" nhp_status nhp_disc_netvb_run(nhp_ctx *ctx, const nhp_disc_dataset *d
         NHP_HIP(ctx, hipGetLastError());
         hipLaunchKernelGGL(k_vb_baseline, dim3((unsigned)((N + 63) / 64)), dim3(256), 0, st, (int)N, row_blocks, dcolp, u.e0,
                            alpha0, beta0, (double)T * dt, u.av, u.bv);
+        if (sb) {                                     // the block network: a per-link term in, tables and the sweep after
+            sbmvb_before_finish(st, s, N, KB);
+            hipLaunchKernelGGL((k_netvb_finish<false, true>), dim3(link_blocks), dim3(256), 0, st, (int)N, (int)B, splits, dslab, u.E,
+                               ds->d_colsum, kappa0, nu0, kappa1, nu1, gamma, 1.0, 1.0, 1, prior, u.netp, u.kv0, u.nv0, u.kv1, u.nv1, u.gv,
+                               u.rho, u.part, sbmvb_link{(int)KB, s.m, s.mD, s.D, nullptr});
+            NHP_TRY(sbmvb_after_finish(ctx, st, s, *sb, N, u.rho, false, (sb->step0 + step + 1) % sb->labels_every == 0, 1.0));
+            continue;
+        }
         hipLaunchKernelGGL(k_netvb_finish<false>, dim3(link_blocks), dim3(256), 0, st, (int)N, (int)B, splits, dslab, u.E, ds->d_colsum,
                            kappa0, nu0, kappa1, nu1, gamma, 1.0, 1.0, (int)net_kind, prior, u.netp, u.kv0, u.nv0, u.kv1, u.nv1, u.gv,
-                           u.rho, u.part);
+                           u.rho, u.part, sbmvb_link{});
         if (net_kind)
             hipLaunchKernelGGL(k_netvb_network<false>, dim3(1), dim3(256), 0, st, (int)link_blocks, u.part, net_alpha, net_beta, 1.0, u.netp);
         NHP_HIP(ctx, hipGetLastError());
     }
+    if (sb) NHP_TRY(sbmvb_copy(ctx, st, s, *sb, N, false));
     return netvb_download(ctx, st, u, h, N, B, net_kind, net_stage);
 }
 
-extern "C" nhp_status nhp_disc_netsvi_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
-                                          double alpha0, double beta0, double kappa0, double nu0, double kappa1, double nu1, double gamma,
-                                          int32_t net_kind, double net_alpha, double net_beta,
-                                          int64_t batch_bins, double delay, double forgetting, uint64_t seed, int64_t step0,
-                                          int32_t n_steps, const int32_t *blocks, const double *phi, int32_t n_lags, int32_t n_basis,
-                                          double *alpha_v, double *beta_v, double *kappa_v0, double *nu_v0, double *kappa_v1,
-                                          double *nu_v1, double *gamma_v, double *rho_v, double *net_alpha_v, double *net_beta_v)
+extern "C" nhp_status nhp_disc_netvb_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
+                                         double alpha0, double beta0, double kappa0, double nu0, double kappa1, double nu1, double gamma,
+                                         int32_t net_kind, double net_alpha, double net_beta, int32_t n_steps,
+                                         double *alpha_v, double *beta_v, double *kappa_v0, double *nu_v0, double *kappa_v1,
+                                         double *nu_v1, double *gamma_v, double *rho_v, double *net_alpha_v, double *net_beta_v)
+{
+    return netvb_run_impl(ctx, ds, dt, alpha0, beta0, kappa0, nu0, kappa1, nu1, gamma, net_kind, net_alpha, net_beta, n_steps, alpha_v,
+                          beta_v, kappa_v0, nu_v0, kappa_v1, nu_v1, gamma_v, rho_v, net_alpha_v, net_beta_v, nullptr);
+}
+
+// update! / vb! with a StochasticBlockNetworkModel
+extern "C" nhp_status nhp_disc_sbmvb_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
+                                         double alpha0, double beta0, double kappa0, double nu0, double kappa1, double nu1, double gamma,
+                                         int32_t n_blocks, double net_alpha, double net_beta, double net_gamma, int32_t labels_every,
+                                         int64_t step0, int32_t n_steps, double *alpha_v, double *beta_v, double *kappa_v0, double *nu_v0,
+                                         double *kappa_v1, double *nu_v1, double *gamma_v, double *rho_v, double *m,
+                                         double *net_alpha_v, double *net_beta_v, double *gamma_v_net)
+{
+    if (ctx && step0 < 0) { nhp_set_error(ctx, "sbmvb: step0 = %lld must be >= 0", (long long)step0); return NHP_EINVAL; }
+    const sbmvb_args sb{n_blocks, net_alpha, net_beta, net_gamma, labels_every, step0, m, net_alpha_v, net_beta_v, gamma_v_net};
+    double one_a = 1.0, one_b = 1.0;                  // what the Bernoulli checks and the upload read in place of (αv, βv)
+    return netvb_run_impl(ctx, ds, dt, alpha0, beta0, kappa0, nu0, kappa1, nu1, gamma, 1, 1.0, 1.0, n_steps, alpha_v, beta_v, kappa_v0,
+                          nu_v0, kappa_v1, nu_v1, gamma_v, rho_v, &one_a, &one_b, &sb);
+}
+
+// The SVI run of a dense or Bernoulli network (sb = nullptr) or of a block network, as netvb_run_impl
+static nhp_status netsvi_run_impl(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
+                                  double alpha0, double beta0, double kappa0, double nu0, double kappa1, double nu1, double gamma,
+                                  int32_t net_kind, double net_alpha, double net_beta,
+                                  int64_t batch_bins, double delay, double forgetting, uint64_t seed, int64_t step0,
+                                  int32_t n_steps, const int32_t *blocks, const double *phi, int32_t n_lags, int32_t n_basis,
+                                  double *alpha_v, double *beta_v, double *kappa_v0, double *nu_v0, double *kappa_v1,
+                                  double *nu_v1, double *gamma_v, double *rho_v, double *net_alpha_v, double *net_beta_v,
+                                  const sbmvb_args *sb)
 {
     if (!ctx || !ds) return NHP_EINVAL;
+    const char *what = sb ? "sbmsvi" : "netsvi";
     const netvb_priors q{alpha0, beta0, kappa0, nu0, kappa1, nu1, gamma, net_kind, net_alpha, net_beta};
     const netvb_host h{alpha_v, beta_v, kappa_v0, nu_v0, kappa_v1, nu_v1, gamma_v, rho_v, net_alpha_v, net_beta_v};
-    if (n_steps < 1 || step0 < 0) { nhp_set_error(ctx, "netsvi: n_steps must be >= 1 and step0 >= 0"); return NHP_EINVAL; }
-    if (!(delay >= 0.0)) { nhp_set_error(ctx, "netsvi: delay must be >= 0"); return NHP_EINVAL; }
-    if (!(forgetting > 0.5 && forgetting <= 1.0)) { nhp_set_error(ctx, "netsvi: forgetting must lie in (0.5, 1]"); return NHP_EINVAL; }
+    if (n_steps < 1 || step0 < 0) { nhp_set_error(ctx, "%s: n_steps must be >= 1 and step0 >= 0", what); return NHP_EINVAL; }
+    if (!(delay >= 0.0)) { nhp_set_error(ctx, "%s: delay must be >= 0", what); return NHP_EINVAL; }
+    if (!(forgetting > 0.5 && forgetting <= 1.0)) { nhp_set_error(ctx, "%s: forgetting must lie in (0.5, 1]", what); return NHP_EINVAL; }
     const int64_t Tn = ds->T;
     if (batch_bins < Tn && (batch_bins < 16 || batch_bins % 16 != 0)) {
-        nhp_set_error(ctx, "netsvi: batch_bins = %lld must be a multiple of 16 (>= 16), or >= the %lld bins of the data", (long long)batch_bins, (long long)Tn);
+        nhp_set_error(ctx, "%s: batch_bins = %lld must be a multiple of 16 (>= 16), or >= the %lld bins of the data", what, (long long)batch_bins, (long long)Tn);
         return NHP_EINVAL;
     }
     const int64_t Tb = std::min(batch_bins, Tn);
     const int32_t nb = (int32_t)((Tn + Tb - 1) / Tb);
     if (blocks)
         for (int32_t k = 0; k < n_steps; ++k)
-            if (blocks[k] < 0 || blocks[k] >= nb) { nhp_set_error(ctx, "netsvi: blocks[%d] = %d is outside [0, %d)", k, blocks[k], nb); return NHP_EINVAL; }
-    if (ds->d_baseT) { nhp_set_error(ctx, "netsvi: defined for DiscreteHomogeneousProcess baselines only"); return NHP_ENOTIMPL; }
+            if (blocks[k] < 0 || blocks[k] >= nb) { nhp_set_error(ctx, "%s: blocks[%d] = %d is outside [0, %d)", what, k, blocks[k], nb); return NHP_EINVAL; }
+    if (ds->d_baseT) { nhp_set_error(ctx, "%s: defined for DiscreteHomogeneousProcess baselines only", what); return NHP_ENOTIMPL; }
     const bool streamed = phi != nullptr;
-    if (streamed && (n_lags < 1 || n_basis < 1)) { nhp_set_error(ctx, "netsvi: the streamed mode needs n_lags >= 1 and n_basis >= 1"); return NHP_EINVAL; }
-    if (!streamed && !ds->d_conv) { nhp_set_error(ctx, "netsvi: convolve(process, data) must run first, or pass the basis for the streamed mode"); return NHP_EINVAL; }
-    NHP_TRY(netvb_check(ctx, "netsvi", ds, q, dt, streamed ? n_basis : ds->B, n_steps, h));
+    if (streamed && (n_lags < 1 || n_basis < 1)) { nhp_set_error(ctx, "%s: the streamed mode needs n_lags >= 1 and n_basis >= 1", what); return NHP_EINVAL; }
+    if (!streamed && !ds->d_conv) { nhp_set_error(ctx, "%s: convolve(process, data) must run first, or pass the basis for the streamed mode", what); return NHP_EINVAL; }
+    NHP_TRY(netvb_check(ctx, what, ds, q, dt, streamed ? n_basis : ds->B, n_steps, h));
+    if (sb) NHP_TRY(sbmvb_check(ctx, what, ds->N, *sb));
     const size_t N = (size_t)ds->N, B = (size_t)(streamed ? n_basis : ds->B), K = N * B, T = (size_t)Tn, L = streamed ? (size_t)n_lags : 0;
+    const size_t KB = sb ? (size_t)sb->K : 0;
     const size_t lds_conv = 8 * (256 + L + L * ((B + CONV_CB - 1) / CONV_CB * CONV_CB));
-    if (streamed && lds_conv > 64 * 1024) { nhp_set_error(ctx, "netsvi: nlags * nbasis = %d * %d exceeds the LDS budget", n_lags, n_basis); return NHP_ENOTIMPL; }
+    if (streamed && lds_conv > 64 * 1024) { nhp_set_error(ctx, "%s: nlags * nbasis = %d * %d exceeds the LDS budget", what, n_lags, n_basis); return NHP_ENOTIMPL; }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     const int tiles2 = (int)(((K + BM - 1) / BM) * ((N + BN - 1) / BN));
     const int max_splits = svi_split_cap(Tb, tiles2, ctx->cu_count);
     const size_t max_row_blocks = (size_t)((Tb + BM - 1) / BM);
     const size_t need = 8 * (netvb_param_doubles(N, B) + 2 * (size_t)Tb * N + max_row_blocks * N + (size_t)max_splits * K * N +
-                             (streamed ? (size_t)Tb * K + L * B : 0));
+                             (streamed ? (size_t)Tb * K + L * B : 0) + (sb ? sbmvb_param_doubles(N, KB, true) : 0));
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, need));
     const netvb_bufs u = netvb_carve((double *)ctx->d_scratch, N, B);
     double *p = u.end;
@@ -1946,13 +2326,18 @@ extern "C" nhp_status nhp_disc_netsvi_run(nhp_ctx *ctx, const nhp_disc_dataset *
     double *dcolp = p; p += max_row_blocks * N;
     double *dslab = p; p += (size_t)max_splits * K * N;
     double *dimg = p; p += streamed ? (size_t)Tb * K : 0;
-    double *dphi = p;
+    double *dphi = p; p += streamed ? L * B : 0;
     const unsigned link_blocks = (unsigned)netvb_link_blocks(N);
     const double prior = netvb_prior_logit(q);
     double net_stage[2];
     hipStream_t st = ctx->main();
     NHP_TRY(netvb_upload(ctx, st, u, h, N, B, net_kind, net_stage));
     if (streamed) NHP_HIP(ctx, hipMemcpyAsync(dphi, phi, 8 * L * B, hipMemcpyHostToDevice, st));
+    sbmvb_bufs s{};
+    if (sb) {
+        s = sbmvb_carve(p, N, KB, true);
+        NHP_TRY(sbmvb_copy(ctx, st, s, *sb, N, true));
+    }
     for (int32_t k = 0; k < n_steps; ++k) {           // every parameter stays on the device between steps
         const uint64_t i = (uint64_t)step0 + (uint64_t)k + 1;
         const int64_t j = blocks ? blocks[k] : svi_block_of(seed, i, nb);
@@ -1991,14 +2376,53 @@ extern "C" nhp_status nhp_disc_netsvi_run(nhp_ctx *ctx, const nhp_disc_dataset *
         NHP_HIP(ctx, hipGetLastError());
         hipLaunchKernelGGL(k_svi_baseline, dim3((unsigned)((N + 63) / 64)), dim3(256), 0, st, (int)N, row_blocks, dcolp, u.e0,
                            alpha0, beta0, (double)T * dt, (double)nb, rho, u.av, u.bv);
+        if (sb) {                                     // the block network: the hats from ρ̂v and the current m, then the blend
+            sbmvb_before_finish(st, s, N, KB);
+            hipLaunchKernelGGL((k_netvb_finish<true, true>), dim3(link_blocks), dim3(256), 0, st, (int)N, (int)B, splits, dslab, u.E,
+                               ds->d_colsum, kappa0, nu0, kappa1, nu1, gamma, (double)nb, rho, 1, prior, u.netp, u.kv0, u.nv0, u.kv1, u.nv1,
+                               u.gv, u.rho, u.part, sbmvb_link{(int)KB, s.m, s.mD, s.D, s.rho_hat});
+            NHP_TRY(sbmvb_after_finish(ctx, st, s, *sb, N, s.rho_hat, true, i % (uint64_t)sb->labels_every == 0, rho));
+            continue;
+        }
         hipLaunchKernelGGL(k_netvb_finish<true>, dim3(link_blocks), dim3(256), 0, st, (int)N, (int)B, splits, dslab, u.E, ds->d_colsum,
                            kappa0, nu0, kappa1, nu1, gamma, (double)nb, rho, (int)net_kind, prior, u.netp, u.kv0, u.nv0, u.kv1, u.nv1,
-                           u.gv, u.rho, u.part);
+                           u.gv, u.rho, u.part, sbmvb_link{});
         if (net_kind)
             hipLaunchKernelGGL(k_netvb_network<true>, dim3(1), dim3(256), 0, st, (int)link_blocks, u.part, net_alpha, net_beta, rho, u.netp);
         NHP_HIP(ctx, hipGetLastError());
     }
+    if (sb) NHP_TRY(sbmvb_copy(ctx, st, s, *sb, N, false));
     return netvb_download(ctx, st, u, h, N, B, net_kind, net_stage);
+}
+
+extern "C" nhp_status nhp_disc_netsvi_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
+                                          double alpha0, double beta0, double kappa0, double nu0, double kappa1, double nu1, double gamma,
+                                          int32_t net_kind, double net_alpha, double net_beta,
+                                          int64_t batch_bins, double delay, double forgetting, uint64_t seed, int64_t step0,
+                                          int32_t n_steps, const int32_t *blocks, const double *phi, int32_t n_lags, int32_t n_basis,
+                                          double *alpha_v, double *beta_v, double *kappa_v0, double *nu_v0, double *kappa_v1,
+                                          double *nu_v1, double *gamma_v, double *rho_v, double *net_alpha_v, double *net_beta_v)
+{
+    return netsvi_run_impl(ctx, ds, dt, alpha0, beta0, kappa0, nu0, kappa1, nu1, gamma, net_kind, net_alpha, net_beta, batch_bins, delay,
+                           forgetting, seed, step0, n_steps, blocks, phi, n_lags, n_basis, alpha_v, beta_v, kappa_v0, nu_v0, kappa_v1,
+                           nu_v1, gamma_v, rho_v, net_alpha_v, net_beta_v, nullptr);
+}
+
+// svi! with a StochasticBlockNetworkModel
+extern "C" nhp_status nhp_disc_sbmsvi_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, double dt,
+                                          double alpha0, double beta0, double kappa0, double nu0, double kappa1, double nu1, double gamma,
+                                          int32_t n_blocks, double net_alpha, double net_beta, double net_gamma, int32_t labels_every,
+                                          int64_t batch_bins, double delay, double forgetting, uint64_t seed, int64_t step0,
+                                          int32_t n_steps, const int32_t *blocks, const double *phi, int32_t n_lags, int32_t n_basis,
+                                          double *alpha_v, double *beta_v, double *kappa_v0, double *nu_v0, double *kappa_v1,
+                                          double *nu_v1, double *gamma_v, double *rho_v, double *m, double *net_alpha_v,
+                                          double *net_beta_v, double *gamma_v_net)
+{
+    const sbmvb_args sb{n_blocks, net_alpha, net_beta, net_gamma, labels_every, 0, m, net_alpha_v, net_beta_v, gamma_v_net};
+    double one_a = 1.0, one_b = 1.0;
+    return netsvi_run_impl(ctx, ds, dt, alpha0, beta0, kappa0, nu0, kappa1, nu1, gamma, 1, 1.0, 1.0, batch_bins, delay, forgetting, seed,
+                           step0, n_steps, blocks, phi, n_lags, n_basis, alpha_v, beta_v, kappa_v0, nu_v0, kappa_v1, nu_v1, gamma_v, rho_v,
+                           &one_a, &one_b, &sb);
 }
 
 // DiscreteLogGaussianCoxProcess(x, λ, Σ, m, dt) as the baseline of this dataset's process (src/baselines.jl:461-509):

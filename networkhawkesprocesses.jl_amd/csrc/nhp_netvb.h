@@ -27,7 +27,7 @@ inline int netvb_check_args(const char *what, const netvb_priors &q, double dt, 
     if (!(dt > 0.0)) { snprintf(msg, cap, "%s: dt must be positive", what); return NETVB_EINVAL; }
     if (N < 1 || B < 1) { snprintf(msg, cap, "%s: the dataset has no nodes or no basis", what); return NETVB_EINVAL; }
     if (q.net_kind != 0 && q.net_kind != 1) {
-        snprintf(msg, cap, "%s: net_kind = %d is not built (0 dense, 1 Bernoulli; the block model has no variational update)", what, (int)q.net_kind);
+        snprintf(msg, cap, "%s: net_kind = %d is not built (0 dense, 1 Bernoulli; the block model has entry points of its own, nhp_disc_sbmvb_run / nhp_disc_sbmsvi_run)", what, (int)q.net_kind);
         return NETVB_ENOTIMPL;
     }
     if (!alpha_v || !beta_v || !kappa_v0 || !nu_v0 || !kappa_v1 || !nu_v1 || !gamma_v || !rho_v) {

@@ -320,8 +320,13 @@ class DiscreteNetworkHawkesProcess(DiscreteHawkesProcess):
         return self.network.link_probability() if ρv is None else ρv
 
     def variational_params(self):
-        """[baseline; κv0; νv0; κv1; νv1; γv; vec(ρv); αv; βv] -- the last two for a Bernoulli network only"""
-        net = [np.array([self.network.αv, self.network.βv])] if hasattr(self.network, "αv") else []
+        """[baseline; κv0; νv0; κv1; νv1; γv; vec(ρv); αv; βv] -- the last two for a Bernoulli network only; a block
+        network appends [vec(αv); vec(βv); γv; vec(mv)] instead"""
+        from .components import StochasticBlockNetworkModel
+        if isinstance(self.network, StochasticBlockNetworkModel):
+            net = [self.network.variational_params()] if self.network.has_variational_state() else []
+        else:
+            net = [np.array([self.network.αv, self.network.βv])] if hasattr(self.network, "αv") else []
         return np.concatenate([self.baseline.variational_params(), self.weights.variational_params(),
                                self.impulses.variational_params(), self.link_probabilities().ravel(order="F")] + net)
 
@@ -1065,14 +1070,19 @@ def disc_mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, 
 def _vb_kind(process, what):
     """'standard' or 'network' for the models the variational drivers are built for; NotImplementedError naming the
     part that is not."""
-    from .components import BernoulliNetworkModel, DenseNetworkModel, SparseWeightModel
+    from .components import BernoulliNetworkModel, DenseNetworkModel, SparseWeightModel, StochasticBlockNetworkModel
     if isinstance(process, DiscreteNetworkHawkesProcess):
         if not isinstance(process.weights, SparseWeightModel):
             raise NotImplementedError(f"{what}: a DiscreteNetworkHawkesProcess needs a SparseWeightModel (weights: "
                                       f"{type(process.weights).__name__} has no spike-and-slab parameters)")
-        if not isinstance(process.network, (DenseNetworkModel, BernoulliNetworkModel)):
-            raise NotImplementedError(f"{what}: network VB is built for DenseNetworkModel and BernoulliNetworkModel (network: "
-                                      f"{type(process.network).__name__} has no variational update)")
+        if isinstance(process.network, StochasticBlockNetworkModel):
+            if not process.network.has_variational_state():
+                raise NotImplementedError(f"{what}: the network (StochasticBlockNetworkModel) has no variational state: mean-field "
+                                          "over labels cannot leave the uniform state, so none is created implicitly -- call "
+                                          "network.variational_init_() first")
+        elif not isinstance(process.network, (DenseNetworkModel, BernoulliNetworkModel)):
+            raise NotImplementedError(f"{what}: network VB is built for DenseNetworkModel, BernoulliNetworkModel and "
+                                      f"StochasticBlockNetworkModel (network: {type(process.network).__name__} has no variational update)")
         kind = "network"
     elif (isinstance(process, DiscreteStandardHawkesProcess) and isinstance(process.weights, DenseWeightModel)
           and not isinstance(process.weights, SparseWeightModel)):
@@ -1128,18 +1138,66 @@ class _NetVB:
             p.network.αv, p.network.βv = self.na.value, self.nb.value
 
 
-def update_(process, data, convolved, ctx=None, n_steps=1):
+class _BlockVB(_NetVB):
+    """The same for a StochasticBlockNetworkModel with a variational state (nhp_disc_sbmvb_run / nhp_disc_sbmsvi_run):
+    mv [n, k] and the K x K tables column-major, in place of the Bernoulli network's two scalars."""
+
+    def __init__(self, process):
+        super().__init__(process)
+        net = process.network
+        K = self.K = net.nblocks
+        self.m = _lib.colmajor(np.asarray(net.mv, dtype=np.float64)).copy()
+        self.na, self.nb = _lib.colmajor(np.asarray(net.αv, dtype=np.float64)).copy(), _lib.colmajor(np.asarray(net.βv, dtype=np.float64)).copy()
+        self.ng = _lib.f64(net.γv).copy()
+        if self.m.size != self.N * K or self.na.size != K * K or self.nb.size != K * K or self.ng.size != K:
+            raise ValueError("the block network's mv must be N x K, αv and βv K x K and γv of length K")
+        if not np.all((self.rho >= 0.0) & (self.rho <= 1.0)):
+            raise DomainError("ρv: link probabilities must lie in [0, 1]")
+
+    def priors(self):
+        b, w, imp, net = self.process.baseline, self.process.weights, self.process.impulses, self.process.network
+        return (b.α0, b.β0, w.κ0, w.ν0, w.κ1, w.ν1, imp.γ, self.K, net.α, net.β, net.γ, int(net.labels_every))
+
+    def pointers(self):
+        return tuple(_lib.dptr(x) for x in (self.av, self.bv, self.k0, self.n0, self.k1, self.n1, self.gv, self.rho, self.m, self.na,
+                                            self.nb, self.ng))
+
+    def store(self):
+        super().store()                                # kind is 0 there: no scalars to write back
+        net, N, K = self.process.network, self.N, self.K
+        net.mv = self.m.reshape((N, K), order="F")
+        net.αv, net.βv, net.γv = self.na.reshape((K, K), order="F"), self.nb.reshape((K, K), order="F"), self.ng
+
+
+def _net_holder(process):
+    from .components import StochasticBlockNetworkModel
+    return _BlockVB(process) if isinstance(process.network, StochasticBlockNetworkModel) else _NetVB(process)
+
+
+def update_(process, data, convolved, ctx=None, n_steps=1, step0=None):
     """update!(process, data, convolved) -- src/discrete.jl:369-375: one mean-field step (or n_steps
     of them with the parameters resident on the device in between); the variational parameters of
     baseline, weights and impulses are overwritten in place.  For a DiscreteNetworkHawkesProcess with a
     SparseWeightModel (src/discrete.jl:494-501, intended semantics: DESIGN §3.19) also weights.ρv and the Bernoulli
-    network's (αv, βv); process.adjacency_matrix is not touched."""
+    network's (αv, βv), or the (mv, αv, βv, γv) of a StochasticBlockNetworkModel that carries a variational state
+    (network.variational_init_()); process.adjacency_matrix is not touched.  The block network's label
+    sweep runs at the steps whose GLOBAL number is a multiple of network.labels_every: the network counts the steps it has
+    taken (network.vb_step, 0 after variational_init_, advanced here), so a loop of one-step calls -- vb_ with its trace --
+    keeps the schedule of one call of n steps; step0 overrides the count."""
     kind = _vb_kind(process, "update!")
     ctx = ctx or _lib.default_context()
     ds = _convolved(process, data, convolved, ctx)
     if kind == "network":
-        st = _NetVB(process)
-        _lib.check(_lib.lib().nhp_disc_netvb_run(ctx.h, ds.h, process.dt, *st.priors(), n_steps, *st.pointers()), ctx.h)
+        st = _net_holder(process)
+        if isinstance(st, _BlockVB):                  # the sweep's schedule counts steps across calls: network.vb_step
+            net = process.network
+            first = int(net.vb_step if step0 is None else step0)
+            if first < 0:
+                raise ValueError("update!: step0 must be non-negative")
+            _lib.check(_lib.lib().nhp_disc_sbmvb_run(ctx.h, ds.h, process.dt, *st.priors(), first, n_steps, *st.pointers()), ctx.h)
+            net.vb_step = first + int(n_steps)
+        else:
+            _lib.check(_lib.lib().nhp_disc_netvb_run(ctx.h, ds.h, process.dt, *st.priors(), n_steps, *st.pointers()), ctx.h)
         st.store()
         return process.variational_params()
     b, w, imp = process.baseline, process.weights, process.impulses
@@ -1157,7 +1215,8 @@ def update_(process, data, convolved, ctx=None, n_steps=1):
 
 def variational_mean_(process):
     """Set the process's parameters to the means of its variational factors: λ0 = αv/βv, θ = γv/Σ_b γv, W = κv/νv; for a
-    network process W = κv1/νv1 (the slab), A = (ρv > 0.5) and, for a Bernoulli network, ρ = αv/(αv + βv).  After it
+    network process W = κv1/νv1 (the slab), A = (ρv > 0.5) and, for a Bernoulli network, ρ = αv/(αv + βv); for a block
+    network ρ = αv/(αv + βv) per pair of blocks, π = γv/Σγv and z = argmax_k mv.  After it
     disc_loglikelihood, disc_forecast and disc_residuals run on a VB fit."""
     b, w, imp = process.baseline, process.weights, process.impulses
     b.λ = np.asarray(b.αv, dtype=np.float64) / np.asarray(b.βv, dtype=np.float64)
@@ -1167,8 +1226,13 @@ def variational_mean_(process):
         _vb_kind(process, "variational_mean!")
         w.W = np.asarray(w.κv1, dtype=np.float64) / np.asarray(w.νv1, dtype=np.float64)
         process.adjacency_matrix = (np.asarray(process.link_probabilities()) > 0.5).astype(np.float64)
-        if hasattr(process.network, "αv"):
-            process.network.ρ = process.network.αv / (process.network.αv + process.network.βv)
+        net = process.network
+        if hasattr(net, "mv"):                        # a block network: ρ = αv/(αv + βv) per pair, π = γv/Σγv, z = argmax_k mv
+            net.ρ = np.asarray(net.αv) / (np.asarray(net.αv) + np.asarray(net.βv))
+            net.π = np.asarray(net.γv) / np.sum(net.γv)
+            net.z = np.argmax(net.mv, axis=1).astype(np.int32)
+        elif hasattr(net, "αv"):
+            net.ρ = net.αv / (net.αv + net.βv)
     else:
         w.W = np.asarray(w.κv, dtype=np.float64) / np.asarray(w.νv, dtype=np.float64)
     return process
@@ -1237,8 +1301,9 @@ def svi_(process, data, nsteps=1000, batch_bins=4096, delay=1.0, forgetting=0.6,
         ds = data if isinstance(data, DiscreteDataset) and data.B == B else convolve(process, data, ctx)
         ph, L = None, 0
     if kind == "network":                         # the same loop on nhp_disc_netsvi_run: four weight tables, ρv, the network
-        net = _NetVB(process)
+        net = _net_holder(process)
         store = net.store
+        net_run = _lib.lib().nhp_disc_sbmsvi_run if isinstance(net, _BlockVB) else _lib.lib().nhp_disc_netsvi_run
     else:
         av, bv = _lib.f64(b.αv).copy(), _lib.f64(b.βv).copy()
         kv, nv, gv = _lib.colmajor(w.κv).copy(), _lib.colmajor(w.νv).copy(), _lib.colmajor(imp.γv).copy()
@@ -1255,9 +1320,8 @@ def svi_(process, data, nsteps=1000, batch_bins=4096, delay=1.0, forgetting=0.6,
         n = min(trace_every, nsteps - done) if trace_every else nsteps
         blk = None if blocks is None else blocks[done:done + n].ctypes.data_as(C.POINTER(C.c_int32))
         if kind == "network":
-            _lib.check(_lib.lib().nhp_disc_netsvi_run(ctx.h, ds.h, process.dt, *net.priors(), batch_bins, float(delay),
-                                                      float(forgetting), int(seed), step0 + done, n, blk, _lib.dptr(ph), L, B,
-                                                      *net.pointers()), ctx.h)
+            _lib.check(net_run(ctx.h, ds.h, process.dt, *net.priors(), batch_bins, float(delay), float(forgetting), int(seed),
+                               step0 + done, n, blk, _lib.dptr(ph), L, B, *net.pointers()), ctx.h)
         else:
             _lib.check(_lib.lib().nhp_disc_svi_run(ctx.h, ds.h, process.dt, b.α0, b.β0, w.κ, w.ν, imp.γ, batch_bins, float(delay),
                                                    float(forgetting), int(seed), step0 + done, n, blk, _lib.dptr(ph), L, B,

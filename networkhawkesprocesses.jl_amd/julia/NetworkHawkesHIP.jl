@@ -1033,6 +1033,88 @@ function svi!(p::NHP.DiscreteNetworkHawkesProcess, data::Matrix{Int64}; nsteps::
     return res, ρ
 end
 
+# --- update! / svi! with a StochasticBlockNetworkModel (nhp_disc_sbmvb_run, nhp_disc_sbmsvi_run; DESIGN §3.21) ---
+# q(z_n) = Categorical(m[n,:]), q(ρ[k,l]) = Beta(αv[k,l], βv[k,l]), q(π) = Dirichlet(γv) around the network step above.  The
+# block model here is this module's own struct, so it travels next to the process (whose `network` field is not read), and
+# its variational state is a BlockVariational the caller keeps, updated in place like ρv.  Mean-field over labels has the
+# uniform state as a fixed point: variational_init refuses sharpness = 0, and nothing creates the state implicitly.
+mutable struct BlockVariational
+    m::Matrix{Float64}; αv::Matrix{Float64}; βv::Matrix{Float64}; γv::Vector{Float64}
+    labels_every::Int
+    step::Int          # VB steps taken so far: the sweep runs at the global steps that are multiples of labels_every
+end
+function variational_init(net::StochasticBlockNetworkModel; sharpness=0.5, labels_every::Integer=1)
+    0 < sharpness <= 1 || throw(ArgumentError("sharpness must lie in (0, 1]; 0 is the symmetric fixed point of the label update"))
+    labels_every >= 1 || throw(ArgumentError("labels_every must be positive"))
+    N, K = net.nnodes, net.nblocks
+    m = fill((1 - sharpness) / K, N, K)
+    for n in 1:N
+        m[n, net.z[n]] += sharpness
+    end
+    BlockVariational(m ./ sum(m, dims=2), fill(net.α, K, K), fill(net.β, K, K), fill(net.γ, K), labels_every, 0)
+end
+block_params(p, ρv, q::BlockVariational) =
+    [NHP.variational_params(p.baseline); NHP.variational_params(p.weights); NHP.variational_params(p.impulses); vec(ρv);
+     vec(q.αv); vec(q.βv); q.γv; vec(q.m)]
+
+function sbm_update!(p::NHP.DiscreteNetworkHawkesProcess, data, c::Convolved, net::StochasticBlockNetworkModel, q::BlockVariational;
+                     ρv::Union{Nothing,Matrix{Float64}}=nothing, n_steps::Integer=1, ctx=context())
+    p.weights isa NHP.SparseWeightModel || error("network update! needs a SparseWeightModel")
+    b, w, imp = p.baseline, p.weights, p.impulses
+    ρ = ρv === nothing ? Matrix{Float64}(link_probability(net)) : ρv
+    αv, βv, γv = Vector{Float64}(b.αv), Vector{Float64}(b.βv), Array{Float64,3}(imp.γv)
+    κ0, ν0, κ1, ν1 = Matrix{Float64}(w.κv0), Matrix{Float64}(w.νv0), Matrix{Float64}(w.κv1), Matrix{Float64}(w.νv1)
+    check(ccall((:nhp_disc_sbmvb_run, libnhp), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, Float64, Float64, Float64, Int32, Float64, Float64, Float64,
+         Int32, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        ctx.h, c.h, p.dt, b.α0, b.β0, w.κ0, w.ν0, w.κ1, w.ν1, imp.γ, net.nblocks, net.α, net.β, net.γ, q.labels_every, q.step, n_steps,
+        αv, βv, κ0, ν0, κ1, ν1, γv, ρ, q.m, q.αv, q.βv, q.γv), ctx.h)
+    q.step += n_steps
+    b.αv, b.βv, w.κv0, w.νv0, w.κv1, w.νv1, imp.γv = αv, βv, κ0, ν0, κ1, ν1, γv
+    (block_params(p, ρ, q), ρ)
+end
+
+# resident mode; the keywords are svi!'s for the standard process
+function sbm_svi!(p::NHP.DiscreteNetworkHawkesProcess, data::Matrix{Int64}, net::StochasticBlockNetworkModel, q::BlockVariational;
+                  nsteps::Integer=1_000, batch_bins::Integer=4096, delay=1.0, forgetting=0.6, seed::Integer=0, blocks=nothing,
+                  step0::Integer=0, ρv::Union{Nothing,Matrix{Float64}}=nothing, ctx=context())
+    p.weights isa NHP.SparseWeightModel || error("network svi! needs a SparseWeightModel")
+    N, T = size(data)
+    nb_ = cld(T, min(batch_bins, T))
+    blk = blocks === nothing ? nothing : Vector{Int32}(blocks)
+    blk === nothing || (length(blk) >= nsteps && all(0 .<= blk .< nb_)) || throw(ArgumentError("blocks: nsteps indices in [0, $nb_) are required"))
+    c = convolve(p, data; ctx=ctx)
+    b, w, imp = p.baseline, p.weights, p.impulses
+    ρ = ρv === nothing ? Matrix{Float64}(link_probability(net)) : ρv
+    αv, βv, γv = Vector{Float64}(b.αv), Vector{Float64}(b.βv), Array{Float64,3}(imp.γv)
+    κ0, ν0, κ1, ν1 = Matrix{Float64}(w.κv0), Matrix{Float64}(w.νv0), Matrix{Float64}(w.κv1), Matrix{Float64}(w.νv1)
+    res = NHP.VariationalInference(p)
+    bp = blk === nothing ? Ptr{Int32}(C_NULL) : pointer(blk)
+    start_time = time()
+    GC.@preserve blk c check(ccall((:nhp_disc_sbmsvi_run, libnhp), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, Float64, Float64, Float64, Int32, Float64, Float64, Float64,
+         Int32, Int64, Float64, Float64, UInt64, Int64, Int32, Ptr{Int32}, Ptr{Float64}, Int32, Int32,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        ctx.h, c.h, p.dt, b.α0, b.β0, w.κ0, w.ν0, w.κ1, w.ν1, imp.γ, net.nblocks, net.α, net.β, net.γ, q.labels_every,
+        batch_bins, delay, forgetting, seed % UInt64, step0, nsteps, bp, Ptr{Float64}(C_NULL), 0, 0,
+        αv, βv, κ0, ν0, κ1, ν1, γv, ρ, q.m, q.αv, q.βv, q.γv), ctx.h)
+    b.αv, b.βv, w.κv0, w.νv0, w.κv1, w.νv1, imp.γv = αv, βv, κ0, ν0, κ1, ν1, γv
+    res.step = step0 + nsteps
+    push!(res.trace, block_params(p, ρ, q))
+    res.elapsed = time() - start_time
+    return res, ρ
+end
+
+# the fit as a block model: ρ = αv/(αv + βv), π = γv/Σγv, z = argmax_k m (1-based)
+function variational_mean!(net::StochasticBlockNetworkModel, q::BlockVariational)
+    net.ρ = q.αv ./ (q.αv .+ q.βv)
+    net.π = q.γv ./ sum(q.γv)
+    net.z = [argmax(q.m[n, :]) for n in 1:net.nnodes]
+    net
+end
+
 # --- mle!(process::DiscreteStandardHawkesProcess, data; optimizer=BFGS, verbose=false, f_abstol=1e-6, regularize=false,
 #          guess=nothing, max_increase_steps=3) -> MaximumLikelihood   src/discrete.jl:211-296 ---------------------------
 # Parameter vector [λ0; vec(W .* θ)] (params / params!, src/discrete.jl:174-201).  regularize=true calls the reference's

@@ -414,6 +414,49 @@ nhp_status nhp_cont_model_moments_reset(nhp_ctx *ctx, nhp_cont_model *model);
 nhp_status nhp_cont_model_moments_accumulate(nhp_ctx *ctx, nhp_cont_model *model);
 nhp_status nhp_cont_model_moments_fetch(nhp_ctx *ctx, const nhp_cont_model *model, double *sum, double *sumsq,
                                         int64_t len, int64_t *count);
+/* Streaming convergence diagnostics of a chain that keeps no samples: effective sample size, Monte-Carlo standard error and
+ * split R-hat of every entry the sums above cover, accumulated in the same pass (csrc/cont_diagnostics.hip: with
+ * diagnostics configured, _accumulate launches ONE fused kernel in place of the moments kernel).  The definitions are the
+ * contract; tests/chain_diagnostics_ref.py restates them in numpy.
+ *
+ * One scalar entry x of [λ0; θ | μ; τ; W; vec(A) if any]; kept steps t = 0 … n−1 (one _accumulate each).  Fixed by
+ * _configure: batch_len b ≥ 1, n_planned ≥ 0 (the kept steps the chain is going to make), h = ⌊n_planned/2⌋.
+ *   S1 = Σx, S2 = Σx²: the sums above -- same expressions, same bits, still in the moments' own planes.
+ *   B: sum over the current batch.  At every kept step whose 1-based count is a multiple of b:
+ *        m = B/b;  SB += m;  QB += m·m (the product rounded, then added);  B = 0.   A trailing partial batch is never folded in.
+ *   snapA = (S1, S2) when the kept count reaches h, snapB = (S1, S2) when it reaches n_planned − h (one copy when
+ *        n_planned is even); taken only when h ≥ 2.
+ * At fetch, with n kept steps (n ≥ 1), a = ⌊n/b⌋ and pos(v) = v if v > 0, else 0 (so a NaN gives 0):
+ *   s²     = pos(S2 − S1·S1/n)/(n−1)
+ *   σ²_bm  = b·pos(QB − SB·SB/a)/(a−1);  NaN when a < 2
+ *   MCSE   = √(σ²_bm/n)
+ *   ESS    = n·s²/σ²_bm, not capped at n;  NaN when s² = 0
+ *   split R-hat: only when n = n_planned and h ≥ 2, NaN otherwise.  First half: sums snapA; second half: (S1, S2) − snapB,
+ *        h steps each (the middle step of an odd n is dropped).  m_i = S1_i/h, v_i = pos(S2_i − S1_i·S1_i/h)/(h−1),
+ *        W = (v₁+v₂)/2, R-hat = √((h−1)/h + (m₁−m₂)·(m₁−m₂)/(2W));  NaN when W = 0.
+ *   An entry with s² = 0 (a link of A that never flipped) is "undefined": it is counted and takes no part in any extreme
+ *   or count below; so does a NaN (excluded, not counted as undefined).
+ * The Bernoulli network's scalar ρ (nhp_cont_model_set_rho) gets the same treatment next to its Σρ, Σρ².  A block network's
+ * ρ / π and a latent distance network's b are not diagnosed (labels and positions are not identified anyway).
+ *
+ * summary [NHP_DIAG_GROUPS * NHP_DIAG_FIELDS], group g at g·NHP_DIAG_FIELDS.  Groups: 0 λ0, 1 θ | μ, 2 τ (no entries for
+ * exponential impulses), 3 W, 4 vec(A) (no entries without one), 5 ρ (one entry when the model has a scalar ρ and neither
+ * a block nor a latent distance network).  Fields: 0 entries, 1 undefined, 2 min ESS, 3 its index inside the group
+ * (p + N·c; −1: none), 4 max R-hat, 5 its index, 6 entries with ESS < ess_below, 7 entries with R-hat > rhat_above,
+ * 8 max MCSE.  Ties go to the lower index; an extreme nobody defines is NaN.  The reduction is exact (minima, maxima and
+ * integer counts in a fixed order, no atomics): two runs give the same bits.
+ *
+ * _configure(b, n_planned) allocates 3 planes of len doubles (+ 2 per snapshot: 5–7 when h ≥ 2; ≈ 235 MB for the
+ * logit-normal network at N = 1024) and zeroes them and the kept count; (0, 0) turns diagnostics off and frees them.  It
+ * leaves the moments alone: configure before the chain's first kept step (or call _moments_reset, which zeroes the
+ * diagnostic planes too); a fetch whose diagnostics saw fewer steps than the moments is NHP_EINVAL.  NHP_ENOMEM leaves
+ * diagnostics off and the moments usable.  nhp_cont_mcmc_run on a column shard with diagnostics configured is NHP_ENOTIMPL.
+ * _fetch: ess, mcse, rhat nullable, [len] each in the order of the sums; NHP_EINVAL with nothing configured or accumulated. */
+#define NHP_DIAG_GROUPS 6
+#define NHP_DIAG_FIELDS 9
+nhp_status nhp_cont_model_diagnostics_configure(nhp_ctx *ctx, nhp_cont_model *model, int64_t batch_len, int64_t n_planned);
+nhp_status nhp_cont_model_diagnostics_fetch(nhp_ctx *ctx, const nhp_cont_model *model, double ess_below, double rhat_above,
+                                            double *summary, double *ess, double *mcse, double *rhat, int64_t len);
 /* the uniform stream itself (host side, same bits as the kernel draws) */
 void nhp_uniform_stream(uint64_t seed, uint64_t step, int64_t n, double *u);
 

@@ -21,6 +21,7 @@ IMPULSE_EXPONENTIAL, IMPULSE_LOGITNORMAL = 0, 1
 LL_RECURSIVE = 1
 LL_FULL_RECURSION = 2
 MAX_SLOTS = 4096
+DIAG_GROUPS, DIAG_FIELDS = 6, 9
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -126,6 +127,8 @@ def _declare(lib):
     f("nhp_cont_model_moments_reset", i32, _vp, _vp)
     f("nhp_cont_model_moments_accumulate", i32, _vp, _vp)
     f("nhp_cont_model_moments_fetch", i32, _vp, _vp, _dp, _dp, i64, C.POINTER(i64))
+    f("nhp_cont_model_diagnostics_configure", i32, _vp, _vp, i64, i64)
+    f("nhp_cont_model_diagnostics_fetch", i32, _vp, _vp, dbl, dbl, _dp, _dp, _dp, _dp, i64)
     f("nhp_cont_loglik", i32, _vp, _vp, _vp, i32, _dp)
     f("nhp_cont_loglik_enqueue", i32, _vp, _vp, _vp, i32, i32)
     f("nhp_ctx_fetch", i32, _vp, i32, i32, _dp)

@@ -27,6 +27,27 @@ def summarize_chain(samples, burn=0):
     return {"n": np.array([float(len(x))]), "mean": x.mean(axis=0), "m2": (x ** 2).mean(axis=0)}
 
 
+def potential_scale_reduction(summaries):
+    """The classic between-chain R-hat of every entry from the chains' {n, mean, m2} (what run_chains gathers; a dict by
+    chain id or a sequence): each chain's variance is n/(n−1)·(m2 − mean²) floored at 0, W their mean, and
+    R-hat = √((n−1)/n + Var(means)/W) with the sample variance (ddof = 1) of the chains' means.  Needs at least two
+    chains of equal n ≥ 2 (ValueError otherwise); an entry with W = 0 is NaN.  Runs on the host: O(chains · P)."""
+    chains = list(summaries.values()) if isinstance(summaries, dict) else list(summaries)
+    if len(chains) < 2:
+        raise ValueError("potential_scale_reduction needs at least two chains")
+    ns = {float(np.asarray(c["n"]).ravel()[0]) for c in chains}
+    if len(ns) != 1:
+        raise ValueError("potential_scale_reduction needs chains of equal length")
+    n = ns.pop()
+    if n < 2:
+        raise ValueError("potential_scale_reduction needs at least two kept steps per chain")
+    means = np.array([np.asarray(c["mean"], dtype=np.float64) for c in chains])
+    m2 = np.array([np.asarray(c["m2"], dtype=np.float64) for c in chains])
+    W = (np.maximum(m2 - means ** 2, 0.0) * (n / (n - 1.0))).mean(axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(W > 0.0, np.sqrt((n - 1.0) / n + means.var(axis=0, ddof=1) / W), np.nan)
+
+
 def gather_summaries(local, n_chains, device=None):
     """All-gather {chain id: summary} dicts so every rank sees every chain.
 

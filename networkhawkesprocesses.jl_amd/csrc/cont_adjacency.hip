@@ -748,6 +748,7 @@ extern "C" nhp_status nhp_cont_mcmc_run(nhp_ctx *ctx, nhp_comm *comm, const nhp_
     if (!ctx || !m || !pr || n_steps < 0) return NHP_EINVAL;
     NHP_TRY(nhp_check_pair(ctx, ds, m));
     if (m->has_A && !m->sbm && !m->latent && !m->d_rho) { nhp_set_error(ctx, "mcmc_run: set the network's link probability first (nhp_cont_model_set_rho)"); return NHP_EINVAL; }
+    if (m->diag && burn >= 0 && (comm || nhp_is_column_shard(ds))) { nhp_set_error(ctx, "mcmc_run: convergence diagnostics are not available on a column shard"); return NHP_ENOTIMPL; }
     for (int64_t k = 0; k < n_steps; ++k) {
         const uint64_t step = step0 + (uint64_t)k;
         NHP_TRY(nhp_cont_gibbs_step(ctx, ds, m, pr, seed, step));           // (reports a sampler error one sweep late)

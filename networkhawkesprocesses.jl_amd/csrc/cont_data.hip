@@ -607,6 +607,7 @@ extern "C" void nhp_cont_model_destroy(nhp_cont_model *m)
     (void)hipFree(m->d_mom); (void)hipFree(m->d_rho);
     nhp_sbm_free(m);
     nhp_latent_free(m);
+    nhp_diag_free(m);
     (void)hipFree(m->d_params); (void)hipFree(m->d_grid); (void)hipFree(m->d_A);
     delete m;
 }

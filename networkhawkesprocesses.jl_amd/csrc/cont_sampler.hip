@@ -648,6 +648,7 @@ extern "C" nhp_status nhp_cont_model_moments_reset(nhp_ctx *ctx, nhp_cont_model 
     if (m->sbm) NHP_TRY(nhp_sbm_moments_reset(ctx, m));
     if (m->latent) NHP_TRY(nhp_latent_moments_reset(ctx, m));
     m->mom_count = 0;
+    if (m->diag) NHP_TRY(nhp_diag_reset(ctx, m));
     return NHP_OK;
 }
 
@@ -657,10 +658,13 @@ extern "C" nhp_status nhp_cont_model_moments_accumulate(nhp_ctx *ctx, nhp_cont_m
     if (m->ctx != ctx) { nhp_set_error(ctx, "model belongs to another ctx"); return NHP_EINVAL; }
     if (!m->d_mom) NHP_TRY(nhp_cont_model_moments_reset(ctx, m));
     NHP_HIP(ctx, hipSetDevice(ctx->device));
-    const unsigned blocks = (unsigned)std::min<int64_t>((m->mom_len + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_moments, dim3(blocks), dim3(256), 0, ctx->main(), (const double *)m->d_params, (int64_t)nhp_layout(m).P,
-                       (const double *)(m->has_A ? m->d_A : nullptr), m->mom_len, m->d_mom, m->d_rho);
-    NHP_HIP(ctx, hipGetLastError());
+    if (m->diag) NHP_TRY(nhp_diag_accumulate(ctx, m));         // the same sums, same bits, and the batch planes in one pass
+    else {
+        const unsigned blocks = (unsigned)std::min<int64_t>((m->mom_len + 255) / 256, 4096);
+        hipLaunchKernelGGL(k_moments, dim3(blocks), dim3(256), 0, ctx->main(), (const double *)m->d_params, (int64_t)nhp_layout(m).P,
+                           (const double *)(m->has_A ? m->d_A : nullptr), m->mom_len, m->d_mom, m->d_rho);
+        NHP_HIP(ctx, hipGetLastError());
+    }
     if (m->sbm) NHP_TRY(nhp_sbm_moments_accumulate(ctx, m));
     if (m->latent) NHP_TRY(nhp_latent_moments_accumulate(ctx, m));
     ++m->mom_count;

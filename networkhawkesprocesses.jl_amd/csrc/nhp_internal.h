@@ -313,7 +313,16 @@ struct nhp_cont_model {
     // offset b, the link-probability matrix and the running sums of the kept steps; null: no latent distance network.  At
     // most one of sbm and latent is set.
     struct nhp_latent_state *latent = nullptr;
+    // streaming convergence diagnostics (cont_diagnostics.hip: nhp_cont_model_diagnostics_*): the batch planes and the
+    // snapshots of the sums above; null: not configured, _accumulate runs the moments kernel alone
+    struct nhp_diag_state *diag = nullptr;
 };
+// cont_diagnostics.hip: release the diagnostic planes; their share of nhp_cont_model_moments_reset (zero the planes, fitted
+// to the sums' current length) and of _accumulate (the fused kernel IN PLACE of the moments kernel, then the snapshots) --
+// all asynchronous on the main stream
+void nhp_diag_free(nhp_cont_model *m);
+nhp_status nhp_diag_reset(nhp_ctx *ctx, nhp_cont_model *m);
+nhp_status nhp_diag_accumulate(nhp_ctx *ctx, nhp_cont_model *m);
 // sbm.hip: release the block network's state; its share of nhp_cont_model_moments_reset / _accumulate (asynchronous)
 void nhp_sbm_free(nhp_cont_model *m);
 nhp_status nhp_sbm_detach(nhp_ctx *ctx, nhp_cont_model *m);      // set_rho: the model's network is no block model (any more)

@@ -5,6 +5,7 @@ on the host is O(N²) bookkeeping and the conjugate random draws (SURVEY.md 2.1:
 Result containers keep the reference's field names (src/inference.jl:6-12,24-29,78-83).
 """
 import collections
+import math
 import time
 
 import numpy as np
@@ -578,6 +579,38 @@ def _moments_in_params_order(process, s, q, count, network, rho_sum, rho_sq):
     return mean, m2
 
 
+DIAGNOSTIC_FIELDS = ("entries", "undefined", "min_ess", "min_ess_index", "max_rhat", "max_rhat_index", "ess_below", "rhat_above",
+                     "max_mcse")
+
+
+def _fetch_diagnostics(process, model, ctx, network, full, ess_below, rhat_above):
+    """nhp_cont_model_diagnostics_fetch -> {"summary"[, "ess", "mcse", "rhat"]} (the caller adds n, batch_len, nbatches).
+    The per-entry arrays take the reordering of _moments_in_params_order."""
+    from .components import BernoulliNetworkModel
+    L = moments_length(process)
+    summary = np.empty(_lib.DIAG_GROUPS * _lib.DIAG_FIELDS)
+    planes = [np.empty(L) for _ in range(3)] if full else [None] * 3
+    _lib.check(_lib.lib().nhp_cont_model_diagnostics_fetch(ctx.h, model.h, float(ess_below), float(rhat_above), _lib.dptr(summary),
+                                                          *[_lib.dptr(v) for v in planes], L), ctx.h)
+    summary = summary.reshape(_lib.DIAG_GROUPS, _lib.DIAG_FIELDS)
+    exponential = isinstance(process.impulses, ExponentialImpulseResponse)
+    names = ["baseline", "impulses.θ" if exponential else "impulses.μ", None if exponential else "impulses.τ", "weights",
+             "adjacency" if network else None,
+             "network.ρ" if network and isinstance(process.network, BernoulliNetworkModel) else None]
+    ints = ("entries", "undefined", "min_ess_index", "max_rhat_index", "ess_below", "rhat_above")
+    out = {"summary": {name: {f: (int(v) if f in ints else float(v)) for f, v in zip(DIAGNOSTIC_FIELDS, row)}
+                       for name, row in zip(names, summary) if name is not None}}
+    if full:
+        if network:    # [ρ-entries; λ0; W; impulses; vec(A)]; ρ's single entry is its group's extreme, anything else NaN
+            k = len(process.network.params())
+            lay = param_layout(process)
+            rho = summary[5, [2, 8, 4]] if "network.ρ" in out["summary"] else [np.nan] * 3
+            planes = [np.concatenate([np.full(k, r), v[lay.baseline], v[lay.weights], v[lay.impulses], v[lay.adjacency]])
+                      for v, r in zip(planes, rho)]
+        out["ess"], out["mcse"], out["rhat"] = planes
+    return out
+
+
 def _owned_mask(process, shard, network):
     """1 on the entries of params(process) this rank owns (its columns; rank 0 also the network's ρ), 0 elsewhere."""
     N = process.ndims()
@@ -606,7 +639,8 @@ def _merge_shards(process, shard, network):
 
 
 def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_samples=True, device_draws=True,
-          ctx=None, moments=False, burn=0, labels_every=1, positions_every=1):
+          ctx=None, moments=False, burn=0, labels_every=1, positions_every=1, diagnostics=False, batch_len=None, ess_below=100.0,
+          rhat_above=1.01):
     """mcmc!(process, data; nsteps, log_freq, verbose) -- src/inference.jl:49-70.
 
     With `device_draws` (default) a whole sweep -- parents, statistics, conjugate draws -- stays on
@@ -619,6 +653,18 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
     run `res.mean` and `res.m2` hold the mean and the mean square of params(process) over the steps >= `burn` -- the
     summaries chains.py gathers -- with no per-step transfer; combine with keep_samples=False for long chains at large N
     (a sample is 4N²+N doubles, 33.5 MB at N = 1024).
+
+    `diagnostics=True` (with `moments=True`) says whether those means can be trusted, still without samples: the pass that
+    keeps the running sums also keeps batch sums and two snapshots (nhp_cont_model_diagnostics_*, one launch per kept step),
+    and `res.diagnostics` holds `n`, `batch_len`, `nbatches` and `summary`: per group ("baseline", "impulses.θ" or
+    "impulses.μ" / "impulses.τ", "weights", "adjacency", "network.ρ") the entries, the undefined ones (never moved: a link
+    that never flipped), the smallest batch-means effective sample size and the largest split R-hat with their entries'
+    indices inside the group (p + N·c), how many entries have ESS < `ess_below` and R-hat > `rhat_above`, and the largest
+    Monte-Carlo standard error.  `diagnostics="full"` adds `ess`, `mcse`, `rhat` per entry, in params(process) order.
+    `batch_len` defaults to max(1, ⌊√(nsteps − burn)⌋).  Definitions: include/nhp.h.  Only a BernoulliNetworkModel's ρ is
+    diagnosed among the network parameters: a block network's ρ / π and a latent distance network's b are NaN in the
+    per-entry arrays and have no group (labels and positions are not identified anyway).  A ShardedDataset raises
+    NotImplementedError.
 
     A StochasticBlockNetworkModel is resampled on the GPU on every route (csrc/sbm.hip): with the device-side draws its
     labels, ρ and π stay next to the model and a network step never leaves the device; with device_draws=False (or an
@@ -647,6 +693,14 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
     from .sharded import ShardedDataset, _all_reduce_sum
     from .components import BernoulliNetworkModel, DenseNetworkModel, LatentDistanceNetworkModel, StochasticBlockNetworkModel
     shard = data if isinstance(data, ShardedDataset) else None
+    if diagnostics not in (False, True, "full"):
+        raise ValueError('diagnostics must be False, True or "full"')
+    if diagnostics and not moments:
+        raise ValueError("diagnostics need the device-side running sums (moments=True)")
+    if diagnostics and shard is not None:
+        raise NotImplementedError("convergence diagnostics are not available for a sharded chain")
+    if batch_len is not None and int(batch_len) < 1:
+        raise ValueError("batch_len must be a positive integer")
     sbm = isinstance(getattr(process, "network", None), StochasticBlockNetworkModel)
     latent = isinstance(getattr(process, "network", None), LatentDistanceNetworkModel)
     if sbm and shard is not None:
@@ -691,6 +745,12 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
         _lib.check(lib.nhp_cont_model_set_rho(ctx.h, model.h, net.ρ if isinstance(net, BernoulliNetworkModel) else 1.0), ctx.h)
     comm = _lib.comm_for(ctx) if shard is not None else None
     host_exchange = shard is not None and shard.world > 1 and comm is None        # gloo rehearsal: link counts through the host
+    if diagnostics:
+        n_planned = max(0, int(nsteps) - int(burn))
+        diag_b = int(batch_len) if batch_len is not None else max(1, math.isqrt(n_planned))
+        _lib.check(lib.nhp_cont_model_diagnostics_configure(ctx.h, model.h, diag_b, n_planned), ctx.h)
+    elif model is not None:                # a cached device model may carry an earlier chain's planes
+        _lib.check(lib.nhp_cont_model_diagnostics_configure(ctx.h, model.h, 0, 0), ctx.h)
     if moments:
         _lib.check(lib.nhp_cont_model_moments_reset(ctx.h, model.h), ctx.h)
 
@@ -793,6 +853,12 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
         res.mean, res.m2, res.n = _fetch_moments(process, model, ctx, network, r3[1], r3[2])
         if latent:
             res.link_probability_mean = p_sum[0] / max(1, res.n)
+        if diagnostics and res.n < 1:
+            res.diagnostics = {"summary": {}}               # no kept step: nothing to diagnose
+        elif diagnostics:
+            res.diagnostics = _fetch_diagnostics(process, model, ctx, network, diagnostics == "full", ess_below, rhat_above)
+        if diagnostics:
+            res.diagnostics.update(n=res.n, batch_len=diag_b, nbatches=res.n // diag_b)
         if shard is not None and shard.world > 1:
             mask = _owned_mask(process, shard, network)
             res.mean, res.m2 = _all_reduce_sum(res.mean * mask, ctx), _all_reduce_sum(res.m2 * mask, ctx)

@@ -611,12 +611,20 @@ end
 # moments=true: the chain's posterior sums over the steps >= burn are kept on the device (nhp_cont_model_moments_*, what
 # `gather_moments` exchanges between chains) and come back as the second value: (res, (sum, sumsq, count, rho)) -- fetched
 # before the device model is released.  Without it no sum is accumulated (burn = -1 to the library).
+# diagnostics=true (with moments=true): batch-means ESS, MCSE and split R-hat are accumulated in the same pass
+# (nhp_cont_model_diagnostics_configure before the chain, batch_len = max(1, isqrt(nsteps - burn)) unless given) and a third
+# value follows: (summary, batch_len), summary the 9 x 6 matrix of nhp_cont_model_diagnostics_fetch -- fields x groups
+# (λ0, θ | μ, τ, W, vec(A), ρ), include/nhp.h; group-relative indices are 0-based as the library returns them.
 function mcmc!(p::NHP.ContinuousHawkesProcess, data; nsteps=1000, log_freq=100, verbose=false, seed::UInt64=UInt64(0),
                keep_samples=true, moments=false, burn::Integer=0, ctx=context(), comm=nothing,
+               diagnostics=false, batch_len::Integer=max(1, isqrt(max(0, nsteps - burn))), ess_below=100.0, rhat_above=1.01,
                ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
     p.baseline isa NHP.HomogeneousProcess || error("mcmc! on the device draws the homogeneous baseline; use the package's mcmc! with an LGCP baseline")
+    diagnostics && !moments && throw(ArgumentError("diagnostics need the device-side running sums (moments=true)"))
+    diagnostics && comm !== nothing && error("convergence diagnostics are not available for a sharded chain")
     res = NHP.MarkovChainMonteCarlo(p)
     mom = nothing
+    diag = nothing
     start_time = time()
     network = p isa NHP.ContinuousNetworkHawkesProcess
     bern = network && p.network isa NHP.BernoulliNetworkModel
@@ -624,6 +632,8 @@ function mcmc!(p::NHP.ContinuousHawkesProcess, data; nsteps=1000, log_freq=100, 
     pr = Ref(priors(p))
     with_model(ctx, p) do m
         network && check(ccall((:nhp_cont_model_set_rho, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Float64), ctx.h, m, bern ? p.network.ρ : 1.0), ctx.h)
+        check(ccall((:nhp_cont_model_diagnostics_configure, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64), ctx.h, m,
+                    diagnostics ? Int64(batch_len) : Int64(0), diagnostics ? Int64(max(0, nsteps - burn)) : Int64(0)), ctx.h)
         moments && check(ccall((:nhp_cont_model_moments_reset, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), ctx.h, m), ctx.h)
         while res.steps < nsteps
             n = keep_samples ? 1 : min(nsteps - res.steps, verbose ? log_freq : nsteps)
@@ -648,10 +658,17 @@ function mcmc!(p::NHP.ContinuousHawkesProcess, data; nsteps=1000, log_freq=100, 
                         ctx.h, m, s, q, len, cnt), ctx.h)
             network && check(ccall((:nhp_cont_model_get_rho, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}), ctx.h, m, rho), ctx.h)
             mom = (s, q, cnt[], rho)
+            if diagnostics && cnt[] >= 1
+                summary = Matrix{Float64}(undef, 9, 6)
+                check(ccall((:nhp_cont_model_diagnostics_fetch, libnhp), Int32,
+                            (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64),
+                            ctx.h, m, Float64(ess_below), Float64(rhat_above), summary, C_NULL, C_NULL, C_NULL, len), ctx.h)
+                diag = (summary, Int(batch_len))
+            end
         end
     end
     res.elapsed = time() - start_time
-    return moments ? (res, mom) : res
+    return diagnostics ? (res, mom, diag) : moments ? (res, mom) : res
 end
 
 # --- StochasticBlockNetworkModel: the reference names it and leaves an empty stub (src/networks.jl, last lines) -------------

@@ -551,6 +551,62 @@ nhp_status nhp_disc_resample_adjacency(nhp_ctx *ctx, const nhp_disc_dataset *ds,
                                        const double *W, const double *theta, double *A, double dt,
                                        const double *rho_matrix, double rho, const double *u,
                                        uint64_t seed, uint64_t step, double *n_links);
+
+/* ---- the discrete chain on the device (csrc/disc_chain.hip) ---------------------------------------------------
+ * nhp_disc_model: the state of a discrete mcmc! chain as ONE device block, [λ0 (N); vec(W) (N²); vec(θ) (N²B); vec(A) (N², only
+ * with has_A)], column-major as every nhp_disc_* entry takes them, and next to it -- with has_A -- the network's scalars
+ * {ρ, Σρ, Σρ², ΣA of the latest sweep}, as nhp_cont_model keeps them.  Homogeneous baseline only.  `dt` is the process's bin
+ * width (the entries above take it per call; a resident chain has one).  _set / _get copy host arrays in and out, each
+ * nullable (A: NHP_EINVAL without has_A); both are synchronous.  _set_rho / _get_rho are nhp_cont_model_set_rho / _get_rho:
+ * NHP_EDOMAIN outside [0, 1], _get_rho returns {ρ, Σρ, Σρ²}.  Every entry below that takes a dataset refuses one whose N or B
+ * differs from the model's (NHP_EINVAL). */
+typedef struct nhp_disc_model nhp_disc_model;
+nhp_status nhp_disc_model_create(nhp_ctx *ctx, int32_t n_nodes, int32_t n_basis, int32_t has_A, double dt, nhp_disc_model **out);
+void nhp_disc_model_destroy(nhp_disc_model *model);
+nhp_status nhp_disc_model_set(nhp_ctx *ctx, nhp_disc_model *model, const double *lambda0, const double *W, const double *theta,
+                              const double *A);
+nhp_status nhp_disc_model_get(nhp_ctx *ctx, const nhp_disc_model *model, double *lambda0, double *W, double *theta, double *A);
+nhp_status nhp_disc_model_set_rho(nhp_ctx *ctx, nhp_disc_model *model, double rho);
+nhp_status nhp_disc_model_get_rho(nhp_ctx *ctx, const nhp_disc_model *model, double *rho_sum_sumsq /* [3] */);
+/* nhp_disc_gibbs_step on the model, in place: the same launches, Philox keys and arithmetic, so the same bits -- but E and
+ * base are staged from the device block, the draws land in it, and the call is asynchronous (no copy to or from the host, no
+ * stream synchronise). */
+nhp_status nhp_disc_model_gibbs_step(nhp_ctx *ctx, const nhp_disc_dataset *ds, nhp_disc_model *model, double alpha0, double beta0,
+                                     double kappa, double nu, double gamma0, uint64_t seed, uint64_t step);
+/* The network half of a step: the sweep of nhp_disc_resample_adjacency on the model's A with the model's scalar ρ and Philox
+ * uniforms (seed, step), then ΣA on the device (an exact integer sum in one fixed order, no atomics), then
+ * ρ ~ Beta(net_alpha + ΣA, net_beta + N² − ΣA) with the kernel and key of nhp_cont_network_rho; net_alpha = net_beta = 0 holds
+ * ρ fixed (DenseNetworkModel: set ρ = 1).  nhp_disc_model_set_rho must have run.  The sweep chooses between its two routes
+ * to the initial λ from ΣA of the A it starts from, as nhp_disc_resample_adjacency does from its host copy: after _set that
+ * count is the upload's, afterwards it is the previous sweep's device count, read back as 8 bytes at the start of this call --
+ * the one host read of a step; the route, and so the bits, are those of the host entry.  Otherwise asynchronous. */
+nhp_status nhp_disc_model_network_step(nhp_ctx *ctx, const nhp_disc_dataset *ds, nhp_disc_model *model, double net_alpha,
+                                       double net_beta, uint64_t seed, uint64_t step);
+/* Running sums and streaming convergence diagnostics of the model's kept steps.  The contracts are those of
+ * nhp_cont_model_moments_reset / _accumulate / _fetch and nhp_cont_model_diagnostics_configure / _fetch above, definition by
+ * definition: the same planes, the same expressions operation by operation (Σx² += x·x as one fused multiply-add, with or
+ * without diagnostics), the same NaN and "undefined" rules, the same summary fields, the same errors.  What differs is the
+ * entries.  Their order is that of params(process) without the network's ρ (the scalar beside them):
+ *   has_A:  [λ0; vec(W); vec(θ); vec(A)], len = N + N² + N²B + N²;
+ *   else:   [λ0; vec(W .* θ)], len = N + N²B, x = W[p,c]·θ[p,c,b] formed in the pass as ONE rounded product (no contraction).
+ * Summary groups: 0 λ0; 1 θ (has_A) or W∘θ; 2 no entries; 3 W (no entries without has_A); 4 vec(A); 5 ρ (one entry once
+ * nhp_disc_model_set_rho has run).  The index fields count inside the group: p + N·c (+ N²·b). */
+nhp_status nhp_disc_model_moments_reset(nhp_ctx *ctx, nhp_disc_model *model);
+nhp_status nhp_disc_model_moments_accumulate(nhp_ctx *ctx, nhp_disc_model *model);
+nhp_status nhp_disc_model_moments_fetch(nhp_ctx *ctx, const nhp_disc_model *model, double *sum, double *sumsq, int64_t len,
+                                        int64_t *count);
+nhp_status nhp_disc_model_diagnostics_configure(nhp_ctx *ctx, nhp_disc_model *model, int64_t batch_len, int64_t n_planned);
+nhp_status nhp_disc_model_diagnostics_fetch(nhp_ctx *ctx, const nhp_disc_model *model, double ess_below, double rhat_above,
+                                            double *summary, double *ess, double *mcse, double *rhat, int64_t len);
+/* mcmc!(process::DiscreteHawkesProcess, data) inside the library, the loop of nhp_cont_mcmc_run: n_steps times
+ * nhp_disc_model_gibbs_step with the priors (alpha0 … gamma0), nhp_disc_model_network_step when the model has A, and one
+ * nhp_disc_model_moments_accumulate from chain step `burn` on (burn < 0: never); ONE host synchronise, at the end; between the
+ * steps nothing crosses PCIe but the 8-byte link count.  Steps are step0 … step0 + n_steps − 1 and the kept count lives in
+ * the model: a chain cut into calls gives the planes of the chain in one call. */
+nhp_status nhp_disc_mcmc_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, nhp_disc_model *model, double alpha0, double beta0,
+                             double kappa, double nu, double gamma0, double net_alpha, double net_beta, uint64_t seed,
+                             uint64_t step0, int64_t n_steps, int64_t burn);
+
 /* DiscreteLogGaussianCoxProcess(x, λ, Σ, m, dt) as this dataset's baseline (src/baselines.jl:461-509): lam
  * [grid_n * N] (λ[:, n] at n*grid_n) on grid_x [grid_n].  The per-bin baseline intensity(p, 1:T)
  * (src/discrete.jl:117, src/baselines.jl:531-537) is built on the device and kept with the dataset; the other

@@ -144,6 +144,20 @@ def _declare(lib):
     f("nhp_disc_resample_parents", i32, _vp, _vp, _dp, _dp, _dp, _dp, dbl, u64, u64, _ip)
     f("nhp_disc_gibbs_step", i32, _vp, _vp, _dp, _dp, _dp, _dp, dbl, dbl, dbl, dbl, dbl, dbl, u64, u64)
     f("nhp_disc_resample_adjacency", i32, _vp, _vp, _dp, _dp, _dp, _dp, dbl, _dp, dbl, _dp, u64, u64, _dp)
+    f("nhp_disc_model_create", i32, _vp, i32, i32, i32, dbl, C.POINTER(_vp))
+    f("nhp_disc_model_destroy", None, _vp)
+    f("nhp_disc_model_set", i32, _vp, _vp, _dp, _dp, _dp, _dp)
+    f("nhp_disc_model_get", i32, _vp, _vp, _dp, _dp, _dp, _dp)
+    f("nhp_disc_model_set_rho", i32, _vp, _vp, dbl)
+    f("nhp_disc_model_get_rho", i32, _vp, _vp, _dp)
+    f("nhp_disc_model_gibbs_step", i32, _vp, _vp, _vp, dbl, dbl, dbl, dbl, dbl, u64, u64)
+    f("nhp_disc_model_network_step", i32, _vp, _vp, _vp, dbl, dbl, u64, u64)
+    f("nhp_disc_model_moments_reset", i32, _vp, _vp)
+    f("nhp_disc_model_moments_accumulate", i32, _vp, _vp)
+    f("nhp_disc_model_moments_fetch", i32, _vp, _vp, _dp, _dp, i64, C.POINTER(i64))
+    f("nhp_disc_model_diagnostics_configure", i32, _vp, _vp, i64, i64)
+    f("nhp_disc_model_diagnostics_fetch", i32, _vp, _vp, dbl, dbl, _dp, _dp, _dp, _dp, i64)
+    f("nhp_disc_mcmc_run", i32, _vp, _vp, _vp, dbl, dbl, dbl, dbl, dbl, dbl, dbl, u64, u64, i64, i64)
     f("nhp_disc_simulate", i32, _vp, _dp, _dp, _dp, _dp, _dp, _dp, i32, i32, dbl, i32, i64, u64, i64, i32, _vp, _vp, C.POINTER(i64),
       C.POINTER(i32))
     f("nhp_disc_forecast", i32, _vp, _dp, _dp, _dp, _dp, _dp, _dp, i32, i32, dbl, i32, _vp, i64, i32, i64, i64, u64, i64, i32, _vp, _vp,

@@ -641,7 +641,7 @@ extern "C" nhp_status nhp_cont_resample_adjacency(nhp_ctx *ctx, const nhp_cont_d
 // ---- BernoulliNetworkModel on the device: resample!(network, A) (src/networks.jl:70-78) -----------------------------
 // ρ ~ Beta(α + ΣA, β + N² - ΣA) as X / (X + Y), X ~ Gamma(α + ΣA), Y ~ Gamma(β + N² - ΣA), Philox-keyed (seed, step); the
 // link counts of the columns are added in a fixed order (one workgroup: deterministic).  state = {ρ, Σρ, Σρ², ΣA}.
-#include "nhp_rng.h"
+#include "nhp_rho.h"         // k_rho_draw: shared with the discrete chain
 __global__ __launch_bounds__(256) void k_links_total(const double *__restrict__ col_links, int N, double *__restrict__ state)
 {
     __shared__ double red[4];
@@ -649,15 +649,6 @@ __global__ __launch_bounds__(256) void k_links_total(const double *__restrict__ 
     for (int c = threadIdx.x; c < N; c += 256) s += col_links[c];
     s = nhp_block_sum_n<4>(s, red);
     if (threadIdx.x == 0) state[3] = s;
-}
-
-__global__ void k_rho_draw(double *__restrict__ state, double alpha, double beta, double nn, uint64_t seed, uint64_t step)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const double links = state[3];
-    const double x = dev_gamma(alpha + links, 1.0, seed ^ 0x3F84D5B5B5470917ull, step, 0);
-    const double y = dev_gamma(beta + nn - links, 1.0, seed ^ 0x3F84D5B5B5470917ull, step, 1);
-    state[0] = x / (x + y);
 }
 
 static nhp_status ensure_rho(nhp_ctx *ctx, nhp_cont_model *m)

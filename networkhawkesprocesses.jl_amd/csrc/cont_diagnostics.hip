@@ -3,8 +3,9 @@
 // sample size, Monte-Carlo standard error and split R-hat need three more running planes (batch sum, Σ and Σ² of the batch
 // means) and two snapshots of the sums.  k_diag_accumulate makes the moments' pass and these updates in ONE launch per kept
 // step -- same expressions and bits for Σx, Σx² -- and the finalize kernels turn the planes into per-entry values and one
-// summary per parameter group, once per chain.
-#include "nhp_internal.h"
+// summary per parameter group, once per chain.  The planes, the snapshots and the finalize serve the discrete chain too
+// (nhp_diag.h; disc_chain.hip brings its own accumulate kernel, since its source of x differs).
+#include "nhp_diag.h"
 #include <algorithm>
 #include <math.h>
 
@@ -12,47 +13,12 @@
 // restatement): no contraction.  The one fused multiply-add is explicit: Σx² += x·x, as the moments kernel compiles it.
 #pragma clang fp contract(off)
 
-struct nhp_diag_state {
-    int64_t b = 0, planned = 0, h = 0;      // batch length, planned kept steps, ⌊planned/2⌋
-    int64_t count = 0;                      // kept steps the planes have seen
-    int64_t len = 0;                        // entries
-    int nsnap = 0;                          // 0 (h < 2), 1 (planned even) or 2
-    double *d_bat = nullptr;                // ONE allocation: B | SB | QB [3][len], snapshots [nsnap][2][len], ρ's scalars [8]
-    double *d_snap = nullptr;
-    double *d_rho = nullptr;                // {B, SB, QB, snapA Σρ, Σρ², snapB Σρ, Σρ², -}
-};
-
 // ---- the fused accumulate ----------------------------------------------------------------------------------------------
 // Streaming: per entry one read of x and a read + write of Σx, Σx², B (7 planes; 11 on a batch boundary, which adds SB and
 // QB), nothing reused; at most 2048 workgroups stride over the entries.  Accesses stay at 8 bytes per lane: the planes of
 // the sums start at multiples of len and the A seam sits at P, so with an odd len or P no pairing of entries is 16-byte
 // aligned in every plane, and where it is (P and len even) a 16-byte variant measured the same within the spread of the
 // runs -- the kernel moves its plane count at the rate k_moments moves its own.
-template <bool BOUNDARY>
-__device__ __forceinline__ void diag_update(double x, double &s1, double &s2, double &B, double &SB, double &QB, double b)
-{
-    s1 += x;
-    s2 = __builtin_fma(x, x, s2);
-    B += x;
-    if (BOUNDARY) {
-        const double m = B / b;
-        SB += m;
-        QB += m * m;
-        B = 0.0;
-    }
-}
-
-template <bool BOUNDARY>
-__device__ __forceinline__ void diag_rho(double *__restrict__ rho, double *__restrict__ rd, double b)
-{
-    const double r = rho[0];
-    double s1 = rho[1], s2 = rho[2], B = rd[0], SB = 0.0, QB = 0.0;
-    if (BOUNDARY) { SB = rd[1]; QB = rd[2]; }
-    diag_update<BOUNDARY>(r, s1, s2, B, SB, QB, b);
-    rho[1] = s1; rho[2] = s2; rd[0] = B;
-    if (BOUNDARY) { rd[1] = SB; rd[2] = QB; }
-}
-
 template <bool BOUNDARY>
 __global__ __launch_bounds__(256) void k_diag_accumulate(const double *__restrict__ params, int64_t P, const double *__restrict__ A,
                                                          int64_t len, double *__restrict__ mom, double *__restrict__ bat, double b,
@@ -69,13 +35,16 @@ __global__ __launch_bounds__(256) void k_diag_accumulate(const double *__restric
     if (rho && blockIdx.x == 0 && threadIdx.x == 0) diag_rho<BOUNDARY>(rho, rd, b);
 }
 
-void nhp_diag_free(nhp_cont_model *m)
+// ---- planes and snapshots: shared by the two models (nhp_diag.h) -------------------------------------------------------
+void nhp_diag_release(nhp_diag_state **pd)
 {
-    if (!m->diag) return;
-    (void)hipFree(m->diag->d_bat);
-    delete m->diag;
-    m->diag = nullptr;
+    if (!*pd) return;
+    (void)hipFree((*pd)->d_bat);
+    delete *pd;
+    *pd = nullptr;
 }
+
+void nhp_diag_free(nhp_cont_model *m) { nhp_diag_release(&m->diag); }
 
 static int64_t diag_model_len(const nhp_cont_model *m)
 {
@@ -83,16 +52,16 @@ static int64_t diag_model_len(const nhp_cont_model *m)
 }
 
 // (re)allocate the planes for `len` entries; on failure diagnostics are off and the moments untouched
-static nhp_status diag_fit(nhp_ctx *ctx, nhp_cont_model *m, int64_t len)
+static nhp_status diag_fit(nhp_ctx *ctx, nhp_diag_state **pd, int64_t len)
 {
-    nhp_diag_state *d = m->diag;
+    nhp_diag_state *d = *pd;
     if (d->d_bat && d->len == len) return NHP_OK;
     if (d->d_bat) { NHP_HIP(ctx, hipStreamSynchronize(ctx->main())); (void)hipFree(d->d_bat); d->d_bat = nullptr; }
     d->len = len;
     const size_t n = (3 + 2 * (size_t)d->nsnap) * (size_t)len + 8;
     if (hipMalloc((void **)&d->d_bat, sizeof(double) * n) != hipSuccess) {
         (void)hipGetLastError();
-        nhp_diag_free(m);
+        nhp_diag_release(pd);
         nhp_set_error(ctx, "out of device memory (convergence diagnostics): diagnostics are off, the moments are kept");
         return NHP_ENOMEM;
     }
@@ -101,14 +70,51 @@ static nhp_status diag_fit(nhp_ctx *ctx, nhp_cont_model *m, int64_t len)
     return NHP_OK;
 }
 
-nhp_status nhp_diag_reset(nhp_ctx *ctx, nhp_cont_model *m)
+nhp_status nhp_diag_zero(nhp_ctx *ctx, nhp_diag_state **pd, int64_t len)
 {
-    NHP_TRY(diag_fit(ctx, m, m->mom_len > 0 ? m->mom_len : diag_model_len(m)));
-    nhp_diag_state *d = m->diag;
+    NHP_TRY(diag_fit(ctx, pd, len));
+    nhp_diag_state *d = *pd;
     const size_t n = (3 + 2 * (size_t)d->nsnap) * (size_t)d->len + 8;
     NHP_HIP(ctx, hipMemsetAsync(d->d_bat, 0, sizeof(double) * n, ctx->main()));
     d->count = 0;
     return NHP_OK;
+}
+
+nhp_status nhp_diag_advance(nhp_ctx *ctx, nhp_diag_state *d, const nhp_diag_sums &s)
+{
+    const int64_t len = d->len;
+    hipStream_t st = ctx->main();
+    ++d->count;
+    // the halves of split R-hat: (Σx, Σx²) as they stand after h and after n_planned − h kept steps, device to device
+    for (int k = 0; k < d->nsnap; ++k) {
+        if (d->count != (k == 0 ? d->h : d->planned - d->h)) continue;
+        NHP_HIP(ctx, hipMemcpyAsync(d->d_snap + (size_t)k * 2 * (size_t)len, s.d_mom, sizeof(double) * 2 * (size_t)len,
+                                    hipMemcpyDeviceToDevice, st));
+        if (s.d_rho) NHP_HIP(ctx, hipMemcpyAsync(d->d_rho + 3 + 2 * k, s.d_rho + 1, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+    return NHP_OK;
+}
+
+nhp_status nhp_diag_configure(nhp_ctx *ctx, nhp_diag_state **pd, int64_t len, int64_t batch_len, int64_t n_planned)
+{
+    if (batch_len == 0 && n_planned == 0) {
+        if (*pd) { NHP_HIP(ctx, hipStreamSynchronize(ctx->main())); nhp_diag_release(pd); }
+        return NHP_OK;
+    }
+    if (batch_len < 1 || n_planned < 0) { nhp_set_error(ctx, "diagnostics: batch_len must be >= 1 and n_planned >= 0 (0, 0 turns them off)"); return NHP_EINVAL; }
+    const int64_t h = n_planned / 2;
+    const int nsnap = h < 2 ? 0 : (n_planned % 2 == 0 ? 1 : 2);
+    if (*pd && (*pd)->nsnap != nsnap) { NHP_HIP(ctx, hipStreamSynchronize(ctx->main())); nhp_diag_release(pd); }
+    if (!*pd) *pd = new nhp_diag_state;
+    nhp_diag_state *d = *pd;
+    d->b = batch_len; d->planned = n_planned; d->h = h; d->nsnap = nsnap;
+    return nhp_diag_zero(ctx, pd, len);
+}
+
+// ---- the continuous model's share --------------------------------------------------------------------------------------
+nhp_status nhp_diag_reset(nhp_ctx *ctx, nhp_cont_model *m)
+{
+    return nhp_diag_zero(ctx, &m->diag, m->mom_len > 0 ? m->mom_len : diag_model_len(m));
 }
 
 nhp_status nhp_diag_accumulate(nhp_ctx *ctx, nhp_cont_model *m)
@@ -116,22 +122,12 @@ nhp_status nhp_diag_accumulate(nhp_ctx *ctx, nhp_cont_model *m)
     nhp_diag_state *d = m->diag;
     if (d->len != m->mom_len) { nhp_set_error(ctx, "diagnostics: the model's sums changed their length (nhp_cont_model_moments_reset)"); return NHP_EINVAL; }
     const int64_t len = d->len, P = (int64_t)nhp_layout(m).P;
-    const bool boundary = (d->count + 1) % d->b == 0;
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((len + 255) / 256, 2048));
     const double *A = m->has_A ? m->d_A : nullptr;
-    hipStream_t st = ctx->main();
-    hipLaunchKernelGGL(boundary ? k_diag_accumulate<true> : k_diag_accumulate<false>, dim3(blocks), dim3(256), 0, st,
+    hipLaunchKernelGGL(nhp_diag_boundary(d) ? k_diag_accumulate<true> : k_diag_accumulate<false>, dim3(blocks), dim3(256), 0, ctx->main(),
                        (const double *)m->d_params, P, A, len, m->d_mom, d->d_bat, (double)d->b, m->d_rho, d->d_rho);
     NHP_HIP(ctx, hipGetLastError());
-    ++d->count;
-    // the halves of split R-hat: (Σx, Σx²) as they stand after h and after n_planned − h kept steps, device to device
-    for (int s = 0; s < d->nsnap; ++s) {
-        if (d->count != (s == 0 ? d->h : d->planned - d->h)) continue;
-        NHP_HIP(ctx, hipMemcpyAsync(d->d_snap + (size_t)s * 2 * (size_t)len, m->d_mom, sizeof(double) * 2 * (size_t)len,
-                                    hipMemcpyDeviceToDevice, st));
-        if (m->d_rho) NHP_HIP(ctx, hipMemcpyAsync(d->d_rho + 3 + 2 * s, m->d_rho + 1, 2 * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
-    return NHP_OK;
+    return nhp_diag_advance(ctx, d, nhp_diag_sums{m->d_mom, m->mom_len, m->mom_count, m->d_rho});
 }
 
 extern "C" nhp_status nhp_cont_model_diagnostics_configure(nhp_ctx *ctx, nhp_cont_model *m, int64_t batch_len, int64_t n_planned)
@@ -139,19 +135,11 @@ extern "C" nhp_status nhp_cont_model_diagnostics_configure(nhp_ctx *ctx, nhp_con
     if (!ctx || !m) return NHP_EINVAL;
     if (m->ctx != ctx) { nhp_set_error(ctx, "model belongs to another ctx"); return NHP_EINVAL; }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
-    if (batch_len == 0 && n_planned == 0) {
-        if (m->diag) { NHP_HIP(ctx, hipStreamSynchronize(ctx->main())); nhp_diag_free(m); }
-        return NHP_OK;
+    if ((batch_len != 0 || n_planned != 0) && batch_len >= 1 && n_planned >= 0 && m->baseline_kind != NHP_BASELINE_HOMOGENEOUS) {
+        nhp_set_error(ctx, "diagnostics: homogeneous baseline only");
+        return NHP_ENOTIMPL;
     }
-    if (batch_len < 1 || n_planned < 0) { nhp_set_error(ctx, "diagnostics: batch_len must be >= 1 and n_planned >= 0 (0, 0 turns them off)"); return NHP_EINVAL; }
-    if (m->baseline_kind != NHP_BASELINE_HOMOGENEOUS) { nhp_set_error(ctx, "diagnostics: homogeneous baseline only"); return NHP_ENOTIMPL; }
-    const int64_t h = n_planned / 2;
-    const int nsnap = h < 2 ? 0 : (n_planned % 2 == 0 ? 1 : 2);
-    if (m->diag && m->diag->nsnap != nsnap) { NHP_HIP(ctx, hipStreamSynchronize(ctx->main())); nhp_diag_free(m); }
-    if (!m->diag) m->diag = new nhp_diag_state;
-    nhp_diag_state *d = m->diag;
-    d->b = batch_len; d->planned = n_planned; d->h = h; d->nsnap = nsnap;
-    return nhp_diag_reset(ctx, m);
+    return nhp_diag_configure(ctx, &m->diag, m->mom_len > 0 ? m->mom_len : diag_model_len(m), batch_len, n_planned);
 }
 
 // ---- finalize: per-entry values and one summary per group, once per chain ----------------------------------------------
@@ -219,17 +207,15 @@ __device__ __forceinline__ void diag_part_merge(diag_part &p, const diag_part &o
     if (o.max_mcse == o.max_mcse && !(p.max_mcse >= o.max_mcse)) p.max_mcse = o.max_mcse;
 }
 
-struct diag_groups { int64_t start[NHP_DIAG_GROUPS]; };    // first entry of the five array groups, and their end
-
 // grid (nb, 5): workgroup (x, g) takes entries x·256 + t, + nb·256, ... of group g; its partial goes to parts[g·nb + x]
-__global__ __launch_bounds__(256) void k_diag_entries(diag_groups G, diag_consts k, int64_t len, const double *__restrict__ mom,
+__global__ __launch_bounds__(256) void k_diag_entries(nhp_diag_groups G, diag_consts k, int64_t len, const double *__restrict__ mom,
                                                       const double *__restrict__ bat, const double *__restrict__ snapA,
                                                       const double *__restrict__ snapB, double *__restrict__ ess, double *__restrict__ mcse,
                                                       double *__restrict__ rhat, diag_part *__restrict__ parts)
 {
     __shared__ diag_part sh[256];
     const int g = blockIdx.y;
-    const int64_t first = G.start[g], n = G.start[g + 1] - first;
+    const int64_t first = G.start[g], n = G.end[g] - first;
     diag_part p = diag_part_empty();
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
         const int64_t i = first + e;
@@ -252,7 +238,7 @@ __global__ __launch_bounds__(256) void k_diag_entries(diag_groups G, diag_consts
 
 // one workgroup: thread g < 5 merges its group's partials by index; thread 5 is ρ's single entry (snap_b: where its second
 // snapshot sits in rd -- 5, or 3 when one snapshot serves both halves)
-__global__ __launch_bounds__(64) void k_diag_summary(diag_groups G, diag_consts k, int nb, const diag_part *__restrict__ parts,
+__global__ __launch_bounds__(64) void k_diag_summary(nhp_diag_groups G, diag_consts k, int nb, const diag_part *__restrict__ parts,
                                                      const double *__restrict__ rho, const double *__restrict__ rd, int snap_b,
                                                      double *__restrict__ summary)
 {
@@ -261,7 +247,7 @@ __global__ __launch_bounds__(64) void k_diag_summary(diag_groups G, diag_consts 
     diag_part p = diag_part_empty();
     double entries = 0.0;
     if (g < NHP_DIAG_GROUPS - 1) {
-        entries = (double)(G.start[g + 1] - G.start[g]);
+        entries = (double)(G.end[g] - G.start[g]);
         for (int x = 0; x < nb; ++x) diag_part_merge(p, parts[(size_t)g * nb + x]);
     } else if (rho) {
         entries = 1.0;
@@ -272,31 +258,23 @@ __global__ __launch_bounds__(64) void k_diag_summary(diag_groups G, diag_consts 
     s[6] = p.below; s[7] = p.above; s[8] = p.max_mcse;
 }
 
-extern "C" nhp_status nhp_cont_model_diagnostics_fetch(nhp_ctx *ctx, const nhp_cont_model *m, double ess_below, double rhat_above,
-                                                       double *summary, double *ess, double *mcse, double *rhat, int64_t len)
+nhp_status nhp_diag_finalize(nhp_ctx *ctx, const nhp_diag_state *d, const nhp_diag_sums &sums, const nhp_diag_groups &G, int nb,
+                             bool with_rho, double ess_below, double rhat_above, double *summary, double *ess, double *mcse,
+                             double *rhat, int64_t len)
 {
-    if (!ctx || !m || !summary) return NHP_EINVAL;
-    if (m->ctx != ctx) { nhp_set_error(ctx, "model belongs to another ctx"); return NHP_EINVAL; }
-    const nhp_diag_state *d = m->diag;
-    if (!d) { nhp_set_error(ctx, "diagnostics: nothing configured (nhp_cont_model_diagnostics_configure)"); return NHP_EINVAL; }
-    if (!m->d_mom || m->mom_count < 1) { nhp_set_error(ctx, "diagnostics: nothing accumulated"); return NHP_EINVAL; }
-    if (d->count != m->mom_count) {
+    if (!d) { nhp_set_error(ctx, "diagnostics: nothing configured (nhp_cont_model_diagnostics_configure / nhp_disc_model_diagnostics_configure)"); return NHP_EINVAL; }
+    if (!sums.d_mom || sums.count < 1) { nhp_set_error(ctx, "diagnostics: nothing accumulated"); return NHP_EINVAL; }
+    if (d->count != sums.count) {
         nhp_set_error(ctx, "diagnostics: configured after %lld of the sums' %lld steps (configure before the first kept step, or reset the moments)",
-                      (long long)(m->mom_count - d->count), (long long)m->mom_count);
+                      (long long)(sums.count - d->count), (long long)sums.count);
         return NHP_EINVAL;
     }
-    if (len != m->mom_len || len != d->len) { nhp_set_error(ctx, "Parameter vector length does not match model parameter length."); return NHP_ESHAPE; }
+    if (len != sums.len || len != d->len) { nhp_set_error(ctx, "Parameter vector length does not match model parameter length."); return NHP_ESHAPE; }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
-    const nhp_layout L(m);
-    const int64_t NN = (int64_t)m->N * m->N;
-    diag_groups G;
-    G.start[0] = 0; G.start[1] = (int64_t)L.p1; G.start[2] = (int64_t)L.p2; G.start[3] = (int64_t)L.W; G.start[4] = (int64_t)L.P;
-    G.start[5] = len;
     diag_consts k;
     k.n = (double)d->count; k.a = (double)(d->count / d->b); k.b = (double)d->b; k.h = (double)d->h;
     k.split = d->count == d->planned && d->nsnap > 0 ? 1 : 0;
     k.ess_below = ess_below; k.rhat_above = rhat_above;
-    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((std::max<int64_t>(NN, m->N) + 255) / 256, 256));
     // scratch: summary [GROUPS·FIELDS] | partials [5·nb] | ess, mcse, rhat [len] each as asked for
     const size_t head = NHP_DIAG_GROUPS * NHP_DIAG_FIELDS + (size_t)(NHP_DIAG_GROUPS - 1) * nb * NHP_DIAG_PART;
     const int planes = (ess ? 1 : 0) + (mcse ? 1 : 0) + (rhat ? 1 : 0);
@@ -311,10 +289,10 @@ extern "C" nhp_status nhp_cont_model_diagnostics_fetch(nhp_ctx *ctx, const nhp_c
     const double *snapA = d->nsnap > 0 ? d->d_snap : nullptr;
     const double *snapB = d->nsnap > 1 ? d->d_snap + 2 * (size_t)len : snapA;
     hipStream_t st = ctx->main();
-    hipLaunchKernelGGL(k_diag_entries, dim3(nb, NHP_DIAG_GROUPS - 1), dim3(256), 0, st, G, k, len, (const double *)m->d_mom,
+    hipLaunchKernelGGL(k_diag_entries, dim3(nb, NHP_DIAG_GROUPS - 1), dim3(256), 0, st, G, k, len, (const double *)sums.d_mom,
                        (const double *)d->d_bat, snapA, snapB, d_ess, d_mcse, d_rhat, d_parts);
     NHP_HIP(ctx, hipGetLastError());
-    const double *rho = m->d_rho && !m->sbm && !m->latent ? m->d_rho : nullptr;
+    const double *rho = with_rho ? sums.d_rho : nullptr;
     hipLaunchKernelGGL(k_diag_summary, dim3(1), dim3(64), 0, st, G, k, nb, (const diag_part *)d_parts, rho, (const double *)d->d_rho,
                        d->nsnap > 1 ? 5 : 3, d_summary);
     NHP_HIP(ctx, hipGetLastError());
@@ -323,4 +301,19 @@ extern "C" nhp_status nhp_cont_model_diagnostics_fetch(nhp_ctx *ctx, const nhp_c
     if (mcse) NHP_TRY(nhp_download(ctx, mcse, d_mcse, sizeof(double) * (size_t)len));
     if (rhat) NHP_TRY(nhp_download(ctx, rhat, d_rhat, sizeof(double) * (size_t)len));
     return NHP_OK;
+}
+
+extern "C" nhp_status nhp_cont_model_diagnostics_fetch(nhp_ctx *ctx, const nhp_cont_model *m, double ess_below, double rhat_above,
+                                                       double *summary, double *ess, double *mcse, double *rhat, int64_t len)
+{
+    if (!ctx || !m || !summary) return NHP_EINVAL;
+    if (m->ctx != ctx) { nhp_set_error(ctx, "model belongs to another ctx"); return NHP_EINVAL; }
+    const nhp_layout L(m);
+    const int64_t NN = (int64_t)m->N * m->N;
+    nhp_diag_groups G;                  // λ0 | θ or μ | τ | W | vec(A), one after the other
+    const int64_t cut[NHP_DIAG_GROUPS] = {0, (int64_t)L.p1, (int64_t)L.p2, (int64_t)L.W, (int64_t)L.P, m->mom_len};
+    for (int g = 0; g < NHP_DIAG_GROUPS - 1; ++g) { G.start[g] = cut[g]; G.end[g] = cut[g + 1]; }
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((std::max<int64_t>(NN, m->N) + 255) / 256, 256));
+    return nhp_diag_finalize(ctx, m->diag, nhp_diag_sums{m->d_mom, m->mom_len, m->mom_count, m->d_rho}, G, nb,
+                             m->d_rho && !m->sbm && !m->latent, ess_below, rhat_above, summary, ess, mcse, rhat, len);
 }

@@ -952,8 +952,9 @@ static void launch_gemm(const gemm_args &g, int splits, hipStream_t st, int bm =
 // uploads the model pieces, builds E and base on the device; returns pointers into scratch
 nhp_status nhp_disc_stage_bump(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *lambda0, const double *W,
                                const double *theta, const double *A, double dt, double **E, double **base, size_t extra,
-                               double **extra_ptr, int cat_order)
+                               double **extra_ptr, int cat_order, bool on_device)
 {
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (!ds->d_conv) { nhp_set_error(ctx, "convolve(process, data) must run before intensity / loglikelihood"); return NHP_EINVAL; }
     if (!W || !theta) return NHP_EINVAL;
     if (!lambda0 && !ds->d_baseT) { nhp_set_error(ctx, "lambda0 is NULL and the dataset has no LGCP baseline (nhp_disc_set_lgcp_baseline)"); return NHP_EINVAL; }
@@ -969,11 +970,11 @@ nhp_status nhp_disc_stage_bump(nhp_ctx *ctx, const nhp_disc_dataset *ds, const d
     double *dA = p; p += NN;
     *extra_ptr = p;
     hipStream_t st = ctx->main();
-    if (lambda0) NHP_HIP(ctx, hipMemcpyAsync(dl0, lambda0, 8 * N, hipMemcpyHostToDevice, st));
+    if (lambda0) NHP_HIP(ctx, hipMemcpyAsync(dl0, lambda0, 8 * N, kind, st));
     else NHP_HIP(ctx, hipMemsetAsync(dl0, 0, 8 * N, st));          // per-bin baseline comes from ds->d_baseT
-    NHP_HIP(ctx, hipMemcpyAsync(dW, W, 8 * NN, hipMemcpyHostToDevice, st));
-    NHP_HIP(ctx, hipMemcpyAsync(dth, theta, 8 * NN * B, hipMemcpyHostToDevice, st));
-    if (A) NHP_HIP(ctx, hipMemcpyAsync(dA, A, 8 * NN, hipMemcpyHostToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(dW, W, 8 * NN, kind, st));
+    NHP_HIP(ctx, hipMemcpyAsync(dth, theta, 8 * NN * B, kind, st));
+    if (A) NHP_HIP(ctx, hipMemcpyAsync(dA, A, 8 * NN, kind, st));
     hipLaunchKernelGGL(k_disc_bump, dim3((unsigned)((NN * B + 255) / 256)), dim3(256), 0, st, (int)N, (int)B, dt, dl0, dW,
                        dth, A ? dA : nullptr, dE, dbase, cat_order);
     NHP_HIP(ctx, hipGetLastError());

@@ -327,12 +327,12 @@ __global__ __launch_bounds__(RP_TH, 4) void k_disc_resample_parents(const double
 static nhp_status disc_parent_counts(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *lambda0, const double *W,
                                      const double *theta, const double *A, double dt, uint64_t seed, uint64_t step,
                                      size_t extra_doubles, int **d_counts_out, double **extra_out, double **dW_out,
-                                     double **dth_out, double **dl0_out)
+                                     double **dth_out, double **dl0_out, bool on_device = false)
 {
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t N = (size_t)ds->N, NN = N * N, K = N * (size_t)ds->B, NC = N * (1 + K);
     double *E2, *base, *extra;
-    NHP_TRY(nhp_disc_stage_bump(ctx, ds, lambda0, W, theta, A, dt, &E2, &base, (NC + 1) / 2 + 1 + extra_doubles, &extra, 1));
+    NHP_TRY(nhp_disc_stage_bump(ctx, ds, lambda0, W, theta, A, dt, &E2, &base, (NC + 1) / 2 + 1 + extra_doubles, &extra, 1, on_device));
     int *d_counts = reinterpret_cast<int *>(extra);
     hipStream_t st = ctx->main();
     NHP_HIP(ctx, hipMemsetAsync(d_counts, 0, sizeof(int) * NC, st));
@@ -434,6 +434,21 @@ extern "C" nhp_status nhp_disc_gibbs_step(nhp_ctx *ctx, const nhp_disc_dataset *
     return NHP_OK;
 }
 
+// The same step on a device-resident state (nhp_disc_model): E and base are staged from the device block, the draws land in
+// the block itself -- the launches, the Philox keys and the arithmetic of nhp_disc_gibbs_step, no host copy, no synchronise.
+nhp_status nhp_disc_gibbs_enqueue(nhp_ctx *ctx, const nhp_disc_dataset *ds, double *d_lambda0, double *d_W, double *d_theta,
+                                  const double *d_A, double dt, double alpha0, double beta0, double kappa, double nu, double gamma0,
+                                  uint64_t seed, uint64_t step)
+{
+    const size_t N = (size_t)ds->N, NN = N * N;
+    int *d_counts;
+    NHP_TRY(disc_parent_counts(ctx, ds, d_lambda0, d_W, d_theta, d_A, dt, seed, step, 0, &d_counts, nullptr, nullptr, nullptr, nullptr, true));
+    hipLaunchKernelGGL(k_disc_gibbs_draw, dim3((unsigned)((NN + 255) / 256)), dim3(256), 0, ctx->main(), (int)N, (int)ds->B,
+                       (double)ds->T * dt, alpha0, beta0, kappa, nu, gamma0, seed, step, d_counts, ds->d_colsum, d_lambda0, d_W, d_theta);
+    NHP_HIP(ctx, hipGetLastError());
+    return NHP_OK;
+}
+
 // ---- discrete adjacency Gibbs sweep (reference resample_adjacency_matrix! / resample_column!
 // / conditional_loglikelihood src/discrete.jl:424-480).  For entry (p, c) the reference evaluates two full
 // Poisson log-likelihoods of column c over all T bins and all N·B parent terms.  Their difference is
@@ -478,6 +493,7 @@ __global__ __launch_bounds__(256) void k_dadj_gather(const double *__restrict__ 
 // SX[p][c] = Σ_t x_t
 __global__ __launch_bounds__(256) void k_dadj_tables(int N, int B, double dt, const double *__restrict__ W, const double *__restrict__ theta,
                                                      const double *__restrict__ A, const double *__restrict__ rho_mat, double rho_scalar,
+                                                     const double *__restrict__ rho_dev /* the scalar, on the device (or null) */,
                                                      const double *__restrict__ u, uint64_t seed, uint64_t step, double *__restrict__ Vall,
                                                      double *__restrict__ AT, double *__restrict__ LU, double *__restrict__ LR1,
                                                      double *__restrict__ LR2, const double *__restrict__ convsum, double *__restrict__ SX)
@@ -491,7 +507,7 @@ __global__ __launch_bounds__(256) void k_dadj_tables(int N, int B, double dt, co
         const int p = p0 + lp, c = c0 + lc;
         if (p < N && c < N) {
             const size_t pc = (size_t)p + (size_t)c * N;
-            const double rho = rho_mat ? rho_mat[pc] : rho_scalar;
+            const double rho = rho_mat ? rho_mat[pc] : rho_dev ? rho_dev[0] : rho_scalar;
             const double uu = u ? u[pc] : nhp_philox_uniform(seed ^ 0xAD7AC3117D15C0DEull, step, pc);
             tw[lc][lp] = W[pc]; ta[lc][lp] = A[pc];
             tu[lc][lp] = nhp_log(uu / (1.0 - uu)); t1[lc][lp] = nhp_log(rho); t2[lc][lp] = nhp_log(1.0 - rho);
@@ -859,13 +875,14 @@ static void (*dadj_step_kernel(bool pack, bool vlds))(int, nhp_dadj_args)
 // 12 entries a thread the 128 registers do not hold words + λ + x, so a flip is carried by recomputing x for every entry of
 // a wave that holds one flipped column (13.6 µs a step, as much as the entries' pass itself), and the pass spills
 // (18.7 µs against 13.5); stamps in profiles/README.md.  Removed.)
-extern "C" nhp_status nhp_disc_resample_adjacency(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *lambda0,
-                                                  const double *W, const double *theta, double *A, double dt,
-                                                  const double *rho_matrix, double rho, const double *u,
-                                                  uint64_t seed, uint64_t step, double *n_links)
+// The sweep, enqueued.  λ0, W, θ, A are host arrays, or with `on_device` device arrays outside the scratch; `links` = ΣA of the
+// A the sweep starts from (it picks the route to the initial λ below); d_rho_scalar (nullable): the scalar link probability
+// read on the device in place of `rho`.  The decisions go to the staged copy of A in scratch (*dA_out), or to d_A_out.
+static nhp_status dadj_enqueue(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *lambda0, const double *W, const double *theta,
+                               const double *A, bool on_device, double dt, const double *rho_matrix, double rho,
+                               const double *d_rho_scalar, const double *u, uint64_t seed, uint64_t step, size_t links,
+                               double *d_A_out, double **dA_out)
 {
-    if (!ctx || !ds || !A) return NHP_EINVAL;
-    if (!rho_matrix && !(rho >= 0.0 && rho <= 1.0)) { nhp_set_error(ctx, "link probability must lie in [0, 1]"); return NHP_EDOMAIN; }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     const size_t N = (size_t)ds->N, NN = N * N, B = (size_t)ds->B, TN = (size_t)ds->T * N;
     const size_t nocc = (size_t)(ds->nocc_pad > 0 ? ds->nocc_pad : 4);
@@ -883,7 +900,7 @@ extern "C" nhp_status nhp_disc_resample_adjacency(nhp_ctx *ctx, const nhp_disc_d
     // V (all rows) | A's rows | logit u | log ρ | log(1-ρ) | Σ_t x_t | u | ρ | tickets
     const size_t extra = TN + nocc + 2 + (size_t)nwg * N + std::max<size_t>(2 * (size_t)ngrp, 3) * N + NN * B + 5 * NN + 2 * NN + 4 * (size_t)(2 + ngrp) * 4 + 16;
     double *E, *base, *x;
-    NHP_TRY(nhp_disc_stage_bump(ctx, ds, lambda0, W, theta, A, dt, &E, &base, extra, &x, 0));
+    NHP_TRY(nhp_disc_stage_bump(ctx, ds, lambda0, W, theta, A, dt, &E, &base, extra, &x, 0, on_device));
     double *dlam = x; x += TN;
     double *lam_occ = x + (((uintptr_t)x & 15) ? 1 : 0); x += nocc + 2;      // (16-byte aligned: read as double2)
     double *partial = x; x += (size_t)nwg * N;
@@ -905,8 +922,6 @@ extern "C" nhp_status nhp_disc_resample_adjacency(nhp_ctx *ctx, const nhp_disc_d
     // λ under the current A at the occupied bins: from the entry lists themselves (k_dadj_lambda0) where a thread's share fits
     // its registers, else the T x N intensity GEMM and a gather (NHP_DADJ_LAMBDA0=0: always the GEMM)
     // (the list route skips absent links: measured against the GEMM at link densities 0.2 / 0.5 / 0.8 / 1.0: -0.8 / -2.6 / +1.6 / +1.4 ms)
-    size_t links = 0;
-    for (size_t i = 0; i < NN; ++i) links += A[i] != 0.0;
     const int l0_env = getenv("NHP_DADJ_LAMBDA0") ? atoi(getenv("NHP_DADJ_LAMBDA0")) : -1;        // 0 | 1: never | whenever possible
     const bool lam_pass = ds->d_occ_pack && vlds && (ds->B == 8 || ds->B == 4) && ds->da_max_entries <= 12 * 512 && 2 * 512 >= (int)N &&
                           l0_env != 0 && (l0_env == 1 || (double)links <= 0.6 * (double)NN);
@@ -916,7 +931,7 @@ extern "C" nhp_status nhp_disc_resample_adjacency(nhp_ctx *ctx, const nhp_disc_d
                            ds->nocc_pad, ds->T, lam_occ);
     }
     hipLaunchKernelGGL(k_dadj_tables, dim3((unsigned)((N + 15) / 16), (unsigned)((N + 15) / 16)), dim3(256), 0, st, ds->N, ds->B, dt, dW, dth, dA,
-                       rho_matrix ? d_rho : nullptr, rho, u ? d_u : nullptr, seed, step, Vall, AT, LU, LR1, LR2, ds->d_convsum, SX);
+                       rho_matrix ? d_rho : nullptr, rho, d_rho_scalar, u ? d_u : nullptr, seed, step, Vall, AT, LU, LR1, LR2, ds->d_convsum, SX);
     NHP_HIP(ctx, hipMemsetAsync(tick, 0, 4 * (32 * (size_t)(1 + ngrp) + 4), st));
     NHP_HIP(ctx, hipMemsetAsync(gpartial, 0, 8 * 3 * N, st));
     NHP_HIP(ctx, hipGetLastError());
@@ -924,7 +939,7 @@ extern "C" nhp_status nhp_disc_resample_adjacency(nhp_ctx *ctx, const nhp_disc_d
     a.N = ds->N; a.B = ds->B; a.nspans = nwg; a.gsz = (int)gsz; a.T = ds->T; a.conv = ds->d_conv; a.occ_pack = ds->d_occ_pack;
     a.occ_t = ds->d_occ_t; a.occ_c = ds->d_occ_c; a.occ_off = ds->d_occ_off; a.span_t = ds->d_span_t; a.occ_s = ds->d_occ_s;
     a.Vall = Vall; a.AT = AT; a.LU = LU; a.LR1 = LR1; a.LR2 = LR2; a.SX = SX; a.lam_occ = lam_occ;
-    a.partial = partial; a.gpartial = gpartial; a.tick = tick; a.A = dA;
+    a.partial = partial; a.gpartial = gpartial; a.tick = tick; a.A = d_A_out ? d_A_out : dA;      // (the tables hold the old A: AT)
     if (lam_pass) {
         const size_t l0 = 8 * ((size_t)B * NHP_DA_SPAN + N + N * B);
         if (ds->B == 8) {
@@ -942,8 +957,34 @@ extern "C" nhp_status nhp_disc_resample_adjacency(nhp_ctx *ctx, const nhp_disc_d
     for (int p = 0; p <= ds->N; ++p)                                   // launch N: the last row's decision alone
         hipLaunchKernelGGL(kern, dim3(p < ds->N ? (unsigned)nwg : 1u), dim3(DADJ_TH), lds, st, p, a);
     NHP_HIP(ctx, hipGetLastError());
+    if (dA_out) *dA_out = dA;
+    return NHP_OK;
+}
+
+extern "C" nhp_status nhp_disc_resample_adjacency(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *lambda0,
+                                                  const double *W, const double *theta, double *A, double dt,
+                                                  const double *rho_matrix, double rho, const double *u,
+                                                  uint64_t seed, uint64_t step, double *n_links)
+{
+    if (!ctx || !ds || !A) return NHP_EINVAL;
+    if (!rho_matrix && !(rho >= 0.0 && rho <= 1.0)) { nhp_set_error(ctx, "link probability must lie in [0, 1]"); return NHP_EDOMAIN; }
+    const size_t NN = (size_t)ds->N * ds->N;
+    size_t links = 0;
+    for (size_t i = 0; i < NN; ++i) links += A[i] != 0.0;
+    double *dA = nullptr;
+    NHP_TRY(dadj_enqueue(ctx, ds, lambda0, W, theta, A, false, dt, rho_matrix, rho, nullptr, u, seed, step, links, nullptr, &dA));
+    hipStream_t st = ctx->main();
     NHP_HIP(ctx, hipMemcpyAsync(A, dA, 8 * NN, hipMemcpyDeviceToHost, st));
     NHP_HIP(ctx, hipStreamSynchronize(st));
     if (n_links) { double s = 0.0; for (size_t i = 0; i < NN; ++i) s += A[i]; *n_links = s; }
     return NHP_OK;
+}
+
+// The sweep on a device-resident state (nhp_disc_model): the same launches on the same bits, A decided in place, the scalar
+// link probability read from the device; no download, no synchronise.
+nhp_status nhp_disc_adjacency_enqueue(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *d_lambda0, const double *d_W,
+                                      const double *d_theta, double *d_A, double dt, const double *d_rho, uint64_t seed, uint64_t step,
+                                      size_t links)
+{
+    return dadj_enqueue(ctx, ds, d_lambda0, d_W, d_theta, d_A, true, dt, nullptr, 0.5, d_rho, nullptr, seed, step, links, d_A, nullptr);
 }

@@ -440,9 +440,44 @@ struct nhp_disc_dataset {
 // disc.hip pieces shared with disc_gibbs.hip: upload W, θ, A (and λ0) and build the bump table E [N·B x N] on the device
 // (GEMM order k = p + b·N, or the reference's category order p·B + b with cat_order) plus base[c] = λ0[c]·dt; `extra`
 // doubles of scratch follow at *extra_ptr.  Layout after E: base (N) | λ0 (N) | W (N²) | θ (N²B) | A (N²) | extra.
+// `on_device`: the four sources are device pointers outside the scratch (a device-resident model: nhp_disc_model), copied
+// device to device into the same layout -- everything behind the copies is the same launch on the same bits.
 nhp_status nhp_disc_stage_bump(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *lambda0, const double *W,
                                const double *theta, const double *A, double dt, double **E, double **base, size_t extra,
-                               double **extra_ptr, int cat_order = 0);
+                               double **extra_ptr, int cat_order = 0, bool on_device = false);
+
+// nhp_disc_model (include/nhp.h, disc_chain.hip): the state of a discrete chain on the device.  ONE block in the order
+// nhp_disc_stage_bump lays its copies out -- λ0 (N) | W (N²) | θ (N²B) | A (N², has_A) -- so staging is one copy per piece and
+// the sums below follow the block entry by entry.
+struct nhp_disc_model {
+    nhp_ctx *ctx = nullptr;
+    int32_t N = 0, B = 0, has_A = 0;
+    double dt = 1.0;
+    double *d_block = nullptr;          // owned
+    double *d_lambda0 = nullptr, *d_W = nullptr, *d_theta = nullptr, *d_A = nullptr;      // into d_block
+    // the network's scalars {ρ, Σρ, Σρ², ΣA of the latest sweep} (has_A: allocated with the model) and ΣA once more as the
+    // exact integer the sweep's route is chosen from
+    double *d_rho = nullptr;
+    long long *d_links = nullptr;
+    bool rho_set = false;
+    // ΣA of the current A as the host knows it: counted at _set, read back (8 bytes) after a sweep when the next one asks
+    int64_t links = 0;
+    bool links_on_device = false;
+    // running sums over the kept steps (nhp_disc_model_moments_*): Σx | Σx² [2][mom_len] in params(process) order --
+    // network: the block itself; standard: [λ0; vec(W∘θ)]
+    double *d_mom = nullptr;
+    int64_t mom_len = 0, mom_count = 0;
+    struct nhp_diag_state *diag = nullptr;              // nhp_diag.h; null: not configured
+};
+// disc_gibbs.hip: the two halves of a chain step on device-resident state, asynchronous on the main stream.  The Gibbs half
+// reads and overwrites λ0, W, θ (the bits of nhp_disc_gibbs_step); the sweep overwrites A (the bits of
+// nhp_disc_resample_adjacency with the scalar *d_rho and Philox uniforms), `links` = ΣA of the A it starts from.
+nhp_status nhp_disc_gibbs_enqueue(nhp_ctx *ctx, const nhp_disc_dataset *ds, double *d_lambda0, double *d_W, double *d_theta,
+                                  const double *d_A, double dt, double alpha0, double beta0, double kappa, double nu, double gamma0,
+                                  uint64_t seed, uint64_t step);
+nhp_status nhp_disc_adjacency_enqueue(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *d_lambda0, const double *d_W,
+                                      const double *d_theta, double *d_A, double dt, const double *d_rho, uint64_t seed, uint64_t step,
+                                      size_t links);
 nhp_status nhp_disc_launch_intensity(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *E, const double *base,
                                      bool per_bin_baseline, double *dlam);
 // disc.hip launches re-driven by disc_information.hip: the log-likelihood of a staged bump table (-> ctx->d_results[0], the

@@ -1046,11 +1046,202 @@ def disc_resample_(process, data, convolved, rng, seed=0, step=0, ctx=None, devi
     return process.params()
 
 
-def disc_mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, ctx=None, device_draws=True):
+class DiscreteDeviceModel:
+    """nhp_disc_model handle: the state of a discrete chain in one device block, [λ0; vec(W); vec(θ); vec(A) of a network
+    process], with the network's scalar ρ beside it (csrc/disc_chain.hip)."""
+
+    def __init__(self, ctx, process):
+        self.ctx, self.N, self.B = ctx, process.ndims(), process.impulses.nbasis()
+        self.network = isinstance(process, DiscreteNetworkHawkesProcess)
+        self.h = C.c_void_p()
+        _lib.check(_lib.lib().nhp_disc_model_create(ctx.h, self.N, self.B, int(self.network), process.dt, C.byref(self.h)), ctx.h)
+        self.push(process)
+
+    def push(self, process):
+        """The process's λ0, W, θ (A, ρ) onto the device."""
+        from .components import BernoulliNetworkModel
+        l0, W, th, A = process._lowered()
+        _lib.check(_lib.lib().nhp_disc_model_set(self.ctx.h, self.h, _lib.dptr(l0), _lib.dptr(W), _lib.dptr(th), _lib.dptr(A)), self.ctx.h)
+        if self.network:
+            rho = float(process.network.ρ) if isinstance(process.network, BernoulliNetworkModel) else 1.0
+            _lib.check(_lib.lib().nhp_disc_model_set_rho(self.ctx.h, self.h, rho), self.ctx.h)
+
+    def pull(self, process):
+        """The device state into the process's components; returns {ρ, Σρ, Σρ²} (zeros without a Bernoulli network)."""
+        from .components import BernoulliNetworkModel
+        N, B = self.N, self.B
+        l0, W, th = np.empty(N), np.empty(N * N), np.empty(N * N * B)
+        A = np.empty(N * N) if self.network else None
+        _lib.check(_lib.lib().nhp_disc_model_get(self.ctx.h, self.h, _lib.dptr(l0), _lib.dptr(W), _lib.dptr(th), _lib.dptr(A)), self.ctx.h)
+        process.baseline.λ, process.weights.W = l0, W.reshape((N, N), order="F")
+        process.impulses.θ = th.reshape((N, N, B), order="F")
+        r3 = np.zeros(3)
+        if self.network:
+            process.adjacency_matrix = A.reshape((N, N), order="F")
+            if isinstance(process.network, BernoulliNetworkModel):
+                _lib.check(_lib.lib().nhp_disc_model_get_rho(self.ctx.h, self.h, _lib.dptr(r3)), self.ctx.h)
+                process.network.ρ = float(r3[0])
+        return r3
+
+    def close(self):
+        if getattr(self, "h", None):
+            _lib.lib().nhp_disc_model_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def disc_moments_length(process):
+    """Length of the device-side running sums of nhp_disc_model_moments_*: params(process) without the network's ρ."""
+    N, B = process.ndims(), process.impulses.nbasis()
+    return N + N * N * B + (2 * N * N if isinstance(process, DiscreteNetworkHawkesProcess) else 0)
+
+
+def _check_resident(process, device_draws):
+    """NotImplementedError naming what the device-resident discrete chain (nhp_disc_model) is not built for."""
+    from .components import BernoulliNetworkModel, DenseNetworkModel, SparseWeightModel
+    route = "the default route (keep_samples=True, moments=False) takes it"
+    if not isinstance(process.baseline, DiscreteHomogeneousProcess):
+        raise NotImplementedError(f"the device-resident discrete chain draws a homogeneous baseline (baseline: "
+                                  f"{type(process.baseline).__name__}); {route}")
+    if isinstance(process.weights, SparseWeightModel) or not isinstance(process.weights, DenseWeightModel):
+        raise NotImplementedError(f"the device-resident discrete chain is built for DenseWeightModel (weights: "
+                                  f"{type(process.weights).__name__}); {route}")
+    if not device_draws:
+        raise NotImplementedError(f"the device-resident discrete chain draws on the device (device_draws=False draws with numpy); {route}")
+    if isinstance(process, DiscreteNetworkHawkesProcess) and not isinstance(process.network, (DenseNetworkModel, BernoulliNetworkModel)):
+        raise NotImplementedError(f"the device-resident discrete chain holds a DenseNetworkModel or a BernoulliNetworkModel (network: "
+                                  f"{type(process.network).__name__} keeps its state on the host); {route}")
+
+
+def _disc_fetch_diagnostics(process, model, ctx, full, ess_below, rhat_above):
+    """nhp_disc_model_diagnostics_fetch -> {"summary"[, "ess", "mcse", "rhat"]}; the per-entry arrays in params(process) order
+    (the network's ρ first: its single entry is its group's extreme)."""
+    from .components import BernoulliNetworkModel
+    from .inference import DIAGNOSTIC_FIELDS
+    L = disc_moments_length(process)
+    summary = np.empty(_lib.DIAG_GROUPS * _lib.DIAG_FIELDS)
+    planes = [np.empty(L) for _ in range(3)] if full else [None] * 3
+    _lib.check(_lib.lib().nhp_disc_model_diagnostics_fetch(ctx.h, model.h, float(ess_below), float(rhat_above), _lib.dptr(summary),
+                                                          *[_lib.dptr(v) for v in planes], L), ctx.h)
+    summary = summary.reshape(_lib.DIAG_GROUPS, _lib.DIAG_FIELDS)
+    network = model.network
+    bernoulli = network and isinstance(process.network, BernoulliNetworkModel)
+    names = ["baseline", "impulses.θ" if network else "weights∘impulses", None, "weights" if network else None,
+             "adjacency" if network else None, "network.ρ" if bernoulli else None]
+    ints = ("entries", "undefined", "min_ess_index", "max_rhat_index", "ess_below", "rhat_above")
+    out = {"summary": {name: {f: (int(v) if f in ints else float(v)) for f, v in zip(DIAGNOSTIC_FIELDS, row)}
+                       for name, row in zip(names, summary) if name is not None}}
+    if full:
+        if bernoulli:
+            planes = [np.concatenate([[r], v]) for v, r in zip(planes, summary[5, [2, 8, 4]])]
+        out["ess"], out["mcse"], out["rhat"] = planes
+    return out
+
+
+def _disc_mcmc_resident(process, data, nsteps, log_freq, verbose, seed, ctx, keep_samples, moments, burn, diagnostics, batch_len,
+                        ess_below, rhat_above):
+    """The chain with its state on the device (nhp_disc_model): nothing is uploaded after the start; with keep_samples the
+    state comes back once per step, without it the whole chain is nhp_disc_mcmc_run."""
+    import math
+    import time
+    from .components import BernoulliNetworkModel
+    from .inference import MarkovChainMonteCarlo
+    ctx = ctx or _lib.default_context()
+    ds = convolve(process, data, ctx)
+    lib = _lib.lib()
+    model = DiscreteDeviceModel(ctx, process)
+    b, w, imp = process.baseline, process.weights, process.impulses
+    pri = (b.α0, b.β0, w.κ, w.ν, imp.γ)
+    net = process.network if model.network else None
+    net_a, net_b = (net.α, net.β) if isinstance(net, BernoulliNetworkModel) else (0.0, 0.0)
+    if diagnostics:
+        n_planned = max(0, int(nsteps) - int(burn))
+        diag_b = int(batch_len) if batch_len is not None else max(1, math.isqrt(n_planned))
+        _lib.check(lib.nhp_disc_model_diagnostics_configure(ctx.h, model.h, diag_b, n_planned), ctx.h)
+    if moments:
+        _lib.check(lib.nhp_disc_model_moments_reset(ctx.h, model.h), ctx.h)
+    res = MarkovChainMonteCarlo()
+    start = time.time()
+    try:
+        while res.steps < nsteps:
+            if keep_samples:
+                _lib.check(lib.nhp_disc_model_gibbs_step(ctx.h, ds.h, model.h, *pri, seed, res.steps), ctx.h)
+                if model.network:
+                    _lib.check(lib.nhp_disc_model_network_step(ctx.h, ds.h, model.h, net_a, net_b, seed, res.steps), ctx.h)
+                if moments and res.steps >= burn:
+                    _lib.check(lib.nhp_disc_model_moments_accumulate(ctx.h, model.h), ctx.h)
+                model.pull(process)
+                res.samples.append(process.params())
+                n = 1
+            else:
+                n = min(nsteps - res.steps, log_freq if verbose else nsteps)
+                _lib.check(lib.nhp_disc_mcmc_run(ctx.h, ds.h, model.h, *pri, net_a, net_b, seed, res.steps, n, burn if moments else -1), ctx.h)
+            res.steps += n
+            if res.steps % log_freq == 0 and verbose:
+                res.elapsed = time.time() - start
+                print(f" > step: {res.steps}, elapsed: {res.elapsed}")
+        r3 = model.pull(process)
+        res.elapsed = time.time() - start
+        res.status = "complete"
+        if not keep_samples:
+            res.samples.append(process.params())
+        if moments:
+            L = disc_moments_length(process)
+            s, q, cnt = np.empty(L), np.empty(L), C.c_int64()
+            _lib.check(lib.nhp_disc_model_moments_fetch(ctx.h, model.h, _lib.dptr(s), _lib.dptr(q), L, C.byref(cnt)), ctx.h)
+            res.n = cnt.value
+            n = max(1, res.n)
+            k = len(net.params()) if model.network else 0                 # params(process) = [ρ; λ0; W; θ; vec(A)]
+            res.mean, res.m2 = np.concatenate([np.full(k, r3[1] / n), s / n]), np.concatenate([np.full(k, r3[2] / n), q / n])
+            if diagnostics and res.n < 1:
+                res.diagnostics = {"summary": {}}               # no kept step: nothing to diagnose
+            elif diagnostics:
+                res.diagnostics = _disc_fetch_diagnostics(process, model, ctx, diagnostics == "full", ess_below, rhat_above)
+            if diagnostics:
+                res.diagnostics.update(n=res.n, batch_len=diag_b, nbatches=res.n // diag_b)
+    finally:
+        model.close()
+    return res
+
+
+def disc_mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, ctx=None, device_draws=True, keep_samples=True,
+               moments=False, burn=0, diagnostics=False, batch_len=None, ess_below=100.0, rhat_above=1.01):
     """mcmc!(process::DiscreteHawkesProcess, data) -- src/inference.jl:49-70: convolve once, then
-    resample!(process, data, convolved) per step."""
+    resample!(process, data, convolved) per step.
+
+    By default every step takes the process's arrays to the device and back and `res.samples` holds params(process) of every
+    step.  `moments=True` or `keep_samples=False` keeps the chain's state on the device instead (nhp_disc_model,
+    csrc/disc_chain.hip: the same kernels on the same bits, so λ0, W, θ and A are those of the default route step for step;
+    the network's ρ is drawn on the device, as the continuous chain draws it).  With keep_samples=True the state comes back
+    once per step and nothing is uploaded; with keep_samples=False the whole chain runs inside the library
+    (nhp_disc_mcmc_run, cut at `log_freq` only when `verbose`) and res.samples holds the final params(process) alone.
+    Either way the process holds the final state afterwards.
+
+    `moments`, `burn`, `diagnostics`, `batch_len`, `ess_below`, `rhat_above` are those of the continuous mcmc_
+    (inference.mcmc_): res.mean and res.m2 over the steps >= burn in params(process) order, res.diagnostics with `n`,
+    `batch_len`, `nbatches` and `summary` per group -- "baseline", "weights∘impulses" for a standard process, and
+    "weights", "impulses.θ", "adjacency", "network.ρ" (a BernoulliNetworkModel's) for a network process -- and with
+    diagnostics="full" `ess`, `mcse`, `rhat` per entry.  Definitions: include/nhp.h.
+
+    The device-resident route needs a homogeneous baseline, a DenseWeightModel, device_draws=True and a DenseNetworkModel or
+    BernoulliNetworkModel: anything else is NotImplementedError (the default route takes it)."""
     import time
     from .inference import MarkovChainMonteCarlo
+    if diagnostics not in (False, True, "full"):
+        raise ValueError('diagnostics must be False, True or "full"')
+    if diagnostics and not moments:
+        raise ValueError("diagnostics need the device-side running sums (moments=True)")
+    if batch_len is not None and int(batch_len) < 1:
+        raise ValueError("batch_len must be a positive integer")
+    if moments or not keep_samples:
+        _check_resident(process, device_draws)
+        return _disc_mcmc_resident(process, data, nsteps, log_freq, verbose, seed, ctx, keep_samples, moments, burn, diagnostics,
+                                   batch_len, ess_below, rhat_above)
     ctx = ctx or _lib.default_context()
     ds = convolve(process, data, ctx)
     rng = np.random.default_rng(seed)

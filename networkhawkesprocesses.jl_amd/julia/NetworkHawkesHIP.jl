@@ -1225,9 +1225,105 @@ function resample!(p::NHP.DiscreteHawkesProcess, data, c::Convolved; seed::UInt6
     NHP.params(p)
 end
 
+# --- the discrete chain on the device (nhp_disc_model, csrc/disc_chain.hip) ---------------------------------------------
+# λ0 | W | θ | A in one device block, the Gibbs step and the adjacency sweep in place (the bits of resample! above), ρ drawn
+# on the device; running sums and convergence diagnostics as for the continuous chain.  Returns res, or (res, (sum, sumsq,
+# count, rho)) with moments, or (res, mom, (summary, batch_len)) with diagnostics: sums in params(p) order without ρ
+# ([λ0; vec(W); vec(θ); vec(A)], or [λ0; vec(W .* θ)] for a standard process), summary the 9 x 6 matrix of
+# nhp_disc_model_diagnostics_fetch -- fields x groups (λ0, θ | W∘θ, -, W, vec(A), ρ), include/nhp.h.
+function resident_mcmc!(p::NHP.DiscreteHawkesProcess, convolved::Convolved, ctx; nsteps, log_freq, verbose, seed, keep_samples, moments,
+                        burn, diagnostics, batch_len, ess_below, rhat_above)
+    p.baseline isa NHP.DiscreteHomogeneousProcess || error("the device-resident discrete chain draws a homogeneous baseline; the default route (keep_samples=true, moments=false) takes an LGCP baseline")
+    p.weights isa NHP.SparseWeightModel && error("the device-resident discrete chain is built for DenseWeightModel; the default route takes a SparseWeightModel")
+    network = p isa NHP.DiscreteNetworkHawkesProcess
+    bern = network && p.network isa NHP.BernoulliNetworkModel
+    network && !bern && !(p.network isa NHP.DenseNetworkModel) &&
+        error("the device-resident discrete chain holds a DenseNetworkModel or a BernoulliNetworkModel; the default route takes $(typeof(p.network))")
+    N, B = NHP.ndims(p), size(p.impulses.θ, 3)
+    b, w, imp = p.baseline, p.weights, p.impulses
+    na, nb = bern ? (Float64(p.network.α), Float64(p.network.β)) : (0.0, 0.0)      # 0, 0: ρ held at 1 (DenseNetworkModel)
+    res = NHP.MarkovChainMonteCarlo(p)
+    mom = nothing
+    diag = nothing
+    start_time = time()
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:nhp_disc_model_create, libnhp), Int32, (Ptr{Cvoid}, Int32, Int32, Int32, Float64, Ref{Ptr{Cvoid}}),
+                ctx.h, Int32(N), Int32(B), Int32(network), Float64(p.dt), h), ctx.h)
+    m = h[]
+    pull = function ()
+        l0, W, θ, A = lowered(p)
+        GC.@preserve A check(ccall((:nhp_disc_model_get, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                   ctx.h, m, l0, W, θ, aptr(A)), ctx.h)
+        b.λ, w.W, imp.θ = l0, W, θ
+        rho = zeros(3)
+        if network
+            p.adjacency_matrix = A
+            if bern
+                check(ccall((:nhp_disc_model_get_rho, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}), ctx.h, m, rho), ctx.h)
+                p.network.ρ = rho[1]
+            end
+        end
+        rho
+    end
+    try
+        l0, W, θ, A = lowered(p)
+        GC.@preserve A check(ccall((:nhp_disc_model_set, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                   ctx.h, m, l0, W, θ, aptr(A)), ctx.h)
+        network && check(ccall((:nhp_disc_model_set_rho, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Float64), ctx.h, m, bern ? Float64(p.network.ρ) : 1.0), ctx.h)
+        diagnostics && check(ccall((:nhp_disc_model_diagnostics_configure, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64), ctx.h, m,
+                                   Int64(batch_len), Int64(max(0, nsteps - burn))), ctx.h)
+        moments && check(ccall((:nhp_disc_model_moments_reset, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), ctx.h, m), ctx.h)
+        while res.steps < nsteps
+            n = keep_samples ? 1 : min(nsteps - res.steps, verbose ? log_freq : nsteps)
+            check(ccall((:nhp_disc_mcmc_run, libnhp), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Float64, Float64, Float64, Float64, Float64, UInt64, UInt64, Int64, Int64),
+                        ctx.h, convolved.h, m, b.α0, b.β0, w.κ, w.ν, imp.γ, na, nb, seed, UInt64(res.steps), n, moments ? Int64(burn) : Int64(-1)), ctx.h)
+            res.steps += n
+            if keep_samples
+                pull()
+                push!(res.samples, NHP.params(p))
+            end
+            if res.steps % log_freq == 0 && verbose
+                res.elapsed = time() - start_time
+                println(" > step: $(res.steps), elapsed: $(res.elapsed)")
+            end
+        end
+        rho = pull()
+        keep_samples || push!(res.samples, NHP.params(p))
+        if moments
+            len = N + N * N * B + (network ? 2 * N * N : 0)
+            s, q, cnt = Vector{Float64}(undef, len), Vector{Float64}(undef, len), Ref{Int64}(0)
+            check(ccall((:nhp_disc_model_moments_fetch, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ref{Int64}),
+                        ctx.h, m, s, q, len, cnt), ctx.h)
+            mom = (s, q, cnt[], rho)
+            if diagnostics && cnt[] >= 1
+                summary = Matrix{Float64}(undef, 9, 6)
+                check(ccall((:nhp_disc_model_diagnostics_fetch, libnhp), Int32,
+                            (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64),
+                            ctx.h, m, Float64(ess_below), Float64(rhat_above), summary, C_NULL, C_NULL, C_NULL, len), ctx.h)
+                diag = (summary, Int(batch_len))
+            end
+        end
+    finally
+        ccall((:nhp_disc_model_destroy, libnhp), Cvoid, (Ptr{Cvoid},), m)
+    end
+    res.elapsed = time() - start_time
+    return diagnostics ? (res, mom, diag) : moments ? (res, mom) : res
+end
+
 # --- mcmc!(process::DiscreteHawkesProcess, data; nsteps=1000, log_freq=100, verbose=false)  src/inference.jl:49-70 ----
+# keep_samples=false or moments=true: the chain's state stays on the device (resident_mcmc! above); otherwise every step goes
+# through the host arrays, as before.
 function mcmc!(p::NHP.DiscreteHawkesProcess, data::Matrix{Int64}; nsteps=1000, log_freq=100, verbose=false, seed::UInt64=UInt64(0),
-               ctx=context())
+               ctx=context(), keep_samples=true, moments=false, burn::Integer=0, diagnostics=false,
+               batch_len::Integer=max(1, isqrt(max(0, nsteps - burn))), ess_below=100.0, rhat_above=1.01)
+    diagnostics && !moments && throw(ArgumentError("diagnostics need the device-side running sums (moments=true)"))
+    batch_len >= 1 || throw(ArgumentError("batch_len must be a positive integer"))
+    if moments || !keep_samples
+        return resident_mcmc!(p, convolve(p, data; ctx=ctx), ctx; nsteps=nsteps, log_freq=log_freq, verbose=verbose, seed=seed,
+                              keep_samples=keep_samples, moments=moments, burn=burn, diagnostics=diagnostics, batch_len=batch_len,
+                              ess_below=ess_below, rhat_above=rhat_above)
+    end
     res = NHP.MarkovChainMonteCarlo(p)
     start_time = time()
     convolved = convolve(p, data; ctx=ctx)

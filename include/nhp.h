@@ -607,6 +607,44 @@ nhp_status nhp_disc_mcmc_run(nhp_ctx *ctx, const nhp_disc_dataset *ds, nhp_disc_
                              double kappa, double nu, double gamma0, double net_alpha, double net_beta, uint64_t seed,
                              uint64_t step0, int64_t n_steps, int64_t burn);
 
+/* ---- scoring a discrete chain: held-out predictive log-likelihood and WAIC (csrc/disc_score.hip) -------------
+ * Cell (t, c) of the count matrix is Poisson(λ[t,c]) given the past (nhp_disc_loglik), so with ℓ_i(θ) = log p(s_i | θ) over the
+ * cells i of bins [t0, t1), all nodes, and S kept draws θ_1 … θ_S:
+ *   lppd_i = log mean_s exp ℓ_i(θ_s),  p_i = the sample variance of ℓ_i(θ_s) (denominator S − 1),  elpd_i = lppd_i − p_i,
+ *   joint  = log mean_s exp Σ_i ℓ_i(θ_s): the predictive log-likelihood of the bins as a whole (held-out bins: the metric).
+ * A scorer keeps, per cell, a running log-sum-exp and Welford's mean and M2 of ℓ_i, and the same three scalars for Σ_i ℓ_i:
+ * 24·R·N bytes for R = t1 − t0 (t fastest), plus 8·R·N of context scratch for λ while a draw is scored.
+ * _create: `ds` must be convolved (NHP_EINVAL) and outlive the scorer; 0 <= t0 < t1 <= T (NHP_EINVAL); a dataset with an LGCP
+ *   baseline is NHP_ENOTIMPL, and so is N > 65535 (the pass takes one grid row per node column); NHP_ENOMEM leaves nothing
+ *   allocated.
+ * _accumulate: the model's current state as one draw -- the bump table from its block, λ for rows [t0, t1) alone with the
+ *   fp64 GEMM of nhp_disc_intensity, one pass over the cells (ℓ in the arithmetic of nhp_disc_loglik), one fold of the
+ *   workgroup partials.  Asynchronous on the main stream, no host read; no atomics and every sum in one fixed order, so two
+ *   runs give the same bits.  A model whose N or B differs from the dataset's is NHP_EINVAL.
+ * _reset: forget the draws.  _fetch (synchronous): NHP_EINVAL ("nothing accumulated") with S = 0;
+ *   summary[10] = {S, cells = R·N, lppd = Σ lppd_i, p_waic = Σ p_i, elpd_waic = Σ elpd_i, waic = −2·elpd_waic,
+ *                  se_elpd = sqrt(cells · var_i elpd_i) (sample variance over the cells, two passes),
+ *                  joint_lpd, joint_mean = mean_s Σ_i ℓ_i(θ_s), joint_sd = its sample standard deviation};
+ *   per_node[3N] = lppd, p_waic, elpd_waic per node column; pointwise[R·N] (nullable, index r + R·c) = elpd_i.
+ *   With S = 1, p_i and everything built on it (and joint_sd) are NaN: undefined, as in the diagnostics.
+ * _fetch_planes (synchronous): the running planes themselves, each nullable, [R·N] at index r + R·c -- lse_i, mean_i and M2_i
+ *   of ℓ_i WITHOUT its loggamma(s_i + 1) (the same constant in lse_i and mean_i, absent from M2_i), so that lse_i − log S >=
+ *   mean_i and M2_i >= 0 can be checked on what the device holds; NHP_EINVAL with S = 0.
+ * nhp_disc_model_attach_score: at most two scorers per model (a third is NHP_EINVAL; not owned: detach or destroy the model
+ *   first).  nhp_disc_mcmc_run then calls _accumulate for each on every kept step whose kept index -- counted per scorer
+ *   from the attach on, across calls -- is a multiple of `every` (>= 1, else NHP_EINVAL).  Kept steps are those from `burn`
+ *   on; with the moments off (burn < 0) those from −(burn + 1) on, so −1 keeps every step.  score = NULL detaches all.
+ *   With nothing attached nhp_disc_mcmc_run launches exactly what it launched before. */
+typedef struct nhp_disc_score nhp_disc_score;
+nhp_status nhp_disc_score_create(nhp_ctx *ctx, const nhp_disc_dataset *ds, int64_t t0, int64_t t1, nhp_disc_score **out);
+void nhp_disc_score_destroy(nhp_disc_score *score);
+nhp_status nhp_disc_score_reset(nhp_ctx *ctx, nhp_disc_score *score);
+nhp_status nhp_disc_score_accumulate(nhp_ctx *ctx, nhp_disc_score *score, const nhp_disc_model *model);
+nhp_status nhp_disc_score_fetch(nhp_ctx *ctx, const nhp_disc_score *score, double *summary /* [10] */, double *per_node /* [3N] */,
+                                double *pointwise /* [R*N] or NULL */);
+nhp_status nhp_disc_score_fetch_planes(nhp_ctx *ctx, const nhp_disc_score *score, double *lse, double *mean, double *m2);
+nhp_status nhp_disc_model_attach_score(nhp_ctx *ctx, nhp_disc_model *model, nhp_disc_score *score, int64_t every);
+
 /* DiscreteLogGaussianCoxProcess(x, λ, Σ, m, dt) as this dataset's baseline (src/baselines.jl:461-509): lam
  * [grid_n * N] (λ[:, n] at n*grid_n) on grid_x [grid_n].  The per-bin baseline intensity(p, 1:T)
  * (src/discrete.jl:117, src/baselines.jl:531-537) is built on the device and kept with the dataset; the other

@@ -995,6 +995,20 @@ nhp_status nhp_disc_launch_intensity(nhp_ctx *ctx, const nhp_disc_dataset *ds, c
     return NHP_OK;
 }
 
+// rows [t0, t0 + R) of the same product: the A operand starts t0 rows down its columns (lda stays T), the output is R x N
+nhp_status nhp_disc_launch_intensity_rows(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *E, const double *base, int64_t t0,
+                                          int64_t R, double *dlam)
+{
+    if (t0 < 0 || R < 1 || t0 + R > ds->T) { nhp_set_error(ctx, "intensity rows [%lld, %lld) outside the dataset", (long long)t0, (long long)(t0 + R)); return NHP_EINVAL; }
+    gemm_args g{};
+    g.A = ds->d_conv + t0; g.lda = (size_t)ds->T; g.B = E; g.ldb = (size_t)ds->N * ds->B;
+    g.M = (int)R; g.N = ds->N; g.K = ds->N * ds->B; g.k_chunk = g.K;
+    g.base = base; g.baseT = nullptr; g.out = dlam;
+    launch_gemm<true, EPI_INTENSITY>(g, 1, ctx->main(), gemm1_tile_m(g.M, g.N, ctx->cu_count));
+    NHP_HIP(ctx, hipGetLastError());
+    return NHP_OK;
+}
+
 extern "C" nhp_status nhp_disc_intensity(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *lambda0,
                                          const double *W, const double *theta, const double *A, double dt,
                                          double *lam)

@@ -337,11 +337,23 @@ extern "C" nhp_status nhp_disc_mcmc_run(nhp_ctx *ctx, const nhp_disc_dataset *ds
     if (n_steps < 0) return NHP_EINVAL;
     NHP_TRY(disc_pair_check(ctx, ds, m));
     if (m->has_A && !m->rho_set) { nhp_set_error(ctx, "mcmc_run: set the network's link probability first (nhp_disc_model_set_rho)"); return NHP_EINVAL; }
+    // attached scorers (nhp_disc_model_attach_score) see the kept steps: those the moments take, or with the moments off
+    // (burn < 0) the steps from −(burn + 1) on.  Their scratch is reserved here, so that no step grows it under work in flight.
+    const bool scoring = m->score[0] || m->score[1];
+    const int64_t score_from = burn >= 0 ? burn : -(burn + 1);
+    for (int j = 0; j < 2; ++j)
+        if (m->score[j]) NHP_TRY(nhp_disc_score_reserve(ctx, m->score[j]));
     for (int64_t k = 0; k < n_steps; ++k) {
         const uint64_t step = step0 + (uint64_t)k;
         NHP_TRY(nhp_disc_model_gibbs_step(ctx, ds, m, alpha0, beta0, kappa, nu, gamma0, seed, step));
         if (m->has_A) NHP_TRY(nhp_disc_model_network_step(ctx, ds, m, net_alpha, net_beta, seed, step));
         if (burn >= 0 && (int64_t)step >= burn) NHP_TRY(nhp_disc_model_moments_accumulate(ctx, m));
+        if (scoring && (int64_t)step >= score_from)
+            for (int j = 0; j < 2; ++j) {
+                if (!m->score[j]) continue;
+                if (m->score_kept[j] % m->score_every[j] == 0) NHP_TRY(nhp_disc_score_accumulate(ctx, m->score[j], m));
+                ++m->score_kept[j];
+            }
     }
     return nhp_ctx_synchronize(ctx);
 }

@@ -468,7 +468,13 @@ struct nhp_disc_model {
     double *d_mom = nullptr;
     int64_t mom_len = 0, mom_count = 0;
     struct nhp_diag_state *diag = nullptr;              // nhp_diag.h; null: not configured
+    // scorers attached for nhp_disc_mcmc_run (nhp_disc_model_attach_score; not owned): slot k scores every score_every[k]-th
+    // kept step, score_kept[k] counts the kept steps since the attach (so a chain cut into calls keeps its rhythm)
+    struct nhp_disc_score *score[2] = {nullptr, nullptr};
+    int64_t score_every[2] = {1, 1}, score_kept[2] = {0, 0};
 };
+// disc_score.hip: grow the context's scratch to what nhp_disc_score_accumulate(score, model) stages, ahead of a loop
+nhp_status nhp_disc_score_reserve(nhp_ctx *ctx, const struct nhp_disc_score *score);
 // disc_gibbs.hip: the two halves of a chain step on device-resident state, asynchronous on the main stream.  The Gibbs half
 // reads and overwrites λ0, W, θ (the bits of nhp_disc_gibbs_step); the sweep overwrites A (the bits of
 // nhp_disc_resample_adjacency with the scalar *d_rho and Philox uniforms), `links` = ΣA of the A it starts from.
@@ -480,6 +486,9 @@ nhp_status nhp_disc_adjacency_enqueue(nhp_ctx *ctx, const nhp_disc_dataset *ds, 
                                       size_t links);
 nhp_status nhp_disc_launch_intensity(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *E, const double *base,
                                      bool per_bin_baseline, double *dlam);
+// the same GEMM on rows [t0, t0 + R) of Ŝ alone, homogeneous baseline: λ[t0 + r, c] lands at dlam[r + R·c] (disc_score.hip)
+nhp_status nhp_disc_launch_intensity_rows(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *E, const double *base, int64_t t0,
+                                          int64_t R, double *dlam);
 // disc.hip launches re-driven by disc_information.hip: the log-likelihood of a staged bump table (-> ctx->d_results[0], the
 // bits of nhp_disc_loglik), and the gradient's split-T Gᵀ·R (R [T x N], t fastest) into `splits` slabs of N·B x N
 nhp_status nhp_disc_launch_loglik(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *E, const double *base);

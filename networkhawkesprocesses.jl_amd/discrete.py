@@ -1143,8 +1143,208 @@ def _disc_fetch_diagnostics(process, model, ctx, full, ess_below, rhat_above):
     return out
 
 
+# ---- scoring a chain: held-out predictive log-likelihood and WAIC (csrc/disc_score.hip) ---------------------------------------
+SCORE_FIELDS = ("n", "cells", "lppd", "p_waic", "elpd_waic", "waic", "se_elpd", "joint_lpd", "joint_mean", "joint_sd")
+
+
+class DiscreteScore:
+    """What nhp_disc_score_fetch returns for the cells of bins [t0, t1), all nodes, over `n` kept draws (definitions:
+    include/nhp.h).  `lppd`, `p_waic`, `elpd_waic`, `waic` = −2·elpd_waic and `se_elpd` are the pointwise scores summed over
+    the cells; `joint_lpd` = log mean_s p(all scored cells | θ_s) is the predictive log-likelihood of the bins as a whole (the
+    number to report for held-out bins), `joint_mean` and `joint_sd` the mean and spread of the draws' log-likelihoods.
+    `per_node` is a 3 x N array (lppd, p_waic, elpd_waic per node), `pointwise` -- when asked for -- the R x N array of
+    elpd_i that compare_scores needs."""
+
+    def __init__(self, summary, per_node, pointwise, bins):
+        for name, v in zip(SCORE_FIELDS, summary):
+            setattr(self, name, int(v) if name in ("n", "cells") else float(v))
+        self.per_node, self.pointwise, self.bins = per_node, pointwise, (int(bins[0]), int(bins[1]))
+
+    def __repr__(self):
+        return (f"DiscreteScore(bins={self.bins}, n={self.n}, waic={self.waic:.6g}, elpd_waic={self.elpd_waic:.6g} ± {self.se_elpd:.3g}, "
+                f"p_waic={self.p_waic:.4g}, joint_lpd={self.joint_lpd:.6g})")
+
+
+class ScoreComparison:
+    """compare_scores(a, b): elpd_diff = Σ_i (elpd_a,i − elpd_b,i) (positive: a predicts better) and its standard error."""
+
+    def __init__(self, elpd_diff, se_diff, cells):
+        self.elpd_diff, self.se_diff, self.cells = float(elpd_diff), float(se_diff), int(cells)
+
+    def __repr__(self):
+        return f"ScoreComparison(elpd_diff={self.elpd_diff:.6g} ± {self.se_diff:.3g}, cells={self.cells})"
+
+
+def compare_scores(a, b):
+    """The difference of two models' elpd_waic over the same cells, with the standard error of the paired difference,
+    sqrt(cells · var_i(elpd_a,i − elpd_b,i)) (sample variance): plain numpy on the two `pointwise` arrays."""
+    for s in (a, b):
+        if getattr(s, "pointwise", None) is None:
+            raise ValueError("compare_scores needs scores with pointwise values (pointwise=True)")
+    pa, pb = np.asarray(a.pointwise, dtype=np.float64), np.asarray(b.pointwise, dtype=np.float64)
+    if pa.shape != pb.shape:
+        raise ValueError(f"the scores cover different cells: {pa.shape} and {pb.shape}")
+    if tuple(a.bins) != tuple(b.bins):
+        raise ValueError(f"the scores cover different bins: {tuple(a.bins)} and {tuple(b.bins)}")
+    d = (pa - pb).ravel()
+    se = np.sqrt(d.size * np.var(d, ddof=1)) if d.size > 1 else np.nan
+    return ScoreComparison(d.sum(), se, d.size)
+
+
+class _DeviceScore:
+    """nhp_disc_score handle on a convolved dataset (kept alive with it)."""
+
+    def __init__(self, ctx, ds, bins):
+        self.ctx, self.ds, self.bins = ctx, ds, bins
+        self.h = C.c_void_p()
+        _lib.check(_lib.lib().nhp_disc_score_create(ctx.h, ds.h, int(bins[0]), int(bins[1]), C.byref(self.h)), ctx.h)
+
+    def accumulate(self, model):
+        _lib.check(_lib.lib().nhp_disc_score_accumulate(self.ctx.h, self.h, model.h), self.ctx.h)
+
+    def fetch(self, pointwise=False):
+        N, R = self.ds.N, self.bins[1] - self.bins[0]
+        summary, per_node = np.empty(len(SCORE_FIELDS)), np.empty(3 * N)
+        pw = np.empty(R * N) if pointwise else None
+        _lib.check(_lib.lib().nhp_disc_score_fetch(self.ctx.h, self.h, _lib.dptr(summary), _lib.dptr(per_node), _lib.dptr(pw)), self.ctx.h)
+        return DiscreteScore(summary, per_node.reshape(3, N), pw.reshape((R, N), order="F") if pointwise else None, self.bins)
+
+    def close(self):
+        if getattr(self, "h", None):
+            _lib.lib().nhp_disc_score_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _data_shape(data):
+    if isinstance(data, DiscreteDataset):
+        return data.N, data.T
+    shape = np.shape(data)
+    if len(shape) != 2:
+        raise ValueError("data must be an N x T matrix")
+    return shape
+
+
+def _check_bins(bins, T, what):
+    try:
+        t0, t1 = bins
+        t0, t1 = int(t0), int(t1)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: bins must be a pair (t0, t1)") from None
+    if not 0 <= t0 < t1 <= T:
+        raise ValueError(f"{what}: bins [{t0}, {t1}) must satisfy 0 <= t0 < t1 <= T = {T}")
+    return t0, t1
+
+
+def _score_plan(process, data, waic, heldout, score_every, burn):
+    """The scorers a chain was asked for, as [(name, data or None for the chain's own, (t0, t1))]; every argument is checked here,
+    before the library is touched."""
+    if not waic and heldout is None:
+        return []
+    if int(score_every) != score_every or int(score_every) < 1:
+        raise ValueError("score_every must be a positive integer")
+    if int(burn) < 0:
+        raise ValueError("burn must be non-negative when the chain is scored")
+    if not isinstance(process.baseline, DiscreteHomogeneousProcess):
+        raise NotImplementedError(f"scoring a discrete chain needs a homogeneous baseline (baseline: {type(process.baseline).__name__}: "
+                                  f"its draws are not part of the device model)")
+    N, T = _data_shape(data)
+    plan = []
+    if waic:
+        plan.append(("waic", None, (0, int(T))))
+    if heldout is not None:
+        if isinstance(heldout, tuple):
+            if len(heldout) != 2:
+                raise ValueError("heldout must be (data_full, (t0, t1)) or a count matrix")
+            hd, bins = heldout
+        else:
+            hd, bins = heldout, None
+        hN, hT = _data_shape(hd)
+        if hN != N:
+            raise ValueError(f"heldout data has {hN} nodes, the chain's data {N}")
+        plan.append(("heldout", hd, _check_bins(bins if bins is not None else (0, hT), hT, "heldout")))
+    return plan
+
+
+def _open_scorers(ctx, process, ds, plan):
+    out = []
+    for name, data, bins in plan:
+        out.append((name, _DeviceScore(ctx, ds if data is None else convolve(process, data, ctx), bins)))
+    return out
+
+
+def _close_scorers(res, scorers, pointwise):
+    """Fetch every scorer into res.<name> (a chain that kept no step leaves None) and release it."""
+    try:
+        for name, s in scorers:
+            setattr(res, name, None)
+        for name, s in scorers:
+            try:
+                setattr(res, name, s.fetch(pointwise))
+            except _lib.NhpError as e:
+                if "nothing accumulated" not in str(e):
+                    raise
+    finally:
+        for _, s in scorers:
+            s.close()
+
+
+def _sample_arrays(process, x):
+    """(λ0, W, θ, A) that reproduce the intensity of the draw x = params(process).  A network process's sample holds the four
+    arrays themselves.  A standard process's holds η = W∘θ, which is all the intensity depends on: (W, θ) = (1, η) gives the
+    chain's bump table entry (W·θ)·dt bit for bit, where params!'s split W = Σ_b η, θ = η / W multiplies back to a neighbour."""
+    N, B = process.ndims(), process.impulses.nbasis()
+    NN = N * N
+    x = np.asarray(x, dtype=np.float64)
+    if x.shape != (len(process.params()),):
+        raise ValueError("Parameter vector length does not match model parameter length.")
+    if isinstance(process, DiscreteNetworkHawkesProcess):
+        l0, W, th, A = np.split(x[len(x) - (N + 2 * NN + NN * B):], [N, N + NN, N + NN + NN * B])
+        return l0.copy(), W.copy(), th.copy(), A.copy()
+    return x[:N].copy(), np.ones(NN), x[N:].copy(), None
+
+
+def disc_score_samples(process, samples, data, bins=None, burn=0, every=1, pointwise=False, ctx=None):
+    """Score the draws of a finished chain: samples[burn], samples[burn + every], … (each a params(process) vector, as
+    res.samples holds them) on bins [t0, t1) of `data` (all of it by default).  Every draw is set into a device model through
+    params! and accumulated as the chain itself would have (nhp_disc_score_accumulate): for the same draws the result is
+    the in-chain score bit for bit.  The process supplies the shapes, the basis and dt; it is not changed."""
+    if int(every) != every or int(every) < 1:
+        raise ValueError("every must be a positive integer")
+    if int(burn) != burn or int(burn) < 0:
+        raise ValueError("burn must be a non-negative integer")
+    samples = list(samples)
+    if int(burn) >= len(samples):
+        raise ValueError(f"no draws left: {len(samples)} samples, burn = {burn}")
+    if not isinstance(process.baseline, DiscreteHomogeneousProcess):
+        raise NotImplementedError(f"scoring needs a homogeneous baseline (baseline: {type(process.baseline).__name__})")
+    N, T = _data_shape(data)
+    if N != process.ndims():
+        raise ValueError(f"data has {N} nodes, the process {process.ndims()}")
+    bins = _check_bins(bins if bins is not None else (0, T), T, "disc_score_samples")
+    draws = [_sample_arrays(process, x) for x in samples[int(burn)::int(every)]]
+    ctx = ctx or _lib.default_context()
+    ds = data if isinstance(data, DiscreteDataset) and data.B else convolve(process, data, ctx)
+    model, scorer = DiscreteDeviceModel(ctx, process), None
+    try:
+        scorer = _DeviceScore(ctx, ds, bins)
+        for l0, W, th, A in draws:
+            _lib.check(_lib.lib().nhp_disc_model_set(ctx.h, model.h, _lib.dptr(l0), _lib.dptr(W), _lib.dptr(th), _lib.dptr(A)), ctx.h)
+            scorer.accumulate(model)
+        return scorer.fetch(pointwise)
+    finally:
+        if scorer is not None:
+            scorer.close()
+        model.close()
+
+
 def _disc_mcmc_resident(process, data, nsteps, log_freq, verbose, seed, ctx, keep_samples, moments, burn, diagnostics, batch_len,
-                        ess_below, rhat_above):
+                        ess_below, rhat_above, plan=(), score_every=1, pointwise=False):
     """The chain with its state on the device (nhp_disc_model): nothing is uploaded after the start; with keep_samples the
     state comes back once per step, without it the whole chain is nhp_disc_mcmc_run."""
     import math
@@ -1167,7 +1367,14 @@ def _disc_mcmc_resident(process, data, nsteps, log_freq, verbose, seed, ctx, kee
         _lib.check(lib.nhp_disc_model_moments_reset(ctx.h, model.h), ctx.h)
     res = MarkovChainMonteCarlo()
     start = time.time()
+    scorers, kept = [], 0
     try:
+        scorers = _open_scorers(ctx, process, ds, plan)
+        if not keep_samples:
+            for _, s in scorers:                 # nhp_disc_mcmc_run scores the kept steps itself
+                _lib.check(lib.nhp_disc_model_attach_score(ctx.h, model.h, s.h, int(score_every)), ctx.h)
+        # the driver's kept steps without moments: from −(burn + 1) on (include/nhp.h)
+        run_burn = burn if moments else (-1 - int(burn) if scorers else -1)
         while res.steps < nsteps:
             if keep_samples:
                 _lib.check(lib.nhp_disc_model_gibbs_step(ctx.h, ds.h, model.h, *pri, seed, res.steps), ctx.h)
@@ -1175,12 +1382,17 @@ def _disc_mcmc_resident(process, data, nsteps, log_freq, verbose, seed, ctx, kee
                     _lib.check(lib.nhp_disc_model_network_step(ctx.h, ds.h, model.h, net_a, net_b, seed, res.steps), ctx.h)
                 if moments and res.steps >= burn:
                     _lib.check(lib.nhp_disc_model_moments_accumulate(ctx.h, model.h), ctx.h)
+                if scorers and res.steps >= burn:
+                    if kept % int(score_every) == 0:
+                        for _, s in scorers:
+                            s.accumulate(model)
+                    kept += 1
                 model.pull(process)
                 res.samples.append(process.params())
                 n = 1
             else:
                 n = min(nsteps - res.steps, log_freq if verbose else nsteps)
-                _lib.check(lib.nhp_disc_mcmc_run(ctx.h, ds.h, model.h, *pri, net_a, net_b, seed, res.steps, n, burn if moments else -1), ctx.h)
+                _lib.check(lib.nhp_disc_mcmc_run(ctx.h, ds.h, model.h, *pri, net_a, net_b, seed, res.steps, n, run_burn), ctx.h)
             res.steps += n
             if res.steps % log_freq == 0 and verbose:
                 res.elapsed = time.time() - start
@@ -1204,13 +1416,17 @@ def _disc_mcmc_resident(process, data, nsteps, log_freq, verbose, seed, ctx, kee
                 res.diagnostics = _disc_fetch_diagnostics(process, model, ctx, diagnostics == "full", ess_below, rhat_above)
             if diagnostics:
                 res.diagnostics.update(n=res.n, batch_len=diag_b, nbatches=res.n // diag_b)
+        _close_scorers(res, scorers, pointwise)
     finally:
+        for _, s in scorers:
+            s.close()
         model.close()
     return res
 
 
 def disc_mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, ctx=None, device_draws=True, keep_samples=True,
-               moments=False, burn=0, diagnostics=False, batch_len=None, ess_below=100.0, rhat_above=1.01):
+               moments=False, burn=0, diagnostics=False, batch_len=None, ess_below=100.0, rhat_above=1.01, waic=False,
+               heldout=None, score_every=1, pointwise=False):
     """mcmc!(process::DiscreteHawkesProcess, data) -- src/inference.jl:49-70: convolve once, then
     resample!(process, data, convolved) per step.
 
@@ -1229,7 +1445,16 @@ def disc_mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, 
     diagnostics="full" `ess`, `mcse`, `rhat` per entry.  Definitions: include/nhp.h.
 
     The device-resident route needs a homogeneous baseline, a DenseWeightModel, device_draws=True and a DenseNetworkModel or
-    BernoulliNetworkModel: anything else is NotImplementedError (the default route takes it)."""
+    BernoulliNetworkModel: anything else is NotImplementedError (the default route takes it).
+
+    Scoring (csrc/disc_score.hip; definitions in include/nhp.h, results as DiscreteScore): `waic=True` scores the chain's own
+    bins, `heldout=(data_full, (t0, t1))` bins [t0, t1) of another count matrix with the same draws -- fit on
+    data_full[:, :t0] and pass the full matrix, so that the history before t0 stays in the convolution -- or
+    `heldout=data_test` every bin of a matrix of its own.  Every `score_every`-th step from `burn` on is scored, on the
+    device, as the step is kept: nothing is stored per draw.  The results are res.waic and res.heldout (None when no step
+    was kept), with `pointwise=True` including the per-cell elpd that compare_scores takes.  On the resident routes the
+    chain's device model is scored in place; on the default route -- every model it takes -- each scored step's state is set
+    into a device model kept for scoring.  A baseline other than DiscreteHomogeneousProcess is NotImplementedError."""
     import time
     from .inference import MarkovChainMonteCarlo
     if diagnostics not in (False, True, "full"):
@@ -1238,23 +1463,41 @@ def disc_mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, 
         raise ValueError("diagnostics need the device-side running sums (moments=True)")
     if batch_len is not None and int(batch_len) < 1:
         raise ValueError("batch_len must be a positive integer")
+    plan = _score_plan(process, data, waic, heldout, score_every, burn)
     if moments or not keep_samples:
         _check_resident(process, device_draws)
         return _disc_mcmc_resident(process, data, nsteps, log_freq, verbose, seed, ctx, keep_samples, moments, burn, diagnostics,
-                                   batch_len, ess_below, rhat_above)
+                                   batch_len, ess_below, rhat_above, plan, score_every, pointwise)
     ctx = ctx or _lib.default_context()
     ds = convolve(process, data, ctx)
     rng = np.random.default_rng(seed)
     res = MarkovChainMonteCarlo()
     start = time.time()
-    while res.steps < nsteps:
-        res.samples.append(disc_resample_(process, None, ds, rng, seed=seed, step=res.steps, ctx=ctx, device_draws=device_draws))
-        res.steps += 1
-        if res.steps % log_freq == 0 and verbose:
-            res.elapsed = time.time() - start
-            print(f" > step: {res.steps}, elapsed: {res.elapsed}")
-    res.elapsed = time.time() - start
-    res.status = "complete"
+    scorers, smodel, kept = [], None, 0
+    try:
+        if plan:
+            scorers = _open_scorers(ctx, process, ds, plan)
+            smodel = DiscreteDeviceModel(ctx, process)           # holds the scored step's state; the chain does not read it
+        while res.steps < nsteps:
+            res.samples.append(disc_resample_(process, None, ds, rng, seed=seed, step=res.steps, ctx=ctx, device_draws=device_draws))
+            if scorers and res.steps >= burn:
+                if kept % int(score_every) == 0:
+                    smodel.push(process)
+                    for _, s in scorers:
+                        s.accumulate(smodel)
+                kept += 1
+            res.steps += 1
+            if res.steps % log_freq == 0 and verbose:
+                res.elapsed = time.time() - start
+                print(f" > step: {res.steps}, elapsed: {res.elapsed}")
+        res.elapsed = time.time() - start
+        res.status = "complete"
+        _close_scorers(res, scorers, pointwise)
+    finally:
+        for _, s in scorers:
+            s.close()
+        if smodel is not None:
+            smodel.close()
     return res
 
 

@@ -1339,4 +1339,41 @@ function mcmc!(p::NHP.DiscreteHawkesProcess, data::Matrix{Int64}; nsteps=1000, l
     return res
 end
 
+# --- scoring a discrete chain: held-out predictive log-likelihood and WAIC (include/nhp.h: nhp_disc_score_*) ---------------
+# Thin wrappers: a scorer on bins [t0, t1) (0-based, half-open) of a convolved dataset, fed the state of an nhp_disc_model
+# handle `m` draw by draw (score_accumulate!) or attached to it so that nhp_disc_mcmc_run scores the kept steps itself.
+const SCORE_FIELDS = (:n, :cells, :lppd, :p_waic, :elpd_waic, :waic, :se_elpd, :joint_lpd, :joint_mean, :joint_sd)
+
+function score_create(convolved, t0::Integer, t1::Integer; ctx=context())
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:nhp_disc_score_create, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ref{Ptr{Cvoid}}),
+                ctx.h, convolved.h, Int64(t0), Int64(t1), h), ctx.h)
+    return h[]
+end
+score_destroy(score::Ptr{Cvoid}) = ccall((:nhp_disc_score_destroy, libnhp), Cvoid, (Ptr{Cvoid},), score)
+score_reset!(score::Ptr{Cvoid}; ctx=context()) =
+    check(ccall((:nhp_disc_score_reset, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), ctx.h, score), ctx.h)
+score_accumulate!(score::Ptr{Cvoid}, m::Ptr{Cvoid}; ctx=context()) =
+    check(ccall((:nhp_disc_score_accumulate, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx.h, score, m), ctx.h)
+# every >= 1; score = C_NULL detaches every scorer of the model
+score_attach!(m::Ptr{Cvoid}, score::Ptr{Cvoid}, every::Integer=1; ctx=context()) =
+    check(ccall((:nhp_disc_model_attach_score, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64), ctx.h, m, score, Int64(every)), ctx.h)
+
+# -> (summary::NamedTuple over SCORE_FIELDS, per_node 3 x N rows lppd / p_waic / elpd_waic, pointwise R x N or nothing)
+function score_fetch(score::Ptr{Cvoid}, N::Integer, R::Integer; pointwise=false, ctx=context())
+    summary, per_node = Vector{Float64}(undef, 10), Vector{Float64}(undef, 3 * N)
+    pw = pointwise ? Matrix{Float64}(undef, R, N) : nothing
+    check(ccall((:nhp_disc_score_fetch, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                ctx.h, score, summary, per_node, pointwise ? pointer(pw) : Ptr{Float64}(C_NULL)), ctx.h)
+    return NamedTuple{SCORE_FIELDS}(Tuple(summary)), permutedims(reshape(per_node, Int(N), 3)), pw
+end
+
+# the running planes (lse, mean, M2 of ℓ without its loggamma), each R x N
+function score_fetch_planes(score::Ptr{Cvoid}, N::Integer, R::Integer; ctx=context())
+    lse, mean, m2 = (Matrix{Float64}(undef, R, N) for _ in 1:3)
+    check(ccall((:nhp_disc_score_fetch_planes, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                ctx.h, score, lse, mean, m2), ctx.h)
+    return lse, mean, m2
+end
+
 end # module

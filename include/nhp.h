@@ -159,7 +159,10 @@ int64_t nhp_cont_dataset_pairs(const nhp_cont_dataset *ds);
 enum {
     NHP_DS_TIMES = 0, NHP_DS_NODES = 1, NHP_DS_EV = 2, NHP_DS_EV8 = 3, NHP_DS_POFF = 4, NHP_DS_SL_ROW = 5,
     NHP_DS_SL_ITEM0 = 6, NHP_DS_CHILD = 7, NHP_DS_CHILD_W = 8, NHP_DS_WPOS = 9, NHP_DS_BOFF = 10, NHP_DS_ITEMS = 11,
-    NHP_DS_CNT = 12, NHP_DS_PAIR_OFF = 13, NHP_DS_N_ARRAYS = 14
+    NHP_DS_CNT = 12, NHP_DS_PAIR_OFF = 13,
+    NHP_DS_CHILD_CUT = 14,       /* the children with the recursive route's truncated-window starts (nhp_child, bucket order);
+                                  * none before the first evaluation that took the window */
+    NHP_DS_N_ARRAYS = 15
 };
 nhp_status nhp_cont_dataset_export(nhp_ctx *ctx, const nhp_cont_dataset *ds, int32_t which, void *out, int64_t cap_bytes,
                                    int64_t *bytes);
@@ -490,6 +493,16 @@ nhp_status nhp_probe_stream(nhp_ctx *ctx, int32_t mode, int64_t bytes, int32_t b
  * minimiser out): step counts that can be held against another L-BFGS without a likelihood in between */
 nhp_status nhp_probe_lbfgs(nhp_ctx *ctx, int64_t n, const double *h, const double *c, double lower, double upper, double f_abstol,
                            int32_t max_steps, double *x, double *loss, int32_t *steps, int32_t *converged, int32_t *evaluations);
+/* which way an evaluation with NHP_LL_RECURSIVE goes for (dataset, model): decides exactly as the log-likelihood
+ * (recursion_cost 1.0), the gradient (1.2) and the observed information (1e9) decide, caches included, so it may renew the
+ * model's bound and the dataset's window starts.  out = {cut (the model's look-back for this dataset; 0: no usable bound or
+ * not asked for), used (1: the truncated window, 0: the O(M*N) recursion), group (lanes per child of the windowed kernel;
+ * 0 when not used), cut_pairs (pairs inside the windows that NHP_DS_CHILD_CUT holds; 0 before the first)}.  The switch
+ * NHP_REC_WINDOW=0 (read on every call) gives used = 0.  A recursion_cost other than 1.0 asks as the gradient and the
+ * information do: for a model without any excitation (every W = 0, cut = 1e-300) the empty window is exact for the
+ * log-likelihood alone, and they take the recursion.  Synchronous. */
+nhp_status nhp_probe_recursive_window(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *model, double recursion_cost,
+                                      double out[4]);
 
 /* ---- discrete data: N x T counts  src/discrete.jl:18,80 -------------------------------- */
 /* data [N*T], node fastest.  A negative count anywhere in the matrix is refused with NHP_EDOMAIN ("counts must be

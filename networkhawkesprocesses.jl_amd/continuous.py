@@ -135,6 +135,7 @@ DATASET_ARRAYS = {
     "child": (7, _CHILD), "child_w": (8, _CHILD), "wpos": (9, np.dtype(np.int32)), "boff": (10, np.dtype(np.int32)),
     "items": (11, np.dtype([("node", np.int32), ("kbeg", np.int32), ("kend", np.int32), ("first", np.int32)])),
     "cnt": (12, np.dtype(np.float64)), "pair_off": (13, np.dtype(np.int64)),
+    "child_cut": (14, _CHILD),
 }
 # nhp_cont_dataset_scalars, in order (the last three are the bit patterns of doubles)
 DATASET_SCALARS = ("M", "N", "pairs", "group", "n_items", "max_item", "max_window", "n_zero_time", "all_sole", "sl_rows",

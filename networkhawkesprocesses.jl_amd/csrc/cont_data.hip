@@ -452,6 +452,7 @@ extern "C" nhp_status nhp_cont_dataset_export(nhp_ctx *ctx, const nhp_cont_datas
     case NHP_DS_BOFF: src = ds->d_boff; n = sizeof(int32_t) * (N + 1); break;
     case NHP_DS_ITEMS: src = ds->d_items; n = sizeof(nhp_item) * (size_t)ds->n_items; break;
     case NHP_DS_CNT: src = ds->d_cnt; n = sizeof(double) * N; break;
+    case NHP_DS_CHILD_CUT: src = ds->d_child_cut; n = ds->d_child_cut && ds->cut_cached >= 0.0 ? sizeof(nhp_child) * M : 0; break;
     case NHP_DS_PAIR_OFF: src = ds->h_pair_off.data(); n = sizeof(int64_t) * ds->h_pair_off.size(); host = true; break;
     default: nhp_set_error(ctx, "no dataset array %d", which); return NHP_EINVAL;
     }

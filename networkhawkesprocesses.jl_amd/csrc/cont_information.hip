@@ -435,7 +435,7 @@ nhp_status info_prepare(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont
         const nhp_child *cut = nullptr;
         int g = 0;
         if (ds->M > 0) {
-            NHP_TRY(nhp_recursive_window(ctx, ds, m, &cut, &g, 1e9));
+            NHP_TRY(nhp_recursive_window(ctx, ds, m, &cut, &g, 1e9, true));
             if (!cut) {
                 nhp_set_error(ctx, "%s: the recursive objective has no usable truncated window for these parameters "
                                    "(no decay bound, or more than 8192 parents per window); use the windowed form", what);

@@ -254,7 +254,8 @@ __global__ __launch_bounds__(256) void k_rec_windows(const nhp_child *__restrict
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(pairs, mine);
 }
 
-// cut for this model (cached per parameter version); 0 = no usable bound
+// cut for this model (cached per parameter version); 0 = no usable bound, NHP_REC_EMPTY_CUT = nothing to sum at all
+#define NHP_REC_EMPTY_CUT 1e-300
 static nhp_status rec_cut_for(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, double *cut)
 {
     // the bound uses the dataset's slab statistics as well as the parameters: key it on both (a dataset id, not its size --
@@ -286,8 +287,8 @@ static nhp_status rec_cut_for(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nh
             if (geo > 0.0) count = std::min(count, (double)ds->h_slab_max[q] / geo);
         }
         const double mass = count * wmax;
-        c = mass > 0.0 ? (log(mass / lmin) + 60.0 * 0.6931471805599453) / tmin : 1e-300;
-        if (!(c > 0.0)) c = 1e-300;                          // no excitation at all: an empty window is exact
+        c = mass > 0.0 ? (log(mass / lmin) + 60.0 * 0.6931471805599453) / tmin : NHP_REC_EMPTY_CUT;
+        if (!(c > 0.0)) c = NHP_REC_EMPTY_CUT;               // no excitation that λ_i can register: an empty window is exact (for λ_i)
     }
     m->rec_cut = c;
     m->rec_version = m->version;
@@ -301,13 +302,18 @@ static nhp_status nhp_launch_recursive_full(nhp_ctx *ctx, const nhp_cont_dataset
 // *child_cut = the children with truncated-window starts (and *group the lanes-per-child width for them) when the
 // full-history sum may be evaluated through a window for this (data, parameters); nullptr when the recursion must run
 nhp_status nhp_recursive_window(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const nhp_child **child_cut,
-                                int *group, double recursion_cost)
+                                int *group, double recursion_cost, bool derivatives)
 {
     *child_cut = nullptr;
-    static const int mode = getenv("NHP_REC_WINDOW") ? atoi(getenv("NHP_REC_WINDOW")) : 1;     // 0: always the recursion
+    const char *sw = getenv("NHP_REC_WINDOW");             // read per call: the tests and the benchmark switch it
+    const int mode = sw ? atoi(sw) : 1;                     // 0: always the recursion
     if (!mode || ds->M <= 0 || m->impulse_kind != NHP_IMPULSE_EXPONENTIAL) return NHP_OK;
     double cut = 0.0;
     NHP_TRY(rec_cut_for(ctx, ds, m, &cut));
+    // mass = 0 or below 2^-60·λmin (every W = 0, or as good as): λ_i is its baseline and the empty window exact -- but
+    // ∂/∂W[p,c] = -cnt[p] + Σ_i g_i·a·θ·e^{-θΔ} and the second derivatives keep their pair sums at W = 0, and no cut made from W
+    // bounds what a window drops from them
+    if (derivatives && cut == NHP_REC_EMPTY_CUT) return NHP_OK;
     // Which is faster?  Measured on MI355X: the recursion (k_recursive_waves) spends ≈0.6 µs + 1.25 ns·N per child of its
     // column (all N <= 1024 columns run at once, so a launch takes that times the largest column: 1.98 ms at N = 1024,
     // M = 1e6), the windowed kernel evaluates ≈9.5·10¹¹ pair terms/s at long windows (≈5.5·10¹¹ below 128 parents) plus

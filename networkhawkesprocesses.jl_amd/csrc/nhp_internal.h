@@ -574,9 +574,11 @@ bool nhp_cont_slices_keep(nhp_cont_dataset *ds, uint64_t rows, int32_t n_slices,
 // the 8-byte event records' origin and scale from the first and the last time (false: no 8-byte records)
 bool nhp_ev8_params(int32_t N, int64_t M, double e0, double e1, double *t0, double *scale);
 // recursion_cost: what the caller's O(M·N) kernel costs relative to its windowed route, in units of the log-likelihood's
-// ratio (1 for the log-likelihood; the gradient's recursion is 3.5x the log-likelihood's, its windowed route 2.9x)
+// ratio (1 for the log-likelihood; the gradient's recursion is 3.5x the log-likelihood's, its windowed route 2.9x).
+// derivatives: the caller differentiates the sum (gradient, observed information) -- the empty window of a model without any
+// excitation (all W = 0) is exact for the log-likelihood alone, so these callers get the recursion there
 nhp_status nhp_recursive_window(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const nhp_child **child_cut,
-                                int *group, double recursion_cost = 1.0);
+                                int *group, double recursion_cost = 1.0, bool derivatives = false);
 nhp_status nhp_launch_recursive_flags(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int32_t flags, double *d_out);
 nhp_status nhp_launch_event_intensity_as(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const nhp_child *child_w,
                                          int group, int mask_integral, double *d_lambda);

@@ -200,3 +200,22 @@ extern "C" nhp_status nhp_probe_stream(nhp_ctx *ctx, int32_t mode, int64_t bytes
     if (bytes_read) *bytes_read = (int64_t)(waves * rows_per_wave * row_bytes);        // (the request rounded down to whole rows per wave)
     return NHP_OK;
 }
+
+// Which way a recursive evaluation of (dataset, model) goes (include/nhp.h): nhp_recursive_window itself, called as the
+// log-likelihood (1.0), the gradient (1.2) and the observed information (1e9) call it, so the probe renews the same caches.
+extern "C" nhp_status nhp_probe_recursive_window(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, double recursion_cost,
+                                                 double out[4])
+{
+    if (!ctx || !out) return NHP_EINVAL;
+    ctx->join_lanes();
+    NHP_TRY(nhp_check_pair(ctx, ds, m));
+    NHP_HIP(ctx, hipSetDevice(ctx->device));
+    const nhp_child *child_cut = nullptr;
+    int group = 0;
+    NHP_TRY(nhp_recursive_window(ctx, ds, m, &child_cut, &group, recursion_cost, recursion_cost != 1.0));
+    out[0] = m->rec_version == m->version && m->rec_ds == ds->uid ? m->rec_cut : 0.0;
+    out[1] = child_cut ? 1.0 : 0.0;
+    out[2] = child_cut ? (double)group : 0.0;
+    out[3] = ds->d_child_cut ? (double)ds->cut_pairs : 0.0;
+    return NHP_OK;
+}

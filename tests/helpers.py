@@ -43,3 +43,19 @@ def random_case(N, M, T, kind="exponential", dt_max=1.0, network=False, lgcp=Fal
 
 def rel(a, b):
     return abs(a - b) / max(abs(b), 1e-300)
+
+
+def window_routes(nhp, proc, data, costs=(1.0, 1.2, 1e9)):
+    """Which way loglikelihood(proc, data; recursive=true) goes at each recursion_cost (the log-likelihood's, the gradient's,
+    the observed information's): 1 = the truncated window, 0 = the O(M·N) recursion (nhp_probe_recursive_window).  data: a
+    triple or a DeviceDataset."""
+    from nhp_amd import _lib, continuous
+    ctx = data.ctx if isinstance(data, continuous.DeviceDataset) else _lib.default_context()
+    ds = continuous.device_dataset(proc, data, ctx)
+    model = proc.device_model(ctx)
+    used = []
+    for cost in costs:
+        out = np.full(4, np.nan)
+        _lib.check(_lib.lib().nhp_probe_recursive_window(ctx.h, ds.h, model.h, cost, _lib.dptr(out)), ctx.h)
+        used.append(int(out[1]))
+    return used

@@ -23,8 +23,8 @@ equals its parameter-independent term exactly.  The log-likelihood keeps the sui
                             Shape 4x16 (N > 2048) is left out: 8.4e6 entries and as many pair sums do not fit a few seconds.
     C, C-net                the data of test_recursive_through_the_truncated_window_matches_the_recursion (standard and network
                             process: the window's k_grad_init must NOT mask the integral) against the FULL-history
-                            restatement, + the 2⁻⁶⁰ tail.  Which of window and recursion ran cannot be read from outside: θ in
-                            [20, 40] with 10 events per unit time puts the cut near 2 and the window's cost far below the recursion's
+                            restatement, + the 2⁻⁶⁰ tail.  The route is asserted through nhp_probe_recursive_window: θ in [20, 40]
+                            with 10 events per unit time puts the cut near 2 and the window's cost below the recursion's
     G-W, G-D, G-R           a non-uniform grid of 5 points under W-exp (two-pass and slices), D (slices, not direct: the grid block
                             is accumulated) and R-65; events on grid points, in the last cell, at t = x[4] = T
     S                       W-exp (both routes) and R-65 as column shards [0,3) + [3,N) and the single column [2,3): foreign
@@ -54,6 +54,7 @@ import numpy as np
 import pytest
 
 import cont_grad_ref as cr
+from helpers import window_routes
 
 pytestmark = pytest.mark.gpu
 
@@ -211,6 +212,7 @@ def test_full_recursion_every_shape(nhp, route, N):
 def test_recursive_objective_through_its_truncated_window(nhp, route, name):
     case, res = cr.prepared(name)
     route({})
+    assert window_routes(nhp, cr.process_of(nhp, case), (case["times"], case["nodes"], case["T"])) == [1, 1, 1]
     ll, g, sc = gradient(nhp, case, len(res.grad), flags=1)
     tail = cr.window_tail(res, cr.model_of(case), case["times"], case["nodes"], case["T"])
     hold(name, ll, g, res, case["N"], tail=tail)

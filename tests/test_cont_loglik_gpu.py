@@ -10,7 +10,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import random_case, rel
+from helpers import random_case, rel, window_routes
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-11           # observed ~1e-14; contract (BASELINE.json north_star): 1e-6
@@ -199,6 +199,7 @@ def test_recursive_through_the_truncated_window_matches_the_recursion(nhp, orc, 
     proc = (nhp.ContinuousNetworkHawkesProcess(base, imp, w, A, nhp.BernoulliNetworkModel(0.5, N)) if network
             else nhp.ContinuousStandardHawkesProcess(base, imp, w))
     om = orc.ContModel(lam0, W, theta=th, dt_max=0.05, A=A, grid_x=gx)
+    assert window_routes(nhp, proc, (times, nodes, T)) == [1, 1, 1]      # the window, for the log-likelihood and the gradient
     got = nhp.loglikelihood(proc, (times, nodes, T), recursive=True)
     want = orc.loglik_recursive(om, times, nodes, T)
     assert rel(got, want) < 1e-12

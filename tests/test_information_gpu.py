@@ -30,6 +30,7 @@ import pytest
 
 import cont_grad_ref as cr
 import information_ref as ir
+from helpers import window_routes
 
 pytestmark = pytest.mark.gpu
 
@@ -70,6 +71,7 @@ def test_blocks_against_the_reference(nhp, name):
 @pytest.mark.parametrize("name", ["C", "C-net"])
 def test_recursive_objective_through_its_truncated_window(nhp, name):
     case, res = ir.prepared(name)
+    assert window_routes(nhp, ir.process_of(nhp, case), (case["times"], case["nodes"], case["T"])) == [1, 1, 1]
     hold(name, call(nhp, case), case, res, tail=True)
 
 

@@ -8,7 +8,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import rel
+from helpers import rel, window_routes
 from test_shapes_gpu import build
 
 pytestmark = pytest.mark.gpu
@@ -64,7 +64,9 @@ def test_full_recursion_and_lgcp_baseline_on_shards(nhp, orc, monkeypatch):
                                                nhp.DenseWeightModel(rng.uniform(0, 1, (N, N)) / N))
     data = (times, nodes, T)
     shards = shards_of(nhp, proc, data, 3)
-    monkeypatch.setenv("NHP_REC_WINDOW", "0")                      # the O(M·N) recursion itself
+    monkeypatch.setenv("NHP_REC_WINDOW", "0")                      # the O(M·N) recursion itself (the switch is read per call)
+    for where in [data] + [s.local for s in shards]:
+        assert window_routes(nhp, proc, where) == [0, 0, 0]
     for rec in (False, True):
         whole = nhp.loglikelihood(proc, data, recursive=rec)
         assert rel(sum(nhp.loglikelihood(proc, s.local, recursive=rec) for s in shards), whole) < 1e-12

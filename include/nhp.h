@@ -510,12 +510,28 @@ nhp_status nhp_probe_recursive_window(nhp_ctx *ctx, const nhp_cont_dataset *ds, 
 nhp_status nhp_disc_dataset_create(nhp_ctx *ctx, const int64_t *data, int32_t n_nodes, int64_t n_bins,
                                    nhp_disc_dataset **out);
 void nhp_disc_dataset_destroy(nhp_disc_dataset *ds);
+/* Independent trials of one system, stacked along time: trial r holds the bins offsets[r] <= t < offsets[r + 1].  `offsets`
+ * has n_trials + 1 entries, starts at 0, is strictly increasing and ends at the dataset's n_bins; anything else is
+ * NHP_EINVAL with a message that names the offending entry.  nhp_disc_convolve then stops at the boundaries,
+ *     Ŝ[t, n, b] = max(0, Σ_{l = 1 .. min(L, t − offsets[r])} data[n, t − l]·ϕ_b[l]),
+ * the lags in increasing order with a separate multiply and add: a trial's rows are bit for bit the rows of that trial
+ * convolved alone.  Every other call reads Ŝ row by row and takes the dataset as it is; two convolve across time on their
+ * own and answer NHP_ENOTIMPL on a dataset of several trials: nhp_disc_set_lgcp_baseline (the grid is a function of time)
+ * and the streamed mode of nhp_disc_svi_run, nhp_disc_netsvi_run and nhp_disc_sbmsvi_run.  The call drops an existing Ŝ
+ * and its column sums: nhp_disc_convolve must run again.  n_trials = 1 leaves the dataset as if the call had never been
+ * made.  Bin ranges elsewhere (nhp_disc_score_create) stay in stacked bins. */
+nhp_status nhp_disc_dataset_set_trials(nhp_ctx *ctx, nhp_disc_dataset *ds, const int64_t *offsets, int32_t n_trials);
+/* The trials of a dataset: *n_trials (1 for a dataset that was never cut) and, if non-NULL, offsets [*n_trials + 1]. */
+nhp_status nhp_disc_dataset_get_trials(const nhp_disc_dataset *ds, int32_t *n_trials, int64_t *offsets);
 /* basis(impulse)  src/impulses.jl:321-335 -> phi [L*B], lag fastest (host) */
 nhp_status nhp_disc_basis(int32_t n_lags, int32_t n_basis, double dt, double *phi);
 /* convolve(process, data)  src/discrete.jl:146-151; keeps the T x N x B result on the device
  * and copies it to `out` if non-NULL */
 nhp_status nhp_disc_convolve(nhp_ctx *ctx, nhp_disc_dataset *ds, const double *phi, int32_t n_lags,
                              int32_t n_basis, double *out);
+/* The column sums Σ_t Ŝ[t, n, b] that nhp_disc_convolve leaves beside Ŝ (the gradient and the adjacency sweep read them)
+ * -> out [N*B], node fastest.  NHP_EINVAL before the first convolution. */
+nhp_status nhp_disc_dataset_get_convsum(nhp_ctx *ctx, const nhp_disc_dataset *ds, double *out);
 /* intensity(process, convolved)  src/discrete.jl:115-129 -> T x N; A may be NULL */
 nhp_status nhp_disc_intensity(nhp_ctx *ctx, const nhp_disc_dataset *ds, const double *lambda0,
                               const double *W, const double *theta, const double *A, double dt,

@@ -23,7 +23,7 @@ from .discrete import (DiscreteDataset, DiscreteFitTest, DiscreteForecast, Discr
                        DiscreteInformation, DiscreteStandardErrors, disc_hessian_vector_product, disc_observed_information,
                        disc_standard_errors,
                        DiscreteScore, ScoreComparison, compare_scores, disc_score_samples,
-                       resample_parent_counts, svi_, svi_blocks, update_, variational_mean_, vb_)
+                       resample_parent_counts, stack_trials, svi_, svi_blocks, update_, variational_mean_, vb_)
 from . import discrete as _disc
 from .parents import (Cascades, cascades, map_parents, node_counts, parent_counts, resample_parents,  # noqa: F401
                       uniform_stream)

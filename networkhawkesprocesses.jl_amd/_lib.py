@@ -140,6 +140,9 @@ def _declare(lib):
     f("nhp_cont_lgcp_loglik", i32, _vp, _vp, _ip, _dp, i32, _dp, _dp)
     f("nhp_disc_set_lgcp_baseline", i32, _vp, _vp, _dp, i32, _dp, dbl)
     f("nhp_disc_lgcp_loglik", i32, _vp, _vp, _dp, dbl, _dp)
+    f("nhp_disc_dataset_set_trials", i32, _vp, _vp, _ip, i32)
+    f("nhp_disc_dataset_get_trials", i32, _vp, C.POINTER(i32), _ip)
+    f("nhp_disc_dataset_get_convsum", i32, _vp, _vp, _dp)
     f("nhp_disc_loglik_grad", i32, _vp, _vp, _dp, _dp, _dp, dbl, _dp, _dp, i64)
     f("nhp_disc_resample_parents", i32, _vp, _vp, _dp, _dp, _dp, _dp, dbl, u64, u64, _ip)
     f("nhp_disc_gibbs_step", i32, _vp, _vp, _dp, _dp, _dp, _dp, dbl, dbl, dbl, dbl, dbl, dbl, u64, u64)

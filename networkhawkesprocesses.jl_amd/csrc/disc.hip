@@ -615,6 +615,156 @@ __global__ __launch_bounds__(256) void k_disc_convolve_dense(const double *__res
     }
 }
 
+// ---- trials: independent recordings stacked along time (nhp_disc_dataset_set_trials) ----------------------------------
+// Ŝ[t,n,b] = max(0, Σ_{l=1..min(L, t-o_r)} data[n,t-l]·ϕ_b[l]) for a bin t of the trial that starts at o_r: the lags stop
+// at the trial's first bin.  `start` [T] is 1 at the first bin of every trial but the first.  k_disc_convolve with one
+// more bitmap: the ballot loop that marks the nonzero counts also marks the trial starts, and an output bin clears from
+// its count mask every lag that lies before the latest start inside its window -- one clz and one AND per output, one byte
+// read per bin next to the 64·B stored.  The terms that remain are added as k_disc_convolve adds them, so a trial's rows
+// are bit for bit the rows that kernel writes for the trial alone.  A boundary may fall anywhere in the tile and a stored
+// pair (t, t+1) may straddle one: each output of the pair has its own mask.
+__global__ __launch_bounds__(256) void k_disc_convolve_trials(const double *__restrict__ dataT, const uint8_t *__restrict__ data8,
+                                                              const uint8_t *__restrict__ start, int N, int64_t T,
+                                                              const double *__restrict__ phi, int L, int B,
+                                                              double *__restrict__ conv, double *__restrict__ colpart)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double csm[];
+    double *tile = csm;                                  // [CONV_TB + L]: data[n, t0-L .. t0+CONV_TB-1]
+    const int Bp = (B + CONV_CB - 1) / CONV_CB * CONV_CB;
+    double *phiT = csm + CONV_TB + L;                    // [L][Bp]
+    double *red = phiT + (size_t)L * Bp;                 // [4 waves][CONV_CB]
+    const int span = CONV_TB + L, nwords = (span + 63) / 64 + 1;
+    unsigned long long *bits = reinterpret_cast<unsigned long long *>(red + 4 * CONV_CB);   // [nwords] nonzero counts
+    unsigned long long *sbits = bits + nwords;                                              // [nwords] trial starts
+    const int n = blockIdx.y, tid = threadIdx.x;
+    const int64_t t0 = (int64_t)blockIdx.x * CONV_TB;
+    const double *d = dataT + (size_t)n * T;
+    const uint8_t *d8 = data8 ? data8 + (size_t)n * T : nullptr;
+    for (int i = tid; i < nwords * 64; i += 256) {
+        const int64_t tt = t0 - L + i;
+        const bool in = i < span && tt >= 0 && tt < T;
+        const double x = in ? (d8 ? (double)d8[tt] : d[tt]) : 0.0;
+        const bool s = in && start[tt] != 0;
+        if (i < span) tile[i] = x;
+        const unsigned long long bal = __ballot(x != 0.0), sbal = __ballot(s);
+        if ((tid & 63) == 0) { bits[i >> 6] = bal; sbits[i >> 6] = sbal; }
+    }
+    for (int i = tid; i < L * Bp; i += 256) {
+        const int l = i / Bp, b = i % Bp;
+        phiT[i] = b < B ? phi[l + (size_t)b * L] : 0.0;
+    }
+    __syncthreads();
+    const unsigned long long lmask = L >= 64 ? ~0ull : ((1ull << L) - 1ull);
+    const bool pair = (T & 1) == 0;
+    for (int b0 = 0; b0 < B; b0 += CONV_CB) {
+        double cs[CONV_CB];
+#pragma unroll
+        for (int q = 0; q < CONV_CB; ++q) cs[q] = 0.0;
+        for (int pp = 0; pp < CONV_PP; ++pp) {
+            const int o = 2 * (tid + 256 * pp);
+            const int64_t t = t0 + o;
+            if (t >= T) break;
+            double s[2][CONV_CB];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                // bit k of m <-> tile[o + j + k] = data[n, t + j - (L - k)]; bit k of sm <-> bin t + j - (L - 1 - k), the
+                // window one bin later: it ends at the output bin itself, which as a trial's first bin has no lag at all
+                const int pos = o + j, sh = pos & 63, spos = pos + 1, ssh = spos & 63;
+                const unsigned long long lo = bits[pos >> 6], hi = bits[(pos >> 6) + 1];
+                const unsigned long long slo = sbits[spos >> 6], shi = sbits[(spos >> 6) + 1];
+                unsigned long long m = ((lo >> sh) | (sh ? hi << (64 - sh) : 0ull)) & lmask;
+                const unsigned long long sm = ((slo >> ssh) | (ssh ? shi << (64 - ssh) : 0ull)) & lmask;
+                if (sm) {                                // latest start at bit ks: the counts at bits 0..ks lie before it
+                    const int ks = 63 - __builtin_clzll(sm);
+                    m &= ~((2ull << ks) - 1ull);         // (ks = 63: 2 << 63 = 0, the mask is all ones)
+                }
+#pragma unroll
+                for (int q = 0; q < CONV_CB; ++q) s[j][q] = 0.0;
+                while (m) {
+                    const int k = 63 - __builtin_clzll(m);
+                    m &= ~(1ull << k);
+                    const double x = tile[o + j + k];
+                    const double *ph = phiT + (size_t)(L - k - 1) * Bp + b0;
+#pragma unroll
+                    for (int q = 0; q < CONV_CB; ++q) s[j][q] = s[j][q] + x * ph[q];
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < CONV_CB; ++q)
+                if (b0 + q < B) {
+                    double *dst = conv + (size_t)t + (size_t)n * T + (size_t)(b0 + q) * T * N;
+                    const double v0 = s[0][q] > 0.0 ? s[0][q] : 0.0, v1 = (t + 1 < T && s[1][q] > 0.0) ? s[1][q] : 0.0;
+                    cs[q] += v0 + v1;
+                    if (pair) {
+                        nhp_d2 v = {v0, v1};
+                        __builtin_nontemporal_store(v, reinterpret_cast<nhp_d2 *>(dst));
+                    } else {
+                        __builtin_nontemporal_store(v0, dst);
+                        if (t + 1 < T) __builtin_nontemporal_store(v1, dst + 1);
+                    }
+                }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < CONV_CB; ++q) {
+            const double v = nhp_wave_sum(cs[q]);
+            if ((tid & 63) == 0) red[(tid >> 6) * CONV_CB + q] = v;
+        }
+        __syncthreads();
+        if (tid < CONV_CB && b0 + tid < B)
+            colpart[((size_t)blockIdx.x * N + n) * B + b0 + tid] = (red[tid] + red[CONV_CB + tid]) + (red[2 * CONV_CB + tid] + red[3 * CONV_CB + tid]);
+    }
+}
+
+// k_disc_convolve_dense for trials: the lag loop of bin t ends at min(L, t - o_r), found by walking the start flags of the
+// bins t, t-1, ... in LDS (at most L of them, beside the L·B multiply-adds of the loop itself).
+__global__ __launch_bounds__(256) void k_disc_convolve_dense_trials(const double *__restrict__ dataT, const uint8_t *__restrict__ start,
+                                                                    int N, int64_t T, const double *__restrict__ phi, int L, int B,
+                                                                    double *__restrict__ conv)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double csm[];
+    double *tile = csm;                                  // [256 + L]: data[n, t0-L .. t0+255]
+    double *phiT = csm + 256 + L;                        // [L][Bp]
+    const int n = blockIdx.y, tid = threadIdx.x;
+    const int Bp = (B + CONV_CB - 1) / CONV_CB * CONV_CB;
+    uint8_t *flag = reinterpret_cast<uint8_t *>(phiT + (size_t)L * Bp);     // [256 + L]: start[t0-L .. t0+255]
+    const int64_t t0 = (int64_t)blockIdx.x * 256;
+    const double *d = dataT + (size_t)n * T;
+    for (int i = tid; i < 256 + L; i += 256) {
+        const int64_t tt = t0 - L + i;
+        const bool in = tt >= 0 && tt < T;
+        tile[i] = in ? d[tt] : 0.0;
+        flag[i] = in ? start[tt] : (uint8_t)0;
+    }
+    for (int i = tid; i < L * Bp; i += 256) {
+        const int l = i / Bp, b = i % Bp;
+        phiT[i] = b < B ? phi[l + (size_t)b * L] : 0.0;
+    }
+    __syncthreads();
+    const int64_t t = t0 + tid;
+    int lim = L;                                         // min(L, t - o_r): bin t - l is index tid + L - l
+    for (int l = 0; l < L; ++l)
+        if (flag[tid + L - l]) { lim = l; break; }
+    for (int b0 = 0; b0 < B; b0 += CONV_CB) {
+        double s[CONV_CB];
+#pragma unroll
+        for (int q = 0; q < CONV_CB; ++q) s[q] = 0.0;
+        for (int l = 1; l <= lim; ++l) {
+            const double x = tile[tid + L - l];          // data[n, t - l]
+            const double *ph = phiT + (size_t)(l - 1) * Bp + b0;
+#pragma unroll
+            for (int q = 0; q < CONV_CB; ++q) s[q] = s[q] + x * ph[q];
+        }
+        if (t < T) {
+#pragma unroll
+            for (int q = 0; q < CONV_CB; ++q)
+                if (b0 + q < B) conv[(size_t)t + (size_t)n * T + (size_t)(b0 + q) * T * N] = s[q] > 0.0 ? s[q] : 0.0;
+        }
+    }
+}
+
 // E[k + c·K], k = p + b·N:  bump = ((a·)w·θ)·dt   (src/discrete.jl:381-385,511-516);  base[c] = λ0[c]·dt
 __global__ __launch_bounds__(256) void k_disc_bump(int N, int B, double dt, const double *__restrict__ lambda0,
                                                    const double *__restrict__ W, const double *__restrict__ theta,
@@ -869,8 +1019,63 @@ extern "C" void nhp_disc_dataset_destroy(nhp_disc_dataset *ds)
     (void)hipStreamSynchronize(ds->ctx->main());
     (void)hipFree(ds->d_dataT); (void)hipFree(ds->d_data8); (void)hipFree(ds->d_conv); (void)hipFree(ds->d_colsum);
     (void)hipFree(ds->d_occ_t); (void)hipFree(ds->d_occ_c); (void)hipFree(ds->d_occ_s); (void)hipFree(ds->d_occ_off); (void)hipFree(ds->d_occ_pack); (void)hipFree(ds->d_span_t);
-    (void)hipFree(ds->d_convsum); (void)hipFree(ds->d_baseT); (void)hipFree(ds->d_base_counts);
+    (void)hipFree(ds->d_convsum); (void)hipFree(ds->d_baseT); (void)hipFree(ds->d_base_counts); (void)hipFree(ds->d_trial_start);
     delete ds;
+}
+
+// Trials r = 0..R-1 stacked along time: offsets [R + 1] = first bin of each trial, then T.  Drops Ŝ and its column sums
+// (the convolution depends on the boundaries); R = 1 puts the dataset back to one recording.
+extern "C" nhp_status nhp_disc_dataset_set_trials(nhp_ctx *ctx, nhp_disc_dataset *ds, const int64_t *offsets, int32_t n_trials)
+{
+    if (!ctx || !ds || !offsets) return NHP_EINVAL;
+    if (n_trials < 1) { nhp_set_error(ctx, "set_trials: n_trials = %d must be at least 1", n_trials); return NHP_EINVAL; }
+    if (offsets[0] != 0) { nhp_set_error(ctx, "set_trials: offsets[0] = %lld must be 0", (long long)offsets[0]); return NHP_EINVAL; }
+    for (int32_t r = 1; r <= n_trials; ++r)
+        if (offsets[r] <= offsets[r - 1]) {
+            nhp_set_error(ctx, "set_trials: offsets[%d] = %lld is not above offsets[%d] = %lld (a trial holds at least one bin)", r,
+                          (long long)offsets[r], r - 1, (long long)offsets[r - 1]);
+            return NHP_EINVAL;
+        }
+    if (offsets[n_trials] != ds->T) {
+        nhp_set_error(ctx, "set_trials: offsets[%d] = %lld must be the dataset's %lld bins", n_trials, (long long)offsets[n_trials], (long long)ds->T);
+        return NHP_EINVAL;
+    }
+    if (ds->d_baseT && n_trials > 1) {
+        nhp_set_error(ctx, "set_trials: the dataset carries an LGCP baseline, whose grid is a function of time across the trials");
+        return NHP_ENOTIMPL;
+    }
+    NHP_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->main();
+    NHP_HIP(ctx, hipStreamSynchronize(st));
+    uint8_t *d_start = nullptr;
+    if (n_trials > 1) {
+        std::vector<uint8_t> h((size_t)ds->T, 0);
+        for (int32_t r = 1; r < n_trials; ++r) h[(size_t)offsets[r]] = 1;
+        if (hipMalloc((void **)&d_start, (size_t)ds->T) != hipSuccess) { nhp_set_error(ctx, "out of device memory (trial starts)"); return NHP_ENOMEM; }
+        if (hipMemcpy(d_start, h.data(), (size_t)ds->T, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d_start); nhp_set_error(ctx, "set_trials: the upload of the trial starts failed"); return NHP_EHIP;
+        }
+    }
+    (void)hipFree(ds->d_trial_start);
+    ds->d_trial_start = d_start;
+    if (n_trials > 1) ds->trial_off.assign(offsets, offsets + n_trials + 1);
+    else ds->trial_off.clear();
+    (void)hipFree(ds->d_conv); ds->d_conv = nullptr;
+    (void)hipFree(ds->d_convsum); ds->d_convsum = nullptr;
+    ds->B = 0; ds->L = 0;
+    return NHP_OK;
+}
+
+extern "C" nhp_status nhp_disc_dataset_get_trials(const nhp_disc_dataset *ds, int32_t *n_trials, int64_t *offsets)
+{
+    if (!ds || !n_trials) return NHP_EINVAL;
+    const bool one = ds->trial_off.empty();
+    *n_trials = one ? 1 : (int32_t)ds->trial_off.size() - 1;
+    if (offsets) {
+        if (one) { offsets[0] = 0; offsets[1] = ds->T; }
+        else std::copy(ds->trial_off.begin(), ds->trial_off.end(), offsets);
+    }
+    return NHP_OK;
 }
 
 extern "C" nhp_status nhp_disc_convolve(nhp_ctx *ctx, nhp_disc_dataset *ds, const double *phi, int32_t L,
@@ -896,22 +1101,43 @@ extern "C" nhp_status nhp_disc_convolve(nhp_ctx *ctx, nhp_disc_dataset *ds, cons
     const bool sparse = L <= 64 && !getenv("NHP_CONV_DENSE") && (double)ds->nocc < 0.125 * (double)ds->N * (double)ds->T;
     const int tb = sparse ? CONV_TB : 256;
     dim3 grid((unsigned)((ds->T + tb - 1) / tb), (unsigned)ds->N);
-    const size_t lds_conv = 8 * ((size_t)tb + L + (size_t)L * ((B + CONV_CB - 1) / CONV_CB * CONV_CB) + (sparse ? 4 * CONV_CB + (CONV_TB + L + 63) / 64 + 2 : 0));
+    const uint8_t *d_start = ds->d_trial_start;                    // trials: the lags stop at a trial's first bin
+    const size_t lds_conv = 8 * ((size_t)tb + L + (size_t)L * ((B + CONV_CB - 1) / CONV_CB * CONV_CB) +
+                                 (sparse ? 4 * CONV_CB + (d_start ? 2 : 1) * ((CONV_TB + L + 63) / 64 + 2) : (d_start ? (256 + L + 7) / 8 : 0)));
     if (lds_conv > 64 * 1024) { nhp_set_error(ctx, "convolve: nlags * nbasis = %d * %d exceeds the LDS budget", L, B); return NHP_ENOTIMPL; }
     if (ds->d_convsum) { (void)hipFree(ds->d_convsum); ds->d_convsum = nullptr; }
     if (hipMalloc(&ds->d_convsum, 8 * (size_t)ds->N * B) != hipSuccess) { nhp_set_error(ctx, "out of device memory"); return NHP_ENOMEM; }
     if (sparse) {
-        hipLaunchKernelGGL(k_disc_convolve, grid, dim3(256), lds_conv, st, ds->d_dataT, (const uint8_t *)ds->d_data8, ds->N, ds->T, d_phi, L, B, ds->d_conv, d_part);
+        if (d_start) {
+            hipLaunchKernelGGL(k_disc_convolve_trials, grid, dim3(256), lds_conv, st, ds->d_dataT, (const uint8_t *)ds->d_data8, d_start, ds->N, ds->T, d_phi, L, B, ds->d_conv, d_part);
+        } else {
+            hipLaunchKernelGGL(k_disc_convolve, grid, dim3(256), lds_conv, st, ds->d_dataT, (const uint8_t *)ds->d_data8, ds->N, ds->T, d_phi, L, B, ds->d_conv, d_part);
+        }
         NHP_HIP(ctx, hipGetLastError());
         hipLaunchKernelGGL(k_disc_convsum_blocks, dim3((unsigned)(((size_t)ds->N * B + 255) / 256)), dim3(256), 0, st, d_part, (int)grid.x, ds->N, B, ds->d_convsum);
     } else {
-        hipLaunchKernelGGL(k_disc_convolve_dense, grid, dim3(256), lds_conv, st, ds->d_dataT, ds->N, ds->T, d_phi, L, B, ds->d_conv);
+        if (d_start) {
+            hipLaunchKernelGGL(k_disc_convolve_dense_trials, grid, dim3(256), lds_conv, st, ds->d_dataT, d_start, ds->N, ds->T, d_phi, L, B, ds->d_conv);
+        } else {
+            hipLaunchKernelGGL(k_disc_convolve_dense, grid, dim3(256), lds_conv, st, ds->d_dataT, ds->N, ds->T, d_phi, L, B, ds->d_conv);
+        }
         NHP_HIP(ctx, hipGetLastError());
         hipLaunchKernelGGL(k_disc_convsum, dim3((unsigned)((size_t)ds->N * B)), dim3(256), 0, st, ds->d_conv, ds->T, ds->d_convsum);
     }
     NHP_HIP(ctx, hipGetLastError());
     if (out) NHP_HIP(ctx, hipMemcpyAsync(out, ds->d_conv, 8 * TNB, hipMemcpyDeviceToHost, st));
     NHP_HIP(ctx, hipStreamSynchronize(st));
+    return NHP_OK;
+}
+
+// Σ_t Ŝ[t, n, b] as the convolution left it on the device -> out [N*B], node fastest
+extern "C" nhp_status nhp_disc_dataset_get_convsum(nhp_ctx *ctx, const nhp_disc_dataset *ds, double *out)
+{
+    if (!ctx || !ds || !out) return NHP_EINVAL;
+    if (!ds->d_convsum) { nhp_set_error(ctx, "get_convsum: convolve(process, data) must run first"); return NHP_EINVAL; }
+    NHP_HIP(ctx, hipSetDevice(ctx->device));
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
+    NHP_HIP(ctx, hipMemcpy(out, ds->d_convsum, 8 * (size_t)ds->N * ds->B, hipMemcpyDeviceToHost));
     return NHP_OK;
 }
 
@@ -1551,6 +1777,7 @@ extern "C" nhp_status nhp_disc_svi_run(nhp_ctx *ctx, const nhp_disc_dataset *ds,
             if (blocks[k] < 0 || blocks[k] >= nb) { nhp_set_error(ctx, "svi: blocks[%d] = %d is outside [0, %d)", k, blocks[k], nb); return NHP_EINVAL; }
     if (ds->d_baseT) { nhp_set_error(ctx, "svi: defined for DiscreteHomogeneousProcess baselines only"); return NHP_ENOTIMPL; }
     const bool streamed = phi != nullptr;
+    if (streamed && ds->d_trial_start) { nhp_set_error(ctx, "svi: the streamed mode convolves across the boundaries of the dataset's trials; convolve the dataset and use the resident mode"); return NHP_ENOTIMPL; }
     if (streamed && (n_lags < 1 || n_basis < 1)) { nhp_set_error(ctx, "svi: the streamed mode needs n_lags >= 1 and n_basis >= 1"); return NHP_EINVAL; }
     if (!streamed && !ds->d_conv) { nhp_set_error(ctx, "svi: convolve(process, data) must run first, or pass the basis for the streamed mode"); return NHP_EINVAL; }
     const size_t N = (size_t)ds->N, NN = N * N, B = (size_t)(streamed ? n_basis : ds->B), K = N * B, T = (size_t)Tn, L = streamed ? (size_t)n_lags : 0;
@@ -2319,6 +2546,7 @@ static nhp_status netsvi_run_impl(nhp_ctx *ctx, const nhp_disc_dataset *ds, doub
             if (blocks[k] < 0 || blocks[k] >= nb) { nhp_set_error(ctx, "%s: blocks[%d] = %d is outside [0, %d)", what, k, blocks[k], nb); return NHP_EINVAL; }
     if (ds->d_baseT) { nhp_set_error(ctx, "%s: defined for DiscreteHomogeneousProcess baselines only", what); return NHP_ENOTIMPL; }
     const bool streamed = phi != nullptr;
+    if (streamed && ds->d_trial_start) { nhp_set_error(ctx, "%s: the streamed mode convolves across the boundaries of the dataset's trials; convolve the dataset and use the resident mode", what); return NHP_ENOTIMPL; }
     if (streamed && (n_lags < 1 || n_basis < 1)) { nhp_set_error(ctx, "%s: the streamed mode needs n_lags >= 1 and n_basis >= 1", what); return NHP_EINVAL; }
     if (!streamed && !ds->d_conv) { nhp_set_error(ctx, "%s: convolve(process, data) must run first, or pass the basis for the streamed mode", what); return NHP_EINVAL; }
     NHP_TRY(netvb_check(ctx, what, ds, q, dt, streamed ? n_basis : ds->B, n_steps, h));
@@ -2446,6 +2674,7 @@ extern "C" nhp_status nhp_disc_set_lgcp_baseline(nhp_ctx *ctx, nhp_disc_dataset 
                                                  const double *lam, double dt)
 {
     if (!ctx || !ds || !grid_x || !lam || grid_n < 2) return NHP_EINVAL;
+    if (ds->d_trial_start) { nhp_set_error(ctx, "set_lgcp_baseline: the grid is a function of time and the dataset holds several trials"); return NHP_ENOTIMPL; }
     for (int g = 0; g + 1 < grid_n; ++g)
         if (!(grid_x[g + 1] > grid_x[g])) { nhp_set_error(ctx, "grid points must be strictly increasing"); return NHP_EDOMAIN; }
     // the interpolator throws outside [x[1], x[end]] (src/utils/interpolation.jl:27); bins are evaluated at 1..T

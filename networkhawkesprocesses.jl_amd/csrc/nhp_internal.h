@@ -431,6 +431,9 @@ struct nhp_disc_dataset {
     int32_t *d_base_counts = nullptr;                 // [T*N] events attributed to the baseline by the latest parent sweep
     bool base_counts_valid = false;
     std::vector<double> h_grid_x;                     // the LGCP grid [G]
+    // independent trials stacked along time (nhp_disc_dataset_set_trials): the convolution stops at their first bins
+    std::vector<int64_t> trial_off;                   // [R + 1] first bin of each trial, then T; empty while R = 1
+    uint8_t *d_trial_start = nullptr;                 // [T] 1 at the first bin of every trial but the first; null while R = 1
 };
 
 #ifndef NHP_DA_SPAN

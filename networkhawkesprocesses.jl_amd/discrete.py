@@ -71,8 +71,8 @@ class DiscreteHomogeneousProcess(DiscreteBaseline):
         return self.λ[node - 1] * self.dt
 
     def sufficient_statistics(self, data):
-        """src/baselines.jl:421-425 (pinned by test/baselines.jl:77-78)"""
-        data = np.asarray(data)
+        """src/baselines.jl:421-425 (pinned by test/baselines.jl:77-78); a list of trials counts as its stacked matrix"""
+        data = np.asarray(_trials(data))
         return data.sum(axis=1), data.shape[1]
 
     def integrated_intensity(self, *args):
@@ -92,7 +92,7 @@ class DiscreteHomogeneousProcess(DiscreteBaseline):
     def update_(self, data, parents):
         """The reference's argument check (src/baselines.jl:447, test/baselines.jl:88); the update
         itself is fused into the GPU VB step."""
-        data, parents = np.asarray(data), np.asarray(parents)
+        data, parents = np.asarray(_trials(data)), np.asarray(parents)
         if data.shape != (parents.shape[1], parents.shape[0]):
             raise ValueError("update!: data and parent dimensions do not conform")
         N, T = data.shape
@@ -242,11 +242,78 @@ class DiscreteGaussianImpulseResponse(DiscreteImpulseResponse):
         return phi.T.copy()
 
 
+def stack_trials(trials):
+    """Independent trials of one system -- a list or tuple of N x T_r count matrices with the same N -- stacked along time:
+    returns (counts [N, ΣT_r] int64, offsets int64 [R + 1]); trial r holds the stacked bins offsets[r] <= t < offsets[r + 1].
+    Host code only.  ValueError for an empty list, a non-2-D entry, a trial with zero bins or differing N; DomainError for
+    a negative count."""
+    if isinstance(trials, StackedTrials):
+        return trials.counts, trials.offsets
+    if not isinstance(trials, (list, tuple)):
+        raise ValueError("trials must be a list or tuple of N x T count matrices")
+    if len(trials) == 0:
+        raise ValueError("trials is empty: at least one N x T count matrix is needed")
+    mats = []
+    for r, x in enumerate(trials):
+        x = np.asarray(x)
+        if x.ndim != 2:
+            raise ValueError(f"trial {r} is not an N x T matrix (it has {x.ndim} dimensions)")
+        if x.shape[1] < 1:
+            raise ValueError(f"trial {r} holds no bins")
+        if mats and x.shape[0] != mats[0].shape[0]:
+            raise ValueError(f"trial {r} has {x.shape[0]} nodes, trial 0 has {mats[0].shape[0]}")
+        if x.size and x.min() < 0:
+            raise DomainError(f"trial {r}: counts must be non-negative")
+        mats.append(x.astype(np.int64, copy=False))
+    offsets = np.zeros(len(mats) + 1, dtype=np.int64)
+    np.cumsum([m.shape[1] for m in mats], out=offsets[1:])
+    return np.concatenate(mats, axis=1), offsets
+
+
+class StackedTrials:
+    """What a list of trials becomes at the entry of a discrete call: the stacked count matrix and the trial offsets.
+    np.asarray / np.shape of it give the stacked matrix."""
+
+    def __init__(self, counts, offsets):
+        self.counts, self.offsets = counts, offsets
+        self.shape = counts.shape
+
+    def __array__(self, dtype=None, copy=None):
+        return self.counts if dtype is None else self.counts.astype(dtype)
+
+
+def _is_trials(data):
+    """A list or tuple whose first entry is a matrix is a list of trials (a nested list of numbers stays one matrix)."""
+    return isinstance(data, StackedTrials) or (isinstance(data, (list, tuple)) and len(data) > 0 and np.ndim(data[0]) == 2)
+
+
+def _trials(data):
+    """Normalise `data` once at the entry of a call: a list or tuple of trial matrices becomes StackedTrials (every check of
+    stack_trials runs here, before any device work); anything else is returned as it is."""
+    if isinstance(data, (list, tuple)) and _is_trials(data):
+        return StackedTrials(*stack_trials(data))
+    return data
+
+
+def _has_trials(data):
+    return (isinstance(data, StackedTrials) and len(data.offsets) > 2) or (isinstance(data, DiscreteDataset) and data.ntrials > 1)
+
+
 class DiscreteDataset:
     """nhp_disc_dataset handle: the count matrix (uploaded once, transposed on the device) and,
-    after convolve(), the T x N x B basis-filtered counts."""
+    after convolve(), the T x N x B basis-filtered counts.
 
-    def __init__(self, ctx, data):
+    DiscreteDataset(ctx, data, trial_offsets=None): `data` is an N x T matrix, or a list or tuple of N x T_r matrices --
+    independent trials, stacked along time (stack_trials).  `trial_offsets` (int64 [R + 1]: 0, strictly increasing, ending at
+    T) cuts a stacked matrix into trials.  convolve() stops at the trial boundaries; everything downstream works on rows of Ŝ
+    and takes the dataset as it is, with bin ranges in stacked bins (trial_bins)."""
+
+    def __init__(self, ctx, data, trial_offsets=None):
+        data = _trials(data)
+        if isinstance(data, StackedTrials):
+            if trial_offsets is not None:
+                raise ValueError("trial_offsets comes with one stacked matrix, not with a list of trials")
+            data, trial_offsets = data.counts, data.offsets
         data = np.asarray(data)
         if data.ndim != 2:
             raise ValueError("data must be an N x T matrix")
@@ -261,6 +328,41 @@ class DiscreteDataset:
         self.h = h
         self.B = 0
         self._fin = weakref.finalize(self, _lib.lib().nhp_disc_dataset_destroy, h)
+        self.trial_offsets = np.array([0, self.T], dtype=np.int64)
+        if trial_offsets is not None:
+            self.set_trials(trial_offsets)
+
+    def set_trials(self, offsets):
+        """nhp_disc_dataset_set_trials: cut the T bins into trials at `offsets` (R + 1 entries).  An existing convolution is
+        dropped: convolve() must run again."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.ndim != 1 or len(offsets) < 2:
+            raise ValueError("trial offsets must hold R + 1 >= 2 entries")
+        _lib.check(_lib.lib().nhp_disc_dataset_set_trials(self.ctx.h, self.h, _lib.iptr(offsets), len(offsets) - 1), self.ctx.h)
+        self.B = 0
+        n = C.c_int32()
+        _lib.check(_lib.lib().nhp_disc_dataset_get_trials(self.h, C.byref(n), None), self.ctx.h)
+        out = np.empty(n.value + 1, dtype=np.int64)
+        _lib.check(_lib.lib().nhp_disc_dataset_get_trials(self.h, C.byref(n), _lib.iptr(out)), self.ctx.h)
+        self.trial_offsets = out
+
+    def convsum(self):
+        """Σ_t Ŝ[t, n, b] as the convolution left it on the device -> [N, B]."""
+        out = np.empty(self.N * self.B)
+        _lib.check(_lib.lib().nhp_disc_dataset_get_convsum(self.ctx.h, self.h, _lib.dptr(out)), self.ctx.h)
+        return out.reshape((self.N, self.B), order="F")
+
+    @property
+    def ntrials(self):
+        return len(self.trial_offsets) - 1
+
+    def trial_bins(self, r):
+        """(start, stop) of trial r in stacked bins; negative r counts from the last trial."""
+        R = self.ntrials
+        if not -R <= r < R:
+            raise IndexError(f"trial {r} of {R}")
+        r = int(r) % R
+        return int(self.trial_offsets[r]), int(self.trial_offsets[r + 1])
 
 
 class DiscreteHawkesProcess(HawkesProcess):
@@ -333,7 +435,11 @@ class DiscreteNetworkHawkesProcess(DiscreteHawkesProcess):
 
 def convolve(process, data, ctx=None, fetch=False):
     """convolve(process, data) -- src/discrete.jl:146-151.  Returns a DiscreteDataset whose device
-    copy holds Ŝ (T x N x B); with fetch=True also returns the array itself."""
+    copy holds Ŝ (T x N x B); with fetch=True also returns the array itself.  `data` may be a list or tuple of N x T_r
+    matrices, independent trials (or a DiscreteDataset cut into trials): they are stacked along time, T = ΣT_r, and the
+    convolution stops at every trial's first bin -- the rows of a trial are those of the trial convolved alone."""
+    data = _trials(data)
+    _refuse_lgcp_trials(process, data)
     ctx = ctx or _lib.default_context()
     ds = data if isinstance(data, DiscreteDataset) else DiscreteDataset(ctx, data)
     phi = process.impulses.basis()
@@ -347,7 +453,23 @@ def convolve(process, data, ctx=None, fetch=False):
     return ds
 
 
+def _refuse_lgcp_trials(process, data):
+    if _has_trials(data) and isinstance(process.baseline, DiscreteLogGaussianCoxProcess):
+        raise NotImplementedError("a DiscreteLogGaussianCoxProcess baseline is a function of time across the recording and is "
+                                  "not defined for several trials; fit the trials with a DiscreteHomogeneousProcess baseline")
+
+
+def _enter(process, data, convolved=None):
+    """The head of every discrete call that takes `data`: a trial list normalised once, and the one refusal that needs
+    no device -- before a context is opened."""
+    data = _trials(data)
+    _refuse_lgcp_trials(process, convolved if convolved is not None else data)
+    return data
+
+
 def _convolved(process, data, convolved, ctx):
+    if convolved is not None:
+        _refuse_lgcp_trials(process, convolved)
     ds = convolved if convolved is not None else convolve(process, data, ctx)
     if isinstance(process.baseline, DiscreteLogGaussianCoxProcess):
         process.baseline.attach(ds)           # intensity(baseline, 1:T) follows the current grid values
@@ -433,6 +555,9 @@ class DiscreteForecast:
 
 def _history_tail(data, N, L):
     """The last min(L, T0) bins of an N x T0 count matrix as [bins, N] int64, node fastest -> (tail, T0, on_device)."""
+    if _is_trials(data):
+        raise NotImplementedError("disc_forecast continues one recording, not a list of trials: pass the count matrix of the "
+                                  "trial to continue")
     if isinstance(data, DiscreteDataset):
         raise TypeError("disc_forecast: a DiscreteDataset keeps no host copy of its counts; pass the N x T count matrix "
                         "(a numpy array or a device tensor)")
@@ -552,7 +677,9 @@ def disc_residuals(process, data=None, convolved=None, seed=0, nbins=20, *, pit=
     μ = intensity(process, data), and one pass on the GPU makes of every cell its randomized probability integral transform
     pit = F(s-1) + v·p(s), v uniform -- exactly uniform on [0, 1) under the model, whatever the means --, its Pearson residual
     (s-μ)/√μ, and of every node Σμ against Σs, χ² = Σ(s-μ)²/μ, the deviance and the histogram of its pit values over `nbins`
-    equal bins; `cumulative` is the compensator Σ_{t' <= t} μ[t',c].  The T x N intensity never leaves the device.
+    equal bins; `cumulative` is the compensator Σ_{t' <= t} μ[t',c].  The T x N intensity never leaves the device.  For a list
+    of trials every plane is [N, ΣT_r] in stacked bins, and `cumulative` runs on over the stacked bins: it does not restart
+    at a trial's first bin.
 
     Returns DiscreteResiduals; the planes pit, pearson, cumulative are [N, T] or None when not requested (an absent plane is
     not computed).  device=False: numpy arrays; device=True: torch tensors on the context's device.  `data`: the count matrix,
@@ -568,6 +695,7 @@ def disc_residuals(process, data=None, convolved=None, seed=0, nbins=20, *, pit=
     if isinstance(nbins, bool) or not isinstance(nbins, (int, np.integer)) or not 1 <= nbins <= 4096:
         raise ValueError(f"nbins = {nbins} must be an integer in [1, 4096]")
     nbins = int(nbins)
+    data = _enter(process, data, convolved)
     ctx = ctx or _lib.default_context()
     ds = _convolved(process, data, convolved, ctx)
     l0, W, th, A = process._lowered()
@@ -651,6 +779,7 @@ def disc_goodness_of_fit(process, data=None, convolved=None, residuals=None, see
 
 def disc_intensity(process, data=None, convolved=None, ctx=None):
     """intensity(process, convolved) / intensity(process, data) -> T x N -- src/discrete.jl:115-131"""
+    data = _enter(process, data, convolved)
     ctx = ctx or _lib.default_context()
     ds = _convolved(process, data, convolved, ctx)
     l0, W, th, A = process._lowered()
@@ -662,6 +791,7 @@ def disc_intensity(process, data=None, convolved=None, ctx=None):
 
 def disc_loglikelihood(process, data=None, convolved=None, ctx=None):
     """loglikelihood(process, data[, convolved]) -- src/discrete.jl:86-102"""
+    data = _enter(process, data, convolved)
     ctx = ctx or _lib.default_context()
     ds = _convolved(process, data, convolved, ctx)
     l0, W, th, A = process._lowered()
@@ -674,6 +804,7 @@ def disc_loglikelihood(process, data=None, convolved=None, ctx=None):
 def disc_loglikelihood_gradient(process, data=None, convolved=None, ctx=None):
     """(ll, ∂ll/∂[λ0; vec(W .* θ)]) in one GPU call: the analytic gradient of mle!'s objective
     (src/discrete.jl:211-296 uses finite differences of loglikelihood, 2P calls per gradient)."""
+    data = _enter(process, data, convolved)
     ctx = ctx or _lib.default_context()
     ds = _convolved(process, data, convolved, ctx)
     l0, W, th, _ = process._lowered()
@@ -718,6 +849,7 @@ def disc_mle_(process, data, optimizer="L-BFGS-B", verbose=False, f_abstol=1e-6,
     if regularize:
         raise NotImplementedError("logprior(::DiscreteStandardHawkesProcess) reads fields that do not exist "
                                   "(src/discrete.jl:316-322, SURVEY D5)")
+    data = _enter(process, data)
     ctx = ctx or _lib.default_context()
     ds = convolve(process, data, ctx)
     N = process.ndims()
@@ -818,6 +950,7 @@ def disc_observed_information(process, data=None, convolved=None, columns=None, 
     from .inference import _check_columns
     _disc_information_check(process, "disc_observed_information")
     code = _disc_kind(kind)
+    data = _enter(process, data, convolved)
     ctx = ctx or _lib.default_context()
     ds = _convolved(process, data, convolved, ctx)
     N, B = ds.N, ds.B
@@ -855,6 +988,7 @@ def disc_hessian_vector_product(process, data=None, convolved=None, v=None, kind
     code = _disc_kind(kind)
     if v is None:
         raise ValueError("v is required")
+    data = _enter(process, data, convolved)
     ctx = ctx or _lib.default_context()
     ds = _convolved(process, data, convolved, ctx)
     P = ds.N + ds.N * ds.N * ds.B
@@ -955,6 +1089,7 @@ def resample_parent_counts(process, data=None, convolved=None, seed=0, step=0, c
     (src/parents.jl:82-116): column 0 the baseline, column 1 + p·B + b parent node p through basis b
     (0-based p, b) -- the reduction every discrete resample! applies to the T x N x (1+NB) array, which is
     never materialised here.  Draws are keyed (seed, step), reproducible, and equal to the oracle."""
+    data = _enter(process, data, convolved)
     ctx = ctx or _lib.default_context()
     ds = _convolved(process, data, convolved, ctx)
     l0, W, th, A = process._lowered()
@@ -975,6 +1110,7 @@ def disc_resample_adjacency_matrix_(process, data=None, convolved=None, u=None, 
     the adjacency matrix on the GPU.  `u` (N x N, [parent, child]) supplies the Bernoulli uniforms
     explicitly; otherwise Philox keyed (seed, step).  Updates process.adjacency_matrix, returns ΣA."""
     from .components import BernoulliNetworkModel, DenseNetworkModel
+    data = _enter(process, data, convolved)
     ctx = ctx or _lib.default_context()
     ds = _convolved(process, data, convolved, ctx)
     l0, W, th, _ = process._lowered()
@@ -1015,6 +1151,7 @@ def disc_resample_(process, data, convolved, rng, seed=0, step=0, ctx=None, devi
     λ ~ Gamma(α0 + Σ_t parents[t, c, 1], 1 / (β0 + T·dt))  (src/baselines.jl:413-419)."""
     if not isinstance(process.weights, DenseWeightModel):
         raise NotImplementedError("discrete Gibbs is built for DenseWeightModel (SparseWeightModel: SURVEY 2.1)")
+    data = _enter(process, data, convolved)
     ctx = ctx or _lib.default_context()
     ds = _convolved(process, data, convolved, ctx)
     N, B = ds.N, ds.B
@@ -1224,6 +1361,8 @@ class _DeviceScore:
 def _data_shape(data):
     if isinstance(data, DiscreteDataset):
         return data.N, data.T
+    if _is_trials(data):
+        return _trials(data).shape
     shape = np.shape(data)
     if len(shape) != 2:
         raise ValueError("data must be an N x T matrix")
@@ -1258,7 +1397,9 @@ def _score_plan(process, data, waic, heldout, score_every, burn):
     if waic:
         plan.append(("waic", None, (0, int(T))))
     if heldout is not None:
-        if isinstance(heldout, tuple):
+        # (data_full, (t0, t1)) has a pair of bins second; any other tuple of matrices is a tuple of trials
+        with_bins = isinstance(heldout, tuple) and len(heldout) == 2 and np.ndim(heldout[1]) < 2
+        if with_bins or (isinstance(heldout, tuple) and not _is_trials(heldout)):
             if len(heldout) != 2:
                 raise ValueError("heldout must be (data_full, (t0, t1)) or a count matrix")
             hd, bins = heldout
@@ -1323,6 +1464,7 @@ def disc_score_samples(process, samples, data, bins=None, burn=0, every=1, point
         raise ValueError(f"no draws left: {len(samples)} samples, burn = {burn}")
     if not isinstance(process.baseline, DiscreteHomogeneousProcess):
         raise NotImplementedError(f"scoring needs a homogeneous baseline (baseline: {type(process.baseline).__name__})")
+    data = _trials(data)
     N, T = _data_shape(data)
     if N != process.ndims():
         raise ValueError(f"data has {N} nodes, the process {process.ndims()}")
@@ -1454,7 +1596,12 @@ def disc_mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, 
     device, as the step is kept: nothing is stored per draw.  The results are res.waic and res.heldout (None when no step
     was kept), with `pointwise=True` including the per-cell elpd that compare_scores takes.  On the resident routes the
     chain's device model is scored in place; on the default route -- every model it takes -- each scored step's state is set
-    into a device model kept for scoring.  A baseline other than DiscreteHomogeneousProcess is NotImplementedError."""
+    into a device model kept for scoring.  A baseline other than DiscreteHomogeneousProcess is NotImplementedError.
+
+    `data` (and the data of `heldout`) may be a list or tuple of N x T_r matrices, independent trials, or a DiscreteDataset
+    cut into trials: every route runs on the stacked bins, and bin ranges are in stacked bins --
+    heldout=(trials, ds.trial_bins(-1)) holds out the last trial.  A 2-tuple whose second entry is a pair of bins (or None, for
+    all bins) is read as (data, bins); any other tuple of matrices -- one of exactly two trial matrices too -- as trials."""
     import time
     from .inference import MarkovChainMonteCarlo
     if diagnostics not in (False, True, "full"):
@@ -1463,6 +1610,7 @@ def disc_mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, 
         raise ValueError("diagnostics need the device-side running sums (moments=True)")
     if batch_len is not None and int(batch_len) < 1:
         raise ValueError("batch_len must be a positive integer")
+    data = _enter(process, data)
     plan = _score_plan(process, data, waic, heldout, score_every, burn)
     if moments or not keep_samples:
         _check_resident(process, device_draws)
@@ -1619,6 +1767,7 @@ def update_(process, data, convolved, ctx=None, n_steps=1, step0=None):
     taken (network.vb_step, 0 after variational_init_, advanced here), so a loop of one-step calls -- vb_ with its trace --
     keeps the schedule of one call of n steps; step0 overrides the count."""
     kind = _vb_kind(process, "update!")
+    data = _enter(process, data, convolved)
     ctx = ctx or _lib.default_context()
     ds = _convolved(process, data, convolved, ctx)
     if kind == "network":
@@ -1704,6 +1853,11 @@ def svi_(process, data, nsteps=1000, batch_bins=4096, delay=1.0, forgetting=0.6,
     variational_params(process) after each; 0 keeps only the final parameters.  svi_(..., step0=res.step) resumes a run
     exactly.  Returns a VariationalInference whose `step` counts steps (step0 included)."""
     kind = _vb_kind(process, "svi!")
+    data = _trials(data)
+    if streamed and _has_trials(data):
+        raise NotImplementedError("svi!: streamed=True convolves each block on the fly, across the boundaries of the trials; "
+                                  "use the resident mode (streamed=False) for trials")
+    _refuse_lgcp_trials(process, data)
     T = data.T if isinstance(data, DiscreteDataset) else np.asarray(data).shape[1]
     nsteps, batch_bins, step0, trace_every = int(nsteps), int(batch_bins), int(step0), int(trace_every)
     if nsteps < 0 or step0 < 0 or trace_every < 0:
@@ -1779,6 +1933,7 @@ def vb_(process, data, max_steps=1000, Δx_thresh=1e-6, Δq_thresh=1e-2, verbose
     keep_trace=False runs them back to back on the device and records only the final parameters
     (the reference's per-step trace is 2N + N²B + 2N² doubles a step)."""
     _vb_kind(process, "vb!")
+    data = _enter(process, data)
     ctx = ctx or _lib.default_context()
     start = time.time()
     convolved = convolve(process, data, ctx)

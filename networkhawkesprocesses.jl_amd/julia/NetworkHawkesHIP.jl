@@ -833,6 +833,60 @@ function convolve(p::NHP.DiscreteHawkesProcess, data::Matrix{Int64}; fetch=false
     finalizer(x -> ccall((:nhp_disc_dataset_destroy, libnhp), Cvoid, (Ptr{Cvoid},), x.h), c)
 end
 
+# --- independent trials: N x T_r matrices stacked along time, the convolution stops at every trial's first bin --------------
+# stack_trials(trials) -> (counts N x ΣT_r, offsets [R + 1]); convolve(p, trials) -> `Convolved` over the stacked bins.  Every
+# call that takes a `Convolved` works on rows of Ŝ and takes it as it is; the library refuses an LGCP baseline and the
+# streamed svi window on several trials (NHP_ENOTIMPL).
+function stack_trials(trials::AbstractVector{<:AbstractMatrix{<:Integer}})
+    isempty(trials) && throw(ArgumentError("trials is empty: at least one N x T count matrix is needed"))
+    N = size(trials[1], 1)
+    for (r, x) in enumerate(trials)
+        size(x, 1) == N || throw(ArgumentError("trial $r has $(size(x, 1)) nodes, trial 1 has $N"))
+        size(x, 2) >= 1 || throw(ArgumentError("trial $r holds no bins"))
+        any(<(0), x) && throw(DomainError(r, "counts must be non-negative"))
+    end
+    Matrix{Int64}(reduce(hcat, trials)), Int64[0; cumsum(size.(trials, 2))]
+end
+
+function set_trials!(c::Convolved, offsets::Vector{Int64}; ctx=context())
+    check(ccall((:nhp_disc_dataset_set_trials, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Int32), ctx.h, c.h, offsets,
+                length(offsets) - 1), ctx.h)
+    c.B = 0; c.host = nothing                       # Ŝ is dropped: convolve again
+    c
+end
+
+function trial_offsets(c::Convolved)
+    n = Ref{Int32}(0)
+    check(ccall((:nhp_disc_dataset_get_trials, libnhp), Int32, (Ptr{Cvoid}, Ref{Int32}, Ptr{Int64}), c.h, n, Ptr{Int64}(C_NULL)))
+    off = Vector{Int64}(undef, n[] + 1)
+    check(ccall((:nhp_disc_dataset_get_trials, libnhp), Int32, (Ptr{Cvoid}, Ref{Int32}, Ptr{Int64}), c.h, n, off))
+    off
+end
+
+# Σ_t Ŝ[t, n, b] as the convolution left it on the device -> N x B
+function convsum(c::Convolved; ctx=context())
+    out = Matrix{Float64}(undef, c.N, c.B)
+    check(ccall((:nhp_disc_dataset_get_convsum, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}), ctx.h, c.h, out), ctx.h)
+    out
+end
+
+function convolve(p::NHP.DiscreteHawkesProcess, trials::AbstractVector{<:AbstractMatrix{<:Integer}}; fetch=false, ctx=context())
+    data, offsets = stack_trials(trials)
+    N, T = size(data)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:nhp_disc_dataset_create, libnhp), Int32, (Ptr{Cvoid}, Ptr{Int64}, Int32, Int64, Ref{Ptr{Cvoid}}), ctx.h, data, N, T, r), ctx.h)
+    c = Convolved(r[], N, T, 0, data, nothing)
+    finalizer(x -> ccall((:nhp_disc_dataset_destroy, libnhp), Cvoid, (Ptr{Cvoid},), x.h), c)
+    set_trials!(c, offsets; ctx=ctx)
+    phi = basis_matrix(p.impulses)
+    L, B = size(phi)
+    host = fetch ? Array{Float64,3}(undef, T, N, B) : nothing
+    GC.@preserve host check(ccall((:nhp_disc_convolve, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Float64}),
+                ctx.h, c.h, phi, L, B, fetch ? pointer(host) : Ptr{Float64}(C_NULL)), ctx.h)
+    c.B = B; c.host = host
+    c
+end
+
 lowered(p::NHP.DiscreteHawkesProcess) = (Vector{Float64}(p.baseline.λ), Matrix{Float64}(p.weights.W), Array{Float64,3}(p.impulses.θ),
     p isa NHP.DiscreteNetworkHawkesProcess ? Matrix{Float64}(p.adjacency_matrix) : nothing)
 aptr(A) = A === nothing ? Ptr{Float64}(C_NULL) : pointer(A)

@@ -788,8 +788,12 @@ __global__ __launch_bounds__(BLOCK) void k_sampler_slices(nhp_cont_args a, nhp_s
         const size_t k = (size_t)p + (size_t)c * N;
         double wv = a.W[k];
         if (a.A) wv = a.A[k] * wv;
-        if (IMP == NHP_IMPULSE_EXPONENTIAL) col[p] = make_double2(a.p1[k], wv);          // {rate, a·w}: k_sampler<0>'s column
-        else col[p] = make_double2(a.p1[k], __builtin_sqrt(a.p2[k]));
+        if (IMP == NHP_IMPULSE_EXPONENTIAL) {
+            // {rate, a·w}: k_sampler<0>'s column.  The rate is inv(scale) of Exponential(1/θ), as the reference and the oracle
+            // take it: 1/(1/θ) is not θ for about one double in six, and a weight from θ itself then differs in its last bit
+            const double scale = 1.0 / a.p1[k];
+            col[p] = make_double2(1.0 / scale, wv);
+        } else col[p] = make_double2(a.p1[k], __builtin_sqrt(a.p2[k]));
         colw[p] = wv;
     }
     if (tid == 0) { col[N] = make_double2(0.0, 0.0); colw[N] = 0.0; }

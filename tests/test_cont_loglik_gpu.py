@@ -264,13 +264,20 @@ def test_batches_of_eight_share_one_pass(nhp, orc, kind, network, lgcp, N, M, T,
     """nhp_cont_loglik_batch with 19 compatible models: 8 + 8 + 2 + 1 through k_windowed_batch (one lane per (child, model), the
     S columns in LDS, windows staged once per child) -- every value equals the oracle's windowed log-likelihood of its own
     model and the single evaluation's, also with ragged windows (dense second case: windows of ~50 parents, several record
-    chunks per child), through the slices batch (every workgroup shape) and k_windowed_batch alike."""
+    chunks per child), through the slices batch (every workgroup shape) and k_windowed_batch alike.  The N = 9 dataset is built
+    with items of 4096 children and keeps its child slices (with the default items it drops them and the NHP_SETS_CFG loop
+    would run k_windowed_batch again); the N = 70 one has 222 pairs per event, above the 160 a dataset is sliced at, and stays
+    on k_windowed_batch: both assert it from the dataset's scalars."""
     import ctypes as C
     from nhp_amd import _lib
     ctx = nhp.default_context()
     cases = [random_case(N, M, T, kind, 1.0, network=network, lgcp=lgcp, seed=s, nhp=nhp, orc=orc) for s in range(200, 219)]
     data = cases[0]["data"]
-    ds = nhp.device_dataset(cases[0]["proc"], data, ctx)
+    if N == 9:
+        monkeypatch.setenv("NHP_CHUNK", "4096")
+    ds = nhp.continuous.DeviceDataset(ctx, data, N, 1.0)
+    monkeypatch.delenv("NHP_CHUNK", raising=False)
+    assert (ds.scalars()["sl_rows"] > 0) == (N == 9), ds.scalars()
     models = [c["proc"].device_model(ctx) for c in cases]
     n = len(cases)
     arr = (C.c_void_p * n)(*[m.h for m in models])
@@ -278,7 +285,8 @@ def test_batches_of_eight_share_one_pass(nhp, orc, kind, network, lgcp, N, M, T,
     _lib.check(_lib.lib().nhp_cont_loglik_batch(ctx.h, ds.h, arr, n, 0, _lib.dptr(out)), ctx.h)
     want = np.array([orc.loglik_windowed(c["om"], data[0], data[1], data[2]) for c in cases])
     assert np.max(np.abs(out - want) / np.abs(want)) < TOL
-    single = np.array([nhp.loglikelihood(c["proc"], data, recursive=False) for c in cases])
+    single = np.array([nhp.loglikelihood(c["proc"], ds, recursive=False) for c in cases])
+    print(f"batch against single evaluations: {np.max(np.abs(out - single) / np.abs(single)):.2e}")
     assert np.max(np.abs(out - single) / np.abs(single)) < 1e-13
     # exponential models with flat baselines go four (or two) at a time through one pass over the child slices
     # (k_slices_batch); NHP_BATCH_SLICES=0 keeps them on k_windowed_batch: same values, for every workgroup shape
@@ -331,7 +339,11 @@ def test_pair_list_and_packed_records_agree_with_the_exact_records(nhp, orc, net
     """Short-window exponential evaluations run through the cached pair list (k_windowed_pairs: Δt as a 48-bit fraction of
     Δtmax) and, failing that, through the 8-byte event records (k_windowed<.., PACK>); NHP_PLIST=0 / NHP_EV8=0 switch them
     off one after the other.  All three equal the oracle on the ORIGINAL times, for every (lanes per child, children in
-    flight, workgroup size) the pair kernel is built with, with ties (Δt = 0) and ragged windows in the data."""
+    flight, workgroup size) the pair kernel is built with, with ties (Δt = 0) and ragged windows in the data.  The "slices" legs
+    build their dataset with items of 4096 children: with the default items (32 here) the slices are half empty and dropped,
+    and the leg would run the pair list again.  Every leg asserts from the dataset's scalars which layout it ran on."""
+    def sl_rows(proc, d):
+        return nhp.device_dataset(proc, d).scalars()["sl_rows"]
     c = random_case(12, 6000, 500.0, "exponential", 1.0, network=network, lgcp=lgcp, seed=11, nhp=nhp, orc=orc)
     t = c["times"].copy()
     t[1000:1040:2] = t[1001:1041:2]                                  # ties: parents at Δt = 0
@@ -340,29 +352,34 @@ def test_pair_list_and_packed_records_agree_with_the_exact_records(nhp, orc, net
     data = (t, c["nodes"], c["T"])
     want = orc.loglik(c["om"], t, c["nodes"], c["T"], recursive=False)
     got = {}
-    for name, env in (("slices", {}), ("pairs", {"NHP_SLICES": "0"}), ("ev8", {"NHP_PLIST": "0"}),
+    for name, env in (("slices", {"NHP_CHUNK": "4096"}), ("pairs", {"NHP_SLICES": "0"}), ("ev8", {"NHP_PLIST": "0"}),
                       ("exact", {"NHP_PLIST": "0", "NHP_EV8": "0"})):
-        for k in ("NHP_PLIST", "NHP_EV8", "NHP_SLICES"):
+        for k in ("NHP_PLIST", "NHP_EV8", "NHP_SLICES", "NHP_CHUNK"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         nhp.invalidate_device_datasets()
         got[name] = nhp.loglikelihood(c["proc"], data, recursive=False)
         assert rel(got[name], want) < TOL, name
+        assert (sl_rows(c["proc"], data) > 0) == (name == "slices"), name
     assert rel(got["pairs"], got["exact"]) < 1e-13 and rel(got["ev8"], got["exact"]) < 1e-13
     assert rel(got["slices"], got["exact"]) < 1e-12                  # one lane per child: 6-byte records (cont_slices.hip)
     for k in ("NHP_PLIST", "NHP_EV8", "NHP_SLICES"):
         monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("NHP_CHUNK", "4096")
     nhp.invalidate_device_datasets()
     for cfg in ("64,2", "64,4", "128,2", "128,4", "256,2", "256,4", "512,2", "512,4", "1024,2", "1024,4"):   # (waves per item, rows per request)
         monkeypatch.setenv("NHP_SLICES_CFG", cfg)
         assert rel(nhp.loglikelihood(c["proc"], data, recursive=False), want) < TOL, cfg
+        assert sl_rows(c["proc"], data) > 0
     monkeypatch.delenv("NHP_SLICES_CFG", raising=False)
+    monkeypatch.delenv("NHP_CHUNK", raising=False)
     monkeypatch.setenv("NHP_SLICES", "0")
     nhp.invalidate_device_datasets()
     for cfg in ("1,1,256", "2,4,256", "4,2,512", "8,4,512", "4,1,1024", "8,2,1024", "2,2,512"):
         monkeypatch.setenv("NHP_PAIRS_CFG", cfg)
         assert rel(nhp.loglikelihood(c["proc"], data, recursive=False), want) < TOL, cfg
+        assert sl_rows(c["proc"], data) == 0
     monkeypatch.delenv("NHP_PAIRS_CFG", raising=False)
     monkeypatch.delenv("NHP_SLICES", raising=False)
     # logit-normal impulses: the pair kernel reads {logit(x), 1/(x(1-x))} made once per dataset -- the same operations, so
@@ -372,48 +389,70 @@ def test_pair_list_and_packed_records_agree_with_the_exact_records(nhp, orc, net
     # (round 3: first in line is the slices' twin, k_windowed_slices_ln -- one lane per child over the planes of logit(x) and
     #  1/(x(1-x)) the parent sampler keeps; NHP_SLICES_LN=0 gives the pair kernel, NHP_PLIST=0 the whole pdf per record)
     gl = {}
-    for name, env in (("slices", {}), ("pairs", {"NHP_SLICES_LN": "0"}), ("records", {"NHP_PLIST": "0"})):
-        for k in ("NHP_PLIST", "NHP_SLICES_LN"):
+    datal = (t, cl["nodes"], cl["T"])
+    for name, env in (("slices", {"NHP_CHUNK": "4096"}), ("pairs", {"NHP_SLICES_LN": "0"}), ("records", {"NHP_PLIST": "0"})):
+        for k in ("NHP_PLIST", "NHP_SLICES_LN", "NHP_CHUNK"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         nhp.invalidate_device_datasets()
-        gl[name] = nhp.loglikelihood(cl["proc"], (t, cl["nodes"], cl["T"]), recursive=False)
+        gl[name] = nhp.loglikelihood(cl["proc"], datal, recursive=False)
         assert rel(gl[name], wantl) < TOL, name
+        assert (sl_rows(cl["proc"], datal) > 0) == (name == "slices"), name
     assert rel(gl["pairs"], gl["records"]) < 1e-13 and rel(gl["slices"], gl["records"]) < 1e-13
     monkeypatch.delenv("NHP_PLIST", raising=False)
     monkeypatch.delenv("NHP_SLICES_LN", raising=False)
+    monkeypatch.setenv("NHP_CHUNK", "4096")
+    nhp.invalidate_device_datasets()
     for cfg in ("64,2", "64,4", "256,2", "256,4", "512,2", "512,4"):
         monkeypatch.setenv("NHP_SLICES_LN_CFG", cfg)
-        assert rel(nhp.loglikelihood(cl["proc"], (t, cl["nodes"], cl["T"]), recursive=False), wantl) < TOL, cfg
+        assert rel(nhp.loglikelihood(cl["proc"], datal, recursive=False), wantl) < TOL, cfg
+        assert sl_rows(cl["proc"], datal) > 0
     monkeypatch.delenv("NHP_SLICES_LN_CFG", raising=False)
+    monkeypatch.delenv("NHP_CHUNK", raising=False)
+    nhp.invalidate_device_datasets()
     monkeypatch.setenv("NHP_SLICES_LN", "0")
     for cfg in ("2,2,256", "4,1,512", "8,2,1024"):
         monkeypatch.setenv("NHP_PAIRS_CFG", cfg)
-        assert rel(nhp.loglikelihood(cl["proc"], (t, cl["nodes"], cl["T"]), recursive=False), wantl) < TOL, cfg
+        assert rel(nhp.loglikelihood(cl["proc"], datal, recursive=False), wantl) < TOL, cfg
+        assert sl_rows(cl["proc"], datal) == 0
     monkeypatch.delenv("NHP_PAIRS_CFG", raising=False)
     monkeypatch.delenv("NHP_SLICES_LN", raising=False)
+    nhp.invalidate_device_datasets()
 
 
 def test_child_slices_at_a_thousand_nodes(nhp, orc, monkeypatch):
     """N = 1024 is where the 6-byte records of the child slices are tightest (11 bits of node, 37 bits of delay: 3.6e-12 of
     Δtmax): the log-likelihood through them, through the 8-byte pair list and through the exact records against the oracle on
-    the original times, standard and network model, with a column that has no child and an item with a single one."""
+    the original times, standard and network model, with a column that has no child and an item with a single one.
+    128 events per node at 8 per Δtmax: at the 39 per node this test had, every slice was half empty and the dataset dropped
+    its slices (tests/slices_ref.py restates the rule); the scalars say which layout each leg ran on."""
+    import slices_ref
+    M = 128 * 1024
     for network in (False, True):
-        c = random_case(1024, 40000, 5000.0, "exponential", 1.0, network=network, seed=77, nhp=nhp, orc=orc)
+        c = random_case(1024, M, M / 8.0, "exponential", 1.0, network=network, seed=77, nhp=nhp, orc=orc)
         n = c["nodes"].copy()
         n[n == 5] = 6
         n[n == 9] = 10
         n[123] = 9
         data = (c["times"], n, c["T"])
+        lay = slices_ref.layout(c["times"], n, 1024, 1.0)
+        sizes = lay.items[:, 2] - lay.items[:, 1]
+        assert lay.kept and lay.sl_nb == 11 and np.sum(sizes == 0) >= 1 and np.sum(sizes == 1) == 1
         want = orc.loglik(c["om"], c["times"], n, c["T"], recursive=False)
-        for name, env in (("slices", {}), ("pairs", {"NHP_SLICES": "0"}), ("exact", {"NHP_PLIST": "0", "NHP_EV8": "0"})):
+        for name, env in (("slices", {}), ("pairs", {"NHP_SLICES": "0"}),
+                          ("exact", {"NHP_SLICES": "0", "NHP_PLIST": "0", "NHP_EV8": "0"})):
             for k in ("NHP_PLIST", "NHP_EV8", "NHP_SLICES"):
                 monkeypatch.delenv(k, raising=False)
             for k, v in env.items():
                 monkeypatch.setenv(k, v)
             nhp.invalidate_device_datasets()
             assert rel(nhp.loglikelihood(c["proc"], data, recursive=False), want) < TOL, (name, network)
+            sc = nhp.device_dataset(c["proc"], data).scalars()
+            if name == "slices":
+                assert sc["sl_rows"] == lay.sl_rows and sc["n_slices"] == lay.n_slices and sc["sl_nb"] == 11, sc
+            else:
+                assert sc["sl_rows"] == 0, (name, sc)
     for k in ("NHP_PLIST", "NHP_EV8", "NHP_SLICES"):
         monkeypatch.delenv(k, raising=False)
     nhp.invalidate_device_datasets()
@@ -445,20 +484,23 @@ def test_derived_layouts_agree_on_awkward_data(nhp, monkeypatch):
                 imp = nhp.LogitNormalImpulseResponse(rng.normal(0.0, 1.0, (N, N)), rng.uniform(0.5, 2.0, (N, N)), dtm)
             proc = nhp.ContinuousStandardHawkesProcess(nhp.HomogeneousProcess(lam0), imp, nhp.DenseWeightModel(W))
             got = {}
-            for name, env in (("slices", {}), ("pairs", {"NHP_SLICES": "0"}), ("ev8", {"NHP_PLIST": "0"}),
+            # (the "slices" leg with items of 4096 children: with the default items all six datasets drop their slices)
+            for name, env in (("slices", {"NHP_CHUNK": "4096"}), ("pairs", {"NHP_SLICES": "0"}), ("ev8", {"NHP_PLIST": "0"}),
                               ("exact", {"NHP_PLIST": "0", "NHP_EV8": "0"})):
-                for k in ("NHP_PLIST", "NHP_EV8", "NHP_SLICES"):
+                for k in ("NHP_PLIST", "NHP_EV8", "NHP_SLICES", "NHP_CHUNK"):
                     monkeypatch.delenv(k, raising=False)
                 for k, v in env.items():
                     monkeypatch.setenv(k, v)
                 nhp.invalidate_device_datasets()
                 got[name] = nhp.loglikelihood(proc, (t, n, T), recursive=False)
+                assert (nhp.device_dataset(proc, (t, n, T)).scalars()["sl_rows"] > 0) == (name == "slices"), (N, kind, name)
             assert np.isfinite(got["exact"])
             assert rel(got["slices"], got["exact"]) < 1e-12, (N, kind, dtm, got)
             assert rel(got["pairs"], got["exact"]) < 1e-12, (N, kind, dtm, got)
             assert rel(got["ev8"], got["exact"]) < 1e-12, (N, kind, dtm, got)
-    for k in ("NHP_PLIST", "NHP_EV8", "NHP_SLICES"):
+    for k in ("NHP_PLIST", "NHP_EV8", "NHP_SLICES", "NHP_CHUNK"):
         monkeypatch.delenv(k, raising=False)
+    nhp.invalidate_device_datasets()
 
 
 @pytest.mark.parametrize("N,network,lgcp", [(3, False, False), (70, True, False), (200, False, True), (300, False, False),

@@ -185,7 +185,12 @@ def test_slice_sampler_gives_the_oracle_indices(nhp, orc, kind, network, lgcp, m
     t[500:530:2] = t[501:531:2]
     t[3000:3060] = np.sort(np.random.default_rng(8).uniform(t[3000], t[3000] + 0.9, 60))
     t = np.sort(t)
-    data = (t, c["nodes"], c["T"])
+    # with the default items of 32 children every slice is half empty and the dataset drops its slices (tests/slices_ref.py):
+    # items of 256, built explicitly -- the cached dataset of a data triple would be built without them again
+    monkeypatch.setenv("NHP_CHUNK", "256")
+    data = nhp.continuous.DeviceDataset(nhp.default_context(), (t, c["nodes"], c["T"]), 9, 1.2)
+    monkeypatch.delenv("NHP_CHUNK")
+    assert data.scalars()["sl_rows"] > 0 and data.scalars()["sl_max_rows"] + 1 <= 1024
     M = len(t)
     u = np.random.default_rng(17).uniform(size=M)
     u[::97] = 0.0

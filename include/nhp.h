@@ -197,6 +197,13 @@ nhp_status nhp_cont_loglik(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_c
  * else.  The buffer is the context's, so the sum is still made when the slot's dataset or model has been destroyed in
  * between; a later evaluation into the slot replaces the earlier one, pending or not.  NHP_DEFER_FINALIZE=0 in the
  * environment when the context is created: every evaluation adds its own sums up (one launch each, nothing pending).
+ * Inside a streak of enqueues an evaluation may be LAUNCHED only at the next enqueue or at the next joining call,
+ * whichever comes first: two evaluations on one dataset's child slices (exponential impulses, flat baselines, different
+ * slots) then share one pass over its records.  Nothing else changes: the evaluation reads the parameters its model had
+ * when it was enqueued (a joining call launches what is held before it does anything else), each slot gets the bits
+ * nhp_cont_loglik gives for its model, two evaluations into one slot stay in order, and an enqueue that no other enqueue
+ * precedes since the last joining call starts at once.  NHP_PAIR_ENQUEUE=0 when the context is created: one launch
+ * per evaluation, at the enqueue.
  * The recursive formulation (NHP_LL_RECURSIVE, exponential impulses) is not overlapped: it is a call like any other. */
 #define NHP_MAX_SLOTS 4096
 nhp_status nhp_cont_loglik_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds,

@@ -1045,15 +1045,78 @@ static nhp_status enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_co
     return NHP_OK;
 }
 
-// Odd slots go to the second lane, even ones stay on the main stream: two evaluations into one slot share a lane and stay
-// ordered, successive slots alternate and overlap (include/nhp.h: the ordering contract).
+static bool batch_compatible(const nhp_cont_model *x, const nhp_cont_model *y);
+
+// One evaluation, one launch.  Odd slots go to the second lane, even ones stay on the main stream: two evaluations into one
+// slot share a lane and stay ordered, successive slots alternate and overlap (include/nhp.h: the ordering contract).  A
+// paired launch may have left the slot's last value on the other lane: then the lanes are joined first.
+static nhp_status enqueue_single(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int32_t flags, int32_t slot)
+{
+    const bool rec = recursive_route(m, flags);
+    const int ln = (slot & 1) && ctx->stream2 && !rec ? 2 : 1;
+    const bool in_range = slot >= 0 && slot < NHP_MAX_SLOTS;
+    if (in_range && !rec && ctx->slot_lane[slot] && ctx->slot_lane[slot] != ln) ctx->join_lanes();
+    nhp_lane_guard lane{ctx};
+    if (ln == 2) lane.flip();
+    const nhp_status st = enqueue(ctx, ds, m, flags, slot, ctx->defer_finalize);
+    if (in_range && !rec) ctx->note_lane(slot, ln);
+    return st;
+}
+
+// the pass of two (nhp_launch_slices_pair), on the lane the last enqueue did not take
+static nhp_status enqueue_pair(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *const *ms, const int32_t *slot)
+{
+    auto clash = [&](const int l) {
+        return (ctx->slot_lane[slot[0]] && ctx->slot_lane[slot[0]] != l) || (ctx->slot_lane[slot[1]] && ctx->slot_lane[slot[1]] != l);
+    };
+    int ln = ctx->last_enq_lane == 1 ? 2 : 1;
+    if (clash(ln)) {                                        // (a streak that comes back to its slots: stay where they are, if both agree)
+        if (!clash(3 - ln)) ln = 3 - ln;
+        else ctx->join_lanes();
+    }
+    nhp_lane_guard lane{ctx};
+    if (ln == 2) lane.flip();
+    NHP_TRY(nhp_launch_slices_pair(ctx, ds, ms, slot));
+    for (int k = 0; k < 2; ++k) ctx->note_lane(slot[k], ln);
+    ++ctx->pair_launches;
+    return NHP_OK;
+}
+
+// the held evaluation alone, as if it had been launched when it was enqueued; a failure is reported by the next checked call
+void nhp_ctx::flush_held()
+{
+    const held_eval h = held;
+    held = held_eval{};                                     // (first: the launch below may join, and so come back here)
+    // (never from inside a launch on lane 2: every path that flips the lane has launched or taken what was held before)
+    if (enqueue_single(this, h.ds, h.m, h.flags, h.slot) != NHP_OK) lane_call(hipErrorUnknown);
+}
+
+extern "C" int64_t nhp_debug_pair_launches(const nhp_ctx *ctx) { return ctx ? ctx->pair_launches : -1; }
+
+// Inside a streak an eligible evaluation waits for the next enqueue: two on one dataset share one pass over its records.
 extern "C" nhp_status nhp_cont_loglik_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds,
                                               const nhp_cont_model *m, int32_t flags, int32_t slot)
 {
     if (!ctx) return NHP_EINVAL;
-    nhp_lane_guard lane{ctx};
-    if ((slot & 1) && ctx->stream2 && !recursive_route(m, flags)) lane.flip();
-    return enqueue(ctx, ds, m, flags, slot, ctx->defer_finalize);
+    NHP_TRY(nhp_check_pair(ctx, ds, m));
+    if (slot < 0 || slot >= NHP_MAX_SLOTS) return NHP_EINVAL;
+    const bool eligible = ctx->pair_enqueue && ctx->defer_finalize && ctx->stream2 && !recursive_route(m, flags) &&
+                          nhp_slices_pair_eligible(ds, m);
+    if (ctx->held.ds) {
+        const nhp_ctx::held_eval h = ctx->held;
+        if (eligible && h.ds == ds && h.slot != slot && batch_compatible(h.m, m)) {
+            ctx->held = nhp_ctx::held_eval{};
+            const nhp_cont_model *const ms[2] = {h.m, m};
+            const int32_t slots[2] = {h.slot, slot};
+            return enqueue_pair(ctx, ds, ms, slots);
+        }
+        ctx->flush_held();
+    }
+    if (eligible && ctx->pend.any()) {                      // only inside a streak: a lone enqueue starts at once
+        ctx->held.ds = ds; ctx->held.m = m; ctx->held.flags = flags; ctx->held.slot = slot;
+        return NHP_OK;
+    }
+    return enqueue_single(ctx, ds, m, flags, slot);
 }
 
 extern "C" nhp_status nhp_cont_loglik(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m,
@@ -1071,6 +1134,12 @@ static bool batch_compatible(const nhp_cont_model *x, const nhp_cont_model *y)
     return x && y && x->ctx == y->ctx && x->N == y->N && x->impulse_kind == y->impulse_kind && x->baseline_kind == y->baseline_kind &&
            x->grid_n == y->grid_n && x->has_A == y->has_A && x->dt_max == y->dt_max;
 }
+
+// sets per pass over the child slices: two, at 32 waves per CU, beat four at 16 (64 sets 103–105k evals/s against
+// 94–95k); -DNHP_BATCH_SETS=4 builds the other for the comparison
+#ifndef NHP_BATCH_SETS
+#define NHP_BATCH_SETS 2
+#endif
 
 // nb evaluations (finite-difference sweeps, chain populations) back to back, one synchronisation
 extern "C" nhp_status nhp_cont_loglik_batch(nhp_ctx *ctx, const nhp_cont_dataset *ds,
@@ -1111,10 +1180,10 @@ extern "C" nhp_status nhp_cont_loglik_batch(nhp_ctx *ctx, const nhp_cont_dataset
             const bool second = windowed && ctx && ctx->stream2 && (launches & 1);
             if (second) lane.flip();
             for (int q = 1; q < take; ++q) NHP_TRY(nhp_check_pair(ctx, ds, ms[q]));
-            // exponential models on a dataset with child slices: four (or two) at a time through ONE pass over the slices
+            // exponential models on a dataset with child slices: NHP_BATCH_SETS at a time through ONE pass over the slices
             // (cont_slices.hip: every pair record fetched and decoded once for all of them)
             if (windowed && take >= 2 && ds->d_sl_row) {
-                const int S = take >= 4 ? 4 : 2;
+                const int S = take >= 4 ? NHP_BATCH_SETS : 2;
                 bool launched = false;
                 NHP_TRY(nhp_launch_slices_batch(ctx, ds, ms, S, k, &launched));
                 if (launched) {

@@ -556,11 +556,33 @@ struct nhp_sets {
     double *out[NHP_SETS_MAX];
 };
 
-template <int BLOCK, int C, int S>
+// DEFER (S = 2, the paired enqueue route): each model's result must be what k_windowed_slices<BLOCK, C, true,
+// false> leaves for it alone, bit for bit, so the integral's terms are formed as there; thread 0 stores the two block sums of
+// model m at index 2·blockIdx.x of ITS result slot's buffer (st.out[m]) and k_finalize_slots adds them at the next join: no
+// ticket, no agent-scope atomics.  The waves' integral sums wait in LDS from the head on (red[16 ..]): four registers less
+// in the row loop, which is what lets eight waves per SIMD fit (64 VGPRs).
+__device__ __forceinline__ double sl_flat_integral(const double lam0, const double duration)
+{
+#pragma clang fp contract(off)
+    return threadIdx.x == 0 ? lam0 * duration : 0.0;
+}
+
+// log(mantissa product) + exponent·ln 2 as k_windowed_slices forms it: the product rounded on its own, then the sum
+__device__ __forceinline__ double sl_log_of(const double prod, const int pexp)
+{
+#pragma clang fp contract(off)
+    const double e = (double)pexp * 6.93147180559945286e-01;
+    return e + nhp_log(prod);
+}
+
+template <int BLOCK, int C, int S, bool DEFER = false>
 __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_slices sl, nhp_sets st, double *__restrict__ partials,
                                                          unsigned int *__restrict__ counter)
 {
     constexpr int NW = BLOCK / 64;
+    // two sets, at most eight waves: the waves' integral sums are made in the head and wait in red[16 ..] (the order of
+    // nhp_block_sum2_n: wave sums, then wave by wave), which keeps the row loop inside 64 registers
+    constexpr bool EARLY = DEFER || (S == 2 && NW <= 8);
     extern __shared__ __align__(16) unsigned char smem[];
     double *red = reinterpret_cast<double *>(smem);                 // [2 * NW <= 32] + flag at [32]
     double2 *col = reinterpret_cast<double2 *>(smem + 320);         // [S][N + 1]
@@ -605,7 +627,13 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
             if (it.first) integ[m] += a.cnt[p] * wv;
         }
         if (tid == 0) col[(size_t)m * (N + 1) + N] = make_double2(0.0, 0.0);
-        if (it.first && tid == 0) integ[m] += st.lambda0[m][c] * a.duration;
+        if (DEFER) {
+            if (it.first) integ[m] += sl_flat_integral(st.lambda0[m][c], a.duration);
+        } else if (it.first && tid == 0) integ[m] += st.lambda0[m][c] * a.duration;
+        if (EARLY) {
+            const double wsum = nhp_wave_sum(integ[m]);
+            if (lane == 0) red[16 + m * NW + w] = wsum;
+        }
     }
     if (tid < 64) etab[tid] = tab_v;
     __syncthreads();
@@ -673,13 +701,41 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
         }
         j = jn; row0 = row0n; K = Kn;
     }
+    if (DEFER) {
+        // nhp_block_sum2_n's order for every model, with one pair of barriers for all: wave sums, then wave by wave
+        double ws[S];
+#pragma unroll
+        for (int m = 0; m < S; ++m) {
+            double blk = sl_log_of(prod[m], pexp[m]);
+            if (prod[m] == 0.0) blk = -__builtin_inf();
+            ws[m] = nhp_wave_sum(blk);
+        }
+        __syncthreads();
+        if (lane == 0) {
+#pragma unroll
+            for (int m = 0; m < S; ++m) red[m * NW + w] = ws[m];
+        }
+        __syncthreads();
+        if (tid == 0) {
+#pragma unroll
+            for (int m = 0; m < S; ++m) {
+                double sx = 0.0, sy = 0.0;
+                for (int q = 0; q < NW; ++q) { sx += red[m * NW + q]; sy += red[16 + m * NW + q]; }
+                st.out[m][2 * (size_t)blockIdx.x] = sx;
+                st.out[m][2 * (size_t)blockIdx.x + 1] = sy;
+            }
+        }
+        return;
+    }
     int *flag = reinterpret_cast<int *>(red + 32);
 #pragma unroll
     for (int m = 0; m < S; ++m) {
         double blk = nhp_log(prod[m]) + (double)pexp[m] * 6.93147180559945286e-01;
         if (prod[m] == 0.0) blk = -__builtin_inf();
-        double blk_int = integ[m];
+        double blk_int = EARLY ? 0.0 : integ[m];
         nhp_block_sum2_n<NW>(blk, blk_int, red);
+        if (EARLY && tid == 0)
+            for (int q = 0; q < NW; ++q) blk_int += red[16 + m * NW + q];
         if (tid == 0) {
             __hip_atomic_store(&partials[(2 * (size_t)blockIdx.x) * S + 2 * m], blk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&partials[(2 * (size_t)blockIdx.x) * S + 2 * m + 1], blk_int, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1133,6 +1189,17 @@ static nhp_status ensure_parent_slices(nhp_ctx *ctx, const nhp_cont_dataset *cds
     return NHP_OK;
 }
 
+// the workgroup size and the rows per request of k_windowed_slices on this dataset (the paired launch takes the same)
+static void slices_cfg(const nhp_cont_dataset *ds, int *B, int *C)
+{
+    const int per_item = (ds->max_item + 63) / 64;
+    // (rows in flight per wave = 2C: short slices are served by L2 / the Infinity Cache and want few, long ones stream from HBM)
+    const double mean_rows = ds->n_slices > 0 ? (double)ds->sl_rows / (double)ds->n_slices : 0.0;
+    *B = per_item >= 12 ? 512 : per_item >= 6 ? 256 : per_item >= 3 ? 128 : 64;
+    *C = mean_rows >= 48.0 ? 8 : mean_rows >= 16.0 ? 4 : 2;
+    if (const char *cfg = getenv("NHP_SLICES_CFG")) sscanf(cfg, "%d,%d", B, C);
+}
+
 // grad != nullptr: log-likelihood AND gradient (k_windowed_slices<.., GRAD>); the gradient must have been initialised by
 // k_grad_init unless `direct`
 static nhp_status launch_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int mask_integral, double *d_out,
@@ -1158,11 +1225,8 @@ static nhp_status launch_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const 
     }
     // waves per workgroup from the slices an item has (one item per node at N >= 1024: ~15 slices; short items at small N);
     // rows per request from the windows' length.  NHP_SLICES_CFG = "BLOCK,C" overrides (tools/dbg/slicesweep.sh)
-    const int per_item = (ds->max_item + 63) / 64;
-    // (rows in flight per wave = 2C: short slices are served by L2 / the Infinity Cache and want few, long ones stream from HBM)
-    const double mean_rows = ds->n_slices > 0 ? (double)ds->sl_rows / (double)ds->n_slices : 0.0;
-    int B = per_item >= 12 ? 512 : per_item >= 6 ? 256 : per_item >= 3 ? 128 : 64, C = mean_rows >= 48.0 ? 8 : mean_rows >= 16.0 ? 4 : 2;
-    if (const char *cfg = getenv("NHP_SLICES_CFG")) sscanf(cfg, "%d,%d", &B, &C);
+    int B, C;
+    slices_cfg(ds, &B, &C);
     dim3 grid((unsigned)ds->n_items);
     bool ok = false;
     const bool flat = m->baseline_kind == NHP_BASELINE_HOMOGENEOUS;
@@ -1340,6 +1404,59 @@ nhp_status nhp_launch_slices_batch(nhp_ctx *ctx, const nhp_cont_dataset *ds, con
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     if (S == 4) NHP_TRY(launch_sets<4>(ctx, ds, ms, slot0, lds)); else NHP_TRY(launch_sets<2>(ctx, ds, ms, slot0, lds));
     *launched = true;
+    return NHP_OK;
+}
+
+// ---- two enqueued evaluations in one pass ----------------------------------------------------------------------
+// Whether an enqueue of (ds, m) would take k_windowed_slices' deferred exit AND may share a pass: exponential impulses, flat
+// baseline, one item per node on a whole dataset, a workgroup of at most 512, and two columns in LDS four times per CU.
+bool nhp_slices_pair_eligible(const nhp_cont_dataset *ds, const nhp_cont_model *m)
+{
+    if (!ds || !m || !ds->d_sl_row || ds->n_items <= 0) return false;
+    if (m->impulse_kind != NHP_IMPULSE_EXPONENTIAL || m->baseline_kind != NHP_BASELINE_HOMOGENEOUS) return false;
+    if (!ds->all_sole || nhp_is_column_shard(ds) || nhp_slices_off(nullptr)) return false;
+    if (const char *pl = getenv("NHP_PLIST")) if (atoi(pl) == 0) return false;
+    if (4 * (320 + 32 * ((size_t)ds->N + 1) + 512) > 160 * 1024) return false;
+    int B, C;
+    slices_cfg(ds, &B, &C);
+    return (B == 64 || B == 128 || B == 256 || B == 512) && (C == 2 || C == 4 || C == 8);
+}
+
+// ms[0] -> slot[0], ms[1] -> slot[1] (different slots), both eligible and batch-compatible: one launch of k_slices_batch<B, C, 2,
+// DEFER> on the current lane with launch_slices' (B, C); both slots are marked pending with that B.
+nhp_status nhp_launch_slices_pair(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *const *ms, const int32_t *slot)
+{
+    const size_t lds = 320 + 32 * ((size_t)ds->N + 1) + 512;
+    NHP_HIP(ctx, hipSetDevice(ctx->device));
+    for (int k = 0; k < 2; ++k) NHP_TRY(nhp_ctx_reserve_slot_partials(ctx, slot[k], 2 * (size_t)ds->n_items));
+    nhp_cont_args a = nhp_make_args(ds, ms[0]);
+    NHP_TRY(ensure_slices(ctx, ds, a));
+    const nhp_slices sl = slices_view(ds);
+    nhp_sets st;
+    for (int k = 0; k < NHP_SETS_MAX; ++k) {
+        const nhp_cont_model *m = ms[k & 1];
+        st.p1[k] = m->d_p1; st.W[k] = m->d_W; st.A[k] = m->has_A ? m->d_A : nullptr; st.lambda0[k] = m->d_lambda0;
+        st.out[k] = ctx->d_slot_partials[slot[k & 1]];
+    }
+    int B, C;
+    slices_cfg(ds, &B, &C);
+    dim3 grid((unsigned)ds->n_items);
+    bool ok = false;
+#define NHP_PCASE(b, cc)                                                                                              \
+    if (!ok && B == b && C == cc) {                                                                                   \
+        ok = true;                                                                                                    \
+        if (lds > 64 * 1024)                                                                                          \
+            (void)hipFuncSetAttribute((const void *)k_slices_batch<b, cc, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((k_slices_batch<b, cc, 2, true>), grid, dim3(b), lds, ctx->lane(), a, sl, st, (double *)nullptr,  \
+                           (unsigned int *)nullptr);                                                                  \
+    }
+#define NHP_PROW(b) NHP_PCASE(b, 2) NHP_PCASE(b, 4) NHP_PCASE(b, 8)
+    NHP_PROW(64) NHP_PROW(128) NHP_PROW(256) NHP_PROW(512)
+#undef NHP_PROW
+#undef NHP_PCASE
+    if (!ok) { nhp_set_error(ctx, "paired enqueue: no kernel for %d threads, %d rows", B, C); return NHP_EINVAL; }
+    NHP_HIP(ctx, hipGetLastError());
+    for (int k = 0; k < 2; ++k) ctx->pend.mark(slot[k], ds->n_items, B);
     return NHP_OK;
 }
 

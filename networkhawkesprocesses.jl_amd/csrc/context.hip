@@ -149,6 +149,7 @@ extern "C" nhp_status nhp_ctx_create(int32_t device, nhp_ctx **out)
     nhp_ctx *ctx = new nhp_ctx();
     ctx->device = device;
     if (const char *df = getenv("NHP_DEFER_FINALIZE")) ctx->defer_finalize = atoi(df) != 0;
+    if (const char *pe = getenv("NHP_PAIR_ENQUEUE")) ctx->pair_enqueue = atoi(pe) != 0;
     NHP_HIP(ctx, hipSetDevice(device));
     hipDeviceProp_t prop;
     NHP_HIP(ctx, hipGetDeviceProperties(&prop, device));

@@ -104,10 +104,35 @@ struct nhp_ctx {
     bool defer_finalize = true;
     int64_t finalize_launches = 0;              // k_finalize_slots launches so far (nhp_debug_finalize_launches)
     void finalize_pending();                    // context.hip: one launch (per 240 slots) on the main stream
+    // Paired enqueues: inside a streak -- a deferred slot is already pending -- nhp_cont_loglik_enqueue may hold
+    // ONE eligible evaluation back and launch it with the next one in a single pass over the records (cont_loglik.hip).
+    // Whatever is held is launched alone at the next enqueue that cannot share its pass and at every join, before the join
+    // does anything else: it sees the parameters it was enqueued with, its dataset and model are alive, timer_stop spans it.
+    // NHP_PAIR_ENQUEUE=0 (read when the context is made): nothing is ever held.
+    struct held_eval { const struct nhp_cont_dataset *ds = nullptr; const struct nhp_cont_model *m = nullptr; int32_t flags = 0, slot = -1; };
+    held_eval held;
+    bool pair_enqueue = true;
+    int64_t pair_launches = 0;                  // launches that carried two evaluations (nhp_debug_pair_launches)
+    void flush_held();                          // cont_loglik.hip
+    // A paired launch takes the lane the last enqueue did not, so a slot can meet another lane than its last launch took.
+    // The lane (1: main stream, 2: second) of every slot's launches since the last join is kept here; an enqueue into a slot
+    // last launched on the other lane joins first, which keeps two evaluations into one slot in order.
+    uint8_t slot_lane[NHP_MAX_SLOTS] = {};
+    std::vector<int32_t> laned;                 // the slots with an entry
+    int last_enq_lane = 2;                      // (the first pair of a context's life goes to the main stream's partner)
+    void note_lane(int32_t slot, int ln)
+    {
+        if (!slot_lane[slot]) laned.push_back(slot);
+        slot_lane[slot] = (uint8_t)ln;
+        last_enq_lane = ln;
+    }
     // the JOIN: the main stream waits for what lane 2 has in flight, then adds up the deferred slots of both lanes before
     // anything else is given to it, and is noted as having new work
     void join_lanes()
     {
+        if (held.ds) flush_held();
+        for (const int32_t s : laned) slot_lane[s] = 0;
+        laned.clear();
         if (lane2_busy) {
             lane2_busy = false;
             lane_call(hipEventRecord(ev_join, stream2));
@@ -631,6 +656,12 @@ nhp_status nhp_launch_sampler_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, c
 // models are not covered (the caller falls back to its other kernels).
 nhp_status nhp_launch_slices_batch(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *const *ms, int S, int32_t slot0,
                                    bool *launched);
+// Two enqueued evaluations in one pass (k_slices_batch<B, C, 2, DEFER>): _eligible says whether an enqueue of (ds, m) would take
+// k_windowed_slices' deferred exit and may share a pass; _pair launches ms[0] -> slot[0], ms[1] -> slot[1] (both eligible,
+// batch-compatible, different slots) on the current lane with that kernel's (B, C) and marks both slots pending.  Each
+// slot gets the bits the single launch would have left.
+bool nhp_slices_pair_eligible(const nhp_cont_dataset *ds, const nhp_cont_model *m);
+nhp_status nhp_launch_slices_pair(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *const *ms, const int32_t *slot);
 nhp_cont_args nhp_make_args(const nhp_cont_dataset *ds, const nhp_cont_model *m);
 nhp_status nhp_check_pair(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m);
 // Device -> caller memory through the context's pinned staging buffer: DMA at link speed into pinned memory, then one

@@ -151,6 +151,33 @@ nhp_status nhp_cont_dataset_create_columns(nhp_ctx *ctx, const double *events, c
 nhp_status nhp_cont_dataset_create_device(nhp_ctx *ctx, const double *events, const int64_t *nodes, int64_t n_events,
                                           int32_t n_nodes, double duration, double dt_max, int32_t col_begin,
                                           int32_t col_end, int32_t input_on_device, nhp_cont_dataset **out);
+/* Several independent recordings ("trials") of one system as ONE dataset.  Trial r = 0 .. n_trials - 1 owns
+ * the events [trial_event_offsets[r], trial_event_offsets[r + 1]) and the interval [trial_time_offsets[r],
+ * trial_time_offsets[r + 1]] of the stacked clock; `events` are stacked times (the trial's own time + its time offset,
+ * ascending over the whole array), duration = trial_time_offsets[n_trials].  Both tables have n_trials + 1 entries and are
+ * HOST pointers for every `where`.  The event index, never the time, decides the trial of an event (an event at the end
+ * of one trial and one at the start of the next share a stacked time); a trial may be empty (exposure only).
+ * No look-back window crosses a trial's first event, and everything made from the windows follows: log-likelihood,
+ * gradient, event intensities, the parent sampler and its statistics, the adjacency sweep, EM, the information matrices,
+ * map_parents / cascades.  The recursive formulation (NHP_LL_RECURSIVE) is the reference's on each trial alone, summed: it
+ * always runs as a window sum that starts at the trial's first event after its local time 0 (exact; a cut shortens it
+ * where the model gives one), NHP_LL_FULL_RECURSION included.  nhp_cont_compensator integrates every trial from its own
+ * start.  nhp_cont_intensity, nhp_cont_forecast, nhp_cont_lgcp_loglik and every model with an LGCP baseline answer
+ * NHP_ENOTIMPL on a dataset of more than one trial.
+ * where = 0: host pre-pass; 1: device pre-pass, events / nodes host pointers; 2: device pre-pass, events / nodes device
+ * pointers on ctx's device (as nhp_cont_dataset_create_device).  The routes give the same dataset byte for byte, and
+ * n_trials = 1 gives the dataset of nhp_cont_dataset_create_columns / _create_device over all columns.
+ * Errors beyond theirs: NHP_EINVAL for event offsets that do not start at 0, decrease or do not end at n_events;
+ * NHP_EDOMAIN for time offsets that do not start at 0, do not increase strictly or are not finite, and for an event
+ * outside its trial's interval; the message names the entry. */
+nhp_status nhp_cont_dataset_create_trials(nhp_ctx *ctx, const double *events, const int64_t *nodes, int64_t n_events,
+                                          int32_t n_nodes, const int64_t *trial_event_offsets,
+                                          const double *trial_time_offsets, int32_t n_trials, double dt_max, int32_t where,
+                                          nhp_cont_dataset **out);
+/* *n_trials (1 for a dataset of the other entry points) and, where not NULL, the event offsets [n_trials + 1], the time
+ * offsets [n_trials + 1] and per trial the first event index whose time is not exactly the trial's start [n_trials] */
+nhp_status nhp_cont_dataset_get_trials(const nhp_cont_dataset *ds, int32_t *n_trials, int64_t *event_offsets,
+                                       double *time_offsets, int64_t *first_positive);
 void nhp_cont_dataset_destroy(nhp_cont_dataset *ds);
 /* Σ_i K_i: parent-child pairs inside the look-back window (SURVEY 8d F_alg) */
 int64_t nhp_cont_dataset_pairs(const nhp_cont_dataset *ds);

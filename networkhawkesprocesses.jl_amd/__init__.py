@@ -12,8 +12,9 @@ from .components import (BernoulliNetworkModel, DenseNetworkModel, DenseWeightMo
                          LogGaussianCoxProcess, LogitNormalImpulseResponse, OrnsteinUhlenbeckKernel,
                          PeriodicKernel, SquaredExponentialKernel, split_extract)
 from .continuous import (Compensator, ContinuousHawkesProcess, ContinuousNetworkHawkesProcess,  # noqa: F401
-                         ContinuousStandardHawkesProcess, DeviceDataset, Forecast, HawkesProcess, TimeRescalingTest, compensator,
-                         device_dataset, forecast, invalidate_device_datasets, time_rescaling_test, total_intensity)
+                         ContinuousStandardHawkesProcess, DeviceDataset, Forecast, HawkesProcess, StackedEvents, TimeRescalingTest,
+                         compensator, device_dataset, forecast, invalidate_device_datasets, stack_event_trials, time_rescaling_test,
+                         total_intensity)
 from . import continuous as _cont
 from .discrete import (DiscreteDataset, DiscreteFitTest, DiscreteForecast, DiscreteGaussianImpulseResponse,  # noqa: F401
                        DiscreteHawkesProcess, DiscreteHomogeneousProcess, DiscreteLogGaussianCoxProcess,

@@ -113,6 +113,8 @@ def _declare(lib):
     f("nhp_cont_dataset_create", i32, _vp, _dp, _ip, i64, i32, dbl, dbl, C.POINTER(_vp))
     f("nhp_cont_dataset_create_columns", i32, _vp, _dp, _ip, i64, i32, dbl, dbl, i32, i32, C.POINTER(_vp))
     f("nhp_cont_dataset_create_device", i32, _vp, _vp, _vp, i64, i32, dbl, dbl, i32, i32, i32, C.POINTER(_vp))
+    f("nhp_cont_dataset_create_trials", i32, _vp, _vp, _vp, i64, i32, _ip, _dp, i32, dbl, i32, C.POINTER(_vp))
+    f("nhp_cont_dataset_get_trials", i32, _vp, C.POINTER(i32), _ip, _dp, _ip)
     f("nhp_cont_simulate", i32, _vp, _vp, dbl, u64, i64, i32, _vp, _vp, _vp, C.POINTER(i64))
     f("nhp_cont_compensator", i32, _vp, _vp, _vp, i32, _vp, _vp, _vp)
     f("nhp_cont_forecast", i32, _vp, _vp, _vp, dbl, i32, u64, i64, i32, _vp, _vp, _vp, _vp, _vp, _dp)

@@ -167,17 +167,132 @@ def _device_tensors(events, nodes, ctx):
     return events, nodes
 
 
+class StackedEvents:
+    """Several independent trials as one recording on a stacked clock (stack_event_trials): trial r owns the events
+    [event_offsets[r], event_offsets[r + 1]) and the interval [time_offsets[r], time_offsets[r + 1]] of the clock;
+    `events` are the stacked times, `duration` = time_offsets[-1].  Unpacks like the triple (events, nodes, duration)."""
+
+    def __init__(self, events, nodes, duration, event_offsets, time_offsets):
+        self.events, self.nodes, self.duration = events, nodes, float(duration)
+        self.event_offsets = np.ascontiguousarray(event_offsets, dtype=np.int64)
+        self.time_offsets = np.ascontiguousarray(time_offsets, dtype=np.float64)
+
+    @property
+    def ntrials(self):
+        return len(self.event_offsets) - 1
+
+    def __iter__(self):
+        return iter((self.events, self.nodes, self.duration))
+
+    def __getitem__(self, k):
+        return (self.events, self.nodes, self.duration)[k]
+
+    def __len__(self):
+        return 3
+
+    def __repr__(self):
+        return f"StackedEvents(trials={self.ntrials}, events={int(self.event_offsets[-1])}, duration={self.duration:g})"
+
+
+def _is_trial_list(data):
+    """A Python list whose entries are all 3-tuples: trials.  (A 3-tuple, or a list [events, nodes, duration], is one
+    recording, as ever.)"""
+    return isinstance(data, list) and len(data) > 0 and all(isinstance(tr, tuple) and len(tr) == 3 for tr in data)
+
+
+def stack_event_trials(trials):
+    """Stack independent trials [(events_r, nodes_r, T_r), ...] over the same nodes along one clock -> StackedEvents.  Trial r
+    takes the interval [o_r, o_r + T_r] with o_0 = 0, o_{r+1} = o_r + T_r, and its events move to o_r + t.  A trial may be empty
+    (it then adds exposure only), T_r must be positive and finite, and the events of a trial sorted inside [0, T_r].
+
+    The shift rounds every time once: a delay between two events of one trial changes by at most one ulp of ΣT_r (not at all
+    when times and durations are multiples of one power of two and ΣT_r stays below 2^53 of them).
+
+    Host arrays are stacked with numpy; when every trial's events and nodes are torch tensors on one device they are stacked
+    there and never cross to the host (the checks then cost one small read-back per trial)."""
+    if isinstance(trials, StackedEvents):
+        return trials
+    if not isinstance(trials, (list, tuple)) or len(trials) == 0:
+        raise ValueError("trials must be a non-empty list of (events, nodes, duration) tuples")
+    for r, tr in enumerate(trials):
+        if not isinstance(tr, (tuple, list)) or len(tr) != 3:
+            raise ValueError(f"trial {r} is not an (events, nodes, duration) tuple")
+    on_dev = [_on_device(tr[0]) or _on_device(tr[1]) for tr in trials]
+    if any(on_dev) and not all(_on_device(tr[0]) and _on_device(tr[1]) for tr in trials):
+        raise ValueError("the trials' events and nodes must all be torch tensors on one device, or all host arrays")
+    device = all(on_dev)
+    f, o = np.zeros(len(trials) + 1, dtype=np.int64), np.zeros(len(trials) + 1)
+    ev, nd = [], []
+    for r, (e, n, T) in enumerate(trials):
+        T = float(T)
+        if not (np.isfinite(T) and T > 0.0):
+            raise DomainError(f"trial {r}: duration {T} must be positive and finite")
+        if device:
+            import torch
+            if e.dim() != 1 or n.dim() != 1 or e.numel() != n.numel():
+                raise ValueError(f"trial {r}: events and nodes must be 1-D and of the same length")
+            if e.device != n.device or e.device != trials[0][0].device:
+                raise ValueError(f"trial {r}: every tensor must be on the same device")
+            e, n = e.to(torch.float64), n.to(torch.int64)
+            if e.numel():
+                bad = torch.stack([(e[1:] < e[:-1]).any(), (e < 0.0).any() | (e > T).any() | torch.isnan(e).any()]).cpu().numpy()
+            else:
+                bad = (False, False)
+        else:
+            e, n = host_array(e, np.float64), np.asarray(host_array(n, np.int64))
+            if e.ndim != 1 or n.ndim != 1 or len(e) != len(n):
+                raise ValueError(f"trial {r}: events and nodes must be 1-D and of the same length")
+            bad = (bool(np.any(e[1:] < e[:-1])), not bool(np.all((e >= 0.0) & (e <= T))))
+        if bad[0]:
+            raise ValueError(f"trial {r}: events must be sorted")
+        if bad[1]:
+            raise DomainError(f"trial {r}: events must lie in [0, {T}]")
+        o[r + 1] = o[r] + T
+        f[r + 1] = f[r] + len(e)
+        ev.append(e + o[r])
+        nd.append(n)
+    if not np.isfinite(o[-1]):
+        raise DomainError("the durations of the trials do not add up to a finite number")
+    if device:
+        import torch
+        return StackedEvents(torch.cat(ev).contiguous(), torch.cat(nd).contiguous(), o[-1], f, o)
+    return StackedEvents(np.ascontiguousarray(np.concatenate(ev), dtype=np.float64),
+                         np.ascontiguousarray(np.concatenate(nd), dtype=np.int64), o[-1], f, o)
+
+
+def as_data(data):
+    """`data` as the entry points take it: a list of (events, nodes, duration) tuples becomes a StackedEvents; anything else is
+    returned as is.  Nothing is kept: a caller that evaluates the same trials again and again stacks them once itself
+    (stack_event_trials) and passes the StackedEvents, or the DeviceDataset, whose device copy device_dataset then reuses."""
+    return stack_event_trials(data) if _is_trial_list(data) else data
+
+
+def ntrials_of(data):
+    """How many trials `data` holds, without stacking or uploading anything."""
+    if isinstance(data, (DeviceDataset, StackedEvents)):
+        return data.ntrials
+    return len(data) if _is_trial_list(data) else 1
+
+
 class DeviceDataset:
     """nhp_cont_dataset handle: (events, nodes, duration) uploaded once, pre-pass done for Δtmax."""
 
-    def __init__(self, ctx, data, nnodes, Δtmax, columns=None, build="host"):
+    def __init__(self, ctx, data, nnodes, Δtmax, columns=None, build="host", trial_offsets=None):
         """columns = (begin, end), 0-based half-open: a column shard (sharded.py) that evaluates only the children on
         those nodes; None = the whole dataset.  build = "host" (the pre-pass on the host) or "device" (on the GPU,
         nhp_cont_dataset_create_device: the same dataset, byte for byte).  events / nodes given as torch tensors on
         ctx's device always take the device route and are copied on the device; no host copy is kept."""
         if build not in ("host", "device"):
             raise ValueError(f'build must be "host" or "device", not {build!r}')
+        data = as_data(data)
+        if trial_offsets is None and isinstance(data, StackedEvents):
+            trial_offsets = (data.event_offsets, data.time_offsets)
         events, nodes, duration = data
+        if trial_offsets is not None:
+            if columns is not None and tuple(columns) != (0, int(nnodes)):
+                raise NotImplementedError("a dataset of trials is a whole dataset: no column shard (sharded.ShardedDataset)")
+            self._init_trials(ctx, events, nodes, nnodes, Δtmax, build, trial_offsets)
+            return
         self.duration, self.Δtmax, self.nnodes, self.ctx = float(duration), float(Δtmax), int(nnodes), ctx
         h = C.c_void_p()
         self.columns = (0, int(nnodes)) if columns is None else (int(columns[0]), int(columns[1]))
@@ -207,6 +322,62 @@ class DeviceDataset:
         _lib.check(rc, ctx.h)
         self.h = h
         self._fin = weakref.finalize(self, _lib.lib().nhp_cont_dataset_destroy, h)
+
+    def _init_trials(self, ctx, events, nodes, nnodes, Δtmax, build, trial_offsets):
+        """trial_offsets = (event_offsets, time_offsets), R + 1 entries each, over stacked times (StackedEvents;
+        nhp_cont_dataset_create_trials, which checks them).  duration = time_offsets[-1]."""
+        f = np.ascontiguousarray(trial_offsets[0], dtype=np.int64)
+        o = np.ascontiguousarray(trial_offsets[1], dtype=np.float64)
+        if f.ndim != 1 or o.ndim != 1 or len(f) != len(o) or len(f) < 2:
+            raise ValueError("trial_offsets = (event_offsets, time_offsets): two 1-D tables of R + 1 entries, R >= 1")
+        self.duration, self.Δtmax, self.nnodes, self.ctx = float(o[-1]), float(Δtmax), int(nnodes), ctx
+        self.columns = (0, int(nnodes))
+        h = C.c_void_p()
+        lib = _lib.lib()
+        if _on_device(events) or _on_device(nodes):
+            import torch
+            ev, nd = _device_tensors(events, nodes, ctx)
+            self.events = self.nodes = None
+            self.M, self.build = int(ev.numel()), "device"
+            torch.cuda.current_stream(ev.device).synchronize()      # the producer's work is done before the library reads
+            ep, np_, where = ev.data_ptr(), nd.data_ptr(), 2
+        else:
+            self.events = _lib.f64(host_array(events, np.float64))
+            self.nodes = np.ascontiguousarray(host_array(nodes, np.int64))
+            if len(self.events) != len(self.nodes):
+                raise ValueError("events and nodes must have the same length")
+            self.M, self.build = len(self.events), build
+            ep, np_, where = self.events.ctypes.data, self.nodes.ctypes.data, 1 if build == "device" else 0
+        _lib.check(lib.nhp_cont_dataset_create_trials(ctx.h, ep, np_, self.M, nnodes, _lib.iptr(f), _lib.dptr(o), len(f) - 1,
+                                                      self.Δtmax, where, C.byref(h)), ctx.h)
+        self.h = h
+        self._fin = weakref.finalize(self, _lib.lib().nhp_cont_dataset_destroy, h)
+
+    def trials(self):
+        """(event_offsets [R + 1], time_offsets [R + 1], first_positive [R]) of the dataset (nhp_cont_dataset_get_trials);
+        one recording is one trial."""
+        n = C.c_int32()
+        lib = _lib.lib()
+        _lib.check(lib.nhp_cont_dataset_get_trials(self.h, C.byref(n), None, None, None), self.ctx.h)
+        f, o, g = np.empty(n.value + 1, dtype=np.int64), np.empty(n.value + 1), np.empty(n.value, dtype=np.int64)
+        _lib.check(lib.nhp_cont_dataset_get_trials(self.h, C.byref(n), _lib.iptr(f), _lib.dptr(o), _lib.iptr(g)), self.ctx.h)
+        return f, o, g
+
+    @property
+    def ntrials(self):
+        n = C.c_int32()
+        _lib.check(_lib.lib().nhp_cont_dataset_get_trials(self.h, C.byref(n), None, None, None), self.ctx.h)
+        return n.value
+
+    def trial_events(self, r):
+        """(first, end): the events [first, end) of trial r."""
+        f = self.trials()[0]
+        return int(f[r]), int(f[r + 1])
+
+    def trial_interval(self, r):
+        """(start, end) of trial r on the stacked clock."""
+        o = self.trials()[1]
+        return float(o[r]), float(o[r + 1])
 
     def __len__(self):
         return self.M
@@ -247,12 +418,18 @@ def device_dataset(process, data, ctx=None, build="host"):
     if isinstance(data, DeviceDataset):
         return data
     ctx = ctx or _lib.default_context()
-    events, nodes, duration = data
+    if isinstance(process.baseline, LogGaussianCoxProcess) and ntrials_of(data) > 1:
+        raise NotImplementedError("a LogGaussianCoxProcess baseline is not available on several trials: its grid spans one recording")
     N, Δtmax = process.ndims(), float(process.impulses.Δtmax)
+    if _is_trial_list(data):            # stacked for this call and not kept (as_data): the list may change between calls
+        return DeviceDataset(ctx, as_data(data), N, Δtmax, build=build)
+    events, nodes, duration = data
+    trials = isinstance(data, StackedEvents)
+    offsets = (data.event_offsets.tobytes(), data.time_offsets.tobytes()) if trials else None
     if _on_device(events) or _on_device(nodes):
         # (data_ptr, numel, version): an in-place refill of the tensors bumps their version and so builds again
         key = ("tensor", events.data_ptr(), events.numel(), events._version, nodes.data_ptr(), nodes.numel(), nodes._version,
-               float(duration), Δtmax, N, id(ctx))
+               float(duration), Δtmax, N, id(ctx), offsets)
         hit = _ds_cache.get(key)
         if hit is not None and hit[1]() is events and hit[2]() is nodes:
             return hit[0]
@@ -261,7 +438,7 @@ def device_dataset(process, data, ctx=None, build="host"):
             _ds_cache.clear()
         _ds_cache[key] = (ds, weakref.ref(events), weakref.ref(nodes))
         return ds
-    key = (id(events), id(nodes), len(events), float(duration), Δtmax, N, id(ctx), build)
+    key = (id(events), id(nodes), len(events), float(duration), Δtmax, N, id(ctx), build, offsets)
     hit = _ds_cache.get(key)
     # the arrays may have been refilled in place since the upload (a preallocated buffer reused for the next dataset):
     # a cheap content fingerprint decides, not the identity alone
@@ -371,6 +548,9 @@ def total_intensity(process, data, ctx=None):
 def intensity(process, data, times, ctx=None):
     """intensity(process, data, times) -> len(times) x N; a scalar time gives a length-N vector
     -- src/continuous.jl:76-96."""
+    if ntrials_of(data) > 1:            # (before a context is made or anything is stacked or uploaded)
+        raise NotImplementedError("intensity at query times is not available on several trials (a stacked query time names "
+                                  "no trial): evaluate the trial alone")
     ctx = ctx or _lib.default_context()
     scalar = np.isscalar(times)
     q = _lib.f64(np.atleast_1d(times))
@@ -499,6 +679,9 @@ def forecast(process, data, horizon, nsamples=1000, seed=0, *, return_paths=Fals
         raise NotImplementedError("forecast: not available with a LogGaussianCoxProcess baseline (the grid ends where the data end)")
     if isinstance(data, ShardedDataset):
         raise NotImplementedError("forecast: not available on a column shard (sharded.ShardedDataset)")
+    if ntrials_of(data) > 1:            # (before a context is made or anything is stacked or uploaded)
+        raise NotImplementedError("forecast is not available on several trials: a forecast continues one recording, pass the "
+                                  "trial to continue")
     horizon, S, max_events = float(horizon), int(nsamples), int(max_events)
     if S != nsamples or S < 1:
         raise ValueError(f"nsamples = {nsamples} must be a positive integer")
@@ -582,6 +765,7 @@ def time_rescaling_test(process, data, ctx=None, model=None, device=None, residu
     pooled (TimeRescalingTest).  device (default: where the events are) sorts with torch on the GPU instead of numpy on the
     host; `residuals` reuses the result of an earlier compensator() call."""
     _continuous_only(process, "time_rescaling_test")
+    data = as_data(data)
     events, nodes = data[0], data[1]
     if device is None:
         device = _on_device(events)

@@ -159,12 +159,49 @@ __device__ __forceinline__ double comp_prefix(const double *__restrict__ D, cons
     return G[(size_t)(j / COMP_GROUP) * N + c] + D[(size_t)j * N + c];
 }
 
+// ---- several trials ---------------------------------------------------------------------------------------
+// Λ^{(r)} is the compensator of trial r alone, from the trial's start: base at the local time t - o_r, saturated masses and
+// window terms over the trial's own events [f_r, ...).  The stacked prefix S_c(j) and its scans stay as they are; the
+// saturated mass of trial r before ws is S_c(ws) - S_c(f_r), with S_c(f_r) made once per call for every (trial, column):
+// Sf[r][c] = S_c at the start of f_r's chunk + (the chunk's events before f_r, added up from 0 in index order).  Where f_r lies
+// at or after the start of ws's chunk the gather simply starts at f_r and no prefix is read (no subtraction, no extra error).
+// Both prefixes are sums of non-negative terms; with d(.) the prefix depth of tests/compensator_exact_ref.py and P_c(j) the
+// stacked mass before j the subtraction adds at most 2^-53·((d(ws) + 1)·P_c(ws) + d(f_r)·P_c(f_r)) to a value's error:
+// absolute in the STACKED mass, so a late trial of a long stack is known less well, relative to its own Λ, than an early one.
+struct comp_trials {
+    const int32_t *f;      // [R + 1] event offsets
+    const double *o;       // [R + 1] time offsets
+    const double *Sf;      // [R][N] S_c(f_r); null: no saturated part
+    int32_t R;
+};
+
+// the trial of event i: the last r in [0, R) with f[r] <= i
+__device__ __forceinline__ int comp_trial_of(const comp_trials &tr, int i)
+{
+    int lo = 0, hi = tr.R;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (tr.f[mid] <= i) lo = mid; else hi = mid; }
+    return lo;
+}
+
+__global__ __launch_bounds__(COMP_COLS) void k_comp_trial_prefix(const int32_t *__restrict__ nodes, const int32_t *__restrict__ trial_f, int N,
+                                                                 const double *__restrict__ Vt, const double *__restrict__ D,
+                                                                 const double *__restrict__ G, double *__restrict__ Sf)
+{
+    const int c = blockIdx.y * COMP_COLS + threadIdx.x;
+    if (c >= N) return;
+    const int r = blockIdx.x, fr = trial_f[r], j = fr / COMP_CHUNK;
+    double acc = 0.0;
+    for (int i = j * COMP_CHUNK; i < fr; ++i) acc += Vt[(size_t)nodes[i] * N + c];
+    Sf[(size_t)r * N + c] = comp_prefix(D, G, N, j, c) + acc;
+}
+
 // at_b[k] (bucket order) and at_t[idx] (time order, nullable) <- Λ_{n_k}(t_k).  D = nullptr: no saturated part (Δtmax = ∞).
-template <int IMP>
+// TR: a dataset of several trials (above); the one-recording call instantiates the kernel without it.
+template <int IMP, bool TR>
 __global__ __launch_bounds__(NHP_BLOCK) void k_comp_events(nhp_cont_args a, const double *__restrict__ WA, const double *__restrict__ Vc,
                                                            const double *__restrict__ D, const double *__restrict__ G,
                                                            const double *__restrict__ cum, double *__restrict__ at_b,
-                                                           double *__restrict__ at_t)
+                                                           double *__restrict__ at_t, comp_trials tr)
 {
     extern __shared__ double comp_lds[];
     const nhp_item it = a.items[blockIdx.x];
@@ -186,7 +223,17 @@ __global__ __launch_bounds__(NHP_BLOCK) void k_comp_events(nhp_cont_args a, cons
         nhp_child ch;
         ch.t = 0.0; ch.first = 0; ch.idx = 0;
         if (valid) ch = a.child[k];
-        const int i0 = D ? ch.first / COMP_CHUNK * COMP_CHUNK : ch.first;
+        int i0 = D ? ch.first / COMP_CHUNK * COMP_CHUNK : ch.first;
+        int r = 0;
+        bool own = false;                                               // the gather starts at the trial's first event: no prefix
+        double t0 = 0.0;
+        if (TR) {
+            r = comp_trial_of(tr, ch.idx);
+            const int fr = tr.f[r];
+            t0 = tr.o[r];
+            own = fr >= i0;
+            if (own) i0 = fr;
+        }
         double acc = 0.0;
         // two loops, so that the lanes of a wave are all gathering or all evaluating H
         for (int i = i0 + sub; i < ch.first; i += COMP_LANES) acc += s_v[a.nodes[i]];
@@ -199,8 +246,10 @@ __global__ __launch_bounds__(NHP_BLOCK) void k_comp_events(nhp_cont_args a, cons
         }
         for (int off = COMP_LANES / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
         if (valid && sub == 0) {
-            if (D) acc = comp_prefix(D, G, N, ch.first / COMP_CHUNK, c) + acc;
-            const double v = comp_base(a, cum, c, ch.t) + acc;
+            if (TR) {
+                if (D && !own) acc = (comp_prefix(D, G, N, ch.first / COMP_CHUNK, c) - tr.Sf[(size_t)r * N + c]) + acc;
+            } else if (D) acc = comp_prefix(D, G, N, ch.first / COMP_CHUNK, c) + acc;
+            const double v = comp_base(a, cum, c, TR ? ch.t - t0 : ch.t) + acc;
             at_b[k] = v;
             if (at_t) at_t[ch.idx] = v;
         }
@@ -215,6 +264,58 @@ __global__ __launch_bounds__(256) void k_comp_residuals(nhp_cont_args a, const d
     const nhp_child ch = a.child[k];
     const int c = a.nodes[ch.idx];
     res[ch.idx] = k == a.boff[c] ? at_b[k] : at_b[k] - at_b[k - 1];
+}
+
+// several trials: a node's first event INSIDE ITS TRIAL keeps Λ (its predecessor in the bucket belongs to an earlier trial)
+__global__ __launch_bounds__(256) void k_comp_residuals_trials(nhp_cont_args a, const double *__restrict__ at_b, double *__restrict__ res,
+                                                               comp_trials tr)
+{
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= a.M) return;
+    const nhp_child ch = a.child[k];
+    const int c = a.nodes[ch.idx];
+    const bool head = k == a.boff[c] || a.child[k - 1].idx < tr.f[comp_trial_of(tr, ch.idx)];
+    res[ch.idx] = head ? at_b[k] : at_b[k] - at_b[k - 1];
+}
+
+// several trials: part[r][c] = Λ_c^{(r)}(T_r), one workgroup per (trial, node); k_comp_total_sum adds the trials up in order
+template <int IMP>
+__global__ __launch_bounds__(NHP_BLOCK) void k_comp_total_trials(nhp_cont_args a, const double *__restrict__ WA, const double *__restrict__ Vc,
+                                                                 const double *__restrict__ D, const double *__restrict__ G,
+                                                                 const double *__restrict__ cum, comp_trials tr, double *__restrict__ part)
+{
+    __shared__ double red[NHP_WAVES];
+    const int N = a.N, r = blockIdx.x, c = blockIdx.y;
+    const int fb = tr.f[r], fe = tr.f[r + 1];
+    const double t0 = tr.o[r], T = tr.o[r + 1], thr = T - a.dt_max;
+    int lo = fb, hi = fe;                                                // the trial's first event with t_i > T - Δtmax
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (a.times[mid] > thr) hi = mid; else lo = mid + 1; }
+    const int jT = lo, cs = D ? jT / COMP_CHUNK * COMP_CHUNK : jT;
+    const bool own = fb >= cs;
+    double acc = 0.0;
+    for (int i = (own ? fb : cs) + (int)threadIdx.x; i < fe; i += NHP_BLOCK) {
+        const nhp_event e = a.ev[i];
+        const size_t k = (size_t)e.node + (size_t)c * N;
+        if (i < jT) acc += Vc[k];
+        else if (e.t < T) {
+            const double w = WA[k];
+            if (w != 0.0) acc += w * comp_H<IMP>(a.p1[k], IMP == NHP_IMPULSE_LOGITNORMAL ? __builtin_sqrt(a.p2[k]) : 0.0, T - e.t, a.dt_max);
+        }
+    }
+    acc = nhp_block_sum(acc, red);
+    if (threadIdx.x == 0) {
+        if (D && !own) acc = (comp_prefix(D, G, N, jT / COMP_CHUNK, c) - tr.Sf[(size_t)r * N + c]) + acc;
+        part[(size_t)r * N + c] = comp_base(a, cum, c, T - t0) + acc;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_comp_total_sum(const double *__restrict__ part, int R, int N, double *__restrict__ total)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= N) return;
+    double run = 0.0;
+    for (int r = 0; r < R; ++r) run += part[(size_t)r * N + c];
+    total[c] = run;
 }
 
 template <int IMP>
@@ -270,11 +371,13 @@ extern "C" nhp_status nhp_cont_compensator(nhp_ctx *ctx, const nhp_cont_dataset 
     const size_t rows = finite ? M / COMP_CHUNK + 1 : 0, groups = (rows + COMP_GROUP - 1) / COMP_GROUP;
     const size_t n_cum = m->baseline_kind == NHP_BASELINE_LGCP ? N * (size_t)m->grid_n : 0;
     const bool host_out = !output_on_device;
-    size_t need = 3 * NN + rows * N + groups * N + n_cum + (events ? M : 0);
+    const bool trials = nhp_multi_trial(ds);
+    const size_t R = trials ? (size_t)ds->n_trials : 0;
+    size_t need = 3 * NN + rows * N + groups * N + n_cum + (events ? M : 0) + 2 * R * N;
     if (host_out) need += (at_events ? M : 0) + (residuals ? M : 0) + (total ? N : 0);
     NHP_TRY(nhp_ctx_reserve_scratch(ctx, 8 * need + 64));
     double *WA = (double *)ctx->d_scratch, *Vc = WA + NN, *Vt = Vc + NN, *D = Vt + NN, *G = D + rows * N, *cum = G + groups * N;
-    double *at_b = cum + n_cum, *next = at_b + (events ? M : 0);
+    double *at_b = cum + n_cum, *Sf = at_b + (events ? M : 0), *part = Sf + R * N, *next = part + R * N;
     double *o_at = at_events, *o_res = residuals, *o_tot = total;
     if (host_out) {
         if (at_events) { o_at = next; next += M; }
@@ -294,22 +397,34 @@ extern "C" nhp_status nhp_cont_compensator(nhp_ctx *ctx, const nhp_cont_dataset 
         hipLaunchKernelGGL(k_comp_super_scan, dim3(ncol), dim3(COMP_COLS), 0, st, G, (int64_t)groups, (int)N);
     }
     NHP_HIP(ctx, hipGetLastError());
-    if (events) {
-        if (ln) {
-            if (lds > 64 * 1024)
-                NHP_HIP(ctx, hipFuncSetAttribute((const void *)k_comp_events<NHP_IMPULSE_LOGITNORMAL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_comp_events<NHP_IMPULSE_LOGITNORMAL>, dim3((unsigned)ds->n_items), dim3(NHP_BLOCK), lds, st, a, WA, Vc, D, G,
-                               cum, at_b, at_events ? o_at : nullptr);
-        } else {
-            if (lds > 64 * 1024)
-                NHP_HIP(ctx, hipFuncSetAttribute((const void *)k_comp_events<NHP_IMPULSE_EXPONENTIAL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_comp_events<NHP_IMPULSE_EXPONENTIAL>, dim3((unsigned)ds->n_items), dim3(NHP_BLOCK), lds, st, a, WA, Vc, D, G,
-                               cum, at_b, at_events ? o_at : nullptr);
-        }
-        if (residuals) hipLaunchKernelGGL(k_comp_residuals, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, a, at_b, o_res);
+    const comp_trials tr = trials ? comp_trials{ds->d_trial_f, ds->d_trial_o, finite ? Sf : nullptr, ds->n_trials} : comp_trials{};
+    if (trials && finite) {
+        hipLaunchKernelGGL(k_comp_trial_prefix, dim3((unsigned)R, ncol), dim3(COMP_COLS), 0, st, ds->d_nodes, ds->d_trial_f, (int)N, Vt, D, G, Sf);
         NHP_HIP(ctx, hipGetLastError());
     }
-    if (total) {
+    if (events) {
+#define COMP_EVENTS(IMP, TR)                                                                                                        \
+        do {                                                                                                                       \
+            if (lds > 64 * 1024)                                                                                                   \
+                NHP_HIP(ctx, hipFuncSetAttribute((const void *)k_comp_events<IMP, TR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            hipLaunchKernelGGL((k_comp_events<IMP, TR>), dim3((unsigned)ds->n_items), dim3(NHP_BLOCK), lds, st, a, WA, Vc, D, G, cum, at_b, \
+                               at_events ? o_at : nullptr, tr);                                                                    \
+        } while (0)
+        if (trials && ln) COMP_EVENTS(NHP_IMPULSE_LOGITNORMAL, true);
+        else if (trials) COMP_EVENTS(NHP_IMPULSE_EXPONENTIAL, true);
+        else if (ln) COMP_EVENTS(NHP_IMPULSE_LOGITNORMAL, false);
+        else COMP_EVENTS(NHP_IMPULSE_EXPONENTIAL, false);
+#undef COMP_EVENTS
+        if (residuals && trials) hipLaunchKernelGGL(k_comp_residuals_trials, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, a, at_b, o_res, tr);
+        else if (residuals) hipLaunchKernelGGL(k_comp_residuals, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, a, at_b, o_res);
+        NHP_HIP(ctx, hipGetLastError());
+    }
+    if (total && trials) {
+        if (ln) hipLaunchKernelGGL(k_comp_total_trials<NHP_IMPULSE_LOGITNORMAL>, dim3((unsigned)R, (unsigned)N), dim3(NHP_BLOCK), 0, st, a, WA, Vc, D, G, cum, tr, part);
+        else hipLaunchKernelGGL(k_comp_total_trials<NHP_IMPULSE_EXPONENTIAL>, dim3((unsigned)R, (unsigned)N), dim3(NHP_BLOCK), 0, st, a, WA, Vc, D, G, cum, tr, part);
+        hipLaunchKernelGGL(k_comp_total_sum, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, part, (int)R, (int)N, o_tot);
+        NHP_HIP(ctx, hipGetLastError());
+    } else if (total) {
         if (ln) hipLaunchKernelGGL(k_comp_total<NHP_IMPULSE_LOGITNORMAL>, dim3((unsigned)N), dim3(NHP_BLOCK), 0, st, a, WA, Vc, D, G, cum, o_tot);
         else hipLaunchKernelGGL(k_comp_total<NHP_IMPULSE_EXPONENTIAL>, dim3((unsigned)N), dim3(NHP_BLOCK), 0, st, a, WA, Vc, D, G, cum, o_tot);
         NHP_HIP(ctx, hipGetLastError());

@@ -190,20 +190,122 @@ bool nhp_ev8_params(int32_t N, int64_t M, double e0, double e1, double *t0, doub
 // The log-likelihood is a sum over child nodes c of  -∫λ0_c - Σ_p cnt[p]·W[p,c] + Σ_{i: c_i = c} log λ_i  and the
 // gradient is block-separable in the same columns, so one evaluation shards over GPUs by column range: every shard
 // holds all events (they are all parents) but builds work items only for its own columns (second way).
+static nhp_status host_create(nhp_ctx *ctx, const double *events, const int64_t *nodes, int64_t M, int32_t N, double duration,
+                              double dt_max, int32_t col_begin, int32_t col_end, const int64_t *trial_f, const double *trial_o,
+                              int32_t R, nhp_cont_dataset **out);
+
 extern "C" nhp_status nhp_cont_dataset_create_columns(nhp_ctx *ctx, const double *events, const int64_t *nodes,
                                                       int64_t M, int32_t N, double duration, double dt_max,
                                                       int32_t col_begin, int32_t col_end, nhp_cont_dataset **out)
 {
+    return host_create(ctx, events, nodes, M, N, duration, dt_max, col_begin, col_end, nullptr, nullptr, 1, out);
+}
+
+// ---- independent trials -------------------------------------------------------------------------------
+
+static nhp_status nhp_cont_trials_check_tables(nhp_ctx *ctx, int64_t M, const int64_t *trial_f, const double *trial_o, int32_t R)
+{
+    if (R < 1 || !trial_f || !trial_o) { nhp_set_error(ctx, "trials: n_trials must be >= 1 and both offset tables given"); return NHP_EINVAL; }
+    if (trial_f[0] != 0) { nhp_set_error(ctx, "trials: trial_event_offsets[0] = %lld must be 0", (long long)trial_f[0]); return NHP_EINVAL; }
+    if (!(trial_o[0] == 0.0)) { nhp_set_error(ctx, "trials: trial_time_offsets[0] = %g must be 0", trial_o[0]); return NHP_EDOMAIN; }
+    for (int32_t r = 0; r < R; ++r) {
+        if (trial_f[r + 1] < trial_f[r]) {
+            nhp_set_error(ctx, "trials: trial_event_offsets[%d] = %lld is below trial_event_offsets[%d] = %lld", r + 1,
+                          (long long)trial_f[r + 1], r, (long long)trial_f[r]);
+            return NHP_EINVAL;
+        }
+        if (!(trial_o[r + 1] > trial_o[r]) || !std::isfinite(trial_o[r + 1])) {
+            nhp_set_error(ctx, "trials: trial_time_offsets[%d] = %g must be finite and above trial_time_offsets[%d] = %g", r + 1,
+                          trial_o[r + 1], r, trial_o[r]);
+            return NHP_EDOMAIN;
+        }
+    }
+    if (trial_f[R] != M) {
+        nhp_set_error(ctx, "trials: trial_event_offsets[%d] = %lld must be n_events = %lld", R, (long long)trial_f[R], (long long)M);
+        return NHP_EINVAL;
+    }
+    return NHP_OK;
+}
+
+nhp_status nhp_cont_trials_bad_event(nhp_ctx *ctx, int64_t i, int32_t r, double t, double lo, double hi)
+{
+    nhp_set_error(ctx, "trials: event %lld at %.17g lies outside trial %d = [%.17g, %.17g]", (long long)(i + 1), t, r + 1, lo, hi);
+    return NHP_EDOMAIN;
+}
+
+// the trial tables of a finished dataset: host copies, and device copies for a dataset of several trials
+nhp_status nhp_cont_trials_keep(nhp_ctx *ctx, nhp_cont_dataset *ds, const int64_t *trial_f, const double *trial_o, const int64_t *trial_g,
+                                int32_t R)
+{
+    ds->h_trial_f.assign(trial_f, trial_f + R + 1);
+    ds->h_trial_o.assign(trial_o, trial_o + R + 1);
+    ds->h_trial_g.assign(trial_g, trial_g + R);
+    ds->n_trials = R;
+    if (R < 2) return NHP_OK;
+    std::vector<int32_t> f32((size_t)R + 1), g32((size_t)R);
+    for (int32_t r = 0; r <= R; ++r) f32[(size_t)r] = (int32_t)trial_f[r];
+    for (int32_t r = 0; r < R; ++r) g32[(size_t)r] = (int32_t)trial_g[r];
+    if (!ds->d_trial_f) NHP_TRY(upload(ctx, &ds->d_trial_f, f32.data(), (size_t)R + 1));
+    if (!ds->d_trial_o) NHP_TRY(upload(ctx, &ds->d_trial_o, trial_o, (size_t)R + 1));
+    if (!ds->d_trial_g) NHP_TRY(upload(ctx, &ds->d_trial_g, g32.data(), (size_t)R));        // (the device route made all three)
+    NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));        // the host vectors go out of scope
+    return NHP_OK;
+}
+
+extern "C" nhp_status nhp_cont_dataset_get_trials(const nhp_cont_dataset *ds, int32_t *n_trials, int64_t *event_offsets,
+                                                  double *time_offsets, int64_t *first_positive)
+{
+    if (!ds || !n_trials) return NHP_EINVAL;
+    const int32_t R = ds->n_trials;
+    *n_trials = R;
+    const bool plain = ds->h_trial_f.empty();               // made by the one-recording entry points
+    for (int32_t r = 0; r <= R; ++r) {
+        if (event_offsets) event_offsets[r] = plain ? (r ? ds->M : 0) : ds->h_trial_f[(size_t)r];
+        if (time_offsets) time_offsets[r] = plain ? (r ? ds->duration : 0.0) : ds->h_trial_o[(size_t)r];
+        if (first_positive && r < R) first_positive[r] = plain ? ds->n_zero_time : ds->h_trial_g[(size_t)r];
+    }
+    return NHP_OK;
+}
+
+extern "C" nhp_status nhp_cont_dataset_create_trials(nhp_ctx *ctx, const double *events, const int64_t *nodes, int64_t M, int32_t N,
+                                                     const int64_t *trial_f, const double *trial_o, int32_t R, double dt_max,
+                                                     int32_t where, nhp_cont_dataset **out)
+{
+    if (!ctx || !out || M < 0 || N < 1 || (M > 0 && (!events || !nodes))) return NHP_EINVAL;
+    *out = nullptr;
+    if (where < 0 || where > 2) { nhp_set_error(ctx, "trials: where = %d must be 0 (host), 1 (device, host input) or 2 (device input)", where); return NHP_EINVAL; }
+    if (M >= (int64_t)1 << 31) { nhp_set_error(ctx, "n_events must be < 2^31"); return NHP_EINVAL; }
+    NHP_TRY(nhp_cont_trials_check_tables(ctx, M, trial_f, trial_o, R));
+    if (where == 0) return host_create(ctx, events, nodes, M, N, trial_o[R], dt_max, 0, N, trial_f, trial_o, R, out);
+    return nhp_cont_dataset_create_device_trials(ctx, events, nodes, M, N, trial_o[R], dt_max, where == 2, trial_f, trial_o, R, out);
+}
+
+static nhp_status host_create(nhp_ctx *ctx, const double *events, const int64_t *nodes, int64_t M, int32_t N, double duration,
+                              double dt_max, int32_t col_begin, int32_t col_end, const int64_t *trial_f, const double *trial_o,
+                              int32_t R, nhp_cont_dataset **out)
+{
     if (!ctx || !out || M < 0 || N < 1 || (M > 0 && (!events || !nodes))) return NHP_EINVAL;
     *out = nullptr;
     NHP_TRY(nhp_cont_dataset_check_args(ctx, M, N, duration, dt_max, col_begin, col_end));
-    for (int64_t i = 0; i < M; ++i) {
+    // the first failing event and, for it, the checks in this order: what the device route reports (cont_data_dev.hip)
+    auto plain_checks = [&](int64_t i) -> nhp_status {
         if (nodes[i] < 1 || nodes[i] > N) {
             nhp_set_error(ctx, "node id %lld at event %lld outside 1..%d", (long long)nodes[i], (long long)(i + 1), N);
             return NHP_EDOMAIN;
         }
         if (!(events[i] >= 0.0)) { nhp_set_error(ctx, "time must be non-negative (event %lld)", (long long)(i + 1)); return NHP_EDOMAIN; }
         if (i > 0 && events[i] < events[i - 1]) { nhp_set_error(ctx, "events must be sorted (event %lld)", (long long)(i + 1)); return NHP_EINVAL; }
+        return NHP_OK;
+    };
+    if (!trial_f) {
+        for (int64_t i = 0; i < M; ++i) NHP_TRY(plain_checks(i));
+    } else {
+        for (int32_t r = 0; r < R; ++r)
+            for (int64_t i = trial_f[r]; i < trial_f[r + 1]; ++i) {
+                NHP_TRY(plain_checks(i));
+                if (!(events[i] >= trial_o[r] && events[i] <= trial_o[r + 1]))
+                    return nhp_cont_trials_bad_event(ctx, i, r, events[i], trial_o[r], trial_o[r + 1]);
+            }
     }
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     // NHP_TIMING=1: where the host side of a dataset's creation spends its time (stderr)
@@ -233,6 +335,14 @@ extern "C" nhp_status nhp_cont_dataset_create_columns(nhp_ctx *ctx, const double
         while (f < i && !(events[f] > thr)) ++f;
         first[i] = (int32_t)f;
         pairs += i - f;
+    }
+    if (trial_f && R > 1) {                            // no window crosses a trial start (one recording: the loop above, as it was)
+        pairs = 0;
+        for (int32_t r = 0; r < R; ++r)
+            for (int64_t i = trial_f[r]; i < trial_f[r + 1]; ++i) {
+                if (first[i] < (int32_t)trial_f[r]) first[i] = (int32_t)trial_f[r];
+                pairs += i - first[i];
+            }
     }
     ds->pairs = pairs;
     lap("windows");
@@ -369,6 +479,15 @@ extern "C" nhp_status nhp_cont_dataset_create_columns(nhp_ctx *ctx, const double
     hipError_t e = hipStreamSynchronize(ctx->main());   // host vectors go out of scope below
     if (e != hipSuccess) { nhp_set_error(ctx, "upload failed: %s", hipGetErrorString(e)); nhp_cont_dataset_destroy(ds); return NHP_EHIP; }
     lap("uploads");
+    if (trial_f) {
+        std::vector<int64_t> g((size_t)R);
+        for (int32_t r = 0; r < R; ++r) {
+            int64_t i = trial_f[r];
+            while (i < trial_f[r + 1] && events[i] == trial_o[r]) ++i;
+            g[(size_t)r] = i;
+        }
+        if ((s = nhp_cont_trials_keep(ctx, ds, trial_f, trial_o, g.data(), R)) != NHP_OK) { nhp_cont_dataset_destroy(ds); return s; }
+    }
     *out = ds;
     return NHP_OK;
 }
@@ -425,6 +544,7 @@ extern "C" void nhp_cont_dataset_destroy(nhp_cont_dataset *ds)
     (void)hipFree(ds->d_boff); (void)hipFree(ds->d_items); (void)hipFree(ds->d_cnt); (void)hipFree(ds->d_pn);
     (void)hipFree(ds->d_adj_k); (void)hipFree(ds->d_adj_p); (void)hipFree(ds->d_adj_dt); (void)hipFree(ds->d_adj_lq); (void)hipFree(ds->d_adj_start); (void)hipFree(ds->d_adj_off); (void)hipFree(ds->d_adj_group); (void)hipFree(ds->d_child_cut);
     (void)hipFree(ds->d_rec_ev); (void)hipFree(ds->d_rec_poff); (void)hipFree(ds->d_rec_rank);
+    (void)hipFree(ds->d_trial_f); (void)hipFree(ds->d_trial_o); (void)hipFree(ds->d_trial_g);
     delete ds;
 }
 
@@ -639,6 +759,8 @@ nhp_status nhp_check_pair(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_co
     if (ds->N != m->N) { nhp_set_error(ctx, "dataset has %d nodes, model %d", ds->N, m->N); return NHP_ESHAPE; }
     if (!(ds->dt_max == m->dt_max)) { nhp_set_error(ctx, "dataset dt_max %g != model dt_max %g", ds->dt_max, m->dt_max); return NHP_EINVAL; }
     // LinearInterpolator throws DomainError outside its support (src/utils/interpolation.jl:29)
+    // a grid is one recording's clock: the stacked clock of several trials has no meaning for it
+    if (m->baseline_kind == NHP_BASELINE_LGCP) NHP_ONE_RECORDING(ctx, ds, "LogGaussianCoxProcess baseline", "its grid spans one recording");
     if (m->baseline_kind == NHP_BASELINE_LGCP && ds->M > 0 && ds->t_last > m->grid_end) {
         nhp_set_error(ctx, "Value is outside interpolation support (0, %g)", m->grid_end);
         return NHP_EDOMAIN;

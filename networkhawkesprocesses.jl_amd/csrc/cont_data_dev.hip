@@ -40,10 +40,15 @@ __global__ void k_dd_init(dd_scal *sc, int64_t M)
 
 // validation flags, the window start of every event (the host's look-back pointer as a binary search: on sorted times
 // `events[f] > t_i - dt_max` is false then true over f), 0-based nodes (clamped into range, so that nothing below
-// indexes outside its arrays before the validation result is looked at), and the per-event reductions
+// indexes outside its arrays before the validation result is looked at), and the per-event reductions.
+// TR (a dataset of several trials; the one-recording build instantiates the kernel without it): the event's
+// trial r = the last one starting at or before it (trial_f: R + 1 event offsets, checked on the host: 0 .. M, non-decreasing),
+// the event has to lie inside [trial_o[r], trial_o[r + 1]] and its window search starts at trial_f[r].
+template <bool TR>
 __global__ void __launch_bounds__(DD_BLOCK) k_dd_events(const double *__restrict__ t, const int64_t *__restrict__ nodes, int64_t M,
                                                         int32_t N, double dt_max, uint32_t *__restrict__ node32,
-                                                        int32_t *__restrict__ first, dd_scal *__restrict__ sc)
+                                                        int32_t *__restrict__ first, dd_scal *__restrict__ sc,
+                                                        const int32_t *__restrict__ trial_f, const double *__restrict__ trial_o, int32_t R)
 {
     const int64_t i = (int64_t)blockIdx.x * DD_BLOCK + threadIdx.x;
     int bad = INT_MAX, maxw = 0, nz = INT_MAX;
@@ -51,11 +56,18 @@ __global__ void __launch_bounds__(DD_BLOCK) k_dd_events(const double *__restrict
         const double ti = t[i];
         const int64_t nd = nodes[i];
         const double tp = i > 0 ? t[i - 1] : ti;
-        const bool fails = (nd < 1) | (nd > N) | !(ti >= 0.0) | (ti < tp);      // (no short circuit: one select)
+        bool fails = (nd < 1) | (nd > N) | !(ti >= 0.0) | (ti < tp);            // (no short circuit: one select)
+        int32_t fr = 0;
+        if (TR) {
+            int32_t a = 0, b = R;                                               // last r in [0, R) with trial_f[r] <= i
+            while (b - a > 1) { const int32_t mid = (a + b) >> 1; if ((int64_t)trial_f[mid] <= i) a = mid; else b = mid; }
+            fr = trial_f[a];
+            fails |= !((ti >= trial_o[a]) & (ti <= trial_o[a + 1]));
+        }
         bad = fails ? (int)i : INT_MAX;
         node32[i] = (uint32_t)(nd < 1 ? 0 : (nd > N ? N - 1 : nd - 1));
         const double thr = ti - dt_max;
-        int32_t lo = 0, hi = (int32_t)i;
+        int32_t lo = fr, hi = (int32_t)i;
         while (lo < hi) {
             const int32_t mid = (lo + hi) >> 1;
             if (t[mid] > thr) hi = mid; else lo = mid + 1;
@@ -76,6 +88,18 @@ __global__ void __launch_bounds__(DD_BLOCK) k_dd_events(const double *__restrict
         if (maxw) atomicMax(&sc->max_window, maxw);
         if (nz != INT_MAX) atomicMin(&sc->n_zero, nz);
     }
+}
+
+// trial_g[r] = the first index in [trial_f[r], trial_f[r + 1]] whose time is above trial_o[r] (sorted times inside the trial)
+__global__ void k_dd_trial_g(const double *__restrict__ t, const int32_t *__restrict__ trial_f, const double *__restrict__ trial_o,
+                             int32_t R, int32_t *__restrict__ trial_g)
+{
+    const int32_t r = (int32_t)(blockIdx.x * DD_BLOCK + threadIdx.x);
+    if (r >= R) return;
+    const double o = trial_o[r];
+    int32_t lo = trial_f[r], hi = trial_f[r + 1];
+    while (lo < hi) { const int32_t mid = (lo + hi) >> 1; if (t[mid] > o) hi = mid; else lo = mid + 1; }
+    trial_g[r] = lo;
 }
 
 // child records in bucket order and their window lengths
@@ -189,7 +213,8 @@ template <typename T>
 static hipError_t dd_alloc(T **p, int64_t n) { return hipMalloc((void **)p, sizeof(T) * (size_t)std::max<int64_t>(n, 1)); }
 
 static nhp_status dd_create(nhp_ctx *ctx, const double *events, const int64_t *nodes, int64_t M, int32_t N, double dt_max,
-                            bool on_device, nhp_cont_dataset *ds)
+                            bool on_device, nhp_cont_dataset *ds, const int64_t *trial_f = nullptr, const double *trial_o = nullptr,
+                            int32_t R = 1)
 {
     static const bool timing = getenv("NHP_TIMING") && atoi(getenv("NHP_TIMING")) != 0;
     auto t_last = std::chrono::steady_clock::now();
@@ -231,7 +256,28 @@ static nhp_status dd_create(nhp_ctx *ctx, const double *events, const int64_t *n
     lap("allocation + upload (enqueued)");
 
     k_dd_init<<<1, 1, 0, st>>>(d_sc, M);
-    if (M > 0) k_dd_events<<<gM, DD_BLOCK, 0, st>>>(ds->d_times, d_in_nodes, M, N, dt_max, (uint32_t *)ds->d_nodes, d_first, d_sc);
+    const bool trials = trial_f != nullptr;       // (one trial too: its events are held to [0, T])
+    std::vector<int32_t> f32;
+    if (trials) {                             // the tables first: the per-event pass reads them
+        f32.resize((size_t)R + 1);
+        for (int32_t r = 0; r <= R; ++r) f32[(size_t)r] = (int32_t)trial_f[r];
+        NHP_HIP(ctx, dd_alloc(&ds->d_trial_f, (int64_t)R + 1));
+        NHP_HIP(ctx, dd_alloc(&ds->d_trial_o, (int64_t)R + 1));
+        NHP_HIP(ctx, dd_alloc(&ds->d_trial_g, (int64_t)R));
+        NHP_HIP(ctx, hipMemcpyAsync(ds->d_trial_f, f32.data(), sizeof(int32_t) * ((size_t)R + 1), hipMemcpyHostToDevice, st));
+        NHP_HIP(ctx, hipMemcpyAsync(ds->d_trial_o, trial_o, sizeof(double) * ((size_t)R + 1), hipMemcpyHostToDevice, st));
+    }
+    if (M > 0 && trials)
+        k_dd_events<true><<<gM, DD_BLOCK, 0, st>>>(ds->d_times, d_in_nodes, M, N, dt_max, (uint32_t *)ds->d_nodes, d_first, d_sc, ds->d_trial_f,
+                                                   ds->d_trial_o, R);
+    else if (M > 0)
+        k_dd_events<false><<<gM, DD_BLOCK, 0, st>>>(ds->d_times, d_in_nodes, M, N, dt_max, (uint32_t *)ds->d_nodes, d_first, d_sc, nullptr,
+                                                    nullptr, 1);
+    std::vector<int32_t> g32(trials ? (size_t)R : 0);
+    if (trials) {
+        k_dd_trial_g<<<dd_grid(R, DD_BLOCK), DD_BLOCK, 0, st>>>(ds->d_times, ds->d_trial_f, ds->d_trial_o, R, ds->d_trial_g);
+        NHP_HIP(ctx, hipMemcpyAsync(g32.data(), ds->d_trial_g, sizeof(int32_t) * (size_t)R, hipMemcpyDeviceToHost, st));
+    }
     // node bucketing: stable radix sort of the 0-based nodes (d_nodes is kept: the sort works on a copy)
     uint32_t *k_sorted = nullptr;
     int32_t *perm = nullptr;
@@ -267,6 +313,12 @@ static nhp_status dd_create(nhp_ctx *ctx, const double *events, const int64_t *n
             return NHP_EDOMAIN;
         }
         if (!(ti >= 0.0)) { nhp_set_error(ctx, "time must be non-negative (event %lld)", (long long)(i + 1)); return NHP_EDOMAIN; }
+        if (i > 0 && ti < tp) { nhp_set_error(ctx, "events must be sorted (event %lld)", (long long)(i + 1)); return NHP_EINVAL; }
+        if (trials) {
+            int32_t r = 0;
+            while (r + 1 < R && trial_f[r + 1] <= i) ++r;
+            return nhp_cont_trials_bad_event(ctx, i, r, ti, trial_o[r], trial_o[r + 1]);
+        }
         nhp_set_error(ctx, "events must be sorted (event %lld)", (long long)(i + 1));
         return NHP_EINVAL;
     }
@@ -376,6 +428,30 @@ static nhp_status dd_create(nhp_ctx *ctx, const double *events, const int64_t *n
         fprintf(stderr, "[nhp dataset, device] child slices: %d slices, %lld rows = %.3f records per pair\n", ds->n_slices,
                 (long long)sc.rows, (double)sc.rows * 64.0 / (double)ds->pairs);
     }
+    if (trial_f) {
+        std::vector<int64_t> g((size_t)R);
+        for (int32_t r = 0; r < R; ++r) g[(size_t)r] = g32[(size_t)r];
+        NHP_TRY(nhp_cont_trials_keep(ctx, ds, trial_f, trial_o, g.data(), R));
+    }
+    return NHP_OK;
+}
+
+nhp_status nhp_cont_dataset_create_device_trials(nhp_ctx *ctx, const double *events, const int64_t *nodes, int64_t M, int32_t N,
+                                                 double duration, double dt_max, bool input_on_device, const int64_t *trial_f,
+                                                 const double *trial_o, int32_t R, nhp_cont_dataset **out)
+{
+    NHP_TRY(nhp_cont_dataset_check_args(ctx, M, N, duration, dt_max, 0, N));
+    NHP_HIP(ctx, hipSetDevice(ctx->device));
+    nhp_cont_dataset *ds = new nhp_cont_dataset();
+    ds->uid = nhp_new_dataset_uid();
+    ds->ctx = ctx; ds->M = M; ds->N = N; ds->duration = duration; ds->dt_max = dt_max;
+    ds->col_begin = 0; ds->col_end = N;
+    const nhp_status s = dd_create(ctx, events, nodes, M, N, dt_max, input_on_device, ds, trial_f, trial_o, R);
+    if (s != NHP_OK) {
+        nhp_cont_dataset_destroy(ds);
+        return s;
+    }
+    *out = ds;
     return NHP_OK;
 }
 

@@ -357,6 +357,7 @@ extern "C" nhp_status nhp_cont_forecast(nhp_ctx *ctx, const nhp_cont_dataset *ds
         return NHP_ENOTIMPL;
     }
     NHP_WHOLE_DATASET(ctx, ds, "forecast");
+    NHP_ONE_RECORDING(ctx, ds, "forecast", "a forecast continues one recording: pass the trial to continue");
     const auto t_begin = std::chrono::steady_clock::now();
     const int32_t N = m->N;
     const int64_t S = nsamples, SN = S * N, cap = max_events, M = ds->M;

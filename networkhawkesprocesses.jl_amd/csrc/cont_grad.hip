@@ -312,7 +312,7 @@ nhp_status nhp_grad_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_
     // gradient on the other window starts, with the recursion's unmasked integral
     const nhp_child *child_cut = nullptr;
     int cut_group = 0;
-    if ((flags & NHP_LL_RECURSIVE) && !(flags & NHP_LL_FULL_RECURSION) && exp_imp)
+    if ((flags & NHP_LL_RECURSIVE) && (!(flags & NHP_LL_FULL_RECURSION) || nhp_multi_trial(ds)) && exp_imp)
         NHP_TRY(nhp_recursive_window(ctx, ds, m, &child_cut, &cut_group, 1.2, true));
     if ((flags & NHP_LL_RECURSIVE) && exp_imp && !child_cut) {
         // two passes of the wave-partitioned recursion: log-likelihood + 1/λ of every child, then the gradient sums

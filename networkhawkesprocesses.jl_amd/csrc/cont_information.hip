@@ -428,7 +428,7 @@ nhp_status info_prepare(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont
     *child = ds->d_child;
     *group = ds->group;
     if ((flags & NHP_LL_RECURSIVE) && m->impulse_kind == NHP_IMPULSE_EXPONENTIAL) {
-        if (flags & NHP_LL_FULL_RECURSION) {
+        if ((flags & NHP_LL_FULL_RECURSION) && !nhp_multi_trial(ds)) {      // (several trials: the window sum is that recursion)
             nhp_set_error(ctx, "%s: the O(M*N) recursion forms no second derivatives (NHP_LL_FULL_RECURSION)", what);
             return NHP_ENOTIMPL;
         }

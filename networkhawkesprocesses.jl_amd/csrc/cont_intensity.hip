@@ -94,6 +94,7 @@ extern "C" nhp_status nhp_cont_intensity(nhp_ctx *ctx, const nhp_cont_dataset *d
                                          const double *times, int64_t Q, double *out)
 {
     NHP_TRY(nhp_check_pair(ctx, ds, m));
+    NHP_ONE_RECORDING(ctx, ds, "intensity at query times", "a stacked query time names no trial: evaluate the trial alone");
     if (Q < 0 || (Q > 0 && (!times || !out))) return NHP_EINVAL;
     if (Q == 0) return NHP_OK;
     for (int64_t i = 0; i < Q; ++i) {

@@ -254,6 +254,33 @@ __global__ __launch_bounds__(256) void k_rec_windows(const nhp_child *__restrict
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(pairs, mine);
 }
 
+// The same for a dataset of several trials: the start is never before trial_g[r], the trial's first event after
+// its local time 0 -- the recursion of the trial alone has no earlier parent (D9) -- and cut = +inf walks from there: the sum
+// over ALL of the trial's earlier events, which IS the recursion, exactly.  The trial of child k is the last one whose
+// first event is at or before it.
+__global__ __launch_bounds__(256) void k_rec_windows_trials(const nhp_child *__restrict__ child, const double *__restrict__ times,
+                                                            int64_t M, double cut, const int32_t *__restrict__ trial_f,
+                                                            const int32_t *__restrict__ trial_g, int32_t R,
+                                                            nhp_child *__restrict__ child_cut, unsigned long long *__restrict__ pairs)
+{
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    unsigned long long mine = 0;
+    if (k < M) {
+        nhp_child ch = child[k];
+        int32_t a = 0, b = R;                                // last r in [0, R) with trial_f[r] <= idx
+        while (b - a > 1) { const int32_t mid = (a + b) >> 1; if (trial_f[mid] <= ch.idx) a = mid; else b = mid; }
+        const double lim = ch.t - cut;
+        int lo = trial_g[a], hi = ch.idx;                    // first j in [g_r, idx] with times[j] > lim
+        if (lo > hi) lo = hi;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (times[mid] > lim) hi = mid; else lo = mid + 1; }
+        ch.first = lo;
+        child_cut[k] = ch;
+        mine = (unsigned long long)(ch.idx - lo);
+    }
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(pairs, mine);
+}
+
 // cut for this model (cached per parameter version); 0 = no usable bound, NHP_REC_EMPTY_CUT = nothing to sum at all
 #define NHP_REC_EMPTY_CUT 1e-300
 static nhp_status rec_cut_for(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, double *cut)
@@ -299,12 +326,65 @@ static nhp_status rec_cut_for(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nh
 
 static nhp_status nhp_launch_recursive_full(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, double *d_out);
 
+// Several trials: ALWAYS a child list -- the recursion kernels carry their state along the whole stacked clock,
+// across the seams, so they never run here; the window sum over all of a trial's earlier events is that recursion on the
+// trial alone.  The cut of the one-recording route shortens the windows where it is usable: its bound counts the events
+// older than `cut` before a child on the stacked clock, and a trial's own earlier events are a subset of those, at the same
+// distances, so what is dropped is bounded as before.  No usable cut (none from the parameters, the empty cut under
+// derivatives, or more than 8192 expected parents a window, where the bound's speed model stops): cut = +inf, every window
+// starts at trial_g[r], Σ_r M_r²/2 pair terms.  The cached list is keyed on the cut: a dataset is of one trial or of
+// several for its whole life, so the one-recording cache (same field, finite cuts only) never sees these.
+static nhp_status rec_window_trials(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const nhp_child **child_cut,
+                                    int *group, bool derivatives)
+{
+    if (ds->M <= 0 || m->impulse_kind != NHP_IMPULSE_EXPONENTIAL) return NHP_OK;
+    double cut = 0.0;
+    NHP_TRY(rec_cut_for(ctx, ds, m, &cut));
+    const double rate = ds->t_last > 0.0 ? (double)ds->M / ds->t_last : 0.0;
+    if (!(cut > 0.0) || (derivatives && cut == NHP_REC_EMPTY_CUT) || cut * rate > 8192.0) cut = __builtin_inf();
+    if (cut == __builtin_inf()) {
+        // the launch path works with the pair count as a double (mean window, pairs per item): exact up to 2^53
+        double uncut = 0.0;
+        for (int32_t r = 0; r < ds->n_trials; ++r) {
+            const double n = (double)(ds->h_trial_f[(size_t)r + 1] - ds->h_trial_g[(size_t)r]);
+            uncut += 0.5 * n * (n - 1.0);
+        }
+        if (uncut > 9007199254740992.0) {
+            nhp_set_error(ctx, "recursive route on %d trials: no usable cut for these parameters, and the %.0f pair terms of the "
+                               "uncut windows exceed the 2^53 the launch path counts exactly", ds->n_trials, uncut);
+            return NHP_ENOTIMPL;
+        }
+    }
+    nhp_cont_dataset *mds = const_cast<nhp_cont_dataset *>(ds);
+    if (!mds->d_child_cut && hipMalloc((void **)&mds->d_child_cut, sizeof(nhp_child) * (size_t)ds->M) != hipSuccess) {
+        nhp_set_error(ctx, "out of device memory (recursive windows)");
+        return NHP_ENOMEM;
+    }
+    if (ds->cut_cached != cut) {
+        unsigned long long *d_pairs = reinterpret_cast<unsigned long long *>(ctx->d_counter + 32 * (NHP_REC_PAIR_SLOT));
+        NHP_HIP(ctx, hipMemsetAsync(d_pairs, 0, sizeof(unsigned long long), ctx->main()));
+        hipLaunchKernelGGL(k_rec_windows_trials, dim3((unsigned)((ds->M + 255) / 256)), dim3(256), 0, ctx->main(), ds->d_child, ds->d_times,
+                           ds->M, cut, ds->d_trial_f, ds->d_trial_g, ds->n_trials, mds->d_child_cut, d_pairs);
+        NHP_HIP(ctx, hipGetLastError());
+        unsigned long long hp = 0;
+        NHP_HIP(ctx, hipMemcpyAsync(&hp, d_pairs, sizeof(hp), hipMemcpyDeviceToHost, ctx->main()));
+        NHP_HIP(ctx, hipStreamSynchronize(ctx->main()));
+        NHP_HIP(ctx, hipMemsetAsync(d_pairs, 0, sizeof(unsigned long long), ctx->main()));    // counters rest at 0
+        ds->cut_cached = cut;
+        ds->cut_pairs = (int64_t)hp;
+    }
+    *child_cut = ds->d_child_cut;
+    *group = nhp_pick_group((double)ds->cut_pairs / (double)ds->M);
+    return NHP_OK;
+}
+
 // *child_cut = the children with truncated-window starts (and *group the lanes-per-child width for them) when the
 // full-history sum may be evaluated through a window for this (data, parameters); nullptr when the recursion must run
 nhp_status nhp_recursive_window(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const nhp_child **child_cut,
                                 int *group, double recursion_cost, bool derivatives)
 {
     *child_cut = nullptr;
+    if (nhp_multi_trial(ds)) return rec_window_trials(ctx, ds, m, child_cut, group, derivatives);
     const char *sw = getenv("NHP_REC_WINDOW");             // read per call: the tests and the benchmark switch it
     const int mode = sw ? atoi(sw) : 1;                     // 0: always the recursion
     if (!mode || ds->M <= 0 || m->impulse_kind != NHP_IMPULSE_EXPONENTIAL) return NHP_OK;
@@ -363,7 +443,7 @@ nhp_status nhp_launch_recursive_flags(nhp_ctx *ctx, const nhp_cont_dataset *ds, 
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     const nhp_child *child_cut = nullptr;
     int group = 0;
-    if (!(flags & NHP_LL_FULL_RECURSION)) NHP_TRY(nhp_recursive_window(ctx, ds, m, &child_cut, &group));
+    if (!(flags & NHP_LL_FULL_RECURSION) || nhp_multi_trial(ds)) NHP_TRY(nhp_recursive_window(ctx, ds, m, &child_cut, &group));
     if (child_cut) return nhp_launch_windowed_as(ctx, ds, m, child_cut, group, 0, d_out);
     return nhp_launch_recursive_full(ctx, ds, m, d_out);
 }

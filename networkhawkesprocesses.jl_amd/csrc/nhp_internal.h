@@ -305,7 +305,26 @@ struct nhp_cont_dataset {
     std::vector<int64_t> h_slab_max;
     bool slab_done = false;             // the two vectors above have been made (nhp_dataset_slab_stats: at the recursion's first bound)
     std::vector<int64_t> h_pair_off;    // [N+1] prefix of window pairs per child node (adjacency sweep scratch)
+    // Independent trials stacked along time (nhp_cont_dataset_create_trials): trial r owns the events
+    // [trial_f[r], trial_f[r+1]) and the clock interval [trial_o[r], trial_o[r+1]]; trial_g[r] = the first index in
+    // [trial_f[r], trial_f[r+1]] whose time is not exactly trial_o[r] (the recursion's D9 per trial).  No window crosses a trial
+    // start: nhp_child::first is clipped at trial_f[r] when the dataset is made, and everything built from the windows follows.
+    // n_trials = 1 (every other entry point): one recording, no device tables; the host tables are then {0, M} / {0, duration}.
+    int32_t n_trials = 1;
+    std::vector<int64_t> h_trial_f, h_trial_g;      // [R + 1], [R]
+    std::vector<double> h_trial_o;                  // [R + 1]
+    int32_t *d_trial_f = nullptr, *d_trial_g = nullptr;
+    double *d_trial_o = nullptr;
 };
+inline bool nhp_multi_trial(const nhp_cont_dataset *ds) { return ds->n_trials > 1; }
+// the entry points that read events by time, or continue one recording, refuse a dataset of several trials
+#define NHP_ONE_RECORDING(ctx, ds, what, why)                                                                  \
+    do {                                                                                                      \
+        if (nhp_multi_trial(ds)) {                                                                            \
+            nhp_set_error(ctx, what ": not available on a dataset of %d trials (" why ")", (ds)->n_trials);    \
+            return NHP_ENOTIMPL;                                                                              \
+        }                                                                                                     \
+    } while (0)
 
 struct nhp_cont_model {
     nhp_ctx *ctx = nullptr;
@@ -597,6 +616,14 @@ void nhp_cont_partition(nhp_cont_dataset *ds, const nhp_lower_fn &lower, nhp_con
 // the argument checks before the per-event validation (same status and message on both routes)
 nhp_status nhp_cont_dataset_check_args(nhp_ctx *ctx, int64_t M, int32_t N, double duration, double dt_max, int32_t col_begin,
                                        int32_t col_end);
+// independent trials (cont_data.hip): the message of an event outside its trial's interval, the tables of a
+// finished dataset, and the device route of nhp_cont_dataset_create_trials (cont_data_dev.hip; the tables are host pointers)
+nhp_status nhp_cont_trials_bad_event(nhp_ctx *ctx, int64_t i, int32_t r, double t, double lo, double hi);
+nhp_status nhp_cont_trials_keep(nhp_ctx *ctx, nhp_cont_dataset *ds, const int64_t *trial_f, const double *trial_o, const int64_t *trial_g,
+                                int32_t R);
+nhp_status nhp_cont_dataset_create_device_trials(nhp_ctx *ctx, const double *events, const int64_t *nodes, int64_t M, int32_t N,
+                                                 double duration, double dt_max, bool input_on_device, const int64_t *trial_f,
+                                                 const double *trial_o, int32_t R, nhp_cont_dataset **out);
 // child slices with `rows` rows in all: kept (sets sl_rows, n_slices, sl_nb, sl_max_rows) or dropped (false)
 bool nhp_cont_slices_keep(nhp_cont_dataset *ds, uint64_t rows, int32_t n_slices, int32_t max_rows);
 // the 8-byte event records' origin and scale from the first and the last time (false: no 8-byte records)

@@ -15,7 +15,7 @@ from scipy.special import gammaln
 from . import _lib
 from .components import (ExponentialImpulseResponse, HomogeneousProcess, LogitNormalImpulseResponse, param_layout)
 from .continuous import (ContinuousNetworkHawkesProcess, ContinuousStandardHawkesProcess,
-                         device_dataset, loglikelihood, loglikelihood_gradient)
+                         as_data, device_dataset, loglikelihood, loglikelihood_gradient)
 from .parents import resample_parents
 
 
@@ -508,6 +508,7 @@ def resample_(process, data, rng, step=0, seed=0, ctx=None, labels_every=1, posi
 
     Parents and every sufficient statistic come from one GPU call; the conjugate draws are host
     numpy; the network process then resamples its adjacency matrix on the GPU and redraws ρ."""
+    data = as_data(data)                # (trials: stacked once; the stacked duration ΣT_r is the exposure)
     _, _, st = resample_parents(process, data, seed=seed, step=step, with_stats=True, want_parents=False, ctx=ctx)
     duration = data.duration if hasattr(data, "duration") else data[2]
     if isinstance(process.baseline, HomogeneousProcess):

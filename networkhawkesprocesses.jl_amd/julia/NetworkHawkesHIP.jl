@@ -113,6 +113,45 @@ function Dataset(ctx::Context, data, N::Integer, Δtmax::Real; columns::UnitRang
     finalizer(d -> ccall((:nhp_cont_dataset_destroy, libnhp), Cvoid, (Ptr{Cvoid},), d.h), ds)
 end
 
+# Several independent trials [(events_r, nodes_r, T_r), ...] over the same nodes as ONE dataset (DESIGN §3.26): stacked along
+# one clock, trial r on [o_r, o_r + T_r]; no look-back window crosses a trial's first event.  The shift rounds every time
+# once: a delay inside a trial changes by at most one ulp of ΣT_r.
+function stack_event_trials(trials)
+    R = length(trials)
+    f, o = zeros(Int64, R + 1), zeros(Float64, R + 1)
+    ev, nd = Float64[], Int64[]
+    for (r, (e, n, T)) in enumerate(trials)
+        (isfinite(T) && T > 0) || throw(DomainError(T, "trial $r: duration must be positive and finite"))
+        length(e) == length(n) || throw(ArgumentError("trial $r: events and nodes must have the same length"))
+        issorted(e) || throw(ArgumentError("trial $r: events must be sorted"))
+        all(t -> 0 <= t <= T, e) || throw(DomainError(T, "trial $r: events must lie in [0, $T]"))
+        append!(ev, e .+ o[r]); append!(nd, n)
+        f[r + 1], o[r + 1] = f[r] + length(e), o[r] + T
+    end
+    (events=ev, nodes=nd, duration=o[end], event_offsets=f, time_offsets=o)
+end
+function Dataset(ctx::Context, trials::AbstractVector{<:Tuple}, N::Integer, Δtmax::Real; build::Symbol=:host)
+    build in (:host, :device) || throw(ArgumentError("build must be :host or :device"))
+    s = stack_event_trials(trials)
+    r = Ref{Ptr{Cvoid}}(C_NULL)
+    ev, nd, f, o = s.events, s.nodes, s.event_offsets, s.time_offsets
+    GC.@preserve ev nd f o check(ccall((:nhp_cont_dataset_create_trials, libnhp), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Int64, Int32, Ptr{Int64}, Ptr{Float64}, Int32, Float64, Int32, Ref{Ptr{Cvoid}}),
+        ctx.h, ev, nd, length(ev), N, f, o, length(trials), Δtmax, Int32(build === :device ? 1 : 0), r), ctx.h)
+    ds = Dataset(r[])
+    finalizer(d -> ccall((:nhp_cont_dataset_destroy, libnhp), Cvoid, (Ptr{Cvoid},), d.h), ds)
+end
+# (event_offsets, time_offsets, first_positive) of a dataset; one recording is one trial
+function trial_offsets(ds::Dataset)
+    n = Ref{Int32}(0)
+    check(ccall((:nhp_cont_dataset_get_trials, libnhp), Int32, (Ptr{Cvoid}, Ref{Int32}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
+                ds.h, n, Ptr{Int64}(C_NULL), Ptr{Float64}(C_NULL), Ptr{Int64}(C_NULL)))
+    f, o, g = zeros(Int64, n[] + 1), zeros(Float64, n[] + 1), zeros(Int64, n[])
+    check(ccall((:nhp_cont_dataset_get_trials, libnhp), Int32, (Ptr{Cvoid}, Ref{Int32}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}),
+                ds.h, n, f, o, g))
+    f, o, g
+end
+
 function with_model(f, ctx::Context, p)
     desc, keep = lower(p)
     r = Ref{Ptr{Cvoid}}(C_NULL)

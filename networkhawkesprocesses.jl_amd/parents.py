@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .continuous import DeviceDataset, _continuous_only, _is_tensor, _on_device, device_dataset
+from .continuous import DeviceDataset, _continuous_only, _is_tensor, _on_device, as_data, device_dataset
 
 
 def resample_parents(process, data, u=None, seed=0, step=0, with_stats=False, want_parents=True, ctx=None):
@@ -100,7 +100,7 @@ class Cascades:
 def _event_count(data):
     if isinstance(data, DeviceDataset):
         return len(data)
-    ev = data[0]
+    ev = as_data(data)[0]
     return int(ev.numel()) if _is_tensor(ev) else len(ev)
 
 

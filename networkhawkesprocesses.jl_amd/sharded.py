@@ -94,7 +94,9 @@ class ShardedDataset:
 
     def __init__(self, process, data, ctx=None, rank=None, world=None, ranges=None, build="host"):
         """build: where the shard's pre-pass runs (continuous.DeviceDataset); torch tensors take the device route."""
-        from .continuous import DeviceDataset
+        from .continuous import DeviceDataset, StackedEvents, _is_trial_list
+        if _is_trial_list(data) or isinstance(data, StackedEvents):
+            raise NotImplementedError("ShardedDataset: several trials are not sharded over columns; pass one recording")
         r, w = _world()
         self.rank = r if rank is None else int(rank)
         self.world = w if world is None else int(world)

@@ -594,6 +594,7 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nchild = it.kend - it.kbeg;
     const int s0 = sl.item0[blockIdx.x], ns = sl.item0[blockIdx.x + 1] - s0;
+    NHP_SL_STAMP(0);
 
     struct chunk { uint32_t lo[C], hi[C]; };
     auto request = [&](chunk &q, const uint32_t row0, const int r) {
@@ -606,30 +607,84 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
             q.hi[u] = ph[u * 64 + lane];
         }
     };
+    // The head, after k_windowed_slices': the parent nodes in trips of UN·BLOCK, and inside a trip every load -- cnt once per
+    // node, then W, θ and (behind a wave-uniform branch) A of G models -- is requested before any is used: one round trip per
+    // trip instead of up to three per model and pass.  The first rows of the wave's first slice follow the first trip's requests
+    // (their addresses need the slice table only) and arrive while the columns are written to LDS.  UN = 2 for every BLOCK: two
+    // models' W, θ, A at 2 nodes a thread are 24 registers, at the single kernel's 4 nodes they would be 48 of the 64 that
+    // eight waves per SIMD leave.  The models' table pointers and λ0[m][c] are read once, with the item header: λ0 serves the
+    // integral here and the walk below.
+    constexpr int UN = 2;
+    constexpr int G = S >= 2 ? 2 : 1;                               // models per request group (S = 4: two and two)
+    const size_t c0 = (size_t)c * N;                                // column c: wave-uniform bases, the node as a 32-bit offset
+    typedef const __attribute__((address_space(1))) double *gptr;   // (global: the pinning below must not leave flat loads)
+    gptr Wc[S], Tc[S], Ac[S];
+    double lam0[S];
+#pragma unroll
+    for (int m = 0; m < S; ++m) {
+        Wc[m] = (gptr)st.W[m]; Tc[m] = (gptr)st.p1[m]; Ac[m] = (gptr)st.A[m];
+        lam0[m] = st.lambda0[m][c];
+    }
+#pragma unroll
+    for (int m = 0; m < S; ++m) asm("" : "+s"(Wc[m]), "+s"(Tc[m]), "+s"(Ac[m]));   // all of them in SGPRs before the first request
+    const double unit = __builtin_ldexp(a.dt_max, -sl.dbits);
     int j = w;
     uint32_t row0 = 0;
     int K = 0;
-    if (j < ns) { row0 = sl.row[s0 + j]; K = (int)(sl.row[s0 + j + 1] - row0); }
     chunk qa, qb;
-    request(qa, row0, 0);
-
-    const double unit = __builtin_ldexp(a.dt_max, -sl.dbits);
     double integ[S];
 #pragma unroll
-    for (int m = 0; m < S; ++m) {
-        integ[m] = 0.0;
-        for (int p = tid; p < N; p += BLOCK) {
-            const size_t k = (size_t)p + (size_t)c * N;
-            double wv = st.W[m][k];
-            if (st.A[m]) wv = st.A[m][k] * wv;                      // windowed route: the integral is masked too
-            const double th = st.p1[m][k];
-            col[(size_t)m * (N + 1) + p] = make_double2(-((th * unit) * 92.33248261689366), wv * th);
-            if (it.first) integ[m] += a.cnt[p] * wv;
+    for (int m = 0; m < S; ++m) integ[m] = 0.0;
+    for (int p0 = 0; p0 < N; p0 += UN * BLOCK) {
+        double cnt_[UN];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const int p = p0 + u * BLOCK + tid;
+            cnt_[u] = it.first ? a.cnt[(uint32_t)(p < N ? p : 0)] : 0.0;
         }
+#pragma unroll
+        for (int g = 0; g < S; g += G) {
+            double w_[G][UN], th_[G][UN], a_[G][UN];
+#pragma unroll
+            for (int mm = 0; mm < G; ++mm) {
+                const int m = g + mm;
+#pragma unroll
+                for (int u = 0; u < UN; ++u) {
+                    const int p = p0 + u * BLOCK + tid;
+                    const uint32_t k = (uint32_t)(p < N ? p : 0);
+                    w_[mm][u] = (Wc[m] + c0)[k];
+                    th_[mm][u] = (Tc[m] + c0)[k];
+                    a_[mm][u] = Ac[m] ? (Ac[m] + c0)[k] : 1.0;
+                }
+            }
+            if (p0 == 0 && g == 0) {                                 // (N >= 1 on every route that launches this kernel: the first trip always runs)
+                if (j < ns) { row0 = sl.row[s0 + j]; K = (int)(sl.row[s0 + j + 1] - row0); }
+                asm volatile("" ::: "memory");
+                request(qa, row0, 0);
+                asm volatile("" ::: "memory");
+            }
+#pragma unroll
+            for (int mm = 0; mm < G; ++mm) {
+                const int m = g + mm;
+#pragma unroll
+                for (int u = 0; u < UN; ++u) {
+                    const int p = p0 + u * BLOCK + tid;
+                    if (p < N) {
+                        double wv = w_[mm][u];
+                        if (Ac[m]) wv = a_[mm][u] * wv;                // windowed route: the integral is masked too
+                        col[(size_t)m * (N + 1) + p] = make_double2(-((th_[mm][u] * unit) * 92.33248261689366), wv * th_[mm][u]);
+                        if (it.first) integ[m] += cnt_[u] * wv;
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < S; ++m) {
         if (tid == 0) col[(size_t)m * (N + 1) + N] = make_double2(0.0, 0.0);
         if (DEFER) {
-            if (it.first) integ[m] += sl_flat_integral(st.lambda0[m][c], a.duration);
-        } else if (it.first && tid == 0) integ[m] += st.lambda0[m][c] * a.duration;
+            if (it.first) integ[m] += sl_flat_integral(lam0[m], a.duration);
+        } else if (it.first && tid == 0) integ[m] += lam0[m] * a.duration;
         if (EARLY) {
             const double wsum = nhp_wave_sum(integ[m]);
             if (lane == 0) red[16 + m * NW + w] = wsum;
@@ -637,6 +692,7 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
     }
     if (tid < 64) etab[tid] = tab_v;
     __syncthreads();
+    NHP_SL_STAMP(1);
 
     const uint32_t dmask = sl.dmask;
     const int nsh = sl.nsh;
@@ -662,10 +718,10 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
                 if (r + u < K) terms(q.lo[u], q.hi[u], acc);
         }
     };
-    double lam0[S], prod[S];
+    double prod[S];
     int pexp[S];
 #pragma unroll
-    for (int m = 0; m < S; ++m) { lam0[m] = st.lambda0[m][c]; prod[m] = 1.0; pexp[m] = 0; }
+    for (int m = 0; m < S; ++m) { prod[m] = 1.0; pexp[m] = 0; }
     int rnd = 0;                                                    // the wave's slices in snake order (nhp_slice_of)
     while (j < ns) {
         const int jn = nhp_slice_of(++rnd, w, NW);
@@ -701,6 +757,8 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
         }
         j = jn; row0 = row0n; K = Kn;
     }
+    NHP_SL_STAMP_WAVE();
+    NHP_SL_STAMP(2);
     if (DEFER) {
         // nhp_block_sum2_n's order for every model, with one pair of barriers for all: wave sums, then wave by wave
         double ws[S];
@@ -716,6 +774,7 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
             for (int m = 0; m < S; ++m) red[m * NW + w] = ws[m];
         }
         __syncthreads();
+        NHP_SL_STAMP(3);
         if (tid == 0) {
 #pragma unroll
             for (int m = 0; m < S; ++m) {
@@ -725,6 +784,7 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
                 st.out[m][2 * (size_t)blockIdx.x + 1] = sy;
             }
         }
+        NHP_SL_STAMP(4);
         return;
     }
     int *flag = reinterpret_cast<int *>(red + 32);
@@ -742,6 +802,7 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
         }
         __syncthreads();
     }
+    NHP_SL_STAMP(3);
     if (tid == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const unsigned int nb = gridDim.x, sh = blockIdx.x % NHP_SL_SHARDS;
@@ -753,6 +814,7 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
         *flag = last;
     }
     __syncthreads();
+    NHP_SL_STAMP(4);
     if (!*flag) return;
 #pragma unroll
     for (int m = 0; m < S; ++m) {

@@ -1,4 +1,5 @@
-"""Phase timeline of k_windowed_slices from a -DNHP_STAMP build (NHP_LIB=... python tools/dbg/slstamps.py): wave 0 of every
+"""Phase timeline of k_windowed_slices -- PAIR=1: of k_slices_batch<BLOCK, C, 2, DEFER>, one enqueued pair, stamped at the same
+phase boundaries -- from a -DNHP_STAMP build (NHP_LIB=... python tools/dbg/slstamps.py): wave 0 of every
 workgroup stamps s_memrealtime (100 MHz, the same clock on every XCD) at its start, after the column is staged, after its
 slices, after the block sums, after the ticket (ENQUEUE=1: after the stores of the deferred exit); EVERY wave stamps the end of its own slices, and the spread between a
 workgroup's first and last wave to finish is what the dealing of slices to waves (nhp_slice_of) is there to shrink: the early
@@ -13,7 +14,23 @@ ctx = nhp.Context(0)
 N, M = 1024, 1_000_000
 times, nodes, T = nhp.synthetic.s_metric_data(N, M, kbar=float(os.environ.get("KBAR", 8.0)))
 proc = nhp.synthetic.s_metric_process(N, M, T, "exponential", 1.0)
-if os.environ.get("ENQUEUE"):                        # the enqueue route: its last stamp is the deferred exit (NHP_DEFER_FINALIZE=0: the ticket)
+if os.environ.get("PAIR"):
+    # one pass of two, alone on the device: a single evaluation opens the streak (only inside a streak is an enqueue held) and has
+    # long ended, unjoined, when the next enqueue is held and the one after it shares its pass; the pair's 1024 workgroups stamp last
+    import time
+    ds0, model, model2 = nhp.device_dataset(proc, (times, nodes, T), ctx), proc.device_model(ctx), proc.device_model(ctx)
+    count = _lib.lib().nhp_debug_pair_launches
+    count.restype, count.argtypes = C.c_int64, [C.c_void_p]
+    for _ in range(5):
+        p0 = int(count(ctx.h))
+        _lib.check(_lib.lib().nhp_cont_loglik_enqueue(ctx.h, ds0.h, model.h, 0, 0), ctx.h)
+        time.sleep(0.005)
+        _lib.check(_lib.lib().nhp_cont_loglik_enqueue(ctx.h, ds0.h, model.h, 0, 1), ctx.h)
+        _lib.check(_lib.lib().nhp_cont_loglik_enqueue(ctx.h, ds0.h, model2.h, 0, 2), ctx.h)
+        ctx.synchronize()
+        assert int(count(ctx.h)) - p0 == 1, "the two evaluations did not share a pass"
+    print("one pass of two (k_slices_batch, deferred exit)")
+elif os.environ.get("ENQUEUE"):                        # the enqueue route: its last stamp is the deferred exit (NHP_DEFER_FINALIZE=0: the ticket)
     ds0, model = nhp.device_dataset(proc, (times, nodes, T), ctx), proc.device_model(ctx)
     for _ in range(5):
         _lib.check(_lib.lib().nhp_cont_loglik_enqueue(ctx.h, ds0.h, model.h, 0, 0), ctx.h)

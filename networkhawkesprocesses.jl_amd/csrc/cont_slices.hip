@@ -13,8 +13,8 @@
 //    there is no cross-lane reduction, no per-pair predicate and no per-child offset arithmetic at all.
 //  * Per evaluation the kernel streams 6 bytes per (padded) pair + 16 bytes per parameter pair: 67 MB at N = 1024, M = 1e6,
 //    mean window 8 (the 8-byte list of k_windowed_pairs: 85 MB), and issues ~25 VALU instructions per pair instead of ~44.
-//  * Σ log λ as one logarithm per lane of a running mantissa product; block sums and the fused last-workgroup reduction as
-//    in k_windowed.
+//  * Σ log λ from a running mantissa product and exponent sum per lane: multiplied and added across the wave, one logarithm
+//    per wave (the shared exit, sl_exit_sums); the fused last-workgroup reduction as in k_windowed.
 #include <algorithm>
 #include <vector>
 
@@ -253,6 +253,109 @@ __global__ __launch_bounds__(256) void k_ps_sort(int N, nhp_pslices ps, const ui
     }
 }
 
+// ---- the exit every exponential log-likelihood kernel of this file shares ------------------------------------------
+// A workgroup leaves two numbers per model: Σ log λ over its children and its share of the integral.  Both are formed HERE for
+// k_windowed_slices (fused and deferred exit) and k_slices_batch (every S, DEFER or not), so the routes the tests hold to each
+// other with `==` agree by construction.  Q = S·NW (model, wave) pairs, q = m·NW + w; behind the 2^(j/64) table the kernels keep
+//   park [Q][17]  the integral's partial sums, one per quad of lanes (16 a wave; the 17th pads the banks for the read below)
+//   mant [Q]      the wave's mantissa product, in [0.5, 1)
+//   wexp [Q]      its exponent sum (int32)
+// Σ log λ: a lane carries a mantissa product and an exponent sum over its children.  The 64 mantissas are multiplied in the
+// wave (the sum tree's steps; 64 factors in [0.5, 1) stay above 2^-64: no underflow) and the exponents added as integers;
+// after the barrier lane q of the first wave takes ONE logarithm for (model, wave) q, and thread 0 adds them wave by wave.
+// A lane without a child holds {1.0, 0} and changes nothing; a wave without a slice leaves {0.5, 1}: log 0.5 + ln 2 is exactly 0
+// (nhp_log's ln2_hi + ln2_lo rounds to the constant below).  A child with λ = 0 makes the product 0 and the sum -inf, one
+// with λ < 0 made its mantissa NaN in the row loop.
+// The integral: a wave stops its sum after the two quad steps, in the head, and parks 16 partial sums; lane q of the first wave
+// adds the 16 of (model, wave) q in lane order at the exit, where it is alone anyway, and thread 0 adds the waves' sums in wave
+// order.  Nothing of the integral is live in the row loop.
+__host__ __device__ constexpr size_t sl_exit_bytes(const int S, const int NW) { return ((size_t)S * NW * (17 * 8 + 8 + 4) + 15) / 16 * 16; }
+
+__device__ __forceinline__ double sl_dpp_mul(const double v, const int sel)
+{
+#pragma clang fp contract(off)
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    int plo, phi;
+    switch (sel) {
+    case 0: plo = __builtin_amdgcn_mov_dpp(lo, 0xB1, 0xF, 0xF, true); phi = __builtin_amdgcn_mov_dpp(hi, 0xB1, 0xF, 0xF, true); break;   // quad_perm [1,0,3,2]
+    case 1: plo = __builtin_amdgcn_mov_dpp(lo, 0x4E, 0xF, 0xF, true); phi = __builtin_amdgcn_mov_dpp(hi, 0x4E, 0xF, 0xF, true); break;   // quad_perm [2,3,0,1]
+    case 2: plo = __builtin_amdgcn_mov_dpp(lo, 0x141, 0xF, 0xF, true); phi = __builtin_amdgcn_mov_dpp(hi, 0x141, 0xF, 0xF, true); break; // row_half_mirror
+    default: plo = __builtin_amdgcn_mov_dpp(lo, 0x140, 0xF, 0xF, true); phi = __builtin_amdgcn_mov_dpp(hi, 0x140, 0xF, 0xF, true); break; // row_mirror
+    }
+    return v * __hiloint2double(phi, plo);
+}
+
+// the head's half of the integral: v = this thread's terms of model m
+template <int NW>
+__device__ __forceinline__ void sl_exit_park(double v, double *__restrict__ park, const int m, const int w, const int lane)
+{
+#pragma clang fp contract(off)
+    v = nhp_dpp_add(v, 0);
+    v = nhp_dpp_add(v, 1);
+    if ((lane & 3) == 0) park[(m * NW + w) * 17 + (lane >> 2)] = v;
+}
+
+// Every thread calls it once, after its last slice; the integral's partial sums were parked before an earlier barrier.  Thread 0
+// returns with sx[m] = Σ log λ and sy[m] = the integral's share of the workgroup; the other threads' values mean nothing.
+template <int NW, int S>
+__device__ __forceinline__ void sl_exit_sums(const double (&prod)[S], const int (&pexp)[S], double *__restrict__ park, double (&sx)[S], double (&sy)[S])
+{
+#pragma clang fp contract(off)
+    constexpr int Q = S * NW;
+    static_assert(Q <= 64, "one lane of the first wave per (model, wave)");
+    double *mant = park + Q * 17;
+    int *wexp = reinterpret_cast<int *>(mant + Q);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+#pragma unroll
+    for (int m = 0; m < S; ++m) {
+        double p = prod[m];
+        p = sl_dpp_mul(p, 0);
+        p = sl_dpp_mul(p, 1);
+        p = sl_dpp_mul(p, 2);
+        p = sl_dpp_mul(p, 3);
+        const int lo = __double2loint(p), hi = __double2hiint(p);
+        double r = __hiloint2double(__builtin_amdgcn_readlane(hi, 0), __builtin_amdgcn_readlane(lo, 0));
+        r *= __hiloint2double(__builtin_amdgcn_readlane(hi, 16), __builtin_amdgcn_readlane(lo, 16));
+        r *= __hiloint2double(__builtin_amdgcn_readlane(hi, 32), __builtin_amdgcn_readlane(lo, 32));
+        r *= __hiloint2double(__builtin_amdgcn_readlane(hi, 48), __builtin_amdgcn_readlane(lo, 48));
+        int e = pexp[m];
+        e += __builtin_amdgcn_mov_dpp(e, 0xB1, 0xF, 0xF, true);
+        e += __builtin_amdgcn_mov_dpp(e, 0x4E, 0xF, 0xF, true);
+        e += __builtin_amdgcn_mov_dpp(e, 0x141, 0xF, 0xF, true);
+        e += __builtin_amdgcn_mov_dpp(e, 0x140, 0xF, 0xF, true);
+        const int es = __builtin_amdgcn_readlane(e, 0) + __builtin_amdgcn_readlane(e, 16) + __builtin_amdgcn_readlane(e, 32) +
+                       __builtin_amdgcn_readlane(e, 48) + __builtin_amdgcn_frexp_exp(r);
+        if (lane == 0) {
+            mant[m * NW + w] = __builtin_amdgcn_frexp_mant(r);
+            wexp[m * NW + w] = es;
+        }
+    }
+    __syncthreads();
+    if (w != 0) return;                                             // (the helper's end: the callers' exits go on)
+    if (lane < Q) {
+        const double lg = nhp_log(mant[lane]) + (double)wexp[lane] * 6.93147180559945286e-01;
+        double *pk = park + lane * 17;
+        double si = 0.0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) si += pk[i];
+        mant[lane] = lg;                                            // (each lane its own entries, read above by itself only)
+        pk[0] = si;
+    }
+    // the first wave alone: its LDS operations complete in order, the fences keep the compiler from moving them
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (tid == 0) {
+#pragma unroll
+        for (int m = 0; m < S; ++m) {
+            double x = 0.0, y = 0.0;
+            for (int q = 0; q < NW; ++q) { x += mant[m * NW + q]; y += park[(m * NW + q) * 17]; }
+            sx[m] = x; sy[m] = y;
+        }
+    }
+}
+
 // C rows of a slice are requested at a time into one of two register sets: the next set is in flight while this one is
 // summed, across slice boundaries too (the first rows of a wave's next slice are requested under the last rows of this one,
 // and the very first set before the column is staged: its addresses need the slice table only).
@@ -275,6 +378,7 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
     double2 *col = reinterpret_cast<double2 *>(smem + 320);         // [N + 1] {-θ·unit·64/ln2, a·w·θ}; [N] = {0, 0}
     double *etab = reinterpret_cast<double *>(col + a.N + 1);       // [64] 2^(j/64)
     double *ginv = etab + 64;                                       // GRAD: [max_item + 1] 1/λ of the item's children; [max_item] = 0
+    double *park = etab + 64;                                       // !GRAD: the shared exit's sums (sl_exit_bytes(1, NW))
     const int tid = threadIdx.x, lane = tid & 63;
     const double tab_v = nhp_exp2_64[lane];                         // requested first, parked in LDS with the column (one wait)
 
@@ -343,6 +447,7 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
     if (tid == 0) col[N] = make_double2(0.0, 0.0);
     if (GRAD && tid == 0) ginv[ps.max_item] = 0.0;
     if (out && it.first) integ += sl_baseline_integral_col(a, c);
+    if (!GRAD) sl_exit_park<NW>(integ, park, 0, w, lane);           // (the gradient build keeps its own exit: DESIGN 3.1d)
     __syncthreads();
     NHP_SL_STAMP(1);
 
@@ -494,10 +599,19 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
             jp = jn; prow0 = row0n; Kp = Kn; cur = nxt;
         }
     }
-    double acc = nhp_log(prod) + (double)pexp * 6.93147180559945286e-01;
-    if (prod == 0.0) acc = -__builtin_inf();
-    double blk = acc, blk_int = integ;
-    nhp_block_sum2_n<NW>(blk, blk_int, red);
+    double blk = 0.0, blk_int = 0.0;
+    if constexpr (GRAD) {
+        double acc = nhp_log(prod) + (double)pexp * 6.93147180559945286e-01;
+        if (prod == 0.0) acc = -__builtin_inf();
+        blk = acc; blk_int = integ;
+        nhp_block_sum2_n<NW>(blk, blk_int, red);
+    } else {
+        const double p1[1] = {prod};
+        const int e1[1] = {pexp};
+        double sx[1] = {0.0}, sy[1] = {0.0};
+        sl_exit_sums<NW, 1>(p1, e1, park, sx, sy);
+        blk = sx[0]; blk_int = sy[0];
+    }
     if (GRAD && FLAT) {
         const double gs = nhp_block_sum_n<NW>(gsum, red);
         if (tid == 0) {
@@ -557,22 +671,15 @@ struct nhp_sets {
 };
 
 // DEFER (S = 2, the paired enqueue route): each model's result must be what k_windowed_slices<BLOCK, C, true,
-// false> leaves for it alone, bit for bit, so the integral's terms are formed as there; thread 0 stores the two block sums of
-// model m at index 2·blockIdx.x of ITS result slot's buffer (st.out[m]) and k_finalize_slots adds them at the next join: no
-// ticket, no agent-scope atomics.  The waves' integral sums wait in LDS from the head on (red[16 ..]): four registers less
-// in the row loop, which is what lets eight waves per SIMD fit (64 VGPRs).
+// false> leaves for it alone, bit for bit, so the integral's terms are formed as there (λ0·T rounded on its own: the single
+// kernel's select keeps the compiler from contracting it; every build of this kernel takes the same line) and the sums by the
+// shared exit; thread 0 stores the two block sums of model m at index 2·blockIdx.x of ITS result slot's buffer (st.out[m]) and
+// k_finalize_slots adds them at the next join: no ticket, no agent-scope atomics.  The integral's partial sums wait in LDS from
+// the head on (sl_exit_park): four registers less in the row loop, which is what lets eight waves per SIMD fit (64 VGPRs).
 __device__ __forceinline__ double sl_flat_integral(const double lam0, const double duration)
 {
 #pragma clang fp contract(off)
     return threadIdx.x == 0 ? lam0 * duration : 0.0;
-}
-
-// log(mantissa product) + exponent·ln 2 as k_windowed_slices forms it: the product rounded on its own, then the sum
-__device__ __forceinline__ double sl_log_of(const double prod, const int pexp)
-{
-#pragma clang fp contract(off)
-    const double e = (double)pexp * 6.93147180559945286e-01;
-    return e + nhp_log(prod);
 }
 
 template <int BLOCK, int C, int S, bool DEFER = false>
@@ -580,13 +687,11 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
                                                          unsigned int *__restrict__ counter)
 {
     constexpr int NW = BLOCK / 64;
-    // two sets, at most eight waves: the waves' integral sums are made in the head and wait in red[16 ..] (the order of
-    // nhp_block_sum2_n: wave sums, then wave by wave), which keeps the row loop inside 64 registers
-    constexpr bool EARLY = DEFER || (S == 2 && NW <= 8);
     extern __shared__ __align__(16) unsigned char smem[];
     double *red = reinterpret_cast<double *>(smem);                 // [2 * NW <= 32] + flag at [32]
     double2 *col = reinterpret_cast<double2 *>(smem + 320);         // [S][N + 1]
     double *etab = reinterpret_cast<double *>(col + (size_t)S * (a.N + 1));
+    double *park = etab + 64;                                       // the shared exit's sums (sl_exit_bytes(S, NW))
     const int tid = threadIdx.x, lane = tid & 63;
     const double tab_v = nhp_exp2_64[lane];
     const nhp_item it = a.items[blockIdx.x];
@@ -682,13 +787,8 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
 #pragma unroll
     for (int m = 0; m < S; ++m) {
         if (tid == 0) col[(size_t)m * (N + 1) + N] = make_double2(0.0, 0.0);
-        if (DEFER) {
-            if (it.first) integ[m] += sl_flat_integral(lam0[m], a.duration);
-        } else if (it.first && tid == 0) integ[m] += lam0[m] * a.duration;
-        if (EARLY) {
-            const double wsum = nhp_wave_sum(integ[m]);
-            if (lane == 0) red[16 + m * NW + w] = wsum;
-        }
+        if (it.first) integ[m] += sl_flat_integral(lam0[m], a.duration);
+        sl_exit_park<NW>(integ[m], park, m, w, lane);
     }
     if (tid < 64) etab[tid] = tab_v;
     __syncthreads();
@@ -759,51 +859,29 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
     }
     NHP_SL_STAMP_WAVE();
     NHP_SL_STAMP(2);
+    double sx[S], sy[S];
+#pragma unroll
+    for (int m = 0; m < S; ++m) { sx[m] = 0.0; sy[m] = 0.0; }
+    sl_exit_sums<NW, S>(prod, pexp, park, sx, sy);
+    NHP_SL_STAMP(3);
     if (DEFER) {
-        // nhp_block_sum2_n's order for every model, with one pair of barriers for all: wave sums, then wave by wave
-        double ws[S];
-#pragma unroll
-        for (int m = 0; m < S; ++m) {
-            double blk = sl_log_of(prod[m], pexp[m]);
-            if (prod[m] == 0.0) blk = -__builtin_inf();
-            ws[m] = nhp_wave_sum(blk);
-        }
-        __syncthreads();
-        if (lane == 0) {
-#pragma unroll
-            for (int m = 0; m < S; ++m) red[m * NW + w] = ws[m];
-        }
-        __syncthreads();
-        NHP_SL_STAMP(3);
         if (tid == 0) {
 #pragma unroll
             for (int m = 0; m < S; ++m) {
-                double sx = 0.0, sy = 0.0;
-                for (int q = 0; q < NW; ++q) { sx += red[m * NW + q]; sy += red[16 + m * NW + q]; }
-                st.out[m][2 * (size_t)blockIdx.x] = sx;
-                st.out[m][2 * (size_t)blockIdx.x + 1] = sy;
+                st.out[m][2 * (size_t)blockIdx.x] = sx[m];
+                st.out[m][2 * (size_t)blockIdx.x + 1] = sy[m];
             }
         }
         NHP_SL_STAMP(4);
         return;
     }
     int *flag = reinterpret_cast<int *>(red + 32);
-#pragma unroll
-    for (int m = 0; m < S; ++m) {
-        double blk = nhp_log(prod[m]) + (double)pexp[m] * 6.93147180559945286e-01;
-        if (prod[m] == 0.0) blk = -__builtin_inf();
-        double blk_int = EARLY ? 0.0 : integ[m];
-        nhp_block_sum2_n<NW>(blk, blk_int, red);
-        if (EARLY && tid == 0)
-            for (int q = 0; q < NW; ++q) blk_int += red[16 + m * NW + q];
-        if (tid == 0) {
-            __hip_atomic_store(&partials[(2 * (size_t)blockIdx.x) * S + 2 * m], blk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&partials[(2 * (size_t)blockIdx.x) * S + 2 * m + 1], blk_int, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-    }
-    NHP_SL_STAMP(3);
     if (tid == 0) {
+#pragma unroll
+        for (int m = 0; m < S; ++m) {
+            __hip_atomic_store(&partials[(2 * (size_t)blockIdx.x) * S + 2 * m], sx[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&partials[(2 * (size_t)blockIdx.x) * S + 2 * m + 1], sy[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const unsigned int nb = gridDim.x, sh = blockIdx.x % NHP_SL_SHARDS;
         const unsigned int pop = (nb - sh + NHP_SL_SHARDS - 1) / NHP_SL_SHARDS;
@@ -1271,7 +1349,8 @@ static nhp_status launch_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const 
     if (deferred) *deferred = false;
     if (!ds->d_sl_row || ds->n_items <= 0 || m->impulse_kind != NHP_IMPULSE_EXPONENTIAL) return NHP_OK;
     if (nhp_slices_off(d_grad ? "NHP_GRAD_SLICES" : nullptr)) return NHP_OK;     // (NHP_GRAD_SLICES=0: the two-pass route of cont_grad.hip)
-    const size_t lds = 320 + 16 * ((size_t)ds->N + 1) + 512 + (d_grad ? 8 * ((size_t)ds->max_item + 1) : 0);
+    // (behind the column and the 2^(j/64) table: the gradient's 1/λ, or the shared exit's sums for the largest workgroup)
+    const size_t lds = 320 + 16 * ((size_t)ds->N + 1) + 512 + (d_grad ? 8 * ((size_t)ds->max_item + 1) : sl_exit_bytes(1, 16));
     if (lds > 160 * 1024) return NHP_OK;
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_ctx_reserve_partials(ctx, 2 * (size_t)ds->n_items));
@@ -1461,7 +1540,7 @@ nhp_status nhp_launch_slices_batch(nhp_ctx *ctx, const nhp_cont_dataset *ds, con
     if (nhp_slices_off("NHP_BATCH_SLICES")) return NHP_OK;
     for (int k = 0; k < S; ++k)
         if (!ms[k] || ms[k]->impulse_kind != NHP_IMPULSE_EXPONENTIAL || ms[k]->baseline_kind != NHP_BASELINE_HOMOGENEOUS) return NHP_OK;
-    const size_t lds = 320 + 16 * ((size_t)ds->N + 1) * (size_t)S + 512;
+    const size_t lds = 320 + 16 * ((size_t)ds->N + 1) * (size_t)S + 512 + sl_exit_bytes(S, 16);
     if (lds > 160 * 1024) return NHP_OK;
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     if (S == 4) NHP_TRY(launch_sets<4>(ctx, ds, ms, slot0, lds)); else NHP_TRY(launch_sets<2>(ctx, ds, ms, slot0, lds));
@@ -1478,7 +1557,7 @@ bool nhp_slices_pair_eligible(const nhp_cont_dataset *ds, const nhp_cont_model *
     if (m->impulse_kind != NHP_IMPULSE_EXPONENTIAL || m->baseline_kind != NHP_BASELINE_HOMOGENEOUS) return false;
     if (!ds->all_sole || nhp_is_column_shard(ds) || nhp_slices_off(nullptr)) return false;
     if (const char *pl = getenv("NHP_PLIST")) if (atoi(pl) == 0) return false;
-    if (4 * (320 + 32 * ((size_t)ds->N + 1) + 512) > 160 * 1024) return false;
+    if (4 * (320 + 32 * ((size_t)ds->N + 1) + 512 + sl_exit_bytes(2, 8)) > 160 * 1024) return false;   // (N = 1024: 4 x 36000 bytes)
     int B, C;
     slices_cfg(ds, &B, &C);
     return (B == 64 || B == 128 || B == 256 || B == 512) && (C == 2 || C == 4 || C == 8);
@@ -1488,7 +1567,7 @@ bool nhp_slices_pair_eligible(const nhp_cont_dataset *ds, const nhp_cont_model *
 // DEFER> on the current lane with launch_slices' (B, C); both slots are marked pending with that B.
 nhp_status nhp_launch_slices_pair(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *const *ms, const int32_t *slot)
 {
-    const size_t lds = 320 + 32 * ((size_t)ds->N + 1) + 512;
+    const size_t lds = 320 + 32 * ((size_t)ds->N + 1) + 512 + sl_exit_bytes(2, 8);
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     for (int k = 0; k < 2; ++k) NHP_TRY(nhp_ctx_reserve_slot_partials(ctx, slot[k], 2 * (size_t)ds->n_items));
     nhp_cont_args a = nhp_make_args(ds, ms[0]);

@@ -1028,6 +1028,53 @@ nhp_status nhp_cont_mcmc_run(nhp_ctx *ctx, nhp_comm *comm /* nullable */, const 
                              const nhp_gibbs_priors *priors, double net_alpha, double net_beta, uint64_t seed,
                              uint64_t step0, int64_t n_steps, int64_t burn);
 
+/* ---- scoring a continuous chain: held-out predictive log-likelihood and WAIC (csrc/cont_score.hip) -------------
+ * The time axis is cut at edges b_0 < b_1 < ... < b_K with 0 <= b_0 and b_K <= duration.  Cell i = (k, c) is node c on the block
+ * [b_k, b_{k+1}); its log-likelihood under a draw θ is
+ *   ℓ_{k,c}(θ) = Σ_{events m of node c, b_k <= t_m < b_{k+1}} log λ_c(t_m)  −  (Λ_c(b_{k+1}) − Λ_c(b_k)),
+ * λ the per-event intensity of nhp_cont_event_intensity (exact delays), Λ the compensator of nhp_cont_compensator with all of
+ * its conventions (strict window, exponential cut at Δtmax and not renormalised, logit-normal mass W·Δtmax, mask A).  Events
+ * before b_0 excite the scored range; events at or after b_K are not scored.  Each term is the density of the block given the
+ * past, so the likelihood factorises over the cells sequentially and the pointwise definitions of nhp_disc_score_* carry over:
+ * lppd_i, p_i (sample variance, S − 1), elpd_i, waic, se_elpd, joint_lpd, joint_mean, joint_sd.  Over edges covering
+ * [0, duration], Σ_k ℓ_{k,c} = Σ log λ_c − Λ_c(duration): the exact log-likelihood, NOT nhp_cont_loglik, which charges every event
+ * the full mass of its impulses (the reference's "approximate" integral).
+ * A scorer keeps, per cell, a running log-sum-exp and Welford's mean and M2 of ℓ_i, and the same three scalars for Σ_i ℓ_i:
+ * 24·K·N bytes of planes (k fastest), plus 8·(bx·N + 4N + K + 25) bytes of sums (bx = min(ceil(K / 256), max(1, 4096 / N)) workgroup partials per
+ * column, so bx·N <= max(4096, N)).
+ * While a draw is scored the context's scratch holds 8·(max(M, 1) + t·N² + s·K·N) bytes: λ, t = 3 row-major tables (W·A, V, θ;
+ * 4 with √τ for logit-normal impulses) and the s <= 64 parts a block's events are summed in (s = 1 unless
+ * K·ceil(N / 256) <= 4096 and M / K >= 512).
+ * _create: `ds` must outlive the scorer.  NHP_EINVAL: fewer than 2 edges, edges not finite, outside [0, duration] or not
+ *   strictly increasing.  NHP_ENOTIMPL: a dataset of several trials, a column shard, N > 65535.  NHP_ENOMEM leaves nothing
+ *   allocated.
+ * _accumulate: the model's current state as one draw -- λ[M], the tables, the block compensators ΔΛ[k, c] formed directly (a
+ *   saturated mass for an event whose whole window lies inside the block, a difference of two CDF values only for events
+ *   within Δtmax of an edge), one pass over the cells, one fold of the workgroup partials.  Asynchronous on the main stream, no
+ *   host read; no atomics and every sum in one fixed order, so two runs give the same bits.  The dataset / model mismatches
+ *   of nhp_cont_loglik apply (NHP_ESHAPE, NHP_EINVAL for another Δtmax); a model with an LGCP baseline and an N beyond the LDS
+ *   column budget of the per-event intensity are NHP_ENOTIMPL.
+ * _reset: forget the draws.  _fetch (synchronous): NHP_EINVAL ("nothing accumulated") with S = 0;
+ *   summary[10] = {S, cells = K·N, lppd, p_waic, elpd_waic, waic = −2·elpd_waic, se_elpd = sqrt(cells · var_i elpd_i) (two
+ *   passes), joint_lpd, joint_mean, joint_sd}; per_node[3N] = lppd, p_waic, elpd_waic per node; pointwise[K·N] (nullable,
+ *   index k + K·c) = elpd_i.  With S = 1, p_i and everything built on it (and joint_sd) are NaN.
+ * _fetch_planes (synchronous): the running planes, each nullable, [K·N] at index k + K·c; NHP_EINVAL with S = 0.
+ * nhp_cont_model_attach_score: at most two scorers per model (a third is NHP_EINVAL; not owned: detach before a scorer is
+ *   destroyed).  nhp_cont_mcmc_run then reserves their scratch once and calls _accumulate for each on every kept step whose
+ *   kept index -- counted per scorer from the attach on, across calls -- is a multiple of `every` (>= 1, else NHP_EINVAL).
+ *   Kept steps are those from `burn` on; with the moments off (burn < 0) those from −(burn + 1) on.  score = NULL detaches
+ *   all.  With scorers attached a column shard / communicator is NHP_ENOTIMPL; with nothing attached nhp_cont_mcmc_run
+ *   launches exactly what it launched before. */
+typedef struct nhp_cont_score nhp_cont_score;
+nhp_status nhp_cont_score_create(nhp_ctx *ctx, const nhp_cont_dataset *ds, const double *edges, int64_t n_edges, nhp_cont_score **out);
+void nhp_cont_score_destroy(nhp_cont_score *score);
+nhp_status nhp_cont_score_reset(nhp_ctx *ctx, nhp_cont_score *score);
+nhp_status nhp_cont_score_accumulate(nhp_ctx *ctx, nhp_cont_score *score, const nhp_cont_model *model);
+nhp_status nhp_cont_score_fetch(nhp_ctx *ctx, const nhp_cont_score *score, double *summary /* [10] */, double *per_node /* [3N] */,
+                                double *pointwise /* [K*N] or NULL */);
+nhp_status nhp_cont_score_fetch_planes(nhp_ctx *ctx, const nhp_cont_score *score, double *lse, double *mean, double *m2);
+nhp_status nhp_cont_model_attach_score(nhp_ctx *ctx, nhp_cont_model *model, nhp_cont_score *score, int64_t every);
+
 /* ---- StochasticBlockNetworkModel (csrc/sbm.hip; the reference's src/networks.jl ends in its empty stub) --------------
  * K blocks, N nodes: z_n ~ Categorical(π), π ~ Dirichlet(γ·1_K), ρ[k,l] ~ Beta(α, β), A[p,c] ~ Bernoulli(ρ[z_p, z_c]) for all
  * N² entries.  Labels are 0-based int32; ρ is K x K column-major (ρ[k,l] at k + K·l); A is N x N column-major.

@@ -170,6 +170,13 @@ def _declare(lib):
     f("nhp_disc_score_fetch", i32, _vp, _vp, _dp, _dp, _dp)
     f("nhp_disc_score_fetch_planes", i32, _vp, _vp, _dp, _dp, _dp)
     f("nhp_disc_model_attach_score", i32, _vp, _vp, _vp, i64)
+    f("nhp_cont_score_create", i32, _vp, _vp, _dp, i64, C.POINTER(_vp))
+    f("nhp_cont_score_destroy", None, _vp)
+    f("nhp_cont_score_reset", i32, _vp, _vp)
+    f("nhp_cont_score_accumulate", i32, _vp, _vp, _vp)
+    f("nhp_cont_score_fetch", i32, _vp, _vp, _dp, _dp, _dp)
+    f("nhp_cont_score_fetch_planes", i32, _vp, _vp, _dp, _dp, _dp)
+    f("nhp_cont_model_attach_score", i32, _vp, _vp, _vp, i64)
     f("nhp_disc_simulate", i32, _vp, _dp, _dp, _dp, _dp, _dp, _dp, i32, i32, dbl, i32, i64, u64, i64, i32, _vp, _vp, C.POINTER(i64),
       C.POINTER(i32))
     f("nhp_disc_forecast", i32, _vp, _dp, _dp, _dp, _dp, _dp, _dp, i32, i32, dbl, i32, _vp, i64, i32, i64, i64, u64, i64, i32, _vp, _vp,

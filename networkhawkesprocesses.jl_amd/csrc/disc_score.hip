@@ -5,11 +5,12 @@
 // are: on the device, streaming, in the pass that keeps a step.  Per scored cell three doubles -- a running log-sum-exp of ℓ
 // and Welford's mean and M2 of ℓ -- and for the draw's total over the scored cells the same three as scalars.  A draw is
 // scored in four launches on the main stream: the bump table from the model's block, the fp64 GEMM on the scored rows of Ŝ
-// with its plain epilogue, k_disc_score over the cells, k_disc_score_fold over the workgroup partials.  No atomics, every
+// with its plain epilogue, k_disc_score over the cells, k_score_fold (nhp_score.h) over the workgroup partials.  No atomics, every
 // sum in one fixed order: two runs give the same bits.  The data-only loggamma(s + 1) shifts ℓ by a constant per cell: it
 // leaves the variance alone and moves the log-sum-exp by itself, so it is left out of the pass and restored at fetch.
 #include "nhp_internal.h"
 #include "nhp_math.h"
+#include "nhp_score.h"
 #include <algorithm>
 #include <cmath>
 
@@ -25,13 +26,6 @@ struct nhp_disc_score {
 };
 // joint: 0 lse, 1 mean, 2 M2 of the draw's total over the scored cells, 3 the latest total, 4 Σ loggamma(s + 1) of the range
 
-// one more value into a running log-sum-exp
-__device__ __forceinline__ double score_lse(double a, double b)
-{
-    const double d = a == b ? 0.0 : fabs(a - b);               // (equal infinities: no NaN)
-    return fmax(a, b) + log1p(exp(-d));
-}
-
 // ---- Σ_t loggamma(s + 1) per node over the scored bins (once, at create) --------------------------------------------------
 __global__ __launch_bounds__(256) void k_disc_score_lgamma(const double *__restrict__ data, int64_t T, int64_t R, double *__restrict__ lgcol)
 {
@@ -44,14 +38,6 @@ __global__ __launch_bounds__(256) void k_disc_score_lgamma(const double *__restr
     }
     lg = nhp_block_sum(lg, red);
     if (threadIdx.x == 0) lgcol[blockIdx.x] = lg;
-}
-
-// Σ over `n` values at x (stride 1), one workgroup, one fixed order; valid in thread 0
-__device__ __forceinline__ double score_sum(const double *__restrict__ x, int64_t n, double *red)
-{
-    double s = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 256) s += x[i];
-    return nhp_block_sum(s, red);
 }
 
 __global__ __launch_bounds__(256) void k_disc_score_lgamma_total(const double *__restrict__ lgcol, int N, double *__restrict__ joint)
@@ -92,25 +78,6 @@ __global__ __launch_bounds__(256) void k_disc_score(const double *__restrict__ l
     if (threadIdx.x == 0) partials[blockIdx.x + (size_t)gridDim.x * blockIdx.y] = acc;
 }
 
-// the draw's total over the scored cells, and the joint scalars (one workgroup)
-__global__ __launch_bounds__(256) void k_disc_score_fold(const double *__restrict__ partials, int64_t np, double n, double *__restrict__ joint)
-{
-#pragma clang fp contract(off)
-    __shared__ double red[NHP_WAVES];
-    const double s = score_sum(partials, np, red);
-    if (threadIdx.x != 0) return;
-    const double tot = s - joint[4];
-    if (n == 1.0) {
-        joint[0] = tot; joint[1] = tot; joint[2] = 0.0;
-    } else {
-        const double mean = joint[1], d = tot - mean, mean1 = mean + d / n;
-        joint[0] = score_lse(joint[0], tot);
-        joint[1] = mean1;
-        joint[2] = joint[2] + d * (tot - mean1);
-    }
-    joint[3] = tot;
-}
-
 // ---- fetch ------------------------------------------------------------------------------------------------------------------
 // One workgroup per node column, rows in a fixed order.  SPREAD = false: elpd_i (-> pointwise when asked) and the column's
 // Σ lppd_i, Σ p_i, Σ elpd_i -> col[c], col[N + c], col[2N + c].  SPREAD = true: Σ (elpd_i − mean elpd)² -> col[3N + c], the
@@ -145,28 +112,6 @@ __global__ __launch_bounds__(256) void k_disc_score_finalize(const double *__res
     a1 = nhp_block_sum(a1, red);
     a2 = nhp_block_sum(a2, red);
     if (threadIdx.x == 0) { col[c] = a0; col[N + c] = a1; col[2 * N + c] = a2; }
-}
-
-// over the nodes, one workgroup.  STAGE 0: tot[0..2] = Σ_c of the three column sums, tot[3] = mean elpd_i.  STAGE 1: the
-// summary (tot[4..13], the order of nhp_disc_score_fetch).
-template <int STAGE>
-__global__ __launch_bounds__(256) void k_disc_score_total(const double *__restrict__ col, int N, double cells, double S, double logS,
-                                                          const double *__restrict__ joint, double *__restrict__ tot)
-{
-#pragma clang fp contract(off)
-    __shared__ double red[NHP_WAVES];
-    if (STAGE == 0) {
-        const double lppd = score_sum(col, N, red), p = score_sum(col + N, N, red), e = score_sum(col + 2 * (size_t)N, N, red);
-        if (threadIdx.x == 0) { tot[0] = lppd; tot[1] = p; tot[2] = e; tot[3] = e / cells; }
-    } else {
-        const double ss = score_sum(col + 3 * (size_t)N, N, red);
-        if (threadIdx.x == 0) {
-            double *o = tot + 4;
-            o[0] = S; o[1] = cells; o[2] = tot[0]; o[3] = tot[1]; o[4] = tot[2]; o[5] = -2.0 * tot[2];
-            o[6] = sqrt(cells * (ss / (cells - 1.0)));
-            o[7] = joint[0] - logS; o[8] = joint[1]; o[9] = sqrt(joint[2] / (S - 1.0));
-        }
-    }
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
@@ -267,7 +212,7 @@ extern "C" nhp_status nhp_disc_score_accumulate(nhp_ctx *ctx, nhp_disc_score *sc
     hipStream_t st = ctx->main();
     hipLaunchKernelGGL(k_disc_score, dim3(sc->bx, (unsigned)sc->N), dim3(256), 0, st, (const double *)dlam, (const double *)(ds->d_dataT + sc->t0),
                        ds->T, R, RN, sc->d_planes, n, sc->d_partials);
-    hipLaunchKernelGGL(k_disc_score_fold, dim3(1), dim3(256), 0, st, (const double *)sc->d_partials, (int64_t)sc->bx * sc->N, n, sc->d_joint);
+    hipLaunchKernelGGL(k_score_fold, dim3(1), dim3(256), 0, st, (const double *)sc->d_partials, (int64_t)sc->bx * sc->N, n, sc->d_joint);
     NHP_HIP(ctx, hipGetLastError());
     ++sc->count;
     return NHP_OK;
@@ -290,11 +235,11 @@ extern "C" nhp_status nhp_disc_score_fetch(nhp_ctx *ctx, const nhp_disc_score *s
     hipStream_t st = ctx->main();
     hipLaunchKernelGGL(k_disc_score_finalize<false>, dim3((unsigned)N), dim3(256), 0, st, (const double *)sc->d_planes, data, ds->T, R, RN, logS,
                        S - 1.0, sc->d_col, (const double *)sc->d_tot, d_pw);
-    hipLaunchKernelGGL(k_disc_score_total<0>, dim3(1), dim3(256), 0, st, (const double *)sc->d_col, (int)N, cells, S, logS,
+    hipLaunchKernelGGL(k_score_total<0>, dim3(1), dim3(256), 0, st, (const double *)sc->d_col, (int)N, cells, S, logS,
                        (const double *)sc->d_joint, sc->d_tot);
     hipLaunchKernelGGL(k_disc_score_finalize<true>, dim3((unsigned)N), dim3(256), 0, st, (const double *)sc->d_planes, data, ds->T, R, RN, logS,
                        S - 1.0, sc->d_col, (const double *)sc->d_tot, (double *)nullptr);
-    hipLaunchKernelGGL(k_disc_score_total<1>, dim3(1), dim3(256), 0, st, (const double *)sc->d_col, (int)N, cells, S, logS,
+    hipLaunchKernelGGL(k_score_total<1>, dim3(1), dim3(256), 0, st, (const double *)sc->d_col, (int)N, cells, S, logS,
                        (const double *)sc->d_joint, sc->d_tot);
     NHP_HIP(ctx, hipGetLastError());
     NHP_TRY(nhp_download(ctx, summary, sc->d_tot + 4, 10 * sizeof(double)));

@@ -360,7 +360,13 @@ struct nhp_cont_model {
     // streaming convergence diagnostics (cont_diagnostics.hip: nhp_cont_model_diagnostics_*): the batch planes and the
     // snapshots of the sums above; null: not configured, _accumulate runs the moments kernel alone
     struct nhp_diag_state *diag = nullptr;
+    // scorers attached for nhp_cont_mcmc_run (cont_score.hip: nhp_cont_model_attach_score; not owned): slot k scores every
+    // score_every[k]-th kept step, score_kept[k] counts the kept steps seen since the attach (it persists across calls)
+    struct nhp_cont_score *score[2] = {nullptr, nullptr};
+    int64_t score_every[2] = {1, 1}, score_kept[2] = {0, 0};
 };
+// cont_score.hip: grow the context's scratch to what nhp_cont_score_accumulate(score, model) stages, ahead of a loop
+nhp_status nhp_cont_score_reserve(nhp_ctx *ctx, const struct nhp_cont_score *score, const nhp_cont_model *m);
 // cont_diagnostics.hip: release the diagnostic planes; their share of nhp_cont_model_moments_reset (zero the planes, fitted
 // to the sums' current length) and of _accumulate (the fused kernel IN PLACE of the moments kernel, then the snapshots) --
 // all asynchronous on the main stream

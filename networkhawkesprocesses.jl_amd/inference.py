@@ -639,9 +639,221 @@ def _merge_shards(process, shard, network):
         process.adjacency_matrix = full[L.adjacency].reshape((N, N), order="F").copy()
 
 
+# ---- scoring a chain: held-out predictive log-likelihood and WAIC (csrc/cont_score.hip) ---------------------------
+class ContinuousScore:
+    """What nhp_cont_score_fetch returns for the cells (block [edges[k], edges[k+1]), node) over `n` kept draws (definitions:
+    include/nhp.h).  `lppd`, `p_waic`, `elpd_waic`, `waic` = −2·elpd_waic and `se_elpd` are the pointwise scores summed over the
+    cells; `joint_lpd` = log mean_s p(all scored cells | θ_s) is the predictive log-likelihood of the scored range as a whole
+    (the number to report for held-out data), `joint_mean` and `joint_sd` the mean and spread of the draws' log-likelihoods.
+    `per_node` is 3 x N (lppd, p_waic, elpd_waic per node), `pointwise` -- when asked for -- the K x N array of elpd_i that
+    compare_scores needs; `bins` = tuple(edges) is what compare_scores holds two scores' cells equal by."""
+
+    def __init__(self, summary, per_node, pointwise, edges):
+        from .discrete import SCORE_FIELDS
+        for name, v in zip(SCORE_FIELDS, summary):
+            setattr(self, name, int(v) if name in ("n", "cells") else float(v))
+        self.per_node, self.pointwise = per_node, pointwise
+        self.edges = np.array(edges, dtype=np.float64)
+        self.bins = tuple(float(e) for e in self.edges)
+
+    def __repr__(self):
+        return (f"ContinuousScore(blocks={len(self.edges) - 1}, n={self.n}, waic={self.waic:.6g}, elpd_waic={self.elpd_waic:.6g} ± "
+                f"{self.se_elpd:.3g}, p_waic={self.p_waic:.4g}, joint_lpd={self.joint_lpd:.6g})")
+
+
+class _DeviceScore:
+    """nhp_cont_score handle on a device dataset (kept alive with it)."""
+
+    def __init__(self, ctx, ds, edges):
+        import ctypes as C
+        self.ctx, self.ds, self.edges = ctx, ds, _lib.f64(edges)
+        self.h = C.c_void_p()
+        _lib.check(_lib.lib().nhp_cont_score_create(ctx.h, ds.h, _lib.dptr(self.edges), len(self.edges), C.byref(self.h)), ctx.h)
+
+    def accumulate(self, model):
+        _lib.check(_lib.lib().nhp_cont_score_accumulate(self.ctx.h, self.h, model.h), self.ctx.h)
+
+    def fetch(self, pointwise=False):
+        """The ContinuousScore of the draws so far; None when nothing was accumulated."""
+        from .discrete import SCORE_FIELDS
+        N, K = self.ds.nnodes, len(self.edges) - 1
+        summary, per_node = np.empty(len(SCORE_FIELDS)), np.empty(3 * N)
+        pw = np.empty(K * N) if pointwise else None
+        try:
+            _lib.check(_lib.lib().nhp_cont_score_fetch(self.ctx.h, self.h, _lib.dptr(summary), _lib.dptr(per_node), _lib.dptr(pw)), self.ctx.h)
+        except _lib.NhpError as e:
+            if "nothing accumulated" not in str(e):
+                raise
+            return None
+        return ContinuousScore(summary, per_node.reshape(3, N), pw.reshape((K, N), order="F") if pointwise else None, self.edges)
+
+    def fetch_planes(self):
+        """The running planes lse, mean, M2 of ℓ as the device holds them, each K x N."""
+        N, K = self.ds.nnodes, len(self.edges) - 1
+        planes = [np.empty(K * N) for _ in range(3)]
+        _lib.check(_lib.lib().nhp_cont_score_fetch_planes(self.ctx.h, self.h, *[_lib.dptr(v) for v in planes]), self.ctx.h)
+        return tuple(v.reshape((K, N), order="F") for v in planes)
+
+    def close(self):
+        if getattr(self, "h", None):
+            _lib.lib().nhp_cont_score_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _check_edges(edges, T, what):
+    """An int K -> K equal blocks over [0, T]; else the edges themselves: at least two, finite, strictly increasing, inside
+    [0, T]."""
+    if isinstance(edges, (bool, np.bool_)):
+        raise ValueError(f"{what}: give a number of blocks or an array of edges")
+    if isinstance(edges, (int, np.integer)):
+        if int(edges) < 1:
+            raise ValueError(f"{what}: the number of blocks must be positive")
+        e = np.linspace(0.0, float(T), int(edges) + 1)
+        e[-1] = float(T)
+        return e
+    try:
+        e = np.array(edges, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: edges must be a number of blocks or a 1-D array of times") from None
+    if e.ndim != 1 or len(e) < 2:
+        raise ValueError(f"{what}: edges must be a 1-D array of at least two times")
+    if not np.all(np.isfinite(e)):
+        raise ValueError(f"{what}: edges must be finite")
+    if not np.all(np.diff(e) > 0):
+        raise ValueError(f"{what}: edges must increase strictly")
+    if e[0] < 0 or e[-1] > T:
+        raise ValueError(f"{what}: edges must lie inside [0, duration = {T}]")
+    return e
+
+
+def _scored_data(process, data, what):
+    """(N, duration) of the data a scorer would run on; whatever scoring is not built for raises here, before any upload."""
+    from .continuous import DeviceDataset, ntrials_of
+    from .sharded import ShardedDataset
+    if isinstance(data, ShardedDataset):
+        raise NotImplementedError(f"{what}: scoring is not available on a ShardedDataset (a draw needs every column)")
+    if not isinstance(process.baseline, HomogeneousProcess):
+        raise NotImplementedError(f"{what}: scoring needs a homogeneous baseline (baseline: {type(process.baseline).__name__}: the draws "
+                                  f"of its grid values are not scored)")
+    N = process.ndims()
+    if isinstance(data, DeviceDataset):
+        if getattr(data, "ntrials", 1) > 1:
+            raise NotImplementedError(f"{what}: scoring is not available on several trials (a block of the stacked clock would straddle them)")
+        if data.nnodes != N:
+            raise ValueError(f"{what}: the data has {data.nnodes} nodes, the process {N}")
+        return N, float(data.duration)
+    if ntrials_of(data) > 1:
+        raise NotImplementedError(f"{what}: scoring is not available on several trials (a block of the stacked clock would straddle them)")
+    events, nodes, duration = as_data(data)
+    if not (hasattr(nodes, "device") and not isinstance(nodes, np.ndarray)):
+        nd = np.asarray(nodes)
+        if nd.size and (nd.min() < 1 or nd.max() > N):
+            raise ValueError(f"{what}: the data's nodes run from {nd.min()} to {nd.max()}, the process has {N}")
+    return N, float(duration)
+
+
+def _score_plan(process, data, waic, heldout, score_every, burn):
+    """The scorers a chain was asked for, as [(name, data or None for the chain's own, edges)]; every argument is checked here,
+    before the library is touched."""
+    if (waic is False or waic is None) and heldout is None:
+        return []
+    if isinstance(score_every, bool) or int(score_every) != score_every or int(score_every) < 1:
+        raise ValueError("score_every must be a positive integer")
+    if int(burn) < 0:
+        raise ValueError("burn must be non-negative when the chain is scored")
+    plan = []
+    if waic is not False and waic is not None:
+        _, T = _scored_data(process, data, "waic")
+        plan.append(("waic", None, _check_edges(waic, T, "waic")))
+    if heldout is not None:
+        if not (isinstance(heldout, tuple) and len(heldout) == 2):
+            raise ValueError("heldout must be (data_full, edges)")
+        _scored_data(process, data, "heldout")
+        _, T = _scored_data(process, heldout[0], "heldout")
+        plan.append(("heldout", heldout[0], _check_edges(heldout[1], T, "heldout")))
+    return plan
+
+
+def _open_scorers(ctx, process, ds, plan):
+    out = []
+    try:
+        for name, data, edges in plan:
+            out.append((name, _DeviceScore(ctx, ds if data is None else device_dataset(process, data, ctx), edges)))
+    except Exception:
+        for _, s in out:
+            s.close()
+        raise
+    return out
+
+
+def _set_score_model(model, ctx, process, x):
+    """The draw x = params(process) as the state of a device model kept for scoring (made at the first call): the tables are
+    read out of x, the process supplies the shapes, the kinds and Δtmax and is not changed."""
+    from .continuous import DeviceModel
+    N = process.ndims()
+    network = isinstance(process, ContinuousNetworkHawkesProcess)
+    x = _lib.f64(x)
+    L = param_layout(process, network)
+    if x.shape != (L.adjacency.stop if network else L.weights.stop,):
+        raise ValueError("Parameter vector length does not match model parameter length.")
+    exponential = isinstance(process.impulses, ExponentialImpulseResponse)
+    d = _lib.ModelDesc()
+    d.n_nodes, d.baseline_kind, d.grid_n = N, _lib.BASELINE_HOMOGENEOUS, 0
+    d.impulse_kind = _lib.IMPULSE_EXPONENTIAL if exponential else _lib.IMPULSE_LOGITNORMAL
+    d.dt_max = float(process.impulses.Δtmax)
+    keep = [np.ascontiguousarray(x[L.baseline]), np.ascontiguousarray(x[L.weights]), np.ascontiguousarray(x[L.impulses])]
+    d.lambda0, d.W = _lib.dptr(keep[0]), _lib.dptr(keep[1])
+    if exponential:
+        d.theta = _lib.dptr(keep[2])
+    else:
+        keep += [np.ascontiguousarray(keep[2][:N * N]), np.ascontiguousarray(keep[2][N * N:])]
+        d.mu, d.tau = _lib.dptr(keep[3]), _lib.dptr(keep[4])
+    if network:
+        keep.append(np.ascontiguousarray(x[L.adjacency]))
+        d.A = _lib.dptr(keep[-1])
+    if model is None:
+        return DeviceModel(ctx, d)
+    model.update(d)
+    return model
+
+
+def score_samples(process, samples, data, edges, burn=0, every=1, pointwise=False, ctx=None):
+    """Score the draws of a finished chain: samples[burn], samples[burn + every], … (each a params(process) vector, as
+    res.samples holds them) on the blocks `edges` (an int K or an array, as mcmc_'s waic=) of `data`.  Every draw is set into a
+    device model and accumulated as the chain itself would have (nhp_cont_score_accumulate): for the same draws the result
+    is the in-chain score bit for bit.  The process supplies the shapes, the kinds and Δtmax; it is not changed."""
+    if isinstance(every, bool) or int(every) != every or int(every) < 1:
+        raise ValueError("every must be a positive integer")
+    if isinstance(burn, bool) or int(burn) != burn or int(burn) < 0:
+        raise ValueError("burn must be a non-negative integer")
+    samples = list(samples)
+    if int(burn) >= len(samples):
+        raise ValueError(f"no draws left: {len(samples)} samples, burn = {burn}")
+    _, T = _scored_data(process, data, "score_samples")
+    edges = _check_edges(edges, T, "score_samples")
+    ctx = ctx or _lib.default_context()
+    ds = device_dataset(process, data, ctx)
+    model, scorer = None, None
+    try:
+        scorer = _DeviceScore(ctx, ds, edges)
+        for x in samples[int(burn)::int(every)]:
+            model = _set_score_model(model, ctx, process, x)
+            scorer.accumulate(model)
+        return scorer.fetch(pointwise)
+    finally:
+        if scorer is not None:
+            scorer.close()
+
+
 def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_samples=True, device_draws=True,
           ctx=None, moments=False, burn=0, labels_every=1, positions_every=1, diagnostics=False, batch_len=None, ess_below=100.0,
-          rhat_above=1.01):
+          rhat_above=1.01, waic=False, heldout=None, score_every=1, pointwise=False):
     """mcmc!(process, data; nsteps, log_freq, verbose) -- src/inference.jl:49-70.
 
     With `device_draws` (default) a whole sweep -- parents, statistics, conjugate draws -- stays on
@@ -689,8 +901,20 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
     separable by child-node column -- the parents of the children on c, column c's statistics and conjugate draws and
     the sweep of A[:, c] touch column c only, and every random stream is keyed by global event / entry indices -- so
     each rank sweeps its own columns and the chain is the single-GPU chain, value for value; the only exchange per step
-    is the scalar link count the network's ρ update needs, and at the end the ranks' columns (and moments) are merged."""
+    is the scalar link count the network's ρ update needs, and at the end the ranks' columns (and moments) are merged.
+
+    Scoring the chain (csrc/cont_score.hip, definitions: include/nhp.h): `waic=` K (K equal blocks over [0, T]) or
+    an array of block edges gives `res.waic`, `heldout=(data_full, edges)` gives `res.heldout` -- each a ContinuousScore over
+    the cells (block, node), accumulated on the device from the steps >= `burn`, every `score_every`-th of them, with no draw
+    kept: ℓ of a cell is Σ log λ over the node's events in the block minus the compensator's increment over it, so over edges
+    covering [0, T] the cells add up to Σ log λ_c − Λ_c(T), the exact log-likelihood -- not loglikelihood(process, data), which
+    charges every event the full mass of its impulses.  Events of `data_full` before the first edge excite the scored range.
+    `pointwise=True` keeps the K x N array of elpd_i that compare_scores needs.  On the resident route the scorers are attached
+    to the chain's model; step by step they are fed after every kept step; with device_draws=False (or a network model the
+    library does not hold) every scored state is set into a device model kept for scoring.  A LogGaussianCoxProcess baseline,
+    several trials and a ShardedDataset raise NotImplementedError."""
     import ctypes as C
+    plan = _score_plan(process, data, waic, heldout, score_every, burn)      # (every argument checked before the library is touched)
     from .sharded import ShardedDataset, _all_reduce_sum
     from .components import BernoulliNetworkModel, DenseNetworkModel, LatentDistanceNetworkModel, StochasticBlockNetworkModel
     shard = data if isinstance(data, ShardedDataset) else None
@@ -789,60 +1013,85 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
         _lib.check(lib.nhp_cont_model_get_adjacency(ctx.h, model.h, _lib.dptr(A), N * N), ctx.h)
         process.adjacency_matrix = A.reshape((N, N), order="F")
 
-    # The whole chain inside the library (nhp_cont_mcmc_run: the body of src/inference.jl:55-62, one synchronisation per
-    # call) when no step needs the host: no samples kept, device-side network.  `verbose` cuts it at the log points.
-    resident = device_draws and not keep_samples and (not network or device_net) and not host_exchange
-    if resident:
+    scorers, score_model, kept = [], None, 0
+    chain_model_scored = device_draws and (not network or device_net)      # the chain's own device model holds every scored state
+    try:
+        scorers = _open_scorers(ctx, process, ds, plan)
+        # The whole chain inside the library (nhp_cont_mcmc_run: the body of src/inference.jl:55-62, one synchronisation per
+        # call) when no step needs the host: no samples kept, device-side network.  `verbose` cuts it at the log points.
+        resident = device_draws and not keep_samples and (not network or device_net) and not host_exchange
+        if resident:
+            for _, s in scorers:                 # nhp_cont_mcmc_run scores the kept steps itself
+                _lib.check(lib.nhp_cont_model_attach_score(ctx.h, model.h, s.h, int(score_every)), ctx.h)
+            # the driver's kept steps without moments: from −(burn + 1) on (include/nhp.h)
+            run_burn = burn if moments else (-1 - int(burn) if scorers else -1)
+            while res.steps < nsteps:
+                n = min(nsteps - res.steps, log_freq if verbose else nsteps)
+                _lib.check(lib.nhp_cont_mcmc_run(ctx.h, comm.h if comm is not None else None, ds.h, model.h, C.byref(pri), net_a, net_b,
+                                                 seed, res.steps, n, run_burn), ctx.h)
+                res.steps += n
+                if verbose and res.steps % log_freq == 0:
+                    res.elapsed = time.time() - start
+                    print(f" > step: {res.steps}, elapsed: {res.elapsed}")
+            _pull_params(process, model, ctx)
+            if network:
+                pull_adjacency()
+                pull_rho()
         while res.steps < nsteps:
-            n = min(nsteps - res.steps, log_freq if verbose else nsteps)
-            _lib.check(lib.nhp_cont_mcmc_run(ctx.h, comm.h if comm is not None else None, ds.h, model.h, C.byref(pri), net_a, net_b,
-                                             seed, res.steps, n, burn if moments else -1), ctx.h)
-            res.steps += n
-            if verbose and res.steps % log_freq == 0:
+            scored = bool(scorers) and res.steps >= burn and kept % int(score_every) == 0
+            if device_draws:
+                _lib.check(lib.nhp_cont_gibbs_step(ctx.h, ds.h, model.h, C.byref(pri), seed, res.steps), ctx.h)
+                last = keep_samples or res.steps == nsteps - 1 or (scored and not chain_model_scored)
+                if network and device_net and sbm:
+                    _lib.check(lib.nhp_cont_sbm_step(ctx.h, ds.h, model.h, seed, res.steps), ctx.h)
+                elif network and device_net and latent:
+                    _lib.check(lib.nhp_cont_latent_step(ctx.h, ds.h, model.h, seed, res.steps), ctx.h)
+                elif network and device_net and not host_exchange:
+                    _lib.check(lib.nhp_cont_network_step(ctx.h, comm.h if comm is not None else None, ds.h, model.h, net_a, net_b,
+                                                         seed, res.steps), ctx.h)
+                elif network and device_net:                     # ranks without an RCCL clique: the one exchange of a step, by hand
+                    nl = C.c_double()
+                    _lib.check(lib.nhp_cont_network_sweep(ctx.h, ds.h, model.h, seed, res.steps, C.byref(nl)), ctx.h)
+                    links = float(_all_reduce_sum(np.array([nl.value]), ctx)[0])
+                    _lib.check(lib.nhp_cont_network_rho(ctx.h, model.h, net_a, net_b, links, float(process.ndims()) ** 2, seed, res.steps), ctx.h)
+                elif network:                                    # a network model the library does not hold: host-side ρ
+                    links = resample_adjacency_matrix_(process, ds, seed=seed, step=res.steps, model=model, fetch=last, ctx=ctx)
+                    process.network.resample_links_(links, process.ndims() ** 2, rng)
+                if moments and res.steps >= burn:
+                    _lib.check(lib.nhp_cont_model_moments_accumulate(ctx.h, model.h), ctx.h)
+                if scored and chain_model_scored:
+                    for _, s in scorers:
+                        s.accumulate(model)
+                if last:
+                    _pull_params(process, model, ctx)
+                    if network and device_net:
+                        pull_adjacency()
+                        pull_rho()
+                x = process.params() if keep_samples else None
+            else:
+                x = resample_(process, ds, rng, step=res.steps, seed=seed, ctx=ctx, labels_every=int(labels_every),
+                              positions_every=int(positions_every))
+                if latent:
+                    res.exhausted = getattr(res, "exhausted", 0) + net.exhausted
+            if scored and not chain_model_scored:    # the state as params(process) into a device model kept for scoring
+                score_model = _set_score_model(score_model, ctx, process, process.params())
+                for _, s in scorers:
+                    s.accumulate(score_model)
+            if scorers and res.steps >= burn:
+                kept += 1
+            if keep_samples:
+                res.samples.append(x)
+            res.steps += 1
+            if res.steps % log_freq == 0 and verbose:
                 res.elapsed = time.time() - start
                 print(f" > step: {res.steps}, elapsed: {res.elapsed}")
-        _pull_params(process, model, ctx)
-        if network:
-            pull_adjacency()
-            pull_rho()
-    while res.steps < nsteps:
-        if device_draws:
-            _lib.check(lib.nhp_cont_gibbs_step(ctx.h, ds.h, model.h, C.byref(pri), seed, res.steps), ctx.h)
-            last = keep_samples or res.steps == nsteps - 1
-            if network and device_net and sbm:
-                _lib.check(lib.nhp_cont_sbm_step(ctx.h, ds.h, model.h, seed, res.steps), ctx.h)
-            elif network and device_net and latent:
-                _lib.check(lib.nhp_cont_latent_step(ctx.h, ds.h, model.h, seed, res.steps), ctx.h)
-            elif network and device_net and not host_exchange:
-                _lib.check(lib.nhp_cont_network_step(ctx.h, comm.h if comm is not None else None, ds.h, model.h, net_a, net_b,
-                                                     seed, res.steps), ctx.h)
-            elif network and device_net:                     # ranks without an RCCL clique: the one exchange of a step, by hand
-                nl = C.c_double()
-                _lib.check(lib.nhp_cont_network_sweep(ctx.h, ds.h, model.h, seed, res.steps, C.byref(nl)), ctx.h)
-                links = float(_all_reduce_sum(np.array([nl.value]), ctx)[0])
-                _lib.check(lib.nhp_cont_network_rho(ctx.h, model.h, net_a, net_b, links, float(process.ndims()) ** 2, seed, res.steps), ctx.h)
-            elif network:                                    # a network model the library does not hold: host-side ρ
-                links = resample_adjacency_matrix_(process, ds, seed=seed, step=res.steps, model=model, fetch=last, ctx=ctx)
-                process.network.resample_links_(links, process.ndims() ** 2, rng)
-            if moments and res.steps >= burn:
-                _lib.check(lib.nhp_cont_model_moments_accumulate(ctx.h, model.h), ctx.h)
-            if last:
-                _pull_params(process, model, ctx)
-                if network and device_net:
-                    pull_adjacency()
-                    pull_rho()
-            x = process.params() if keep_samples else None
-        else:
-            x = resample_(process, ds, rng, step=res.steps, seed=seed, ctx=ctx, labels_every=int(labels_every),
-                          positions_every=int(positions_every))
-            if latent:
-                res.exhausted = getattr(res, "exhausted", 0) + net.exhausted
-        if keep_samples:
-            res.samples.append(x)
-        res.steps += 1
-        if res.steps % log_freq == 0 and verbose:
-            res.elapsed = time.time() - start
-            print(f" > step: {res.steps}, elapsed: {res.elapsed}")
+        for name, s in scorers:
+            setattr(res, name, s.fetch(pointwise))
+    finally:                                     # the scorers are not the model's: detach before they are destroyed
+        if scorers and model is not None:
+            lib.nhp_cont_model_attach_score(ctx.h, model.h, None, 1)
+        for _, s in scorers:
+            s.close()
     res.elapsed = time.time() - start
     res.status = "complete"
     if shard is not None and shard.world > 1:

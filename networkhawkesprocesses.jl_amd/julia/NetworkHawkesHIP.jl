@@ -1469,4 +1469,39 @@ function score_fetch_planes(score::Ptr{Cvoid}, N::Integer, R::Integer; ctx=conte
     return lse, mean, m2
 end
 
+# --- scoring a continuous chain (include/nhp.h: nhp_cont_score_*) ---------------------------------------------------------------
+# The same wrappers for a continuous dataset handle `ds` and an nhp_cont_model handle `m`: a scorer on the blocks
+# [edges[k], edges[k+1]) of the recording (0 <= edges[1] < ... < edges[end] <= duration), K = length(edges) - 1.
+function cont_score_create(ds::Ptr{Cvoid}, edges::AbstractVector{<:Real}; ctx=context())
+    e = Vector{Float64}(edges)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:nhp_cont_score_create, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Int64, Ref{Ptr{Cvoid}}),
+                ctx.h, ds, e, Int64(length(e)), h), ctx.h)
+    return h[]
+end
+cont_score_destroy(score::Ptr{Cvoid}) = ccall((:nhp_cont_score_destroy, libnhp), Cvoid, (Ptr{Cvoid},), score)
+cont_score_reset!(score::Ptr{Cvoid}; ctx=context()) =
+    check(ccall((:nhp_cont_score_reset, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), ctx.h, score), ctx.h)
+cont_score_accumulate!(score::Ptr{Cvoid}, m::Ptr{Cvoid}; ctx=context()) =
+    check(ccall((:nhp_cont_score_accumulate, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), ctx.h, score, m), ctx.h)
+# every >= 1; score = C_NULL detaches every scorer of the model (detach before a scorer is destroyed)
+cont_score_attach!(m::Ptr{Cvoid}, score::Ptr{Cvoid}, every::Integer=1; ctx=context()) =
+    check(ccall((:nhp_cont_model_attach_score, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64), ctx.h, m, score, Int64(every)), ctx.h)
+
+# -> (summary::NamedTuple over SCORE_FIELDS, per_node 3 x N, pointwise K x N or nothing)
+function cont_score_fetch(score::Ptr{Cvoid}, N::Integer, K::Integer; pointwise=false, ctx=context())
+    summary, per_node = Vector{Float64}(undef, 10), Vector{Float64}(undef, 3 * N)
+    pw = pointwise ? Matrix{Float64}(undef, K, N) : nothing
+    check(ccall((:nhp_cont_score_fetch, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                ctx.h, score, summary, per_node, pointwise ? pointer(pw) : Ptr{Float64}(C_NULL)), ctx.h)
+    return NamedTuple{SCORE_FIELDS}(Tuple(summary)), permutedims(reshape(per_node, Int(N), 3)), pw
+end
+
+function cont_score_fetch_planes(score::Ptr{Cvoid}, N::Integer, K::Integer; ctx=context())
+    lse, mean, m2 = (Matrix{Float64}(undef, K, N) for _ in 1:3)
+    check(ccall((:nhp_cont_score_fetch_planes, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                ctx.h, score, lse, mean, m2), ctx.h)
+    return lse, mean, m2
+end
+
 end # module

@@ -258,30 +258,35 @@ __global__ __launch_bounds__(256) void k_ps_sort(int N, nhp_pslices ps, const ui
 // k_windowed_slices (fused and deferred exit) and k_slices_batch (every S, DEFER or not), so the routes the tests hold to each
 // other with `==` agree by construction.  Q = S·NW (model, wave) pairs, q = m·NW + w; behind the 2^(j/64) table the kernels keep
 //   park [Q][17]  the integral's partial sums, one per quad of lanes (16 a wave; the 17th pads the banks for the read below)
-//   mant [Q]      the wave's mantissa product, in [0.5, 1)
-//   wexp [Q]      its exponent sum (int32)
-// Σ log λ: a lane carries a mantissa product and an exponent sum over its children.  The 64 mantissas are multiplied in the
-// wave (the sum tree's steps; 64 factors in [0.5, 1) stay above 2^-64: no underflow) and the exponents added as integers;
-// after the barrier lane q of the first wave takes ONE logarithm for (model, wave) q, and thread 0 adds them wave by wave.
+//   qman [Q][17]  the wave's mantissa products, one per quad of lanes, each in [2^-4, 1)
+//   qexp [Q][17]  the quads' exponent sums (int32)
+// Σ log λ: a lane carries a mantissa product and an exponent sum over its children.  A wave multiplies the mantissas of every
+// quad of lanes (two DPP steps: lanes i and i^1, then the pairs) and adds the quad's exponents as integers, and the lanes with
+// (lane & 3) == 0 park the 16 products and 16 sums of (model, wave).  After the barrier lane q of the first wave multiplies the 16
+// of (model, wave) q in lane order (16 factors >= 2^-4 stay >= 2^-64: no underflow), adds the 16 exponents, renormalises once
+// with frexp and takes ONE logarithm; thread 0 adds the logarithms wave by wave.
 // A lane without a child holds {1.0, 0} and changes nothing; a wave without a slice leaves {0.5, 1}: log 0.5 + ln 2 is exactly 0
 // (nhp_log's ln2_hi + ln2_lo rounds to the constant below).  A child with λ = 0 makes the product 0 and the sum -inf, one
 // with λ < 0 made its mantissa NaN in the row loop.
 // The integral: a wave stops its sum after the two quad steps, in the head, and parks 16 partial sums; lane q of the first wave
 // adds the 16 of (model, wave) q in lane order at the exit, where it is alone anyway, and thread 0 adds the waves' sums in wave
 // order.  Nothing of the integral is live in the row loop.
-__host__ __device__ constexpr size_t sl_exit_bytes(const int S, const int NW) { return ((size_t)S * NW * (17 * 8 + 8 + 4) + 15) / 16 * 16; }
+__host__ __device__ constexpr size_t sl_exit_bytes(const int S, const int NW) { return ((size_t)S * NW * (17 * 8 + 17 * 8 + 17 * 4) + 15) / 16 * 16; }
+
+// What a workgroup of `block` threads with the columns of S models takes: the block sums' words, the columns, the 2^(j/64)
+// table, the shared exit's area for the waves actually launched.  Every launcher and the pairing rule take this one line.
+static inline size_t sl_lds_bytes(const int N, const int S, const int block)
+{
+    return 320 + 16 * ((size_t)N + 1) * (size_t)S + 512 + sl_exit_bytes(S, block / 64);
+}
 
 __device__ __forceinline__ double sl_dpp_mul(const double v, const int sel)
 {
 #pragma clang fp contract(off)
     const int lo = __double2loint(v), hi = __double2hiint(v);
     int plo, phi;
-    switch (sel) {
-    case 0: plo = __builtin_amdgcn_mov_dpp(lo, 0xB1, 0xF, 0xF, true); phi = __builtin_amdgcn_mov_dpp(hi, 0xB1, 0xF, 0xF, true); break;   // quad_perm [1,0,3,2]
-    case 1: plo = __builtin_amdgcn_mov_dpp(lo, 0x4E, 0xF, 0xF, true); phi = __builtin_amdgcn_mov_dpp(hi, 0x4E, 0xF, 0xF, true); break;   // quad_perm [2,3,0,1]
-    case 2: plo = __builtin_amdgcn_mov_dpp(lo, 0x141, 0xF, 0xF, true); phi = __builtin_amdgcn_mov_dpp(hi, 0x141, 0xF, 0xF, true); break; // row_half_mirror
-    default: plo = __builtin_amdgcn_mov_dpp(lo, 0x140, 0xF, 0xF, true); phi = __builtin_amdgcn_mov_dpp(hi, 0x140, 0xF, 0xF, true); break; // row_mirror
-    }
+    if (sel == 0) { plo = __builtin_amdgcn_mov_dpp(lo, 0xB1, 0xF, 0xF, true); phi = __builtin_amdgcn_mov_dpp(hi, 0xB1, 0xF, 0xF, true); }   // quad_perm [1,0,3,2]
+    else { plo = __builtin_amdgcn_mov_dpp(lo, 0x4E, 0xF, 0xF, true); phi = __builtin_amdgcn_mov_dpp(hi, 0x4E, 0xF, 0xF, true); }          // quad_perm [2,3,0,1]
     return v * __hiloint2double(phi, plo);
 }
 
@@ -303,43 +308,51 @@ __device__ __forceinline__ void sl_exit_sums(const double (&prod)[S], const int 
 #pragma clang fp contract(off)
     constexpr int Q = S * NW;
     static_assert(Q <= 64, "one lane of the first wave per (model, wave)");
-    double *mant = park + Q * 17;
-    int *wexp = reinterpret_cast<int *>(mant + Q);
+    double *qman = park + Q * 17;
+    int *qexp = reinterpret_cast<int *>(qman + Q * 17);
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    double p[S];
+    int e[S];
 #pragma unroll
     for (int m = 0; m < S; ++m) {
-        double p = prod[m];
-        p = sl_dpp_mul(p, 0);
-        p = sl_dpp_mul(p, 1);
-        p = sl_dpp_mul(p, 2);
-        p = sl_dpp_mul(p, 3);
-        const int lo = __double2loint(p), hi = __double2hiint(p);
-        double r = __hiloint2double(__builtin_amdgcn_readlane(hi, 0), __builtin_amdgcn_readlane(lo, 0));
-        r *= __hiloint2double(__builtin_amdgcn_readlane(hi, 16), __builtin_amdgcn_readlane(lo, 16));
-        r *= __hiloint2double(__builtin_amdgcn_readlane(hi, 32), __builtin_amdgcn_readlane(lo, 32));
-        r *= __hiloint2double(__builtin_amdgcn_readlane(hi, 48), __builtin_amdgcn_readlane(lo, 48));
-        int e = pexp[m];
-        e += __builtin_amdgcn_mov_dpp(e, 0xB1, 0xF, 0xF, true);
-        e += __builtin_amdgcn_mov_dpp(e, 0x4E, 0xF, 0xF, true);
-        e += __builtin_amdgcn_mov_dpp(e, 0x141, 0xF, 0xF, true);
-        e += __builtin_amdgcn_mov_dpp(e, 0x140, 0xF, 0xF, true);
-        const int es = __builtin_amdgcn_readlane(e, 0) + __builtin_amdgcn_readlane(e, 16) + __builtin_amdgcn_readlane(e, 32) +
-                       __builtin_amdgcn_readlane(e, 48) + __builtin_amdgcn_frexp_exp(r);
-        if (lane == 0) {
-            mant[m * NW + w] = __builtin_amdgcn_frexp_mant(r);
-            wexp[m * NW + w] = es;
+        p[m] = sl_dpp_mul(sl_dpp_mul(prod[m], 0), 1);
+        e[m] = pexp[m];
+        e[m] += __builtin_amdgcn_mov_dpp(e[m], 0xB1, 0xF, 0xF, true);
+        e[m] += __builtin_amdgcn_mov_dpp(e[m], 0x4E, 0xF, 0xF, true);
+    }
+    int ql = lane;                                                  // (formed here: taken from the head's parking address it would
+    asm volatile("" : "+v"(ql));                                    //  stay in two registers through the row loop)
+    if ((ql & 3) == 0) {
+        const int o = w * 17 + (ql >> 2);
+#pragma unroll
+        for (int m = 0; m < S; ++m) {
+            qman[m * NW * 17 + o] = p[m];
+            qexp[m * NW * 17 + o] = e[m];
         }
     }
     __syncthreads();
     if (w != 0) return;                                             // (the helper's end: the callers' exits go on)
     if (lane < Q) {
-        const double lg = nhp_log(mant[lane]) + (double)wexp[lane] * 6.93147180559945286e-01;
+        double *pm = qman + lane * 17;
+        const int *pe = qexp + lane * 17;
         double *pk = park + lane * 17;
-        double si = 0.0;
+        // (three groups of 16 loads, each used up before the next is requested: all 48 in flight under the logarithm would set
+        //  the kernel's register count)
+        double r = pm[0], si = 0.0;
+        int es = pe[0];
+#pragma unroll
+        for (int i = 1; i < 16; ++i) r *= pm[i];
+        asm volatile("" : "+v"(r) : : "memory");
+#pragma unroll
+        for (int i = 1; i < 16; ++i) es += pe[i];
+        asm volatile("" : "+v"(es) : : "memory");
 #pragma unroll
         for (int i = 0; i < 16; ++i) si += pk[i];
-        mant[lane] = lg;                                            // (each lane its own entries, read above by itself only)
+        asm volatile("" : "+v"(si) : : "memory");
+        es += __builtin_amdgcn_frexp_exp(r);
+        const double lg = nhp_log(__builtin_amdgcn_frexp_mant(r)) + (double)es * 6.93147180559945286e-01;
+        pm[0] = lg;                                                 // (each lane its own entries, read above by itself only)
         pk[0] = si;
     }
     // the first wave alone: its LDS operations complete in order, the fences keep the compiler from moving them
@@ -350,7 +363,7 @@ __device__ __forceinline__ void sl_exit_sums(const double (&prod)[S], const int 
 #pragma unroll
         for (int m = 0; m < S; ++m) {
             double x = 0.0, y = 0.0;
-            for (int q = 0; q < NW; ++q) { x += mant[m * NW + q]; y += park[(m * NW + q) * 17]; }
+            for (int q = 0; q < NW; ++q) { x += qman[(m * NW + q) * 17]; y += park[(m * NW + q) * 17]; }
             sx[m] = x; sy[m] = y;
         }
     }
@@ -740,26 +753,34 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
     double integ[S];
 #pragma unroll
     for (int m = 0; m < S; ++m) integ[m] = 0.0;
+    // `first`: the item is its node's first, the one that carries the node's integral.  DEFER is launched on all_sole datasets
+    // only (nhp_launch_slices_pair refuses others): every item is first, and the kernel knows it when it is compiled; elsewhere
+    // it is one wave-uniform branch around the integral's terms.  A model without a mask multiplies by a = 1.0: 1.0·w is w.
+    const bool first = DEFER ? true : it.first != 0;
+    gptr cntp = (gptr)a.cnt;
+    auto at = [](gptr base, const uint32_t off) {                   // a wave-uniform base and the node as a 32-bit BYTE offset
+        return *(gptr)((const __attribute__((address_space(1))) char *)base + off);
+    };
     for (int p0 = 0; p0 < N; p0 += UN * BLOCK) {
         double cnt_[UN];
+        uint32_t off_[UN];
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
             const int p = p0 + u * BLOCK + tid;
-            cnt_[u] = it.first ? a.cnt[(uint32_t)(p < N ? p : 0)] : 0.0;
+            off_[u] = (uint32_t)(p < N ? p : 0) * 8u;
+            cnt_[u] = first ? at(cntp, off_[u]) : 0.0;
         }
 #pragma unroll
         for (int g = 0; g < S; g += G) {
-            double w_[G][UN], th_[G][UN], a_[G][UN];
+            double w_[G][UN], th_[G][UN], a_[G][UN], wv_[G][UN];
 #pragma unroll
             for (int mm = 0; mm < G; ++mm) {
                 const int m = g + mm;
 #pragma unroll
                 for (int u = 0; u < UN; ++u) {
-                    const int p = p0 + u * BLOCK + tid;
-                    const uint32_t k = (uint32_t)(p < N ? p : 0);
-                    w_[mm][u] = (Wc[m] + c0)[k];
-                    th_[mm][u] = (Tc[m] + c0)[k];
-                    a_[mm][u] = Ac[m] ? (Ac[m] + c0)[k] : 1.0;
+                    w_[mm][u] = at(Wc[m] + c0, off_[u]);
+                    th_[mm][u] = at(Tc[m] + c0, off_[u]);
+                    a_[mm][u] = Ac[m] ? at(Ac[m] + c0, off_[u]) : 1.0;
                 }
             }
             if (p0 == 0 && g == 0) {                                 // (N >= 1 on every route that launches this kernel: the first trip always runs)
@@ -774,20 +795,26 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
 #pragma unroll
                 for (int u = 0; u < UN; ++u) {
                     const int p = p0 + u * BLOCK + tid;
+                    wv_[mm][u] = a_[mm][u] * w_[mm][u];                // windowed route: the integral is masked too
                     if (p < N) {
-                        double wv = w_[mm][u];
-                        if (Ac[m]) wv = a_[mm][u] * wv;                // windowed route: the integral is masked too
-                        col[(size_t)m * (N + 1) + p] = make_double2(-((th_[mm][u] * unit) * 92.33248261689366), wv * th_[mm][u]);
-                        if (it.first) integ[m] += cnt_[u] * wv;
+                        col[(size_t)m * (N + 1) + p] = make_double2(-((th_[mm][u] * unit) * 92.33248261689366), wv_[mm][u] * th_[mm][u]);
+                        if (DEFER) integ[m] += cnt_[u] * wv_[mm][u];   // (the same terms in the same order as below)
                     }
                 }
+            }
+            if (!DEFER && first) {
+#pragma unroll
+                for (int mm = 0; mm < G; ++mm)
+#pragma unroll
+                    for (int u = 0; u < UN; ++u)
+                        if (p0 + u * BLOCK + tid < N) integ[g + mm] += cnt_[u] * wv_[mm][u];
             }
         }
     }
 #pragma unroll
     for (int m = 0; m < S; ++m) {
         if (tid == 0) col[(size_t)m * (N + 1) + N] = make_double2(0.0, 0.0);
-        if (it.first) integ[m] += sl_flat_integral(lam0[m], a.duration);
+        if (first) integ[m] += sl_flat_integral(lam0[m], a.duration);
         sl_exit_park<NW>(integ[m], park, m, w, lane);
     }
     if (tid < 64) etab[tid] = tab_v;
@@ -1349,8 +1376,13 @@ static nhp_status launch_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const 
     if (deferred) *deferred = false;
     if (!ds->d_sl_row || ds->n_items <= 0 || m->impulse_kind != NHP_IMPULSE_EXPONENTIAL) return NHP_OK;
     if (nhp_slices_off(d_grad ? "NHP_GRAD_SLICES" : nullptr)) return NHP_OK;     // (NHP_GRAD_SLICES=0: the two-pass route of cont_grad.hip)
-    // (behind the column and the 2^(j/64) table: the gradient's 1/λ, or the shared exit's sums for the largest workgroup)
-    const size_t lds = 320 + 16 * ((size_t)ds->N + 1) + 512 + (d_grad ? 8 * ((size_t)ds->max_item + 1) : sl_exit_bytes(1, 16));
+    // waves per workgroup from the slices an item has (one item per node at N >= 1024: ~15 slices; short items at small N);
+    // rows per request from the windows' length.  NHP_SLICES_CFG = "BLOCK,C" overrides (tools/dbg/slicesweep.sh)
+    int B, C;
+    slices_cfg(ds, &B, &C);
+    if (!((B == 64 || B == 128 || B == 256 || B == 512 || B == 1024) && (C == 2 || C == 4 || C == 8))) { B = 256; C = 4; }
+    // (behind the column and the 2^(j/64) table: the gradient's 1/λ, or the shared exit's sums for the waves of this launch)
+    const size_t lds = d_grad ? 320 + 16 * ((size_t)ds->N + 1) + 512 + 8 * ((size_t)ds->max_item + 1) : sl_lds_bytes(ds->N, 1, B);
     if (lds > 160 * 1024) return NHP_OK;
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_ctx_reserve_partials(ctx, 2 * (size_t)ds->n_items));
@@ -1364,10 +1396,6 @@ static nhp_status launch_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const 
         ps.grad = d_grad;
         ps.direct = direct ? 1 : 0;
     }
-    // waves per workgroup from the slices an item has (one item per node at N >= 1024: ~15 slices; short items at small N);
-    // rows per request from the windows' length.  NHP_SLICES_CFG = "BLOCK,C" overrides (tools/dbg/slicesweep.sh)
-    int B, C;
-    slices_cfg(ds, &B, &C);
     dim3 grid((unsigned)ds->n_items);
     bool ok = false;
     const bool flat = m->baseline_kind == NHP_BASELINE_HOMOGENEOUS;
@@ -1395,7 +1423,6 @@ static nhp_status launch_slices(nhp_ctx *ctx, const nhp_cont_dataset *ds, const 
     }
 #define NHP_SROW(b) NHP_SCASE(b, 2) NHP_SCASE(b, 4) NHP_SCASE(b, 8)
     NHP_SROW(64) NHP_SROW(128) NHP_SROW(256) NHP_SROW(512) NHP_SROW(1024)
-    if (!ok) { B = 256; C = 4; NHP_SCASE(256, 4) }
 #undef NHP_SLAUNCH
 #undef NHP_SROW
 #undef NHP_SCASE
@@ -1500,8 +1527,20 @@ extern "C" int64_t nhp_debug_parent_slices(const nhp_cont_dataset *ds, uint32_t 
     return n;
 }
 
+// the workgroup size and the rows per request of the fused k_slices_batch on this dataset
+// (the columns of S models leave room for two workgroups of 512 per CU at N = 1024, S = 4; NHP_SETS_CFG = "BLOCK,C" overrides)
+static void sets_cfg(const nhp_cont_dataset *ds, int *B, int *C)
+{
+    const double mean_rows = ds->n_slices > 0 ? (double)ds->sl_rows / (double)ds->n_slices : 0.0;
+    *B = (ds->max_item + 63) / 64 >= 6 ? 512 : 256;
+    *C = mean_rows >= 16.0 ? 4 : 2;
+    if (const char *cfg = getenv("NHP_SETS_CFG")) sscanf(cfg, "%d,%d", B, C);
+    if (*B != 256 && *B != 1024) *B = 512;
+    if (*C != 2) *C = 4;
+}
+
 template <int S>
-static nhp_status launch_sets(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *const *ms, int32_t slot0, size_t lds)
+static nhp_status launch_sets(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *const *ms, int32_t slot0, int B, int C, size_t lds)
 {
     NHP_TRY(nhp_ctx_reserve_partials(ctx, 2 * (size_t)ds->n_items * S));
     nhp_cont_args a = nhp_make_args(ds, ms[0]);
@@ -1513,11 +1552,7 @@ static nhp_status launch_sets(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nh
         st.p1[k] = m->d_p1; st.W[k] = m->d_W; st.A[k] = m->has_A ? m->d_A : nullptr; st.lambda0[k] = m->d_lambda0;
         st.out[k] = ctx->d_results + slot0 + (k < S ? k : 0);
     }
-    const double mean_rows = ds->n_slices > 0 ? (double)ds->sl_rows / (double)ds->n_slices : 0.0;
     dim3 grid((unsigned)ds->n_items);
-    // (the columns of S models leave room for two workgroups of 512 per CU at N = 1024, S = 4; NHP_SETS_CFG = "BLOCK,C" overrides)
-    int B = (ds->max_item + 63) / 64 >= 6 ? 512 : 256, C = mean_rows >= 16.0 ? 4 : 2;
-    if (const char *cfg = getenv("NHP_SETS_CFG")) sscanf(cfg, "%d,%d", &B, &C);
 #define NHP_BL(b, cc)                                                                                                  \
     do {                                                                                                               \
         if (lds > 64 * 1024)                                                                                           \
@@ -1540,10 +1575,12 @@ nhp_status nhp_launch_slices_batch(nhp_ctx *ctx, const nhp_cont_dataset *ds, con
     if (nhp_slices_off("NHP_BATCH_SLICES")) return NHP_OK;
     for (int k = 0; k < S; ++k)
         if (!ms[k] || ms[k]->impulse_kind != NHP_IMPULSE_EXPONENTIAL || ms[k]->baseline_kind != NHP_BASELINE_HOMOGENEOUS) return NHP_OK;
-    const size_t lds = 320 + 16 * ((size_t)ds->N + 1) * (size_t)S + 512 + sl_exit_bytes(S, 16);
+    int B, C;
+    sets_cfg(ds, &B, &C);
+    const size_t lds = sl_lds_bytes(ds->N, S, B);
     if (lds > 160 * 1024) return NHP_OK;
     NHP_HIP(ctx, hipSetDevice(ctx->device));
-    if (S == 4) NHP_TRY(launch_sets<4>(ctx, ds, ms, slot0, lds)); else NHP_TRY(launch_sets<2>(ctx, ds, ms, slot0, lds));
+    if (S == 4) NHP_TRY(launch_sets<4>(ctx, ds, ms, slot0, B, C, lds)); else NHP_TRY(launch_sets<2>(ctx, ds, ms, slot0, B, C, lds));
     *launched = true;
     return NHP_OK;
 }
@@ -1557,17 +1594,21 @@ bool nhp_slices_pair_eligible(const nhp_cont_dataset *ds, const nhp_cont_model *
     if (m->impulse_kind != NHP_IMPULSE_EXPONENTIAL || m->baseline_kind != NHP_BASELINE_HOMOGENEOUS) return false;
     if (!ds->all_sole || nhp_is_column_shard(ds) || nhp_slices_off(nullptr)) return false;
     if (const char *pl = getenv("NHP_PLIST")) if (atoi(pl) == 0) return false;
-    if (4 * (320 + 32 * ((size_t)ds->N + 1) + 512 + sl_exit_bytes(2, 8)) > 160 * 1024) return false;   // (N = 1024: 4 x 36000 bytes)
     int B, C;
     slices_cfg(ds, &B, &C);
-    return (B == 64 || B == 128 || B == 256 || B == 512) && (C == 2 || C == 4 || C == 8);
+    if (!((B == 64 || B == 128 || B == 256 || B == 512) && (C == 2 || C == 4 || C == 8))) return false;
+    return 4 * sl_lds_bytes(ds->N, 2, B) <= 160 * 1024;            // (N = 1024, 512 threads: 4 x 39072 bytes)
 }
 
 // ms[0] -> slot[0], ms[1] -> slot[1] (different slots), both eligible and batch-compatible: one launch of k_slices_batch<B, C, 2,
 // DEFER> on the current lane with launch_slices' (B, C); both slots are marked pending with that B.
 nhp_status nhp_launch_slices_pair(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *const *ms, const int32_t *slot)
 {
-    const size_t lds = 320 + 32 * ((size_t)ds->N + 1) + 512 + sl_exit_bytes(2, 8);
+    // (k_slices_batch<., ., 2, DEFER> is compiled for items that are all their node's first: nhp_slices_pair_eligible's rule)
+    if (!ds->all_sole) { nhp_set_error(ctx, "paired enqueue: the dataset has nodes with more than one item"); return NHP_EINVAL; }
+    int B, C;
+    slices_cfg(ds, &B, &C);
+    const size_t lds = sl_lds_bytes(ds->N, 2, B);
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     for (int k = 0; k < 2; ++k) NHP_TRY(nhp_ctx_reserve_slot_partials(ctx, slot[k], 2 * (size_t)ds->n_items));
     nhp_cont_args a = nhp_make_args(ds, ms[0]);
@@ -1579,8 +1620,6 @@ nhp_status nhp_launch_slices_pair(nhp_ctx *ctx, const nhp_cont_dataset *ds, cons
         st.p1[k] = m->d_p1; st.W[k] = m->d_W; st.A[k] = m->has_A ? m->d_A : nullptr; st.lambda0[k] = m->d_lambda0;
         st.out[k] = ctx->d_slot_partials[slot[k & 1]];
     }
-    int B, C;
-    slices_cfg(ds, &B, &C);
     dim3 grid((unsigned)ds->n_items);
     bool ok = false;
 #define NHP_PCASE(b, cc)                                                                                              \

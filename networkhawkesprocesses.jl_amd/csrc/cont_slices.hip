@@ -16,6 +16,7 @@
 //  * Σ log λ from a running mantissa product and exponent sum per lane: multiplied and added across the wave, one logarithm
 //    per wave (the shared exit, sl_exit_sums); the fused last-workgroup reduction as in k_windowed.
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "nhp_internal.h"
@@ -280,6 +281,25 @@ static inline size_t sl_lds_bytes(const int N, const int S, const int block)
     return 320 + 16 * ((size_t)N + 1) * (size_t)S + 512 + sl_exit_bytes(S, block / 64);
 }
 
+// The pair term of k_slices_batch and k_windowed_slices<., ., ., GRAD = false> is nhp_exp_term_fast / _slow (nhp_math.h) on the
+// table's BIASED entries; the gradient build, the logit-normal and sampler kernels keep nhp_exp_neg_tab_scaled and the plain ones.
+// Which path the item's terms take (nhp_math.h: the limit).  Every thread compares the column entries IT forms with
+// sl_term_limit -- `bad` is true for |cx| above it, NaN and +-inf -- a wave leaves the OR of its lanes in flg[wave] before the
+// head's barrier, and behind it every wave reads all NW words: one wave-uniform answer per workgroup, for every model of the pass.
+// flg = the block sums' words, which nothing touches before the exit's barrier.
+__device__ __forceinline__ double sl_term_limit(const int dbits) { return __builtin_ldexp(NHP_EXP_TERM_LIMIT, -dbits); }
+__device__ __forceinline__ bool sl_term_outside(const double cx, const double lim) { return !(__builtin_fabs(cx) <= lim); }
+__device__ __forceinline__ void sl_limit_post(const bool bad, int *__restrict__ flg, const int w, const int lane)
+{
+    const bool any = __builtin_amdgcn_ballot_w64(bad) != 0;
+    if (lane == 0) flg[w] = any ? 1 : 0;
+}
+template <int NW>
+__device__ __forceinline__ bool sl_limit_all_inside(const int *__restrict__ flg, const int lane)
+{
+    return __builtin_amdgcn_ballot_w64(flg[lane & (NW - 1)] != 0) == 0;
+}
+
 __device__ __forceinline__ double sl_dpp_mul(const double v, const int sel)
 {
 #pragma clang fp contract(off)
@@ -389,7 +409,7 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
     extern __shared__ __align__(16) unsigned char smem[];
     double *red = reinterpret_cast<double *>(smem);                 // [2 * NW <= 32] + flag at [32]
     double2 *col = reinterpret_cast<double2 *>(smem + 320);         // [N + 1] {-θ·unit·64/ln2, a·w·θ}; [N] = {0, 0}
-    double *etab = reinterpret_cast<double *>(col + a.N + 1);       // [64] 2^(j/64)
+    double *etab = reinterpret_cast<double *>(col + a.N + 1);       // [64] 2^(j/64); !GRAD: biased (nhp_exp_tab_biased)
     double *ginv = etab + 64;                                       // GRAD: [max_item + 1] 1/λ of the item's children; [max_item] = 0
     double *park = etab + 64;                                       // !GRAD: the shared exit's sums (sl_exit_bytes(1, NW))
     const int tid = threadIdx.x, lane = tid & 63;
@@ -420,6 +440,8 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
     // (their addresses need the slice table only), so they arrive while the column is being written to LDS.
     constexpr int UN = BLOCK >= 512 ? 2 : 4;
     const double unit = __builtin_ldexp(a.dt_max, -sl.dbits);      // Δtmax · 2^-dbits
+    const double tlim = GRAD ? 0.0 : sl_term_limit(sl.dbits);
+    bool outside = false;
     int j = w;
     uint32_t row0 = 0;
     int K = 0;
@@ -452,49 +474,74 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
                     if (mask_integral) wint = wv;
                 }
                 col[p] = make_double2(-((th_[u] * unit) * 92.33248261689366), wv * th_[u]);   // term = (a·w·θ)·exp(-(θ·unit)·q), the rate times 64/ln 2
+                if constexpr (!GRAD) outside |= sl_term_outside(-((th_[u] * unit) * 92.33248261689366), tlim);
                 integ += cnt_[u] * wint;
             }
         }
     }
-    if (tid < 64) etab[tid] = tab_v;
+    if (tid < 64) etab[tid] = GRAD ? tab_v : nhp_exp_tab_biased(tab_v, tid);
     if (tid == 0) col[N] = make_double2(0.0, 0.0);
     if (GRAD && tid == 0) ginv[ps.max_item] = 0.0;
     if (out && it.first) integ += sl_baseline_integral_col(a, c);
-    if (!GRAD) sl_exit_park<NW>(integ, park, 0, w, lane);           // (the gradient build keeps its own exit: DESIGN 3.1d)
+    if constexpr (!GRAD) {
+        sl_exit_park<NW>(integ, park, 0, w, lane);                  // (the gradient build keeps its own exit: DESIGN 3.1d)
+        sl_limit_post(outside, reinterpret_cast<int *>(red), w, lane);
+    }
     __syncthreads();
     NHP_SL_STAMP(1);
+    const bool fast = GRAD ? false : sl_limit_all_inside<NW>(reinterpret_cast<const int *>(red), lane);
 
     const double lam0 = FLAT ? a.lambda0[c] : 0.0;
     const uint32_t dmask = sl.dmask;
     const int nsh = sl.nsh;
+    const nhp_exp_term_consts ekc = nhp_exp_term_setup();
     // the high delay bits under the exponent of 2^52 (one v_bfi_b32): the double 2^52 + delay, minus 2^52
     auto delay = [&](const uint32_t lo, const uint32_t h, const uint32_t mask) {
         uint32_t hw;
         asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(hw) : "s"(mask), "v"(h), "v"(0x43300000u));
         return __hiloint2double((int)hw, (int)lo) - 4503599627370496.0;
     };
-    auto term = [&](const uint32_t lo, const uint32_t h) {
+    // A term, once per way of forming it: MODE 0 the gradient build's (nhp_exp_neg_tab_scaled: phase B shares its table), 1 and 2
+    // the fast and the slow path of nhp_exp_term -- chosen per slice by ONE wave-uniform branch, outside the row loop.
+    auto term = [&](auto mode, const uint32_t lo, const uint32_t h) {
+        constexpr int MODE = decltype(mode)::value;
         const double v = delay(lo, h, dmask);
         const double2 cw = col[h >> nsh];
-        return cw.y * nhp_exp_neg_tab_scaled(cw.x * v, etab);
+        if constexpr (MODE == 0) return cw.y * nhp_exp_neg_tab_scaled(cw.x * v, etab);
+        else if constexpr (MODE == 1) return cw.y * nhp_exp_term_fast(cw.x, v, etab, ekc);
+        else return cw.y * nhp_exp_term_slow(cw.x, v, etab, ekc);
     };
     // A request that lies wholly inside the slice is summed as C independent straight-line chains (their LDS round trips --
-    // column entry, then the 2^(j/64) entry -- overlap); the slice's last request goes row by row behind wave-uniform
+    // column entry, then the table's entry -- overlap); the slice's last request goes row by row behind wave-uniform
     // branches.  The sum itself is sequential in both: most recent parent first, the reference's order.
-    auto sum = [&](const chunk &q, const int r, const int K, double s) {
-        if (r + C <= K) {
+    // (The slow path goes row by row throughout: summed as chains, its longer terms would set the kernel's register count.)
+    auto sum = [&](auto mode, const chunk &q, const int r, const int K, double s) {
+        constexpr int MODE = decltype(mode)::value;
+        if (MODE != 2 && r + C <= K) {
             double t[C];
 #pragma unroll
-            for (int u = 0; u < C; ++u) t[u] = term(q.lo[u], q.hi[u]);
+            for (int u = 0; u < C; ++u) t[u] = term(mode, q.lo[u], q.hi[u]);
 #pragma unroll
             for (int u = 0; u < C; ++u) s += t[u];
         } else {
 #pragma unroll
             for (int u = 0; u < C; ++u)
-                if (r + u < K) s += term(q.lo[u], q.hi[u]);
+                if (r + u < K) s += term(mode, q.lo[u], q.hi[u]);
         }
         return s;
     };
+    // the rows of one slice, the next slice's first request under its last rows (a macro, not a lambda: the gradient build's
+    // instructions stay what they were before there were three modes)
+#define NHP_SL_ROWS(mode)                                                                                             \
+    for (int r0 = 0; r0 < K; r0 += 2 * C) {                                                                           \
+        request(qb, sl.lo, sl.hi, row0, r0 + C);                                                                      \
+        asm volatile("" ::: "memory");                                                                                \
+        s = sum(mode, qa, r0, K, s);                                                                                  \
+        const bool more = r0 + 2 * C < K;                                                                             \
+        request(qa, sl.lo, sl.hi, more ? row0 : row0n, more ? r0 + 2 * C : 0);                                        \
+        asm volatile("" ::: "memory");                                                                                \
+        s = sum(mode, qb, r0 + C, K, s);                                                                              \
+    }
     double prod = 1.0, gsum = 0.0;
     int pexp = 0;
     int rnd = 0;                                                    // the wave's slices in snake order (nhp_slice_of)
@@ -505,15 +552,10 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
         if (jn < ns) { row0n = sl.row[s0 + jn]; Kn = (int)(sl.row[s0 + jn + 1] - row0n); }
         double s = 0.0;
         if (K <= 0) request(qa, sl.lo, sl.hi, row0n, 0);
-        for (int r0 = 0; r0 < K; r0 += 2 * C) {
-            request(qb, sl.lo, sl.hi, row0, r0 + C);
-            asm volatile("" ::: "memory");
-            s = sum(qa, r0, K, s);
-            const bool more = r0 + 2 * C < K;
-            request(qa, sl.lo, sl.hi, more ? row0 : row0n, more ? r0 + 2 * C : 0);
-            asm volatile("" ::: "memory");
-            s = sum(qb, r0 + C, K, s);
-        }
+        if constexpr (GRAD) { NHP_SL_ROWS((std::integral_constant<int, 0>{})) }
+        else if (fast) { NHP_SL_ROWS((std::integral_constant<int, 1>{})) }
+        else { NHP_SL_ROWS((std::integral_constant<int, 2>{})) }
+#undef NHP_SL_ROWS
         const int kk = 64 * j + lane;
         if (kk < nchild) {
             const double tk = FLAT ? 0.0 : a.child_w[it.kbeg + kk].t;
@@ -746,6 +788,8 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
 #pragma unroll
     for (int m = 0; m < S; ++m) asm("" : "+s"(Wc[m]), "+s"(Tc[m]), "+s"(Ac[m]));   // all of them in SGPRs before the first request
     const double unit = __builtin_ldexp(a.dt_max, -sl.dbits);
+    const double tlim = sl_term_limit(sl.dbits);
+    bool outside = false;
     int j = w;
     uint32_t row0 = 0;
     int K = 0;
@@ -797,7 +841,9 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
                     const int p = p0 + u * BLOCK + tid;
                     wv_[mm][u] = a_[mm][u] * w_[mm][u];                // windowed route: the integral is masked too
                     if (p < N) {
-                        col[(size_t)m * (N + 1) + p] = make_double2(-((th_[mm][u] * unit) * 92.33248261689366), wv_[mm][u] * th_[mm][u]);
+                        const double cx = -((th_[mm][u] * unit) * 92.33248261689366);
+                        col[(size_t)m * (N + 1) + p] = make_double2(cx, wv_[mm][u] * th_[mm][u]);
+                        outside |= sl_term_outside(cx, tlim);
                         if (DEFER) integ[m] += cnt_[u] * wv_[mm][u];   // (the same terms in the same order as below)
                     }
                 }
@@ -817,73 +863,83 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
         if (first) integ[m] += sl_flat_integral(lam0[m], a.duration);
         sl_exit_park<NW>(integ[m], park, m, w, lane);
     }
-    if (tid < 64) etab[tid] = tab_v;
+    if (tid < 64) etab[tid] = nhp_exp_tab_biased(tab_v, tid);
+    sl_limit_post(outside, reinterpret_cast<int *>(red), w, lane);
     __syncthreads();
     NHP_SL_STAMP(1);
+    const bool fast = sl_limit_all_inside<NW>(reinterpret_cast<const int *>(red), lane);   // every entry of every model of the pass
 
     const uint32_t dmask = sl.dmask;
     const int nsh = sl.nsh;
+    const nhp_exp_term_consts ekc = nhp_exp_term_setup();
     const uint32_t plane = (uint32_t)(N + 1) * 16u;                 // bytes between the models' columns
-    auto terms = [&](const uint32_t lo, const uint32_t h, double (&acc)[S]) {
-        uint32_t hw;
-        asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(hw) : "s"(dmask), "v"(h), "v"(0x43300000u));
-        const double v = __hiloint2double((int)hw, (int)lo) - 4503599627370496.0;
-        const unsigned char *base = reinterpret_cast<const unsigned char *>(col) + ((h >> nsh) << 4);
-#pragma unroll
-        for (int m = 0; m < S; ++m) {
-            const double2 cw = *reinterpret_cast<const double2 *>(base + m * plane);
-            acc[m] = __builtin_fma(cw.y, nhp_exp_neg_tab_scaled(cw.x * v, etab), acc[m]);
-        }
-    };
-    auto sum = [&](const chunk &q, const int r, const int K, double (&acc)[S]) {
-        if (r + C <= K) {
-#pragma unroll
-            for (int u = 0; u < C; ++u) terms(q.lo[u], q.hi[u], acc);
-        } else {
-#pragma unroll
-            for (int u = 0; u < C; ++u)
-                if (r + u < K) terms(q.lo[u], q.hi[u], acc);
-        }
-    };
     double prod[S];
     int pexp[S];
 #pragma unroll
     for (int m = 0; m < S; ++m) { prod[m] = 1.0; pexp[m] = 0; }
     int rnd = 0;                                                    // the wave's slices in snake order (nhp_slice_of)
-    while (j < ns) {
-        const int jn = nhp_slice_of(++rnd, w, NW);
-        uint32_t row0n = 0;
-        int Kn = 0;
-        if (jn < ns) { row0n = sl.row[s0 + jn]; Kn = (int)(sl.row[s0 + jn + 1] - row0n); }
-        double acc[S];
-#pragma unroll
-        for (int m = 0; m < S; ++m) acc[m] = 0.0;
-        if (K <= 0) request(qa, row0n, 0);
-        for (int r0 = 0; r0 < K; r0 += 2 * C) {
-            request(qb, row0, r0 + C);
-            asm volatile("" ::: "memory");
-            sum(qa, r0, K, acc);
-            const bool more = r0 + 2 * C < K;
-            request(qa, more ? row0 : row0n, more ? r0 + 2 * C : 0);
-            asm volatile("" ::: "memory");
-            sum(qb, r0 + C, K, acc);
-        }
-        const int kk = 64 * j + lane;
-        if (kk < nchild) {
+    // the walk, once for each path of nhp_exp_term: ONE wave-uniform branch out here, none in the rows
+    auto walk = [&](auto fastc) {
+        constexpr bool FAST = decltype(fastc)::value;
+        auto terms = [&](const uint32_t lo, const uint32_t h, double (&acc)[S]) {
+            uint32_t hw;
+            asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(hw) : "s"(dmask), "v"(h), "v"(0x43300000u));
+            const double v = __hiloint2double((int)hw, (int)lo) - 4503599627370496.0;
+            const unsigned char *base = reinterpret_cast<const unsigned char *>(col) + ((h >> nsh) << 4);
 #pragma unroll
             for (int m = 0; m < S; ++m) {
-                const double lam = lam0[m] + acc[m];
-                prod[m] *= lam < 0.0 ? __builtin_nan("") : __builtin_amdgcn_frexp_mant(lam);
-                pexp[m] += __builtin_amdgcn_frexp_exp(lam);
+                const double2 cw = *reinterpret_cast<const double2 *>(base + m * plane);
+                if constexpr (FAST) acc[m] = __builtin_fma(cw.y, nhp_exp_term_fast(cw.x, v, etab, ekc), acc[m]);
+                else acc[m] = __builtin_fma(cw.y, nhp_exp_term_slow(cw.x, v, etab, ekc), acc[m]);
             }
-        }
+        };
+        // (the slow path row by row throughout: interleaved, its longer terms would set the kernel's register count)
+        auto sum = [&](const chunk &q, const int r, const int K, double (&acc)[S]) {
+            if (FAST && r + C <= K) {
 #pragma unroll
-        for (int m = 0; m < S; ++m) {
-            pexp[m] += __builtin_amdgcn_frexp_exp(prod[m]);
-            prod[m] = __builtin_amdgcn_frexp_mant(prod[m]);
+                for (int u = 0; u < C; ++u) terms(q.lo[u], q.hi[u], acc);
+            } else {
+#pragma unroll
+                for (int u = 0; u < C; ++u)
+                    if (r + u < K) terms(q.lo[u], q.hi[u], acc);
+            }
+        };
+        while (j < ns) {
+            const int jn = nhp_slice_of(++rnd, w, NW);
+            uint32_t row0n = 0;
+            int Kn = 0;
+            if (jn < ns) { row0n = sl.row[s0 + jn]; Kn = (int)(sl.row[s0 + jn + 1] - row0n); }
+            double acc[S];
+#pragma unroll
+            for (int m = 0; m < S; ++m) acc[m] = 0.0;
+            if (K <= 0) request(qa, row0n, 0);
+            for (int r0 = 0; r0 < K; r0 += 2 * C) {
+                request(qb, row0, r0 + C);
+                asm volatile("" ::: "memory");
+                sum(qa, r0, K, acc);
+                const bool more = r0 + 2 * C < K;
+                request(qa, more ? row0 : row0n, more ? r0 + 2 * C : 0);
+                asm volatile("" ::: "memory");
+                sum(qb, r0 + C, K, acc);
+            }
+            const int kk = 64 * j + lane;
+            if (kk < nchild) {
+#pragma unroll
+                for (int m = 0; m < S; ++m) {
+                    const double lam = lam0[m] + acc[m];
+                    prod[m] *= lam < 0.0 ? __builtin_nan("") : __builtin_amdgcn_frexp_mant(lam);
+                    pexp[m] += __builtin_amdgcn_frexp_exp(lam);
+                }
+            }
+#pragma unroll
+            for (int m = 0; m < S; ++m) {
+                pexp[m] += __builtin_amdgcn_frexp_exp(prod[m]);
+                prod[m] = __builtin_amdgcn_frexp_mant(prod[m]);
+            }
+            j = jn; row0 = row0n; K = Kn;
         }
-        j = jn; row0 = row0n; K = Kn;
-    }
+    };
+    if (fast) walk(std::true_type{}); else walk(std::false_type{});
     NHP_SL_STAMP_WAVE();
     NHP_SL_STAMP(2);
     double sx[S], sy[S];

@@ -176,6 +176,94 @@ __device__ __forceinline__ double nhp_exp_neg_tab_scaled(double t, const double 
     return __builtin_ldexp(__builtin_fma(tb, p, tb), k >> 6);
 }
 
+// ---- the slice kernels' pair term: rate and delay apart ---------------------------------------------------------
+// e^(cx·v·ln2/64) on the same 64 entries and the same degree-5 polynomial, with cx = the column entry's rate times 64/ln 2 (the
+// records' delay unit and the sign folded in) and v = the decoded delay, an integer below 2^dbits, passed apart.  Against
+// nhp_exp_neg_tab_scaled(cx·v), 12 instructions instead of 15 and 9 fp64 instead of 12:
+//  * the reduction is three instructions instead of four: km = fma(cx, v, 1.5·2^52) rounds the EXACT product to an integer k
+//    (to nearest, ties to even: one ulp of [2^52, 2^53) is 1) and carries k in its low dword as a two's-complement int while
+//    |cx·v| < 2^31; kf = km - 1.5·2^52 is k as a double (exact), u = fma(cx, v, -kf) the reduced argument rounded ONCE (the
+//    product cx·v is never rounded on its own: the 8e-14 of the helper above at large arguments is gone; 2.3e-16 per term
+//    against exp, tests/test_slices_exp_host.py);
+//  * the scaling is one integer add instead of a shift and v_ldexp_f64: the LDS table holds entry j = 2^(j/64) with j << 14
+//    SUBTRACTED from its high dword (nhp_exp_tab_biased), so adding k << 14 = (n << 20) + (j << 14), k = 64·n + j, leaves
+//    2^(j/64) with n added to its exponent field: 2^(j/64)·2^n exactly while that stays a normal number.  Scaling the entry
+//    BEFORE the fmac gives the bits ldexp gives after it as long as nothing underflows: both round tb·(1 + p)·2^n once.
+// The fast path is valid while |cx|·v < NHP_EXP_TERM_LIMIT = 65000 = 1015.625·64 for every v the records can hold: then
+// |k| <= 65000, n = k >> 6 >= -1016 and the result >= 2^-1016·(1 - ln2/128) is a normal number (smallest normal exponent:
+// -1022; the same margin covers positive arguments, n <= 1015), and |cx·v| < 2^16 is far inside the low dword.  In the model's
+// terms: θ·Δtmax <= 1015.625·ln 2 = 703.98.  The caller compares |cx| with the limit over 2^dbits once per column entry (NaN
+// and ±inf fail the comparison) and sends items with an entry outside it down nhp_exp_term_slow: the same reduction and
+// polynomial, k from a saturating v_cvt_i32_f64 of kf (any magnitude; NaN gives 0 and u = NaN carries it), the entry un-biased,
+// v_ldexp_f64 -- terms underflow gradually and to 0 as in nhp_exp_neg_tab_scaled.  Wherever both are valid they return the
+// same bits, so a model's value does not depend on which path its pass took.
+#define NHP_EXP_TERM_MAGIC 6755399441055744.0                      // 1.5·2^52
+#define NHP_EXP_TERM_LIMIT 65000.0
+
+// entry j of the LDS table from 2^(j/64): j << 14 subtracted from the high dword
+__device__ __forceinline__ double nhp_exp_tab_biased(const double e, const int j)
+{
+    return __hiloint2double((int)((uint32_t)__double2hiint(e) - ((uint32_t)j << 14)), __double2loint(e));
+}
+
+// The constants the callers hold in registers through their row loops, made opaque ONCE outside them: 1.5·2^52 in a scalar pair
+// (left to itself the compiler keeps it in vector registers) and the polynomial's leading coefficient in a vector pair (a VOP3
+// instruction reads one scalar operand, and the Horner step's addend is the other coefficient; left to itself the compiler copies
+// it from scalar registers again in every block of rows, into a second pair).
+struct nhp_exp_term_consts { double magic, top; };
+__device__ __forceinline__ nhp_exp_term_consts nhp_exp_term_setup()
+{
+    nhp_exp_term_consts c;
+    c.magic = NHP_EXP_TERM_MAGIC;
+    c.top = 0x1.5d87fe78a6731p-40;
+    asm("" : "+s"(c.magic));
+    asm("" : "+v"(c.top));
+    return c;
+}
+
+// e^(u·ln2/64) - 1 for |u| <= 1/2: nhp_exp_neg_tab_scaled's coefficients, `top` the leading one
+__device__ __forceinline__ double nhp_exp_term_poly(const double u, const double top)
+{
+    double p;
+    asm("v_fma_f64 %0, %1, %2, %3\n\t"
+        "v_fma_f64 %0, %0, %2, %4\n\t"
+        "v_fma_f64 %0, %0, %2, %5\n\t"
+        "v_fma_f64 %0, %0, %2, %6\n\t"
+        "v_mul_f64 %0, %0, %2"
+        : "=&v"(p)
+        : "v"(top), "v"(u), "s"(0x1.3b2ab6fba4e77p-31), "s"(0x1.c6b08d704a0c0p-23), "s"(0x1.ebfbdff82c58fp-15), "s"(0x1.62e42fefa39efp-7));
+    return p;
+}
+
+// `tabb`: 64 biased entries in LDS; `kc`: nhp_exp_term_setup()
+__device__ __forceinline__ double nhp_exp_term_fast(const double cx, const double v, const double *tabb, const nhp_exp_term_consts &kc)
+{
+#pragma clang fp contract(off)
+    const double km = __builtin_fma(cx, v, kc.magic);
+    const double kf = km - kc.magic;
+    const double u = __builtin_fma(cx, v, -kf);
+    const uint32_t k = (uint32_t)__double2loint(km);
+    const double tb = tabb[k & 63u];
+    const double ts = __hiloint2double((int)((k << 14) + (uint32_t)__double2hiint(tb)), __double2loint(tb));   // one v_lshl_add_u32
+    return __builtin_fma(ts, nhp_exp_term_poly(u, kc.top), ts);
+}
+
+__device__ __forceinline__ double nhp_exp_term_slow(const double cx, const double v, const double *tabb, const nhp_exp_term_consts &kc)
+{
+#pragma clang fp contract(off)
+    const double km = __builtin_fma(cx, v, kc.magic);
+    const double kf = km - kc.magic;
+    const double u = __builtin_fma(cx, v, -kf);
+    const int k = (int)kf;                                          // v_cvt_i32_f64: saturates, NaN -> 0
+    // k saturated: the term is 0 (or inf) whatever u is -- and past |cx·v| = 2^106, where the constant no longer registers in km,
+    // u is the product's own rounding error, large enough to overflow the polynomial.  (kf = ±inf keeps u = NaN, as the parent.)
+    const double us = (__builtin_fabs(kf) >= 0x1p31 && __builtin_fabs(kf) < __builtin_inf()) ? 0.0 : u;
+    const uint32_t j = (uint32_t)k & 63u;
+    const double tb = tabb[j];
+    const double t1 = __hiloint2double((int)((j << 14) + (uint32_t)__double2hiint(tb)), __double2loint(tb));
+    return __builtin_ldexp(__builtin_fma(t1, nhp_exp_term_poly(us, kc.top), t1), k >> 6);
+}
+
 __device__ __forceinline__ double nhp_pdf_exponential_tab(double r, double dt, const double *tab)
 {
 #pragma clang fp contract(off)

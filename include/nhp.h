@@ -494,6 +494,53 @@ nhp_status nhp_cont_model_moments_fetch(nhp_ctx *ctx, const nhp_cont_model *mode
 nhp_status nhp_cont_model_diagnostics_configure(nhp_ctx *ctx, nhp_cont_model *model, int64_t batch_len, int64_t n_planned);
 nhp_status nhp_cont_model_diagnostics_fetch(nhp_ctx *ctx, const nhp_cont_model *model, double ess_below, double rhat_above,
                                             double *summary, double *ess, double *mcse, double *rhat, int64_t len);
+/* Streaming quantiles of a chain that keeps no samples: credible intervals of every parameter entry by the extended P²
+ * algorithm (csrc/chain_quantiles.hip), one separate launch after a kept step's _moments_accumulate -- the
+ * sums and the diagnostics keep their kernels and their bits, and with nothing configured nothing is launched.  The
+ * definition is the contract; tests/chain_quantiles_ref.py restates it in numpy and the tests hold the kernel to it bit
+ * for bit.
+ *
+ * m probabilities 0 < p_1 < … < p_m < 1, 1 ≤ m ≤ NHP_QUANT_MAX; K = 2m + 3 markers.  With p_0 = 0 and p_{m+1} = 1 the marker
+ * probabilities are d_{2j} = p_j and d_{2j+1} = (p_j + p_{j+1})/2 (the sum rounded, then halved), so d_0 = 0, d_{K−1} = 1.
+ * Per entry: heights q_0 … q_{K−1} (fp64), positions pos_1 … pos_{K−2} (int32; pos_0 = 1 and pos_{K−1} = n are implied) and n,
+ * the number of values seen (one host-side counter for all entries).  Feeding a value x:
+ *   n < K:  insert x into the sorted prefix q_0 … q_{n−1}, after equal values; n += 1; when n reaches K, pos_i = i + 1.
+ *   otherwise, in this order:
+ *     1. x < q_0: q_0 = x, k = 0;  else x ≥ q_{K−1}: q_{K−1} = x, k = K − 2;  else k = the largest i ≤ K − 2 with q_i ≤ x.
+ *     2. pos_i += 1 for every i > k; n += 1.
+ *     3. for i = 1 … K − 2 ascending, each step seeing the positions and heights the earlier ones left:
+ *          δ = (1 + (n − 1)·d_i) − pos_i, in fp64 as written (n − 1 and pos_i converted, product, sum, difference);
+ *          s = +1 if δ ≥ 1 and pos_{i+1} − pos_i > 1;  s = −1 if δ ≤ −1 and pos_{i−1} − pos_i < −1;  otherwise nothing moves;
+ *          a = pos_i − pos_{i−1}, b = pos_{i+1} − pos_i, c = pos_{i+1} − pos_{i−1}, converted to fp64:
+ *          q′ = q_i + (s/c)·( ((a + s)·(q_{i+1} − q_i))/b + ((b − s)·(q_i − q_{i−1}))/a );
+ *          q_i = q′ if q_{i−1} < q′ < q_{i+1}, else q_i + (s·(q_{i+s} − q_i))/(pos_{i+s} − pos_i);  then pos_i += s.
+ * IEEE fp64 + − × ÷ and int32 → fp64 conversions only, every operation rounded on its own (no contraction).
+ * At fetch the estimate of p_j is q_{2j}; the smallest and largest value seen are q_0 and q_{K−1}.  With n < K every estimate
+ * is NaN while min and max are exact once n ≥ 1 (q_0 and q_{n−1} of the sorted prefix; NaN at n = 0).  A constant entry gives
+ * that constant everywhere.
+ *
+ * Entries: the first P = N + N²·(2 | 3) of the sums' order, [λ0; θ | μ; τ; W].  vec(A) is 0 / 1, its mean says everything: it
+ * has no state and its slots of `values`, `min`, `max` are NaN.  effective_weights (fixed at _configure) feeds A[p,c]·W[p,c],
+ * ONE rounded product, for W[p,c] of a model with an adjacency matrix -- the quantity whose interval answers "is this link
+ * there"; 0: the raw W, as the moments see it.  The Bernoulli network's scalar ρ (nhp_cont_model_set_rho; neither a block nor
+ * a latent distance network) has one state of its own: rho [m + 2] = {the m estimates, min, max}, NaN otherwise.
+ *
+ * _configure(probs, m, every, effective_weights): m = 0 turns quantiles off and frees the planes; anything else (re)allocates
+ * K planes of P + 1 doubles and K − 2 of P + 1 int32 (100 bytes per entry at m = 3) and zeroes them and n.  NHP_EINVAL for
+ * m > NHP_QUANT_MAX, probabilities that do not increase strictly inside (0, 1), every < 1; NHP_ENOTIMPL for an LGCP baseline;
+ * NHP_ENOMEM leaves quantiles off and the moments and diagnostics usable.  _moments_reset zeroes the planes and n too.
+ * _accumulate feeds the model's current state (step-by-step drivers call it after _moments_accumulate, on the kept steps they
+ * choose); nhp_cont_mcmc_run calls it itself after every `every`-th kept step's _moments_accumulate, counted from the
+ * configure or the last _moments_reset, and is NHP_ENOTIMPL on a column shard with quantiles configured.
+ * _fetch: values [m][len] (row j: the estimate of p_{j+1}), min, max [len] nullable, rho [m + 2] nullable, len = the sums'
+ * length, *count = n; NHP_EINVAL with nothing configured. */
+#define NHP_QUANT_MAX 4
+nhp_status nhp_cont_model_quantiles_configure(nhp_ctx *ctx, nhp_cont_model *model, const double *probs, int32_t m, int32_t every,
+                                              int32_t effective_weights);
+nhp_status nhp_cont_model_quantiles_accumulate(nhp_ctx *ctx, nhp_cont_model *model);
+nhp_status nhp_cont_model_quantiles_fetch(nhp_ctx *ctx, const nhp_cont_model *model, double *values /* [m][len] */,
+                                          double *min, double *max /* [len], nullable */, double *rho /* [m+2], nullable */,
+                                          int64_t len, int64_t *count);
 /* the uniform stream itself (host side, same bits as the kernel draws) */
 void nhp_uniform_stream(uint64_t seed, uint64_t step, int64_t n, double *u);
 
@@ -661,6 +708,17 @@ nhp_status nhp_disc_model_moments_fetch(nhp_ctx *ctx, const nhp_disc_model *mode
 nhp_status nhp_disc_model_diagnostics_configure(nhp_ctx *ctx, nhp_disc_model *model, int64_t batch_len, int64_t n_planned);
 nhp_status nhp_disc_model_diagnostics_fetch(nhp_ctx *ctx, const nhp_disc_model *model, double ess_below, double rhat_above,
                                             double *summary, double *ess, double *mcse, double *rhat, int64_t len);
+/* Streaming quantiles of the model's kept steps: the contract of nhp_cont_model_quantiles_* above, definition by definition.
+ * The entries with a state are the first P of the sums' order:
+ *   has_A:  [λ0; vec(W); vec(θ)], P = N + N² + N²B; vec(A)'s slots are NaN; effective_weights feeds A[p,c]·W[p,c];
+ *   else:   [λ0; vec(W .* θ)], P = len, x the one rounded product the sums take (effective_weights has nothing to act on).
+ * rho: the scalar's state once nhp_disc_model_set_rho has run.  nhp_disc_mcmc_run feeds every `every`-th kept step. */
+nhp_status nhp_disc_model_quantiles_configure(nhp_ctx *ctx, nhp_disc_model *model, const double *probs, int32_t m, int32_t every,
+                                              int32_t effective_weights);
+nhp_status nhp_disc_model_quantiles_accumulate(nhp_ctx *ctx, nhp_disc_model *model);
+nhp_status nhp_disc_model_quantiles_fetch(nhp_ctx *ctx, const nhp_disc_model *model, double *values /* [m][len] */,
+                                          double *min, double *max /* [len], nullable */, double *rho /* [m+2], nullable */,
+                                          int64_t len, int64_t *count);
 /* mcmc!(process::DiscreteHawkesProcess, data) inside the library, the loop of nhp_cont_mcmc_run: n_steps times
  * nhp_disc_model_gibbs_step with the priors (alpha0 … gamma0), nhp_disc_model_network_step when the model has A, and one
  * nhp_disc_model_moments_accumulate from chain step `burn` on (burn < 0: never); ONE host synchronise, at the end; between the

@@ -31,7 +31,7 @@ from .parents import (Cascades, cascades, map_parents, node_counts, parent_count
 from .inference import (ExpectedStatistics, Information, MarkovChainMonteCarlo, MaximumLikelihood, StandardErrors,  # noqa: F401
                         em_, expected_statistics, hessian_vector_product, logprior, observed_information,
                         resample_adjacency_matrix_, standard_errors,
-                        ContinuousScore, score_samples)
+                        ContinuousScore, score_samples, ChainQuantiles)
 from . import inference as _inf
 from . import synthetic  # noqa: F401
 from .synthetic import rand  # noqa: F401   rand(process, duration): the reference's exported simulator name

@@ -22,6 +22,7 @@ LL_RECURSIVE = 1
 LL_FULL_RECURSION = 2
 MAX_SLOTS = 4096
 DIAG_GROUPS, DIAG_FIELDS = 6, 9
+QUANT_MAX = 4
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -131,6 +132,9 @@ def _declare(lib):
     f("nhp_cont_model_moments_fetch", i32, _vp, _vp, _dp, _dp, i64, C.POINTER(i64))
     f("nhp_cont_model_diagnostics_configure", i32, _vp, _vp, i64, i64)
     f("nhp_cont_model_diagnostics_fetch", i32, _vp, _vp, dbl, dbl, _dp, _dp, _dp, _dp, i64)
+    f("nhp_cont_model_quantiles_configure", i32, _vp, _vp, _dp, i32, i32, i32)
+    f("nhp_cont_model_quantiles_accumulate", i32, _vp, _vp)
+    f("nhp_cont_model_quantiles_fetch", i32, _vp, _vp, _dp, _dp, _dp, _dp, i64, C.POINTER(i64))
     f("nhp_cont_loglik", i32, _vp, _vp, _vp, i32, _dp)
     f("nhp_cont_loglik_enqueue", i32, _vp, _vp, _vp, i32, i32)
     f("nhp_ctx_fetch", i32, _vp, i32, i32, _dp)
@@ -162,6 +166,9 @@ def _declare(lib):
     f("nhp_disc_model_moments_fetch", i32, _vp, _vp, _dp, _dp, i64, C.POINTER(i64))
     f("nhp_disc_model_diagnostics_configure", i32, _vp, _vp, i64, i64)
     f("nhp_disc_model_diagnostics_fetch", i32, _vp, _vp, dbl, dbl, _dp, _dp, _dp, _dp, i64)
+    f("nhp_disc_model_quantiles_configure", i32, _vp, _vp, _dp, i32, i32, i32)
+    f("nhp_disc_model_quantiles_accumulate", i32, _vp, _vp)
+    f("nhp_disc_model_quantiles_fetch", i32, _vp, _vp, _dp, _dp, _dp, _dp, i64, C.POINTER(i64))
     f("nhp_disc_mcmc_run", i32, _vp, _vp, _vp, dbl, dbl, dbl, dbl, dbl, dbl, dbl, u64, u64, i64, i64)
     f("nhp_disc_score_create", i32, _vp, _vp, i64, i64, C.POINTER(_vp))
     f("nhp_disc_score_destroy", None, _vp)

@@ -91,7 +91,10 @@ def run_chains(make_process, data, n_chains, nsteps, base_seed=0, burn=0, ctx=No
     """Run this rank's share of `n_chains` independent mcmc! chains and gather every chain's summary.
 
     make_process(chain) must build a fresh process (its parameters are overwritten by the chain).
-    Works single-process (world = 1) and under torch.distributed.run (one rank per GPU)."""
+    Works single-process (world = 1) and under torch.distributed.run (one rank per GPU).
+
+    Streaming quantiles (mcmc_'s quantiles=) are not gathered: the marker states of different chains do not merge into the
+    markers of the pooled draws.  Run mcmc_ itself for a chain's credible intervals."""
     from .inference import mcmc_
     from .continuous import device_dataset
     rank, world = 0, 1

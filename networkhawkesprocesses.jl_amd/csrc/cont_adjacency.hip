@@ -740,6 +740,7 @@ extern "C" nhp_status nhp_cont_mcmc_run(nhp_ctx *ctx, nhp_comm *comm, const nhp_
     NHP_TRY(nhp_check_pair(ctx, ds, m));
     if (m->has_A && !m->sbm && !m->latent && !m->d_rho) { nhp_set_error(ctx, "mcmc_run: set the network's link probability first (nhp_cont_model_set_rho)"); return NHP_EINVAL; }
     if (m->diag && burn >= 0 && (comm || nhp_is_column_shard(ds))) { nhp_set_error(ctx, "mcmc_run: convergence diagnostics are not available on a column shard"); return NHP_ENOTIMPL; }
+    if (m->quant && burn >= 0 && (comm || nhp_is_column_shard(ds))) { nhp_set_error(ctx, "mcmc_run: streaming quantiles are not available on a column shard"); return NHP_ENOTIMPL; }
     // attached scorers (nhp_cont_model_attach_score) see the kept steps: those the moments take, or with the moments off
     // (burn < 0) the steps from −(burn + 1) on.  Their scratch is reserved here, so that no step grows it under work in flight.
     const bool scoring = m->score[0] || m->score[1];
@@ -753,7 +754,10 @@ extern "C" nhp_status nhp_cont_mcmc_run(nhp_ctx *ctx, nhp_comm *comm, const nhp_
         if (m->has_A && m->sbm) NHP_TRY(nhp_cont_sbm_step(ctx, ds, m, seed, step));      // (net_alpha, net_beta: the model has its own priors)
         else if (m->has_A && m->latent) NHP_TRY(nhp_cont_latent_step(ctx, ds, m, seed, step));
         else if (m->has_A) NHP_TRY(nhp_cont_network_step(ctx, comm, ds, m, net_alpha, net_beta, seed, step));
-        if (burn >= 0 && (int64_t)step >= burn) NHP_TRY(nhp_cont_model_moments_accumulate(ctx, m));
+        if (burn >= 0 && (int64_t)step >= burn) {
+            NHP_TRY(nhp_cont_model_moments_accumulate(ctx, m));
+            if (m->quant) NHP_TRY(nhp_quant_kept_step(ctx, m));
+        }
         if (scoring && (int64_t)step >= score_from)
             for (int j = 0; j < 2; ++j) {
                 if (!m->score[j]) continue;

@@ -729,6 +729,7 @@ extern "C" void nhp_cont_model_destroy(nhp_cont_model *m)
     nhp_sbm_free(m);
     nhp_latent_free(m);
     nhp_diag_free(m);
+    nhp_quant_release(&m->quant);
     (void)hipFree(m->d_params); (void)hipFree(m->d_grid); (void)hipFree(m->d_A);
     delete m;
 }

@@ -649,6 +649,7 @@ extern "C" nhp_status nhp_cont_model_moments_reset(nhp_ctx *ctx, nhp_cont_model 
     if (m->latent) NHP_TRY(nhp_latent_moments_reset(ctx, m));
     m->mom_count = 0;
     if (m->diag) NHP_TRY(nhp_diag_reset(ctx, m));
+    if (m->quant) NHP_TRY(nhp_quant_reset(ctx, m));
     return NHP_OK;
 }
 

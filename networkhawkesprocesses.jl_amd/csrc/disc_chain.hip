@@ -148,6 +148,7 @@ extern "C" void nhp_disc_model_destroy(nhp_disc_model *m)
     if (!m) return;
     if (m->ctx) { (void)hipSetDevice(m->ctx->device); (void)hipStreamSynchronize(m->ctx->main()); }
     nhp_diag_release(&m->diag);
+    nhp_quant_release(&m->quant);
     (void)hipFree(m->d_mom);
     (void)hipFree(m->d_block);
     delete m;
@@ -257,6 +258,7 @@ extern "C" nhp_status nhp_disc_model_moments_reset(nhp_ctx *ctx, nhp_disc_model 
     if (m->d_rho) NHP_HIP(ctx, hipMemsetAsync(m->d_rho + 1, 0, 2 * sizeof(double), ctx->main()));
     m->mom_count = 0;
     if (m->diag) NHP_TRY(nhp_diag_zero(ctx, &m->diag, len));
+    if (m->quant) NHP_TRY(nhp_quant_reset(ctx, m));
     return NHP_OK;
 }
 
@@ -347,7 +349,10 @@ extern "C" nhp_status nhp_disc_mcmc_run(nhp_ctx *ctx, const nhp_disc_dataset *ds
         const uint64_t step = step0 + (uint64_t)k;
         NHP_TRY(nhp_disc_model_gibbs_step(ctx, ds, m, alpha0, beta0, kappa, nu, gamma0, seed, step));
         if (m->has_A) NHP_TRY(nhp_disc_model_network_step(ctx, ds, m, net_alpha, net_beta, seed, step));
-        if (burn >= 0 && (int64_t)step >= burn) NHP_TRY(nhp_disc_model_moments_accumulate(ctx, m));
+        if (burn >= 0 && (int64_t)step >= burn) {
+            NHP_TRY(nhp_disc_model_moments_accumulate(ctx, m));
+            if (m->quant) NHP_TRY(nhp_quant_kept_step(ctx, m));
+        }
         if (scoring && (int64_t)step >= score_from)
             for (int j = 0; j < 2; ++j) {
                 if (!m->score[j]) continue;

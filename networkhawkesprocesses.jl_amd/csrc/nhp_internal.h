@@ -364,7 +364,15 @@ struct nhp_cont_model {
     // score_every[k]-th kept step, score_kept[k] counts the kept steps seen since the attach (it persists across calls)
     struct nhp_cont_score *score[2] = {nullptr, nullptr};
     int64_t score_every[2] = {1, 1}, score_kept[2] = {0, 0};
+    // streaming quantiles (chain_quantiles.hip: nhp_cont_model_quantiles_*; nhp_quant.h): the marker planes; null: not
+    // configured, nothing is launched
+    struct nhp_quant_state *quant = nullptr;
 };
+// chain_quantiles.hip, for either model: release the marker planes; their share of a moments reset (zero the planes, fitted
+// to the model's entries; NHP_ENOMEM: quantiles off); the driver's kept step (feeds every `every`-th one)
+void nhp_quant_release(struct nhp_quant_state **q);
+nhp_status nhp_quant_reset(nhp_ctx *ctx, nhp_cont_model *m);
+nhp_status nhp_quant_kept_step(nhp_ctx *ctx, nhp_cont_model *m);
 // cont_score.hip: grow the context's scratch to what nhp_cont_score_accumulate(score, model) stages, ahead of a loop
 nhp_status nhp_cont_score_reserve(nhp_ctx *ctx, const struct nhp_cont_score *score, const nhp_cont_model *m);
 // cont_diagnostics.hip: release the diagnostic planes; their share of nhp_cont_model_moments_reset (zero the planes, fitted
@@ -525,7 +533,11 @@ struct nhp_disc_model {
     // kept step, score_kept[k] counts the kept steps since the attach (so a chain cut into calls keeps its rhythm)
     struct nhp_disc_score *score[2] = {nullptr, nullptr};
     int64_t score_every[2] = {1, 1}, score_kept[2] = {0, 0};
+    struct nhp_quant_state *quant = nullptr;            // nhp_quant.h; null: not configured
 };
+// chain_quantiles.hip: the discrete model's share of the streaming quantiles (as for nhp_cont_model above)
+nhp_status nhp_quant_reset(nhp_ctx *ctx, nhp_disc_model *m);
+nhp_status nhp_quant_kept_step(nhp_ctx *ctx, nhp_disc_model *m);
 // disc_score.hip: grow the context's scratch to what nhp_disc_score_accumulate(score, model) stages, ahead of a loop
 nhp_status nhp_disc_score_reserve(nhp_ctx *ctx, const struct nhp_disc_score *score);
 // disc_gibbs.hip: the two halves of a chain step on device-resident state, asynchronous on the main stream.  The Gibbs half

@@ -1280,6 +1280,25 @@ def _disc_fetch_diagnostics(process, model, ctx, full, ess_below, rhat_above):
     return out
 
 
+def _disc_fetch_quantiles(process, model, ctx, probs, every, effective):
+    """nhp_disc_model_quantiles_fetch -> inference.ChainQuantiles in params(process) order (the network's ρ first; only a
+    BernoulliNetworkModel's has a state)."""
+    from .components import BernoulliNetworkModel
+    from .inference import ChainQuantiles
+    L, m = disc_moments_length(process), len(probs)
+    values, lo, hi, rho = np.empty((m, L)), np.empty(L), np.empty(L), np.empty(m + 2)
+    cnt = C.c_int64()
+    _lib.check(_lib.lib().nhp_disc_model_quantiles_fetch(ctx.h, model.h, _lib.dptr(values), _lib.dptr(lo), _lib.dptr(hi), _lib.dptr(rho), L,
+                                                        C.byref(cnt)), ctx.h)
+    if model.network:
+        k = len(process.network.params())
+        if not isinstance(process.network, BernoulliNetworkModel):
+            rho = np.full(m + 2, np.nan)
+        values = np.concatenate([np.repeat(rho[:m, None], k, axis=1), values], axis=1)
+        lo, hi = np.concatenate([np.full(k, rho[m]), lo]), np.concatenate([np.full(k, rho[m + 1]), hi])
+    return ChainQuantiles(probs, values, lo, hi, cnt.value, every, effective)
+
+
 # ---- scoring a chain: held-out predictive log-likelihood and WAIC (csrc/disc_score.hip) ---------------------------------------
 SCORE_FIELDS = ("n", "cells", "lppd", "p_waic", "elpd_waic", "waic", "se_elpd", "joint_lpd", "joint_mean", "joint_sd")
 
@@ -1486,7 +1505,8 @@ def disc_score_samples(process, samples, data, bins=None, burn=0, every=1, point
 
 
 def _disc_mcmc_resident(process, data, nsteps, log_freq, verbose, seed, ctx, keep_samples, moments, burn, diagnostics, batch_len,
-                        ess_below, rhat_above, plan=(), score_every=1, pointwise=False):
+                        ess_below, rhat_above, plan=(), score_every=1, pointwise=False, qprobs=None, quantiles_every=1,
+                        effective_weights=False):
     """The chain with its state on the device (nhp_disc_model): nothing is uploaded after the start; with keep_samples the
     state comes back once per step, without it the whole chain is nhp_disc_mcmc_run."""
     import math
@@ -1505,11 +1525,14 @@ def _disc_mcmc_resident(process, data, nsteps, log_freq, verbose, seed, ctx, kee
         n_planned = max(0, int(nsteps) - int(burn))
         diag_b = int(batch_len) if batch_len is not None else max(1, math.isqrt(n_planned))
         _lib.check(lib.nhp_disc_model_diagnostics_configure(ctx.h, model.h, diag_b, n_planned), ctx.h)
+    if qprobs is not None:
+        _lib.check(lib.nhp_disc_model_quantiles_configure(ctx.h, model.h, _lib.dptr(qprobs), len(qprobs), int(quantiles_every),
+                                                          1 if effective_weights else 0), ctx.h)
     if moments:
         _lib.check(lib.nhp_disc_model_moments_reset(ctx.h, model.h), ctx.h)
     res = MarkovChainMonteCarlo()
     start = time.time()
-    scorers, kept = [], 0
+    scorers, kept, qkept = [], 0, 0
     try:
         scorers = _open_scorers(ctx, process, ds, plan)
         if not keep_samples:
@@ -1524,6 +1547,10 @@ def _disc_mcmc_resident(process, data, nsteps, log_freq, verbose, seed, ctx, kee
                     _lib.check(lib.nhp_disc_model_network_step(ctx.h, ds.h, model.h, net_a, net_b, seed, res.steps), ctx.h)
                 if moments and res.steps >= burn:
                     _lib.check(lib.nhp_disc_model_moments_accumulate(ctx.h, model.h), ctx.h)
+                    if qprobs is not None:
+                        if qkept % int(quantiles_every) == 0:
+                            _lib.check(lib.nhp_disc_model_quantiles_accumulate(ctx.h, model.h), ctx.h)
+                        qkept += 1
                 if scorers and res.steps >= burn:
                     if kept % int(score_every) == 0:
                         for _, s in scorers:
@@ -1558,6 +1585,8 @@ def _disc_mcmc_resident(process, data, nsteps, log_freq, verbose, seed, ctx, kee
                 res.diagnostics = _disc_fetch_diagnostics(process, model, ctx, diagnostics == "full", ess_below, rhat_above)
             if diagnostics:
                 res.diagnostics.update(n=res.n, batch_len=diag_b, nbatches=res.n // diag_b)
+            if qprobs is not None:
+                res.quantiles = _disc_fetch_quantiles(process, model, ctx, qprobs, int(quantiles_every), effective_weights)
         _close_scorers(res, scorers, pointwise)
     finally:
         for _, s in scorers:
@@ -1568,7 +1597,7 @@ def _disc_mcmc_resident(process, data, nsteps, log_freq, verbose, seed, ctx, kee
 
 def disc_mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, ctx=None, device_draws=True, keep_samples=True,
                moments=False, burn=0, diagnostics=False, batch_len=None, ess_below=100.0, rhat_above=1.01, waic=False,
-               heldout=None, score_every=1, pointwise=False):
+               heldout=None, score_every=1, pointwise=False, quantiles=False, quantiles_every=1, effective_weights=False):
     """mcmc!(process::DiscreteHawkesProcess, data) -- src/inference.jl:49-70: convolve once, then
     resample!(process, data, convolved) per step.
 
@@ -1598,6 +1627,12 @@ def disc_mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, 
     chain's device model is scored in place; on the default route -- every model it takes -- each scored step's state is set
     into a device model kept for scoring.  A baseline other than DiscreteHomogeneousProcess is NotImplementedError.
 
+    `quantiles`, `quantiles_every`, `effective_weights` are those of the continuous mcmc_ too (csrc/chain_quantiles.hip;
+    definition in include/nhp.h): with `moments=True`, res.quantiles is a ChainQuantiles over params(process) -- for a standard
+    process the quantiles of the products W∘θ the sums take, for a network process those of W (or A·W), θ and a
+    BernoulliNetworkModel's ρ, NaN at vec(A).  They live next to the device-resident model, so whatever that route refuses
+    (above) is NotImplementedError here as well.
+
     `data` (and the data of `heldout`) may be a list or tuple of N x T_r matrices, independent trials, or a DiscreteDataset
     cut into trials: every route runs on the stacked bins, and bin ranges are in stacked bins --
     heldout=(trials, ds.trial_bins(-1)) holds out the last trial.  A 2-tuple whose second entry is a pair of bins (or None, for
@@ -1610,12 +1645,15 @@ def disc_mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, 
         raise ValueError("diagnostics need the device-side running sums (moments=True)")
     if batch_len is not None and int(batch_len) < 1:
         raise ValueError("batch_len must be a positive integer")
+    from .inference import _check_quantiles
+    qprobs = _check_quantiles(quantiles, quantiles_every, moments)
     data = _enter(process, data)
     plan = _score_plan(process, data, waic, heldout, score_every, burn)
     if moments or not keep_samples:
         _check_resident(process, device_draws)
         return _disc_mcmc_resident(process, data, nsteps, log_freq, verbose, seed, ctx, keep_samples, moments, burn, diagnostics,
-                                   batch_len, ess_below, rhat_above, plan, score_every, pointwise)
+                                   batch_len, ess_below, rhat_above, plan, score_every, pointwise, qprobs, quantiles_every,
+                                   effective_weights)
     ctx = ctx or _lib.default_context()
     ds = convolve(process, data, ctx)
     rng = np.random.default_rng(seed)

@@ -612,6 +612,85 @@ def _fetch_diagnostics(process, model, ctx, network, full, ess_below, rhat_above
     return out
 
 
+# ---- streaming quantiles of a chain that keeps no samples (csrc/chain_quantiles.hip) -----------------------------
+DEFAULT_QUANTILES = (0.025, 0.5, 0.975)
+
+
+class ChainQuantiles:
+    """Streaming quantile estimates of params(process) over a chain's kept steps (extended P², definition: include/nhp.h).
+    `probs` [m]; `values` [m, len(params(process))], row j the estimate of probs[j]; `min`, `max` the smallest and largest
+    value seen, exact; `n` the values every entry was fed, one per `every`-th kept step.  NaN where an entry has no state:
+    vec(A), a block network's ρ / π, a latent distance network's b -- and everywhere in `values` while n < 2m + 3."""
+
+    def __init__(self, probs, values, lo, hi, n, every, effective_weights=False):
+        self.probs = np.array(probs, dtype=np.float64)
+        self.values, self.min, self.max = values, lo, hi
+        self.n, self.every, self.effective_weights = int(n), int(every), bool(effective_weights)
+
+    def interval(self, level=0.95):
+        """(lower, upper): the rows of `values` for the probabilities (1 − level)/2 and (1 + level)/2, which must have been
+        among `probs`."""
+        if not 0.0 < level < 1.0:
+            raise ValueError("level must lie in (0, 1)")
+        rows = []
+        for p in ((1.0 - level) / 2.0, (1.0 + level) / 2.0):
+            hit = np.flatnonzero(np.abs(self.probs - p) <= 1e-12)
+            if len(hit) == 0:
+                raise ValueError(f"interval({level}) needs the quantile {p:.6g}, which the chain did not estimate "
+                                 f"(probs = {tuple(float(v) for v in self.probs)})")
+            rows.append(self.values[hit[0]])
+        return rows[0], rows[1]
+
+    def __repr__(self):
+        return f"ChainQuantiles(probs={tuple(float(v) for v in self.probs)}, n={self.n}, every={self.every}, entries={self.values.shape[1]})"
+
+
+def _check_quantiles(quantiles, quantiles_every, moments):
+    """mcmc_'s quantiles= as a float64 array of probabilities, or None; every argument error is raised here, before the
+    library is touched."""
+    if quantiles is None or quantiles is False:
+        return None
+    if not moments:
+        raise ValueError("quantiles need the device-side running sums (moments=True)")
+    if isinstance(quantiles_every, bool) or int(quantiles_every) != quantiles_every or int(quantiles_every) < 1:
+        raise ValueError("quantiles_every must be a positive integer")
+    if quantiles is True:
+        return np.array(DEFAULT_QUANTILES, dtype=np.float64)
+    try:
+        p = np.array(quantiles, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("quantiles must be True or a sequence of probabilities") from None
+    if p.ndim != 1 or len(p) < 1:
+        raise ValueError("quantiles must be True or a non-empty sequence of probabilities")
+    if len(p) > _lib.QUANT_MAX:
+        raise ValueError(f"at most {_lib.QUANT_MAX} quantiles are estimated per chain ({len(p)} asked for)")
+    if not (np.all(np.isfinite(p)) and np.all(p > 0.0) and np.all(p < 1.0) and np.all(np.diff(p) > 0.0)):
+        raise ValueError("quantiles must increase strictly inside (0, 1)")
+    return p
+
+
+def _fetch_quantiles(process, model, ctx, network, probs, every, effective):
+    """nhp_cont_model_quantiles_fetch -> ChainQuantiles in params(process) order (the reordering of _moments_in_params_order)."""
+    import ctypes as C
+    from .components import BernoulliNetworkModel
+    L, m = moments_length(process), len(probs)
+    values, lo, hi, rho = np.empty((m, L)), np.empty(L), np.empty(L), np.empty(m + 2)
+    cnt = C.c_int64()
+    _lib.check(_lib.lib().nhp_cont_model_quantiles_fetch(ctx.h, model.h, _lib.dptr(values), _lib.dptr(lo), _lib.dptr(hi), _lib.dptr(rho), L,
+                                                        C.byref(cnt)), ctx.h)
+    if network:        # [ρ-entries; λ0; W; impulses; vec(A)]; only a Bernoulli network's scalar ρ has a state
+        k = len(process.network.params())
+        lay = param_layout(process)
+        if not isinstance(process.network, BernoulliNetworkModel):
+            rho = np.full(m + 2, np.nan)
+
+        def order(v, r):
+            return np.concatenate([np.full(k, r), v[lay.baseline], v[lay.weights], v[lay.impulses], v[lay.adjacency]])
+        values = np.stack([order(values[j], rho[j]) for j in range(m)])
+        lo, hi = order(lo, rho[m]), order(hi, rho[m + 1])
+    return ChainQuantiles(probs, values, lo, hi, cnt.value, every, effective)
+
+
 def _owned_mask(process, shard, network):
     """1 on the entries of params(process) this rank owns (its columns; rank 0 also the network's ρ), 0 elsewhere."""
     N = process.ndims()
@@ -853,7 +932,8 @@ def score_samples(process, samples, data, edges, burn=0, every=1, pointwise=Fals
 
 def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_samples=True, device_draws=True,
           ctx=None, moments=False, burn=0, labels_every=1, positions_every=1, diagnostics=False, batch_len=None, ess_below=100.0,
-          rhat_above=1.01, waic=False, heldout=None, score_every=1, pointwise=False):
+          rhat_above=1.01, waic=False, heldout=None, score_every=1, pointwise=False, quantiles=False, quantiles_every=1,
+          effective_weights=False):
     """mcmc!(process, data; nsteps, log_freq, verbose) -- src/inference.jl:49-70.
 
     With `device_draws` (default) a whole sweep -- parents, statistics, conjugate draws -- stays on
@@ -912,9 +992,21 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
     `pointwise=True` keeps the K x N array of elpd_i that compare_scores needs.  On the resident route the scorers are attached
     to the chain's model; step by step they are fed after every kept step; with device_draws=False (or a network model the
     library does not hold) every scored state is set into a device model kept for scoring.  A LogGaussianCoxProcess baseline,
-    several trials and a ShardedDataset raise NotImplementedError."""
+    several trials and a ShardedDataset raise NotImplementedError.
+
+    Credible intervals without samples (csrc/chain_quantiles.hip, definition: include/nhp.h): `quantiles=` up to
+    four probabilities (True: 0.025, 0.5, 0.975), with `moments=True`, gives `res.quantiles`, a ChainQuantiles -- streaming
+    estimates (extended P²) of those quantiles of every entry of params(process) over the steps >= `burn`, every
+    `quantiles_every`-th of them, with the exact `min` and `max`; `res.quantiles.interval(0.95)` is the pair of rows.  The
+    state is 100 bytes per entry at three probabilities and is updated by one launch after the kept step's sums, on the
+    resident route and step by step alike; the sums and the diagnostics keep their bits.  vec(A) has no quantiles (NaN: its
+    mean says everything); `effective_weights=True` estimates the quantiles of A[p,c]·W[p,c] in W's place, the interval that
+    answers whether a link is there.  Only a BernoulliNetworkModel's ρ is estimated among the network parameters.
+    device_draws=False, an LGCP baseline and a ShardedDataset raise NotImplementedError; chains.run_chains does not gather
+    quantiles (marker states of different chains do not merge)."""
     import ctypes as C
     plan = _score_plan(process, data, waic, heldout, score_every, burn)      # (every argument checked before the library is touched)
+    qprobs = _check_quantiles(quantiles, quantiles_every, moments)
     from .sharded import ShardedDataset, _all_reduce_sum
     from .components import BernoulliNetworkModel, DenseNetworkModel, LatentDistanceNetworkModel, StochasticBlockNetworkModel
     shard = data if isinstance(data, ShardedDataset) else None
@@ -926,6 +1018,11 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
         raise NotImplementedError("convergence diagnostics are not available for a sharded chain")
     if batch_len is not None and int(batch_len) < 1:
         raise ValueError("batch_len must be a positive integer")
+    if qprobs is not None and shard is not None:
+        raise NotImplementedError("streaming quantiles are not available for a sharded chain (each rank holds its own columns)")
+    if qprobs is not None and not (device_draws and isinstance(process.baseline, HomogeneousProcess)):
+        raise NotImplementedError("streaming quantiles live next to a device-resident model: the route with device_draws=True and a "
+                                  "homogeneous baseline holds one (device_draws=False and an LGCP baseline draw on the host)")
     sbm = isinstance(getattr(process, "network", None), StochasticBlockNetworkModel)
     latent = isinstance(getattr(process, "network", None), LatentDistanceNetworkModel)
     if sbm and shard is not None:
@@ -976,6 +1073,11 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
         _lib.check(lib.nhp_cont_model_diagnostics_configure(ctx.h, model.h, diag_b, n_planned), ctx.h)
     elif model is not None:                # a cached device model may carry an earlier chain's planes
         _lib.check(lib.nhp_cont_model_diagnostics_configure(ctx.h, model.h, 0, 0), ctx.h)
+    if qprobs is not None:
+        _lib.check(lib.nhp_cont_model_quantiles_configure(ctx.h, model.h, _lib.dptr(qprobs), len(qprobs), int(quantiles_every),
+                                                          1 if effective_weights else 0), ctx.h)
+    elif model is not None:                # ... or its marker planes
+        _lib.check(lib.nhp_cont_model_quantiles_configure(ctx.h, model.h, None, 0, 1, 0), ctx.h)
     if moments:
         _lib.check(lib.nhp_cont_model_moments_reset(ctx.h, model.h), ctx.h)
 
@@ -1013,7 +1115,7 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
         _lib.check(lib.nhp_cont_model_get_adjacency(ctx.h, model.h, _lib.dptr(A), N * N), ctx.h)
         process.adjacency_matrix = A.reshape((N, N), order="F")
 
-    scorers, score_model, kept = [], None, 0
+    scorers, score_model, kept, qkept = [], None, 0, 0
     chain_model_scored = device_draws and (not network or device_net)      # the chain's own device model holds every scored state
     try:
         scorers = _open_scorers(ctx, process, ds, plan)
@@ -1059,6 +1161,10 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
                     process.network.resample_links_(links, process.ndims() ** 2, rng)
                 if moments and res.steps >= burn:
                     _lib.check(lib.nhp_cont_model_moments_accumulate(ctx.h, model.h), ctx.h)
+                    if qprobs is not None:
+                        if qkept % int(quantiles_every) == 0:
+                            _lib.check(lib.nhp_cont_model_quantiles_accumulate(ctx.h, model.h), ctx.h)
+                        qkept += 1
                 if scored and chain_model_scored:
                     for _, s in scorers:
                         s.accumulate(model)
@@ -1109,6 +1215,8 @@ def mcmc_(process, data, nsteps=1000, log_freq=100, verbose=False, seed=0, keep_
             res.diagnostics = _fetch_diagnostics(process, model, ctx, network, diagnostics == "full", ess_below, rhat_above)
         if diagnostics:
             res.diagnostics.update(n=res.n, batch_len=diag_b, nbatches=res.n // diag_b)
+        if qprobs is not None:
+            res.quantiles = _fetch_quantiles(process, model, ctx, network, qprobs, int(quantiles_every), effective_weights)
         if shard is not None and shard.world > 1:
             mask = _owned_mask(process, shard, network)
             res.mean, res.m2 = _all_reduce_sum(res.mean * mask, ctx), _all_reduce_sum(res.m2 * mask, ctx)

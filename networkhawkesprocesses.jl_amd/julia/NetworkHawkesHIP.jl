@@ -710,6 +710,49 @@ function mcmc!(p::NHP.ContinuousHawkesProcess, data; nsteps=1000, log_freq=100, 
     return diagnostics ? (res, mom, diag) : moments ? (res, mom) : res
 end
 
+# --- streaming quantiles of a device-resident chain (include/nhp.h: nhp_cont_model_quantiles_*, nhp_disc_model_quantiles_*) ----
+# Credible intervals with no sample kept: the extended P² markers of every parameter entry sit next to a device model `m`
+# (with_model / a discrete model handle; discrete=true picks the nhp_disc_model_* entries).  Configure before the chain's first
+# kept step (with moments: nhp_*_mcmc_run then feeds every `every`-th kept step itself; a step-by-step driver calls
+# quantiles_accumulate! after its moments accumulate) and fetch while the model is alive.  `len` is the sums' length;
+# values is len x m (column j: the estimate of probs[j]), NaN at vec(A) and, while count < 2m + 3, everywhere; min and max are
+# exact; rho = (the m estimates, min, max) of a Bernoulli network's scalar ρ, NaN otherwise.
+function quantiles_configure!(ctx, m, probs; every::Integer=1, effective_weights::Bool=false, discrete::Bool=false)
+    p = collect(Float64, probs)
+    if discrete
+        check(ccall((:nhp_disc_model_quantiles_configure, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Int32),
+                    ctx.h, m, p, Int32(length(p)), Int32(every), Int32(effective_weights)), ctx.h)
+    else
+        check(ccall((:nhp_cont_model_quantiles_configure, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Int32),
+                    ctx.h, m, p, Int32(length(p)), Int32(every), Int32(effective_weights)), ctx.h)
+    end
+end
+
+quantiles_off!(ctx, m; discrete::Bool=false) = quantiles_configure!(ctx, m, Float64[]; discrete=discrete)
+
+function quantiles_accumulate!(ctx, m; discrete::Bool=false)
+    if discrete
+        check(ccall((:nhp_disc_model_quantiles_accumulate, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), ctx.h, m), ctx.h)
+    else
+        check(ccall((:nhp_cont_model_quantiles_accumulate, libnhp), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), ctx.h, m), ctx.h)
+    end
+end
+
+function quantiles_fetch(ctx, m, nprobs::Integer, len::Integer; discrete::Bool=false)
+    values, lo, hi = Matrix{Float64}(undef, len, nprobs), Vector{Float64}(undef, len), Vector{Float64}(undef, len)
+    rho, cnt = Vector{Float64}(undef, nprobs + 2), Ref{Int64}(0)
+    if discrete
+        check(ccall((:nhp_disc_model_quantiles_fetch, libnhp), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ref{Int64}),
+                    ctx.h, m, values, lo, hi, rho, Int64(len), cnt), ctx.h)
+    else
+        check(ccall((:nhp_cont_model_quantiles_fetch, libnhp), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ref{Int64}),
+                    ctx.h, m, values, lo, hi, rho, Int64(len), cnt), ctx.h)
+    end
+    return (values, lo, hi, rho, cnt[])
+end
+
 # --- StochasticBlockNetworkModel: the reference names it and leaves an empty stub (src/networks.jl, last lines) -------------
 # z_n ~ Categorical(π), π ~ Dirichlet(γ), ρ[k,l] ~ Beta(α, β), A[p,c] ~ Bernoulli(ρ[z_p, z_c]); labels are 1-based here and
 # 0-based in the library.  resample!(net, A) runs on the GPU through the stand-alone entries (csrc/sbm.hip); set_sbm! /

@@ -58,6 +58,12 @@ enum {
     NHP_LL_FULL_RECURSION = 2,   /* with NHP_LL_RECURSIVE: always run the O(M*N) recursion, never its
                                     truncated-window evaluation (same value to fp64 resolution) */
 };
+/* further flags of nhp_cont_vb_step / nhp_cont_vb_run, or-ed to the ones above */
+enum {
+    NHP_VB_RESUME = 256,         /* nhp_cont_vb_run: S, R hold a state on entry and the run continues it (x is output only) */
+    NHP_VB_FROM_MODEL = 512,     /* nhp_cont_vb_step: step from the model's current parameters, used as if they were a
+                                    surrogate (iteration 0 of a run), instead of from the state in S, R */
+};
 
 typedef struct nhp_ctx nhp_ctx;
 typedef struct nhp_cont_dataset nhp_cont_dataset;
@@ -1274,6 +1280,50 @@ nhp_status nhp_cont_em_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_mo
                            const nhp_gibbs_priors *priors /* nullable: unregularised */, double lower, double upper, double f_abstol,
                            int32_t max_steps, double *x, int64_t len, double *loss, int32_t *steps, int32_t *converged,
                            double *trace /* nullable, [max_steps + 1] */);
+
+/* Mean-field variational inference for the same model (csrc/cont_vb.hip): em!'s objective with the branching z kept,
+ *   log p(events, z | λ0, W, ħ) = Σ_i [z_i0 log λ0[c_i] + Σ_j z_ij (log W[n_j,c_i] + log ħ(Δt_ij))] - T Σ λ0 - Σ_p cnt_p Σ_c W[p,c]
+ * over the pairs of `flags`, under the priors of nhp_gibbs_priors (required): λ0 ~ Gamma(α0, β0), W ~ Gamma(κ, ν), θ ~ Gamma(a, b)
+ * or (μ, τ) ~ NormalGamma(μμ, κμ, a, b).  One factor per entry, held in two planes S (shape-like) and R (rate-like) of
+ * len = N + N²·(2 | 3) doubles in params! order, from the statistics bg, EM, S1, S2 of nhp_cont_em_stats:
+ *   block λ0:  S = α' = α0 + bg,  R = β' = β0 + T               block W:  S = κ' = κ + EM,  R = ν' = ν + cnt_p
+ *   block θ:   S = a' = a + EM,   R = b' = b + S1
+ *   block μ:   S = m',  R = k'    block τ:  S = a',  R = b'     with, centred at the μ = c the statistics were taken at
+ *              (D1 = Σ r (z - c), S2 = Σ r (z - c)², d0 = μμ - c):  k' = κμ + EM, m' = c + (D1 + κμ d0)/k', a' = a + EM/2,
+ *              b' = b + ½[S2 + κμ d0² - k'(m' - c)²]
+ * The statistics are em!'s E-step evaluated at the state's surrogate vector x̃ (not clamped to any box):
+ *   λ̃0 = exp(ψ(α') - log β');  θ̃ = a'/b', W̃ = exp(ψ(κ') - log ν' + ψ(a') - log a');
+ *   μ̃ = m', τ̃ = a'/b', W̃ = exp(ψ(κ') - log ν' + ½(ψ(a') - log a') - 1/(2k')),
+ * whose responsibilities are q(z)'s and whose Σ_i log λ̃_i is its log-normaliser.  The ELBO of a state, q(z) optimal for it:
+ *   L = Σ_i log λ̃_i - E_q[compensator] - KL_λ0 - KL_W - KL_imp,     E_q[compensator] = T Σ_c α'/β' + Σ_p cnt_p Σ_c κ'/ν',
+ *   KL(Gamma(a₁,b₁)‖Gamma(a₀,b₀)) = (a₁-a₀)ψ(a₁) - lnΓ(a₁) + lnΓ(a₀) + a₀(log b₁ - log b₀) + a₁(b₀-b₁)/b₁, and for the normal-gamma
+ *   factor the Gamma KL of (a', b') plus ½[κμ/k' - 1 + log(k'/κμ) + κμ (a'/b')(m' - μμ)²].
+ * Every sum of the O(P) passes is taken in one fixed order (no atomics); the statistics' order is the E-step's.
+ *
+ * nhp_cont_vb_step: one coordinate-ascent update.  S, R [len]: the state on entry, the updated state on return (host or
+ * device pointers by output_on_device); with NHP_VB_FROM_MODEL they are output only and the E-step runs at the model's
+ * current parameters.  stats [9] (host): [0] Σ_i log λ̃_i at the surrogate stepped from; [1..4] E_q[compensator], KL_λ0, KL_W,
+ * KL_imp of the state stepped from (0 with NHP_VB_FROM_MODEL), so that L of that state is stats[0] - stats[1] - ... - stats[4];
+ * [5..8] the same four pieces of the updated state.  Synchronous; the model is not changed.
+ *
+ * nhp_cont_vb_run: the whole iteration on the device.  Iteration 0 runs the E-step at x (the guess, used as if it were a
+ * surrogate; it has no ELBO) or, with NHP_VB_RESUME, at the surrogate of the state in S, R; iteration k >= 1 at the
+ * surrogate of state k, whose ELBO L_k goes to trace[k] (nullable, [max_steps + 1]; trace[0] is NaN for a run from a guess);
+ * then the update to state k + 1.  L_k never falls.  Stops when |L_k - L_{k-1}| < f_abstol (*converged = 1, *steps = k) or
+ * with k = max_steps (*converged = 0; max_steps >= 1 for a run from a guess).  On return S, R hold state k, x its means
+ * (α'/β'; a'/b' | m', a'/b'; κ'/ν') and the device-resident `model` holds them too; *elbo = L_k.  The host reads six
+ * scalars per iteration through a pinned slot.  An empty dataset and nodes without events are handled (prior + exposure).
+ *
+ * Errors of both: the NHP_ENOTIMPL refusals of nhp_cont_em_run; NHP_EINVAL, before any launch, for a missing `priors` or a
+ * hyper-parameter that is not positive and finite (μμ: finite; κμ and μμ are read for logit-normal impulses only);
+ * NHP_EDOMAIN when the intensity of some event is not positive and finite; NHP_ESHAPE for a wrong len. */
+nhp_status nhp_cont_vb_step(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *model, int32_t flags,
+                            const nhp_gibbs_priors *priors, double *S /* [len] */, double *R /* [len] */, int64_t len,
+                            int32_t output_on_device, double *stats /* [9] */);
+nhp_status nhp_cont_vb_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *model, int32_t flags,
+                           const nhp_gibbs_priors *priors, double f_abstol, int32_t max_steps, double *x /* [len] */,
+                           double *S /* [len] */, double *R /* [len] */, int64_t len, double *elbo, int32_t *steps,
+                           int32_t *converged, double *trace /* nullable, [max_steps + 1] */);
 
 /* Observed information and Hessian-vector products of the continuous log-likelihood (csrc/cont_information.hip).  The
  * objective nhp_cont_loglik evaluates separates by child node c, so its Hessian is block diagonal: one block per column

@@ -24,14 +24,14 @@ from .discrete import (DiscreteDataset, DiscreteFitTest, DiscreteForecast, Discr
                        DiscreteInformation, DiscreteStandardErrors, disc_hessian_vector_product, disc_observed_information,
                        disc_standard_errors,
                        DiscreteScore, ScoreComparison, compare_scores, disc_score_samples,
-                       resample_parent_counts, stack_trials, svi_, svi_blocks, update_, variational_mean_, vb_)
+                       resample_parent_counts, stack_trials, svi_, svi_blocks, variational_mean_)
 from . import discrete as _disc
 from .parents import (Cascades, cascades, map_parents, node_counts, parent_counts, resample_parents,  # noqa: F401
                       uniform_stream)
 from .inference import (ExpectedStatistics, Information, MarkovChainMonteCarlo, MaximumLikelihood, StandardErrors,  # noqa: F401
                         em_, expected_statistics, hessian_vector_product, logprior, observed_information,
                         resample_adjacency_matrix_, standard_errors,
-                        ContinuousScore, score_samples, ChainQuantiles)
+                        ContinuousScore, score_samples, ChainQuantiles, ContinuousVariational)
 from . import inference as _inf
 from . import synthetic  # noqa: F401
 from .synthetic import rand  # noqa: F401   rand(process, duration): the reference's exported simulator name
@@ -88,6 +88,20 @@ def resample_(process, data, *args, **kwargs):
     return _inf.resample_(process, data, *args, **kwargs)
 
 
+def vb_(process, data, *args, **kwargs):
+    """vb!(process, data; ...) -- src/inference.jl:153-181 for discrete processes; for a continuous standard process the
+    mean-field fit of inference.vb_continuous (a ContinuousVariational)."""
+    if isinstance(process, ContinuousHawkesProcess):
+        return _inf.vb_continuous(process, data, *args, **kwargs)
+    return _disc.vb_(process, data, *args, **kwargs)
+
+
+def update_(process, data, *args, **kwargs):
+    """update!(process, data, convolved) -- src/discrete.jl:369-375: one mean-field step of a discrete process; for a
+    continuous standard process update_(process, data, init=None, ...) is one step of inference.vb_step_continuous."""
+    if isinstance(process, ContinuousHawkesProcess):
+        return _inf.vb_step_continuous(process, data, *args, **kwargs)
+    return _disc.update_(process, data, *args, **kwargs)
 
 def isstable(process):
     """isstable(process): spectral radius of (A .*) W below one -- src/continuous.jl:58, src/discrete.jl:172,404"""

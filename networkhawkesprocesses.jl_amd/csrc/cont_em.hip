@@ -208,7 +208,10 @@ __global__ __launch_bounds__(256) void k_em_empty(int N, double T, const double 
     if (threadIdx.x == 0) *ll = -T * s;
 }
 
-nhp_status em_check(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const char *what)
+}   // namespace
+
+// what em!, expected_statistics and the variational fit (cont_vb.hip) are built for
+nhp_status nhp_em_check(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const char *what)
 {
     NHP_TRY(nhp_check_pair(ctx, ds, m));
     if (m->baseline_kind != NHP_BASELINE_HOMOGENEOUS) {
@@ -226,6 +229,8 @@ nhp_status em_check(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_mod
     return NHP_OK;
 }
 
+namespace {
+
 em_args em_make_args(const nhp_cont_dataset *ds, const nhp_cont_model *m, const nhp_gibbs_priors *pr, double lo, double hi)
 {
     em_args a{};
@@ -241,9 +246,11 @@ em_args em_make_args(const nhp_cont_dataset *ds, const nhp_cont_model *m, const 
     return a;
 }
 
+}   // namespace
+
 // E-step at the DEVICE vector d_x (through nhp_model_view, as nhp_cont_mle_run evaluates a trial):
 // log-likelihood -> ctx->d_results[0], gradient -> *d_grad
-nhp_status em_estep(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *m, int32_t flags, const double *d_x, int64_t P, double **d_grad)
+nhp_status nhp_em_estep(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *m, int32_t flags, const double *d_x, int64_t P, double **d_grad)
 {
     if (ds->M == 0) {
         NHP_TRY(nhp_ctx_reserve_scratch(ctx, 8 * (2 + (size_t)P)));
@@ -261,23 +268,12 @@ nhp_status em_estep(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *m,
     return rc;
 }
 
-struct em_host {                     // one pinned scalar and the event behind its copy
-    double *h = nullptr;
-    hipEvent_t ev = nullptr;
-    ~em_host()
-    {
-        if (h) (void)hipHostFree(h);
-        if (ev) (void)hipEventDestroy(ev);
-    }
-};
-
-}   // namespace
 
 extern "C" nhp_status nhp_cont_em_stats(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int32_t flags,
                                         int32_t output_on_device, double *ll, double *bg, double *EM, double *S1, double *S2)
 {
     if (!ctx || !ds || !m || !ll || !bg || !EM || !S1) return NHP_EINVAL;
-    NHP_TRY(em_check(ctx, ds, m, "expected_statistics"));
+    NHP_TRY(nhp_em_check(ctx, ds, m, "expected_statistics"));
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_check_deferred(ctx));
     const size_t N = (size_t)m->N, NN = N * N;
@@ -290,7 +286,7 @@ extern "C" nhp_status nhp_cont_em_stats(nhp_ctx *ctx, const nhp_cont_dataset *ds
     hipStream_t st = ctx->main();
     double *d_grad = nullptr;
     nhp_cont_model mm = *m;                                           // (the E-step bumps the version of what it evaluates)
-    NHP_TRY(em_estep(ctx, ds, &mm, flags, d_x, P, &d_grad));
+    NHP_TRY(nhp_em_estep(ctx, ds, &mm, flags, d_x, P, &d_grad));
     if (output_on_device) { o_bg = bg; o_EM = EM; o_S1 = S1; o_S2 = S2; }
     const em_args a = em_make_args(ds, m, nullptr, 0.0, 0.0);
     const unsigned nblk = (unsigned)std::min<size_t>(2048, (N + NN + 255) / 256);
@@ -316,14 +312,14 @@ extern "C" nhp_status nhp_cont_em_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, 
                                       double *x, int64_t len, double *loss, int32_t *steps_out, int32_t *converged_out, double *trace)
 {
     if (!ctx || !ds || !m || !x || !loss || !steps_out || !converged_out) return NHP_EINVAL;
-    NHP_TRY(em_check(ctx, ds, m, "em!"));
+    NHP_TRY(nhp_em_check(ctx, ds, m, "em!"));
     if (!(lower < upper) || max_steps < 0) return NHP_EDOMAIN;
     const size_t P = nhp_layout(m).P;
     NHP_TRY(nhp_layout_check(ctx, nhp_layout(m), len));
     NHP_HIP(ctx, hipSetDevice(ctx->device));
     NHP_TRY(nhp_check_deferred(ctx));
     hipStream_t st = ctx->main();
-    em_host hs;
+    nhp_em_host hs;
     if (hipHostMalloc((void **)&hs.h, 8) != hipSuccess) { hs.h = nullptr; nhp_set_error(ctx, "out of pinned memory"); return NHP_ENOMEM; }
     NHP_HIP(ctx, hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
 
@@ -345,7 +341,7 @@ extern "C" nhp_status nhp_cont_em_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, 
         // E-step at x_k and its objective; the M-step is enqueued behind the scalar's copy, so it runs while the host looks at
         // the stopping rule (it writes the other vector only: nothing is lost when the rule says stop)
         double *d_grad = nullptr;
-        NHP_TRY(em_estep(ctx, ds, m, flags, d_x, (int64_t)P, &d_grad));
+        NHP_TRY(nhp_em_estep(ctx, ds, m, flags, d_x, (int64_t)P, &d_grad));
         hipLaunchKernelGGL(k_em_objective, dim3(1), block, 0, st, (const double *)ctx->d_results, (const double *)(d_x + P), a.use_prior, d_f);
         NHP_HIP(ctx, hipGetLastError());
         NHP_HIP(ctx, hipMemcpyAsync(hs.h, d_f, 8, hipMemcpyDeviceToHost, st));

@@ -783,17 +783,6 @@ __global__ __launch_bounds__(256) void k_disc_bump(int N, int B, double dt, cons
     if (i < (size_t)N) base[i] = lambda0[i] * dt;
 }
 
-// [3P] SpecialFunctions.digamma, x > 0: recurrence to x >= 10 then the asymptotic series
-__device__ __forceinline__ double nhp_digamma(double x)
-{
-    double r = 0.0;
-    while (x < 10.0) { r -= 1.0 / x; x += 1.0; }
-    const double f = 1.0 / (x * x);
-    const double t = f * (-1.0 / 12.0 + f * (1.0 / 120.0 + f * (-1.0 / 252.0 + f * (1.0 / 240.0 +
-                     f * (-1.0 / 132.0 + f * (691.0 / 32760.0 + f * (-1.0 / 12.0)))))));
-    return r + nhp_log(x) - 0.5 / x + t;
-}
-
 // VB factors from the OLD variational parameters (src/parents.jl:169-177):
 // E[k + c·K] = exp(ψ(γv[p,c,b]) - ψ(Σ_b γv[p,c,·]) + ψ(κv[p,c]) - log νv[p,c]);  e0[c] = exp(ψ(αv) - log βv)
 __global__ __launch_bounds__(256) void k_vb_factors(int N, int B, const double *__restrict__ alpha_v,

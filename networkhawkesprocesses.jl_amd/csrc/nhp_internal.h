@@ -410,6 +410,21 @@ nhp_status nhp_grad_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_
 // comm.hip: the same, with the shards' [ll; grad] summed over the ranks on the device when `comm` is given (nullable)
 nhp_status nhp_grad_enqueue_reduced(nhp_ctx *ctx, nhp_comm *comm, const nhp_cont_dataset *ds, const nhp_cont_model *m, int32_t flags,
                                     int64_t grad_len, double **d_grad);
+// cont_em.hip, shared with cont_vb.hip: the refusals of em! (LGCP baseline, a model with A, a column shard; `what` names the
+// caller), and the E-step at the DEVICE vector d_x in params! order (through nhp_model_view): log-likelihood ->
+// ctx->d_results[0], gradient -> *d_grad (scratch), by whichever route nhp_grad_enqueue picks; an empty dataset is handled
+nhp_status nhp_em_check(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const char *what);
+nhp_status nhp_em_estep(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *m, int32_t flags, const double *d_x, int64_t P,
+                        double **d_grad);
+struct nhp_em_host {                 // one pinned scalar and the event behind its copy: the stopping rule's read per iteration
+    double *h = nullptr;
+    hipEvent_t ev = nullptr;
+    ~nhp_em_host()
+    {
+        if (h) (void)hipHostFree(h);
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
 // cont_adjacency.hip: enqueue one sweep of A; per-column link counts land at *d_links [N] (scratch).  d_rho_matrix
 // (nullable): the N x N link probabilities already on the device (outside the context's scratch), used when rho_matrix is null
 nhp_status nhp_adj_enqueue(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *m, const double *rho_matrix, double rho,

@@ -311,6 +311,38 @@ __device__ __forceinline__ double nhp_log(double x)
     return s * (hfsq + R) + dk * ln2_lo - hfsq + f + dk * ln2_hi;
 }
 
+// [3P] SpecialFunctions.digamma, x > 0: recurrence to x >= 10 then the asymptotic series (the variational kernels of
+// disc.hip; cont_vb.hip takes it together with lnΓ, below)
+__device__ __forceinline__ double nhp_digamma(double x)
+{
+    double r = 0.0;
+    while (x < 10.0) { r -= 1.0 / x; x += 1.0; }
+    const double f = 1.0 / (x * x);
+    const double t = f * (-1.0 / 12.0 + f * (1.0 / 120.0 + f * (-1.0 / 252.0 + f * (1.0 / 240.0 +
+                     f * (-1.0 / 132.0 + f * (691.0 / 32760.0 + f * (-1.0 / 12.0)))))));
+    return r + nhp_log(x) - 0.5 / x + t;
+}
+
+// ψ(x) and log Γ(x) together, x > 0, in registers (the library lgamma spills: nhp_sim.h), for the O(P) pass of cont_vb.hip,
+// which needs both of every shape and is bound by this arithmetic.  The same recurrence to x >= 10 and the same series as
+// nhp_digamma, but the recurrence's sum is kept as one fraction: with den = x (x + 1) ... (x + n - 1),
+//   ψ(x) = ψ(x + n) - num/den,   lnΓ(x) = lnΓ(x + n) - log(den),
+// so the (up to ten) divisions become one and lnΓ costs one product, which ψ's fraction needs anyway, and one more logarithm.
+// lnΓ(x + n): Stirling's series through x^-13 (the first term left out is 3617/122400·x^-15 < 3e-17 at x = 10).  num and den
+// are sums and products of positive numbers (at most 20 roundings; den < 10·11·...·19 < 4e11, and x >= 1e-300 keeps it normal).
+__device__ __forceinline__ void nhp_digamma_lgamma(double x, double &psi, double &lg)
+{
+    double num = 0.0, den = 1.0;
+    while (x < 10.0) { num = num * x + den; den *= x; x += 1.0; }
+    const double r = 1.0 / x, f = r * r, lx = nhp_log(x);
+    const double tp = f * (-1.0 / 12.0 + f * (1.0 / 120.0 + f * (-1.0 / 252.0 + f * (1.0 / 240.0 +
+                      f * (-1.0 / 132.0 + f * (691.0 / 32760.0 + f * (-1.0 / 12.0)))))));
+    const double tl = r * (1.0 / 12.0 + f * (-1.0 / 360.0 + f * (1.0 / 1260.0 + f * (-1.0 / 1680.0 +
+                      f * (1.0 / 1188.0 + f * (-691.0 / 360360.0 + f * (1.0 / 156.0)))))));
+    psi = ((lx - 0.5 * r) + tp) - num / den;
+    lg = (((x - 0.5) * lx - x + 0.9189385332046727418) + tl) - nhp_log(den);
+}
+
 // Philox4x32-10, counter (event, step), key seed -> 53-bit uniform in [0,1).
 __host__ __device__ __forceinline__ double nhp_philox_uniform(uint64_t seed, uint64_t step, uint64_t event)
 {

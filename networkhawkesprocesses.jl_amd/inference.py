@@ -277,8 +277,200 @@ def em_(process, data, max_steps=1000, f_abstol=1e-6, regularize=False, guess=No
     return res
 
 
+# ---- mean-field variational inference for the continuous standard process (csrc/cont_vb.hip) -----------------------------
+NHP_VB_RESUME, NHP_VB_FROM_MODEL = 256, 512
+
+
+class ContinuousVariational:
+    """The mean-field posterior of a continuous standard process (definition: include/nhp.h, nhp_cont_vb_run): one factor per
+    entry, λ0[c] ~ Gamma(alpha, beta), W[p,c] ~ Gamma(kappa, nu), θ[p,c] ~ Gamma(a, b) or (μ, τ)[p,c] ~ NormalGamma(m, k, a, b)
+    (rates, not scales).  `alpha`, `beta` are N-vectors, the other tables N×N arrays indexed [parent, child] (`m`, `k` None for
+    exponential impulses); `S`, `R` are the same numbers as the two planes of the C entry points, in params(process) order.
+    `elbo` is the evidence lower bound of the state, `trace` its value at every state the run passed (never falling),
+    `steps` the updates made, `status` "success" when |ΔELBO| < f_abstol stopped the run, `pieces` the ELBO's terms where a
+    single step returned them."""
+
+    def __init__(self, kind, N, S, R, prior_kappa=0.0, elbo=float("nan"), trace=None, steps=0, status="incomplete", elapsed=0.0):
+        if kind not in ("exponential", "logitnormal"):
+            raise ValueError("kind must be 'exponential' or 'logitnormal'")
+        self.kind, self.N = kind, int(N)
+        N, NN = self.N, self.N * self.N
+        self.S, self.R = np.array(S, dtype=np.float64), np.array(R, dtype=np.float64)
+        P = N + NN * (2 if kind == "exponential" else 3)
+        if self.S.shape != (P,) or self.R.shape != (P,):
+            raise ValueError("Parameter vector length does not match model parameter length.")
+        self.prior_kappa = float(prior_kappa)
+        self.elbo, self.steps, self.status, self.elapsed = float(elbo), int(steps), status, float(elapsed)
+        self.trace = np.empty(0) if trace is None else np.asarray(trace, dtype=np.float64)
+        self.pieces = None
+
+    def _table(self, plane, block):
+        N, NN = self.N, self.N * self.N
+        return plane[N + block * NN:N + (block + 1) * NN].reshape((N, N), order="F")
+
+    @property
+    def _mu_block(self):
+        N, NN = self.N, self.N * self.N
+        return slice(N, N + NN) if self.kind == "logitnormal" else slice(0, 0)
+
+    alpha = property(lambda self: self.S[:self.N])
+    beta = property(lambda self: self.R[:self.N])
+    kappa = property(lambda self: self._table(self.S, 1 if self.kind == "exponential" else 2))
+    nu = property(lambda self: self._table(self.R, 1 if self.kind == "exponential" else 2))
+    a = property(lambda self: self._table(self.S, 0 if self.kind == "exponential" else 1))
+    b = property(lambda self: self._table(self.R, 0 if self.kind == "exponential" else 1))
+    m = property(lambda self: self._table(self.S, 0) if self.kind == "logitnormal" else None)
+    k = property(lambda self: self._table(self.R, 0) if self.kind == "logitnormal" else None)
+
+    def mean(self):
+        """The posterior means in params(process) order: α'/β'; a'/b' | m', a'/b'; κ'/ν'."""
+        out = self.S / self.R
+        out[self._mu_block] = self.S[self._mu_block]
+        return out
+
+    def sd(self):
+        """The posterior standard deviations in params(process) order: sqrt(shape)/rate for the Gamma factors; the marginal
+        of μ is Student-t with 2a' degrees of freedom, sd = sqrt(b'/(k'(a' - 1))), inf for a' <= 1."""
+        with np.errstate(invalid="ignore"):                   # (the μ block of S holds means of either sign: overwritten below)
+            out = np.sqrt(self.S) / self.R
+        if self.kind == "logitnormal":
+            a, b, k = self.a.ravel(order="F"), self.b.ravel(order="F"), self.k.ravel(order="F")
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out[self._mu_block] = np.where(a > 1.0, np.sqrt(b / (k * np.where(a > 1.0, a - 1.0, 1.0))), np.inf)
+        return out
+
+    def interval(self, level=0.95):
+        """(lower, upper): the central credible interval of every parameter at `level`, in params(process) order, from the
+        Gamma quantiles of the factors and the Student-t quantiles of μ's marginal (scipy, on the host)."""
+        from scipy import stats
+        if not 0.0 < level < 1.0:
+            raise ValueError("level must lie in (0, 1)")
+        tail = 0.5 * (1.0 - level)
+        lo, hi = (stats.gamma.ppf(q, self.S, scale=1.0 / self.R) for q in (tail, 1.0 - tail))
+        if self.kind == "logitnormal":
+            a, b, k = self.a.ravel(order="F"), self.b.ravel(order="F"), self.k.ravel(order="F")
+            m, scale = self.S[self._mu_block], np.sqrt(b / (a * k))
+            lo[self._mu_block], hi[self._mu_block] = (stats.t.ppf(q, 2.0 * a, loc=m, scale=scale) for q in (tail, 1.0 - tail))
+        return lo, hi
+
+    def expected_links(self):
+        """EM[p, c]: the expected number of events of node c that are children of node p under q(z) -- κ' minus the prior's κ."""
+        return self.kappa - self.prior_kappa
+
+    def __repr__(self):
+        return f"\n* Status: {self.status}\n    steps: {self.steps}\n    elapsed: {self.elapsed}\n    elbo: {self.elbo}"
+
+
+def _vb_check(process, data, what):
+    """_em_check's argument errors and the hyper-parameters' (positive and finite; μμ finite), before any device work."""
+    _em_check(process, data, what)
+    pr = _priors(process)
+    names = ["alpha0", "beta0", "kappa", "nu", "a", "b"] + ([] if isinstance(process.impulses, ExponentialImpulseResponse) else ["kappa_mu"])
+    for name in names:
+        v = float(getattr(pr, name))
+        if not (v > 0.0 and math.isfinite(v)):
+            raise ValueError(f"{what}: the prior hyper-parameter {name} = {v} must be positive and finite")
+    if not math.isfinite(float(pr.mu_mu)):
+        raise ValueError(f"{what}: the prior mean mu_mu = {pr.mu_mu} must be finite")
+    return pr
+
+
+def _vb_kind_of(process):
+    return "exponential" if isinstance(process.impulses, ExponentialImpulseResponse) else "logitnormal"
+
+
+def _vb_state(process, init, P):
+    if not isinstance(init, ContinuousVariational):
+        raise TypeError("init must be a ContinuousVariational (the result of an earlier vb_ or update_)")
+    if init.kind != _vb_kind_of(process) or init.S.shape != (P,):
+        raise ValueError("Parameter vector length does not match model parameter length.")
+    return init.S.copy(), init.R.copy()
+
+
+def vb_step_continuous(process, data, init=None, recursive=True, ctx=None):
+    """One coordinate-ascent update of the mean-field posterior (nhp_cont_vb_step): from the state `init` (a
+    ContinuousVariational), or with init=None from the process's current parameters used as if they were a surrogate
+    (iteration 0 of vb_).  Returns the updated ContinuousVariational; its `pieces` is a dict with "loglam" = Σ_i log λ̃_i at the
+    surrogate stepped from, "before" = (E_q[compensator], KL_λ0, KL_W, KL_imp) of the state stepped from (zeros for
+    init=None) and "after" = the same of the state returned; `elbo` is that of the state stepped from (NaN for init=None).
+    The process is not changed."""
+    import ctypes as C
+    from .continuous import _check_recursive
+    pr = _vb_check(process, data, "update!")
+    P = len(process.params())
+    flags = _check_recursive(process, recursive)
+    if init is None:
+        S, R = np.empty(P), np.empty(P)
+        flags |= NHP_VB_FROM_MODEL
+    else:
+        S, R = _vb_state(process, init, P)
+    ctx = ctx or _lib.default_context()
+    ds = device_dataset(process, data, ctx)
+    start = time.time()
+    model = process.device_model(ctx)
+    stats = np.empty(9)
+    _lib.check(_lib.lib().nhp_cont_vb_step(ctx.h, ds.h, model.h, flags, C.byref(pr), S.ctypes.data, R.ctypes.data, P, 0, _lib.dptr(stats)),
+               ctx.h)
+    elbo = float("nan") if init is None else float(stats[0] - stats[1] - stats[2] - stats[3] - stats[4])
+    res = ContinuousVariational(_vb_kind_of(process), process.ndims(), S, R, pr.kappa, elbo=elbo, steps=1, elapsed=time.time() - start)
+    res.pieces = {"loglam": float(stats[0]), "before": tuple(stats[1:5]), "after": tuple(stats[5:9])}
+    return res
+
+
+def vb_continuous(process, data, max_steps=1000, f_abstol=1e-6, guess=None, recursive=True, init=None, keep_trace=True,
+                  verbose=False, ctx=None):
+    """Mean-field variational fit of a standard process with a homogeneous baseline under its own priors, the whole
+    iteration on the GPU (nhp_cont_vb_run; the definition is in include/nhp.h).
+
+    Iteration 0 runs em_'s E-step at `guess` (default: the process's current parameters), used as if it were a surrogate
+    vector; every later iteration at the surrogate of the current factors, followed by the conjugate update of every
+    factor.  The ELBO never falls; the run stops when it changes by less than f_abstol or after max_steps updates.
+    `init=res` resumes from an earlier result instead of a guess.  `data` as for em_ (a list of trials included; T is the
+    summed duration).  Like mle_, `process` is overwritten with the posterior means.  Returns a ContinuousVariational; its
+    trace (keep_trace) holds the ELBO of states 1 .. steps (of the resumed state too with `init`)."""
+    import ctypes as C
+    from .continuous import _check_recursive
+    pr = _vb_check(process, data, "vb!")
+    P = len(process.params())
+    flags = _check_recursive(process, recursive)
+    max_steps = int(max_steps)
+    if init is not None:
+        if guess is not None:
+            raise ValueError("vb!: give a guess or a state to resume (init), not both")
+        S, R = _vb_state(process, init, P)
+        x = np.empty(P)
+        flags |= NHP_VB_RESUME
+    else:
+        x = np.array(process.params() if guess is None else guess, dtype=np.float64)
+        if x.shape != (P,):
+            raise ValueError("Parameter vector length does not match model parameter length.")
+        S, R = np.empty(P), np.empty(P)
+    if max_steps < (0 if init is not None else 1):
+        raise ValueError("vb!: max_steps must be at least 1 (0 with init)")
+    ctx = ctx or _lib.default_context()
+    ds = device_dataset(process, data, ctx)
+    start = time.time()
+    if init is None:
+        process.params_(x)                                          # column-major tables, as in em_
+    model = process.device_model(ctx)
+    elbo, steps, conv = C.c_double(), C.c_int32(), C.c_int32()
+    trace = np.full(max_steps + 1, np.nan)
+    _lib.check(_lib.lib().nhp_cont_vb_run(ctx.h, ds.h, model.h, flags, C.byref(pr), float(f_abstol), max_steps, _lib.dptr(x),
+                                          _lib.dptr(S), _lib.dptr(R), P, C.byref(elbo), C.byref(steps), C.byref(conv),
+                                          _lib.dptr(trace)), ctx.h)
+    first = 0 if init is not None else 1
+    if verbose:
+        for k in range(first, steps.value + 1):
+            print(f" > step: {k}, elbo: {trace[k]}")
+        print(f" > steps: {steps.value}, elbo: {elbo.value}, elapsed: {time.time() - start}")
+    process.params_(x)
+    return ContinuousVariational(_vb_kind_of(process), process.ndims(), S, R, pr.kappa, elbo=elbo.value,
+                                 trace=trace[first:steps.value + 1].copy() if keep_trace else None, steps=steps.value,
+                                 status="success" if conv.value else "failure", elapsed=time.time() - start)
+
+
 # ---- observed information, Hessian-vector products, standard errors ------------------------------------------------------
-Information = collections.namedtuple("Information", "ll columns blocks names")
+Information =collections.namedtuple("Information", "ll columns blocks names")
 StandardErrors = collections.namedtuple("StandardErrors", "se lower_ci upper_ci free pd")
 
 

@@ -585,6 +585,58 @@ function em!(p::NHP.ContinuousStandardHawkesProcess, data; max_steps=1000, f_abs
     keep_trace ? (res, trace[1:steps[]+1]) : res
 end
 
+# --- vb!(process, data; ...) and update!(process, data; state) for the continuous standard process: no reference counterpart ---
+# Mean-field variational inference under the process's own priors (nhp_cont_vb_run / nhp_cont_vb_step; the definition is in
+# include/nhp.h): one Gamma factor per entry of λ0, W and θ, one normal-gamma factor per (μ, τ), held in two planes S (shape-like)
+# and R (rate-like) in params! order.  vb! returns (S, R, elbo, trace, steps, status, elapsed) and overwrites the process with
+# the posterior means; state=(S, R) resumes.  update! is one step from a state, or from the process's current parameters
+# (state=nothing), and returns (S, R, stats) with the nine numbers of nhp_cont_vb_step; the process is not changed.
+const VB_RESUME, VB_FROM_MODEL = Int32(256), Int32(512)
+
+function vb!(p::NHP.ContinuousStandardHawkesProcess, data; max_steps=1000, f_abstol=1e-6, guess=nothing, recursive=true,
+             state=nothing, verbose=false, ctx=context(), ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    p.baseline isa NHP.HomogeneousProcess || error("vb!: the M-step of a LogGaussianCoxProcess baseline has no closed form")
+    P = length(NHP.params(p))
+    x = Vector{Float64}(guess === nothing ? NHP.params(p) : guess)
+    length(x) == P || error("Parameter vector length does not match model parameter length.")
+    S, R = state === nothing ? (Vector{Float64}(undef, P), Vector{Float64}(undef, P)) : (Vector{Float64}(state[1]), Vector{Float64}(state[2]))
+    (length(S) == P && length(R) == P) || error("Parameter vector length does not match model parameter length.")
+    flags = llflags(p, recursive) | (state === nothing ? Int32(0) : VB_RESUME)
+    elbo, steps, conv = Ref{Float64}(0.0), Ref{Int32}(0), Ref{Int32}(0)
+    trace = fill(NaN, max_steps + 1)
+    pri = Ref(priors(p))
+    t0 = time()
+    state === nothing && NHP.params!(p, x)
+    with_model(ctx, p) do m
+        GC.@preserve pri check(ccall((:nhp_cont_vb_run, libnhp), Int32,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Priors}, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64,
+             Ref{Float64}, Ref{Int32}, Ref{Int32}, Ptr{Float64}),
+            ctx.h, ds.h, m, flags, Base.unsafe_convert(Ptr{Priors}, pri), f_abstol, Int32(max_steps), x, S, R, P, elbo, steps, conv,
+            trace), ctx.h)
+    end
+    verbose && println(" > steps: $(steps[]), elbo: $(elbo[])")
+    NHP.params!(p, x)
+    first = state === nothing ? 2 : 1
+    (S=S, R=R, elbo=elbo[], trace=trace[first:steps[]+1], steps=Int(steps[]), status=conv[] == 1 ? "success" : "failure",
+     elapsed=time() - t0)
+end
+
+function update!(p::NHP.ContinuousStandardHawkesProcess, data; state=nothing, recursive=true, ctx=context(),
+                 ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    P = length(NHP.params(p))
+    S, R = state === nothing ? (Vector{Float64}(undef, P), Vector{Float64}(undef, P)) : (Vector{Float64}(state[1]), Vector{Float64}(state[2]))
+    (length(S) == P && length(R) == P) || error("Parameter vector length does not match model parameter length.")
+    flags = llflags(p, recursive) | (state === nothing ? VB_FROM_MODEL : Int32(0))
+    stats = Vector{Float64}(undef, 9)
+    pri = Ref(priors(p))
+    with_model(ctx, p) do m
+        GC.@preserve pri check(ccall((:nhp_cont_vb_step, libnhp), Int32,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Priors}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Ptr{Float64}),
+            ctx.h, ds.h, m, flags, Base.unsafe_convert(Ptr{Priors}, pri), S, R, P, Int32(0), stats), ctx.h)
+    end
+    (S=S, R=R, stats=stats)
+end
+
 # --- observed_information(process, data) and hessian_vector_product(process, data, v): no reference counterpart ---------------
 # The objective separates by child node, so minus its Hessian is block diagonal: blocks[:, :, k] is the D x D block of column
 # columns[k] (1-based here) over [λ0[c]; θ[:,c] | μ[:,c]; τ[:,c]; W[:,c]], D = 1 + kinds·N (nhp_cont_information; homogeneous

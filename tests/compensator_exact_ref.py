@@ -124,12 +124,14 @@ class _Math:
         mpmath.mp.dps = max(mpmath.mp.dps, ar.MP_DIGITS)
         if self.mpb:
             return np.frompyfunc(lambda v: mpmath.ncdf(v), 1, 1)(z)
-        out = np.empty(len(z), dtype=self.b.real)
-        for i, v in enumerate(z):
+        # every distinct argument once: on a dyadic grid of times many pairs of a link share their delay
+        uniq, inverse = np.unique(np.asarray(z, dtype=self.b.real), return_inverse=True)
+        out = np.empty(len(uniq), dtype=self.b.real)
+        for i, v in enumerate(uniq):
             r = mpmath.ncdf(_to_mp(mpmath, v))
             hi = float(r)
             out[i] = self.b.real(hi) + self.b.real(float(r - mpmath.mpf(hi)))
-        return out
+        return out[inverse]
 
 
 def erfc_scale(z):
@@ -519,6 +521,9 @@ COMPENSATOR_CASES = tuple(CASES)
 FAR = ("W-exp", "W-logit", "W-net", "W-net-logit", "L-exp", "L-logit", "S-tiny", "P-129", "P-8193")
 """Run also with T = t_last + 2·Δtmax: no event inside the last window (G-W cannot: its grid ends at T)."""
 CASES.update({"N-70": lambda: wide_case(70), "N-300": lambda: wide_case(300)})
+TIME_PART_CASES = ("P4-exp", "P4-logit", "P2-inf")
+"""cont_grad_ref's cases that the default rule lays out in XCD time parts (tests/test_time_parts_gpu.py); P2-inf: Δtmax = ∞."""
+CASES.update({name: gr.CASES[name] for name in TIME_PART_CASES})
 INTENSITY_CASES = GRAD_CASES + ("L-exp", "L-logit", "S-tiny", "N-70", "N-300")
 
 

@@ -443,6 +443,58 @@ def long_case(kind):
                 tau=rng.uniform(0.5, 2.0, (N, N)), A=None, grid_x=None, recursive=False)
 
 
+TIME_PART_SHAPES = {"P4": (9, 1000, 4.0, 1.0), "P2": (10, 1000, 5.2, 1.0), "P2-inf": (10, 300, 30.0, np.inf)}
+"""(N, M, T, Δtmax) of the cases that the default rule lays out in XCD time parts (tests/slices_ref.time_parts): a mean window
+of 218 pairs (TP = 4, 40 items of which 4 are padding), of 175, between the 160 above which the plan does not slice and the
+192 of TP = 4 (TP = 2, 24 items, 4 padding), and every earlier event with Δtmax = ∞ (149.5; TP = 2, 24 items, 4 padding)."""
+
+
+def time_part_case(shape, kind="exponential", network=False, seed=61):
+    """P4-exp / P4-logit / P4-net, P2-exp / P2-logit, P2-inf: built like windowed_case on the dyadic grid 2⁻¹⁰, every time
+    distinct except 12 planted ties (whose two events sit on different nodes, so that no two categories of a child have the
+    same weight: tests/test_cascades_host.py's condition), exact zeros in W, θ·Δtmax from 0.5 to 40 (Δtmax = ∞: θ from 0.05
+    to 4).  Nodes 1..N-3 carry the bulk; node N-2 has one event; node N-1 has 40, all inside the last quarter of the event
+    indices, so its first item is empty in every time-part layout and still owns the column's constants; node N has none
+    and is the node the padding items name."""
+    N, M, T, dt_max = TIME_PART_SHAPES[shape]
+    rng = np.random.default_rng(seed)
+    k = np.sort(rng.choice(np.arange(1, int(T * 1024)), M, replace=False))
+    t = k / 1024.0
+    tied = np.arange(M // 5, M // 5 + 24, 2)
+    t[tied] = t[tied + 1]                                                # sorted still: t[i] moves up to its neighbour
+    nodes = rng.integers(1, N - 2, M).astype(np.int64)                   # nodes 1..N-3 carry the bulk
+    nodes[tied + 1] = nodes[tied] % (N - 3) + 1                          # a tie's two events on different nodes
+    late = 3 * M // 4 + np.sort(rng.choice(M - 3 * M // 4, 40, replace=False))
+    nodes[late] = N - 1
+    nodes[3 * M // 8] = N - 2
+    assert np.all(np.diff(t) >= 0)
+    W = rng.uniform(0.05, 1.0, (N, N)) / N * 2.0
+    W[1, 2] = W[4, 4] = W[0, 3] = 0.0
+    if np.isfinite(dt_max):
+        theta = np.exp(rng.uniform(np.log(0.5), np.log(40.0), (N, N))) / dt_max
+        theta[0, 0], theta[3, 1] = 0.5 / dt_max, 40.0 / dt_max
+    else:
+        theta = np.exp(rng.uniform(np.log(0.05), np.log(4.0), (N, N)))
+    mu = rng.normal(0.0, 1.0, (N, N))
+    tau = rng.uniform(0.5, 2.0, (N, N))
+    A = None
+    if network:
+        A = (rng.uniform(size=(N, N)) < 0.6).astype(np.float64)
+        A[2, :] = 0.0
+        A[:, 3] = 0.0
+        A[0, 0] = A[1, 1] = 1.0
+    return dict(N=N, T=T, times=t, nodes=nodes, kind=kind, dt_max=dt_max, lam0=rng.uniform(0.5, 1.5, N), W=W, theta=theta, mu=mu,
+                tau=tau, A=A, grid_x=None, recursive=False)
+
+
+def large_item_data(seed=8):
+    """N = 8, M = 140 000 uniform times on T = 680 with Δtmax = 1: about 2.9·10⁷ pairs, a mean window of about 206, so TP = 4 and
+    32 items of about 4375 children -- more than the 4096 that bound an item of the default layout."""
+    rng = np.random.default_rng(seed)
+    N, M, T = 8, 140_000, 680.0
+    return np.sort(rng.uniform(0.0, T, M)), rng.integers(1, N + 1, M).astype(np.int64), T, N, 1.0
+
+
 REC_M = {1: 1500, 64: 2500, 65: 2500, 257: 2000, 513: 2000, 1025: 2000}
 
 
@@ -490,6 +542,10 @@ CASES = {
     "G-R": lambda: recursive_case(65, lgcp=True),
 }
 CASES.update({"R-%d" % n: (lambda n=n: recursive_case(n)) for n in REC_M})
+TIME_PART_CASES = ("P4-exp", "P4-logit", "P4-net", "P2-exp", "P2-logit", "P2-inf")
+CASES.update({"P4-exp": lambda: time_part_case("P4"), "P4-logit": lambda: time_part_case("P4", "logitnormal"),
+              "P4-net": lambda: time_part_case("P4", network=True), "P2-exp": lambda: time_part_case("P2"),
+              "P2-logit": lambda: time_part_case("P2", "logitnormal"), "P2-inf": lambda: time_part_case("P2-inf")})
 
 
 def model_of(case):

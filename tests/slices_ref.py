@@ -11,7 +11,12 @@ its longest window.  The slices are kept when rows < 2^25, rows·64 <= 2·pairs 
 160·M, a finite positive dt_max, N <= 65534).
 
 Inputs that would be laid out in XCD time parts (a mean window of 192 pairs, or of 24 on a dataset that is not sliced, with
-N >= 8 and M >= 16·N) are refused: no test here uses them."""
+N >= 8 and M >= 16·N) are refused by layout(); their item table is restated apart, from the rule, by
+
+    time_parts(times, nodes, N, dt_max, columns=None) -> None | (TP, items [n_items, 4]: node, kbeg, kend, first)
+
+which tests/test_time_parts_host.py holds to the properties of a partition and tests/test_time_parts_gpu.py compares with
+what the dataset exports."""
 from dataclasses import dataclass
 
 import numpy as np
@@ -68,6 +73,56 @@ def item_size(M, N, chunk=None):
     if chunk is not None and int(chunk) > 0:                     # NHP_CHUNK
         c = min(int(chunk), 4096)
     return c
+
+
+def time_part_count(pairs, M, N, dt_max):
+    """TP of the default rule: 4 from a mean window of 192 pairs on, 2 from 24 on where the plan does not slice (pairs > 160·M
+    or no finite positive Δtmax), and only with N >= 8 and M >= 16·N; otherwise 0."""
+    if M == 0 or N < 8 or M < 16 * N:
+        return 0
+    sliced = 0 < pairs <= SLICES_MAXK * M and np.isfinite(dt_max) and dt_max > 0.0 and N <= 65534
+    kbar = pairs / M
+    return 4 if kbar >= 192.0 else (2 if kbar >= 24.0 and not sliced else 0)
+
+
+def time_parts(times, nodes, N, dt_max, columns=None, parts=None):
+    """The XCD time-part layout restated from its rule: None where the rule gives TP = 0, otherwise (TP, items) with items an
+    [n_items, 4] table of node (0-based), kbeg, kend, first.
+
+    Workgroup b runs on XCD b % 8.  XCD x = s·(8/TP) + g gets time part s -- the events with index in [M·s/TP, M·(s+1)/TP) --
+    of the nodes c with c % (8/TP) == g, so the table is one run of 8 items per group of 8/TP consecutive nodes; kbeg and
+    kend count positions in the node-sorted child array, where a node's children stand in time order.  Only the s = 0 item of
+    a node is `first` (bit 0); bit 1 (the node's only item) is never set, every node having TP >= 2 items.  Where N is no
+    multiple of 8/TP the last run is filled with empty items that name node N - 1 and are not first.  A column shard keeps
+    the items whose node it owns (the padding with node N - 1).  parts: NHP_XCD's value instead of the rule's (2, 4 or 8)."""
+    t = np.asarray(times, dtype=np.float64)
+    node = np.asarray(nodes, dtype=np.int64) - 1
+    M, N = len(t), int(N)
+    assert len(node) == M and (M == 0 or (node.min() >= 0 and node.max() < N)) and np.all(np.diff(t) >= 0.0)
+    pairs = int((np.arange(M, dtype=np.int64) - windows(t, dt_max)).sum())
+    TP = time_part_count(pairs, M, N, dt_max) if parts is None else (int(parts) if N >= 8 and M >= 16 * N else 0)
+    if TP == 0:
+        return None
+    assert TP in (2, 4, 8)
+    per_run = 8 // TP                                                     # nodes per run of 8 items
+    runs = -(-N // per_run)
+    boff = np.concatenate([[0], np.cumsum(np.bincount(node, minlength=N))]).astype(np.int64)
+    cuts = [M * s // TP for s in range(TP + 1)]
+    # children of node c with an event index below each cut: c's events are the sorted indices where node == c
+    below = np.stack([np.bincount(node[:cut], minlength=N) for cut in cuts], axis=1)
+    c0, c1 = (0, N) if columns is None else (int(columns[0]), int(columns[1]))
+    items = []
+    for b in range(runs * 8):
+        x = b % 8
+        s, g = x // per_run, x % per_run
+        c = (b // 8) * per_run + g
+        if c < N:
+            row = (c, boff[c] + below[c, s], boff[c] + below[c, s + 1], 1 if s == 0 else 0)
+        else:
+            row = (N - 1, boff[N - 1], boff[N - 1], 0)
+        if c0 <= row[0] < c1:
+            items.append(row)
+    return TP, np.array(items, dtype=np.int64).reshape(-1, 4)
 
 
 def layout(times, nodes, N, dt_max, chunk=None, columns=None):

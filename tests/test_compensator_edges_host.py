@@ -5,7 +5,8 @@ intensity_at agrees with the oracle.
 
 Largest error/bound of the float64 evaluations (the largest of at_events / residuals / total over the three orders):
 W-exp 0.13, W-logit 0.17, W-net 0.18, W-net-logit 0.24, G-W 0.13, L-exp 0.19, L-logit 0.14, L-exp-inf 0.19, S-tiny 0.22,
-P-127 0.11, P-128 0.098, P-129 0.11, P-8191 0.082, P-8192 0.12, P-8193 0.14.  The mutants reach 1e10 to 1e14 on their cases
+P-127 0.11, P-128 0.098, P-129 0.11, P-8191 0.082, P-8192 0.12, P-8193 0.14; the time-part cases of
+tests/test_time_parts_gpu.py: P4-exp 0.21, P4-logit 0.16, P2-inf 0.20.  The mutants reach 1e10 to 1e14 on their cases
 (a whole link mass or a run of them against a few 2⁻⁵³), 1 - exp(-x) 6.3e3 on S-tiny."""
 import numpy as np
 import pytest
@@ -33,7 +34,7 @@ def f64(case, **kw):
     return [np.asarray(getattr(r, k).value, dtype=np.float64) for k in KEYS]
 
 
-@pytest.mark.parametrize("name", ce.COMPENSATOR_CASES)
+@pytest.mark.parametrize("name", ce.COMPENSATOR_CASES + ce.TIME_PART_CASES)
 def test_float64_sums_in_three_orders_within_the_bound(name):
     case, res = ce.prepared(name)
     for order in ("forward", "reverse", "shuffled"):

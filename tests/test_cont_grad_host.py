@@ -5,13 +5,16 @@ sums in three orders inside the bound the GPU suite uses, and a census showing t
 Largest error/bound of the float64 evaluations (the largest of forward / reversed / permuted; they differ in the third digit
 at most except where noted), the headroom of the derivation: W-exp 0.059, W-logit 0.058, W-net 0.041, W-net-logit 0.064,
 D 0.00076 (0.00046 forward), L-exp 0.0016 (0.00043 reversed), L-logit 0.00063, C 0.022, C-net 0.020, G-W 0.054, G-D 0.013, G-R 0.039,
-R-1 0.00035, R-64 0.019, R-65 0.022, R-257 0.069, R-513 0.14, R-1025 0.12.  The largest ratios belong to entries of a few
+R-1 0.00035, R-64 0.019, R-65 0.022, R-257 0.069, R-513 0.14, R-1025 0.12, P4-exp 0.012, P4-logit 0.011, P4-net 0.020,
+P2-exp 0.041, P2-logit 0.057, P2-inf 0.025 (the P cases: the inputs of tests/test_time_parts_gpu.py, whose census here also
+counts their time parts, the empty first item, the empty last node and the padding).  The largest ratios belong to entries of a few
 terms with θΔ in the hundreds, where the error of a float64 exponential's argument is nearly all of the bound."""
 import mpmath
 import numpy as np
 import pytest
 
 import cont_grad_ref as cr
+import slices_ref as sr
 from oracle import mp_eval
 
 REL_LL = 1e-11
@@ -130,6 +133,10 @@ CENSUS = {
     "R-257": dict(zero_time=3, ties=10, empty=128), "R-513": dict(zero_time=3, ties=10, empty=1),
     "R-1025": dict(zero_time=3, ties=10, empty=1),
 }
+CENSUS.update({name: dict(ties=12, empty=1, single=1, edge=0 if name == "P2-inf" else 100) for name in cr.TIME_PART_CASES})
+TIME_PARTS = {"P4-exp": (4, 40, 4), "P4-logit": (4, 40, 4), "P4-net": (4, 40, 4), "P2-exp": (2, 24, 4), "P2-logit": (2, 24, 4),
+              "P2-inf": (2, 24, 4)}
+"""(TP, items, padding items) of the cases the default rule lays out in XCD time parts."""
 
 
 @pytest.mark.parametrize("name", list(cr.CASES))
@@ -148,6 +155,35 @@ def test_cases_contain_what_they_are_named_for(name):
         if case["A"] is not None:
             assert (case["A"].sum(axis=1) == 0).any() and (case["A"].sum(axis=0) == 0).any()
             assert ((case["W"] == 0) & (case["A"] == 1)).any()
+    if name in TIME_PARTS:
+        # the time-part count from the rule, the empty first item of the late node, the empty last node, the padding
+        M = len(case["times"])
+        TP, items = sr.time_parts(case["times"], case["nodes"], N, case["dt_max"])
+        pairs_per_event = cs["pairs"] / M
+        assert (TP, len(items)) == TIME_PARTS[name][:2] and N >= 8 and M >= 16 * N
+        if name.startswith("P4"):
+            assert pairs_per_event >= 192
+        elif name == "P2-inf":                                           # Δtmax = ∞ is never sliced: TP = 2 from a mean window of 24 on
+            assert 24 <= pairs_per_event < 192 and not np.isfinite(case["dt_max"])
+        else:                                                             # above the 160 the plan slices at, below the 192 of TP = 4
+            assert 160 < pairs_per_event < 192
+        cnt = np.bincount(case["nodes"] - 1, minlength=N)
+        assert cnt[N - 1] == 0 and cnt[N - 2] == 40 and cnt[N - 3] == 1 and np.all(cnt[:N - 3] > 16)
+        assert np.all(np.nonzero(case["nodes"] == N - 1)[0] >= 3 * M // 4)           # all in the last quarter of the event indices
+        late = items[items[:, 0] == N - 2]
+        assert late[0, 3] == 1 and late[0, 1] == late[0, 2] and late[-1, 2] - late[-1, 1] > 0
+        per_run = 8 // TP
+        slot = (np.arange(len(items)) // 8) * per_run + (np.arange(len(items)) % 8) % per_run
+        pad = items[slot >= N]
+        assert len(pad) == TIME_PARTS[name][2] and np.all(pad[:, 0] == N - 1) and np.all(pad[:, 1] == pad[:, 2]) and np.all(pad[:, 3] == 0)
+        assert (items[:, 3] & 1).sum() == N and np.all((items[:, 3] & 2) == 0)
+        assert (case["W"] == 0).sum() == 3
+        th = case["theta"] * (case["dt_max"] if np.isfinite(case["dt_max"]) else 1.0)
+        assert (th.min() == 0.5 and th.max() == 40.0) if np.isfinite(case["dt_max"]) else (0.05 <= th.min() and th.max() <= 4.0)
+        tied = np.nonzero(np.diff(case["times"]) == 0)[0]
+        assert len(tied) == 12 and np.all(case["nodes"][tied] != case["nodes"][tied + 1])
+        if case["A"] is not None:
+            assert (case["A"].sum(axis=1) == 0).any() and (case["A"].sum(axis=0) == 0).any()
     if name == "R-257":                                               # part 3 of 4 (nodes 129..192), and part 4's first 64, have no events
         cnt = np.bincount(case["nodes"] - 1, minlength=N)
         assert cnt[128:256].sum() == 0 and cnt[256] > 0

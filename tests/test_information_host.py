@@ -63,7 +63,8 @@ def test_blocks_equal_central_differences_of_the_gradient_reference(name):
     print(f"{name}: largest difference / tolerance {worst:.3g}")
 
 
-@pytest.mark.parametrize("name", ["W-exp", "W-logit", "W-net", "W-net-logit", "D", "L-exp", "L-logit"])
+@pytest.mark.parametrize("name", ["W-exp", "W-logit", "W-net", "W-net-logit", "D", "L-exp", "L-logit",
+                                  "P4-exp", "P4-logit", "P4-net", "P2-inf"])
 def test_float64_in_any_order_stays_inside_the_bound(name):
     case, res = ir.prepared(name)
     m = cr.model_of(case)

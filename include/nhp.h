@@ -63,6 +63,8 @@ enum {
     NHP_VB_RESUME = 256,         /* nhp_cont_vb_run: S, R hold a state on entry and the run continues it (x is output only) */
     NHP_VB_FROM_MODEL = 512,     /* nhp_cont_vb_step: step from the model's current parameters, used as if they were a
                                     surrogate (iteration 0 of a run), instead of from the state in S, R */
+    NHP_VB_DENSE_NETWORK = 1024, /* nhp_cont_netvb_step / _run: a DenseNetworkModel (ρ ≡ 1): ρv ≡ 1 is written, no network update
+                                    runs, net[2..3] are ignored and Q's (αv, βv) pass through */
 };
 
 typedef struct nhp_ctx nhp_ctx;
@@ -1324,6 +1326,58 @@ nhp_status nhp_cont_vb_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_mo
                            const nhp_gibbs_priors *priors, double f_abstol, int32_t max_steps, double *x /* [len] */,
                            double *S /* [len] */, double *R /* [len] */, int64_t len, double *elbo, int32_t *steps,
                            int32_t *converged, double *trace /* nullable, [max_steps + 1] */);
+
+/* Mean-field variational inference for the continuous NETWORK process (csrc/cont_netvb.hip): spike-and-slab weights under a
+ * dense or Bernoulli network.  `model` is the lowered network process (it has an adjacency matrix).
+ *
+ * Likelihood and priors.  The likelihood is nhp_cont_vb_run's full-mass likelihood with the branching z kept; no mask appears
+ * in it.  The network acts through the prior of W:  A[p,c] ~ Bernoulli(ρ),  W[p,c] | A = a ~ Gamma(κ_a, ν_a)  (a = 0 the spike,
+ * a Gamma of small mean the caller chooses; a = 1 the slab),  ρ ~ Beta(α, β) for a Bernoulli network, ρ ≡ 1 for a dense one
+ * (NHP_VB_DENSE_NETWORK).  λ0 and the impulse factors are nhp_cont_vb_run's.  priors->kappa, priors->nu are the slab's
+ * (κ1, ν1); net = [κ0, ν0, α, β].
+ * Factors:  q(A = 1) = ρv[p,c],  q(W | A = a) = Gamma(κv_a, νv_a),  q(ρ) = Beta(αv, βv).  The state is S, R (nhp_cont_vb_run's
+ * planes, device layout [λ0; impulses; W]; the W block holds the slab's κv1, νv1) and Q = [κv0; νv0; ρv; αv; βv] of
+ * 3·N² + 2 doubles, matrices column-major [p + c·N].
+ * One step from state k:
+ *   1. surrogate: nhp_cont_vb_run's with  E log W = (1 - ρv)(ψ(κv0) - log νv0) + ρv (ψ(κv1) - log νv1)  in place of ψ(κ') - log ν'
+ *      (two products and a sum, not contracted: ρv = 1 gives the slab's term exactly); the E-step runs at x̃ on a view of the
+ *      model without its adjacency matrix, and bg, EM, S1 | D1, S2 are recovered from (x̃, ∇ll) as nhp_cont_vb_step does;
+ *   2. λ0 and the impulse factors as nhp_cont_vb_run;  κv_a = κ_a + EM,  νv_a = ν_a + cnt_p  for both a;
+ *   3. logit ρv = [ψ(αv) - ψ(βv)] + [κ1 log ν1 - lnΓκ1 + lnΓκv1 - κv1 log νv1] - [κ0 log ν0 - lnΓκ0 + lnΓκv0 - κv0 log νv0]  with the
+ *      NEW κv, νv and the OLD (αv, βv);  ρv is the sigmoid of it (exactly 1 or 0 where it saturates, never NaN);
+ *   4. αv = α + Σρv,  βv = β + Σ(1 - ρv),  the sums over all N² links, the diagonal included.
+ * Every block is an exact coordinate-ascent update, so the ELBO never falls:
+ *   L = Σ_i log λ̃_i - E_q[comp] - KL_λ0 - KL_W - KL_imp - KL_net
+ *   E_q[comp] = T Σ α'/β' + Σ_p cnt_p Σ_c [(1-ρv) κv0/νv0 + ρv κv1/νv1]
+ *   KL_W = Σ [(1-ρv) KL(Gamma(κv0,νv0)‖Gamma(κ0,ν0)) + ρv KL(Gamma(κv1,νv1)‖Gamma(κ1,ν1))]
+ *   KL_net = Σ [ρv log ρv + (1-ρv) log(1-ρv) - ρv(ψ(αv) - ψ(αv+βv)) - (1-ρv)(ψ(βv) - ψ(αv+βv))] + KL(Beta(αv,βv)‖Beta(α,β)),
+ *   0·log 0 = 0; KL_net = 0 for a dense network.
+ * Every sum of the O(P) passes is taken in one fixed order (no atomics); the statistics' order is the E-step's.
+ *
+ * nhp_cont_netvb_step: one update.  S, R [len], Q: the state on entry, the updated state on return (host pointers, or all
+ * three device pointers with output_on_device); with NHP_VB_FROM_MODEL the E-step runs at the model's current parameters
+ * and of the state on entry only Q's (αv, βv) are read (step 3 needs the old ones in every mode).  stats [11] (host):
+ * [0] Σ_i log λ̃_i at the surrogate stepped from; [1..5] E_q[comp], KL_λ0, KL_W, KL_imp, KL_net of the state stepped from (0 with
+ * NHP_VB_FROM_MODEL); [6..10] the same of the state returned.  Synchronous; the model is not changed.
+ *
+ * nhp_cont_netvb_run: the whole iteration on the device; its loop, stopping rule, trace, NHP_VB_RESUME (S, R, Q hold a state)
+ * and empty-dataset handling are nhp_cont_vb_run's.  A run from a guess x reads Q's (αv, βv) alone.  On return S, R, Q hold
+ * state k, x its means (the slab's κv1/νv1 for W) and the device model holds them and A = (ρv > ½).  The host reads eight
+ * scalars per iteration through a pinned slot.
+ *
+ * Errors of both, before any launch: NHP_ENOTIMPL for an LGCP baseline, a column shard, a model without A, a model with a
+ * block or latent distance network attached; NHP_EINVAL for a missing argument, a prior hyper-parameter or one of κ0, ν0, α,
+ * β that is not positive and finite, and (host pointers) αv, βv not positive and finite, and where a state is read a ρv
+ * outside [0, 1] or a κv / νv that is not positive and finite.  Then NHP_EDOMAIN and NHP_ESHAPE as nhp_cont_vb_run. */
+nhp_status nhp_cont_netvb_step(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *model, int32_t flags,
+                               const nhp_gibbs_priors *priors, const double *net /* [4] */, double *S /* [len] */,
+                               double *R /* [len] */, int64_t len, double *Q /* [3*N*N + 2] */, int32_t output_on_device,
+                               double *stats /* [11] */);
+nhp_status nhp_cont_netvb_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *model, int32_t flags,
+                              const nhp_gibbs_priors *priors, const double *net /* [4] */, double f_abstol, int32_t max_steps,
+                              double *x /* [len] */, double *S /* [len] */, double *R /* [len] */, int64_t len,
+                              double *Q /* [3*N*N + 2] */, double *elbo, int32_t *steps, int32_t *converged,
+                              double *trace /* nullable, [max_steps + 1] */);
 
 /* Observed information and Hessian-vector products of the continuous log-likelihood (csrc/cont_information.hip).  The
  * objective nhp_cont_loglik evaluates separates by child node c, so its Hessian is block diagonal: one block per column

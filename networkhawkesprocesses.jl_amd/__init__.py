@@ -31,7 +31,7 @@ from .parents import (Cascades, cascades, map_parents, node_counts, parent_count
 from .inference import (ExpectedStatistics, Information, MarkovChainMonteCarlo, MaximumLikelihood, StandardErrors,  # noqa: F401
                         em_, expected_statistics, hessian_vector_product, logprior, observed_information,
                         resample_adjacency_matrix_, standard_errors,
-                        ContinuousScore, score_samples, ChainQuantiles, ContinuousVariational)
+                        ContinuousScore, score_samples, ChainQuantiles, ContinuousVariational, ContinuousNetworkVariational)
 from . import inference as _inf
 from . import synthetic  # noqa: F401
 from .synthetic import rand  # noqa: F401   rand(process, duration): the reference's exported simulator name
@@ -90,7 +90,11 @@ def resample_(process, data, *args, **kwargs):
 
 def vb_(process, data, *args, **kwargs):
     """vb!(process, data; ...) -- src/inference.jl:153-181 for discrete processes; for a continuous standard process the
-    mean-field fit of inference.vb_continuous (a ContinuousVariational)."""
+    mean-field fit of inference.vb_continuous (a ContinuousVariational); for a continuous network process with
+    SparseWeightModel weights and a Dense or Bernoulli network inference.vb_network_continuous (a
+    ContinuousNetworkVariational with the link probabilities)."""
+    if isinstance(process, ContinuousNetworkHawkesProcess):
+        return _inf.vb_network_continuous(process, data, *args, **kwargs)
     if isinstance(process, ContinuousHawkesProcess):
         return _inf.vb_continuous(process, data, *args, **kwargs)
     return _disc.vb_(process, data, *args, **kwargs)
@@ -98,7 +102,10 @@ def vb_(process, data, *args, **kwargs):
 
 def update_(process, data, *args, **kwargs):
     """update!(process, data, convolved) -- src/discrete.jl:369-375: one mean-field step of a discrete process; for a
-    continuous standard process update_(process, data, init=None, ...) is one step of inference.vb_step_continuous."""
+    continuous standard process update_(process, data, init=None, ...) is one step of inference.vb_step_continuous, for a
+    continuous network process one step of inference.vb_step_network_continuous."""
+    if isinstance(process, ContinuousNetworkHawkesProcess):
+        return _inf.vb_step_network_continuous(process, data, *args, **kwargs)
     if isinstance(process, ContinuousHawkesProcess):
         return _inf.vb_step_continuous(process, data, *args, **kwargs)
     return _disc.update_(process, data, *args, **kwargs)

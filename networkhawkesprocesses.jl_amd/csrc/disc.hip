@@ -1886,37 +1886,7 @@ __global__ __launch_bounds__(256) void k_netvb_factors(int N, int B, const doubl
     if (pc < (size_t)N) e0[pc] = nhp_exp(nhp_digamma(alpha_v[pc]) - nhp_log(beta_v[pc]));
 }
 
-// lgamma(x + d) - lgamma(x) for x > 0, x + d > 0.  Both arguments grow with the counts while d = κ1 - κ0 stays, so past
-// 16 the difference is taken inside Stirling's formula, where the two leading terms combine without cancellation:
-//   (x - 1/2) log1p(d/x) + d log(x + d) - d + [s(x + d) - s(x)],   s(z) = 1/(12 z) - 1/(360 z³) + ... (error < 1e-16 at 16).
-// Below 16 the two library values are at most 28 in size and their difference loses nothing that matters.
-__device__ __forceinline__ double netvb_stirling_tail(double z)
-{
-    const double f = 1.0 / (z * z);
-    return (1.0 / 12.0 + f * (-1.0 / 360.0 + f * (1.0 / 1260.0 + f * (-1.0 / 1680.0 + f * (1.0 / 1188.0))))) / z;
-}
-__device__ __forceinline__ double netvb_lgamma_diff(double x, double d)
-{
-    const double y = x + d;
-    if (x < 16.0 || y < 16.0) return lgamma(y) - lgamma(x);
-    return ((x - 0.5) * log1p(d / x) + d * nhp_log(y) - d) + (netvb_stirling_tail(y) - netvb_stirling_tail(x));
-}
-
-// logit ρv = net + prior + [lgamma κv1 - lgamma κv0] - [κv1 log νv1 - κv0 log νv0] with κv1 = κv0 + dk, νv1 = νv0 + dn
-// (dk = κ1 - κ0, dn = ν1 - ν0): the second bracket is κv0 log1p(dn/νv0) + dk log νv1, again without cancellation
-__device__ __forceinline__ double netvb_logit(double net, double prior, double dk, double dn, double kv0, double nv0, double nv1)
-{
-#pragma clang fp contract(off)
-    return ((net + prior) + netvb_lgamma_diff(kv0, dk)) - (kv0 * log1p(dn / nv0) + dk * nhp_log(nv1));
-}
-
-// 1/(1 + exp(-x)) in the form that keeps the small side's relative accuracy; exactly 0 below -708 and 1 above 37, no NaN
-__device__ __forceinline__ double netvb_sigmoid(double x)
-{
-    if (x >= 0.0) return 1.0 / (1.0 + nhp_exp(-x));
-    const double e = nhp_exp(x);
-    return e / (1.0 + e);
-}
+// (netvb_lgamma_diff, netvb_logit, netvb_sigmoid: nhp_math.h, shared with cont_netvb.hip)
 
 // After GEMM-2: Γ = E ⊙ Σ_z slab_z and the hats γ̂ = γ + nb Γ, κ̂_a = κ_a + Σ_b (γ̂ - γ), ν̂_a[p,c] = ν_a + Σ_t data[p,t]
 // (VB: nb = 1 and γ̂ = γ + Γ as k_vb_finish writes it); ρ̂ from the logit at the hats and the OLD network parameters

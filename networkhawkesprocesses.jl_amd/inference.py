@@ -469,6 +469,205 @@ def vb_continuous(process, data, max_steps=1000, f_abstol=1e-6, guess=None, recu
                                  status="success" if conv.value else "failure", elapsed=time.time() - start)
 
 
+# ---- mean-field variational inference for the continuous network process (csrc/cont_netvb.hip) ---------------------------
+NHP_VB_DENSE_NETWORK = 1024
+
+
+class ContinuousNetworkVariational(ContinuousVariational):
+    """The mean-field posterior of a continuous network process with spike-and-slab weights (definition: include/nhp.h,
+    nhp_cont_netvb_run).  ContinuousVariational's factors, where `kappa`, `nu` (the W block of `S`, `R`) are the SLAB's
+    q(W | A = 1) = Gamma(kappa, nu); in addition `kappa0`, `nu0` (the spike's q(W | A = 0)), `rho` = q(A = 1) (N×N, indexed
+    [parent, child]) and `net_alpha`, `net_beta` of q(ρ) = Beta (the values given for a dense network, where rho ≡ 1).
+    `pieces`, where a single step returned them: "loglam", and "before" / "after" = (E_q[compensator], KL_λ0, KL_W, KL_imp,
+    KL_net) of the state stepped from / returned.
+
+    mean() / sd() / interval() run over the planes S, R, in THEIR order [λ0; θ | μ, τ; W] with the slab for W -- the order of
+    the standard process's params().  A network process's own params() is ordered [ρ; λ0; W; impulses; vec(A)], so index
+    these summaries through the accessors (alpha, a, kappa, ...) rather than by position in process.params()."""
+
+    def __init__(self, kind, N, S, R, Q, prior_kappa=0.0, dense=False, **kw):
+        super().__init__(kind, N, S, R, prior_kappa, **kw)
+        NN = self.N * self.N
+        self.Q = np.array(Q, dtype=np.float64)
+        if self.Q.shape != (3 * NN + 2,):
+            raise ValueError("Q must hold 3·N² + 2 numbers: [κv0; νv0; ρv; αv; βv]")
+        self.dense = bool(dense)
+
+    def _qtable(self, block):
+        NN = self.N * self.N
+        return self.Q[block * NN:(block + 1) * NN].reshape((self.N, self.N), order="F")
+
+    kappa0 = property(lambda self: self._qtable(0))
+    nu0 = property(lambda self: self._qtable(1))
+    rho = property(lambda self: self._qtable(2))
+    net_alpha = property(lambda self: float(self.Q[-2]))
+    net_beta = property(lambda self: float(self.Q[-1]))
+
+    def link_probability(self):
+        """q(A[p, c] = 1) = ρv."""
+        return self.rho.copy()
+
+    def effective_weight_mean(self):
+        """E_q[W] with the link marginalised: (1 - ρv) κv0/νv0 + ρv κv1/νv1."""
+        return (1.0 - self.rho) * (self.kappa0 / self.nu0) + self.rho * (self.kappa / self.nu)
+
+
+def _netvb_check(process, data, what):
+    """The argument errors of the network fit, raised before any device work; returns (priors, net [κ0, ν0, α, β], dense)."""
+    from .components import BernoulliNetworkModel, DenseNetworkModel, SparseWeightModel
+    from .sharded import ShardedDataset
+    if not isinstance(process.weights, SparseWeightModel):
+        raise TypeError(f"{what} on a ContinuousNetworkHawkesProcess needs a SparseWeightModel (spike and slab); with other weights "
+                        f"it is defined for ContinuousStandardHawkesProcess")
+    if not isinstance(process.network, (BernoulliNetworkModel, DenseNetworkModel)):
+        raise NotImplementedError(f"{what}: a {type(process.network).__name__} is not implemented for continuous processes "
+                                  f"(DenseNetworkModel and BernoulliNetworkModel are)")
+    if not isinstance(process.baseline, HomogeneousProcess):
+        raise NotImplementedError(f"{what}: the update of a LogGaussianCoxProcess baseline has no closed form")
+    if isinstance(data, ShardedDataset):
+        raise NotImplementedError(f"{what}: not available on a column shard (sharded.ShardedDataset)")
+    w, net = process.weights, process.network
+    dense = isinstance(net, DenseNetworkModel)
+    b, imp = process.baseline, process.impulses
+    if isinstance(imp, ExponentialImpulseResponse):
+        pr = _lib.GibbsPriors(b.α0, b.β0, w.κ1, w.ν1, imp.α, imp.β, 0.0, 1.0)
+    else:
+        pr = _lib.GibbsPriors(b.α0, b.β0, w.κ1, w.ν1, imp.α0, imp.β0, imp.μμ, imp.κμ)
+    names = ["alpha0", "beta0", "kappa", "nu", "a", "b"] + ([] if isinstance(imp, ExponentialImpulseResponse) else ["kappa_mu"])
+    values = [(n, float(getattr(pr, n))) for n in names] + [("kappa0", w.κ0), ("nu0", w.ν0)]
+    if not dense:
+        values += [("network alpha", net.α), ("network beta", net.β), ("network alpha_v", net.αv), ("network beta_v", net.βv)]
+    for name, v in values:
+        if not (v > 0.0 and math.isfinite(v)):
+            raise ValueError(f"{what}: the hyper-parameter {name} = {v} must be positive and finite")
+    if not math.isfinite(float(pr.mu_mu)):
+        raise ValueError(f"{what}: the prior mean mu_mu = {pr.mu_mu} must be finite")
+    netp = np.array([w.κ0, w.ν0, 1.0 if dense else net.α, 1.0 if dense else net.β], dtype=np.float64)
+    return pr, netp, dense
+
+
+def _netvb_start_Q(process, dense):
+    """Q of a start without a state: ρv from weights.ρv (None: network.link_probability()), the network's own (αv, βv); the
+    spike's tables are output only."""
+    N = process.ndims()
+    w, net = process.weights, process.network
+    rho = net.link_probability() if w.ρv is None else np.asarray(w.ρv, dtype=np.float64)
+    if rho.shape != (N, N) or not np.all((rho >= 0.0) & (rho <= 1.0)):
+        raise ValueError("weights.ρv must be an N x N matrix of probabilities")
+    return np.concatenate([np.ones(2 * N * N), rho.ravel(order="F"), [1.0 if dense else net.αv, 1.0 if dense else net.βv]])
+
+
+def _netvb_state(process, init, P):
+    if not isinstance(init, ContinuousNetworkVariational):
+        raise TypeError("init must be a ContinuousNetworkVariational (the result of an earlier vb_ or update_ of a network process)")
+    if init.kind != _vb_kind_of(process) or init.S.shape != (P,):
+        raise ValueError("Parameter vector length does not match model parameter length.")
+    return init.S.copy(), init.R.copy(), init.Q.copy()
+
+
+def _device_length(process):
+    from .components import param_layout
+    return param_layout(process).weights.stop
+
+
+def vb_step_network_continuous(process, data, init=None, recursive=True, ctx=None):
+    """One coordinate-ascent update of the network process's mean-field posterior (nhp_cont_netvb_step): from the state
+    `init` (a ContinuousNetworkVariational), or with init=None from the process's current λ0, impulses and W used as if they
+    were a surrogate (iteration 0 of vb_) and the network's (αv, βv).  Returns the updated ContinuousNetworkVariational with
+    `pieces` (see the class); `elbo` is that of the state stepped from (NaN for init=None).  The process is not changed."""
+    import ctypes as C
+    from .continuous import _check_recursive
+    pr, netp, dense = _netvb_check(process, data, "update!")
+    P = _device_length(process)
+    flags = _check_recursive(process, recursive) | (NHP_VB_DENSE_NETWORK if dense else 0)
+    if init is None:
+        S, R, Q = np.empty(P), np.empty(P), _netvb_start_Q(process, dense)
+        flags |= NHP_VB_FROM_MODEL
+    else:
+        S, R, Q = _netvb_state(process, init, P)
+    ctx = ctx or _lib.default_context()
+    ds = device_dataset(process, data, ctx)
+    start = time.time()
+    model = process.device_model(ctx)
+    stats = np.empty(11)
+    _lib.check(_lib.lib().nhp_cont_netvb_step(ctx.h, ds.h, model.h, flags, C.byref(pr), _lib.dptr(netp), S.ctypes.data, R.ctypes.data, P,
+                                              Q.ctypes.data, 0, _lib.dptr(stats)), ctx.h)
+    elbo = float("nan") if init is None else float(stats[0] - stats[1] - stats[2] - stats[3] - stats[4] - stats[5])
+    res = ContinuousNetworkVariational(_vb_kind_of(process), process.ndims(), S, R, Q, pr.kappa, dense, elbo=elbo, steps=1,
+                                       elapsed=time.time() - start)
+    res.pieces = {"loglam": float(stats[0]), "before": tuple(stats[1:6]), "after": tuple(stats[6:11])}
+    return res
+
+
+def _netvb_write_back(process, x, res):
+    """vb_'s overwrite of a network process: posterior means, W = κv1/νv1, A = (ρv > ½), the network's Beta and the tables."""
+    from .components import param_layout
+    L = param_layout(process)
+    process.baseline.λ = x[L.baseline].copy()
+    process.impulses.params_(x[L.impulses])
+    process.weights.params_(x[L.weights])
+    w, net = process.weights, process.network
+    w.κv0, w.νv0, w.κv1, w.νv1, w.ρv = res.kappa0.copy(), res.nu0.copy(), res.kappa.copy(), res.nu.copy(), res.rho.copy()
+    w.κv, w.νv = w.κv1, w.νv1
+    process.adjacency_matrix = (res.rho > 0.5).astype(np.float64)
+    if not res.dense:
+        net.αv, net.βv = res.net_alpha, res.net_beta
+        net.ρ = net.αv / (net.αv + net.βv)
+
+
+def vb_network_continuous(process, data, max_steps=1000, f_abstol=1e-6, guess=None, recursive=True, init=None, keep_trace=True,
+                          verbose=False, ctx=None):
+    """Mean-field variational fit of a ContinuousNetworkHawkesProcess with SparseWeightModel weights under a Dense or
+    Bernoulli network, the whole iteration on the GPU (nhp_cont_netvb_run; the definition is in include/nhp.h).  It answers
+    "which links are there" -- q(A[p, c] = 1) = ρv -- without running a chain.
+
+    Arguments and stopping rule are vb_continuous's; `guess` is a vector in the device order [λ0; θ | μ, τ; W] (default: the
+    process's current values), `init=res` resumes from an earlier ContinuousNetworkVariational.  The network's (αv, βv) start
+    from the network's own.  The process is overwritten: λ0 and the impulses take their posterior means, weights.W = κv1/νv1,
+    adjacency_matrix = (ρv > ½), network.ρ = αv/(αv + βv) with network.αv, network.βv, and the weights' variational tables and ρv."""
+    import ctypes as C
+    from .continuous import _check_recursive
+    pr, netp, dense = _netvb_check(process, data, "vb!")
+    P = _device_length(process)
+    flags = _check_recursive(process, recursive) | (NHP_VB_DENSE_NETWORK if dense else 0)
+    max_steps = int(max_steps)
+    if init is not None:
+        if guess is not None:
+            raise ValueError("vb!: give a guess or a state to resume (init), not both")
+        S, R, Q = _netvb_state(process, init, P)
+        x = np.empty(P)
+        flags |= NHP_VB_RESUME
+    else:
+        if guess is None:
+            x = np.concatenate([process.baseline.params(), process.impulses.params(), process.weights.params()]).astype(np.float64)
+        else:
+            x = np.array(guess, dtype=np.float64)
+        if x.shape != (P,):
+            raise ValueError("Parameter vector length does not match model parameter length.")
+        S, R, Q = np.empty(P), np.empty(P), _netvb_start_Q(process, dense)
+    if max_steps < (0 if init is not None else 1):
+        raise ValueError("vb!: max_steps must be at least 1 (0 with init)")
+    ctx = ctx or _lib.default_context()
+    ds = device_dataset(process, data, ctx)
+    start = time.time()
+    model = process.device_model(ctx)
+    elbo, steps, conv = C.c_double(), C.c_int32(), C.c_int32()
+    trace = np.full(max_steps + 1, np.nan)
+    _lib.check(_lib.lib().nhp_cont_netvb_run(ctx.h, ds.h, model.h, flags, C.byref(pr), _lib.dptr(netp), float(f_abstol), max_steps,
+                                             _lib.dptr(x), _lib.dptr(S), _lib.dptr(R), P, _lib.dptr(Q), C.byref(elbo), C.byref(steps),
+                                             C.byref(conv), _lib.dptr(trace)), ctx.h)
+    first = 0 if init is not None else 1
+    if verbose:
+        for k in range(first, steps.value + 1):
+            print(f" > step: {k}, elbo: {trace[k]}")
+        print(f" > steps: {steps.value}, elbo: {elbo.value}, elapsed: {time.time() - start}")
+    res = ContinuousNetworkVariational(_vb_kind_of(process), process.ndims(), S, R, Q, pr.kappa, dense, elbo=elbo.value,
+                                       trace=trace[first:steps.value + 1].copy() if keep_trace else None, steps=steps.value,
+                                       status="success" if conv.value else "failure", elapsed=time.time() - start)
+    _netvb_write_back(process, x, res)
+    return res
+
+
 # ---- observed information, Hessian-vector products, standard errors ------------------------------------------------------
 Information =collections.namedtuple("Information", "ll columns blocks names")
 StandardErrors = collections.namedtuple("StandardErrors", "se lower_ci upper_ci free pd")

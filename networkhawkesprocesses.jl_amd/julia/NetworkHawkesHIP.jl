@@ -637,6 +637,93 @@ function update!(p::NHP.ContinuousStandardHawkesProcess, data; state=nothing, re
     (S=S, R=R, stats=stats)
 end
 
+# --- vb!(process, data; ...) and update!(process, data; state) for the continuous NETWORK process: no reference counterpart ---
+# Spike-and-slab weights (SparseWeightModel) under a DenseNetworkModel or BernoulliNetworkModel (nhp_cont_netvb_run /
+# nhp_cont_netvb_step; the definition is in include/nhp.h).  The state is (S, R, Q): the standard fit's planes in the device
+# order [λ0; impulses; W] with the slab's (κv1, νv1) in the W block, and Q = [κv0; νv0; ρv; αv; βv] (3N² + 2).  vb! returns
+# (S, R, Q, rho, elbo, trace, steps, status, elapsed) and overwrites the process: posterior means, weights.W = κv1/νv1,
+# adjacency_matrix = (ρv > ½), network.ρ = αv/(αv + βv) with αv, βv, and the weights' variational tables.  update! is one step
+# and returns (S, R, Q, stats) with the eleven numbers of nhp_cont_netvb_step; the process is not changed.
+const VB_DENSE_NETWORK = Int32(1024)
+
+function netvb_setup(p::NHP.ContinuousNetworkHawkesProcess, what)
+    p.weights isa NHP.SparseWeightModel || throw(ArgumentError("$what on a ContinuousNetworkHawkesProcess needs a SparseWeightModel"))
+    p.baseline isa NHP.HomogeneousProcess || error("$what: the update of a LogGaussianCoxProcess baseline has no closed form")
+    dense = p.network isa NHP.DenseNetworkModel
+    (dense || p.network isa NHP.BernoulliNetworkModel) || error("$what: only DenseNetworkModel and BernoulliNetworkModel are implemented")
+    w, imp, b = p.weights, p.impulses, p.baseline
+    pri = imp isa NHP.ExponentialImpulseResponse ? Priors(b.α0, b.β0, w.κ1, w.ν1, imp.α, imp.β, 0.0, 1.0) :
+                                                   Priors(b.α0, b.β0, w.κ1, w.ν1, imp.α0, imp.β0, imp.μμ, imp.κμ)
+    net = Float64[w.κ0, w.ν0, dense ? 1.0 : p.network.α, dense ? 1.0 : p.network.β]
+    N = NHP.ndims(p)
+    P = N + N * N * (imp isa NHP.ExponentialImpulseResponse ? 2 : 3)
+    pri, net, dense, N, P
+end
+
+# Q of a start without a state.  A run or a step from a guess reads of it the pair (αv, βv) alone (include/nhp.h): the three
+# planes are output only there, so the ρv plane written here (the network's link probability, where the Python front end
+# takes weights.ρv when it is set) never enters a result.
+function netvb_start_Q(p, dense, N)
+    rho = dense ? ones(N, N) : fill(Float64(p.network.ρ), N, N)
+    vcat(ones(2 * N * N), vec(rho), dense ? [1.0, 1.0] : Float64[p.network.αv, p.network.βv])
+end
+
+function vb!(p::NHP.ContinuousNetworkHawkesProcess, data; max_steps=1000, f_abstol=1e-6, guess=nothing, recursive=true,
+             state=nothing, verbose=false, ctx=context(), ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    pri0, net, dense, N, P = netvb_setup(p, "vb!")
+    x = Vector{Float64}(guess === nothing ? vcat(NHP.params(p.baseline), NHP.params(p.impulses), NHP.params(p.weights)) : guess)
+    length(x) == P || error("Parameter vector length does not match model parameter length.")
+    S, R, Q = state === nothing ? (Vector{Float64}(undef, P), Vector{Float64}(undef, P), netvb_start_Q(p, dense, N)) :
+                                  (Vector{Float64}(state[1]), Vector{Float64}(state[2]), Vector{Float64}(state[3]))
+    (length(S) == P && length(R) == P && length(Q) == 3 * N * N + 2) || error("Parameter vector length does not match model parameter length.")
+    flags = llflags(p, recursive) | (state === nothing ? Int32(0) : VB_RESUME) | (dense ? VB_DENSE_NETWORK : Int32(0))
+    elbo, steps, conv = Ref{Float64}(0.0), Ref{Int32}(0), Ref{Int32}(0)
+    trace = fill(NaN, max_steps + 1)
+    pri = Ref(pri0)
+    t0 = time()
+    with_model(ctx, p) do m
+        GC.@preserve pri check(ccall((:nhp_cont_netvb_run, libnhp), Int32,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Priors}, Ptr{Float64}, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+             Int64, Ptr{Float64}, Ref{Float64}, Ref{Int32}, Ref{Int32}, Ptr{Float64}),
+            ctx.h, ds.h, m, flags, Base.unsafe_convert(Ptr{Priors}, pri), net, f_abstol, Int32(max_steps), x, S, R, P, Q, elbo, steps, conv,
+            trace), ctx.h)
+    end
+    verbose && println(" > steps: $(steps[]), elbo: $(elbo[])")
+    NN = N * N
+    nimp = P - N - NN
+    NHP.params!(p.baseline, x[1:N]); NHP.params!(p.impulses, x[N+1:N+nimp]); NHP.params!(p.weights, x[N+nimp+1:end])
+    tab(v, j) = reshape(v[(j-1)*NN+1:j*NN], N, N)
+    rho = tab(Q, 3)
+    w = p.weights
+    w.κv0, w.νv0, w.κv1, w.νv1 = tab(Q, 1), tab(Q, 2), reshape(S[P-NN+1:P], N, N), reshape(R[P-NN+1:P], N, N)
+    p.adjacency_matrix .= rho .> 0.5
+    if !dense
+        p.network.αv, p.network.βv = Q[end-1], Q[end]
+        p.network.ρ = Q[end-1] / (Q[end-1] + Q[end])
+    end
+    first = state === nothing ? 2 : 1
+    (S=S, R=R, Q=Q, rho=rho, elbo=elbo[], trace=trace[first:steps[]+1], steps=Int(steps[]), status=conv[] == 1 ? "success" : "failure",
+     elapsed=time() - t0)
+end
+
+function update!(p::NHP.ContinuousNetworkHawkesProcess, data; state=nothing, recursive=true, ctx=context(),
+                 ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    pri0, net, dense, N, P = netvb_setup(p, "update!")
+    S, R, Q = state === nothing ? (Vector{Float64}(undef, P), Vector{Float64}(undef, P), netvb_start_Q(p, dense, N)) :
+                                  (Vector{Float64}(state[1]), Vector{Float64}(state[2]), Vector{Float64}(state[3]))
+    (length(S) == P && length(R) == P && length(Q) == 3 * N * N + 2) || error("Parameter vector length does not match model parameter length.")
+    flags = llflags(p, recursive) | (state === nothing ? VB_FROM_MODEL : Int32(0)) | (dense ? VB_DENSE_NETWORK : Int32(0))
+    stats = Vector{Float64}(undef, 11)
+    pri = Ref(pri0)
+    with_model(ctx, p) do m
+        GC.@preserve pri check(ccall((:nhp_cont_netvb_step, libnhp), Int32,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Priors}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Int32,
+             Ptr{Float64}),
+            ctx.h, ds.h, m, flags, Base.unsafe_convert(Ptr{Priors}, pri), net, S, R, P, Q, Int32(0), stats), ctx.h)
+    end
+    (S=S, R=R, Q=Q, stats=stats)
+end
+
 # --- observed_information(process, data) and hessian_vector_product(process, data, v): no reference counterpart ---------------
 # The objective separates by child node, so minus its Hessian is block diagonal: blocks[:, :, k] is the D x D block of column
 # columns[k] (1-based here) over [λ0[c]; θ[:,c] | μ[:,c]; τ[:,c]; W[:,c]], D = 1 + kinds·N (nhp_cont_information; homogeneous

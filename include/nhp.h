@@ -1379,6 +1379,60 @@ nhp_status nhp_cont_netvb_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont
                               double *Q /* [3*N*N + 2] */, double *elbo, int32_t *steps, int32_t *converged,
                               double *trace /* nullable, [max_steps + 1] */);
 
+/* Mean-field variational inference for the continuous network process under a STOCHASTIC BLOCK network (csrc/cont_netvb.hip,
+ * DESIGN §3.31).  Likelihood, λ0, impulse and weight factors are exactly nhp_cont_netvb_run's; the network part is
+ *   z_n ~ Categorical(π),  π ~ Dirichlet(γ·1_K),  ρ[k,l] ~ Beta(α, β),  A[p,c] ~ Bernoulli(ρ[z_p, z_c]),  diagonal included,
+ *   q(z_n) = Categorical(m[n,:]),  q(π) = Dirichlet(γv),  q(ρ[k,l]) = Beta(αv[k,l], βv[k,l]),  q(A[p,c] = 1) = ρv[p,c].
+ * With  E1 = ψ(αv) - ψ(αv+βv),  E0 = ψ(βv) - ψ(αv+βv),  D = ψ(αv) - ψ(βv),  Eπ = ψ(γv) - ψ(Σγv)  and
+ *   ω[p,c,k,l] = m[p,k] m[c,l] (p ≠ c),   ω[p,p,k,l] = m[p,k] δ_kl   (a node has one label).
+ * net = [κ0, ν0] (the spike), sbm = [α, β, γ], n_blocks = K in 1..64.  The state is S, R [len] (nhp_cont_netvb_run's),
+ * Q = [κv0; νv0; ρv] of 3·N² doubles, column-major [p + c·N], and B = [vec αv; vec βv; γv; vec m] of 2K² + K + N·K doubles,
+ * column-major (m is [n + k·N]).  One step from state k has the global number i = step0 + (steps taken in this call) + 1:
+ *   1. surrogate and E-step as nhp_cont_netvb_step (E log W mixes spike and slab with ρv; the E-step runs at x̃ on the model
+ *      without its adjacency matrix);
+ *   2. λ0, the impulse factors and κv_a = κ_a + EM, νv_a = ν_a + cnt_p as nhp_cont_netvb_step;
+ *   3. logit ρv[p,c] = net[p,c] + the prior and lnΓ / log ν terms of nhp_cont_netvb_step's step 3, in the same cancellation-free
+ *      form, where  net[p,c] = Σ_kl ω[p,c,k,l] D[k,l]  from the OLD m, αv, βv:  m·D first (k increasing), then
+ *      Σ_l (m·D)[p,l] m[c,l] (l increasing) off the diagonal and Σ_k m[p,k] D[k,k] on it;
+ *   4. αv = α + Σ_pc ω ρv,  βv = β + Σ_pc ω (1 - ρv),  γv = γ + Σ_n m  from the NEW ρv and the current m;
+ *   5. if i % labels_every == 0 the sequential label sweep over the nodes 0 .. N-1, each node reading the current m of the
+ *      others:  m[n,:] = softmax(s),  s_k = Eπ[k] + ρv[n,n] E1[k,k] + (1 - ρv[n,n]) E0[k,k] + Σ_{c≠n} Σ_l m[c,l] (ρv[n,c] E1[k,l]
+ *      + (1 - ρv[n,c]) E0[k,l] + ρv[c,n] E1[l,k] + (1 - ρv[c,n]) E0[l,k])  at the tables of step 4 (nhp_disc_sbmvb_run's sweep: there
+ *      is one in the library); otherwise m stays bit for bit.
+ * Each of (2-3), 4 and 5 is an exact block of coordinate ascent, so the ELBO never falls:
+ *   L = Σ_i log λ̃_i - E_q[comp] - KL_λ0 - KL_W - KL_imp - KL_net          (the first five as nhp_cont_netvb_run)
+ *   KL_net = Σ_pc [ρv ln ρv + (1-ρv) ln(1-ρv)] - [links + labels - KL_Dir - ΣKL_Beta]
+ *   links = Σ_kl (T1 E1 + T0 E0),  T1 = Σ_pc ω ρv,  T0 = Σ_pc ω (1 - ρv)  at the state's OWN m (after the sweep, if one ran)
+ *   labels = Σ_nk m (Eπ - ln m),  KL_Dir = KL(Dir(γv) ‖ Dir(γ·1_K)),  ΣKL_Beta = Σ_kl KL(Beta(αv,βv) ‖ Beta(α,β)),  0·ln 0 = 0.
+ * With K = 1 every formula is the Bernoulli network's (m ≡ 1, Eπ = 0, KL_Dir = 0).  Every sum is taken in one fixed order.
+ *
+ * nhp_cont_sbmvb_step: one update, numbered step0 + 1.  S, R, Q, B: the state on entry, the updated state on return (host
+ * pointers, or all four device pointers with output_on_device); with NHP_VB_FROM_MODEL the E-step runs at the model's current
+ * parameters and of the state on entry B alone is read.  stats [21] (host): [0..10] as nhp_cont_netvb_step with KL_net as
+ * above in [5] and [10]; [11..15] the network pieces (Σ entropy of ρv, links, labels, KL_Dir, ΣKL_Beta) of the state stepped
+ * from (0 with NHP_VB_FROM_MODEL), [16..20] of the state returned.  Synchronous; the model is not changed.
+ *
+ * nhp_cont_sbmvb_run: the whole iteration on the device; loop, stopping rule, trace, NHP_VB_RESUME (S, R, Q hold a state; B
+ * always does) and empty-dataset handling are nhp_cont_vb_run's.  On return S, R, Q, B hold state k, x its means and the
+ * device model holds them and A = (ρv > ½), as nhp_cont_netvb_run leaves them.
+ *
+ * Errors of both, before any launch: NHP_ENOTIMPL for an LGCP baseline, a column shard, a model without A, a latent
+ * distance network attached, and a label sweep whose LDS need exceeds a CU's; NHP_EINVAL for a missing argument, K outside
+ * 1..64, labels_every < 1, step0 < 0, priors or (host pointers) tables that are not positive and finite, a row of m that
+ * does not sum to 1 within 1e-12, the NHP_VB_DENSE_NETWORK flag, and nhp_cont_netvb_step's checks of κ0, ν0, ρv, κv, νv.  Then
+ * NHP_EDOMAIN and NHP_ESHAPE as nhp_cont_vb_run.  nhp_cont_netvb_step / _run keep refusing a model with a block network. */
+nhp_status nhp_cont_sbmvb_step(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *model, int32_t flags,
+                               const nhp_gibbs_priors *priors, const double *net /* [2] */, const double *sbm /* [3] */,
+                               int32_t n_blocks, int32_t labels_every, int64_t step0, double *S /* [len] */, double *R /* [len] */,
+                               int64_t len, double *Q /* [3*N*N] */, double *B /* [2*K*K + K + N*K] */, int32_t output_on_device,
+                               double *stats /* [21] */);
+nhp_status nhp_cont_sbmvb_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *model, int32_t flags,
+                              const nhp_gibbs_priors *priors, const double *net /* [2] */, const double *sbm /* [3] */,
+                              int32_t n_blocks, int32_t labels_every, int64_t step0, double f_abstol, int32_t max_steps,
+                              double *x /* [len] */, double *S /* [len] */, double *R /* [len] */, int64_t len,
+                              double *Q /* [3*N*N] */, double *B /* [2*K*K + K + N*K] */, double *elbo, int32_t *steps,
+                              int32_t *converged, double *trace /* nullable, [max_steps + 1] */);
+
 /* Observed information and Hessian-vector products of the continuous log-likelihood (csrc/cont_information.hip).  The
  * objective nhp_cont_loglik evaluates separates by child node c, so its Hessian is block diagonal: one block per column
  * over the D = 1 + kinds·N parameters [λ0[c]; θ[:,c] | μ[:,c]; τ[:,c]; W[:,c]] (kinds = 2 exponential, 3 logit-normal), row and

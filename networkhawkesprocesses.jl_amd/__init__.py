@@ -31,7 +31,8 @@ from .parents import (Cascades, cascades, map_parents, node_counts, parent_count
 from .inference import (ExpectedStatistics, Information, MarkovChainMonteCarlo, MaximumLikelihood, StandardErrors,  # noqa: F401
                         em_, expected_statistics, hessian_vector_product, logprior, observed_information,
                         resample_adjacency_matrix_, standard_errors,
-                        ContinuousScore, score_samples, ChainQuantiles, ContinuousVariational, ContinuousNetworkVariational)
+                        ContinuousScore, score_samples, ChainQuantiles, ContinuousVariational, ContinuousNetworkVariational,
+                        ContinuousBlockNetworkVariational)
 from . import inference as _inf
 from . import synthetic  # noqa: F401
 from .synthetic import rand  # noqa: F401   rand(process, duration): the reference's exported simulator name
@@ -92,7 +93,8 @@ def vb_(process, data, *args, **kwargs):
     """vb!(process, data; ...) -- src/inference.jl:153-181 for discrete processes; for a continuous standard process the
     mean-field fit of inference.vb_continuous (a ContinuousVariational); for a continuous network process with
     SparseWeightModel weights and a Dense or Bernoulli network inference.vb_network_continuous (a
-    ContinuousNetworkVariational with the link probabilities)."""
+    ContinuousNetworkVariational with the link probabilities), and under a StochasticBlockNetworkModel with a variational state
+    (network.variational_init_()) a ContinuousBlockNetworkVariational with the labels and block tables as well."""
     if isinstance(process, ContinuousNetworkHawkesProcess):
         return _inf.vb_network_continuous(process, data, *args, **kwargs)
     if isinstance(process, ContinuousHawkesProcess):

@@ -17,8 +17,10 @@
 #include <cmath>
 
 #include "nhp_cnetvb.h"
+#include "nhp_csbmvb.h"
 #include "nhp_internal.h"
 #include "nhp_math.h"
+#include "nhp_sbmvb_dev.h"
 #include "nhp_vb.h"
 
 namespace {
@@ -265,7 +267,7 @@ __global__ __launch_bounds__(256) void k_cnetvb_mean(vb_args a, const double *__
 
 // the refusals and argument errors of both entry points, before any launch
 nhp_status cn_check(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const nhp_gibbs_priors *pr, const double *net, bool dense,
-                    const char *what)
+                    const char *what, bool block = false)
 {
     NHP_TRY(nhp_check_pair(ctx, ds, m));
     if (m->baseline_kind != NHP_BASELINE_HOMOGENEOUS) {
@@ -276,7 +278,11 @@ nhp_status cn_check(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_mod
         nhp_set_error(ctx, "%s (network) is defined for ContinuousNetworkHawkesProcess: the model has no adjacency matrix (nhp_cont_vb_run fits the standard process)", what);
         return NHP_ENOTIMPL;
     }
-    if (m->sbm || m->latent) {
+    if (block && m->latent) {
+        nhp_set_error(ctx, "%s: a latent distance network is attached to the model (the block-network fit needs none)", what);
+        return NHP_ENOTIMPL;
+    }
+    if (!block && (m->sbm || m->latent)) {
         nhp_set_error(ctx, "%s: a block or latent distance network is not implemented (dense and Bernoulli networks are)", what);
         return NHP_ENOTIMPL;
     }
@@ -291,7 +297,7 @@ nhp_status cn_check(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_mod
         return NHP_EINVAL;
     }
     char msg[200];
-    if (cnetvb_check_net(what, net, dense, msg, sizeof msg) != CNETVB_OK) { nhp_set_error(ctx, "%s", msg); return NHP_EINVAL; }
+    if (cnetvb_check_net(what, net, dense || block, msg, sizeof msg) != CNETVB_OK) { nhp_set_error(ctx, "%s", msg); return NHP_EINVAL; }
     return NHP_OK;
 }
 
@@ -337,6 +343,240 @@ nhp_cont_model cn_unmasked(const nhp_cont_model *m)
     nhp_cont_model v = *m;
     v.has_A = 0; v.d_A = nullptr;
     return v;
+}
+
+// ---- the block network (the definition is in include/nhp.h, nhp_cont_sbmvb_run) --------------------------------
+// The Bernoulli fit with A[p,c] ~ Bernoulli(ρ[z_p, z_c]): the scalar ψ(αv) - ψ(βv) of the logit becomes the link's own
+// net[p,c] = Σ_kl ω D (sbmvb_net), and the network's Beta becomes the block model's state B = [αv; βv; γv; m], updated by the
+// kernels of nhp_sbmvb_dev.h -- the tables from the new ρv, then THE label sweep at the steps that have one.
+
+struct cb_args {
+    int N, K;
+    double alpha, beta, gamma;       // the block model's priors
+    double beta_const, dir_const;    // lnΓ(α+β) - lnΓα - lnΓβ and lnΓ(Kγ) - K lnΓγ
+};
+
+// a state on the device: cn_state's (Q = the three planes alone), B = [αv; βv; γv; m] and T = [T1; T0; Σ_n m] at its own m
+struct cb_state { double *x, *S, *R, *Q, *B, *T, *part; };
+// what both states share: D, the four tables, Eπ, m·D, U1, U0
+struct cb_scratch { double *D, *tabs, *Epi, *mD, *U1, *U0; };
+
+// k_cnetvb_update with the link's own network term in place of the scalar: factors (S, R, Q) from the surrogate x, the
+// gradient g at it and blk = (m, m·D, D) of the state stepped from; their surrogate xn, their pieces.  Link k = p + c·N, p
+// fastest: (m·D)[p,l] is coalesced per l, m[c,l] one address for (almost) the whole wave; the term is a running sum.
+__global__ __launch_bounds__(256) void k_csbmvb_update(cn_args A, const double *__restrict__ x, const double *__restrict__ g, sbmvb_link blk,
+                                                       double *__restrict__ S, double *__restrict__ R, double *__restrict__ Q,
+                                                       double *__restrict__ xn, double *__restrict__ part)
+{
+    const vb_args &a = A.v;
+    const size_t N = (size_t)a.N, NN = N * N;
+    const nhp_layout L = vb_layout(a);
+    const nhp_gibbs_priors &q = a.pr;
+    cn_acc s;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < N + NN; i += (size_t)gridDim.x * 256) {
+        if (i < N) {
+            const double al = q.alpha0 + x[i] * (g[i] + a.T), be = q.beta0 + a.T;
+            S[i] = al; R[i] = be;
+            xn[i] = vb_baseline(a, al, be, s);
+            continue;
+        }
+        const size_t k = i - N, p = k % N, c = k / N;
+        const double cp = a.cnt ? a.cnt[p] : 0.0;
+        const double EM = x[L.W + k] * (g[L.W + k] + cp);
+        const double kv1 = q.kappa + EM, nv1 = q.nu + cp, kv0 = A.k0 + EM, nv0 = A.n0 + cp;
+        double m = 0.0, kk = 1.0, sa, sb;
+        if (a.impulse == NHP_IMPULSE_EXPONENTIAL) {
+            sa = q.a + EM;
+            sb = q.b + (EM / x[L.p1 + k] - g[L.p1 + k]);
+            S[L.p1 + k] = sa; R[L.p1 + k] = sb;
+        } else {
+            const double cc = x[L.p1 + k], tau = x[L.p2 + k];
+            const double D1 = g[L.p1 + k] / tau, S2 = EM / tau - 2.0 * g[L.p2 + k], d0 = q.mu_mu - cc;
+            kk = q.kappa_mu + EM;
+            const double dm = (D1 + q.kappa_mu * d0) / kk;
+            m = cc + dm;
+            sa = q.a + 0.5 * EM;
+            sb = q.b + 0.5 * ((S2 + q.kappa_mu * (d0 * d0)) - kk * (dm * dm));
+            S[L.p1 + k] = m; R[L.p1 + k] = kk;
+            S[L.p2 + k] = sa; R[L.p2 + k] = sb;
+        }
+        S[L.W + k] = kv1; R[L.W + k] = nv1;
+        const cn_tab t = cn_tables(kv0, nv0, kv1, nv1);
+        const double rho = cn_rho(A, sbmvb_net(blk, N, p, c), kv0, nv0, kv1, t);
+        double w, p1, p2;
+        cn_link(A, cp, kv0, nv0, kv1, nv1, t, rho, m, kk, sa, sb, s, w, p1, p2);
+        Q[k] = kv0; Q[NN + k] = nv0; Q[2 * NN + k] = rho;
+        vb_write(a, L, xn, k, w, p1, p2);
+    }
+    cn_store(s, part);
+}
+
+// out = k_cnetvb_elbo's eight, then [Σ entropy of ρv, links, labels, KL_Dir, Σ KL_Beta]: the partial sums in one fixed order and
+// the network pieces of the state (B, T) -- T1, T0 taken at the state's OWN m --
+//   links = Σ_kl (T1 E1 + T0 E0),  labels = Σ_nk m (Eπ - ln m)  (0·ln 0 = 0),  KL_net = Σ entropy - (links + labels - KL_Dir - Σ KL_Beta).
+// Thread i adds the entries i, i + 256, ... in increasing order and nhp_block_sum_n joins the threads in its fixed order.
+__global__ __launch_bounds__(256) void k_csbmvb_elbo(cb_args b, const double *__restrict__ ll, const double *__restrict__ part,
+                                                     const double *__restrict__ B, const double *__restrict__ T, double *__restrict__ out)
+{
+    __shared__ double red[4];
+    __shared__ double tot[CNETVB_PIECES];
+    __shared__ double epi[SBMVB_MAX_BLOCKS];
+    for (int j = 0; j < CNETVB_PIECES; ++j) {
+        double v = 0.0;
+        for (int i = threadIdx.x; i < VB_BLK; i += 256) v += part[j * VB_BLK + i];
+        v = nhp_block_sum_n<4>(v, red);
+        if (threadIdx.x == 0) tot[j] = v;
+    }
+    const int K = b.K, KK = K * K;
+    const size_t N = (size_t)b.N;
+    const double *av = B, *bv = B + KK, *gv = B + 2 * KK, *m = B + 2 * KK + K;
+    const double *T1 = T, *T0 = T + KK;
+    double links = 0.0, klb = 0.0;
+    for (int i = threadIdx.x; i < KK; i += 256) {
+        double pa, la, pb, lb, ps, ls;
+        nhp_digamma_lgamma(av[i], pa, la);
+        nhp_digamma_lgamma(bv[i], pb, lb);
+        nhp_digamma_lgamma(av[i] + bv[i], ps, ls);
+        const double e1 = pa - ps, e0 = pb - ps;                     // E log ρ[k,l], E log(1 - ρ[k,l])
+        links += T1[i] * e1 + T0[i] * e0;
+        klb += (((ls - la) - lb) - b.beta_const) + ((av[i] - b.alpha) * e1 + (bv[i] - b.beta) * e0);
+    }
+    links = nhp_block_sum_n<4>(links, red);
+    klb = nhp_block_sum_n<4>(klb, red);
+    double gs = 0.0;
+    for (int k = 0; k < K; ++k) gs += gv[k];
+    if ((int)threadIdx.x < K) epi[threadIdx.x] = nhp_digamma(gv[threadIdx.x]) - nhp_digamma(gs);
+    __syncthreads();
+    double lab = 0.0;
+    for (size_t i = threadIdx.x; i < N * (size_t)K; i += 256) {
+        const double v = m[i];
+        lab += v * epi[i / N] - (v > 0.0 ? v * nhp_log(v) : 0.0);
+    }
+    lab = nhp_block_sum_n<4>(lab, red);
+    if (threadIdx.x == 0) {
+        double pg, lgs, lsum = 0.0, dot = 0.0;
+        nhp_digamma_lgamma(gs, pg, lgs);
+        for (int k = 0; k < K; ++k) {
+            double pk, lk;
+            nhp_digamma_lgamma(gv[k], pk, lk);
+            lsum += lk;
+            dot += (gv[k] - b.gamma) * epi[k];
+        }
+        const double kldir = ((lgs - lsum) - b.dir_const) + dot;
+        const double sl = *ll + tot[0];
+        const double klnet = tot[5] - (((links + lab) - kldir) - klb);
+        out[0] = sl;
+        for (int j = 1; j < 5; ++j) out[j] = tot[j];
+        out[5] = klnet;
+        out[6] = ((((sl - tot[1]) - tot[2]) - tot[3]) - tot[4]) - klnet;
+        out[7] = 0.0;
+        out[8] = tot[5]; out[9] = links; out[10] = lab; out[11] = kldir; out[12] = klb;
+    }
+}
+
+void cb_carve(double *base, size_t P, size_t N, size_t K, cb_state &cur, cb_state &nxt, cb_scratch &w, double **d_out)
+{
+    const size_t stride = csbmvb_state_doubles(P, N, K, VB_BLK), NN = N * N, KK = K * K, NK = N * K;
+    cb_state *st[2] = {&cur, &nxt};
+    for (int j = 0; j < 2; ++j) {
+        double *p = base + j * stride;
+        st[j]->x = p; p += P;
+        st[j]->S = p; p += P;
+        st[j]->R = p; p += P;
+        st[j]->Q = p; p += 3 * NN;
+        st[j]->B = p; p += csbmvb_b_doubles(N, K);
+        st[j]->T = p; p += csbmvb_t_doubles(K);
+        st[j]->part = p;
+    }
+    double *p = base + 2 * stride;
+    w.D = p; p += KK;
+    w.tabs = p; p += 4 * KK;
+    w.Epi = p; p += K;
+    w.mD = p; p += NK;
+    w.U1 = p; p += NK;
+    w.U0 = p; p += NK;
+    *d_out = p;
+}
+
+// the checks of both block entry points before any launch: cn_check's, then the block model's own
+nhp_status cb_check(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int32_t flags, const nhp_gibbs_priors *pr, const double *net,
+                    const double *sbm, int32_t K, int32_t labels_every, int64_t step0, const double *B, bool B_on_host, const char *what)
+{
+    const bool dense = (flags & NHP_VB_DENSE_NETWORK) != 0;
+    char msg[256];
+    // (the flag and the pointers first: cn_check reads net)
+    if (dense || !net || !sbm) {
+        csbmvb_check_args(what, m ? m->N : 0, net, sbm, K, labels_every, step0, dense, nullptr, msg, sizeof msg);
+        nhp_set_error(ctx, "%s", msg);
+        return NHP_EINVAL;
+    }
+    NHP_TRY(cn_check(ctx, ds, m, pr, net, false, what, true));
+    const int rc = csbmvb_check_args(what, m->N, net, sbm, K, labels_every, step0, false, B, msg, sizeof msg, !B_on_host);
+    if (rc == CSBMVB_OK) return NHP_OK;
+    nhp_set_error(ctx, "%s", msg);
+    return rc == CSBMVB_ENOTIMPL ? NHP_ENOTIMPL : NHP_EINVAL;
+}
+
+nhp_status cb_check_state(nhp_ctx *ctx, const nhp_cont_model *m, bool state, const double *S, const double *R, const double *Q, const char *what)
+{
+    const nhp_layout L(m);
+    char msg[200];
+    if (csbmvb_check_state(what, (size_t)m->N, state, Q, S + L.W, R + L.W, msg, sizeof msg) != CSBMVB_OK) {
+        nhp_set_error(ctx, "%s", msg);
+        return NHP_EINVAL;
+    }
+    return NHP_OK;
+}
+
+cb_args cb_make_args(const nhp_cont_model *m, const double *sbm, int32_t K)
+{
+    cb_args b{};
+    b.N = m->N; b.K = K;
+    b.alpha = sbm[0]; b.beta = sbm[1]; b.gamma = sbm[2];
+    b.beta_const = cnetvb_beta_const(sbm[0], sbm[1]);
+    b.dir_const = csbmvb_dir_const(sbm[2], K);
+    return b;
+}
+
+// T = [T1; T0; Σ_n m] of state s at its own m (k_sbmvb_u, then the tables' reduction with zero priors); with `have_U` the link
+// sums in w.U1, w.U0 are already those of (s's ρv, s's m)
+void cb_own_sums(hipStream_t st, const cb_args &b, const cb_state &s, const cb_scratch &w, bool have_U)
+{
+    const size_t N = (size_t)b.N, K = (size_t)b.K, KK = K * K;
+    const double *rho = s.Q + 2 * N * N, *m = s.B + 2 * KK + K;
+    if (!have_U) hipLaunchKernelGGL(k_sbmvb_u, dim3((unsigned)((N * K + 255) / 256)), dim3(256), 0, st, b.N, b.K, rho, m, w.U1, w.U0);
+    hipLaunchKernelGGL(k_sbmvb_tables, dim3((unsigned)KK), dim3(256), 0, st, b.N, b.K, rho, m, (const double *)w.U1, (const double *)w.U0, 0.0, 0.0,
+                       0.0, s.T, s.T + KK, s.T + 2 * KK);
+}
+
+// the update from `cur` (surrogate cur.x, gradient g) to `nxt`: steps 2-5 of the definition
+nhp_status cb_update(nhp_ctx *ctx, hipStream_t st, const cn_args &A, const cb_args &b, const cb_state &cur, const cb_state &nxt, const cb_scratch &w,
+                     const double *g, bool sweep)
+{
+    const size_t N = (size_t)b.N, K = (size_t)b.K, KK = K * K, NK = N * K, NN = N * N;
+    const dim3 block(256), gk((unsigned)((KK + 255) / 256)), gnk((unsigned)((NK + 255) / 256));
+    double *cm = cur.B + 2 * KK + K, *nm = nxt.B + 2 * KK + K, *nrho = nxt.Q + 2 * NN;
+    // D from the OLD tables and m·D from the OLD m, then the O(P) pass
+    hipLaunchKernelGGL(k_sbmvb_expect, gk, block, 0, st, b.K, (const double *)cur.B, (const double *)(cur.B + KK), (const double *)(cur.B + 2 * KK),
+                       w.D, w.tabs, w.Epi);
+    hipLaunchKernelGGL(k_sbmvb_md, gnk, block, 0, st, b.N, b.K, (const double *)cm, (const double *)w.D, w.mD);
+    hipLaunchKernelGGL(k_csbmvb_update, dim3(VB_BLK), block, 0, st, A, (const double *)cur.x, g,
+                       sbmvb_link{b.K, cm, w.mD, w.D, nullptr}, nxt.S, nxt.R, nxt.Q, nxt.x, nxt.part);
+    // the tables from the NEW ρv and the current m
+    hipLaunchKernelGGL(k_sbmvb_u, gnk, block, 0, st, b.N, b.K, (const double *)nrho, (const double *)cm, w.U1, w.U0);
+    hipLaunchKernelGGL(k_sbmvb_tables, dim3((unsigned)KK), block, 0, st, b.N, b.K, (const double *)nrho, (const double *)cm, (const double *)w.U1,
+                       (const double *)w.U0, b.alpha, b.beta, b.gamma, nxt.B, nxt.B + KK, nxt.B + 2 * KK);
+    NHP_HIP(ctx, hipMemcpyAsync(nm, cm, 8 * NK, hipMemcpyDeviceToDevice, st));
+    if (sweep) {
+        hipLaunchKernelGGL(k_sbmvb_expect, gk, block, 0, st, b.K, (const double *)nxt.B, (const double *)(nxt.B + KK),
+                           (const double *)(nxt.B + 2 * KK), w.D, w.tabs, w.Epi);
+        sbmvb_bufs s{};
+        s.tabs = w.tabs; s.Epi = w.Epi;
+        NHP_TRY(sbmvb_launch_sweep(ctx, st, s, N, K, nrho, nm));
+    }
+    cb_own_sums(st, b, nxt, w, !sweep);                              // (no sweep: m is the one the link sums were taken at)
+    NHP_HIP(ctx, hipGetLastError());
+    return NHP_OK;
 }
 
 }   // namespace
@@ -490,6 +730,177 @@ extern "C" nhp_status nhp_cont_netvb_run(nhp_ctx *ctx, const nhp_cont_dataset *d
     NHP_TRY(nhp_download(ctx, S, cur.S, 8 * P));
     NHP_TRY(nhp_download(ctx, R, cur.R, 8 * P));
     NHP_TRY(nhp_download(ctx, Q, cur.Q, 8 * (3 * NN + 2)));
+    NHP_HIP(ctx, hipStreamSynchronize(st));
+    *elbo = L; *steps_out = k; *converged_out = converged ? 1 : 0;
+    return NHP_OK;
+}
+
+extern "C" nhp_status nhp_cont_sbmvb_step(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int32_t flags,
+                                          const nhp_gibbs_priors *priors, const double *net, const double *sbm, int32_t n_blocks,
+                                          int32_t labels_every, int64_t step0, double *S, double *R, int64_t len, double *Q, double *B,
+                                          int32_t output_on_device, double *stats)
+{
+    if (!ctx || !ds || !m || !priors || !S || !R || !Q || !B || !stats) return NHP_EINVAL;
+    const bool from_model = (flags & NHP_VB_FROM_MODEL) != 0;
+    NHP_TRY(cb_check(ctx, ds, m, flags, priors, net, sbm, n_blocks, labels_every, step0, B, !output_on_device, "update!"));
+    const size_t P = nhp_layout(m).P, N = (size_t)m->N, NN = N * N, K = (size_t)n_blocks, nB = csbmvb_b_doubles(N, K);
+    NHP_TRY(nhp_layout_check(ctx, nhp_layout(m), len));
+    if (!output_on_device) NHP_TRY(cb_check_state(ctx, m, !from_model, S, R, Q, "update!"));
+    NHP_HIP(ctx, hipSetDevice(ctx->device));
+    NHP_TRY(nhp_check_deferred(ctx));
+    hipStream_t st = ctx->main();
+    flags &= ~(int32_t)(NHP_VB_FROM_MODEL | NHP_VB_RESUME | NHP_VB_DENSE_NETWORK);
+
+    NHP_TRY(nhp_ctx_reserve_mle(ctx, 8 * csbmvb_reserve_doubles(P, N, K, VB_BLK), "variational state"));
+    cb_state cur, nxt;
+    cb_scratch w;
+    double *d_out = nullptr;
+    cb_carve((double *)ctx->d_mle, P, N, K, cur, nxt, w, &d_out);
+    cn_args A = cn_make_args(ds, m, priors, net, true);              // (net = [κ0, ν0] alone: the Beta's slots stay 0 and unread)
+    A.dense = 0;
+    const cb_args b = cb_make_args(m, sbm, n_blocks);
+    const dim3 grid(VB_BLK), block(256);
+    const hipMemcpyKind in = output_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    NHP_HIP(ctx, hipMemcpyAsync(cur.B, B, 8 * nB, in, st));
+    if (from_model) {
+        hipLaunchKernelGGL(k_cnetvb_start, grid, block, 0, st, A, (const double *)m->d_params, cur.x, cur.part);
+        NHP_HIP(ctx, hipMemsetAsync(cur.T, 0, 8 * csbmvb_t_doubles(K), st));     // (no state: of its evaluation Σ log λ̃ alone is used)
+    } else {
+        NHP_HIP(ctx, hipMemcpyAsync(cur.Q, Q, 8 * 3 * NN, in, st));
+        NHP_HIP(ctx, hipMemcpyAsync(cur.S, S, 8 * P, in, st));
+        NHP_HIP(ctx, hipMemcpyAsync(cur.R, R, 8 * P, in, st));
+        hipLaunchKernelGGL(k_cnetvb_surrogate, grid, block, 0, st, A, (const double *)cur.S, (const double *)cur.R, cur.Q, cur.x, cur.part);
+        cb_own_sums(st, b, cur, w, false);
+    }
+    NHP_HIP(ctx, hipGetLastError());
+    double *d_grad = nullptr;
+    nhp_cont_model mm = cn_unmasked(m);                               // (the E-step bumps the version of what it evaluates)
+    NHP_TRY(nhp_em_estep(ctx, ds, &mm, flags, cur.x, (int64_t)P, &d_grad));
+    hipLaunchKernelGGL(k_csbmvb_elbo, dim3(1), block, 0, st, b, (const double *)ctx->d_results, (const double *)cur.part, (const double *)cur.B,
+                       (const double *)cur.T, d_out);
+    NHP_TRY(cb_update(ctx, st, A, b, cur, nxt, w, d_grad, (step0 + 1) % labels_every == 0));
+    hipLaunchKernelGGL(k_csbmvb_elbo, dim3(1), block, 0, st, b, (const double *)ctx->d_results, (const double *)nxt.part, (const double *)nxt.B,
+                       (const double *)nxt.T, d_out + CSBMVB_OUT);
+    NHP_HIP(ctx, hipGetLastError());
+    double h[2 * CSBMVB_OUT];
+    NHP_TRY(nhp_download(ctx, h, d_out, sizeof h));
+    if (!std::isfinite(h[0])) {
+        NHP_HIP(ctx, hipStreamSynchronize(st));
+        nhp_set_error(ctx, "update!: the intensity of some event is not positive and finite");
+        return NHP_EDOMAIN;
+    }
+    if (output_on_device) {
+        NHP_HIP(ctx, hipMemcpyAsync(S, nxt.S, 8 * P, hipMemcpyDeviceToDevice, st));
+        NHP_HIP(ctx, hipMemcpyAsync(R, nxt.R, 8 * P, hipMemcpyDeviceToDevice, st));
+        NHP_HIP(ctx, hipMemcpyAsync(Q, nxt.Q, 8 * 3 * NN, hipMemcpyDeviceToDevice, st));
+        NHP_HIP(ctx, hipMemcpyAsync(B, nxt.B, 8 * nB, hipMemcpyDeviceToDevice, st));
+    } else {
+        NHP_TRY(nhp_download(ctx, S, nxt.S, 8 * P));
+        NHP_TRY(nhp_download(ctx, R, nxt.R, 8 * P));
+        NHP_TRY(nhp_download(ctx, Q, nxt.Q, 8 * 3 * NN));
+        NHP_TRY(nhp_download(ctx, B, nxt.B, 8 * nB));
+    }
+    NHP_HIP(ctx, hipStreamSynchronize(st));
+    stats[0] = h[0];
+    for (int j = 1; j <= 5; ++j) { stats[j] = from_model ? 0.0 : h[j]; stats[5 + j] = h[CSBMVB_OUT + j]; }
+    for (int j = 0; j < CSBMVB_NET_PIECES; ++j) {
+        stats[11 + j] = from_model ? 0.0 : h[8 + j];
+        stats[11 + CSBMVB_NET_PIECES + j] = h[CSBMVB_OUT + 8 + j];
+    }
+    return NHP_OK;
+}
+
+extern "C" nhp_status nhp_cont_sbmvb_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *m, int32_t flags,
+                                         const nhp_gibbs_priors *priors, const double *net, const double *sbm, int32_t n_blocks,
+                                         int32_t labels_every, int64_t step0, double f_abstol, int32_t max_steps, double *x, double *S, double *R,
+                                         int64_t len, double *Q, double *B, double *elbo, int32_t *steps_out, int32_t *converged_out, double *trace)
+{
+    if (!ctx || !ds || !m || !priors || !x || !S || !R || !Q || !B || !elbo || !steps_out || !converged_out) return NHP_EINVAL;
+    const bool resume = (flags & NHP_VB_RESUME) != 0;
+    NHP_TRY(cb_check(ctx, ds, m, flags, priors, net, sbm, n_blocks, labels_every, step0, B, true, "vb!"));
+    flags &= ~(int32_t)(NHP_VB_FROM_MODEL | NHP_VB_RESUME | NHP_VB_DENSE_NETWORK);
+    if (max_steps < (resume ? 0 : 1)) {
+        nhp_set_error(ctx, "vb!: max_steps = %d (a run from a guess needs at least one step to have a state)", max_steps);
+        return NHP_EDOMAIN;
+    }
+    const size_t P = nhp_layout(m).P, N = (size_t)m->N, NN = N * N, K = (size_t)n_blocks, nB = csbmvb_b_doubles(N, K);
+    NHP_TRY(nhp_layout_check(ctx, nhp_layout(m), len));
+    NHP_TRY(cb_check_state(ctx, m, resume, S, R, Q, "vb!"));
+    NHP_HIP(ctx, hipSetDevice(ctx->device));
+    NHP_TRY(nhp_check_deferred(ctx));
+    hipStream_t st = ctx->main();
+    nhp_em_host hs;
+    if (hipHostMalloc((void **)&hs.h, 8 * CSBMVB_OUT) != hipSuccess) { hs.h = nullptr; nhp_set_error(ctx, "out of pinned memory"); return NHP_ENOMEM; }
+    NHP_HIP(ctx, hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
+
+    // two states (surrogate, planes, Q, B, T, pieces): an update writes the other one only -- the sweep works on the copy of m --
+    // so nothing is lost when the rule says stop
+    NHP_TRY(nhp_ctx_reserve_mle(ctx, 8 * csbmvb_reserve_doubles(P, N, K, VB_BLK), "variational state"));
+    cb_state cur, nxt;
+    cb_scratch w;
+    double *d_out = nullptr;
+    cb_carve((double *)ctx->d_mle, P, N, K, cur, nxt, w, &d_out);
+    cn_args A = cn_make_args(ds, m, priors, net, true);
+    A.dense = 0;
+    const cb_args b = cb_make_args(m, sbm, n_blocks);
+    const dim3 grid(VB_BLK), block(256);
+
+    NHP_HIP(ctx, hipMemcpyAsync(cur.B, B, 8 * nB, hipMemcpyHostToDevice, st));
+    if (resume) {
+        NHP_HIP(ctx, hipMemcpyAsync(cur.Q, Q, 8 * 3 * NN, hipMemcpyHostToDevice, st));
+        NHP_HIP(ctx, hipMemcpyAsync(cur.S, S, 8 * P, hipMemcpyHostToDevice, st));
+        NHP_HIP(ctx, hipMemcpyAsync(cur.R, R, 8 * P, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_cnetvb_surrogate, grid, block, 0, st, A, (const double *)cur.S, (const double *)cur.R, cur.Q, cur.x, cur.part);
+        cb_own_sums(st, b, cur, w, false);
+    } else {
+        NHP_HIP(ctx, hipMemcpyAsync(nxt.x, x, 8 * P, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_cnetvb_start, grid, block, 0, st, A, (const double *)nxt.x, cur.x, cur.part);
+        NHP_HIP(ctx, hipMemsetAsync(cur.T, 0, 8 * csbmvb_t_doubles(K), st));     // (a guess has no state: Σ log λ̃ alone is used)
+    }
+    NHP_HIP(ctx, hipGetLastError());
+
+    const double nan = std::nan("");
+    double L = nan, L_prev = nan;
+    bool has_state = resume, converged = false;
+    nhp_cont_model view = cn_unmasked(m);
+    int k = 0;
+    for (;; ++k) {
+        // E-step at x̃_k and the ELBO of state k; the update is enqueued behind the scalars' copy, so it runs while the host looks
+        // at the stopping rule
+        double *d_grad = nullptr;
+        NHP_TRY(nhp_em_estep(ctx, ds, &view, flags, cur.x, (int64_t)P, &d_grad));
+        hipLaunchKernelGGL(k_csbmvb_elbo, dim3(1), block, 0, st, b, (const double *)ctx->d_results, (const double *)cur.part,
+                           (const double *)cur.B, (const double *)cur.T, d_out);
+        NHP_HIP(ctx, hipGetLastError());
+        NHP_HIP(ctx, hipMemcpyAsync(hs.h, d_out, 8 * CSBMVB_OUT, hipMemcpyDeviceToHost, st));
+        NHP_HIP(ctx, hipEventRecord(hs.ev, st));
+        if (k < max_steps) NHP_TRY(cb_update(ctx, st, A, b, cur, nxt, w, d_grad, (step0 + k + 1) % labels_every == 0));
+        NHP_HIP(ctx, hipEventSynchronize(hs.ev));
+        if (!std::isfinite(hs.h[0])) {
+            NHP_HIP(ctx, hipStreamSynchronize(st));
+            nhp_set_error(ctx, "vb!: the intensity of some event is not positive and finite (iteration %d)", k);
+            return NHP_EDOMAIN;
+        }
+        L_prev = L; L = has_state ? hs.h[6] : nan;
+        if (trace) trace[k] = L;
+        if (has_state && std::fabs(L - L_prev) < f_abstol) { converged = true; break; }     // (false while L_prev is NaN)
+        if (k == max_steps) break;
+        std::swap(cur, nxt);
+        has_state = true;
+    }
+    m->version = view.version;
+    nhp_model_view_keep_bound(m, view);
+    // the state, and its means and A = (ρv > ½) into x and the model's own block
+    hipLaunchKernelGGL(k_cnetvb_mean, grid, block, 0, st, A.v, (const double *)cur.S, (const double *)cur.R, (const double *)(cur.Q + 2 * NN),
+                       nxt.x, m->d_A);
+    NHP_HIP(ctx, hipGetLastError());
+    ++m->version;
+    NHP_HIP(ctx, hipMemcpyAsync(m->d_params, nxt.x, 8 * P, hipMemcpyDeviceToDevice, st));
+    NHP_TRY(nhp_download(ctx, x, nxt.x, 8 * P));
+    NHP_TRY(nhp_download(ctx, S, cur.S, 8 * P));
+    NHP_TRY(nhp_download(ctx, R, cur.R, 8 * P));
+    NHP_TRY(nhp_download(ctx, Q, cur.Q, 8 * 3 * NN));
+    NHP_TRY(nhp_download(ctx, B, cur.B, 8 * nB));
     NHP_HIP(ctx, hipStreamSynchronize(st));
     *elbo = L; *steps_out = k; *converged_out = converged ? 1 : 0;
     return NHP_OK;

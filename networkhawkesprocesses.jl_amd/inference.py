@@ -514,14 +514,20 @@ class ContinuousNetworkVariational(ContinuousVariational):
 
 def _netvb_check(process, data, what):
     """The argument errors of the network fit, raised before any device work; returns (priors, net [κ0, ν0, α, β], dense)."""
-    from .components import BernoulliNetworkModel, DenseNetworkModel, SparseWeightModel
+    from .components import BernoulliNetworkModel, DenseNetworkModel, SparseWeightModel, StochasticBlockNetworkModel
     from .sharded import ShardedDataset
     if not isinstance(process.weights, SparseWeightModel):
         raise TypeError(f"{what} on a ContinuousNetworkHawkesProcess needs a SparseWeightModel (spike and slab); with other weights "
                         f"it is defined for ContinuousStandardHawkesProcess")
-    if not isinstance(process.network, (BernoulliNetworkModel, DenseNetworkModel)):
+    block = isinstance(process.network, StochasticBlockNetworkModel)
+    if block:
+        if not process.network.has_variational_state():
+            raise NotImplementedError(f"{what}: the network (StochasticBlockNetworkModel) has no variational state: mean-field "
+                                      "over labels cannot leave the uniform state, so none is created implicitly -- call "
+                                      "network.variational_init_() first")
+    elif not isinstance(process.network, (BernoulliNetworkModel, DenseNetworkModel)):
         raise NotImplementedError(f"{what}: a {type(process.network).__name__} is not implemented for continuous processes "
-                                  f"(DenseNetworkModel and BernoulliNetworkModel are)")
+                                  f"(DenseNetworkModel, BernoulliNetworkModel and StochasticBlockNetworkModel are)")
     if not isinstance(process.baseline, HomogeneousProcess):
         raise NotImplementedError(f"{what}: the update of a LogGaussianCoxProcess baseline has no closed form")
     if isinstance(data, ShardedDataset):
@@ -535,14 +541,16 @@ def _netvb_check(process, data, what):
         pr = _lib.GibbsPriors(b.α0, b.β0, w.κ1, w.ν1, imp.α0, imp.β0, imp.μμ, imp.κμ)
     names = ["alpha0", "beta0", "kappa", "nu", "a", "b"] + ([] if isinstance(imp, ExponentialImpulseResponse) else ["kappa_mu"])
     values = [(n, float(getattr(pr, n))) for n in names] + [("kappa0", w.κ0), ("nu0", w.ν0)]
-    if not dense:
+    if block:
+        values += [("network alpha", net.α), ("network beta", net.β), ("network gamma", net.γ)]
+    elif not dense:
         values += [("network alpha", net.α), ("network beta", net.β), ("network alpha_v", net.αv), ("network beta_v", net.βv)]
     for name, v in values:
         if not (v > 0.0 and math.isfinite(v)):
             raise ValueError(f"{what}: the hyper-parameter {name} = {v} must be positive and finite")
     if not math.isfinite(float(pr.mu_mu)):
         raise ValueError(f"{what}: the prior mean mu_mu = {pr.mu_mu} must be finite")
-    netp = np.array([w.κ0, w.ν0, 1.0 if dense else net.α, 1.0 if dense else net.β], dtype=np.float64)
+    netp = np.array([w.κ0, w.ν0, 1.0 if dense or block else net.α, 1.0 if dense or block else net.β], dtype=np.float64)
     return pr, netp, dense
 
 
@@ -554,6 +562,8 @@ def _netvb_start_Q(process, dense):
     rho = net.link_probability() if w.ρv is None else np.asarray(w.ρv, dtype=np.float64)
     if rho.shape != (N, N) or not np.all((rho >= 0.0) & (rho <= 1.0)):
         raise ValueError("weights.ρv must be an N x N matrix of probabilities")
+    if _is_block(process):                                          # (the block state travels in B)
+        return np.concatenate([np.ones(2 * N * N), rho.ravel(order="F")])
     return np.concatenate([np.ones(2 * N * N), rho.ravel(order="F"), [1.0 if dense else net.αv, 1.0 if dense else net.βv]])
 
 
@@ -578,6 +588,8 @@ def vb_step_network_continuous(process, data, init=None, recursive=True, ctx=Non
     import ctypes as C
     from .continuous import _check_recursive
     pr, netp, dense = _netvb_check(process, data, "update!")
+    if _is_block(process):
+        return _vb_step_block_network_continuous(process, data, pr, netp, init, recursive, ctx)
     P = _device_length(process)
     flags = _check_recursive(process, recursive) | (NHP_VB_DENSE_NETWORK if dense else 0)
     if init is None:
@@ -610,7 +622,11 @@ def _netvb_write_back(process, x, res):
     w.κv0, w.νv0, w.κv1, w.νv1, w.ρv = res.kappa0.copy(), res.nu0.copy(), res.kappa.copy(), res.nu.copy(), res.rho.copy()
     w.κv, w.νv = w.κv1, w.νv1
     process.adjacency_matrix = (res.rho > 0.5).astype(np.float64)
-    if not res.dense:
+    if isinstance(res, ContinuousBlockNetworkVariational):
+        net.mv, net.αv, net.βv, net.γv = res.mv.copy(), res.alpha_v.copy(), res.beta_v.copy(), res.gamma_v.copy()
+        net.ρ, net.π, net.z = res.block_link_probability(), net.γv / net.γv.sum(), res.labels()
+        net.vb_step = res.vb_step
+    elif not res.dense:
         net.αv, net.βv = res.net_alpha, res.net_beta
         net.ρ = net.αv / (net.αv + net.βv)
 
@@ -628,6 +644,8 @@ def vb_network_continuous(process, data, max_steps=1000, f_abstol=1e-6, guess=No
     import ctypes as C
     from .continuous import _check_recursive
     pr, netp, dense = _netvb_check(process, data, "vb!")
+    if _is_block(process):
+        return _vb_block_network_continuous(process, data, pr, netp, max_steps, f_abstol, guess, recursive, init, keep_trace, verbose, ctx)
     P = _device_length(process)
     flags = _check_recursive(process, recursive) | (NHP_VB_DENSE_NETWORK if dense else 0)
     max_steps = int(max_steps)
@@ -664,6 +682,149 @@ def vb_network_continuous(process, data, max_steps=1000, f_abstol=1e-6, guess=No
     res = ContinuousNetworkVariational(_vb_kind_of(process), process.ndims(), S, R, Q, pr.kappa, dense, elbo=elbo.value,
                                        trace=trace[first:steps.value + 1].copy() if keep_trace else None, steps=steps.value,
                                        status="success" if conv.value else "failure", elapsed=time.time() - start)
+    _netvb_write_back(process, x, res)
+    return res
+
+
+# ---- ... under a stochastic block network (csrc/cont_netvb.hip) ---------------------------------------------
+
+def _is_block(process):
+    from .components import StochasticBlockNetworkModel
+    return isinstance(process.network, StochasticBlockNetworkModel)
+
+
+class ContinuousBlockNetworkVariational(ContinuousNetworkVariational):
+    """The mean-field posterior of a continuous network process under a StochasticBlockNetworkModel (definition:
+    include/nhp.h, nhp_cont_sbmvb_run).  ContinuousNetworkVariational's factors -- Q holds the three planes [κv0; νv0; ρv] -- and
+    the block model's: `mv` (N×K, q(z_n) = Categorical(mv[n, :])), `alpha_v`, `beta_v` (K×K, q(ρ[k,l]) = Beta) and `gamma_v`
+    (K, q(π) = Dirichlet), kept in `B` = [vec αv; vec βv; γv; vec mv] (StochasticBlockNetworkModel.variational_params()).
+    `vb_step` is the number of steps taken since network.variational_init_() -- the label sweep runs at the steps whose
+    number is a multiple of `labels_every` -- and travels with `init=res`.  `pieces`, where a single step returned them:
+    ContinuousNetworkVariational's, and "network_before" / "network_after" = (Σ entropy of ρv, links, labels, KL_Dir, ΣKL_Beta)
+    with KL_net = entropy - (links + labels - KL_Dir - ΣKL_Beta).  There is no single Beta: net_alpha, net_beta are None."""
+
+    def __init__(self, kind, N, S, R, Q, B, nblocks, prior_kappa=0.0, vb_step=0, labels_every=1, **kw):
+        ContinuousVariational.__init__(self, kind, N, S, R, prior_kappa, **kw)
+        N, K = self.N, int(nblocks)
+        self.Q, self.B = np.array(Q, dtype=np.float64), np.array(B, dtype=np.float64)
+        if self.Q.shape != (3 * N * N,):
+            raise ValueError("Q must hold 3·N² numbers: [κv0; νv0; ρv]")
+        if K < 1 or self.B.shape != (2 * K * K + K + N * K,):
+            raise ValueError("B must hold 2·K² + K + N·K numbers: [vec αv; vec βv; γv; vec mv]")
+        self.nblocks, self.vb_step, self.labels_every, self.dense = K, int(vb_step), int(labels_every), False
+
+    net_alpha = property(lambda self: None)
+    net_beta = property(lambda self: None)
+    alpha_v = property(lambda self: self.B[:self.nblocks ** 2].reshape((self.nblocks, self.nblocks), order="F"))
+    beta_v = property(lambda self: self.B[self.nblocks ** 2:2 * self.nblocks ** 2].reshape((self.nblocks, self.nblocks), order="F"))
+    gamma_v = property(lambda self: self.B[2 * self.nblocks ** 2:2 * self.nblocks ** 2 + self.nblocks])
+    mv = property(lambda self: self.B[2 * self.nblocks ** 2 + self.nblocks:].reshape((self.N, self.nblocks), order="F"))
+
+    def labels(self):
+        """argmax_k mv[n, k], the lowest index on ties (0-based, as StochasticBlockNetworkModel.z)."""
+        return np.argmax(self.mv, axis=1).astype(np.int32)
+
+    def block_link_probability(self):
+        """E_q ρ[k, l] = αv / (αv + βv)."""
+        return self.alpha_v / (self.alpha_v + self.beta_v)
+
+
+def _sbmvb_inputs(process, init, P, what):
+    """(S, R, Q, B, step0) of a call: the state of `init`, or without one the network's own block state and step count."""
+    net, N = process.network, process.ndims()
+    K = net.nblocks
+    if net.nnodes != N:
+        raise ValueError(f"{what}: the network has {net.nnodes} nodes, the process {N}")
+    if init is not None:
+        if not isinstance(init, ContinuousBlockNetworkVariational):
+            raise TypeError("init must be a ContinuousBlockNetworkVariational (the result of an earlier vb_ or update_ of this process)")
+        if init.kind != _vb_kind_of(process) or init.S.shape != (P,) or init.nblocks != K:
+            raise ValueError("Parameter vector length does not match model parameter length.")
+        return init.S.copy(), init.R.copy(), init.Q.copy(), init.B.copy(), init.vb_step
+    shapes = ((net.mv, (N, K), "mv"), (net.αv, (K, K), "αv"), (net.βv, (K, K), "βv"), (net.γv, (K,), "γv"))
+    for v, shape, name in shapes:
+        if np.shape(v) != shape:
+            raise ValueError(f"{what}: network.{name} must have shape {shape}")
+    B = np.ascontiguousarray(net.variational_params(), dtype=np.float64)
+    return np.empty(P), np.empty(P), _netvb_start_Q(process, False), B, int(net.vb_step)
+
+
+def _sbmvb_priors(process):
+    net = process.network
+    return np.array([net.α, net.β, net.γ], dtype=np.float64)
+
+
+def _vb_step_block_network_continuous(process, data, pr, netp, init, recursive, ctx):
+    """update_ under a block network (nhp_cont_sbmvb_step): the step numbered init.vb_step + 1, or network.vb_step + 1 without a
+    state.  Returns a ContinuousBlockNetworkVariational; the process and its network are not changed."""
+    import ctypes as C
+    from .continuous import _check_recursive
+    P = _device_length(process)
+    flags = _check_recursive(process, recursive) | (NHP_VB_FROM_MODEL if init is None else 0)
+    S, R, Q, B, step0 = _sbmvb_inputs(process, init, P, "update!")
+    net, sbm = process.network, _sbmvb_priors(process)
+    ctx = ctx or _lib.default_context()
+    ds = device_dataset(process, data, ctx)
+    start = time.time()
+    model = process.device_model(ctx)
+    stats = np.empty(21)
+    _lib.check(_lib.lib().nhp_cont_sbmvb_step(ctx.h, ds.h, model.h, flags, C.byref(pr), _lib.dptr(netp), _lib.dptr(sbm), net.nblocks,
+                                              int(net.labels_every), step0, S.ctypes.data, R.ctypes.data, P, Q.ctypes.data, B.ctypes.data, 0,
+                                              _lib.dptr(stats)), ctx.h)
+    elbo = float("nan") if init is None else float(stats[0] - stats[1] - stats[2] - stats[3] - stats[4] - stats[5])
+    res = ContinuousBlockNetworkVariational(_vb_kind_of(process), process.ndims(), S, R, Q, B, net.nblocks, pr.kappa, step0 + 1,
+                                            net.labels_every, elbo=elbo, steps=1, elapsed=time.time() - start)
+    res.pieces = {"loglam": float(stats[0]), "before": tuple(stats[1:6]), "after": tuple(stats[6:11]),
+                  "network_before": tuple(stats[11:16]), "network_after": tuple(stats[16:21])}
+    return res
+
+
+def _vb_block_network_continuous(process, data, pr, netp, max_steps, f_abstol, guess, recursive, init, keep_trace, verbose, ctx):
+    """vb_ under a block network (nhp_cont_sbmvb_run).  Arguments and stopping rule are vb_network_continuous's.  The block
+    state starts from the network's (variational_init_) or from `init`; the sweep over the labels runs at the steps whose
+    number since variational_init_ is a multiple of network.labels_every.  The process is overwritten as for a Bernoulli
+    network; in addition network.mv, αv, βv, γv hold the state, network.ρ = αv/(αv + βv), network.π = γv/Σγv, network.z =
+    labels() and network.vb_step advances by the steps taken."""
+    import ctypes as C
+    from .continuous import _check_recursive
+    P = _device_length(process)
+    flags = _check_recursive(process, recursive)
+    max_steps = int(max_steps)
+    if init is not None and guess is not None:
+        raise ValueError("vb!: give a guess or a state to resume (init), not both")
+    S, R, Q, B, step0 = _sbmvb_inputs(process, init, P, "vb!")
+    if init is not None:
+        x = np.empty(P)
+        flags |= NHP_VB_RESUME
+    else:
+        if guess is None:
+            x = np.concatenate([process.baseline.params(), process.impulses.params(), process.weights.params()]).astype(np.float64)
+        else:
+            x = np.array(guess, dtype=np.float64)
+        if x.shape != (P,):
+            raise ValueError("Parameter vector length does not match model parameter length.")
+    if max_steps < (0 if init is not None else 1):
+        raise ValueError("vb!: max_steps must be at least 1 (0 with init)")
+    net, sbm = process.network, _sbmvb_priors(process)
+    ctx = ctx or _lib.default_context()
+    ds = device_dataset(process, data, ctx)
+    start = time.time()
+    model = process.device_model(ctx)
+    elbo, steps, conv = C.c_double(), C.c_int32(), C.c_int32()
+    trace = np.full(max_steps + 1, np.nan)
+    _lib.check(_lib.lib().nhp_cont_sbmvb_run(ctx.h, ds.h, model.h, flags, C.byref(pr), _lib.dptr(netp), _lib.dptr(sbm), net.nblocks,
+                                             int(net.labels_every), step0, float(f_abstol), max_steps, _lib.dptr(x), _lib.dptr(S),
+                                             _lib.dptr(R), P, _lib.dptr(Q), _lib.dptr(B), C.byref(elbo), C.byref(steps), C.byref(conv),
+                                             _lib.dptr(trace)), ctx.h)
+    first = 0 if init is not None else 1
+    if verbose:
+        for k in range(first, steps.value + 1):
+            print(f" > step: {k}, elbo: {trace[k]}")
+        print(f" > steps: {steps.value}, elbo: {elbo.value}, elapsed: {time.time() - start}")
+    res = ContinuousBlockNetworkVariational(_vb_kind_of(process), process.ndims(), S, R, Q, B, net.nblocks, pr.kappa, step0 + steps.value,
+                                            net.labels_every, elbo=elbo.value,
+                                            trace=trace[first:steps.value + 1].copy() if keep_trace else None, steps=steps.value,
+                                            status="success" if conv.value else "failure", elapsed=time.time() - start)
     _netvb_write_back(process, x, res)
     return res
 

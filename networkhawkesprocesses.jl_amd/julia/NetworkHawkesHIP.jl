@@ -724,6 +724,85 @@ function update!(p::NHP.ContinuousNetworkHawkesProcess, data; state=nothing, rec
     (S=S, R=R, Q=Q, stats=stats)
 end
 
+# ... under a STOCHASTIC BLOCK network (nhp_cont_sbmvb_run / nhp_cont_sbmvb_step; the definition is in include/nhp.h).  The
+# reference package has no block model type, so the caller passes the priors sbm = (α, β, γ), the number of blocks and the
+# block state B = [vec αv; vec βv; γv; vec m] (2K² + K + N·K, column-major; m[n, :] on the simplex and not uniform: the uniform
+# state is a fixed point of the label update).  Q holds the three planes [κv0; νv0; ρv] (3N²).  The label sweep runs at the
+# steps whose number step0 + 1, step0 + 2, ... is a multiple of labels_every.  block_vb! returns (S, R, Q, B, rho, m, elbo,
+# trace, steps, status, elapsed) and overwrites the process as vb! does (p.network is not touched); block_update! is one step
+# and returns (S, R, Q, B, stats) with the 21 numbers of nhp_cont_sbmvb_step; the process is not changed.
+function sbmvb_setup(p::NHP.ContinuousNetworkHawkesProcess, what, sbm, n_blocks, B)
+    p.weights isa NHP.SparseWeightModel || throw(ArgumentError("$what on a ContinuousNetworkHawkesProcess needs a SparseWeightModel"))
+    p.baseline isa NHP.HomogeneousProcess || error("$what: the update of a LogGaussianCoxProcess baseline has no closed form")
+    w, imp, b = p.weights, p.impulses, p.baseline
+    pri = imp isa NHP.ExponentialImpulseResponse ? Priors(b.α0, b.β0, w.κ1, w.ν1, imp.α, imp.β, 0.0, 1.0) :
+                                                   Priors(b.α0, b.β0, w.κ1, w.ν1, imp.α0, imp.β0, imp.μμ, imp.κμ)
+    N = NHP.ndims(p)
+    P = N + N * N * (imp isa NHP.ExponentialImpulseResponse ? 2 : 3)
+    K = Int(n_blocks)
+    1 <= K <= 64 || error("$what: n_blocks must lie in 1..64")
+    length(B) == 2 * K * K + K + N * K || error("$what: B must hold 2K² + K + N·K numbers")
+    length(sbm) == 3 || error("$what: sbm = (α, β, γ)")
+    pri, Float64[w.κ0, w.ν0], Float64[sbm...], N, P, K
+end
+
+function block_vb!(p::NHP.ContinuousNetworkHawkesProcess, data, sbm, n_blocks, B; labels_every=1, step0=0, max_steps=1000, f_abstol=1e-6,
+                   guess=nothing, recursive=true, state=nothing, verbose=false, ctx=context(),
+                   ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    pri0, net, sb, N, P, K = sbmvb_setup(p, "vb!", sbm, n_blocks, B)
+    x = Vector{Float64}(guess === nothing ? vcat(NHP.params(p.baseline), NHP.params(p.impulses), NHP.params(p.weights)) : guess)
+    length(x) == P || error("Parameter vector length does not match model parameter length.")
+    NN = N * N
+    S, R, Q = state === nothing ? (Vector{Float64}(undef, P), Vector{Float64}(undef, P), vcat(ones(2 * NN), fill(0.5, NN))) :
+                                  (Vector{Float64}(state[1]), Vector{Float64}(state[2]), Vector{Float64}(state[3]))
+    (length(S) == P && length(R) == P && length(Q) == 3 * NN) || error("Parameter vector length does not match model parameter length.")
+    Bv = Vector{Float64}(B)
+    flags = llflags(p, recursive) | (state === nothing ? Int32(0) : VB_RESUME)
+    elbo, steps, conv = Ref{Float64}(0.0), Ref{Int32}(0), Ref{Int32}(0)
+    trace = fill(NaN, max_steps + 1)
+    pri = Ref(pri0)
+    t0 = time()
+    with_model(ctx, p) do m
+        GC.@preserve pri check(ccall((:nhp_cont_sbmvb_run, libnhp), Int32,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Priors}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Int64, Float64, Int32,
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ref{Int32}, Ref{Int32}, Ptr{Float64}),
+            ctx.h, ds.h, m, flags, Base.unsafe_convert(Ptr{Priors}, pri), net, sb, Int32(K), Int32(labels_every), Int64(step0), f_abstol,
+            Int32(max_steps), x, S, R, P, Q, Bv, elbo, steps, conv, trace), ctx.h)
+    end
+    verbose && println(" > steps: $(steps[]), elbo: $(elbo[])")
+    nimp = P - N - NN
+    NHP.params!(p.baseline, x[1:N]); NHP.params!(p.impulses, x[N+1:N+nimp]); NHP.params!(p.weights, x[N+nimp+1:end])
+    tab(v, j) = reshape(v[(j-1)*NN+1:j*NN], N, N)
+    rho = tab(Q, 3)
+    w = p.weights
+    w.κv0, w.νv0, w.κv1, w.νv1 = tab(Q, 1), tab(Q, 2), reshape(S[P-NN+1:P], N, N), reshape(R[P-NN+1:P], N, N)
+    p.adjacency_matrix .= rho .> 0.5
+    first = state === nothing ? 2 : 1
+    (S=S, R=R, Q=Q, B=Bv, rho=rho, m=reshape(Bv[2*K*K+K+1:end], N, K), elbo=elbo[], trace=trace[first:steps[]+1], steps=Int(steps[]),
+     status=conv[] == 1 ? "success" : "failure", elapsed=time() - t0)
+end
+
+function block_update!(p::NHP.ContinuousNetworkHawkesProcess, data, sbm, n_blocks, B; labels_every=1, step0=0, state=nothing, recursive=true,
+                       ctx=context(), ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    pri0, net, sb, N, P, K = sbmvb_setup(p, "update!", sbm, n_blocks, B)
+    NN = N * N
+    S, R, Q = state === nothing ? (Vector{Float64}(undef, P), Vector{Float64}(undef, P), vcat(ones(2 * NN), fill(0.5, NN))) :
+                                  (Vector{Float64}(state[1]), Vector{Float64}(state[2]), Vector{Float64}(state[3]))
+    (length(S) == P && length(R) == P && length(Q) == 3 * NN) || error("Parameter vector length does not match model parameter length.")
+    Bv = Vector{Float64}(B)
+    flags = llflags(p, recursive) | (state === nothing ? VB_FROM_MODEL : Int32(0))
+    stats = Vector{Float64}(undef, 21)
+    pri = Ref(pri0)
+    with_model(ctx, p) do m
+        GC.@preserve pri check(ccall((:nhp_cont_sbmvb_step, libnhp), Int32,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Priors}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Int64, Ptr{Float64}, Ptr{Float64},
+             Int64, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}),
+            ctx.h, ds.h, m, flags, Base.unsafe_convert(Ptr{Priors}, pri), net, sb, Int32(K), Int32(labels_every), Int64(step0), S, R, P, Q, Bv,
+            Int32(0), stats), ctx.h)
+    end
+    (S=S, R=R, Q=Q, B=Bv, stats=stats)
+end
+
 # --- observed_information(process, data) and hessian_vector_product(process, data, v): no reference counterpart ---------------
 # The objective separates by child node, so minus its Hessian is block diagonal: blocks[:, :, k] is the D x D block of column
 # columns[k] (1-based here) over [λ0[c]; θ[:,c] | μ[:,c]; τ[:,c]; W[:,c]], D = 1 + kinds·N (nhp_cont_information; homogeneous

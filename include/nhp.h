@@ -1306,7 +1306,8 @@ nhp_status nhp_cont_em_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_mo
  * device pointers by output_on_device); with NHP_VB_FROM_MODEL they are output only and the E-step runs at the model's
  * current parameters.  stats [9] (host): [0] Σ_i log λ̃_i at the surrogate stepped from; [1..4] E_q[compensator], KL_λ0, KL_W,
  * KL_imp of the state stepped from (0 with NHP_VB_FROM_MODEL), so that L of that state is stats[0] - stats[1] - ... - stats[4];
- * [5..8] the same four pieces of the updated state.  Synchronous; the model is not changed.
+ * [5..8] the same four pieces of the updated state.  Synchronous; the model is not changed.  A step that returns
+ * NHP_EDOMAIN leaves host S, R as they were passed in (device planes are updated in place and hold the update's output).
  *
  * nhp_cont_vb_run: the whole iteration on the device.  Iteration 0 runs the E-step at x (the guess, used as if it were a
  * surrogate; it has no ELBO) or, with NHP_VB_RESUME, at the surrogate of the state in S, R; iteration k >= 1 at the

@@ -13,15 +13,13 @@
 // order, forms the state's (αv, βv) = (α + Σρv, β + Σ(1-ρv)), finishes KL_net and L, and leaves ψ(αv) - ψ(βv) behind the pair
 // for the next update.  No atomics.  lnΓ: the pass has lnΓ(κv0), lnΓ(κv1) from nhp_digamma_lgamma for KL_W, so below 16 the
 // logit's lnΓ difference is their difference (no library lgamma, no scratch) and from 16 on the Stirling form.
-#include <algorithm>
-#include <cmath>
-
-#include "nhp_cnetvb.h"
+//
+// The block network's fit (further down) is the same pass with the link's own network term: both update kernels are one body,
+// cn_update_body<NET>.  The host side is nhp_vb_drive.h's step and run drivers, shared with cont_vb.hip; cn_fit and cb_fit tell
+// them what a state of either network fit is, how it is carved and which kernels run.
 #include "nhp_csbmvb.h"
-#include "nhp_internal.h"
-#include "nhp_math.h"
 #include "nhp_sbmvb_dev.h"
-#include "nhp_vb.h"
+#include "nhp_vb_drive.h"
 
 namespace {
 
@@ -35,18 +33,9 @@ struct cn_args {
 
 struct cn_acc : vb_acc { double ent = 0.0, sr = 0.0, s1r = 0.0; };
 
-// a state on the device: surrogate, planes, Q = [κv0; νv0; ρv; αv, βv, ψ(αv) - ψ(βv)], partial sums
-struct cn_state { double *x, *S, *R, *Q, *part; };
-
 __device__ __forceinline__ void cn_store(const cn_acc &s, double *__restrict__ part)
 {
-    __shared__ double red[4];
-    const double v[CNETVB_PIECES] = {s.fix, s.comp, s.kl0, s.klw, s.kli, s.ent, s.sr, s.s1r};
-#pragma unroll
-    for (int j = 0; j < CNETVB_PIECES; ++j) {
-        const double t = nhp_block_sum_n<4>(v[j], red);
-        if (threadIdx.x == 0) part[j * VB_BLK + blockIdx.x] = t;
-    }
+    vb_store<CNETVB_PIECES>({s.fix, s.comp, s.kl0, s.klw, s.kli, s.ent, s.sr, s.s1r}, part);
 }
 
 // lnΓ(κv1) - lnΓ(κv0) with both values at hand: their difference below 16, inside Stirling's formula from there on
@@ -124,21 +113,10 @@ __device__ __forceinline__ void cn_link(const cn_args &A, double cp, double kv0,
     }
 }
 
-// iteration 0: an ordinary parameter vector used as if it were a surrogate; only the part of its ll to undo has a meaning
+// iteration 0: an ordinary parameter vector used as if it were a surrogate
 __global__ __launch_bounds__(256) void k_cnetvb_start(cn_args A, const double *__restrict__ xin, double *__restrict__ x, double *__restrict__ part)
 {
-    const vb_args &a = A.v;
-    const size_t N = (size_t)a.N, NN = N * N;
-    const nhp_layout L = vb_layout(a);
-    cn_acc s;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < N + NN; i += (size_t)gridDim.x * 256) {
-        if (i < N) { const double v = xin[i]; x[i] = v; s.fix += a.T * v; continue; }
-        const size_t k = i - N;
-        const double w = xin[L.W + k];
-        vb_write(a, L, x, k, w, xin[L.p1 + k], a.impulse != NHP_IMPULSE_EXPONENTIAL ? xin[L.p2 + k] : 0.0);
-        s.fix += (a.cnt ? a.cnt[k % N] : 0.0) * w;
-    }
-    cn_store(s, part);
+    vb_start_body<CNETVB_PIECES>(A.v, xin, x, part);
 }
 
 // the surrogate and the pieces of a given state (S, R, Q): the start of nhp_cont_netvb_step and of a resumed run
@@ -165,55 +143,72 @@ __global__ __launch_bounds__(256) void k_cnetvb_surrogate(cn_args A, const doubl
     cn_store(s, part);
 }
 
-// the coordinate-ascent update: factors (S, R, Q) from the surrogate x, the gradient g at it and the network scalars `old`
-// = [αv, βv, ψ(αv) - ψ(βv)] of the state stepped from; their surrogate xn, their pieces
-__global__ __launch_bounds__(256) void k_cnetvb_update(cn_args A, const double *__restrict__ x, const double *__restrict__ g,
-                                                       const double *__restrict__ old, double *__restrict__ S, double *__restrict__ R,
-                                                       double *__restrict__ Q, double *__restrict__ xn, double *__restrict__ part)
+// Where a link's network term of the logit comes from.  A dense or Bernoulli network: the scalar ψ(αv) - ψ(βv) of the state
+// stepped from, old = [αv, βv, ψ(αv) - ψ(βv)] (a dense network: no kernel writes the slot, no link reads it, and the pair passes
+// through into the new Q).  A block network: the link's own net[p,c] = Σ_kl ω D (sbmvb_net) from blk = (m, m·D, D)
+// of the state stepped from; link k = p + c·N, p fastest: (m·D)[p,l] is coalesced per l, m[c,l] one address for (almost) the
+// whole wave; the term is a running sum.  This source has no dense branch.
+struct cn_scalar_net {
+    double net;
+    __device__ __forceinline__ cn_scalar_net(const cn_args &A, const double *__restrict__ old, double *__restrict__ Q, size_t NN)
+        : net(A.dense ? 0.0 : old[2])
+    {
+        if (A.dense && blockIdx.x == 0 && threadIdx.x < 2) Q[3 * NN + threadIdx.x] = old[threadIdx.x];
+    }
+    __device__ __forceinline__ double rho(const cn_args &A, size_t, size_t, size_t, double kv0, double nv0, double kv1, const cn_tab &t) const
+    {
+        return A.dense ? 1.0 : cn_rho(A, net, kv0, nv0, kv1, t);
+    }
+};
+struct cn_block_net {
+    sbmvb_link blk;
+    __device__ __forceinline__ double rho(const cn_args &A, size_t N, size_t p, size_t c, double kv0, double nv0, double kv1, const cn_tab &t) const
+    {
+        return cn_rho(A, sbmvb_net(blk, N, p, c), kv0, nv0, kv1, t);
+    }
+};
+
+// the coordinate-ascent update of both network fits: factors (S, R, Q) from the surrogate x, the gradient g at it and the
+// network term of `net`; their surrogate xn, their pieces
+template <class NET>
+__device__ __forceinline__ void cn_update_body(const cn_args &A, const double *__restrict__ x, const double *__restrict__ g, const NET &net,
+                                               double *__restrict__ S, double *__restrict__ R, double *__restrict__ Q,
+                                               double *__restrict__ xn, double *__restrict__ part)
 {
     const vb_args &a = A.v;
     const size_t N = (size_t)a.N, NN = N * N;
     const nhp_layout L = vb_layout(a);
-    const nhp_gibbs_priors &q = a.pr;
-    const double net = A.dense ? 0.0 : old[2];                       // (a dense network: no kernel writes the slot, no link reads it)
-    if (A.dense && blockIdx.x == 0 && threadIdx.x < 2) Q[3 * NN + threadIdx.x] = old[threadIdx.x];     // (a dense network's pass through)
     cn_acc s;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < N + NN; i += (size_t)gridDim.x * 256) {
-        if (i < N) {
-            const double al = q.alpha0 + x[i] * (g[i] + a.T), be = q.beta0 + a.T;
-            S[i] = al; R[i] = be;
-            xn[i] = vb_baseline(a, al, be, s);
-            continue;
-        }
-        const size_t k = i - N;
-        const double cp = a.cnt ? a.cnt[k % N] : 0.0;
-        const double EM = x[L.W + k] * (g[L.W + k] + cp);
-        const double kv1 = q.kappa + EM, nv1 = q.nu + cp, kv0 = A.k0 + EM, nv0 = A.n0 + cp;
-        double m = 0.0, kk = 1.0, sa, sb;
-        if (a.impulse == NHP_IMPULSE_EXPONENTIAL) {
-            sa = q.a + EM;
-            sb = q.b + (EM / x[L.p1 + k] - g[L.p1 + k]);
-            S[L.p1 + k] = sa; R[L.p1 + k] = sb;
-        } else {
-            const double c = x[L.p1 + k], tau = x[L.p2 + k];
-            const double D1 = g[L.p1 + k] / tau, S2 = EM / tau - 2.0 * g[L.p2 + k], d0 = q.mu_mu - c;
-            kk = q.kappa_mu + EM;
-            const double dm = (D1 + q.kappa_mu * d0) / kk;
-            m = c + dm;
-            sa = q.a + 0.5 * EM;
-            sb = q.b + 0.5 * ((S2 + q.kappa_mu * (d0 * d0)) - kk * (dm * dm));
-            S[L.p1 + k] = m; R[L.p1 + k] = kk;
-            S[L.p2 + k] = sa; R[L.p2 + k] = sb;
-        }
+        if (i < N) { vb_update_baseline(a, x, g, i, S, R, xn, s); continue; }
+        const size_t k = i - N, p = k % N, c = k / N;                // (c: the block network's alone)
+        const double cp = a.cnt ? a.cnt[p] : 0.0;
+        const double EM = vb_link_em(L, x, g, k, cp);
+        const double kv1 = a.pr.kappa + EM, nv1 = a.pr.nu + cp, kv0 = A.k0 + EM, nv0 = A.n0 + cp;
+        double m, kk, sa, sb;
+        vb_update_impulse(a, L, x, g, k, EM, S, R, m, kk, sa, sb);
         S[L.W + k] = kv1; R[L.W + k] = nv1;
         const cn_tab t = cn_tables(kv0, nv0, kv1, nv1);
-        const double rho = A.dense ? 1.0 : cn_rho(A, net, kv0, nv0, kv1, t);
+        const double rho = net.rho(A, N, p, c, kv0, nv0, kv1, t);
         double w, p1, p2;
         cn_link(A, cp, kv0, nv0, kv1, nv1, t, rho, m, kk, sa, sb, s, w, p1, p2);
         Q[k] = kv0; Q[NN + k] = nv0; Q[2 * NN + k] = rho;
         vb_write(a, L, xn, k, w, p1, p2);
     }
     cn_store(s, part);
+}
+
+__global__ __launch_bounds__(256) void k_cnetvb_update(cn_args A, const double *__restrict__ x, const double *__restrict__ g,
+                                                       const double *__restrict__ old, double *__restrict__ S, double *__restrict__ R,
+                                                       double *__restrict__ Q, double *__restrict__ xn, double *__restrict__ part)
+{
+    cn_update_body(A, x, g, cn_scalar_net(A, old, Q, (size_t)A.v.N * (size_t)A.v.N), S, R, Q, xn, part);
+}
+__global__ __launch_bounds__(256) void k_csbmvb_update(cn_args A, const double *__restrict__ x, const double *__restrict__ g, sbmvb_link blk,
+                                                       double *__restrict__ S, double *__restrict__ R, double *__restrict__ Q,
+                                                       double *__restrict__ xn, double *__restrict__ part)
+{
+    cn_update_body(A, x, g, cn_block_net{blk}, S, R, Q, xn, part);
 }
 
 // out = [Σ_i log λ̃_i = ll + fix, E_q[compensator], KL_λ0, KL_W, KL_imp, KL_net, L, 0]: the partial sums in one fixed order.
@@ -224,12 +219,7 @@ __global__ __launch_bounds__(256) void k_cnetvb_elbo(cn_args A, int form_new, co
 {
     __shared__ double red[4];
     __shared__ double tot[CNETVB_PIECES];
-    for (int j = 0; j < CNETVB_PIECES; ++j) {
-        double v = 0.0;
-        for (int b = threadIdx.x; b < VB_BLK; b += 256) v += part[j * VB_BLK + b];
-        v = nhp_block_sum_n<4>(v, red);
-        if (threadIdx.x == 0) tot[j] = v;
-    }
+    vb_sum_parts<CNETVB_PIECES>(part, tot, red);
     if (threadIdx.x == 0) {
         const double sl = *ll + tot[0];
         double klnet = 0.0;
@@ -290,12 +280,7 @@ nhp_status cn_check(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_mod
         nhp_set_error(ctx, "%s: not available on a column shard", what);
         return NHP_ENOTIMPL;
     }
-    const bool ln = m->impulse_kind != NHP_IMPULSE_EXPONENTIAL;
-    if (!vb_positive(pr->alpha0) || !vb_positive(pr->beta0) || !vb_positive(pr->kappa) || !vb_positive(pr->nu) || !vb_positive(pr->a) ||
-        !vb_positive(pr->b) || (ln && (!vb_positive(pr->kappa_mu) || !std::isfinite(pr->mu_mu)))) {
-        nhp_set_error(ctx, "%s: every prior hyper-parameter but the mean μμ must be positive and finite", what);
-        return NHP_EINVAL;
-    }
+    NHP_TRY(vb_check_priors(ctx, m, pr, what));
     char msg[200];
     if (cnetvb_check_net(what, net, dense || block, msg, sizeof msg) != CNETVB_OK) { nhp_set_error(ctx, "%s", msg); return NHP_EINVAL; }
     return NHP_OK;
@@ -326,24 +311,53 @@ cn_args cn_make_args(const nhp_cont_dataset *ds, const nhp_cont_model *m, const 
     return A;
 }
 
-void cn_carve(double *base, size_t P, size_t N, cn_state &cur, cn_state &nxt, double **d_out)
-{
-    const size_t stride = cnetvb_state_doubles(P, N, VB_BLK);
-    cn_state *st[2] = {&cur, &nxt};
-    for (int j = 0; j < 2; ++j) {
-        double *p = base + j * stride;
-        st[j]->x = p; st[j]->S = p + P; st[j]->R = p + 2 * P; st[j]->Q = p + 3 * P; st[j]->part = p + 3 * P + cnetvb_q_doubles(N);
-    }
-    *d_out = base + 2 * stride;
-}
+// the dense / Bernoulli fit for the drivers of nhp_vb_drive.h: S, R, Q the caller's arrays
+struct cn_fit {
+    static constexpr int OUT = CNETVB_OUT, L_SLOT = 6, STAT_PIECES = 5, PLANES = 3;
+    static constexpr bool UNMASK = true;
+    // a state on the device: surrogate, planes, Q = [κv0; νv0; ρv; αv, βv, ψ(αv) - ψ(βv)], partial sums
+    struct state { double *x, *S, *R, *Q, *part; };
+    nhp_ctx *ctx;
+    cn_args A;
+    size_t P, N;
+    double *S, *R, *Q;
 
-// the model as the E-step sees it: no adjacency matrix (the network acts through the prior of W alone)
-nhp_cont_model cn_unmasked(const nhp_cont_model *m)
-{
-    nhp_cont_model v = *m;
-    v.has_A = 0; v.d_A = nullptr;
-    return v;
-}
+    size_t reserve_doubles() const { return cnetvb_reserve_doubles(P, N, VB_BLK); }
+    void carve(vb_bump &b, state &s) const
+    {
+        s.x = b.take(P); s.S = b.take(P); s.R = b.take(P); s.Q = b.take(cnetvb_q_doubles(N)); s.part = b.take((size_t)CNETVB_PIECES * VB_BLK);
+    }
+    void carve_shared(vb_bump &) const {}
+    void place_step(state &, state &, bool) const {}
+    // (Q: a guess's or the model's αv, βv are read without a state too; the third scalar behind them is the device's own)
+    void planes(const state &s, vb_plane *pl) const { pl[0] = {S, s.S, P, false}; pl[1] = {R, s.R, P, false}; pl[2] = {Q, s.Q, 3 * N * N + 2, true}; }
+    void start(hipStream_t st, const double *xin, const state &s) const
+    {
+        hipLaunchKernelGGL(k_cnetvb_start, dim3(VB_BLK), dim3(256), 0, st, A, xin, s.x, s.part);
+    }
+    void surrogate(hipStream_t st, const state &s) const
+    {
+        hipLaunchKernelGGL(k_cnetvb_surrogate, dim3(VB_BLK), dim3(256), 0, st, A, (const double *)s.S, (const double *)s.R, s.Q, s.x, s.part);
+    }
+    // (the ELBO kernel also completes the state's network scalars, read by the update)
+    void elbo(hipStream_t st, const state &s, bool made_here, double *out) const
+    {
+        hipLaunchKernelGGL(k_cnetvb_elbo, dim3(1), dim3(256), 0, st, A, made_here ? 1 : 0, (const double *)ctx->d_results, (const double *)s.part,
+                           s.Q + 3 * N * N, out);
+    }
+    nhp_status update(nhp_ctx *, hipStream_t st, const state &cur, const state &nxt, const double *g, int) const
+    {
+        hipLaunchKernelGGL(k_cnetvb_update, dim3(VB_BLK), dim3(256), 0, st, A, (const double *)cur.x, g, (const double *)(cur.Q + 3 * N * N), nxt.S,
+                           nxt.R, nxt.Q, nxt.x, nxt.part);
+        return NHP_OK;
+    }
+    void mean(hipStream_t st, const state &s, double *x, nhp_cont_model *m) const
+    {
+        hipLaunchKernelGGL(k_cnetvb_mean, dim3(VB_BLK), dim3(256), 0, st, A.v, (const double *)s.S, (const double *)s.R,
+                           (const double *)(s.Q + 2 * N * N), x, m->d_A);
+    }
+    void stats(const double *h, bool from_model, double *out) const { vb_fill_stats(h, OUT, STAT_PIECES, from_model, out); }
+};
 
 // ---- the block network (the definition is in include/nhp.h, nhp_cont_sbmvb_run) --------------------------------
 // The Bernoulli fit with A[p,c] ~ Bernoulli(ρ[z_p, z_c]): the scalar ψ(αv) - ψ(βv) of the logit becomes the link's own
@@ -356,60 +370,10 @@ struct cb_args {
     double beta_const, dir_const;    // lnΓ(α+β) - lnΓα - lnΓβ and lnΓ(Kγ) - K lnΓγ
 };
 
-// a state on the device: cn_state's (Q = the three planes alone), B = [αv; βv; γv; m] and T = [T1; T0; Σ_n m] at its own m
+// a state on the device: cn_fit::state's (Q = the three planes alone), B = [αv; βv; γv; m] and T = [T1; T0; Σ_n m] at its own m
 struct cb_state { double *x, *S, *R, *Q, *B, *T, *part; };
 // what both states share: D, the four tables, Eπ, m·D, U1, U0
 struct cb_scratch { double *D, *tabs, *Epi, *mD, *U1, *U0; };
-
-// k_cnetvb_update with the link's own network term in place of the scalar: factors (S, R, Q) from the surrogate x, the
-// gradient g at it and blk = (m, m·D, D) of the state stepped from; their surrogate xn, their pieces.  Link k = p + c·N, p
-// fastest: (m·D)[p,l] is coalesced per l, m[c,l] one address for (almost) the whole wave; the term is a running sum.
-__global__ __launch_bounds__(256) void k_csbmvb_update(cn_args A, const double *__restrict__ x, const double *__restrict__ g, sbmvb_link blk,
-                                                       double *__restrict__ S, double *__restrict__ R, double *__restrict__ Q,
-                                                       double *__restrict__ xn, double *__restrict__ part)
-{
-    const vb_args &a = A.v;
-    const size_t N = (size_t)a.N, NN = N * N;
-    const nhp_layout L = vb_layout(a);
-    const nhp_gibbs_priors &q = a.pr;
-    cn_acc s;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < N + NN; i += (size_t)gridDim.x * 256) {
-        if (i < N) {
-            const double al = q.alpha0 + x[i] * (g[i] + a.T), be = q.beta0 + a.T;
-            S[i] = al; R[i] = be;
-            xn[i] = vb_baseline(a, al, be, s);
-            continue;
-        }
-        const size_t k = i - N, p = k % N, c = k / N;
-        const double cp = a.cnt ? a.cnt[p] : 0.0;
-        const double EM = x[L.W + k] * (g[L.W + k] + cp);
-        const double kv1 = q.kappa + EM, nv1 = q.nu + cp, kv0 = A.k0 + EM, nv0 = A.n0 + cp;
-        double m = 0.0, kk = 1.0, sa, sb;
-        if (a.impulse == NHP_IMPULSE_EXPONENTIAL) {
-            sa = q.a + EM;
-            sb = q.b + (EM / x[L.p1 + k] - g[L.p1 + k]);
-            S[L.p1 + k] = sa; R[L.p1 + k] = sb;
-        } else {
-            const double cc = x[L.p1 + k], tau = x[L.p2 + k];
-            const double D1 = g[L.p1 + k] / tau, S2 = EM / tau - 2.0 * g[L.p2 + k], d0 = q.mu_mu - cc;
-            kk = q.kappa_mu + EM;
-            const double dm = (D1 + q.kappa_mu * d0) / kk;
-            m = cc + dm;
-            sa = q.a + 0.5 * EM;
-            sb = q.b + 0.5 * ((S2 + q.kappa_mu * (d0 * d0)) - kk * (dm * dm));
-            S[L.p1 + k] = m; R[L.p1 + k] = kk;
-            S[L.p2 + k] = sa; R[L.p2 + k] = sb;
-        }
-        S[L.W + k] = kv1; R[L.W + k] = nv1;
-        const cn_tab t = cn_tables(kv0, nv0, kv1, nv1);
-        const double rho = cn_rho(A, sbmvb_net(blk, N, p, c), kv0, nv0, kv1, t);
-        double w, p1, p2;
-        cn_link(A, cp, kv0, nv0, kv1, nv1, t, rho, m, kk, sa, sb, s, w, p1, p2);
-        Q[k] = kv0; Q[NN + k] = nv0; Q[2 * NN + k] = rho;
-        vb_write(a, L, xn, k, w, p1, p2);
-    }
-    cn_store(s, part);
-}
 
 // out = k_cnetvb_elbo's eight, then [Σ entropy of ρv, links, labels, KL_Dir, Σ KL_Beta]: the partial sums in one fixed order and
 // the network pieces of the state (B, T) -- T1, T0 taken at the state's OWN m --
@@ -421,12 +385,7 @@ __global__ __launch_bounds__(256) void k_csbmvb_elbo(cb_args b, const double *__
     __shared__ double red[4];
     __shared__ double tot[CNETVB_PIECES];
     __shared__ double epi[SBMVB_MAX_BLOCKS];
-    for (int j = 0; j < CNETVB_PIECES; ++j) {
-        double v = 0.0;
-        for (int i = threadIdx.x; i < VB_BLK; i += 256) v += part[j * VB_BLK + i];
-        v = nhp_block_sum_n<4>(v, red);
-        if (threadIdx.x == 0) tot[j] = v;
-    }
+    vb_sum_parts<CNETVB_PIECES>(part, tot, red);
     const int K = b.K, KK = K * K;
     const size_t N = (size_t)b.N;
     const double *av = B, *bv = B + KK, *gv = B + 2 * KK, *m = B + 2 * KK + K;
@@ -472,30 +431,6 @@ __global__ __launch_bounds__(256) void k_csbmvb_elbo(cb_args b, const double *__
         out[7] = 0.0;
         out[8] = tot[5]; out[9] = links; out[10] = lab; out[11] = kldir; out[12] = klb;
     }
-}
-
-void cb_carve(double *base, size_t P, size_t N, size_t K, cb_state &cur, cb_state &nxt, cb_scratch &w, double **d_out)
-{
-    const size_t stride = csbmvb_state_doubles(P, N, K, VB_BLK), NN = N * N, KK = K * K, NK = N * K;
-    cb_state *st[2] = {&cur, &nxt};
-    for (int j = 0; j < 2; ++j) {
-        double *p = base + j * stride;
-        st[j]->x = p; p += P;
-        st[j]->S = p; p += P;
-        st[j]->R = p; p += P;
-        st[j]->Q = p; p += 3 * NN;
-        st[j]->B = p; p += csbmvb_b_doubles(N, K);
-        st[j]->T = p; p += csbmvb_t_doubles(K);
-        st[j]->part = p;
-    }
-    double *p = base + 2 * stride;
-    w.D = p; p += KK;
-    w.tabs = p; p += 4 * KK;
-    w.Epi = p; p += K;
-    w.mD = p; p += NK;
-    w.U1 = p; p += NK;
-    w.U0 = p; p += NK;
-    *d_out = p;
 }
 
 // the checks of both block entry points before any launch: cn_check's, then the block model's own
@@ -579,6 +514,86 @@ nhp_status cb_update(nhp_ctx *ctx, hipStream_t st, const cn_args &A, const cb_ar
     return NHP_OK;
 }
 
+// the block fit for the drivers of nhp_vb_drive.h: S, R, Q, B the caller's arrays; update number k of a call is step
+// step0 + k + 1 of the label sweep's schedule
+struct cb_fit {
+    static constexpr int OUT = CSBMVB_OUT, L_SLOT = 6, STAT_PIECES = 5, PLANES = 4;
+    static constexpr bool UNMASK = true;
+    using state = cb_state;
+    nhp_ctx *ctx;
+    cn_args A;
+    cb_args b;
+    size_t P, N, K;
+    int32_t labels_every;
+    int64_t step0;
+    double *S, *R, *Q, *B;
+    cb_scratch w;
+
+    size_t reserve_doubles() const { return csbmvb_reserve_doubles(P, N, K, VB_BLK); }
+    void carve(vb_bump &m, state &s) const
+    {
+        s.x = m.take(P); s.S = m.take(P); s.R = m.take(P); s.Q = m.take(3 * N * N);
+        s.B = m.take(csbmvb_b_doubles(N, K)); s.T = m.take(csbmvb_t_doubles(K)); s.part = m.take((size_t)CNETVB_PIECES * VB_BLK);
+    }
+    void carve_shared(vb_bump &m)
+    {
+        w.D = m.take(K * K); w.tabs = m.take(4 * K * K); w.Epi = m.take(K); w.mD = m.take(N * K); w.U1 = m.take(N * K); w.U0 = m.take(N * K);
+    }
+    void place_step(state &, state &, bool) const {}
+    void planes(const state &s, vb_plane *pl) const
+    {
+        pl[0] = {S, s.S, P, false}; pl[1] = {R, s.R, P, false}; pl[2] = {Q, s.Q, 3 * N * N, false}; pl[3] = {B, s.B, csbmvb_b_doubles(N, K), true};
+    }
+    void start(hipStream_t st, const double *xin, const state &s) const
+    {
+        hipLaunchKernelGGL(k_cnetvb_start, dim3(VB_BLK), dim3(256), 0, st, A, xin, s.x, s.part);
+        (void)hipMemsetAsync(s.T, 0, 8 * csbmvb_t_doubles(K), st);    // (no state: of its evaluation Σ log λ̃ alone is used; errors: the driver's)
+    }
+    void surrogate(hipStream_t st, const state &s) const
+    {
+        hipLaunchKernelGGL(k_cnetvb_surrogate, dim3(VB_BLK), dim3(256), 0, st, A, (const double *)s.S, (const double *)s.R, s.Q, s.x, s.part);
+        cb_own_sums(st, b, s, w, false);
+    }
+    void elbo(hipStream_t st, const state &s, bool, double *out) const
+    {
+        hipLaunchKernelGGL(k_csbmvb_elbo, dim3(1), dim3(256), 0, st, b, (const double *)ctx->d_results, (const double *)s.part, (const double *)s.B,
+                           (const double *)s.T, out);
+    }
+    nhp_status update(nhp_ctx *c, hipStream_t st, const state &cur, const state &nxt, const double *g, int k) const
+    {
+        return cb_update(c, st, A, b, cur, nxt, w, g, (step0 + k + 1) % labels_every == 0);
+    }
+    void mean(hipStream_t st, const state &s, double *x, nhp_cont_model *m) const
+    {
+        hipLaunchKernelGGL(k_cnetvb_mean, dim3(VB_BLK), dim3(256), 0, st, A.v, (const double *)s.S, (const double *)s.R,
+                           (const double *)(s.Q + 2 * N * N), x, m->d_A);
+    }
+    void stats(const double *h, bool from_model, double *out) const
+    {
+        vb_fill_stats(h, OUT, STAT_PIECES, from_model, out);
+        for (int j = 0; j < CSBMVB_NET_PIECES; ++j) {
+            out[11 + j] = from_model ? 0.0 : h[8 + j];
+            out[11 + CSBMVB_NET_PIECES + j] = h[OUT + 8 + j];
+        }
+    }
+};
+
+cn_fit cn_make_fit(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const nhp_gibbs_priors *pr, const double *net, bool dense,
+                   double *S, double *R, double *Q)
+{
+    return cn_fit{ctx, cn_make_args(ds, m, pr, net, dense), nhp_layout(m).P, (size_t)m->N, S, R, Q};
+}
+
+cb_fit cb_make_fit(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const nhp_gibbs_priors *pr, const double *net,
+                   const double *sbm, int32_t K, int32_t labels_every, int64_t step0, double *S, double *R, double *Q, double *B)
+{
+    cn_args A = cn_make_args(ds, m, pr, net, true);                  // (net = [κ0, ν0] alone: the Beta's slots stay 0 and unread)
+    A.dense = 0;
+    return cb_fit{ctx, A, cb_make_args(m, sbm, K), nhp_layout(m).P, (size_t)m->N, (size_t)K, labels_every, step0, S, R, Q, B, cb_scratch{}};
+}
+
+constexpr int32_t CN_MODE_FLAGS = NHP_VB_FROM_MODEL | NHP_VB_RESUME | NHP_VB_DENSE_NETWORK;     // not the E-step's
+
 }   // namespace
 
 extern "C" nhp_status nhp_cont_netvb_step(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int32_t flags,
@@ -588,59 +603,10 @@ extern "C" nhp_status nhp_cont_netvb_step(nhp_ctx *ctx, const nhp_cont_dataset *
     if (!ctx || !ds || !m || !priors || !net || !S || !R || !Q || !stats) return NHP_EINVAL;
     const bool dense = (flags & NHP_VB_DENSE_NETWORK) != 0, from_model = (flags & NHP_VB_FROM_MODEL) != 0;
     NHP_TRY(cn_check(ctx, ds, m, priors, net, dense, "update!"));
-    const size_t P = nhp_layout(m).P, N = (size_t)m->N, NN = N * N;
     NHP_TRY(nhp_layout_check(ctx, nhp_layout(m), len));
     if (!output_on_device) NHP_TRY(cn_check_state(ctx, m, dense, !from_model, S, R, Q, "update!"));
-    NHP_HIP(ctx, hipSetDevice(ctx->device));
-    NHP_TRY(nhp_check_deferred(ctx));
-    hipStream_t st = ctx->main();
-    flags &= ~(int32_t)(NHP_VB_FROM_MODEL | NHP_VB_RESUME | NHP_VB_DENSE_NETWORK);
-
-    NHP_TRY(nhp_ctx_reserve_mle(ctx, 8 * cnetvb_reserve_doubles(P, N, VB_BLK), "variational state"));
-    cn_state cur, nxt;
-    double *d_out = nullptr;
-    cn_carve((double *)ctx->d_mle, P, N, cur, nxt, &d_out);
-    const cn_args A = cn_make_args(ds, m, priors, net, dense);
-    const dim3 grid(VB_BLK), block(256);
-    const hipMemcpyKind in = output_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    NHP_HIP(ctx, hipMemcpyAsync(cur.Q, Q, 8 * (3 * NN + 2), in, st));
-    if (from_model) {
-        hipLaunchKernelGGL(k_cnetvb_start, grid, block, 0, st, A, (const double *)m->d_params, cur.x, cur.part);
-    } else {
-        NHP_HIP(ctx, hipMemcpyAsync(cur.S, S, 8 * P, in, st));
-        NHP_HIP(ctx, hipMemcpyAsync(cur.R, R, 8 * P, in, st));
-        hipLaunchKernelGGL(k_cnetvb_surrogate, grid, block, 0, st, A, (const double *)cur.S, (const double *)cur.R, cur.Q, cur.x, cur.part);
-    }
-    NHP_HIP(ctx, hipGetLastError());
-    double *d_grad = nullptr;
-    nhp_cont_model mm = cn_unmasked(m);                               // (the E-step bumps the version of what it evaluates)
-    NHP_TRY(nhp_em_estep(ctx, ds, &mm, flags, cur.x, (int64_t)P, &d_grad));
-    hipLaunchKernelGGL(k_cnetvb_elbo, dim3(1), block, 0, st, A, 0, (const double *)ctx->d_results, (const double *)cur.part, cur.Q + 3 * NN, d_out);
-    hipLaunchKernelGGL(k_cnetvb_update, grid, block, 0, st, A, (const double *)cur.x, (const double *)d_grad, (const double *)(cur.Q + 3 * NN),
-                       nxt.S, nxt.R, nxt.Q, nxt.x, nxt.part);
-    hipLaunchKernelGGL(k_cnetvb_elbo, dim3(1), block, 0, st, A, 1, (const double *)ctx->d_results, (const double *)nxt.part, nxt.Q + 3 * NN,
-                       d_out + CNETVB_OUT);
-    NHP_HIP(ctx, hipGetLastError());
-    double h[2 * CNETVB_OUT];
-    NHP_TRY(nhp_download(ctx, h, d_out, sizeof h));
-    if (!std::isfinite(h[0])) {
-        NHP_HIP(ctx, hipStreamSynchronize(st));
-        nhp_set_error(ctx, "update!: the intensity of some event is not positive and finite");
-        return NHP_EDOMAIN;
-    }
-    if (output_on_device) {
-        NHP_HIP(ctx, hipMemcpyAsync(S, nxt.S, 8 * P, hipMemcpyDeviceToDevice, st));
-        NHP_HIP(ctx, hipMemcpyAsync(R, nxt.R, 8 * P, hipMemcpyDeviceToDevice, st));
-        NHP_HIP(ctx, hipMemcpyAsync(Q, nxt.Q, 8 * (3 * NN + 2), hipMemcpyDeviceToDevice, st));
-    } else {
-        NHP_TRY(nhp_download(ctx, S, nxt.S, 8 * P));
-        NHP_TRY(nhp_download(ctx, R, nxt.R, 8 * P));
-        NHP_TRY(nhp_download(ctx, Q, nxt.Q, 8 * (3 * NN + 2)));
-    }
-    NHP_HIP(ctx, hipStreamSynchronize(st));
-    stats[0] = h[0];
-    for (int j = 1; j <= 5; ++j) { stats[j] = from_model ? 0.0 : h[j]; stats[5 + j] = h[CNETVB_OUT + j]; }
-    return NHP_OK;
+    cn_fit f = cn_make_fit(ctx, ds, m, priors, net, dense, S, R, Q);
+    return vb_step_drive(ctx, ds, m, flags & ~CN_MODE_FLAGS, f, from_model, output_on_device != 0, stats);
 }
 
 extern "C" nhp_status nhp_cont_netvb_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *m, int32_t flags,
@@ -651,88 +617,10 @@ extern "C" nhp_status nhp_cont_netvb_run(nhp_ctx *ctx, const nhp_cont_dataset *d
     if (!ctx || !ds || !m || !priors || !net || !x || !S || !R || !Q || !elbo || !steps_out || !converged_out) return NHP_EINVAL;
     const bool dense = (flags & NHP_VB_DENSE_NETWORK) != 0, resume = (flags & NHP_VB_RESUME) != 0;
     NHP_TRY(cn_check(ctx, ds, m, priors, net, dense, "vb!"));
-    flags &= ~(int32_t)(NHP_VB_FROM_MODEL | NHP_VB_RESUME | NHP_VB_DENSE_NETWORK);
-    if (max_steps < (resume ? 0 : 1)) {
-        nhp_set_error(ctx, "vb!: max_steps = %d (a run from a guess needs at least one step to have a state)", max_steps);
-        return NHP_EDOMAIN;
-    }
-    const size_t P = nhp_layout(m).P, N = (size_t)m->N, NN = N * N;
-    NHP_TRY(nhp_layout_check(ctx, nhp_layout(m), len));
+    NHP_TRY(vb_run_args(ctx, m, resume, max_steps, len));
     NHP_TRY(cn_check_state(ctx, m, dense, resume, S, R, Q, "vb!"));
-    NHP_HIP(ctx, hipSetDevice(ctx->device));
-    NHP_TRY(nhp_check_deferred(ctx));
-    hipStream_t st = ctx->main();
-    nhp_em_host hs;
-    if (hipHostMalloc((void **)&hs.h, 8 * CNETVB_OUT) != hipSuccess) { hs.h = nullptr; nhp_set_error(ctx, "out of pinned memory"); return NHP_ENOMEM; }
-    NHP_HIP(ctx, hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
-
-    // two states (surrogate, planes, Q, pieces): an update writes the other one only, so nothing is lost when the rule says stop
-    NHP_TRY(nhp_ctx_reserve_mle(ctx, 8 * cnetvb_reserve_doubles(P, N, VB_BLK), "variational state"));
-    cn_state cur, nxt;
-    double *d_out = nullptr;
-    cn_carve((double *)ctx->d_mle, P, N, cur, nxt, &d_out);
-    const cn_args A = cn_make_args(ds, m, priors, net, dense);
-    const dim3 grid(VB_BLK), block(256);
-
-    NHP_HIP(ctx, hipMemcpyAsync(cur.Q, Q, 8 * (3 * NN + 2), hipMemcpyHostToDevice, st));     // (a guess: its αv, βv alone are read)
-    if (resume) {
-        NHP_HIP(ctx, hipMemcpyAsync(cur.S, S, 8 * P, hipMemcpyHostToDevice, st));
-        NHP_HIP(ctx, hipMemcpyAsync(cur.R, R, 8 * P, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_cnetvb_surrogate, grid, block, 0, st, A, (const double *)cur.S, (const double *)cur.R, cur.Q, cur.x, cur.part);
-    } else {
-        NHP_HIP(ctx, hipMemcpyAsync(nxt.x, x, 8 * P, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_cnetvb_start, grid, block, 0, st, A, (const double *)nxt.x, cur.x, cur.part);
-    }
-    NHP_HIP(ctx, hipGetLastError());
-
-    const double nan = std::nan("");
-    double L = nan, L_prev = nan;
-    bool has_state = resume, converged = false, made_here = false;    // made_here: `cur` came out of k_cnetvb_update
-    nhp_cont_model view = cn_unmasked(m);
-    int k = 0;
-    for (;; ++k) {
-        // E-step at x̃_k and the ELBO of state k (which also completes the state's network scalars, read by the update); the
-        // update is enqueued behind the scalars' copy, so it runs while the host looks at the stopping rule
-        double *d_grad = nullptr;
-        NHP_TRY(nhp_em_estep(ctx, ds, &view, flags, cur.x, (int64_t)P, &d_grad));
-        hipLaunchKernelGGL(k_cnetvb_elbo, dim3(1), block, 0, st, A, made_here ? 1 : 0, (const double *)ctx->d_results, (const double *)cur.part,
-                           cur.Q + 3 * NN, d_out);
-        NHP_HIP(ctx, hipGetLastError());
-        NHP_HIP(ctx, hipMemcpyAsync(hs.h, d_out, 8 * CNETVB_OUT, hipMemcpyDeviceToHost, st));
-        NHP_HIP(ctx, hipEventRecord(hs.ev, st));
-        if (k < max_steps) {
-            hipLaunchKernelGGL(k_cnetvb_update, grid, block, 0, st, A, (const double *)cur.x, (const double *)d_grad,
-                               (const double *)(cur.Q + 3 * NN), nxt.S, nxt.R, nxt.Q, nxt.x, nxt.part);
-            NHP_HIP(ctx, hipGetLastError());
-        }
-        NHP_HIP(ctx, hipEventSynchronize(hs.ev));
-        if (!std::isfinite(hs.h[0])) {
-            NHP_HIP(ctx, hipStreamSynchronize(st));
-            nhp_set_error(ctx, "vb!: the intensity of some event is not positive and finite (iteration %d)", k);
-            return NHP_EDOMAIN;
-        }
-        L_prev = L; L = has_state ? hs.h[6] : nan;
-        if (trace) trace[k] = L;
-        if (has_state && std::fabs(L - L_prev) < f_abstol) { converged = true; break; }     // (false while L_prev is NaN)
-        if (k == max_steps) break;
-        std::swap(cur, nxt);
-        has_state = true; made_here = true;
-    }
-    m->version = view.version;
-    nhp_model_view_keep_bound(m, view);
-    // the state, and its means and A = (ρv > ½) into x and the model's own block
-    hipLaunchKernelGGL(k_cnetvb_mean, grid, block, 0, st, A.v, (const double *)cur.S, (const double *)cur.R, (const double *)(cur.Q + 2 * NN),
-                       nxt.x, m->d_A);
-    NHP_HIP(ctx, hipGetLastError());
-    ++m->version;
-    NHP_HIP(ctx, hipMemcpyAsync(m->d_params, nxt.x, 8 * P, hipMemcpyDeviceToDevice, st));
-    NHP_TRY(nhp_download(ctx, x, nxt.x, 8 * P));
-    NHP_TRY(nhp_download(ctx, S, cur.S, 8 * P));
-    NHP_TRY(nhp_download(ctx, R, cur.R, 8 * P));
-    NHP_TRY(nhp_download(ctx, Q, cur.Q, 8 * (3 * NN + 2)));
-    NHP_HIP(ctx, hipStreamSynchronize(st));
-    *elbo = L; *steps_out = k; *converged_out = converged ? 1 : 0;
-    return NHP_OK;
+    cn_fit f = cn_make_fit(ctx, ds, m, priors, net, dense, S, R, Q);
+    return vb_run_drive(ctx, ds, m, flags & ~CN_MODE_FLAGS, f, resume, f_abstol, max_steps, x, elbo, steps_out, converged_out, trace);
 }
 
 extern "C" nhp_status nhp_cont_sbmvb_step(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int32_t flags,
@@ -743,71 +631,10 @@ extern "C" nhp_status nhp_cont_sbmvb_step(nhp_ctx *ctx, const nhp_cont_dataset *
     if (!ctx || !ds || !m || !priors || !S || !R || !Q || !B || !stats) return NHP_EINVAL;
     const bool from_model = (flags & NHP_VB_FROM_MODEL) != 0;
     NHP_TRY(cb_check(ctx, ds, m, flags, priors, net, sbm, n_blocks, labels_every, step0, B, !output_on_device, "update!"));
-    const size_t P = nhp_layout(m).P, N = (size_t)m->N, NN = N * N, K = (size_t)n_blocks, nB = csbmvb_b_doubles(N, K);
     NHP_TRY(nhp_layout_check(ctx, nhp_layout(m), len));
     if (!output_on_device) NHP_TRY(cb_check_state(ctx, m, !from_model, S, R, Q, "update!"));
-    NHP_HIP(ctx, hipSetDevice(ctx->device));
-    NHP_TRY(nhp_check_deferred(ctx));
-    hipStream_t st = ctx->main();
-    flags &= ~(int32_t)(NHP_VB_FROM_MODEL | NHP_VB_RESUME | NHP_VB_DENSE_NETWORK);
-
-    NHP_TRY(nhp_ctx_reserve_mle(ctx, 8 * csbmvb_reserve_doubles(P, N, K, VB_BLK), "variational state"));
-    cb_state cur, nxt;
-    cb_scratch w;
-    double *d_out = nullptr;
-    cb_carve((double *)ctx->d_mle, P, N, K, cur, nxt, w, &d_out);
-    cn_args A = cn_make_args(ds, m, priors, net, true);              // (net = [κ0, ν0] alone: the Beta's slots stay 0 and unread)
-    A.dense = 0;
-    const cb_args b = cb_make_args(m, sbm, n_blocks);
-    const dim3 grid(VB_BLK), block(256);
-    const hipMemcpyKind in = output_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    NHP_HIP(ctx, hipMemcpyAsync(cur.B, B, 8 * nB, in, st));
-    if (from_model) {
-        hipLaunchKernelGGL(k_cnetvb_start, grid, block, 0, st, A, (const double *)m->d_params, cur.x, cur.part);
-        NHP_HIP(ctx, hipMemsetAsync(cur.T, 0, 8 * csbmvb_t_doubles(K), st));     // (no state: of its evaluation Σ log λ̃ alone is used)
-    } else {
-        NHP_HIP(ctx, hipMemcpyAsync(cur.Q, Q, 8 * 3 * NN, in, st));
-        NHP_HIP(ctx, hipMemcpyAsync(cur.S, S, 8 * P, in, st));
-        NHP_HIP(ctx, hipMemcpyAsync(cur.R, R, 8 * P, in, st));
-        hipLaunchKernelGGL(k_cnetvb_surrogate, grid, block, 0, st, A, (const double *)cur.S, (const double *)cur.R, cur.Q, cur.x, cur.part);
-        cb_own_sums(st, b, cur, w, false);
-    }
-    NHP_HIP(ctx, hipGetLastError());
-    double *d_grad = nullptr;
-    nhp_cont_model mm = cn_unmasked(m);                               // (the E-step bumps the version of what it evaluates)
-    NHP_TRY(nhp_em_estep(ctx, ds, &mm, flags, cur.x, (int64_t)P, &d_grad));
-    hipLaunchKernelGGL(k_csbmvb_elbo, dim3(1), block, 0, st, b, (const double *)ctx->d_results, (const double *)cur.part, (const double *)cur.B,
-                       (const double *)cur.T, d_out);
-    NHP_TRY(cb_update(ctx, st, A, b, cur, nxt, w, d_grad, (step0 + 1) % labels_every == 0));
-    hipLaunchKernelGGL(k_csbmvb_elbo, dim3(1), block, 0, st, b, (const double *)ctx->d_results, (const double *)nxt.part, (const double *)nxt.B,
-                       (const double *)nxt.T, d_out + CSBMVB_OUT);
-    NHP_HIP(ctx, hipGetLastError());
-    double h[2 * CSBMVB_OUT];
-    NHP_TRY(nhp_download(ctx, h, d_out, sizeof h));
-    if (!std::isfinite(h[0])) {
-        NHP_HIP(ctx, hipStreamSynchronize(st));
-        nhp_set_error(ctx, "update!: the intensity of some event is not positive and finite");
-        return NHP_EDOMAIN;
-    }
-    if (output_on_device) {
-        NHP_HIP(ctx, hipMemcpyAsync(S, nxt.S, 8 * P, hipMemcpyDeviceToDevice, st));
-        NHP_HIP(ctx, hipMemcpyAsync(R, nxt.R, 8 * P, hipMemcpyDeviceToDevice, st));
-        NHP_HIP(ctx, hipMemcpyAsync(Q, nxt.Q, 8 * 3 * NN, hipMemcpyDeviceToDevice, st));
-        NHP_HIP(ctx, hipMemcpyAsync(B, nxt.B, 8 * nB, hipMemcpyDeviceToDevice, st));
-    } else {
-        NHP_TRY(nhp_download(ctx, S, nxt.S, 8 * P));
-        NHP_TRY(nhp_download(ctx, R, nxt.R, 8 * P));
-        NHP_TRY(nhp_download(ctx, Q, nxt.Q, 8 * 3 * NN));
-        NHP_TRY(nhp_download(ctx, B, nxt.B, 8 * nB));
-    }
-    NHP_HIP(ctx, hipStreamSynchronize(st));
-    stats[0] = h[0];
-    for (int j = 1; j <= 5; ++j) { stats[j] = from_model ? 0.0 : h[j]; stats[5 + j] = h[CSBMVB_OUT + j]; }
-    for (int j = 0; j < CSBMVB_NET_PIECES; ++j) {
-        stats[11 + j] = from_model ? 0.0 : h[8 + j];
-        stats[11 + CSBMVB_NET_PIECES + j] = h[CSBMVB_OUT + 8 + j];
-    }
-    return NHP_OK;
+    cb_fit f = cb_make_fit(ctx, ds, m, priors, net, sbm, n_blocks, labels_every, step0, S, R, Q, B);
+    return vb_step_drive(ctx, ds, m, flags & ~CN_MODE_FLAGS, f, from_model, output_on_device != 0, stats);
 }
 
 extern "C" nhp_status nhp_cont_sbmvb_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *m, int32_t flags,
@@ -818,90 +645,9 @@ extern "C" nhp_status nhp_cont_sbmvb_run(nhp_ctx *ctx, const nhp_cont_dataset *d
     if (!ctx || !ds || !m || !priors || !x || !S || !R || !Q || !B || !elbo || !steps_out || !converged_out) return NHP_EINVAL;
     const bool resume = (flags & NHP_VB_RESUME) != 0;
     NHP_TRY(cb_check(ctx, ds, m, flags, priors, net, sbm, n_blocks, labels_every, step0, B, true, "vb!"));
-    flags &= ~(int32_t)(NHP_VB_FROM_MODEL | NHP_VB_RESUME | NHP_VB_DENSE_NETWORK);
-    if (max_steps < (resume ? 0 : 1)) {
-        nhp_set_error(ctx, "vb!: max_steps = %d (a run from a guess needs at least one step to have a state)", max_steps);
-        return NHP_EDOMAIN;
-    }
-    const size_t P = nhp_layout(m).P, N = (size_t)m->N, NN = N * N, K = (size_t)n_blocks, nB = csbmvb_b_doubles(N, K);
-    NHP_TRY(nhp_layout_check(ctx, nhp_layout(m), len));
+    NHP_TRY(vb_run_args(ctx, m, resume, max_steps, len));
     NHP_TRY(cb_check_state(ctx, m, resume, S, R, Q, "vb!"));
-    NHP_HIP(ctx, hipSetDevice(ctx->device));
-    NHP_TRY(nhp_check_deferred(ctx));
-    hipStream_t st = ctx->main();
-    nhp_em_host hs;
-    if (hipHostMalloc((void **)&hs.h, 8 * CSBMVB_OUT) != hipSuccess) { hs.h = nullptr; nhp_set_error(ctx, "out of pinned memory"); return NHP_ENOMEM; }
-    NHP_HIP(ctx, hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
-
-    // two states (surrogate, planes, Q, B, T, pieces): an update writes the other one only -- the sweep works on the copy of m --
-    // so nothing is lost when the rule says stop
-    NHP_TRY(nhp_ctx_reserve_mle(ctx, 8 * csbmvb_reserve_doubles(P, N, K, VB_BLK), "variational state"));
-    cb_state cur, nxt;
-    cb_scratch w;
-    double *d_out = nullptr;
-    cb_carve((double *)ctx->d_mle, P, N, K, cur, nxt, w, &d_out);
-    cn_args A = cn_make_args(ds, m, priors, net, true);
-    A.dense = 0;
-    const cb_args b = cb_make_args(m, sbm, n_blocks);
-    const dim3 grid(VB_BLK), block(256);
-
-    NHP_HIP(ctx, hipMemcpyAsync(cur.B, B, 8 * nB, hipMemcpyHostToDevice, st));
-    if (resume) {
-        NHP_HIP(ctx, hipMemcpyAsync(cur.Q, Q, 8 * 3 * NN, hipMemcpyHostToDevice, st));
-        NHP_HIP(ctx, hipMemcpyAsync(cur.S, S, 8 * P, hipMemcpyHostToDevice, st));
-        NHP_HIP(ctx, hipMemcpyAsync(cur.R, R, 8 * P, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_cnetvb_surrogate, grid, block, 0, st, A, (const double *)cur.S, (const double *)cur.R, cur.Q, cur.x, cur.part);
-        cb_own_sums(st, b, cur, w, false);
-    } else {
-        NHP_HIP(ctx, hipMemcpyAsync(nxt.x, x, 8 * P, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_cnetvb_start, grid, block, 0, st, A, (const double *)nxt.x, cur.x, cur.part);
-        NHP_HIP(ctx, hipMemsetAsync(cur.T, 0, 8 * csbmvb_t_doubles(K), st));     // (a guess has no state: Σ log λ̃ alone is used)
-    }
-    NHP_HIP(ctx, hipGetLastError());
-
-    const double nan = std::nan("");
-    double L = nan, L_prev = nan;
-    bool has_state = resume, converged = false;
-    nhp_cont_model view = cn_unmasked(m);
-    int k = 0;
-    for (;; ++k) {
-        // E-step at x̃_k and the ELBO of state k; the update is enqueued behind the scalars' copy, so it runs while the host looks
-        // at the stopping rule
-        double *d_grad = nullptr;
-        NHP_TRY(nhp_em_estep(ctx, ds, &view, flags, cur.x, (int64_t)P, &d_grad));
-        hipLaunchKernelGGL(k_csbmvb_elbo, dim3(1), block, 0, st, b, (const double *)ctx->d_results, (const double *)cur.part,
-                           (const double *)cur.B, (const double *)cur.T, d_out);
-        NHP_HIP(ctx, hipGetLastError());
-        NHP_HIP(ctx, hipMemcpyAsync(hs.h, d_out, 8 * CSBMVB_OUT, hipMemcpyDeviceToHost, st));
-        NHP_HIP(ctx, hipEventRecord(hs.ev, st));
-        if (k < max_steps) NHP_TRY(cb_update(ctx, st, A, b, cur, nxt, w, d_grad, (step0 + k + 1) % labels_every == 0));
-        NHP_HIP(ctx, hipEventSynchronize(hs.ev));
-        if (!std::isfinite(hs.h[0])) {
-            NHP_HIP(ctx, hipStreamSynchronize(st));
-            nhp_set_error(ctx, "vb!: the intensity of some event is not positive and finite (iteration %d)", k);
-            return NHP_EDOMAIN;
-        }
-        L_prev = L; L = has_state ? hs.h[6] : nan;
-        if (trace) trace[k] = L;
-        if (has_state && std::fabs(L - L_prev) < f_abstol) { converged = true; break; }     // (false while L_prev is NaN)
-        if (k == max_steps) break;
-        std::swap(cur, nxt);
-        has_state = true;
-    }
-    m->version = view.version;
-    nhp_model_view_keep_bound(m, view);
-    // the state, and its means and A = (ρv > ½) into x and the model's own block
-    hipLaunchKernelGGL(k_cnetvb_mean, grid, block, 0, st, A.v, (const double *)cur.S, (const double *)cur.R, (const double *)(cur.Q + 2 * NN),
-                       nxt.x, m->d_A);
-    NHP_HIP(ctx, hipGetLastError());
-    ++m->version;
-    NHP_HIP(ctx, hipMemcpyAsync(m->d_params, nxt.x, 8 * P, hipMemcpyDeviceToDevice, st));
-    NHP_TRY(nhp_download(ctx, x, nxt.x, 8 * P));
-    NHP_TRY(nhp_download(ctx, S, cur.S, 8 * P));
-    NHP_TRY(nhp_download(ctx, R, cur.R, 8 * P));
-    NHP_TRY(nhp_download(ctx, Q, cur.Q, 8 * 3 * NN));
-    NHP_TRY(nhp_download(ctx, B, cur.B, 8 * nB));
-    NHP_HIP(ctx, hipStreamSynchronize(st));
-    *elbo = L; *steps_out = k; *converged_out = converged ? 1 : 0;
-    return NHP_OK;
+    cb_fit f = cb_make_fit(ctx, ds, m, priors, net, sbm, n_blocks, labels_every, step0, S, R, Q, B);
+    return vb_run_drive(ctx, ds, m, flags & ~CN_MODE_FLAGS, f, resume, f_abstol, max_steps, x, elbo, steps_out, converged_out, trace);
 }
+

@@ -27,46 +27,26 @@
 // order, a wave adds with DPP, a workgroup its four waves in order, k_vb_elbo the VB_BLK partials with a fixed thread stride and
 // the same block sum.  The statistics' own order is the E-step's (cont_em.hip: fixed on the slices route and in the
 // recursion, LDS atomics on the two-pass windowed route).
-#include <algorithm>
-#include <cmath>
-
-#include "nhp_internal.h"
-#include "nhp_math.h"
-#include "nhp_vb.h"
+//
+// The host side is nhp_vb_drive.h's: vb_step_drive and vb_run_drive, which the network fits of cont_netvb.hip run through as
+// well.  This file supplies its kernels, its argument checks and vb_fit, the struct that tells the drivers what a state of
+// the standard fit is; the update kernel's conjugate lines, the start kernel's body and the sums are nhp_vb.h's.
+#include "nhp_vb_drive.h"
 
 namespace {
 
-constexpr int VB_PIECES = 5;         // fix = T Σ λ̃0 + Σ cnt_p W̃, then E_q[compensator], KL_λ0, KL_W, KL_imp
-constexpr int VB_OUT = 6;            // k_vb_elbo: Σ log λ̃, the four pieces, L
+// (the kernels' shared pieces -- vb_args, vb_acc, vb_baseline, vb_pair, vb_update_*, vb_start_body, vb_store, vb_sum_parts, VB_BLK --
+// are nhp_vb.h's, shared with cont_netvb.hip; VB_PIECES, VB_OUT and the state's sizing are nhp_cnetvb.h's, host-only)
 
-// (vb_args, vb_acc, vb_baseline, vb_pair, vb_kl_gamma, vb_write, VB_BLK: nhp_vb.h, shared with cont_netvb.hip)
-
-// part[piece·VB_BLK + blockIdx.x] = this workgroup's share of each piece
-__device__ __forceinline__ void vb_store(const vb_acc &s, double *__restrict__ part)
+__device__ __forceinline__ void vb_store_acc(const vb_acc &s, double *__restrict__ part)
 {
-    __shared__ double red[4];
-    const double v[VB_PIECES] = {s.fix, s.comp, s.kl0, s.klw, s.kli};
-#pragma unroll
-    for (int j = 0; j < VB_PIECES; ++j) {
-        const double t = nhp_block_sum_n<4>(v[j], red);
-        if (threadIdx.x == 0) part[j * VB_BLK + blockIdx.x] = t;
-    }
+    vb_store<VB_PIECES>({s.fix, s.comp, s.kl0, s.klw, s.kli}, part);
 }
 
-// iteration 0: an ordinary parameter vector used as if it were a surrogate; only the part of its ll to undo has a meaning
+// iteration 0: an ordinary parameter vector used as if it were a surrogate
 __global__ __launch_bounds__(256) void k_vb_start(vb_args a, const double *__restrict__ xin, double *__restrict__ x, double *__restrict__ part)
 {
-    const size_t N = (size_t)a.N, NN = N * N;
-    const nhp_layout L = vb_layout(a);
-    vb_acc s;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < N + NN; i += (size_t)gridDim.x * 256) {
-        if (i < N) { const double v = xin[i]; x[i] = v; s.fix += a.T * v; continue; }
-        const size_t k = i - N;
-        const double w = xin[L.W + k];
-        vb_write(a, L, x, k, w, xin[L.p1 + k], a.impulse != NHP_IMPULSE_EXPONENTIAL ? xin[L.p2 + k] : 0.0);
-        s.fix += (a.cnt ? a.cnt[k % N] : 0.0) * w;
-    }
-    vb_store(s, part);
+    vb_start_body<VB_PIECES>(a, xin, x, part);
 }
 
 // the surrogate and the pieces of a given state (S, R): the start of nhp_cont_vb_step and of a resumed run
@@ -85,7 +65,7 @@ __global__ __launch_bounds__(256) void k_vb_surrogate(vb_args a, const double *_
         vb_pair(a, a.cnt ? a.cnt[k % N] : 0.0, S[L.W + k], R[L.W + k], ln ? S[L.p1 + k] : 0.0, ln ? R[L.p1 + k] : 1.0, S[sh], R[sh], s, w, p1, p2);
         vb_write(a, L, x, k, w, p1, p2);
     }
-    vb_store(s, part);
+    vb_store_acc(s, part);
 }
 
 // the coordinate-ascent update: factors (S, R) from the surrogate x and the gradient g at it, their surrogate xn, their pieces
@@ -95,41 +75,21 @@ __global__ __launch_bounds__(256) void k_vb_update(vb_args a, const double *__re
 {
     const size_t N = (size_t)a.N, NN = N * N;
     const nhp_layout L = vb_layout(a);
-    const nhp_gibbs_priors &q = a.pr;
     vb_acc s;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < N + NN; i += (size_t)gridDim.x * 256) {
-        if (i < N) {
-            const double al = q.alpha0 + x[i] * (g[i] + a.T), be = q.beta0 + a.T;
-            S[i] = al; R[i] = be;
-            xn[i] = vb_baseline(a, al, be, s);
-            continue;
-        }
+        if (i < N) { vb_update_baseline(a, x, g, i, S, R, xn, s); continue; }
         const size_t k = i - N;
         const double cp = a.cnt ? a.cnt[k % N] : 0.0;
-        const double EM = x[L.W + k] * (g[L.W + k] + cp);
-        const double ka = q.kappa + EM, nu = q.nu + cp;
-        double m = 0.0, kk = 1.0, sa, sb;
-        if (a.impulse == NHP_IMPULSE_EXPONENTIAL) {
-            sa = q.a + EM;
-            sb = q.b + (EM / x[L.p1 + k] - g[L.p1 + k]);
-            S[L.p1 + k] = sa; R[L.p1 + k] = sb;
-        } else {
-            const double c = x[L.p1 + k], tau = x[L.p2 + k];
-            const double D1 = g[L.p1 + k] / tau, S2 = EM / tau - 2.0 * g[L.p2 + k], d0 = q.mu_mu - c;
-            kk = q.kappa_mu + EM;
-            const double dm = (D1 + q.kappa_mu * d0) / kk;
-            m = c + dm;
-            sa = q.a + 0.5 * EM;
-            sb = q.b + 0.5 * ((S2 + q.kappa_mu * (d0 * d0)) - kk * (dm * dm));
-            S[L.p1 + k] = m; R[L.p1 + k] = kk;
-            S[L.p2 + k] = sa; R[L.p2 + k] = sb;
-        }
+        const double EM = vb_link_em(L, x, g, k, cp);
+        const double ka = a.pr.kappa + EM, nu = a.pr.nu + cp;
+        double m, kk, sa, sb;
+        vb_update_impulse(a, L, x, g, k, EM, S, R, m, kk, sa, sb);
         S[L.W + k] = ka; R[L.W + k] = nu;
         double w, p1, p2;
         vb_pair(a, cp, ka, nu, m, kk, sa, sb, s, w, p1, p2);
         vb_write(a, L, xn, k, w, p1, p2);
     }
-    vb_store(s, part);
+    vb_store_acc(s, part);
 }
 
 // out = [Σ_i log λ̃_i = ll + fix, E_q[compensator], KL_λ0, KL_W, KL_imp, L]: the partial sums in one fixed order
@@ -137,12 +97,7 @@ __global__ __launch_bounds__(256) void k_vb_elbo(const double *__restrict__ ll, 
 {
     __shared__ double red[4];
     __shared__ double tot[VB_PIECES];
-    for (int j = 0; j < VB_PIECES; ++j) {
-        double v = 0.0;
-        for (int b = threadIdx.x; b < VB_BLK; b += 256) v += part[j * VB_BLK + b];
-        v = nhp_block_sum_n<4>(v, red);
-        if (threadIdx.x == 0) tot[j] = v;
-    }
+    vb_sum_parts<VB_PIECES>(part, tot, red);
     if (threadIdx.x == 0) {
         const double sl = *ll + tot[0];
         out[0] = sl;
@@ -163,16 +118,52 @@ __global__ __launch_bounds__(256) void k_vb_mean(vb_args a, const double *__rest
 nhp_status vb_check(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const nhp_gibbs_priors *pr, const char *what)
 {
     NHP_TRY(nhp_em_check(ctx, ds, m, what));
-    const bool ln = m->impulse_kind != NHP_IMPULSE_EXPONENTIAL;
-    if (!vb_positive(pr->alpha0) || !vb_positive(pr->beta0) || !vb_positive(pr->kappa) || !vb_positive(pr->nu) || !vb_positive(pr->a) ||
-        !vb_positive(pr->b) || (ln && (!vb_positive(pr->kappa_mu) || !std::isfinite(pr->mu_mu)))) {
-        nhp_set_error(ctx, "%s: every prior hyper-parameter but the mean μμ must be positive and finite", what);
-        return NHP_EINVAL;
-    }
-    return NHP_OK;
+    return vb_check_priors(ctx, m, pr, what);
 }
 
-struct vb_state { double *x, *S, *R, *part; };                       // a state, its surrogate and its pieces
+// the standard fit for the drivers of nhp_vb_drive.h: S, R the caller's planes (host, or device for a step in place)
+struct vb_fit {
+    static constexpr int OUT = VB_OUT, L_SLOT = 5, STAT_PIECES = 4, PLANES = 2;
+    static constexpr bool UNMASK = false;
+    struct state { double *x, *S, *R, *part; };                      // a state, its surrogate and its pieces
+    nhp_ctx *ctx;
+    vb_args a;
+    size_t P;
+    double *S, *R;
+
+    size_t reserve_doubles() const { return cvb_reserve_doubles(P, VB_BLK); }
+    void carve(vb_bump &b, state &s) const { s.x = b.take(P); s.S = b.take(P); s.R = b.take(P); s.part = b.take((size_t)VB_PIECES * VB_BLK); }
+    void carve_shared(vb_bump &) const {}
+    // a step updates one pair of planes in place: the caller's own when they are on the device
+    void place_step(state &cur, state &nxt, bool on_device) const
+    {
+        if (on_device) { cur.S = S; cur.R = R; }
+        nxt.S = cur.S; nxt.R = cur.R;
+    }
+    void planes(const state &s, vb_plane *pl) const { pl[0] = {S, s.S, P, false}; pl[1] = {R, s.R, P, false}; }
+    void start(hipStream_t st, const double *xin, const state &s) const
+    {
+        hipLaunchKernelGGL(k_vb_start, dim3(VB_BLK), dim3(256), 0, st, a, xin, s.x, s.part);
+    }
+    void surrogate(hipStream_t st, const state &s) const
+    {
+        hipLaunchKernelGGL(k_vb_surrogate, dim3(VB_BLK), dim3(256), 0, st, a, (const double *)s.S, (const double *)s.R, s.x, s.part);
+    }
+    void elbo(hipStream_t st, const state &s, bool, double *out) const
+    {
+        hipLaunchKernelGGL(k_vb_elbo, dim3(1), dim3(256), 0, st, (const double *)ctx->d_results, (const double *)s.part, out);
+    }
+    nhp_status update(nhp_ctx *, hipStream_t st, const state &cur, const state &nxt, const double *g, int) const
+    {
+        hipLaunchKernelGGL(k_vb_update, dim3(VB_BLK), dim3(256), 0, st, a, (const double *)cur.x, g, nxt.S, nxt.R, nxt.x, nxt.part);
+        return NHP_OK;
+    }
+    void mean(hipStream_t st, const state &s, double *x, nhp_cont_model *) const
+    {
+        hipLaunchKernelGGL(k_vb_mean, dim3(VB_BLK), dim3(256), 0, st, a, (const double *)s.S, (const double *)s.R, x);
+    }
+    void stats(const double *h, bool from_model, double *out) const { vb_fill_stats(h, OUT, STAT_PIECES, from_model, out); }
+};
 
 }   // namespace
 
@@ -182,53 +173,10 @@ extern "C" nhp_status nhp_cont_vb_step(nhp_ctx *ctx, const nhp_cont_dataset *ds,
 {
     if (!ctx || !ds || !m || !priors || !S || !R || !stats) return NHP_EINVAL;
     NHP_TRY(vb_check(ctx, ds, m, priors, "update!"));
-    const size_t P = nhp_layout(m).P;
     NHP_TRY(nhp_layout_check(ctx, nhp_layout(m), len));
-    NHP_HIP(ctx, hipSetDevice(ctx->device));
-    NHP_TRY(nhp_check_deferred(ctx));
-    hipStream_t st = ctx->main();
-    const bool from_model = (flags & NHP_VB_FROM_MODEL) != 0;
-    flags &= ~(int32_t)(NHP_VB_FROM_MODEL | NHP_VB_RESUME);
-
-    // the surrogate stepped from and the one stepped to, each with its pieces; the planes of a host caller; the sums
-    const size_t np = (size_t)VB_PIECES * VB_BLK;
-    NHP_TRY(nhp_ctx_reserve_mle(ctx, 8 * (4 * P + 2 * np + 2 * VB_OUT), "variational state"));
-    double *d_x = (double *)ctx->d_mle, *d_xn = d_x + P, *d_S = d_xn + P, *d_R = d_S + P;
-    double *d_p0 = d_R + P, *d_p1 = d_p0 + np, *d_out = d_p1 + np;
-    if (output_on_device) { d_S = S; d_R = R; }
-    const vb_args a = vb_make_args(ds, m, priors);
-    const dim3 grid(VB_BLK), block(256);
-    if (from_model) {
-        hipLaunchKernelGGL(k_vb_start, grid, block, 0, st, a, (const double *)m->d_params, d_x, d_p0);
-    } else {
-        if (!output_on_device) {
-            NHP_HIP(ctx, hipMemcpyAsync(d_S, S, 8 * P, hipMemcpyHostToDevice, st));
-            NHP_HIP(ctx, hipMemcpyAsync(d_R, R, 8 * P, hipMemcpyHostToDevice, st));
-        }
-        hipLaunchKernelGGL(k_vb_surrogate, grid, block, 0, st, a, (const double *)d_S, (const double *)d_R, d_x, d_p0);
-    }
-    NHP_HIP(ctx, hipGetLastError());
-    double *d_grad = nullptr;
-    nhp_cont_model mm = *m;                                           // (the E-step bumps the version of what it evaluates)
-    NHP_TRY(nhp_em_estep(ctx, ds, &mm, flags, d_x, (int64_t)P, &d_grad));
-    hipLaunchKernelGGL(k_vb_elbo, dim3(1), block, 0, st, (const double *)ctx->d_results, (const double *)d_p0, d_out);
-    hipLaunchKernelGGL(k_vb_update, grid, block, 0, st, a, (const double *)d_x, (const double *)d_grad, d_S, d_R, d_xn, d_p1);
-    hipLaunchKernelGGL(k_vb_elbo, dim3(1), block, 0, st, (const double *)ctx->d_results, (const double *)d_p1, d_out + VB_OUT);
-    NHP_HIP(ctx, hipGetLastError());
-    double h[2 * VB_OUT];
-    NHP_TRY(nhp_download(ctx, h, d_out, sizeof h));
-    if (!output_on_device) {
-        NHP_TRY(nhp_download(ctx, S, d_S, 8 * P));
-        NHP_TRY(nhp_download(ctx, R, d_R, 8 * P));
-    }
-    NHP_HIP(ctx, hipStreamSynchronize(st));
-    if (!std::isfinite(h[0])) {
-        nhp_set_error(ctx, "update!: the intensity of some event is not positive and finite");
-        return NHP_EDOMAIN;
-    }
-    stats[0] = h[0];
-    for (int j = 1; j < VB_PIECES; ++j) { stats[j] = from_model ? 0.0 : h[j]; stats[4 + j] = h[VB_OUT + j]; }
-    return NHP_OK;
+    vb_fit f{ctx, vb_make_args(ds, m, priors), nhp_layout(m).P, S, R};
+    return vb_step_drive(ctx, ds, m, flags & ~(int32_t)(NHP_VB_FROM_MODEL | NHP_VB_RESUME), f, (flags & NHP_VB_FROM_MODEL) != 0,
+                         output_on_device != 0, stats);
 }
 
 extern "C" nhp_status nhp_cont_vb_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *m, int32_t flags,
@@ -238,77 +186,8 @@ extern "C" nhp_status nhp_cont_vb_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, 
     if (!ctx || !ds || !m || !priors || !x || !S || !R || !elbo || !steps_out || !converged_out) return NHP_EINVAL;
     NHP_TRY(vb_check(ctx, ds, m, priors, "vb!"));
     const bool resume = (flags & NHP_VB_RESUME) != 0;
-    flags &= ~(int32_t)(NHP_VB_FROM_MODEL | NHP_VB_RESUME);
-    if (max_steps < (resume ? 0 : 1)) {
-        nhp_set_error(ctx, "vb!: max_steps = %d (a run from a guess needs at least one step to have a state)", max_steps);
-        return NHP_EDOMAIN;
-    }
-    const size_t P = nhp_layout(m).P;
-    NHP_TRY(nhp_layout_check(ctx, nhp_layout(m), len));
-    NHP_HIP(ctx, hipSetDevice(ctx->device));
-    NHP_TRY(nhp_check_deferred(ctx));
-    hipStream_t st = ctx->main();
-    nhp_em_host hs;
-    if (hipHostMalloc((void **)&hs.h, 8 * VB_OUT) != hipSuccess) { hs.h = nullptr; nhp_set_error(ctx, "out of pinned memory"); return NHP_ENOMEM; }
-    NHP_HIP(ctx, hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
-
-    // two states (surrogate, planes, pieces): an update writes the other one only, so nothing is lost when the rule says stop
-    const size_t np = (size_t)VB_PIECES * VB_BLK, stride = 3 * P + np;
-    NHP_TRY(nhp_ctx_reserve_mle(ctx, 8 * (2 * stride + VB_OUT), "variational state"));
-    double *base = (double *)ctx->d_mle, *d_out = base + 2 * stride;
-    vb_state cur{base, base + P, base + 2 * P, base + 3 * P}, nxt{base + stride, base + stride + P, base + stride + 2 * P, base + stride + 3 * P};
-    const vb_args a = vb_make_args(ds, m, priors);
-    const dim3 grid(VB_BLK), block(256);
-
-    if (resume) {
-        NHP_HIP(ctx, hipMemcpyAsync(cur.S, S, 8 * P, hipMemcpyHostToDevice, st));
-        NHP_HIP(ctx, hipMemcpyAsync(cur.R, R, 8 * P, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_vb_surrogate, grid, block, 0, st, a, (const double *)cur.S, (const double *)cur.R, cur.x, cur.part);
-    } else {
-        NHP_HIP(ctx, hipMemcpyAsync(nxt.x, x, 8 * P, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_vb_start, grid, block, 0, st, a, (const double *)nxt.x, cur.x, cur.part);
-    }
-    NHP_HIP(ctx, hipGetLastError());
-
-    const double nan = std::nan("");
-    double L = nan, L_prev = nan;
-    bool has_state = resume, converged = false;
-    int k = 0;
-    for (;; ++k) {
-        // E-step at x̃_k and the ELBO of state k; the update is enqueued behind the scalars' copy, so it runs while the host looks
-        // at the stopping rule
-        double *d_grad = nullptr;
-        NHP_TRY(nhp_em_estep(ctx, ds, m, flags, cur.x, (int64_t)P, &d_grad));
-        hipLaunchKernelGGL(k_vb_elbo, dim3(1), block, 0, st, (const double *)ctx->d_results, (const double *)cur.part, d_out);
-        NHP_HIP(ctx, hipGetLastError());
-        NHP_HIP(ctx, hipMemcpyAsync(hs.h, d_out, 8 * VB_OUT, hipMemcpyDeviceToHost, st));
-        NHP_HIP(ctx, hipEventRecord(hs.ev, st));
-        if (k < max_steps) {
-            hipLaunchKernelGGL(k_vb_update, grid, block, 0, st, a, (const double *)cur.x, (const double *)d_grad, nxt.S, nxt.R, nxt.x, nxt.part);
-            NHP_HIP(ctx, hipGetLastError());
-        }
-        NHP_HIP(ctx, hipEventSynchronize(hs.ev));
-        if (!std::isfinite(hs.h[0])) {
-            NHP_HIP(ctx, hipStreamSynchronize(st));
-            nhp_set_error(ctx, "vb!: the intensity of some event is not positive and finite (iteration %d)", k);
-            return NHP_EDOMAIN;
-        }
-        L_prev = L; L = has_state ? hs.h[5] : nan;
-        if (trace) trace[k] = L;
-        if (has_state && std::fabs(L - L_prev) < f_abstol) { converged = true; break; }     // (false while L_prev is NaN)
-        if (k == max_steps) break;
-        std::swap(cur, nxt);
-        has_state = true;
-    }
-    // the state, and its means into x and the model's own block
-    hipLaunchKernelGGL(k_vb_mean, grid, block, 0, st, a, (const double *)cur.S, (const double *)cur.R, nxt.x);
-    NHP_HIP(ctx, hipGetLastError());
-    ++m->version;
-    NHP_HIP(ctx, hipMemcpyAsync(m->d_params, nxt.x, 8 * P, hipMemcpyDeviceToDevice, st));
-    NHP_TRY(nhp_download(ctx, x, nxt.x, 8 * P));
-    NHP_TRY(nhp_download(ctx, S, cur.S, 8 * P));
-    NHP_TRY(nhp_download(ctx, R, cur.R, 8 * P));
-    NHP_HIP(ctx, hipStreamSynchronize(st));
-    *elbo = L; *steps_out = k; *converged_out = converged ? 1 : 0;
-    return NHP_OK;
+    NHP_TRY(vb_run_args(ctx, m, resume, max_steps, len));
+    vb_fit f{ctx, vb_make_args(ds, m, priors), nhp_layout(m).P, S, R};
+    return vb_run_drive(ctx, ds, m, flags & ~(int32_t)(NHP_VB_FROM_MODEL | NHP_VB_RESUME), f, resume, f_abstol, max_steps, x, elbo, steps_out,
+                        converged_out, trace);
 }

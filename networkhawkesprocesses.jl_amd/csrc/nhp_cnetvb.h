@@ -1,5 +1,6 @@
 // Host-only parts of the continuous network variational fit (cont_netvb.hip): the argument checks that run
-// before any launch and the sizing of the device state.  Plain C++ with no HIP in it, so that a stand-alone program can run
+// before any launch and the sizing of the device state -- the standard fit's (cont_vb.hip) sizing and the bump allocator of
+// the shared drivers too, so that they are checked where the network's are.  Plain C++ with no HIP in it, so that a stand-alone program can run
 // it under the host sanitizers (tools/cnetvb_host_check.cpp).
 #pragma once
 #include <cmath>
@@ -55,6 +56,22 @@ inline int cnetvb_check_state(const char *what, size_t N, bool dense, bool state
     }
     return CNETVB_OK;
 }
+
+// The bump allocator every continuous variational driver carves its reserved block with (nhp_vb_drive.h): what it handed
+// out is compared with the fit's *_reserve_doubles before any launch, which ties the sizing below to the carving.
+struct vb_bump {
+    double *base, *p;
+    explicit vb_bump(double *b) : base(b), p(b) {}
+    double *take(size_t n) { double *r = p; p += n; return r; }
+    size_t used() const { return (size_t)(p - base); }
+};
+
+// the standard fit (cont_vb.hip): a state is its surrogate, S, R (P each) and the partial sums of its pieces; a step or a run
+// reserves two states and the scalars of two ELBO evaluations
+constexpr int VB_PIECES = 5;         // fix = T Σ λ̃0 + Σ cnt_p W̃, then E_q[compensator], KL_λ0, KL_W, KL_imp
+constexpr int VB_OUT = 6;            // k_vb_elbo: Σ log λ̃, the four pieces, L
+inline size_t cvb_state_doubles(size_t P, size_t blocks) { return 3 * P + (size_t)VB_PIECES * blocks; }
+inline size_t cvb_reserve_doubles(size_t P, size_t blocks) { return 2 * cvb_state_doubles(P, blocks) + 2 * VB_OUT; }
 
 // doubles of one device state: surrogate, S, R (P each), Q with the network's [αv, βv, ψ(αv) - ψ(βv)] behind its planes, and
 // the partial sums of its pieces

@@ -361,17 +361,25 @@ class ContinuousVariational:
         return f"\n* Status: {self.status}\n    steps: {self.steps}\n    elapsed: {self.elapsed}\n    elbo: {self.elbo}"
 
 
+def _hyper_check(what, label, values, mu_mu):
+    """The hyper-parameters' argument errors: every named value positive and finite, the prior mean μμ finite."""
+    for name, v in values:
+        if not (v > 0.0 and math.isfinite(v)):
+            raise ValueError(f"{what}: the {label} {name} = {v} must be positive and finite")
+    if not math.isfinite(float(mu_mu)):
+        raise ValueError(f"{what}: the prior mean mu_mu = {mu_mu} must be finite")
+
+
+def _prior_values(pr, impulses):
+    names = ["alpha0", "beta0", "kappa", "nu", "a", "b"] + ([] if isinstance(impulses, ExponentialImpulseResponse) else ["kappa_mu"])
+    return [(n, float(getattr(pr, n))) for n in names]
+
+
 def _vb_check(process, data, what):
     """_em_check's argument errors and the hyper-parameters' (positive and finite; μμ finite), before any device work."""
     _em_check(process, data, what)
     pr = _priors(process)
-    names = ["alpha0", "beta0", "kappa", "nu", "a", "b"] + ([] if isinstance(process.impulses, ExponentialImpulseResponse) else ["kappa_mu"])
-    for name in names:
-        v = float(getattr(pr, name))
-        if not (v > 0.0 and math.isfinite(v)):
-            raise ValueError(f"{what}: the prior hyper-parameter {name} = {v} must be positive and finite")
-    if not math.isfinite(float(pr.mu_mu)):
-        raise ValueError(f"{what}: the prior mean mu_mu = {pr.mu_mu} must be finite")
+    _hyper_check(what, "prior hyper-parameter", _prior_values(pr, process.impulses), pr.mu_mu)
     return pr
 
 
@@ -387,6 +395,96 @@ def _vb_state(process, init, P):
     return init.S.copy(), init.R.copy()
 
 
+# One description per fit for the two helpers every continuous variational entry shares.  entry: nhp_cont_<entry>_step / _run;
+# lead: the C arguments between the priors and the state; arrays(init, what) -> ([S, R, ...] as the entry takes them -- the state
+# of `init`, or what a start without one reads --, step0 or None: the block fit's last lead argument); guess(): the default
+# guess in device order; result(arrays, step0, taken, **kw) and write_back(x, res): the fit's result class and the overwrite
+# of the process; npieces: ELBO pieces per state in stats (a block fit's network pieces follow them).
+_VBFit = collections.namedtuple("_VBFit", "entry pr P flags lead nstats npieces arrays guess result write_back")
+
+
+def _vb_step(process, data, fit, init, recursive, ctx):
+    """update_ of every continuous fit: one call of nhp_cont_<entry>_step on host planes; the result with its `pieces`."""
+    import ctypes as C
+    from .continuous import _check_recursive
+    flags = _check_recursive(process, recursive) | fit.flags | (NHP_VB_FROM_MODEL if init is None else 0)
+    arrays, step0 = fit.arrays(init, "update!")
+    ctx = ctx or _lib.default_context()
+    ds = device_dataset(process, data, ctx)
+    start = time.time()
+    model = process.device_model(ctx)
+    stats = np.empty(fit.nstats)
+    lead = fit.lead + (() if step0 is None else (step0,))
+    _lib.check(getattr(_lib.lib(), f"nhp_cont_{fit.entry}_step")(
+        ctx.h, ds.h, model.h, flags, C.byref(fit.pr), *lead, arrays[0].ctypes.data, arrays[1].ctypes.data, fit.P,
+        *(a.ctypes.data for a in arrays[2:]), 0, _lib.dptr(stats)), ctx.h)
+    n = fit.npieces
+    elbo = float("nan")
+    if init is not None:
+        elbo = stats[0]
+        for j in range(1, n + 1):
+            elbo = elbo - stats[j]
+    res = fit.result(arrays, step0, 1, elbo=float(elbo), steps=1, elapsed=time.time() - start)
+    res.pieces = {"loglam": float(stats[0]), "before": tuple(stats[1:1 + n]), "after": tuple(stats[1 + n:1 + 2 * n])}
+    if fit.nstats > 1 + 2 * n:
+        res.pieces.update(network_before=tuple(stats[11:16]), network_after=tuple(stats[16:21]))
+    return res
+
+
+def _vb_run(process, data, fit, max_steps, f_abstol, guess, recursive, init, keep_trace, verbose, ctx):
+    """vb_ of every continuous fit: one call of nhp_cont_<entry>_run from a guess or from the state of `init`, the trace, the
+    result and the overwrite of the process."""
+    import ctypes as C
+    from .continuous import _check_recursive
+    P = fit.P
+    flags = _check_recursive(process, recursive) | fit.flags
+    max_steps = int(max_steps)
+    if init is not None and guess is not None:
+        raise ValueError("vb!: give a guess or a state to resume (init), not both")
+    arrays, step0 = fit.arrays(init, "vb!")
+    if init is not None:
+        x = np.empty(P)
+        flags |= NHP_VB_RESUME
+    else:
+        x = np.array(fit.guess() if guess is None else guess, dtype=np.float64)
+        if x.shape != (P,):
+            raise ValueError("Parameter vector length does not match model parameter length.")
+    if max_steps < (0 if init is not None else 1):
+        raise ValueError("vb!: max_steps must be at least 1 (0 with init)")
+    ctx = ctx or _lib.default_context()
+    ds = device_dataset(process, data, ctx)
+    start = time.time()
+    if init is None and fit.entry == "vb":
+        process.params_(x)                                          # column-major tables, as in em_
+    model = process.device_model(ctx)
+    elbo, steps, conv = C.c_double(), C.c_int32(), C.c_int32()
+    trace = np.full(max_steps + 1, np.nan)
+    lead = fit.lead + (() if step0 is None else (step0,))
+    _lib.check(getattr(_lib.lib(), f"nhp_cont_{fit.entry}_run")(
+        ctx.h, ds.h, model.h, flags, C.byref(fit.pr), *lead, float(f_abstol), max_steps, _lib.dptr(x), _lib.dptr(arrays[0]),
+        _lib.dptr(arrays[1]), P, *(_lib.dptr(a) for a in arrays[2:]), C.byref(elbo), C.byref(steps), C.byref(conv), _lib.dptr(trace)), ctx.h)
+    first = 0 if init is not None else 1
+    if verbose:
+        for k in range(first, steps.value + 1):
+            print(f" > step: {k}, elbo: {trace[k]}")
+        print(f" > steps: {steps.value}, elbo: {elbo.value}, elapsed: {time.time() - start}")
+    res = fit.result(arrays, step0, steps.value, elbo=elbo.value, trace=trace[first:steps.value + 1].copy() if keep_trace else None,
+                     steps=steps.value, status="success" if conv.value else "failure", elapsed=time.time() - start)
+    fit.write_back(x, res)
+    return res
+
+
+def _standard_fit(process, pr):
+    P = len(process.params())
+
+    def arrays(init, what):
+        return ([np.empty(P), np.empty(P)] if init is None else list(_vb_state(process, init, P))), None
+
+    def result(arrays, step0, taken, **kw):
+        return ContinuousVariational(_vb_kind_of(process), process.ndims(), *arrays, pr.kappa, **kw)
+    return _VBFit("vb", pr, P, 0, (), 9, 4, arrays, process.params, result, lambda x, res: process.params_(x))
+
+
 def vb_step_continuous(process, data, init=None, recursive=True, ctx=None):
     """One coordinate-ascent update of the mean-field posterior (nhp_cont_vb_step): from the state `init` (a
     ContinuousVariational), or with init=None from the process's current parameters used as if they were a surrogate
@@ -394,27 +492,7 @@ def vb_step_continuous(process, data, init=None, recursive=True, ctx=None):
     surrogate stepped from, "before" = (E_q[compensator], KL_λ0, KL_W, KL_imp) of the state stepped from (zeros for
     init=None) and "after" = the same of the state returned; `elbo` is that of the state stepped from (NaN for init=None).
     The process is not changed."""
-    import ctypes as C
-    from .continuous import _check_recursive
-    pr = _vb_check(process, data, "update!")
-    P = len(process.params())
-    flags = _check_recursive(process, recursive)
-    if init is None:
-        S, R = np.empty(P), np.empty(P)
-        flags |= NHP_VB_FROM_MODEL
-    else:
-        S, R = _vb_state(process, init, P)
-    ctx = ctx or _lib.default_context()
-    ds = device_dataset(process, data, ctx)
-    start = time.time()
-    model = process.device_model(ctx)
-    stats = np.empty(9)
-    _lib.check(_lib.lib().nhp_cont_vb_step(ctx.h, ds.h, model.h, flags, C.byref(pr), S.ctypes.data, R.ctypes.data, P, 0, _lib.dptr(stats)),
-               ctx.h)
-    elbo = float("nan") if init is None else float(stats[0] - stats[1] - stats[2] - stats[3] - stats[4])
-    res = ContinuousVariational(_vb_kind_of(process), process.ndims(), S, R, pr.kappa, elbo=elbo, steps=1, elapsed=time.time() - start)
-    res.pieces = {"loglam": float(stats[0]), "before": tuple(stats[1:5]), "after": tuple(stats[5:9])}
-    return res
+    return _vb_step(process, data, _standard_fit(process, _vb_check(process, data, "update!")), init, recursive, ctx)
 
 
 def vb_continuous(process, data, max_steps=1000, f_abstol=1e-6, guess=None, recursive=True, init=None, keep_trace=True,
@@ -428,45 +506,8 @@ def vb_continuous(process, data, max_steps=1000, f_abstol=1e-6, guess=None, recu
     `init=res` resumes from an earlier result instead of a guess.  `data` as for em_ (a list of trials included; T is the
     summed duration).  Like mle_, `process` is overwritten with the posterior means.  Returns a ContinuousVariational; its
     trace (keep_trace) holds the ELBO of states 1 .. steps (of the resumed state too with `init`)."""
-    import ctypes as C
-    from .continuous import _check_recursive
-    pr = _vb_check(process, data, "vb!")
-    P = len(process.params())
-    flags = _check_recursive(process, recursive)
-    max_steps = int(max_steps)
-    if init is not None:
-        if guess is not None:
-            raise ValueError("vb!: give a guess or a state to resume (init), not both")
-        S, R = _vb_state(process, init, P)
-        x = np.empty(P)
-        flags |= NHP_VB_RESUME
-    else:
-        x = np.array(process.params() if guess is None else guess, dtype=np.float64)
-        if x.shape != (P,):
-            raise ValueError("Parameter vector length does not match model parameter length.")
-        S, R = np.empty(P), np.empty(P)
-    if max_steps < (0 if init is not None else 1):
-        raise ValueError("vb!: max_steps must be at least 1 (0 with init)")
-    ctx = ctx or _lib.default_context()
-    ds = device_dataset(process, data, ctx)
-    start = time.time()
-    if init is None:
-        process.params_(x)                                          # column-major tables, as in em_
-    model = process.device_model(ctx)
-    elbo, steps, conv = C.c_double(), C.c_int32(), C.c_int32()
-    trace = np.full(max_steps + 1, np.nan)
-    _lib.check(_lib.lib().nhp_cont_vb_run(ctx.h, ds.h, model.h, flags, C.byref(pr), float(f_abstol), max_steps, _lib.dptr(x),
-                                          _lib.dptr(S), _lib.dptr(R), P, C.byref(elbo), C.byref(steps), C.byref(conv),
-                                          _lib.dptr(trace)), ctx.h)
-    first = 0 if init is not None else 1
-    if verbose:
-        for k in range(first, steps.value + 1):
-            print(f" > step: {k}, elbo: {trace[k]}")
-        print(f" > steps: {steps.value}, elbo: {elbo.value}, elapsed: {time.time() - start}")
-    process.params_(x)
-    return ContinuousVariational(_vb_kind_of(process), process.ndims(), S, R, pr.kappa, elbo=elbo.value,
-                                 trace=trace[first:steps.value + 1].copy() if keep_trace else None, steps=steps.value,
-                                 status="success" if conv.value else "failure", elapsed=time.time() - start)
+    fit = _standard_fit(process, _vb_check(process, data, "vb!"))
+    return _vb_run(process, data, fit, max_steps, f_abstol, guess, recursive, init, keep_trace, verbose, ctx)
 
 
 # ---- mean-field variational inference for the continuous network process (csrc/cont_netvb.hip) ---------------------------
@@ -539,17 +580,12 @@ def _netvb_check(process, data, what):
         pr = _lib.GibbsPriors(b.α0, b.β0, w.κ1, w.ν1, imp.α, imp.β, 0.0, 1.0)
     else:
         pr = _lib.GibbsPriors(b.α0, b.β0, w.κ1, w.ν1, imp.α0, imp.β0, imp.μμ, imp.κμ)
-    names = ["alpha0", "beta0", "kappa", "nu", "a", "b"] + ([] if isinstance(imp, ExponentialImpulseResponse) else ["kappa_mu"])
-    values = [(n, float(getattr(pr, n))) for n in names] + [("kappa0", w.κ0), ("nu0", w.ν0)]
+    values = _prior_values(pr, imp) + [("kappa0", w.κ0), ("nu0", w.ν0)]
     if block:
         values += [("network alpha", net.α), ("network beta", net.β), ("network gamma", net.γ)]
     elif not dense:
         values += [("network alpha", net.α), ("network beta", net.β), ("network alpha_v", net.αv), ("network beta_v", net.βv)]
-    for name, v in values:
-        if not (v > 0.0 and math.isfinite(v)):
-            raise ValueError(f"{what}: the hyper-parameter {name} = {v} must be positive and finite")
-    if not math.isfinite(float(pr.mu_mu)):
-        raise ValueError(f"{what}: the prior mean mu_mu = {pr.mu_mu} must be finite")
+    _hyper_check(what, "hyper-parameter", values, pr.mu_mu)
     netp = np.array([w.κ0, w.ν0, 1.0 if dense or block else net.α, 1.0 if dense or block else net.β], dtype=np.float64)
     return pr, netp, dense
 
@@ -580,35 +616,45 @@ def _device_length(process):
     return param_layout(process).weights.stop
 
 
+def _network_guess(process):
+    return np.concatenate([process.baseline.params(), process.impulses.params(), process.weights.params()]).astype(np.float64)
+
+
+def _network_fit(process, pr, netp, dense):
+    """The fit of a network process for _vb_step / _vb_run: a Dense or Bernoulli network, or a block network."""
+    P, kind, N = _device_length(process), _vb_kind_of(process), process.ndims()
+
+    def write_back(x, res):
+        _netvb_write_back(process, x, res)
+    if _is_block(process):
+        net = process.network
+
+        def result(arrays, step0, taken, **kw):
+            return ContinuousBlockNetworkVariational(kind, N, *arrays, net.nblocks, pr.kappa, step0 + taken, net.labels_every, **kw)
+        lead = (_lib.dptr(netp), _lib.dptr(_sbmvb_priors(process)), net.nblocks, int(net.labels_every))
+        return _VBFit("sbmvb", pr, P, 0, lead, 21, 5, lambda init, what: _sbmvb_inputs(process, init, P, what), lambda: _network_guess(process),
+                      result, write_back)
+
+    def arrays(init, what):
+        if init is None:
+            return [np.empty(P), np.empty(P), _netvb_start_Q(process, dense)], None
+        return list(_netvb_state(process, init, P)), None
+
+    def result(arrays, step0, taken, **kw):
+        return ContinuousNetworkVariational(kind, N, *arrays, pr.kappa, dense, **kw)
+    return _VBFit("netvb", pr, P, NHP_VB_DENSE_NETWORK if dense else 0, (_lib.dptr(netp),), 11, 5, arrays, lambda: _network_guess(process), result,
+                  write_back)
+
+
 def vb_step_network_continuous(process, data, init=None, recursive=True, ctx=None):
     """One coordinate-ascent update of the network process's mean-field posterior (nhp_cont_netvb_step): from the state
     `init` (a ContinuousNetworkVariational), or with init=None from the process's current λ0, impulses and W used as if they
     were a surrogate (iteration 0 of vb_) and the network's (αv, βv).  Returns the updated ContinuousNetworkVariational with
-    `pieces` (see the class); `elbo` is that of the state stepped from (NaN for init=None).  The process is not changed."""
-    import ctypes as C
-    from .continuous import _check_recursive
-    pr, netp, dense = _netvb_check(process, data, "update!")
-    if _is_block(process):
-        return _vb_step_block_network_continuous(process, data, pr, netp, init, recursive, ctx)
-    P = _device_length(process)
-    flags = _check_recursive(process, recursive) | (NHP_VB_DENSE_NETWORK if dense else 0)
-    if init is None:
-        S, R, Q = np.empty(P), np.empty(P), _netvb_start_Q(process, dense)
-        flags |= NHP_VB_FROM_MODEL
-    else:
-        S, R, Q = _netvb_state(process, init, P)
-    ctx = ctx or _lib.default_context()
-    ds = device_dataset(process, data, ctx)
-    start = time.time()
-    model = process.device_model(ctx)
-    stats = np.empty(11)
-    _lib.check(_lib.lib().nhp_cont_netvb_step(ctx.h, ds.h, model.h, flags, C.byref(pr), _lib.dptr(netp), S.ctypes.data, R.ctypes.data, P,
-                                              Q.ctypes.data, 0, _lib.dptr(stats)), ctx.h)
-    elbo = float("nan") if init is None else float(stats[0] - stats[1] - stats[2] - stats[3] - stats[4] - stats[5])
-    res = ContinuousNetworkVariational(_vb_kind_of(process), process.ndims(), S, R, Q, pr.kappa, dense, elbo=elbo, steps=1,
-                                       elapsed=time.time() - start)
-    res.pieces = {"loglam": float(stats[0]), "before": tuple(stats[1:6]), "after": tuple(stats[6:11])}
-    return res
+    `pieces` (see the class); `elbo` is that of the state stepped from (NaN for init=None).  The process is not changed.
+
+    Under a block network (nhp_cont_sbmvb_step): the step numbered init.vb_step + 1, or network.vb_step + 1 without a state;
+    a ContinuousBlockNetworkVariational, and the network is not changed either."""
+    return _vb_step(process, data, _network_fit(process, *_netvb_check(process, data, "update!")), init, recursive, ctx)
 
 
 def _netvb_write_back(process, x, res):
@@ -640,50 +686,14 @@ def vb_network_continuous(process, data, max_steps=1000, f_abstol=1e-6, guess=No
     Arguments and stopping rule are vb_continuous's; `guess` is a vector in the device order [λ0; θ | μ, τ; W] (default: the
     process's current values), `init=res` resumes from an earlier ContinuousNetworkVariational.  The network's (αv, βv) start
     from the network's own.  The process is overwritten: λ0 and the impulses take their posterior means, weights.W = κv1/νv1,
-    adjacency_matrix = (ρv > ½), network.ρ = αv/(αv + βv) with network.αv, network.βv, and the weights' variational tables and ρv."""
-    import ctypes as C
-    from .continuous import _check_recursive
-    pr, netp, dense = _netvb_check(process, data, "vb!")
-    if _is_block(process):
-        return _vb_block_network_continuous(process, data, pr, netp, max_steps, f_abstol, guess, recursive, init, keep_trace, verbose, ctx)
-    P = _device_length(process)
-    flags = _check_recursive(process, recursive) | (NHP_VB_DENSE_NETWORK if dense else 0)
-    max_steps = int(max_steps)
-    if init is not None:
-        if guess is not None:
-            raise ValueError("vb!: give a guess or a state to resume (init), not both")
-        S, R, Q = _netvb_state(process, init, P)
-        x = np.empty(P)
-        flags |= NHP_VB_RESUME
-    else:
-        if guess is None:
-            x = np.concatenate([process.baseline.params(), process.impulses.params(), process.weights.params()]).astype(np.float64)
-        else:
-            x = np.array(guess, dtype=np.float64)
-        if x.shape != (P,):
-            raise ValueError("Parameter vector length does not match model parameter length.")
-        S, R, Q = np.empty(P), np.empty(P), _netvb_start_Q(process, dense)
-    if max_steps < (0 if init is not None else 1):
-        raise ValueError("vb!: max_steps must be at least 1 (0 with init)")
-    ctx = ctx or _lib.default_context()
-    ds = device_dataset(process, data, ctx)
-    start = time.time()
-    model = process.device_model(ctx)
-    elbo, steps, conv = C.c_double(), C.c_int32(), C.c_int32()
-    trace = np.full(max_steps + 1, np.nan)
-    _lib.check(_lib.lib().nhp_cont_netvb_run(ctx.h, ds.h, model.h, flags, C.byref(pr), _lib.dptr(netp), float(f_abstol), max_steps,
-                                             _lib.dptr(x), _lib.dptr(S), _lib.dptr(R), P, _lib.dptr(Q), C.byref(elbo), C.byref(steps),
-                                             C.byref(conv), _lib.dptr(trace)), ctx.h)
-    first = 0 if init is not None else 1
-    if verbose:
-        for k in range(first, steps.value + 1):
-            print(f" > step: {k}, elbo: {trace[k]}")
-        print(f" > steps: {steps.value}, elbo: {elbo.value}, elapsed: {time.time() - start}")
-    res = ContinuousNetworkVariational(_vb_kind_of(process), process.ndims(), S, R, Q, pr.kappa, dense, elbo=elbo.value,
-                                       trace=trace[first:steps.value + 1].copy() if keep_trace else None, steps=steps.value,
-                                       status="success" if conv.value else "failure", elapsed=time.time() - start)
-    _netvb_write_back(process, x, res)
-    return res
+    adjacency_matrix = (ρv > ½), network.ρ = αv/(αv + βv) with network.αv, network.βv, and the weights' variational tables and ρv.
+
+    Under a block network (nhp_cont_sbmvb_run) the block state starts from the network's (variational_init_) or from `init`;
+    the sweep over the labels runs at the steps whose number since variational_init_ is a multiple of network.labels_every.
+    In addition network.mv, αv, βv, γv hold the state, network.ρ = αv/(αv + βv), network.π = γv/Σγv, network.z = labels() and
+    network.vb_step advances by the steps taken."""
+    fit = _network_fit(process, *_netvb_check(process, data, "vb!"))
+    return _vb_run(process, data, fit, max_steps, f_abstol, guess, recursive, init, keep_trace, verbose, ctx)
 
 
 # ---- ... under a stochastic block network (csrc/cont_netvb.hip, DESIGN §3.31) ---------------------------------------------
@@ -730,7 +740,7 @@ class ContinuousBlockNetworkVariational(ContinuousNetworkVariational):
 
 
 def _sbmvb_inputs(process, init, P, what):
-    """(S, R, Q, B, step0) of a call: the state of `init`, or without one the network's own block state and step count."""
+    """([S, R, Q, B], step0) of a call: the state of `init`, or without one the network's own block state and step count."""
     net, N = process.network, process.ndims()
     K = net.nblocks
     if net.nnodes != N:
@@ -740,93 +750,18 @@ def _sbmvb_inputs(process, init, P, what):
             raise TypeError("init must be a ContinuousBlockNetworkVariational (the result of an earlier vb_ or update_ of this process)")
         if init.kind != _vb_kind_of(process) or init.S.shape != (P,) or init.nblocks != K:
             raise ValueError("Parameter vector length does not match model parameter length.")
-        return init.S.copy(), init.R.copy(), init.Q.copy(), init.B.copy(), init.vb_step
+        return [init.S.copy(), init.R.copy(), init.Q.copy(), init.B.copy()], init.vb_step
     shapes = ((net.mv, (N, K), "mv"), (net.αv, (K, K), "αv"), (net.βv, (K, K), "βv"), (net.γv, (K,), "γv"))
     for v, shape, name in shapes:
         if np.shape(v) != shape:
             raise ValueError(f"{what}: network.{name} must have shape {shape}")
     B = np.ascontiguousarray(net.variational_params(), dtype=np.float64)
-    return np.empty(P), np.empty(P), _netvb_start_Q(process, False), B, int(net.vb_step)
+    return [np.empty(P), np.empty(P), _netvb_start_Q(process, False), B], int(net.vb_step)
 
 
 def _sbmvb_priors(process):
     net = process.network
     return np.array([net.α, net.β, net.γ], dtype=np.float64)
-
-
-def _vb_step_block_network_continuous(process, data, pr, netp, init, recursive, ctx):
-    """update_ under a block network (nhp_cont_sbmvb_step): the step numbered init.vb_step + 1, or network.vb_step + 1 without a
-    state.  Returns a ContinuousBlockNetworkVariational; the process and its network are not changed."""
-    import ctypes as C
-    from .continuous import _check_recursive
-    P = _device_length(process)
-    flags = _check_recursive(process, recursive) | (NHP_VB_FROM_MODEL if init is None else 0)
-    S, R, Q, B, step0 = _sbmvb_inputs(process, init, P, "update!")
-    net, sbm = process.network, _sbmvb_priors(process)
-    ctx = ctx or _lib.default_context()
-    ds = device_dataset(process, data, ctx)
-    start = time.time()
-    model = process.device_model(ctx)
-    stats = np.empty(21)
-    _lib.check(_lib.lib().nhp_cont_sbmvb_step(ctx.h, ds.h, model.h, flags, C.byref(pr), _lib.dptr(netp), _lib.dptr(sbm), net.nblocks,
-                                              int(net.labels_every), step0, S.ctypes.data, R.ctypes.data, P, Q.ctypes.data, B.ctypes.data, 0,
-                                              _lib.dptr(stats)), ctx.h)
-    elbo = float("nan") if init is None else float(stats[0] - stats[1] - stats[2] - stats[3] - stats[4] - stats[5])
-    res = ContinuousBlockNetworkVariational(_vb_kind_of(process), process.ndims(), S, R, Q, B, net.nblocks, pr.kappa, step0 + 1,
-                                            net.labels_every, elbo=elbo, steps=1, elapsed=time.time() - start)
-    res.pieces = {"loglam": float(stats[0]), "before": tuple(stats[1:6]), "after": tuple(stats[6:11]),
-                  "network_before": tuple(stats[11:16]), "network_after": tuple(stats[16:21])}
-    return res
-
-
-def _vb_block_network_continuous(process, data, pr, netp, max_steps, f_abstol, guess, recursive, init, keep_trace, verbose, ctx):
-    """vb_ under a block network (nhp_cont_sbmvb_run).  Arguments and stopping rule are vb_network_continuous's.  The block
-    state starts from the network's (variational_init_) or from `init`; the sweep over the labels runs at the steps whose
-    number since variational_init_ is a multiple of network.labels_every.  The process is overwritten as for a Bernoulli
-    network; in addition network.mv, αv, βv, γv hold the state, network.ρ = αv/(αv + βv), network.π = γv/Σγv, network.z =
-    labels() and network.vb_step advances by the steps taken."""
-    import ctypes as C
-    from .continuous import _check_recursive
-    P = _device_length(process)
-    flags = _check_recursive(process, recursive)
-    max_steps = int(max_steps)
-    if init is not None and guess is not None:
-        raise ValueError("vb!: give a guess or a state to resume (init), not both")
-    S, R, Q, B, step0 = _sbmvb_inputs(process, init, P, "vb!")
-    if init is not None:
-        x = np.empty(P)
-        flags |= NHP_VB_RESUME
-    else:
-        if guess is None:
-            x = np.concatenate([process.baseline.params(), process.impulses.params(), process.weights.params()]).astype(np.float64)
-        else:
-            x = np.array(guess, dtype=np.float64)
-        if x.shape != (P,):
-            raise ValueError("Parameter vector length does not match model parameter length.")
-    if max_steps < (0 if init is not None else 1):
-        raise ValueError("vb!: max_steps must be at least 1 (0 with init)")
-    net, sbm = process.network, _sbmvb_priors(process)
-    ctx = ctx or _lib.default_context()
-    ds = device_dataset(process, data, ctx)
-    start = time.time()
-    model = process.device_model(ctx)
-    elbo, steps, conv = C.c_double(), C.c_int32(), C.c_int32()
-    trace = np.full(max_steps + 1, np.nan)
-    _lib.check(_lib.lib().nhp_cont_sbmvb_run(ctx.h, ds.h, model.h, flags, C.byref(pr), _lib.dptr(netp), _lib.dptr(sbm), net.nblocks,
-                                             int(net.labels_every), step0, float(f_abstol), max_steps, _lib.dptr(x), _lib.dptr(S),
-                                             _lib.dptr(R), P, _lib.dptr(Q), _lib.dptr(B), C.byref(elbo), C.byref(steps), C.byref(conv),
-                                             _lib.dptr(trace)), ctx.h)
-    first = 0 if init is not None else 1
-    if verbose:
-        for k in range(first, steps.value + 1):
-            print(f" > step: {k}, elbo: {trace[k]}")
-        print(f" > steps: {steps.value}, elbo: {elbo.value}, elapsed: {time.time() - start}")
-    res = ContinuousBlockNetworkVariational(_vb_kind_of(process), process.ndims(), S, R, Q, B, net.nblocks, pr.kappa, step0 + steps.value,
-                                            net.labels_every, elbo=elbo.value,
-                                            trace=trace[first:steps.value + 1].copy() if keep_trace else None, steps=steps.value,
-                                            status="success" if conv.value else "failure", elapsed=time.time() - start)
-    _netvb_write_back(process, x, res)
-    return res
 
 
 # ---- observed information, Hessian-vector products, standard errors ------------------------------------------------------

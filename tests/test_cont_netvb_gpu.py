@@ -553,6 +553,29 @@ def test_refusals_of_the_device_entry_points(nhp):
         lib.nhp_cont_dataset_destroy(h)
 
 
+def test_a_refused_step_leaves_the_host_planes_alone(nhp):
+    """nhp_cont_netvb_step itself on host planes, N = 2 and three events, from a state whose baseline shapes are 1e-300: the
+    surrogate λ̃0 = exp(ψ(α') - log β') underflows to zero, the first event has no parent, so its intensity is zero:
+    NHP_EDOMAIN (2), and S, R, Q are byte for byte what was passed in."""
+    from nhp_amd import _lib
+    lib, ctx = _lib.lib(), nhp.default_context()
+    N = 2
+    NN = N * N
+    case = random_case(N, 3, 2.0, "exponential", 1.0, seed=1, nhp=nhp)
+    proc = _network(nhp, case["proc"])
+    P = N + 2 * NN
+    S, R, stats = np.full(P, 2.0), np.full(P, 1.5), np.full(11, 7.0)
+    Q = np.concatenate([np.full(NN, 0.5), np.full(NN, 20.0), np.full(NN, 0.5), [2.0, 3.0]])
+    S[:N] = 1e-300
+    keep = S.tobytes(), R.tobytes(), Q.tobytes()
+    pr, netp = _lib.GibbsPriors(2.0, 1.5, 1.5, 2.0, 2.0, 0.7, 0.0, 1.0), np.array([0.3, 30.0, 1.0, 1.0])
+    ds, model = nhp.device_dataset(proc, case["data"], ctx), proc.device_model(ctx)
+    rc = lib.nhp_cont_netvb_step(ctx.h, ds.h, model.h, 0, C.byref(pr), _lib.dptr(netp), S.ctypes.data, R.ctypes.data, P, Q.ctypes.data, 0,
+                                 _lib.dptr(stats))
+    assert rc == 2
+    assert (S.tobytes(), R.tobytes(), Q.tobytes()) == keep
+
+
 def test_the_example_runs():
     truth_A, res, events = importlib.import_module("continuous_exponential_network_hawkes_vb").main()
     assert np.all(np.isfinite(res.trace)) and np.all(np.diff(res.trace) >= -1e-11 * abs(res.elbo))

@@ -429,3 +429,22 @@ def test_refusals_of_the_device_entry_points(nhp):
     assert calls(ln["proc"], ln["data"], _lib.GibbsPriors(2.0, 1.5, 1.5, 2.0, 2.0, 0.7, 0.0, 0.0)) == (1, 1)
     assert calls(ln["proc"], ln["data"], _lib.GibbsPriors(2.0, 1.5, 1.5, 2.0, 2.0, 0.7, np.inf, 1.0)) == (1, 1)
     assert calls(std["proc"], std["data"], good, P=20) == (3, 3)
+
+
+def test_a_refused_step_leaves_the_host_planes_alone(nhp):
+    """nhp_cont_vb_step itself on host planes, N = 2 and three events, from a state whose baseline shapes are 1e-300: the
+    surrogate λ̃0 = exp(ψ(α') - log β') underflows to zero, the first event has no parent, so its intensity is zero:
+    NHP_EDOMAIN (2), and S, R are byte for byte what was passed in."""
+    from nhp_amd import _lib
+    lib, ctx = _lib.lib(), nhp.default_context()
+    N = 2
+    case = random_case(N, 3, 2.0, "exponential", 1.0, seed=1, nhp=nhp)
+    P = N + 2 * N * N
+    S, R, stats = np.full(P, 2.0), np.full(P, 1.5), np.full(9, 7.0)
+    S[:N] = 1e-300
+    keep = S.tobytes(), R.tobytes()
+    pr = _lib.GibbsPriors(2.0, 1.5, 1.5, 2.0, 2.0, 0.7, 0.0, 1.0)
+    ds, model = nhp.device_dataset(case["proc"], case["data"], ctx), case["proc"].device_model(ctx)
+    rc = lib.nhp_cont_vb_step(ctx.h, ds.h, model.h, 0, C.byref(pr), S.ctypes.data, R.ctypes.data, P, 0, _lib.dptr(stats))
+    assert rc == 2
+    assert (S.tobytes(), R.tobytes()) == keep

@@ -91,6 +91,20 @@ int main()
             EXPECT(cnetvb_q_doubles(N) == 3 * NN + 3);
             EXPECT(cnetvb_state_doubles(P, N, blocks) == 3 * P + 3 * NN + 3 + 8 * blocks);
             EXPECT(cnetvb_reserve_doubles(P, N, blocks) == 2 * (3 * P + 3 * NN + 3 + 8 * blocks) + 16);
+            // the standard fit's: surrogate, S, R and five partial sums per state, six scalars per evaluation
+            EXPECT(cvb_state_doubles(P, blocks) == 3 * P + 5 * blocks);
+            EXPECT(cvb_reserve_doubles(P, blocks) == 2 * (3 * P + 5 * blocks) + 12);
+            // the bump allocator, carving as the drivers do: inside the block, in order, and `used` is what was handed out
+            std::vector<double> block(cnetvb_reserve_doubles(P, N, blocks), 0.0);
+            vb_bump mem(block.data());
+            for (int s = 0; s < 2; ++s) {
+                double *x = mem.take(P), *S = mem.take(P), *R = mem.take(P), *Q = mem.take(cnetvb_q_doubles(N)), *part = mem.take(8 * blocks);
+                EXPECT(S == x + P && R == S + P && Q == R + P && part == Q + 3 * NN + 3);
+                x[0] = part[8 * blocks - 1] = 1.0;                                            // both ends lie inside the block
+            }
+            double *out = mem.take(2 * CNETVB_OUT);
+            out[2 * CNETVB_OUT - 1] = 1.0;
+            EXPECT(mem.used() == block.size() && out + 2 * CNETVB_OUT == block.data() + block.size());
         }
     }
     const double pl = cnetvb_prior_logit(0.5, 20.0, 2.0, 1.5);

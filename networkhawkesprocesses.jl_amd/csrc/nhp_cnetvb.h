@@ -1,12 +1,14 @@
 // Host-only parts of the continuous network variational fit (cont_netvb.hip): the argument checks that run
-// before any launch and the sizing of the device state -- the standard fit's (cont_vb.hip) sizing and the bump allocator of
-// the shared drivers too, so that they are checked where the network's are.  Plain C++ with no HIP in it, so that a stand-alone program can run
+// before any launch and the sizing of the device state -- the standard fit's (cont_vb.hip) sizing too, so that it is checked
+// where the network's is (the bump allocator of the shared drivers: nhp_vb_bump.h).  Plain C++ with no HIP in it, so that a stand-alone program can run
 // it under the host sanitizers (tools/cnetvb_host_check.cpp).
 #pragma once
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
+
+#include "nhp_vb_bump.h"
 
 enum { CNETVB_OK = 0, CNETVB_EINVAL = 1 };
 constexpr int CNETVB_PIECES = 8;     // partial sums per workgroup: fix, E_q[comp], KL_λ0, KL_W, KL_imp, Σ entropy terms, Σρv, Σ(1-ρv)
@@ -57,14 +59,7 @@ inline int cnetvb_check_state(const char *what, size_t N, bool dense, bool state
     return CNETVB_OK;
 }
 
-// The bump allocator every continuous variational driver carves its reserved block with (nhp_vb_drive.h): what it handed
-// out is compared with the fit's *_reserve_doubles before any launch, which ties the sizing below to the carving.
-struct vb_bump {
-    double *base, *p;
-    explicit vb_bump(double *b) : base(b), p(b) {}
-    double *take(size_t n) { double *r = p; p += n; return r; }
-    size_t used() const { return (size_t)(p - base); }
-};
+// (vb_bump, which the drivers carve with and compare against the *_reserve_doubles below: nhp_vb_bump.h)
 
 // the standard fit (cont_vb.hip): a state is its surrogate, S, R (P each) and the partial sums of its pieces; a step or a run
 // reserves two states and the scalars of two ELBO evaluations

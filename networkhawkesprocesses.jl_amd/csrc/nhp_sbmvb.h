@@ -1,4 +1,4 @@
-// Host-only parts of the block-model VB / SVI entry points (disc.hip): the argument checks that run before
+// Host-only parts of the block-model VB / SVI entry points (disc_vb.hip): the argument checks that run before
 // any launch, the LDS need of the label sweep and the sizing of the device scratch.  Plain C++ with no HIP in it, so that
 // a stand-alone program can run it under the host sanitizers (tools/sbmvb_host_check.cpp).
 #pragma once

@@ -1717,8 +1717,33 @@ def _vb_kind(process, what):
     return kind
 
 
+class _DenseVB:
+    """The buffers nhp_disc_vb_run / nhp_disc_svi_run update in place, and the way back into the process."""
+    VB_RUN, SVI_RUN = "nhp_disc_vb_run", "nhp_disc_svi_run"
+
+    def __init__(self, process):
+        b, w, imp = process.baseline, process.weights, process.impulses
+        self.process, self.N, self.B = process, process.ndims(), imp.nbasis()
+        self.av, self.bv = _lib.f64(b.αv).copy(), _lib.f64(b.βv).copy()
+        self.kv, self.nv, self.gv = _lib.colmajor(w.κv).copy(), _lib.colmajor(w.νv).copy(), _lib.colmajor(imp.γv).copy()
+
+    def priors(self):
+        b, w, imp = self.process.baseline, self.process.weights, self.process.impulses
+        return (b.α0, b.β0, w.κ, w.ν, imp.γ)
+
+    def pointers(self):
+        return tuple(_lib.dptr(x) for x in (self.av, self.bv, self.kv, self.nv, self.gv))
+
+    def store(self):                              # column-major views of the library's buffers: no transposing copy here or
+        p, N, B = self.process, self.N, self.B    # at the next call (a later chunk of svi_ updates them in place)
+        p.baseline.αv, p.baseline.βv = self.av, self.bv
+        p.weights.κv, p.weights.νv = self.kv.reshape((N, N), order="F"), self.nv.reshape((N, N), order="F")
+        p.impulses.γv = self.gv.reshape((N, N, B), order="F")
+
+
 class _NetVB:
     """The buffers nhp_disc_netvb_run / nhp_disc_netsvi_run update in place, and the way back into the process."""
+    VB_RUN, SVI_RUN = "nhp_disc_netvb_run", "nhp_disc_netsvi_run"
 
     def __init__(self, process):
         from .components import BernoulliNetworkModel
@@ -1761,6 +1786,7 @@ class _NetVB:
 class _BlockVB(_NetVB):
     """The same for a StochasticBlockNetworkModel with a variational state (nhp_disc_sbmvb_run / nhp_disc_sbmsvi_run):
     mv [n, k] and the K x K tables column-major, in place of the Bernoulli network's two scalars."""
+    VB_RUN, SVI_RUN = "nhp_disc_sbmvb_run", "nhp_disc_sbmsvi_run"
 
     def __init__(self, process):
         super().__init__(process)
@@ -1789,8 +1815,11 @@ class _BlockVB(_NetVB):
         net.αv, net.βv, net.γv = self.na.reshape((K, K), order="F"), self.nb.reshape((K, K), order="F"), self.ng
 
 
-def _net_holder(process):
+def _vb_holder(process, kind):
+    """The holder of the fit _vb_kind found; its type picks the library's entry points (VB_RUN, SVI_RUN)."""
     from .components import StochasticBlockNetworkModel
+    if kind != "network":
+        return _DenseVB(process)
     return _BlockVB(process) if isinstance(process.network, StochasticBlockNetworkModel) else _NetVB(process)
 
 
@@ -1808,29 +1837,16 @@ def update_(process, data, convolved, ctx=None, n_steps=1, step0=None):
     data = _enter(process, data, convolved)
     ctx = ctx or _lib.default_context()
     ds = _convolved(process, data, convolved, ctx)
-    if kind == "network":
-        st = _net_holder(process)
-        if isinstance(st, _BlockVB):                  # the sweep's schedule counts steps across calls: network.vb_step
-            net = process.network
-            first = int(net.vb_step if step0 is None else step0)
-            if first < 0:
-                raise ValueError("update!: step0 must be non-negative")
-            _lib.check(_lib.lib().nhp_disc_sbmvb_run(ctx.h, ds.h, process.dt, *st.priors(), first, n_steps, *st.pointers()), ctx.h)
-            net.vb_step = first + int(n_steps)
-        else:
-            _lib.check(_lib.lib().nhp_disc_netvb_run(ctx.h, ds.h, process.dt, *st.priors(), n_steps, *st.pointers()), ctx.h)
-        st.store()
-        return process.variational_params()
-    b, w, imp = process.baseline, process.weights, process.impulses
-    N, B = process.ndims(), imp.nbasis()
-    av, bv = _lib.f64(b.αv).copy(), _lib.f64(b.βv).copy()
-    kv, nv, gv = _lib.colmajor(w.κv).copy(), _lib.colmajor(w.νv).copy(), _lib.colmajor(imp.γv).copy()
-    _lib.check(_lib.lib().nhp_disc_vb_run(ctx.h, ds.h, process.dt, b.α0, b.β0, w.κ, w.ν, imp.γ, n_steps,
-                                          _lib.dptr(av), _lib.dptr(bv), _lib.dptr(kv), _lib.dptr(nv), _lib.dptr(gv)),
-               ctx.h)
-    b.αv, b.βv = av, bv
-    w.κv, w.νv = kv.reshape((N, N), order="F"), nv.reshape((N, N), order="F")
-    imp.γv = gv.reshape((N, N, B), order="F")
+    st = _vb_holder(process, kind)
+    first = ()
+    if isinstance(st, _BlockVB):                      # the sweep's schedule counts steps across calls: network.vb_step
+        first = (int(process.network.vb_step if step0 is None else step0),)
+        if first[0] < 0:
+            raise ValueError("update!: step0 must be non-negative")
+    _lib.check(getattr(_lib.lib(), st.VB_RUN)(ctx.h, ds.h, process.dt, *st.priors(), *first, n_steps, *st.pointers()), ctx.h)
+    if first:
+        process.network.vb_step = first[0] + int(n_steps)
+    st.store()
     return process.variational_params()
 
 
@@ -1916,8 +1932,8 @@ def svi_(process, data, nsteps=1000, batch_bins=4096, delay=1.0, forgetting=0.6,
             raise ValueError(f"svi!: block indices must lie in [0, {nb})")
     ctx = ctx or _lib.default_context()
     start = time.time()
-    b, w, imp = process.baseline, process.weights, process.impulses
-    N, B = process.ndims(), imp.nbasis()
+    imp = process.impulses
+    B = imp.nbasis()
     if streamed:
         ds = data if isinstance(data, DiscreteDataset) else DiscreteDataset(ctx, data)
         phi = imp.basis()
@@ -1926,36 +1942,19 @@ def svi_(process, data, nsteps=1000, batch_bins=4096, delay=1.0, forgetting=0.6,
     else:
         ds = data if isinstance(data, DiscreteDataset) and data.B == B else convolve(process, data, ctx)
         ph, L = None, 0
-    if kind == "network":                         # the same loop on nhp_disc_netsvi_run: four weight tables, ρv, the network
-        net = _net_holder(process)
-        store = net.store
-        net_run = _lib.lib().nhp_disc_sbmsvi_run if isinstance(net, _BlockVB) else _lib.lib().nhp_disc_netsvi_run
-    else:
-        av, bv = _lib.f64(b.αv).copy(), _lib.f64(b.βv).copy()
-        kv, nv, gv = _lib.colmajor(w.κv).copy(), _lib.colmajor(w.νv).copy(), _lib.colmajor(imp.γv).copy()
-
-        def store():                              # column-major views of the library's buffers, as update_ keeps them: no
-            b.αv, b.βv = av, bv                   # transposing copy here or at the next call (a later chunk updates them in place)
-            w.κv, w.νv = kv.reshape((N, N), order="F"), nv.reshape((N, N), order="F")
-            imp.γv = gv.reshape((N, N, B), order="F")
-
+    st = _vb_holder(process, kind)                # the same loop for every fit: the holder's buffers, its entry point
+    run = getattr(_lib.lib(), st.SVI_RUN)
     res = VariationalInference()
     res.step = step0
     done = 0
     while done < nsteps:
         n = min(trace_every, nsteps - done) if trace_every else nsteps
         blk = None if blocks is None else blocks[done:done + n].ctypes.data_as(C.POINTER(C.c_int32))
-        if kind == "network":
-            _lib.check(net_run(ctx.h, ds.h, process.dt, *net.priors(), batch_bins, float(delay), float(forgetting), int(seed),
-                               step0 + done, n, blk, _lib.dptr(ph), L, B, *net.pointers()), ctx.h)
-        else:
-            _lib.check(_lib.lib().nhp_disc_svi_run(ctx.h, ds.h, process.dt, b.α0, b.β0, w.κ, w.ν, imp.γ, batch_bins, float(delay),
-                                                   float(forgetting), int(seed), step0 + done, n, blk, _lib.dptr(ph), L, B,
-                                                   _lib.dptr(av), _lib.dptr(bv), _lib.dptr(kv), _lib.dptr(nv), _lib.dptr(gv)),
-                       ctx.h)
+        _lib.check(run(ctx.h, ds.h, process.dt, *st.priors(), batch_bins, float(delay), float(forgetting), int(seed), step0 + done, n,
+                       blk, _lib.dptr(ph), L, B, *st.pointers()), ctx.h)
         done += n
         res.step = step0 + done
-        store()
+        st.store()
         if trace_every:
             res.trace.append(process.variational_params())
     if not trace_every:

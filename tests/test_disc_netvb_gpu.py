@@ -139,6 +139,30 @@ def test_the_dense_limit_is_the_dense_step(nhp, N, T, B, L):
         assert np.allclose(got[2], PRI[2] + (got[4] - PRI[4]), rtol=1e-12) and np.allclose(got[3], PRI[3] + (got[5] - PRI[5]), rtol=1e-12)
 
 
+@pytest.mark.parametrize("N,T,B,L,Tb", [(5, 700, 3, 7, 128), (130, 300, 2, 3, 112)])
+def test_the_dense_limit_is_the_dense_step_under_svi(nhp, N, T, B, L, Tb):
+    """The same limit through svi_: three blended steps (first block, the short last block, the second), resident and
+    streamed, leave ρv ≡ 1 and (αv, βv, κv1, νv1, γv) those of svi_ on the standard process, to the rounding of the blend
+    (the compiler fuses the two finish kernels' blends kernel by kernel: not the same bits, where the VB twin above has them)."""
+    proc, data, conv, start = problem(nhp, N, T, B, L, net=None)
+    std = nr.make_process(nhp, N, B, L, PRI, None, seed=N, standard=True)
+    nb = sr.n_blocks(T, Tb)
+    assert T % Tb != 0
+    kw = dict(nsteps=3, blocks=np.array([0, nb - 1, min(1, nb - 1)], dtype=np.int32), batch_bins=Tb, delay=1.0, forgetting=0.6)
+    for streamed, arg in ((False, nhp.convolve(proc, data)), (True, data)):
+        nr.put(proc, start)
+        std.baseline.αv, std.baseline.βv, std.weights.κv, std.weights.νv, std.impulses.γv = copy_of((start[0], start[1], start[4], start[5], start[6]))
+        nhp.svi_(proc, arg, streamed=streamed, **kw)
+        nhp.svi_(std, arg, streamed=streamed, **kw)
+        got = nr.get(proc)
+        want = (std.baseline.αv, std.baseline.βv, std.weights.κv, std.weights.νv, std.impulses.γv)
+        mine = (got[0], got[1], got[4], got[5], got[6])
+        print(f"streamed={streamed}: bits equal: {all(np.array_equal(g, w) for g, w in zip(mine, want))}; largest relative difference {worst(mine, want):.2e}")
+        for g, w in zip(mine, want):
+            assert np.allclose(g, w, rtol=1e-13, atol=0.0)
+        assert np.all(got[7] == 1.0)
+
+
 def test_symmetric_priors(nhp):
     N, T, B, L = 5, 700, 3, 7
     sym = (1.0, 1.0, 0.8, 2.0, 0.8, 2.0, 1.0)

@@ -1434,6 +1434,67 @@ nhp_status nhp_cont_sbmvb_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont
                               double *Q /* [3*N*N] */, double *B /* [2*K*K + K + N*K] */, double *elbo, int32_t *steps,
                               int32_t *converged, double *trace /* nullable, [max_steps + 1] */);
 
+/* Mean-field variational inference for the continuous network process under a LATENT DISTANCE network (csrc/cont_netvb.hip,
+ * csrc/nhp_latvb_dev.h).  Likelihood, λ0, impulse and weight factors are exactly nhp_cont_netvb_run's; the network part is
+ *   z_n ~ N(0, σ² I_D),  b ~ N(μb, σb²),  A[p,c] ~ Bernoulli(s(η[p,c])),  η[p,c] = b - ‖z_p - z_c‖²,  s the logistic function,
+ * over all N² entries (the diagonal has η = b), D = n_dims in 1..8.  q(A[p,c] = 1) = ρv[p,c]; the network's factor is a POINT MASS at
+ * (zv, bv): variational EM over the positions and the offset.  (η is quadratic in z, so a bound on the logistic likelihood would
+ * still leave a quartic; a point estimate keeps the bound exact.)  Hence E_q[log s(η)] - E_q[log(1 - s(η))] = η[p,c] exactly.
+ * net = [κ0, ν0] (the spike), lat = [σ, μb, σb].  The state is S, R [len] (nhp_cont_netvb_run's), Q = [κv0; νv0; ρv] of 3·N² doubles,
+ * column-major [p + c·N], and Z = [vec zv; bv] of N·D + 1 doubles, zv column-major (z_n[d] at n + N·d).  One step from state k:
+ *   1. surrogate and E-step as nhp_cont_netvb_step (the E-step runs at x̃ on the model without its adjacency matrix);
+ *   2. λ0, the impulse factors and κv_a = κ_a + EM, νv_a = ν_a + cnt_p as nhp_cont_netvb_step;
+ *   3. logit ρv[p,c] = η[p,c] + the prior and lnΓ / log ν terms of nhp_cont_netvb_step's step 3, in the same cancellation-free form,
+ *      with η from the OLD (zv, bv), ‖z_p - z_c‖² added over d increasing;
+ *   4. J = ascent_steps (0..64) iterations of a monotone ascent, at the NEW ρv, of
+ *        F(z, b) = Σ_pc [ρv η - softplus(η)] - ‖z‖²/(2σ²) - (b - μb)²/(2σb²),   softplus(η) = max(η, 0) + log1p(exp(-|η|)).
+ *      With C = ρv + ρvᵀ (η is symmetric):  Σ_pc [ρv η - softplus(η)] = ½ Σ_nj [C[j,n] η_nj - 2 softplus(η_nj)]  over all ordered (n, j),
+ *        ∂F/∂z_n = -2 Σ_j (C[j,n] - 2 s(η_nj)) (z_n - z_j) - z_n/σ²,     ∂F/∂b = ½ Σ_nj (C[j,n] - 2 s(η_nj)) - (b - μb)/σb².
+ *      One iteration takes G = ∇F at the current (z, b) and evaluates F at (z, b) + t_r·G for the R = 8 step sizes
+ *        t_r = τ·4^(1-r),  r = 0..7,  τ = 1/(N + 1/σ²)
+ *      and at t = 0 in ONE pass over the pairs: with Δz = z_n - z_j, Δg = G_n - G_j, a = ‖Δz‖², bb = Δz·Δg, c = ‖Δg‖²,
+ *        η_nj(t) = (b + t·G_b) - (a + t·(2·bb + t·c)),   ‖z + tG_z‖² = Σz² + t·(2 Σz·g + t·Σg²).
+ *      It moves to the rung with the largest F, the lowest index on ties, if that F EXCEEDS F at t = 0 (same pass, same form), and
+ *      stays where it is otherwise (rung -1).  J = 0 holds the network fixed: zv, bv are returned bit for bit.
+ * Steps (2-3) and every iteration of 4 are coordinate ascents of one bound, so the ELBO never falls:
+ *   L = Σ_i log λ̃_i - E_q[comp] - KL_λ0 - KL_W - KL_imp - KL_net          (the first five as nhp_cont_netvb_run)
+ *   KL_net = Σ_pc [ρv ln ρv + (1-ρv) ln(1-ρv)] - [links + ln p(zv) + ln p(bv)],   links = Σ_pc [ρv η - softplus(η)] at the state's OWN
+ *   (zv, bv), evaluated directly (not through the ray's quadratic),  ln p(z) = -‖z‖²/(2σ²) - (N·D/2) ln(2πσ²),
+ *   ln p(b) = -(b - μb)²/(2σb²) - ½ ln(2πσb²),  0·ln 0 = 0.
+ * No floating-point atomics and no host round trip inside a step; every sum is taken in one fixed order.
+ *
+ * nhp_cont_latvb_step: one update.  S, R, Q, Z: the state on entry, the updated state on return (host pointers, or all four
+ * device pointers with output_on_device); with NHP_VB_FROM_MODEL the E-step runs at the model's current parameters and of the
+ * state on entry Z alone is read (Z is read in every mode).  stats [19 + J] (host): [0..10] as nhp_cont_netvb_step with KL_net as above in [5] and
+ * [10]; [11..14] the network pieces (Σ entropy of ρv, links, ln p(zv), ln p(bv)) of the state stepped from (0 with
+ * NHP_VB_FROM_MODEL), [15..18] of the state returned; [19..19+J-1] the rung each ascent iteration took (-1: it stayed).
+ * Synchronous; the model is not changed.
+ *
+ * nhp_cont_latvb_run: the whole iteration on the device; loop, stopping rule, trace, NHP_VB_RESUME (S, R, Q hold a state; Z always
+ * does) and empty-dataset handling are nhp_cont_vb_run's.  On return S, R, Q, Z hold state k, x its means and the device model
+ * holds them and A = (ρv > ½), as nhp_cont_netvb_run leaves them.
+ *
+ * Errors of both, before any launch: NHP_ENOTIMPL for an LGCP baseline, a column shard, a model without A, a block network
+ * attached; NHP_EINVAL for a missing argument, D outside 1..8, J outside 0..64, σ or σb not positive and finite, μb not finite,
+ * (host pointers) a non-finite position or offset, the NHP_VB_DENSE_NETWORK flag, and nhp_cont_netvb_step's checks of κ0, ν0, ρv,
+ * κv, νv.  Then NHP_EDOMAIN and NHP_ESHAPE as nhp_cont_vb_run.  nhp_cont_netvb_step / _run keep refusing a latent distance network. */
+nhp_status nhp_cont_latvb_step(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *model, int32_t flags,
+                               const nhp_gibbs_priors *priors, const double *net /* [2] */, const double *lat /* [3] */,
+                               int32_t n_dims, int32_t ascent_steps, double *S /* [len] */, double *R /* [len] */, int64_t len,
+                               double *Q /* [3*N*N] */, double *Z /* [N*D + 1] */, int32_t output_on_device,
+                               double *stats /* [19 + ascent_steps] */);
+nhp_status nhp_cont_latvb_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *model, int32_t flags,
+                              const nhp_gibbs_priors *priors, const double *net /* [2] */, const double *lat /* [3] */,
+                              int32_t n_dims, int32_t ascent_steps, double f_abstol, int32_t max_steps, double *x /* [len] */,
+                              double *S /* [len] */, double *R /* [len] */, int64_t len, double *Q /* [3*N*N] */,
+                              double *Z /* [N*D + 1] */, double *elbo, int32_t *steps, int32_t *converged,
+                              double *trace /* nullable, [max_steps + 1] */);
+/* The soft-link counterpart of nhp_latent_loglik: out [N·D + 2] = F(z, b) as above for the link probabilities rho [N*N]
+ * (column-major, each in [0, 1]), then ∇F in the layout of Z (N·D position entries, then ∂F/∂b).  Host pointers; synchronous.
+ * NHP_EINVAL for N < 1, D outside 1..8, a non-finite position or offset, priors that cannot be, a rho outside [0, 1]. */
+nhp_status nhp_latent_expected_loglik(nhp_ctx *ctx, const double *rho, int32_t n_nodes, int32_t n_dims, const double *z, double b,
+                                      const double *lat /* [3]: sigma, mu_b, sigma_b */, double *out /* [N*D + 2] */);
+
 /* Observed information and Hessian-vector products of the continuous log-likelihood (csrc/cont_information.hip).  The
  * objective nhp_cont_loglik evaluates separates by child node c, so its Hessian is block diagonal: one block per column
  * over the D = 1 + kinds·N parameters [λ0[c]; θ[:,c] | μ[:,c]; τ[:,c]; W[:,c]] (kinds = 2 exponential, 3 logit-normal), row and

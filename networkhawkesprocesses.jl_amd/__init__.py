@@ -32,7 +32,7 @@ from .inference import (ExpectedStatistics, Information, MarkovChainMonteCarlo, 
                         em_, expected_statistics, hessian_vector_product, logprior, observed_information,
                         resample_adjacency_matrix_, standard_errors,
                         ContinuousScore, score_samples, ChainQuantiles, ContinuousVariational, ContinuousNetworkVariational,
-                        ContinuousBlockNetworkVariational)
+                        ContinuousBlockNetworkVariational, ContinuousLatentNetworkVariational)
 from . import inference as _inf
 from . import synthetic  # noqa: F401
 from .synthetic import rand  # noqa: F401   rand(process, duration): the reference's exported simulator name
@@ -94,7 +94,8 @@ def vb_(process, data, *args, **kwargs):
     mean-field fit of inference.vb_continuous (a ContinuousVariational); for a continuous network process with
     SparseWeightModel weights and a Dense or Bernoulli network inference.vb_network_continuous (a
     ContinuousNetworkVariational with the link probabilities), and under a StochasticBlockNetworkModel with a variational state
-    (network.variational_init_()) a ContinuousBlockNetworkVariational with the labels and block tables as well."""
+    (network.variational_init_()) a ContinuousBlockNetworkVariational with the labels and block tables as well, under a
+    LatentDistanceNetworkModel with one a ContinuousLatentNetworkVariational with the fitted positions and offset."""
     if isinstance(process, ContinuousNetworkHawkesProcess):
         return _inf.vb_network_continuous(process, data, *args, **kwargs)
     if isinstance(process, ContinuousHawkesProcess):

@@ -110,6 +110,10 @@ def _declare(lib):
     f("nhp_cont_sbmvb_step", i32, _vp, _vp, _vp, i32, C.POINTER(GibbsPriors), _dp, _dp, i32, i32, i64, _vp, _vp, i64, _vp, _vp, i32, _dp)
     f("nhp_cont_sbmvb_run", i32, _vp, _vp, _vp, i32, C.POINTER(GibbsPriors), _dp, _dp, i32, i32, i64, dbl, i32, _dp, _dp, _dp, i64, _dp, _dp,
       C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp)
+    f("nhp_cont_latvb_step", i32, _vp, _vp, _vp, i32, C.POINTER(GibbsPriors), _dp, _dp, i32, i32, _vp, _vp, i64, _vp, _vp, i32, _dp)
+    f("nhp_cont_latvb_run", i32, _vp, _vp, _vp, i32, C.POINTER(GibbsPriors), _dp, _dp, i32, i32, dbl, i32, _dp, _dp, _dp, i64, _dp, _dp,
+      C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp)
+    f("nhp_latent_expected_loglik", i32, _vp, _dp, i32, i32, _dp, dbl, _dp, _dp)
     f("nhp_cont_information", i32, _vp, _vp, _vp, i32, C.POINTER(i32), i32, i32, i32, C.POINTER(C.c_double), _vp)
     f("nhp_cont_hessian_vec", i32, _vp, _vp, _vp, i32, i32, _vp, _vp, i64)
     f("nhp_disc_information", i32, _vp, _vp, _dp, _dp, _dp, dbl, i32, C.POINTER(i32), i32, i32, i32, C.POINTER(C.c_double), _vp)

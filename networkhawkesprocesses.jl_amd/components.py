@@ -572,6 +572,52 @@ class LatentDistanceNetworkModel(Network):
                   else np.array(z, dtype=np.float64).reshape((self.nnodes, self.ndims)))
         if not (np.all(np.isfinite(self.z)) and np.isfinite(self.b)):
             raise _lib.DomainError("positions and offset must be finite")
+        # the variational state: None until variational_init_ creates it
+        self.zv = self.bv = None
+        self.ascent_steps = 4
+
+    def variational_init_(self, seed=0, scale=0.1, ascent_steps=4):
+        """Create the variational state of update_ / vb_ on a continuous network process: the point estimate (zv, bv) the fit
+        moves, zv = the current z plus scale·N(0, I) (seeded), bv = b; `ascent_steps` (0..64) iterations of the ascent run per
+        step (0 holds the network fixed).  All positions equal is a saddle of the ascent -- the position gradient is -z/σ² and
+        nothing separates the nodes --, so scale = 0 with all rows of z equal is refused, and nothing creates this state
+        implicitly."""
+        if not (np.isfinite(scale) and scale >= 0.0):
+            raise ValueError("variational_init!: scale must be finite and >= 0")
+        if not 0 <= int(ascent_steps) <= 64:
+            raise ValueError("variational_init!: ascent_steps must lie in 0..64")
+        z = np.array(self.z, dtype=np.float64).reshape((self.nnodes, self.ndims))
+        if scale == 0.0 and self.nnodes > 1 and np.all(z == z[0]):
+            raise ValueError("variational_init!: scale = 0 with all positions equal is a saddle of the ascent, from which no "
+                             "step separates the nodes")
+        if scale > 0.0:
+            z = z + scale * np.random.default_rng(seed).standard_normal(z.shape)
+        self.zv, self.bv, self.ascent_steps = z, float(self.b), int(ascent_steps)
+        return self
+
+    def has_variational_state(self):
+        return getattr(self, "zv", None) is not None
+
+    def variational_params(self):
+        """Z = [vec(zv) column-major; bv]"""
+        return np.concatenate([np.asarray(self.zv, dtype=np.float64).ravel(order="F"), [float(self.bv)]])
+
+    def expected_loglikelihood(self, rho, gradient=False, ctx=None):
+        """F(z, b) = Σ rho·η - softplus(η) - ‖z‖²/(2σ²) - (b - μb)²/(2σb²) at the current (z, b) for link probabilities rho
+        (N x N, each in [0, 1]), from the GPU: the soft-link counterpart of loglikelihood plus the priors' quadratics, the
+        objective the variational fit climbs.  With `gradient` also (∂F/∂z [N x D], ∂F/∂b)."""
+        N, D = self.nnodes, self.ndims
+        rho = np.asarray(rho, dtype=np.float64)
+        if rho.shape != (N, N) or not np.all((rho >= 0.0) & (rho <= 1.0)):
+            raise ValueError("rho must be an N x N matrix of probabilities")
+        ctx = ctx or _lib.default_context()
+        out = np.empty(N * D + 2)
+        lat = np.array([self.σ, self.μb, self.σb], dtype=np.float64)
+        _lib.check(_lib.lib().nhp_latent_expected_loglik(ctx.h, _lib.dptr(_lib.colmajor(rho)), N, D, _lib.dptr(_lib.colmajor(self.z)),
+                                                         float(self.b), _lib.dptr(lat), _lib.dptr(out)), ctx.h)
+        if not gradient:
+            return float(out[0])
+        return float(out[0]), out[1:1 + N * D].reshape((N, D), order="F").copy(), float(out[-1])
 
     def params(self):
         return np.array([self.b])

@@ -17,7 +17,7 @@ for f in *.hip; do
   o=$BUILD/${f%.hip}.o
   stale=0
   [ -f "$o" ] || stale=1
-  for dep in "$f" nhp_internal.h nhp_math.h nhp_rng.h nhp_lbfgs.h nhp_dd.h nhp_sim.h nhp_dsim.h nhp_samp.h nhp_netvb.h nhp_disc_gemm.h nhp_vb_bump.h nhp_cnetvb.h nhp_vb.h nhp_vb_drive.h nhp_sbmvb.h nhp_sbmvb_dev.h nhp_csbmvb.h nhp_diag.h nhp_quant.h nhp_rho.h nhp_score.h ../../include/nhp.h; do [ "$dep" -nt "$o" ] && stale=1; done
+  for dep in "$f" nhp_internal.h nhp_math.h nhp_rng.h nhp_lbfgs.h nhp_dd.h nhp_sim.h nhp_dsim.h nhp_samp.h nhp_netvb.h nhp_disc_gemm.h nhp_vb_bump.h nhp_cnetvb.h nhp_vb.h nhp_vb_drive.h nhp_sbmvb.h nhp_sbmvb_dev.h nhp_csbmvb.h nhp_clatvb.h nhp_latvb_dev.h nhp_diag.h nhp_quant.h nhp_rho.h nhp_score.h ../../include/nhp.h; do [ "$dep" -nt "$o" ] && stale=1; done
   if [ $stale = 1 ]; then
     hipcc $FLAGS -c "$f" -o "$o" &
     pids+=($!)

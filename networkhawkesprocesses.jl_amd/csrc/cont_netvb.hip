@@ -16,8 +16,10 @@
 //
 // The block network's fit (further down) is the same pass with the link's own network term: both update kernels are one body,
 // cn_update_body<NET>.  The host side is nhp_vb_drive.h's step and run drivers, shared with cont_vb.hip; cn_fit and cb_fit tell
-// them what a state of either network fit is, how it is carved and which kernels run.
+// them what a state of either network fit is, how it is carved and which kernels run.  The latent distance network's fit (last)
+// is the third: cn_latent_net, cl_fit and the kernels of nhp_latvb_dev.h.
 #include "nhp_csbmvb.h"
+#include "nhp_latvb_dev.h"
 #include "nhp_sbmvb_dev.h"
 #include "nhp_vb_drive.h"
 
@@ -168,7 +170,17 @@ struct cn_block_net {
     }
 };
 
-// the coordinate-ascent update of both network fits: factors (S, R, Q) from the surrogate x, the gradient g at it and the
+// A latent distance network: the link's own η[p,c] = b - ‖z_p - z_c‖² at the (zv, bv) of the state stepped from
+// -- a point estimate, so E_q[log s(η)] - E_q[log(1 - s(η))] is η itself.  No dense branch either.
+struct cn_latent_net {
+    latvb_link lat;
+    __device__ __forceinline__ double rho(const cn_args &A, size_t N, size_t p, size_t c, double kv0, double nv0, double kv1, const cn_tab &t) const
+    {
+        return cn_rho(A, latvb_eta(lat, N, p, c), kv0, nv0, kv1, t);
+    }
+};
+
+// the coordinate-ascent update of the network fits: factors (S, R, Q) from the surrogate x, the gradient g at it and the
 // network term of `net`; their surrogate xn, their pieces
 template <class NET>
 __device__ __forceinline__ void cn_update_body(const cn_args &A, const double *__restrict__ x, const double *__restrict__ g, const NET &net,
@@ -209,6 +221,12 @@ __global__ __launch_bounds__(256) void k_csbmvb_update(cn_args A, const double *
                                                        double *__restrict__ xn, double *__restrict__ part)
 {
     cn_update_body(A, x, g, cn_block_net{blk}, S, R, Q, xn, part);
+}
+__global__ __launch_bounds__(256) void k_clatvb_update(cn_args A, const double *__restrict__ x, const double *__restrict__ g, latvb_link lat,
+                                                       double *__restrict__ S, double *__restrict__ R, double *__restrict__ Q,
+                                                       double *__restrict__ xn, double *__restrict__ part)
+{
+    cn_update_body(A, x, g, cn_latent_net{lat}, S, R, Q, xn, part);
 }
 
 // out = [Σ_i log λ̃_i = ll + fix, E_q[compensator], KL_λ0, KL_W, KL_imp, KL_net, L, 0]: the partial sums in one fixed order.
@@ -257,7 +275,7 @@ __global__ __launch_bounds__(256) void k_cnetvb_mean(vb_args a, const double *__
 
 // the refusals and argument errors of both entry points, before any launch
 nhp_status cn_check(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const nhp_gibbs_priors *pr, const double *net, bool dense,
-                    const char *what, bool block = false)
+                    const char *what, bool block = false, bool latent = false)
 {
     NHP_TRY(nhp_check_pair(ctx, ds, m));
     if (m->baseline_kind != NHP_BASELINE_HOMOGENEOUS) {
@@ -272,7 +290,11 @@ nhp_status cn_check(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_mod
         nhp_set_error(ctx, "%s: a latent distance network is attached to the model (the block-network fit needs none)", what);
         return NHP_ENOTIMPL;
     }
-    if (!block && (m->sbm || m->latent)) {
+    if (latent && m->sbm) {
+        nhp_set_error(ctx, "%s: a block network is attached to the model (the latent-distance-network fit needs none)", what);
+        return NHP_ENOTIMPL;
+    }
+    if (!block && !latent && (m->sbm || m->latent)) {
         nhp_set_error(ctx, "%s: a block or latent distance network is not implemented (dense and Bernoulli networks are)", what);
         return NHP_ENOTIMPL;
     }
@@ -282,7 +304,7 @@ nhp_status cn_check(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_mod
     }
     NHP_TRY(vb_check_priors(ctx, m, pr, what));
     char msg[200];
-    if (cnetvb_check_net(what, net, dense || block, msg, sizeof msg) != CNETVB_OK) { nhp_set_error(ctx, "%s", msg); return NHP_EINVAL; }
+    if (cnetvb_check_net(what, net, dense || block || latent, msg, sizeof msg) != CNETVB_OK) { nhp_set_error(ctx, "%s", msg); return NHP_EINVAL; }
     return NHP_OK;
 }
 
@@ -592,6 +614,208 @@ cb_fit cb_make_fit(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_mode
     return cb_fit{ctx, A, cb_make_args(m, sbm, K), nhp_layout(m).P, (size_t)m->N, (size_t)K, labels_every, step0, S, R, Q, B, cb_scratch{}};
 }
 
+// ---- the latent distance network (the definition is in include/nhp.h, nhp_cont_latvb_run) ------------------------
+// The Bernoulli fit with A[p,c] ~ Bernoulli(s(η[p,c])), η = b - ‖z_p - z_c‖²: the scalar of the logit becomes the link's own η at
+// the point estimate (zv, bv) of the state stepped from, and the network's Beta becomes Z = [vec zv; bv], moved by J iterations of
+// the monotone ascent of nhp_latvb_dev.h at the new ρv.
+
+struct cl_args {
+    int N, D, J;
+    latvb_prior pr;
+    double lnz_const, lnb_const;     // the normalising constants of ln p(z) and ln p(b): -(N·D/2) ln(2πσ²), -½ ln(2πσb²)
+    latvb_steps ladder, here;        // the rungs with the current point behind them; the current point alone
+};
+
+// a state on the device: cn_fit::state's (Q = the three planes alone), Z = [vec zv; bv] and lk = the per-node link sums at its own Z
+struct cl_state { double *x, *S, *R, *Q, *Z, *lk, *part; };
+// what both states share: C = ρv + ρvᵀ, G = ∇F, the per-node halves of ∂F/∂b, the per-node sums of every slot, the iteration's
+// scalars and the rungs the latest update took
+struct cl_scratch { double *C, *G, *hb, *lad, *sc, *rungs; };
+
+// out = k_cnetvb_elbo's eight, then [Σ entropy of ρv, links, ln p(zv), ln p(bv)], then the J rungs the update that made the state
+// took (-1: the point stayed; all -1 for a state the caller gave): the partial sums in one fixed order and the network pieces of
+// the state at its OWN (zv, bv),
+//   links = ½ Σ_n lk[n] = Σ_pc [ρv η - softplus(η)],  ln p(z) = -‖z‖²/(2σ²) - (N·D/2) ln(2πσ²),  ln p(b) = -(b - μb)²/(2σb²) - ½ ln(2πσb²),
+//   KL_net = Σ entropy - (links + ln p(z) + ln p(b)).
+// Thread i adds the entries i, i + 256, ... in increasing order and nhp_block_sum_n joins the threads in its fixed order.
+__global__ __launch_bounds__(256) void k_clatvb_elbo(cl_args c, int made_here, const double *__restrict__ ll, const double *__restrict__ part,
+                                                     const double *__restrict__ Z, const double *__restrict__ lk,
+                                                     const double *__restrict__ rungs, double *__restrict__ out)
+{
+    __shared__ double red[4];
+    __shared__ double tot[CNETVB_PIECES];
+    vb_sum_parts<CNETVB_PIECES>(part, tot, red);
+    const size_t ND = (size_t)c.N * c.D;
+    double links = 0.0, zz = 0.0;
+    for (int n = threadIdx.x; n < c.N; n += 256) links += lk[n];
+    links = nhp_block_sum_n<4>(links, red);
+    for (size_t i = threadIdx.x; i < ND; i += 256) zz += Z[i] * Z[i];
+    zz = nhp_block_sum_n<4>(zz, red);
+    if ((int)threadIdx.x < CLATVB_MAX_ASCENT)
+        out[8 + CLATVB_NET_PIECES + threadIdx.x] = (made_here && (int)threadIdx.x < c.J) ? rungs[threadIdx.x] : -1.0;
+    if (threadIdx.x == 0) {
+        links *= 0.5;
+        const double db = Z[ND] - c.pr.mu_b;
+        const double lnz = c.lnz_const - 0.5 * c.pr.inv_s2 * zz, lnb = c.lnb_const - 0.5 * c.pr.inv_sb2 * (db * db);
+        const double sl = *ll + tot[0];
+        const double klnet = tot[5] - ((links + lnz) + lnb);
+        out[0] = sl;
+        for (int j = 1; j < 5; ++j) out[j] = tot[j];
+        out[5] = klnet;
+        out[6] = ((((sl - tot[1]) - tot[2]) - tot[3]) - tot[4]) - klnet;
+        out[7] = 0.0;
+        out[8] = tot[5]; out[9] = links; out[10] = lnz; out[11] = lnb;
+    }
+}
+
+// the checks of the latent entry points before any launch: the flag and the pointers, cn_check's, then the latent model's own
+nhp_status cl_check(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int32_t flags, const nhp_gibbs_priors *pr, const double *net,
+                    const double *lat, int32_t D, int32_t J, const double *Z, bool Z_on_host, const char *what)
+{
+    const bool dense = (flags & NHP_VB_DENSE_NETWORK) != 0;
+    char msg[256];
+    // (the flag and the pointers first: cn_check reads net)
+    if (dense || !net || !lat) {
+        clatvb_check_args(what, m ? m->N : 0, net, lat, D, J, dense, nullptr, msg, sizeof msg);
+        nhp_set_error(ctx, "%s", msg);
+        return NHP_EINVAL;
+    }
+    NHP_TRY(cn_check(ctx, ds, m, pr, net, false, what, false, true));
+    if (clatvb_check_args(what, m->N, net, lat, D, J, false, Z, msg, sizeof msg, !Z_on_host) == CLATVB_OK) return NHP_OK;
+    nhp_set_error(ctx, "%s", msg);
+    return NHP_EINVAL;
+}
+
+nhp_status cl_check_state(nhp_ctx *ctx, const nhp_cont_model *m, bool state, const double *S, const double *R, const double *Q, const char *what)
+{
+    const nhp_layout L(m);
+    char msg[200];
+    if (clatvb_check_state(what, (size_t)m->N, state, Q, S + L.W, R + L.W, msg, sizeof msg) != CLATVB_OK) {
+        nhp_set_error(ctx, "%s", msg);
+        return NHP_EINVAL;
+    }
+    return NHP_OK;
+}
+
+cl_args cl_make_args(int32_t N, const double *lat, int32_t D, int32_t J)
+{
+    cl_args c{};
+    c.N = N; c.D = D; c.J = J;
+    c.pr = latvb_prior{1.0 / (lat[0] * lat[0]), lat[1], 1.0 / (lat[2] * lat[2])};
+    const double two_pi = 6.283185307179586476925;
+    c.lnz_const = -0.5 * (double)N * (double)D * std::log(two_pi * lat[0] * lat[0]);
+    c.lnb_const = -0.5 * std::log(two_pi * lat[2] * lat[2]);
+    c.ladder.n = CLATVB_SLOTS;
+    clatvb_ladder(N, lat[0], c.ladder.t);
+    c.here.n = 1;
+    return c;
+}
+
+inline dim3 cl_tiles(size_t N) { const unsigned t = (unsigned)((N + LATVB_TILE - 1) / LATVB_TILE); return dim3(t, t); }
+
+// lk of state s at its own (zv, bv): C from its ρv (unless `have_C`), then the ladder kernel at the point itself
+void cl_own_sums(hipStream_t st, const cl_args &c, const cl_state &s, const cl_scratch &w, bool have_C)
+{
+    const size_t N = (size_t)c.N;
+    if (!have_C) hipLaunchKernelGGL(k_latvb_sym, cl_tiles(N), dim3(256), 0, st, c.N, (const double *)(s.Q + 2 * N * N), w.C);
+    hipLaunchKernelGGL(k_latvb_ladder, dim3((unsigned)N), dim3(256), 0, st, c.N, c.D, c.here, (const double *)w.C, (const double *)s.Z,
+                       (const double *)nullptr, s.lk, 1);
+}
+
+// J iterations of the ascent of F at the ρv behind C, moving Z in place; rung j of w.rungs = the rung iteration j took
+void cl_ascent(hipStream_t st, const cl_args &c, const cl_scratch &w, double *Z)
+{
+    const size_t N = (size_t)c.N, nz = clatvb_z_doubles(N, (size_t)c.D);
+    for (int j = 0; j < c.J; ++j) {
+        hipLaunchKernelGGL(k_latvb_grad, dim3((unsigned)N), dim3(256), 0, st, c.N, c.D, c.pr.inv_s2, (const double *)w.C, (const double *)Z, w.G, w.hb);
+        hipLaunchKernelGGL(k_latvb_gb, dim3(1), dim3(256), 0, st, c.N, c.D, c.pr.mu_b, c.pr.inv_sb2, (const double *)Z, (const double *)w.hb, w.G);
+        hipLaunchKernelGGL(k_latvb_ladder, dim3((unsigned)N), dim3(256), 0, st, c.N, c.D, c.ladder, (const double *)w.C, (const double *)Z,
+                           (const double *)w.G, w.lad, CLATVB_SLOTS);
+        hipLaunchKernelGGL(k_latvb_finish, dim3(1), dim3(256), 0, st, c.N, c.D, c.ladder, c.pr, (const double *)w.lad, CLATVB_SLOTS,
+                           (const double *)Z, (const double *)w.G, w.sc, w.rungs + j);
+        hipLaunchKernelGGL(k_latvb_apply, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, st, nz, (const double *)w.sc, (const double *)w.G, Z);
+    }
+}
+
+// the latent fit for the drivers of nhp_vb_drive.h: S, R, Q, Z the caller's arrays
+struct cl_fit {
+    static constexpr int OUT = CLATVB_OUT, L_SLOT = 6, STAT_PIECES = 5, PLANES = 4;
+    static constexpr bool UNMASK = true;
+    using state = cl_state;
+    nhp_ctx *ctx;
+    cn_args A;
+    cl_args c;
+    size_t P, N, D;
+    double *S, *R, *Q, *Z;
+    cl_scratch w;
+
+    size_t reserve_doubles() const { return clatvb_reserve_doubles(P, N, D, VB_BLK); }
+    void carve(vb_bump &m, state &s) const
+    {
+        s.x = m.take(P); s.S = m.take(P); s.R = m.take(P); s.Q = m.take(3 * N * N);
+        s.Z = m.take(clatvb_z_doubles(N, D)); s.lk = m.take(N); s.part = m.take((size_t)CNETVB_PIECES * VB_BLK);
+    }
+    void carve_shared(vb_bump &m)
+    {
+        w.C = m.take(N * N); w.G = m.take(clatvb_z_doubles(N, D)); w.hb = m.take(N); w.lad = m.take(N * (size_t)CLATVB_SLOTS);
+        w.sc = m.take(CLATVB_SC); w.rungs = m.take(CLATVB_MAX_ASCENT);
+    }
+    void place_step(state &, state &, bool) const {}
+    void planes(const state &s, vb_plane *pl) const
+    {
+        pl[0] = {S, s.S, P, false}; pl[1] = {R, s.R, P, false}; pl[2] = {Q, s.Q, 3 * N * N, false}; pl[3] = {Z, s.Z, clatvb_z_doubles(N, D), true};
+    }
+    void start(hipStream_t st, const double *xin, const state &s) const
+    {
+        hipLaunchKernelGGL(k_cnetvb_start, dim3(VB_BLK), dim3(256), 0, st, A, xin, s.x, s.part);
+        (void)hipMemsetAsync(s.lk, 0, 8 * N, st);                     // (no state: of its evaluation Σ log λ̃ alone is used; errors: the driver's)
+    }
+    void surrogate(hipStream_t st, const state &s) const
+    {
+        hipLaunchKernelGGL(k_cnetvb_surrogate, dim3(VB_BLK), dim3(256), 0, st, A, (const double *)s.S, (const double *)s.R, s.Q, s.x, s.part);
+        cl_own_sums(st, c, s, w, false);
+    }
+    void elbo(hipStream_t st, const state &s, bool made_here, double *out) const
+    {
+        hipLaunchKernelGGL(k_clatvb_elbo, dim3(1), dim3(256), 0, st, c, made_here ? 1 : 0, (const double *)ctx->d_results, (const double *)s.part,
+                           (const double *)s.Z, (const double *)s.lk, (const double *)w.rungs, out);
+    }
+    // the O(P) pass with η from the OLD (zv, bv), C from the NEW ρv, the ascent on a copy of the old Z, the new state's own sums
+    nhp_status update(nhp_ctx *cx, hipStream_t st, const state &cur, const state &nxt, const double *g, int) const
+    {
+        hipLaunchKernelGGL(k_clatvb_update, dim3(VB_BLK), dim3(256), 0, st, A, (const double *)cur.x, g, latvb_link{c.D, cur.Z}, nxt.S, nxt.R,
+                           nxt.Q, nxt.x, nxt.part);
+        hipLaunchKernelGGL(k_latvb_sym, cl_tiles(N), dim3(256), 0, st, c.N, (const double *)(nxt.Q + 2 * N * N), w.C);
+        NHP_HIP(cx, hipMemcpyAsync(nxt.Z, cur.Z, 8 * clatvb_z_doubles(N, D), hipMemcpyDeviceToDevice, st));
+        cl_ascent(st, c, w, nxt.Z);
+        cl_own_sums(st, c, nxt, w, true);
+        NHP_HIP(cx, hipGetLastError());
+        return NHP_OK;
+    }
+    void mean(hipStream_t st, const state &s, double *x, nhp_cont_model *m) const
+    {
+        hipLaunchKernelGGL(k_cnetvb_mean, dim3(VB_BLK), dim3(256), 0, st, A.v, (const double *)s.S, (const double *)s.R,
+                           (const double *)(s.Q + 2 * N * N), x, m->d_A);
+    }
+    void stats(const double *h, bool from_model, double *out) const
+    {
+        vb_fill_stats(h, OUT, STAT_PIECES, from_model, out);
+        for (int j = 0; j < CLATVB_NET_PIECES; ++j) {
+            out[11 + j] = from_model ? 0.0 : h[8 + j];
+            out[11 + CLATVB_NET_PIECES + j] = h[OUT + 8 + j];
+        }
+        for (int j = 0; j < c.J; ++j) out[CLATVB_STATS_FIXED + j] = h[OUT + 8 + CLATVB_NET_PIECES + j];
+    }
+};
+
+cl_fit cl_make_fit(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, const nhp_gibbs_priors *pr, const double *net,
+                   const double *lat, int32_t D, int32_t J, double *S, double *R, double *Q, double *Z)
+{
+    cn_args A = cn_make_args(ds, m, pr, net, true);                  // (net = [κ0, ν0] alone: the Beta's slots stay 0 and unread)
+    A.dense = 0;
+    return cl_fit{ctx, A, cl_make_args(m->N, lat, D, J), nhp_layout(m).P, (size_t)m->N, (size_t)D, S, R, Q, Z, cl_scratch{}};
+}
+
 constexpr int32_t CN_MODE_FLAGS = NHP_VB_FROM_MODEL | NHP_VB_RESUME | NHP_VB_DENSE_NETWORK;     // not the E-step's
 
 }   // namespace
@@ -651,3 +875,81 @@ extern "C" nhp_status nhp_cont_sbmvb_run(nhp_ctx *ctx, const nhp_cont_dataset *d
     return vb_run_drive(ctx, ds, m, flags & ~CN_MODE_FLAGS, f, resume, f_abstol, max_steps, x, elbo, steps_out, converged_out, trace);
 }
 
+
+extern "C" nhp_status nhp_cont_latvb_step(nhp_ctx *ctx, const nhp_cont_dataset *ds, const nhp_cont_model *m, int32_t flags,
+                                          const nhp_gibbs_priors *priors, const double *net, const double *lat, int32_t n_dims,
+                                          int32_t ascent_steps, double *S, double *R, int64_t len, double *Q, double *Z,
+                                          int32_t output_on_device, double *stats)
+{
+    if (!ctx || !ds || !m || !priors || !S || !R || !Q || !stats) return NHP_EINVAL;     // (net, lat, Z: cl_check's, with a message)
+    const bool from_model = (flags & NHP_VB_FROM_MODEL) != 0;
+    NHP_TRY(cl_check(ctx, ds, m, flags, priors, net, lat, n_dims, ascent_steps, Z, !output_on_device, "update!"));
+    NHP_TRY(nhp_layout_check(ctx, nhp_layout(m), len));
+    if (!output_on_device) NHP_TRY(cl_check_state(ctx, m, !from_model, S, R, Q, "update!"));
+    cl_fit f = cl_make_fit(ctx, ds, m, priors, net, lat, n_dims, ascent_steps, S, R, Q, Z);
+    return vb_step_drive(ctx, ds, m, flags & ~CN_MODE_FLAGS, f, from_model, output_on_device != 0, stats);
+}
+
+extern "C" nhp_status nhp_cont_latvb_run(nhp_ctx *ctx, const nhp_cont_dataset *ds, nhp_cont_model *m, int32_t flags,
+                                         const nhp_gibbs_priors *priors, const double *net, const double *lat, int32_t n_dims,
+                                         int32_t ascent_steps, double f_abstol, int32_t max_steps, double *x, double *S, double *R, int64_t len,
+                                         double *Q, double *Z, double *elbo, int32_t *steps_out, int32_t *converged_out, double *trace)
+{
+    if (!ctx || !ds || !m || !priors || !x || !S || !R || !Q || !elbo || !steps_out || !converged_out) return NHP_EINVAL;
+    const bool resume = (flags & NHP_VB_RESUME) != 0;
+    NHP_TRY(cl_check(ctx, ds, m, flags, priors, net, lat, n_dims, ascent_steps, Z, true, "vb!"));
+    NHP_TRY(vb_run_args(ctx, m, resume, max_steps, len));
+    NHP_TRY(cl_check_state(ctx, m, resume, S, R, Q, "vb!"));
+    cl_fit f = cl_make_fit(ctx, ds, m, priors, net, lat, n_dims, ascent_steps, S, R, Q, Z);
+    return vb_run_drive(ctx, ds, m, flags & ~CN_MODE_FLAGS, f, resume, f_abstol, max_steps, x, elbo, steps_out, converged_out, trace);
+}
+
+extern "C" nhp_status nhp_latent_expected_loglik(nhp_ctx *ctx, const double *rho, int32_t N, int32_t D, const double *z, double b, const double *lat,
+                                                 double *out)
+{
+    if (!ctx || !rho || !z || !lat || !out) return NHP_EINVAL;
+    if (N < 1) { nhp_set_error(ctx, "latent_expected_loglik: n_nodes = %d must be positive", N); return NHP_EINVAL; }
+    const double spike[2] = {1.0, 1.0};
+    char msg[256];
+    if (D >= 1 && D <= CLATVB_MAX_DIMS) {                            // (z, b) as a host Z for the shared check
+        std::vector<double> Zh((size_t)N * D + 1);
+        std::copy(z, z + (size_t)N * D, Zh.begin());
+        Zh.back() = b;
+        if (clatvb_check_args("latent_expected_loglik", N, spike, lat, D, 0, false, Zh.data(), msg, sizeof msg) != CLATVB_OK) {
+            nhp_set_error(ctx, "%s", msg);
+            return NHP_EINVAL;
+        }
+    } else {
+        clatvb_check_args("latent_expected_loglik", N, spike, lat, D, 0, false, z, msg, sizeof msg);
+        nhp_set_error(ctx, "%s", msg);
+        return NHP_EINVAL;
+    }
+    const size_t n = (size_t)N, NN = n * n, nz = clatvb_z_doubles(n, (size_t)D);
+    for (size_t i = 0; i < NN; ++i)
+        if (!(rho[i] >= 0.0 && rho[i] <= 1.0)) {
+            nhp_set_error(ctx, "latent_expected_loglik: rho at link %zu = %g is outside [0, 1]", i, rho[i]);
+            return NHP_EINVAL;
+        }
+    NHP_HIP(ctx, hipSetDevice(ctx->device));
+    NHP_TRY(nhp_check_deferred(ctx));
+    NHP_TRY(nhp_ctx_reserve_scratch(ctx, 8 * clatvb_loglik_doubles(n, (size_t)D)));
+    vb_bump mem((double *)ctx->d_scratch);
+    double *d_rho = mem.take(NN), *C = mem.take(NN), *Z = mem.take(nz), *G = mem.take(nz), *hb = mem.take(n), *lk = mem.take(n);
+    double *sc = mem.take(CLATVB_SC), *d_out = mem.take(nz + 1);
+    hipStream_t st = ctx->main();
+    const cl_args c = cl_make_args(N, lat, D, 0);
+    NHP_HIP(ctx, hipMemcpyAsync(d_rho, rho, 8 * NN, hipMemcpyHostToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(Z, z, 8 * (nz - 1), hipMemcpyHostToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(Z + nz - 1, &b, 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_latvb_sym, cl_tiles(n), dim3(256), 0, st, N, (const double *)d_rho, C);
+    hipLaunchKernelGGL(k_latvb_grad, dim3((unsigned)n), dim3(256), 0, st, N, D, c.pr.inv_s2, (const double *)C, (const double *)Z, G, hb);
+    hipLaunchKernelGGL(k_latvb_gb, dim3(1), dim3(256), 0, st, N, D, c.pr.mu_b, c.pr.inv_sb2, (const double *)Z, (const double *)hb, G);
+    hipLaunchKernelGGL(k_latvb_ladder, dim3((unsigned)n), dim3(256), 0, st, N, D, c.here, (const double *)C, (const double *)Z, (const double *)nullptr,
+                       lk, 1);
+    hipLaunchKernelGGL(k_latvb_finish, dim3(1), dim3(256), 0, st, N, D, c.here, c.pr, (const double *)lk, 1, (const double *)Z, (const double *)nullptr, sc,
+                       (double *)nullptr);
+    NHP_HIP(ctx, hipGetLastError());
+    NHP_HIP(ctx, hipMemcpyAsync(d_out, sc + 2, 8, hipMemcpyDeviceToDevice, st));
+    NHP_HIP(ctx, hipMemcpyAsync(d_out + 1, G, 8 * nz, hipMemcpyDeviceToDevice, st));
+    return nhp_download(ctx, out, d_out, 8 * (nz + 1));              // (waits for the stream: `b` is a stack value)
+}

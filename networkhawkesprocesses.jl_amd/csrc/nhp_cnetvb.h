@@ -59,6 +59,21 @@ inline int cnetvb_check_state(const char *what, size_t N, bool dense, bool state
     return CNETVB_OK;
 }
 
+// Q = [κv0 (N²); νv0 (N²); ρv (N²)] with no network pair behind the planes (the block and the latent distance fits, whose network
+// state travels in an array of its own): the table checks above, and ρv inside [0, 1]
+inline int cnetvb_check_planes(const char *what, size_t N, bool state, const double *Q, const double *kv1, const double *nv1, char *msg, size_t cap)
+{
+    if (cnetvb_check_state(what, N, true, state, Q, kv1, nv1, msg, cap) != CNETVB_OK) return CNETVB_EINVAL;
+    if (!state) return CNETVB_OK;
+    const size_t NN = N * N;
+    for (size_t i = 0; i < NN; ++i)
+        if (!(Q[2 * NN + i] >= 0.0 && Q[2 * NN + i] <= 1.0)) {
+            snprintf(msg, cap, "%s: rho_v at link %zu = %g is outside [0, 1]", what, i, Q[2 * NN + i]);
+            return CNETVB_EINVAL;
+        }
+    return CNETVB_OK;
+}
+
 // (vb_bump, which the drivers carve with and compare against the *_reserve_doubles below: nhp_vb_bump.h)
 
 // the standard fit (cont_vb.hip): a state is its surrogate, S, R (P each) and the partial sums of its pieces; a step or a run

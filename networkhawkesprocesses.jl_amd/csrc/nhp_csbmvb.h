@@ -48,18 +48,10 @@ inline int csbmvb_check_args(const char *what, int64_t N, const double *net, con
 }
 
 // Q = [κv0 (N²); νv0 (N²); ρv (N²)] in host memory, read where a state is (a step from a state, a resumed run) together with
-// the slab's (kv1, nv1): cnetvb_check_state's table checks, and ρv inside [0, 1]
+// the slab's (kv1, nv1): cnetvb_check_planes
 inline int csbmvb_check_state(const char *what, size_t N, bool state, const double *Q, const double *kv1, const double *nv1, char *msg, size_t cap)
 {
-    if (cnetvb_check_state(what, N, true, state, Q, kv1, nv1, msg, cap) != CNETVB_OK) return CSBMVB_EINVAL;
-    if (!state) return CSBMVB_OK;
-    const size_t NN = N * N;
-    for (size_t i = 0; i < NN; ++i)
-        if (!(Q[2 * NN + i] >= 0.0 && Q[2 * NN + i] <= 1.0)) {
-            snprintf(msg, cap, "%s: rho_v at link %zu = %g is outside [0, 1]", what, i, Q[2 * NN + i]);
-            return CSBMVB_EINVAL;
-        }
-    return CSBMVB_OK;
+    return cnetvb_check_planes(what, N, state, Q, kv1, nv1, msg, cap) == CNETVB_OK ? CSBMVB_OK : CSBMVB_EINVAL;
 }
 
 // doubles of one device state: surrogate, S, R (P each), Q's three planes, B, T and the partial sums of its pieces

@@ -399,8 +399,9 @@ def _vb_state(process, init, P):
 # lead: the C arguments between the priors and the state; arrays(init, what) -> ([S, R, ...] as the entry takes them -- the state
 # of `init`, or what a start without one reads --, step0 or None: the block fit's last lead argument); guess(): the default
 # guess in device order; result(arrays, step0, taken, **kw) and write_back(x, res): the fit's result class and the overwrite
-# of the process; npieces: ELBO pieces per state in stats (a block fit's network pieces follow them).
-_VBFit = collections.namedtuple("_VBFit", "entry pr P flags lead nstats npieces arrays guess result write_back")
+# of the process; npieces: ELBO pieces per state in stats (a block or latent fit's netpieces network pieces per state follow them,
+# and with `rungs` the rung of every ascent iteration of a latent fit those).
+_VBFit = collections.namedtuple("_VBFit", "entry pr P flags lead nstats npieces arrays guess result write_back netpieces rungs", defaults=(5, False))
 
 
 def _vb_step(process, data, fit, init, recursive, ctx):
@@ -427,7 +428,10 @@ def _vb_step(process, data, fit, init, recursive, ctx):
     res = fit.result(arrays, step0, 1, elbo=float(elbo), steps=1, elapsed=time.time() - start)
     res.pieces = {"loglam": float(stats[0]), "before": tuple(stats[1:1 + n]), "after": tuple(stats[1 + n:1 + 2 * n])}
     if fit.nstats > 1 + 2 * n:
-        res.pieces.update(network_before=tuple(stats[11:16]), network_after=tuple(stats[16:21]))
+        m = fit.netpieces
+        res.pieces.update(network_before=tuple(stats[11:11 + m]), network_after=tuple(stats[11 + m:11 + 2 * m]))
+        if fit.rungs:
+            res.pieces["rungs"] = tuple(int(v) for v in stats[11 + 2 * m:])
     return res
 
 
@@ -555,7 +559,8 @@ class ContinuousNetworkVariational(ContinuousVariational):
 
 def _netvb_check(process, data, what):
     """The argument errors of the network fit, raised before any device work; returns (priors, net [κ0, ν0, α, β], dense)."""
-    from .components import BernoulliNetworkModel, DenseNetworkModel, SparseWeightModel, StochasticBlockNetworkModel
+    from .components import (BernoulliNetworkModel, DenseNetworkModel, LatentDistanceNetworkModel, SparseWeightModel,
+                             StochasticBlockNetworkModel)
     from .sharded import ShardedDataset
     if not isinstance(process.weights, SparseWeightModel):
         raise TypeError(f"{what} on a ContinuousNetworkHawkesProcess needs a SparseWeightModel (spike and slab); with other weights "
@@ -566,9 +571,15 @@ def _netvb_check(process, data, what):
             raise NotImplementedError(f"{what}: the network (StochasticBlockNetworkModel) has no variational state: mean-field "
                                       "over labels cannot leave the uniform state, so none is created implicitly -- call "
                                       "network.variational_init_() first")
+    elif isinstance(process.network, LatentDistanceNetworkModel):
+        if not process.network.has_variational_state():
+            raise NotImplementedError(f"{what}: the network (LatentDistanceNetworkModel) has no variational state: with all "
+                                      "positions equal the ascent is at a saddle, so none is created implicitly -- call "
+                                      "network.variational_init_() first")
     elif not isinstance(process.network, (BernoulliNetworkModel, DenseNetworkModel)):
         raise NotImplementedError(f"{what}: a {type(process.network).__name__} is not implemented for continuous processes "
-                                  f"(DenseNetworkModel, BernoulliNetworkModel and StochasticBlockNetworkModel are)")
+                                  f"(DenseNetworkModel, BernoulliNetworkModel, StochasticBlockNetworkModel and "
+                                  f"LatentDistanceNetworkModel are)")
     if not isinstance(process.baseline, HomogeneousProcess):
         raise NotImplementedError(f"{what}: the update of a LogGaussianCoxProcess baseline has no closed form")
     if isinstance(data, ShardedDataset):
@@ -581,12 +592,18 @@ def _netvb_check(process, data, what):
     else:
         pr = _lib.GibbsPriors(b.α0, b.β0, w.κ1, w.ν1, imp.α0, imp.β0, imp.μμ, imp.κμ)
     values = _prior_values(pr, imp) + [("kappa0", w.κ0), ("nu0", w.ν0)]
+    latent = isinstance(net, LatentDistanceNetworkModel)
     if block:
         values += [("network alpha", net.α), ("network beta", net.β), ("network gamma", net.γ)]
+    elif latent:
+        values += [("network sigma", net.σ), ("network sigma_b", net.σb)]
     elif not dense:
         values += [("network alpha", net.α), ("network beta", net.β), ("network alpha_v", net.αv), ("network beta_v", net.βv)]
     _hyper_check(what, "hyper-parameter", values, pr.mu_mu)
-    netp = np.array([w.κ0, w.ν0, 1.0 if dense or block else net.α, 1.0 if dense or block else net.β], dtype=np.float64)
+    if latent:
+        _latvb_check(process, what)
+    plain = dense or block or latent
+    netp = np.array([w.κ0, w.ν0, 1.0 if plain else net.α, 1.0 if plain else net.β], dtype=np.float64)
     return pr, netp, dense
 
 
@@ -598,7 +615,7 @@ def _netvb_start_Q(process, dense):
     rho = net.link_probability() if w.ρv is None else np.asarray(w.ρv, dtype=np.float64)
     if rho.shape != (N, N) or not np.all((rho >= 0.0) & (rho <= 1.0)):
         raise ValueError("weights.ρv must be an N x N matrix of probabilities")
-    if _is_block(process):                                          # (the block state travels in B)
+    if _is_block(process) or _is_latent(process):                   # (the block state travels in B, the latent one in Z)
         return np.concatenate([np.ones(2 * N * N), rho.ravel(order="F")])
     return np.concatenate([np.ones(2 * N * N), rho.ravel(order="F"), [1.0 if dense else net.αv, 1.0 if dense else net.βv]])
 
@@ -621,7 +638,8 @@ def _network_guess(process):
 
 
 def _network_fit(process, pr, netp, dense):
-    """The fit of a network process for _vb_step / _vb_run: a Dense or Bernoulli network, or a block network."""
+    """The fit of a network process for _vb_step / _vb_run: a Dense or Bernoulli network, a block network or a
+    latent distance network."""
     P, kind, N = _device_length(process), _vb_kind_of(process), process.ndims()
 
     def write_back(x, res):
@@ -634,6 +652,15 @@ def _network_fit(process, pr, netp, dense):
         lead = (_lib.dptr(netp), _lib.dptr(_sbmvb_priors(process)), net.nblocks, int(net.labels_every))
         return _VBFit("sbmvb", pr, P, 0, lead, 21, 5, lambda init, what: _sbmvb_inputs(process, init, P, what), lambda: _network_guess(process),
                       result, write_back)
+    if _is_latent(process):
+        net = process.network
+        D, J = net.ndims, int(net.ascent_steps)
+
+        def result(arrays, step0, taken, **kw):
+            return ContinuousLatentNetworkVariational(kind, N, *arrays, D, pr.kappa, J, **kw)
+        lead = (_lib.dptr(netp), _lib.dptr(_latvb_priors(process)), D, J)
+        return _VBFit("latvb", pr, P, 0, lead, 19 + J, 5, lambda init, what: _latvb_inputs(process, init, P, what), lambda: _network_guess(process),
+                      result, write_back, 4, True)
 
     def arrays(init, what):
         if init is None:
@@ -653,7 +680,8 @@ def vb_step_network_continuous(process, data, init=None, recursive=True, ctx=Non
     `pieces` (see the class); `elbo` is that of the state stepped from (NaN for init=None).  The process is not changed.
 
     Under a block network (nhp_cont_sbmvb_step): the step numbered init.vb_step + 1, or network.vb_step + 1 without a state;
-    a ContinuousBlockNetworkVariational, and the network is not changed either."""
+    a ContinuousBlockNetworkVariational, and the network is not changed either.  Under a latent distance network
+    (nhp_cont_latvb_step): a ContinuousLatentNetworkVariational, from init's (zv, bv) or the network's."""
     return _vb_step(process, data, _network_fit(process, *_netvb_check(process, data, "update!")), init, recursive, ctx)
 
 
@@ -668,7 +696,10 @@ def _netvb_write_back(process, x, res):
     w.κv0, w.νv0, w.κv1, w.νv1, w.ρv = res.kappa0.copy(), res.nu0.copy(), res.kappa.copy(), res.nu.copy(), res.rho.copy()
     w.κv, w.νv = w.κv1, w.νv1
     process.adjacency_matrix = (res.rho > 0.5).astype(np.float64)
-    if isinstance(res, ContinuousBlockNetworkVariational):
+    if isinstance(res, ContinuousLatentNetworkVariational):
+        net.zv, net.bv = res.positions(), res.offset()
+        net.z, net.b = net.zv.copy(), net.bv
+    elif isinstance(res, ContinuousBlockNetworkVariational):
         net.mv, net.αv, net.βv, net.γv = res.mv.copy(), res.alpha_v.copy(), res.beta_v.copy(), res.gamma_v.copy()
         net.ρ, net.π, net.z = res.block_link_probability(), net.γv / net.γv.sum(), res.labels()
         net.vb_step = res.vb_step
@@ -691,7 +722,11 @@ def vb_network_continuous(process, data, max_steps=1000, f_abstol=1e-6, guess=No
     Under a block network (nhp_cont_sbmvb_run) the block state starts from the network's (variational_init_) or from `init`;
     the sweep over the labels runs at the steps whose number since variational_init_ is a multiple of network.labels_every.
     In addition network.mv, αv, βv, γv hold the state, network.ρ = αv/(αv + βv), network.π = γv/Σγv, network.z = labels() and
-    network.vb_step advances by the steps taken."""
+    network.vb_step advances by the steps taken.
+
+    Under a latent distance network (nhp_cont_latvb_run) the point estimate (zv, bv) starts from the network's
+    (variational_init_) or from `init`; every step runs network.ascent_steps iterations of the ascent.  In addition
+    network.zv, network.bv hold the state and network.z, network.b are set to them."""
     fit = _network_fit(process, *_netvb_check(process, data, "vb!"))
     return _vb_run(process, data, fit, max_steps, f_abstol, guess, recursive, init, keep_trace, verbose, ctx)
 
@@ -762,6 +797,90 @@ def _sbmvb_inputs(process, init, P, what):
 def _sbmvb_priors(process):
     net = process.network
     return np.array([net.α, net.β, net.γ], dtype=np.float64)
+
+
+# ---- ... under a latent distance network (csrc/cont_netvb.hip, csrc/nhp_latvb_dev.h) -------------------------
+
+def _is_latent(process):
+    from .components import LatentDistanceNetworkModel
+    return isinstance(process.network, LatentDistanceNetworkModel)
+
+
+class ContinuousLatentNetworkVariational(ContinuousNetworkVariational):
+    """The variational posterior of a continuous network process under a LatentDistanceNetworkModel (definition:
+    include/nhp.h, nhp_cont_latvb_run).  ContinuousNetworkVariational's factors -- Q holds the three planes [κv0; νv0; ρv] -- and
+    the network's point estimate (zv, bv), kept in `Z` = [vec zv; bv] (LatentDistanceNetworkModel.variational_params()):
+    variational EM over the positions and the offset.  `ascent_steps` iterations of the ascent ran per step.  `pieces`, where a
+    single step returned them: ContinuousNetworkVariational's, "network_before" / "network_after" = (Σ entropy of ρv, links,
+    ln p(zv), ln p(bv)) with KL_net = entropy - (links + ln p(zv) + ln p(bv)), and "rungs" = the rung of the ladder each ascent
+    iteration took (-1: it stayed).  There is no Beta: net_alpha, net_beta are None."""
+
+    def __init__(self, kind, N, S, R, Q, Z, ndims, prior_kappa=0.0, ascent_steps=4, **kw):
+        ContinuousVariational.__init__(self, kind, N, S, R, prior_kappa, **kw)
+        N, D = self.N, int(ndims)
+        self.Q, self.Z = np.array(Q, dtype=np.float64), np.array(Z, dtype=np.float64)
+        if self.Q.shape != (3 * N * N,):
+            raise ValueError("Q must hold 3·N² numbers: [κv0; νv0; ρv]")
+        if D < 1 or D > 8 or self.Z.shape != (N * D + 1,):
+            raise ValueError("Z must hold N·D + 1 numbers, D in 1..8: [vec zv; bv]")
+        if not 0 <= int(ascent_steps) <= 64:
+            raise ValueError("ascent_steps must lie in 0..64")
+        self.ndims, self.ascent_steps, self.dense = D, int(ascent_steps), False
+
+    net_alpha = property(lambda self: None)
+    net_beta = property(lambda self: None)
+
+    def positions(self):
+        """zv (N x D)."""
+        return self.Z[:-1].reshape((self.N, self.ndims), order="F").copy()
+
+    def offset(self):
+        """bv."""
+        return float(self.Z[-1])
+
+    def network_link_probability(self):
+        """s(η[p, c]) at (zv, bv), η = bv - ‖zv_p - zv_c‖²: the network's own link probabilities (link_probability() is ρv)."""
+        z = self.positions()
+        diff = z[:, None, :] - z[None, :, :]
+        with np.errstate(over="ignore"):
+            return 1.0 / (1.0 + np.exp(np.sum(diff * diff, axis=2) - self.offset()))
+
+
+def _latvb_check(process, what):
+    """The latent network's own argument errors: μb finite, the state's shape, finite entries, ascent_steps in 0..64."""
+    net, N = process.network, process.ndims()
+    if not math.isfinite(float(net.μb)):
+        raise ValueError(f"{what}: the network's mu_b = {net.μb} must be finite")
+    if net.nnodes != N:
+        raise ValueError(f"{what}: the network has {net.nnodes} nodes, the process {N}")
+    if not 1 <= int(net.ndims) <= 8:
+        raise ValueError(f"{what}: network.ndims = {net.ndims} must lie in 1..8")
+    if not 0 <= int(net.ascent_steps) <= 64:
+        raise ValueError(f"{what}: network.ascent_steps = {net.ascent_steps} must lie in 0..64")
+    if np.shape(net.zv) != (N, net.ndims):
+        raise ValueError(f"{what}: network.zv must have shape {(N, net.ndims)}")
+    if not (np.all(np.isfinite(net.zv)) and math.isfinite(float(net.bv))):
+        raise ValueError(f"{what}: network.zv and network.bv must be finite")
+
+
+def _latvb_inputs(process, init, P, what):
+    """([S, R, Q, Z], None) of a call: the state of `init`, or without one the network's own (zv, bv)."""
+    net, N = process.network, process.ndims()
+    if init is not None:
+        if not isinstance(init, ContinuousLatentNetworkVariational):
+            raise TypeError("init must be a ContinuousLatentNetworkVariational (the result of an earlier vb_ or update_ of this process)")
+        if init.kind != _vb_kind_of(process) or init.S.shape != (P,) or init.ndims != net.ndims:
+            raise ValueError("Parameter vector length does not match model parameter length.")
+        if not np.all(np.isfinite(init.Z)):
+            raise ValueError(f"{what}: the state's zv and bv must be finite")
+        return [init.S.copy(), init.R.copy(), init.Q.copy(), init.Z.copy()], None
+    Z = np.ascontiguousarray(net.variational_params(), dtype=np.float64)
+    return [np.empty(P), np.empty(P), _netvb_start_Q(process, False), Z], None
+
+
+def _latvb_priors(process):
+    net = process.network
+    return np.array([net.σ, net.μb, net.σb], dtype=np.float64)
 
 
 # ---- observed information, Hessian-vector products, standard errors ------------------------------------------------------

@@ -803,6 +803,92 @@ function block_update!(p::NHP.ContinuousNetworkHawkesProcess, data, sbm, n_block
     (S=S, R=R, Q=Q, B=Bv, stats=stats)
 end
 
+# ... under a LATENT DISTANCE network (nhp_cont_latvb_run / nhp_cont_latvb_step; the definition is in include/nhp.h).  The reference
+# package has no latent distance model type either, so the caller passes the priors lat = (σ, μb, σb), the positions z (N x D, rows
+# not all equal: equal positions are a saddle of the ascent) and the offset b; Z = [vec z; b].  Q holds the three planes
+# [κv0; νv0; ρv] (3N²).  latent_vb! returns (S, R, Q, Z, rho, z, b, elbo, trace, steps, status, elapsed) and overwrites the process
+# as vb! does (p.network is not touched); latent_update! is one step and returns (S, R, Q, Z, stats) with the 19 + ascent_steps
+# numbers of nhp_cont_latvb_step; the process is not changed.  latent_expected_loglik is nhp_latent_expected_loglik: (F, ∇F).
+function latvb_setup(p::NHP.ContinuousNetworkHawkesProcess, what, lat, z, b, ascent_steps)
+    p.weights isa NHP.SparseWeightModel || throw(ArgumentError("$what on a ContinuousNetworkHawkesProcess needs a SparseWeightModel"))
+    p.baseline isa NHP.HomogeneousProcess || error("$what: the update of a LogGaussianCoxProcess baseline has no closed form")
+    w, imp, bl = p.weights, p.impulses, p.baseline
+    pri = imp isa NHP.ExponentialImpulseResponse ? Priors(bl.α0, bl.β0, w.κ1, w.ν1, imp.α, imp.β, 0.0, 1.0) :
+                                                   Priors(bl.α0, bl.β0, w.κ1, w.ν1, imp.α0, imp.β0, imp.μμ, imp.κμ)
+    N = NHP.ndims(p)
+    P = N + N * N * (imp isa NHP.ExponentialImpulseResponse ? 2 : 3)
+    size(z, 1) == N || error("$what: z must have one row per node")
+    D = size(z, 2)
+    1 <= D <= 8 || error("$what: the latent dimension must lie in 1..8")
+    0 <= ascent_steps <= 64 || error("$what: ascent_steps must lie in 0..64")
+    length(lat) == 3 || error("$what: lat = (σ, μb, σb)")
+    pri, Float64[w.κ0, w.ν0], Float64[lat...], N, P, D, vcat(vec(Matrix{Float64}(z)), Float64(b))
+end
+
+function latent_vb!(p::NHP.ContinuousNetworkHawkesProcess, data, lat, z, b; ascent_steps=4, max_steps=1000, f_abstol=1e-6, guess=nothing,
+                    recursive=true, state=nothing, verbose=false, ctx=context(), ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    pri0, net, la, N, P, D, Z = latvb_setup(p, "vb!", lat, z, b, ascent_steps)
+    x = Vector{Float64}(guess === nothing ? vcat(NHP.params(p.baseline), NHP.params(p.impulses), NHP.params(p.weights)) : guess)
+    length(x) == P || error("Parameter vector length does not match model parameter length.")
+    NN = N * N
+    S, R, Q = state === nothing ? (Vector{Float64}(undef, P), Vector{Float64}(undef, P), vcat(ones(2 * NN), fill(0.5, NN))) :
+                                  (Vector{Float64}(state[1]), Vector{Float64}(state[2]), Vector{Float64}(state[3]))
+    (length(S) == P && length(R) == P && length(Q) == 3 * NN) || error("Parameter vector length does not match model parameter length.")
+    flags = llflags(p, recursive) | (state === nothing ? Int32(0) : VB_RESUME)
+    elbo, steps, conv = Ref{Float64}(0.0), Ref{Int32}(0), Ref{Int32}(0)
+    trace = fill(NaN, max_steps + 1)
+    pri = Ref(pri0)
+    t0 = time()
+    with_model(ctx, p) do m
+        GC.@preserve pri check(ccall((:nhp_cont_latvb_run, libnhp), Int32,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Priors}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Float64, Int32,
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ref{Int32}, Ref{Int32}, Ptr{Float64}),
+            ctx.h, ds.h, m, flags, Base.unsafe_convert(Ptr{Priors}, pri), net, la, Int32(D), Int32(ascent_steps), f_abstol,
+            Int32(max_steps), x, S, R, P, Q, Z, elbo, steps, conv, trace), ctx.h)
+    end
+    verbose && println(" > steps: $(steps[]), elbo: $(elbo[])")
+    nimp = P - N - NN
+    NHP.params!(p.baseline, x[1:N]); NHP.params!(p.impulses, x[N+1:N+nimp]); NHP.params!(p.weights, x[N+nimp+1:end])
+    tab(v, j) = reshape(v[(j-1)*NN+1:j*NN], N, N)
+    rho = tab(Q, 3)
+    w = p.weights
+    w.κv0, w.νv0, w.κv1, w.νv1 = tab(Q, 1), tab(Q, 2), reshape(S[P-NN+1:P], N, N), reshape(R[P-NN+1:P], N, N)
+    p.adjacency_matrix .= rho .> 0.5
+    first = state === nothing ? 2 : 1
+    (S=S, R=R, Q=Q, Z=Z, rho=rho, z=reshape(Z[1:N*D], N, D), b=Z[end], elbo=elbo[], trace=trace[first:steps[]+1], steps=Int(steps[]),
+     status=conv[] == 1 ? "success" : "failure", elapsed=time() - t0)
+end
+
+function latent_update!(p::NHP.ContinuousNetworkHawkesProcess, data, lat, z, b; ascent_steps=4, state=nothing, recursive=true,
+                        ctx=context(), ds=Dataset(ctx, data, NHP.ndims(p), p.impulses.Δtmax))
+    pri0, net, la, N, P, D, Z = latvb_setup(p, "update!", lat, z, b, ascent_steps)
+    NN = N * N
+    S, R, Q = state === nothing ? (Vector{Float64}(undef, P), Vector{Float64}(undef, P), vcat(ones(2 * NN), fill(0.5, NN))) :
+                                  (Vector{Float64}(state[1]), Vector{Float64}(state[2]), Vector{Float64}(state[3]))
+    (length(S) == P && length(R) == P && length(Q) == 3 * NN) || error("Parameter vector length does not match model parameter length.")
+    flags = llflags(p, recursive) | (state === nothing ? VB_FROM_MODEL : Int32(0))
+    stats = Vector{Float64}(undef, 19 + ascent_steps)
+    pri = Ref(pri0)
+    with_model(ctx, p) do m
+        GC.@preserve pri check(ccall((:nhp_cont_latvb_step, libnhp), Int32,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Priors}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64},
+             Int64, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}),
+            ctx.h, ds.h, m, flags, Base.unsafe_convert(Ptr{Priors}, pri), net, la, Int32(D), Int32(ascent_steps), S, R, P, Q, Z,
+            Int32(0), stats), ctx.h)
+    end
+    (S=S, R=R, Q=Q, Z=Z, stats=stats)
+end
+
+function latent_expected_loglik(rho::AbstractMatrix, z::AbstractMatrix, b, lat; ctx=context())
+    N, D = size(z)
+    size(rho) == (N, N) || error("rho must be N x N")
+    out = Vector{Float64}(undef, N * D + 2)
+    check(ccall((:nhp_latent_expected_loglik, libnhp), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}),
+                ctx.h, Matrix{Float64}(rho), Int32(N), Int32(D), Matrix{Float64}(z), Float64(b), Float64[lat...], out), ctx.h)
+    (F=out[1], grad=out[2:end])
+end
+
 # --- observed_information(process, data) and hessian_vector_product(process, data, v): no reference counterpart ---------------
 # The objective separates by child node, so minus its Hessian is block diagonal: blocks[:, :, k] is the D x D block of column
 # columns[k] (1-based here) over [λ0[c]; θ[:,c] | μ[:,c]; τ[:,c]; W[:,c]], D = 1 + kinds·N (nhp_cont_information; homogeneous

@@ -35,6 +35,38 @@ struct nhp_slices {               // kernel-side view of nhp_cont_dataset::d_sl_
 
 #define NHP_SL_SHARDS 64
 
+// C rows of records in registers, and how they are requested ("The row diet").  The rows' base is wave-uniform and
+// is formed on the scalar unit; a lane adds its own byte offset (lane·4 in the lo plane, lane·2 in the hi plane) and the C rows
+// are immediates: global_load_* v, v_laneoff, s[base:base+1] offset:u·256 -- no 64-bit vector address arithmetic.  The lane
+// offsets pass through an empty asm at every request, so that the compiler does not hoist their zero-extended 64-bit copies
+// out of the loops and fall back to vector addresses.  The hi plane's 16 bits are zero-extended by the load itself; the
+// annotation keeps the extension beside the load (moved behind the loops' phis it becomes a v_and_b32 0xffff at every use).
+// Both are ways round what the compiler does today and nothing in the suite sees them fail (the results are the same, the
+// instructions come back).  After a compiler update, from csrc/:
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics --cuda-device-only -S cont_slices.hip -o cont_slices.s
+// and in k_slices_batch<512,2,2,true> (_Z14k_slices_batchILi512ELi2ELi2ELb1E...) between the two "Inner Loop Header: Depth=2"
+// labels and their back edges there must be no v_lshl_add_u64 and no `v_and_b32 ..., 0xffff`, the record loads must read
+// `global_load_dword v, v, s[..:..] offset:256`, and no `s_waitcnt vmcnt(0)` may stand between a "Loop Header: Depth=1" label
+// and the inner loop ("The row diet", has the counts to compare with).
+typedef const __attribute__((address_space(1))) unsigned char *sl_gbytes;
+typedef const __attribute__((address_space(4))) uint32_t *sl_ctab;   // the slice table through the scalar cache: written once, by the dataset builders
+template <int C>
+struct sl_chunk { uint32_t lo[C], hi[C]; };
+template <int C>
+__device__ __forceinline__ void sl_request(sl_chunk<C> &q, const uint32_t *plo, const uint16_t *phi, const uint32_t row0, const int r,
+                                           uint32_t &lane4, uint32_t &lane2)
+{
+    const uint64_t o = (uint64_t)row0 + (uint64_t)(uint32_t)r;
+    sl_gbytes pl = (sl_gbytes)plo + o * 256, ph = (sl_gbytes)phi + o * 128;
+    asm("" : "+s"(pl), "+s"(ph));
+    asm volatile("" : "+v"(lane4), "+v"(lane2));
+#pragma unroll
+    for (int u = 0; u < C; ++u) {
+        q.lo[u] = *(const __attribute__((address_space(1))) uint32_t *)(pl + lane4 + u * 256);
+        q.hi[u] = __builtin_annotation((uint32_t)*(const __attribute__((address_space(1))) uint16_t *)(ph + lane2 + u * 128), "zext");
+    }
+}
+
 #ifdef NHP_STAMP      // diagnostic build only (tools/dbg/slstamps.py): s_memrealtime (100 MHz, one clock for all XCDs) at the phase boundaries of wave 0 of every workgroup
 __device__ unsigned long long g_sl_stamps[8 * 4096];
 __device__ unsigned long long g_sl_wave_end[16 * 4096];      // and of EVERY wave at the end of its slices (0: the workgroup has no such wave)
@@ -424,16 +456,24 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
 
     // Rows r .. r+C-1 of the slice that starts at row `row0`: a wave-uniform base and compile-time row offsets.  Rows past the
     // slice's last are simply the next slice's (or the 16 rows of padding behind the list): loaded, never summed.
-    struct chunk { uint32_t lo[C], hi[C]; };
+    typedef sl_chunk<C> chunk;
+    uint32_t lane4 = (uint32_t)lane * 4u, lane2 = (uint32_t)lane * 2u;
+    // (the gradient build keeps vector addresses and vector loads of the slice table: its phase B holds the scalar registers)
     auto request = [&](chunk &q, const uint32_t *plo, const uint16_t *phi, const uint32_t row0, const int r) {
-        const size_t o = ((size_t)row0 + (size_t)r) * 64;
-        const uint32_t *pl = plo + o;
-        const uint16_t *ph = phi + o;
+        if constexpr (GRAD) {
+            const size_t o = ((size_t)row0 + (size_t)r) * 64;
+            const uint32_t *pl = plo + o;
+            const uint16_t *ph = phi + o;
 #pragma unroll
-        for (int u = 0; u < C; ++u) {
-            q.lo[u] = pl[u * 64 + lane];
-            q.hi[u] = ph[u * 64 + lane];
-        }
+            for (int u = 0; u < C; ++u) {
+                q.lo[u] = pl[u * 64 + lane];
+                q.hi[u] = ph[u * 64 + lane];
+            }
+        } else sl_request<C>(q, plo, phi, row0, r, lane4, lane2);
+    };
+    auto rowc = [&](const int i) {
+        if constexpr (GRAD) return sl.row[i];
+        else return ((sl_ctab)sl.row)[i];
     };
     // Column c of the tables: every load of (up to) UN passes over the parent nodes is requested before any is used -- one
     // round trip instead of one per pass -- and the first rows of the wave's first slice are requested right behind them
@@ -459,7 +499,7 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
             cnt_[u] = it.first ? a.cnt[p < N ? p : 0] : 0.0;
         }
         if (p0 == 0) {
-            if (j < ns) { row0 = sl.row[s0 + j]; K = (int)(sl.row[s0 + j + 1] - row0); }
+            if (j < ns) { row0 = rowc(s0 + j); K = (int)(rowc(s0 + j + 1) - row0); }
             asm volatile("" ::: "memory");
             request(qa, sl.lo, sl.hi, row0, 0);
             asm volatile("" ::: "memory");
@@ -547,9 +587,10 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
     int rnd = 0;                                                    // the wave's slices in snake order (nhp_slice_of)
     while (j < ns) {
         const int jn = nhp_slice_of(++rnd, w, NW);
-        uint32_t row0n = 0;
-        int Kn = 0;
-        if (jn < ns) { row0n = sl.row[s0 + jn]; Kn = (int)(sl.row[s0 + jn + 1] - row0n); }
+        // (a scalar load, waited for where row0n is first used; past the wave's last slice it reads the item's last entry: a
+        //  valid row for the request below, which nothing sums, and K is not used again)
+        const int jc = s0 + (jn < ns ? jn : ns - 1);
+        const uint32_t row0n = rowc(jc), rowen = rowc(jc + 1);
         double s = 0.0;
         if (K <= 0) request(qa, sl.lo, sl.hi, row0n, 0);
         if constexpr (GRAD) { NHP_SL_ROWS((std::integral_constant<int, 0>{})) }
@@ -571,7 +612,7 @@ __global__ __launch_bounds__(BLOCK) void k_windowed_slices(nhp_cont_args a, nhp_
         }
         pexp += __builtin_amdgcn_frexp_exp(prod);
         prod = __builtin_amdgcn_frexp_mant(prod);
-        j = jn; row0 = row0n; K = Kn;
+        j = jn; row0 = row0n; K = (int)(rowen - row0n);
     }
     NHP_SL_STAMP_WAVE();
     NHP_SL_STAMP(2);
@@ -756,17 +797,10 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
     const int s0 = sl.item0[blockIdx.x], ns = sl.item0[blockIdx.x + 1] - s0;
     NHP_SL_STAMP(0);
 
-    struct chunk { uint32_t lo[C], hi[C]; };
-    auto request = [&](chunk &q, const uint32_t row0, const int r) {
-        const size_t o = ((size_t)row0 + (size_t)r) * 64;
-        const uint32_t *pl = sl.lo + o;
-        const uint16_t *ph = sl.hi + o;
-#pragma unroll
-        for (int u = 0; u < C; ++u) {
-            q.lo[u] = pl[u * 64 + lane];
-            q.hi[u] = ph[u * 64 + lane];
-        }
-    };
+    typedef sl_chunk<C> chunk;
+    uint32_t lane4 = (uint32_t)lane * 4u, lane2 = (uint32_t)lane * 2u;
+    auto request = [&](chunk &q, const uint32_t row0, const int r) { sl_request<C>(q, sl.lo, sl.hi, row0, r, lane4, lane2); };
+    const sl_ctab rowc = (sl_ctab)sl.row;
     // The head, after k_windowed_slices': the parent nodes in trips of UN·BLOCK, and inside a trip every load -- cnt once per
     // node, then W, θ and (behind a wave-uniform branch) A of G models -- is requested before any is used: one round trip per
     // trip instead of up to three per model and pass.  The first rows of the wave's first slice follow the first trip's requests
@@ -828,7 +862,7 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
                 }
             }
             if (p0 == 0 && g == 0) {                                 // (N >= 1 on every route that launches this kernel: the first trip always runs)
-                if (j < ns) { row0 = sl.row[s0 + j]; K = (int)(sl.row[s0 + j + 1] - row0); }
+                if (j < ns) { row0 = rowc[s0 + j]; K = (int)(rowc[s0 + j + 1] - row0); }
                 asm volatile("" ::: "memory");
                 request(qa, row0, 0);
                 asm volatile("" ::: "memory");
@@ -872,6 +906,9 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
     const uint32_t dmask = sl.dmask;
     const int nsh = sl.nsh;
     const nhp_exp_term_consts ekc = nhp_exp_term_setup();
+    // (the models' columns stay S planes: interleaved, col[p·S + m], model m sits at a constant offset and a row loses its
+    //  v_add_u32, but a ds_read_b128 of one model then finds its 64 nodes on every S-th 16-byte slot only; built, measured and
+    //  not taken: DESIGN 3.1d, "The row diet", profiles/r19a_pmc_pair_counters_interleaved.txt)
     const uint32_t plane = (uint32_t)(N + 1) * 16u;                 // bytes between the models' columns
     double prod[S];
     int pexp[S];
@@ -906,9 +943,11 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
         };
         while (j < ns) {
             const int jn = nhp_slice_of(++rnd, w, NW);
-            uint32_t row0n = 0;
-            int Kn = 0;
-            if (jn < ns) { row0n = sl.row[s0 + jn]; Kn = (int)(sl.row[s0 + jn + 1] - row0n); }
+            // The next slice's rows from the slice table by a scalar load, requested here and waited for where row0n is first
+            // used: no round trip at the top of a slice.  Past the wave's last slice the entry read is the item's last (a
+            // valid row for the request below, which nothing sums) and K is not used again.
+            const int jc = s0 + (jn < ns ? jn : ns - 1);
+            const uint32_t row0n = rowc[jc], rowen = rowc[jc + 1];
             double acc[S];
 #pragma unroll
             for (int m = 0; m < S; ++m) acc[m] = 0.0;
@@ -936,7 +975,7 @@ __global__ __launch_bounds__(BLOCK) void k_slices_batch(nhp_cont_args a, nhp_sli
                 pexp[m] += __builtin_amdgcn_frexp_exp(prod[m]);
                 prod[m] = __builtin_amdgcn_frexp_mant(prod[m]);
             }
-            j = jn; row0 = row0n; K = Kn;
+            j = jn; row0 = row0n; K = (int)(rowen - row0n);
         }
     };
     if (fast) walk(std::true_type{}); else walk(std::false_type{});
